@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: house-steps/s of the fused env step at 4096 envs x 1024 houses per MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one MADemandResponseEnv.step for every env of the batch (one fused HIP launch) on BASELINE.json
@@ -14,8 +14,15 @@ its own 4096 envs (independent replicas, env_offset = rank * 4096, no data-path 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one
 `torch.distributed.run` child, started before this process touches the GPU) and exits with the child's code.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects, plus two
-secondary legs measured after the timed region of the headline (BASELINE.json configs[3] and configs[4]):
+Prints ONE JSON line on rank 0 with a `roofline` object (from the timed steps' HIP events and committed profile constants: no run of
+its own).  A plain run does nothing else: set up, warm up, time the K steps, write the outputs if asked, print the line.
+
+`--dump-outputs DIR` writes what the timed rollout left after its last step (rank 0's replica) as DIR/<name>.npy, float32 / float64,
+about 50 MB: `reward` of every house, and on a fixed, seeded sample of houses (`sample_index`) the seven observation planes, the
+house state and the actions; `cluster_hvac_power` of every env.  The inputs are fixed by the arguments (seed 2024).
+
+`--full` adds, after the timed region of the headline, a `cpu_baseline` object (N = 1) and the secondary legs (BASELINE.json
+configs[3] and configs[4]):
   `ppo_rollout`  policy-in-the-loop rollout collection on the same per-rank batch (observation -> actor -> sample -> step);
   `c5`           1 env x 1,000,000 houses sharded over the N ranks with the per-step exchange (kernel / collective split);
   `c5_graph`     the same step captured in a hipGraph;
@@ -169,9 +176,13 @@ def parse(argv):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed rollout computed in its last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline and the secondary ppo_rollout / c5 legs after the headline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary ppo_rollout / c5 legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the secondary ppo_rollout / c5 legs")
     ap.add_argument("--ppo-steps", type=int, default=20)
     ap.add_argument("--c5-steps", type=int, default=200)
     ap.add_argument("--leg-timeout", type=float, default=float(os.environ.get("MDR_BENCH_LEG_TIMEOUT", "240")),
@@ -476,6 +487,42 @@ def persist_child(args):
     dist.destroy_process_group()
 
 
+DUMP_SAMPLE_HOUSES = 1 << 19      # houses of the fixed sample for the per-house arrays beyond `reward`
+
+
+def dump_outputs(env, out_dir):
+    """What a caller of the timed rollout receives after its last step (step()'s obs planes, reward and cluster power, and the house
+    state the next step starts from) as out_dir/<name>.npy.  `reward` [E, N] in full; the planes, state and actions on a fixed sample
+    of houses (seeded, sorted flat indices into [E, N], written as `sample_index`); about 50 MB at 4096 x 1024."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    E, N = env.nb_envs, env.nb_houses
+    idx = np.sort(np.random.default_rng(2024).choice(E * N, min(DUMP_SAMPLE_HOUSES, E * N), replace=False))
+    sel = torch.from_numpy(idx).to(env.device)
+
+    def sample(t):
+        return t.reshape(-1).index_select(0, sel)
+
+    t = env.t
+    flags = sample(t["flags"]).int()
+    arrays = {
+        "reward": t["reward"].float(),
+        "cluster_hvac_power": t["P"].double(),
+        "sample_index": torch.from_numpy(idx.astype(np.float64)),
+        "house_temp": sample(t["Ta"]).double() + env.spec.temp_ref,          # as env.house_temp() / house_mass_temp()
+        "house_mass_temp": sample(t["Tm"]).double() + env.spec.temp_ref,
+        "seconds_since_off": sample(t["sso"]).float(),
+        "hvac_on": (flags & 1).float(),
+        "hvac_lockout": ((flags >> 1) & 1).float(),
+        "actions": sample(t["actions"]).float(),
+    }
+    if t["obs"].numel():
+        arrays["obs_planes"] = t["obs"].reshape(t["obs"].shape[0], -1).index_select(1, sel).float()
+    for name, val in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), val.cpu().numpy())
+
+
 def dry_rank(rk: Ranks, args):
     """MDR_BENCH_DRY=1: rehearse launcher, rendezvous, fence and max-over-ranks without a GPU (tests/test_bench_launch.py).
     No kernel runs and the line says so; it is never a result."""
@@ -515,6 +562,8 @@ def run_rank(args):
     # sanity: the rollout really advanced and the state is finite (cheap, outside the timed region)
     assert env.steps_taken == args.warmup + args.steps
     assert bool(torch.isfinite(env.t["Ta"]).all()) and bool(torch.isfinite(env.t["reward"]).all())
+    if args.dump_outputs and rk.rank == 0:      # before any leg: the ppo_rollout leg steps this env further
+        dump_outputs(env, args.dump_outputs)
 
     def headline(legs):
         achieved = B_ALG * e_per_gpu * N_HOUSES / (kernel_ms * 1e-3) / 1e9
@@ -555,6 +604,12 @@ def run_rank(args):
         if reasons:
             line["degraded_reasons"] = reasons
         return line
+
+    if not args.full:           # a plain run: the headline alone
+        if rk.rank == 0:
+            emit(headline({}))
+        rk.close()
+        return
 
     # The secondary legs never cost the headline: the headline is measured by now, and if a leg has not returned after
     # --leg-timeout seconds (a collective that never completes on some node, say) rank 0 prints the line without it and every

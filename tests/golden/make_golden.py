@@ -416,6 +416,46 @@ def main():
     # N == 1 (config.py's literal default nb_agents) and no neighbours
     run_scenario("s9_single_house", {CL + "nb_agents": 1, PG + "signal_mode": "sinusoidals"}, 61, 200, "bangbang")
     main_controllers()
+    live_reference_cases()
+
+
+def live_reference_cases():
+    """Only the recorded cases of tests/test_oracle_vs_reference_live.py (python tests/golden/make_golden.py live): its seeded
+    random configurations through the reference, packed live.CASES_PER_FILE cases to a file (the layout live._recorded reads).
+    Not stored: the interpolation grids (the test draws them again from the case's seed) and the configs (rebuilt from the
+    config snapshot and the case's patches - checked here against what the reference ran with)."""
+    import glob
+    import tempfile
+    from tests import test_oracle_vs_reference_live as live
+
+    def same(a, b):
+        return json.dumps(a, sort_keys=True) == json.dumps(b, sort_keys=True)
+    cases = {}
+    for idx in range(live.NB_CASES):
+        a = cases["live%d" % idx] = live.reference_case(idx)
+        assert same(a["meta"]["config"], jsonable(live.case_config(live._patches(idx)[0]))), idx
+    for idx in range(live.NB_INTERP_CASES):
+        with tempfile.TemporaryDirectory() as tmp:
+            a = cases["interp%d" % idx] = live.reference_interp_case(idx, tmp)
+            a["meta"] = json.loads(json.dumps(a["meta"]).replace(tmp + os.sep, ""))      # grid file names, not scratch paths
+        assert same(a["meta"]["config"], jsonable(live.case_config(live.interp_patches(live._interp_case(idx)[2], "")))), idx
+    for path in glob.glob(live.RECORDED.replace("%d", "*")):
+        os.remove(path)
+    names = list(cases)
+    for f in range(0, len(names), live.CASES_PER_FILE):
+        part = {c: {k: v for k, v in cases[c].items() if k == "meta" or k in live.READ[c.rstrip("0123456789")]}
+                for c in names[f:f + live.CASES_PER_FILE]}
+        out = {"meta": np.frombuffer(json.dumps({c: {k: v for k, v in a["meta"].items() if k != "config"}
+                                                 for c, a in part.items()}).encode(), dtype=np.uint8)}
+        for name in sorted({k for a in part.values() for k in a if k != "meta"}):
+            have = [(c, np.asarray(a[name])) for c, a in part.items() if name in a]
+            nd = max(v.ndim for _, v in have)
+            out[name] = np.concatenate([v.ravel() for _, v in have])
+            out[name + "@shapes"] = np.array([list(v.shape) + [-1] * (nd - v.ndim) for _, v in have], dtype=np.int64).reshape(len(have), nd)
+            out[name + "@cases"] = np.array([c for c, _ in have])
+        path = live.RECORDED % (f // live.CASES_PER_FILE)
+        np.savez_compressed(path, **out)
+        print("%s: %d cases, %.1f KB" % (os.path.basename(path), len(part), os.path.getsize(path) / 1024))
 
 
 def main_controllers():
@@ -432,5 +472,7 @@ def main_controllers():
 if __name__ == "__main__":
     if sys.argv[1:] == ["s14"]:
         main_controllers()
+    elif sys.argv[1:] == ["live"]:
+        live_reference_cases()
     else:
         main()

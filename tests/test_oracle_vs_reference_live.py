@@ -1,10 +1,14 @@
-"""Live pin of the oracle: random configurations run through THE REFERENCE ITSELF (imported from /root/reference
-with the inert stand-ins of oracle/ref_harness.py) and replayed by the oracle, fp64 against fp64.
+"""Pin of the oracle on seeded random configurations run through THE REFERENCE ITSELF, fp64 against fp64.
 
-Runs only where the reference is mounted (the build container); skipped on the GPU box.  The committed fixtures in
-tests/golden/ are 29 hand-picked scenarios; this widens the pin to seeded random corners of the config space (time
-step, start date, signal family, penalty mode / weights, noise modes, lockout noise, deadband, solar gain, comm
-topology, optional observation columns) without storing more data."""
+The reference's outputs for the 120 + 40 cases below were recorded once (imported from where it lies, with the inert stand-ins of
+oracle/ref_harness.py) by tests/golden/make_golden.py into tests/golden/live_reference_cases_*.npz; the tests replay the oracle
+on them anywhere.  A recorded case keeps the reference's arrays; its config is rebuilt from the reference's config snapshot
+(tests/golden/reference_env_config.json) and the case's seeded patches.  The committed scenario fixtures in tests/golden/ are 29 hand-picked scenarios; this widens the pin to seeded
+random corners of the config space (time step, start date, signal family, penalty mode / weights, noise modes, lockout noise,
+deadband, solar gain, comm topology, optional observation columns).  MDR_FUZZ_SCALE=k (one-off campaigns) adds cases beyond the
+recorded ones; those run the reference live and skip where it is not installed."""
+import copy
+import glob
 import importlib.util
 import json
 import os
@@ -16,8 +20,14 @@ from oracle import mdr_oracle as mo
 from oracle import ref_harness
 from tests import golden_util as gu
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="the reference is not mounted here")
 SCALE = max(1, int(os.environ.get("MDR_FUZZ_SCALE", "1")))   # one-off campaigns: k times as many seeded cases
+NB_CASES, NB_INTERP_CASES = 120, 40
+RECORDED = os.path.join(gu.GOLDEN_DIR, "live_reference_cases_%d.npz")      # CASES_PER_FILE recorded cases per file
+CASES_PER_FILE = 10
+PARAMS = ("Ta", "Tm", "target", "deadband", "Ua", "Cm", "Ca", "Hm", "capacity", "COP", "latent", "lockout", "t0", "phase", "ratio")
+READ = {"live": ["p_" + k for k in PARAMS + ("max_power",)] + ["od", "actions", "links", "S", "norm_state", "on", "lock", "sso", "P",
+                                                                 "solar", "Ta", "Tm", "reward"],
+        "interp": ["p_" + k for k in PARAMS] + ["od", "actions", "base_power", "S", "Ta", "reward"]}     # what each test reads
 
 ENV = "default_env_prop."
 PG = ENV + "power_grid_prop."
@@ -28,6 +38,49 @@ def _make_golden():
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
     return m
+
+
+_RECORDED = {}
+
+
+def _recorded(prefix):
+    """The reference's arrays of one recorded case ('live<idx>' / 'interp<idx>'), or None.  A file holds, per array name, the
+    flat concatenation over its cases ('<name>'), their shapes ('<name>@shapes', padded with -1) and case names ('<name>@cases');
+    'meta' is the JSON of every case's meta without its config."""
+    if not _RECORDED:
+        for path in sorted(glob.glob(RECORDED.replace("%d", "*"))):
+            with np.load(path, allow_pickle=False) as z:
+                for case, meta in json.loads(z["meta"].tobytes().decode()).items():
+                    _RECORDED[case] = {"meta": meta}
+                for key in z.files:
+                    if not key.endswith("@shapes"):
+                        continue
+                    name, off, flat = key[:-len("@shapes")], 0, z[key[:-len("@shapes")]]
+                    for case, shape in zip(z[name + "@cases"], z[key]):
+                        shape = tuple(int(d) for d in shape if d >= 0)
+                        n = int(np.prod(shape, dtype=np.int64))
+                        _RECORDED[str(case)][name] = flat[off:off + n].reshape(shape)
+                        off += n
+                    assert off == flat.size, key
+    return _RECORDED.get(prefix)
+
+
+def case_config(patches):
+    """The env config a case ran with: the reference's config snapshot, constant base power (make_golden.run_scenario's default),
+    then the case's patches."""
+    cfg = copy.deepcopy(gu.reference_env_config())
+    for dotted, value in [(PG + "base_power_mode", "constant")] + list(patches.items()):
+        node = cfg
+        for part in dotted.split(".")[:-1]:
+            node = node[part]
+        node[dotted.split(".")[-1]] = copy.deepcopy(value)
+    return cfg
+
+
+def _live():
+    if not ref_harness.available():
+        pytest.skip("case beyond the recorded ones (MDR_FUZZ_SCALE) and the reference is not installed here")
+    return _make_golden()
 
 
 def _patches(idx):
@@ -74,20 +127,31 @@ def _patches(idx):
     return p, "perlin" in signal, policy, int(rng.integers(1, 10 ** 6))
 
 
-@pytest.mark.parametrize("idx", range(120 * SCALE))
-def test_oracle_tracks_the_live_reference(idx):
+def reference_case(idx):
+    """Case `idx` run through the reference (needs it installed): the arrays make_golden.run_scenario records."""
     mg = _make_golden()
     patches, perlin, policy, seed = _patches(idx)
-    known = mg.ref_harness.load_reference()["config_dict"]
+    a = mg.run_scenario("live_%d" % idx, patches, seed, 30, policy, perlin=perlin, norm_steps=(0, 7, -1), save=False)
+    a["meta"] = json.loads(str(a["meta"]))
+    return a
+
+
+@pytest.mark.parametrize("idx", range(NB_CASES * SCALE))
+def test_oracle_tracks_the_live_reference(idx):
+    patches, perlin, policy, seed = _patches(idx)
+    known = gu.reference_env_config()
     for dotted in list(patches):          # only keys the reference's config really has (modes differ between snapshots)
         node = known
         for part in dotted.split(".")[:-1]:
             node = node[part]
         assert dotted.split(".")[-1] in node, dotted
     T = 30
-    a = mg.run_scenario("live_%d" % idx, patches, seed, T, policy, perlin=perlin, norm_steps=(0, 7, -1), save=False)
-    meta = json.loads(str(a["meta"]))
-    cfg = gu._intkeys(meta["config"])
+    a = _recorded("live%d" % idx)
+    if a is None:
+        _live()
+        a = reference_case(idx)
+    meta = a["meta"]
+    cfg = gu._intkeys(meta.get("config") or case_config(patches))
     N = meta["N"]
     env = mo.OracleEnv(cfg, nb_envs=1)
     env.seed, env.episode = seed, 0
@@ -116,13 +180,8 @@ def test_oracle_tracks_the_live_reference(idx):
     assert N == env.N
 
 
-@pytest.mark.parametrize("idx", range(40 * SCALE))
-def test_oracle_tracks_the_live_reference_in_interpolation_mode(idx, tmp_path):
-    """base_power_mode='interpolation' (the reference's default): a random grid written in the reference's own file formats is
-    read by ITS PowerInterpolator; the oracle's restatement of interpolatePower / interpolateGridFast must give the same base
-    power and signal at every update (N <= interp_nb_agents: above it the reference samples houses with `random`)."""
-    import csv
-    mg = _make_golden()
+def _interp_case(idx):
+    """Grid, axes, patches (without the grid file paths) and seed of interpolation case `idx`."""
     rng = np.random.default_rng(47000 + idx)
 
     def axis(lo, hi, n, must=None):
@@ -138,15 +197,9 @@ def test_oracle_tracks_the_live_reference_in_interpolation_mode(idx, tmp_path):
             "hour": axis(0, 86399, int(rng.integers(2, 5))), "date": axis(0, 364, int(rng.integers(2, 4)))}
     dims = [len(v) for v in axes.values()]
     values = np.round(rng.uniform(0, 6000, int(np.prod(dims))))
-    np.save(tmp_path / "grid.npy", values)
-    (tmp_path / "params.json").write_text(json.dumps(axes))
-    with open(tmp_path / "keys.csv", "w") as f:
-        csv.writer(f).writerow(list(axes.keys()))
-    ip = PG + "base_power_parameters.interpolation."
     N = int(rng.choice([1, 5, 12, 30]))
     patches = {
-        PG + "base_power_mode": "interpolation", ip + "path_datafile": str(tmp_path / "grid.npy"),
-        ip + "path_parameter_dict": str(tmp_path / "params.json"), ip + "path_dict_keys": str(tmp_path / "keys.csv"),
+        PG + "base_power_mode": "interpolation",
         ENV + "cluster_prop.nb_agents": N,
         ENV + "time_step": int(rng.choice([4, 7, 30, 60, 150, 300, 400])),
         ENV + "start_datetime_mode": str(rng.choice(["random", "fixed"])),
@@ -157,12 +210,47 @@ def test_oracle_tracks_the_live_reference_in_interpolation_mode(idx, tmp_path):
         "noise_house_prop.noise_mode": str(rng.choice(["no_noise", "small_noise", "big_noise"])),
         "noise_hvac_prop.noise_mode": str(rng.choice(["no_noise", "small_noise", "big_noise"])),
     }
-    seed = int(rng.integers(1, 10 ** 6))
-    T = 90
-    a = mg.run_scenario("live_interp_%d" % idx, patches, seed, T, "mixed", perlin="perlin" in patches[PG + "signal_mode"],
+    return values, axes, patches, int(rng.integers(1, 10 ** 6))
+
+
+def reference_interp_case(idx, directory):
+    """Interpolation case `idx` run through the reference (needs it installed), its grid written in the reference's own file
+    formats under `directory` and read by ITS PowerInterpolator."""
+    import csv
+    mg = _make_golden()
+    values, axes, patches, seed = _interp_case(idx)
+    np.save(os.path.join(directory, "grid.npy"), values)
+    with open(os.path.join(directory, "params.json"), "w") as f:
+        f.write(json.dumps(axes))
+    with open(os.path.join(directory, "keys.csv"), "w") as f:
+        csv.writer(f).writerow(list(axes.keys()))
+    patches = interp_patches(patches, directory)
+    a = mg.run_scenario("live_interp_%d" % idx, patches, seed, 90, "mixed", perlin="perlin" in patches[PG + "signal_mode"],
                         norm_steps=(0,), extra={"live": np.array(1)}, save=False)
-    meta = json.loads(str(a["meta"]))
-    cfg = gu._intkeys(meta["config"])
+    a["meta"] = json.loads(str(a["meta"]))
+    return a
+
+
+def interp_patches(patches, directory):
+    """The case's patches with the grid files of `directory` (file names alone for "": how a recorded case's config names them)."""
+    ip = PG + "base_power_parameters.interpolation."
+    return dict(patches, **{ip + "path_datafile": os.path.join(directory, "grid.npy"), ip + "path_parameter_dict": os.path.join(directory, "params.json"),
+                            ip + "path_dict_keys": os.path.join(directory, "keys.csv")})
+
+
+@pytest.mark.parametrize("idx", range(NB_INTERP_CASES * SCALE))
+def test_oracle_tracks_the_live_reference_in_interpolation_mode(idx, tmp_path):
+    """base_power_mode='interpolation' (the reference's default): a random grid written in the reference's own file formats is
+    read by ITS PowerInterpolator; the oracle's restatement of interpolatePower / interpolateGridFast must give the same base
+    power and signal at every update (N <= interp_nb_agents: above it the reference samples houses with `random`)."""
+    values, axes, patches, seed = _interp_case(idx)
+    T = 90
+    a = _recorded("interp%d" % idx)
+    if a is None:
+        _live()
+        a = reference_interp_case(idx, str(tmp_path))
+    meta = a["meta"]
+    cfg = gu._intkeys(meta.get("config") or case_config(interp_patches(patches, "")))
     env = mo.OracleEnv(cfg, nb_envs=1)
     env.seed, env.episode = seed, 0
     env.interp_grid = mo.InterpGrid(values, axes)
