@@ -125,3 +125,92 @@ def test_the_fence_falls_back_to_gloo_when_rccl_does_not_come_up():
                 "--full", "--no-cpu-baseline", "--ppo-steps", "2", "--c5-steps", "10")
     assert line["value"] > 1e9 and "fence over gloo" in line["backend_note"]
     assert line["c5"]["backend"] == "gloo" and line["c5_graph"]["captured"] is False
+
+
+# ---- the benchmark's own batch against the oracle -------------------------------------------------------------------------------
+BENCH_SLICES = (0, 2047, 4094)      # envs [0, 2), [2047, 2049), [4094, 4096) of bench.py's 4096 x 1024 batch
+_REPLICA = {}
+
+
+def _bench_replica():
+    """bench.run_rank's env, built the same way (c3_config, 4096 x 1024, seed 2024, env_offset 0, table_steps 64, the default
+    --stagger, episode 0), stepped through bench.py's default warm-up + timed steps with in-kernel bang-bang one step at a time.
+    Every step: the device's decisions on three slices against the oracle's rule (threshold rule of tests/slice_oracle.py), the
+    oracle replaying them, the step checked with the contract.  Leaves the env and its oracles in _REPLICA."""
+    import bench
+    import mdr_amd
+    from tests.slice_oracle import SliceOracle
+    if _REPLICA:
+        return _REPLICA
+    args = bench.parse([])
+    cfg = bench.c3_config(mdr_amd)
+    E, N = bench.E_PER_GPU, bench.N_HOUSES
+    env = mdr_amd.BatchedDemandResponseEnv(cfg, nb_envs=E, device="cuda:0", seed=2024, env_offset=0, table_steps=64,
+                                           stagger_bytes=args.stagger)
+    env.reset(episode=0)
+    sl = SliceOracle(cfg, env, 2024, 0, k=2, offsets=BENCH_SLICES)
+    steps = args.warmup + args.steps
+    near_edge = 0
+    for t in range(steps):
+        want = sl.decisions("bangbang")
+        env.step_bangbang()
+        acts = sl.take(env.t["actions"])
+        diff, off_edge = sl.decision_misses(acts, "bangbang", want)
+        assert off_edge == 0, "step %d: %d bang-bang decisions differ away from the threshold" % (t, off_edge)
+        near_edge += diff
+        sl.step(acts)
+        sl.check(env, "bench batch step %d" % t)
+    assert env.steps_taken == steps
+    _REPLICA.update(env=env, oracle=sl, steps=steps, near_edge=near_edge, args=args)
+    return _REPLICA
+
+
+@pytest.mark.gpu
+def test_bench_batch_matches_the_oracle_on_three_slices():
+    """1050 steps (16 table refills) of the benchmark's batch: every step of envs [0, 2), [2047, 2049) and [4094, 4096) against
+    the oracle, the in-kernel bang-bang decisions included."""
+    rep = _bench_replica()
+    assert rep["steps"] == 1050 and rep["steps"] // 64 >= 16
+    # decisions of houses within 1e-5 relative of the target may go either way (the device decides on its fp32 temperature); the
+    # oracle replays the device's, so the run stays comparable.  Reported, and bounded by 1 in 100,000 of the decisions checked
+    print("bench batch: %d of %d bang-bang decisions differ from the fp64 rule, all at the threshold" % (rep["near_edge"], 6 * 1024 * rep["steps"]))
+    assert rep["near_edge"] <= 1e-5 * 6 * 1024 * rep["steps"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_equals_the_replica_and_the_oracle(tmp_path):
+    """bench.py at its defaults (no MDR_BENCH_ENVS) with --dump-outputs: what the timed rollout (mdr_env_rollout, bang-bang) leaves
+    equals the replica stepped one step_bangbang() at a time bit for bit, and its sampled houses inside the oracle slices agree
+    with the oracle."""
+    import bench
+    from tests.slice_oracle import OBS_ATOL, OBS_RTOL, R_ATOL, R_RTOL, T_RTOL
+    assert "MDR_BENCH_ENVS" not in os.environ, "the benchmark's own batch: MDR_BENCH_ENVS must not be set"
+    rep = _bench_replica()
+    env, sl = rep["env"], rep["oracle"]
+    line = _run({}, "--dump-outputs", str(tmp_path / "bench"))
+    assert line["steps"] == rep["args"].steps and line["warmup"] == rep["args"].warmup
+    assert line["config"]["envs_per_gpu"] == bench.E_PER_GPU and line["config"]["seed"] == 2024
+    bench.dump_outputs(env, str(tmp_path / "replica"))
+    dump = {p.stem: np.load(p) for p in (tmp_path / "bench").iterdir()}
+    mine = {p.stem: np.load(p) for p in (tmp_path / "replica").iterdir()}
+    assert sorted(dump) == sorted(mine)
+    for name in sorted(dump):
+        assert dump[name].dtype == mine[name].dtype and dump[name].shape == mine[name].shape, name
+        assert np.array_equal(dump[name], mine[name]), "%s: bench.py's rollout and the step-by-step replica differ" % name
+    N = bench.N_HOUSES
+    idx = dump["sample_index"].astype(np.int64)
+    e, h = idx // N, idx % N
+    inside = 0
+    for j, (off, o) in enumerate(zip(sl.offsets, sl.oras)):
+        sel = np.nonzero((e >= off) & (e < off + sl.k))[0]
+        inside += sel.size
+        le, lh = e[sel] - off, h[sel]
+        np.testing.assert_allclose(dump["house_temp"][sel], o.Ta[le, lh], rtol=T_RTOL, atol=0)
+        np.testing.assert_allclose(dump["house_mass_temp"][sel], o.Tm[le, lh], rtol=T_RTOL, atol=0)
+        np.testing.assert_array_equal(dump["seconds_since_off"][sel], o.sso[le, lh])
+        np.testing.assert_array_equal(dump["hvac_on"][sel], o.on[le, lh])
+        np.testing.assert_array_equal(dump["hvac_lockout"][sel], o.lock[le, lh])
+        np.testing.assert_allclose(dump["obs_planes"][:, sel], o.dynamic_obs()[:, le, lh], rtol=OBS_RTOL, atol=OBS_ATOL)
+        np.testing.assert_allclose(dump["reward"][off:off + sl.k], sl.rewards[j], rtol=R_RTOL, atol=R_ATOL)
+        np.testing.assert_array_equal(dump["cluster_hvac_power"][off:off + sl.k], o.P)
+    assert inside > 200, inside          # 2^19 of the 2^22 houses are sampled: ~770 fall in the six envs
