@@ -404,6 +404,34 @@ int mdr_mailbox_close(uint64_t *box);
 /* Word 0 of a mailbox (the error word) copied to the host: a SYNCHRONOUS 8-byte copy - call it when the stream has drained. */
 int mdr_mailbox_peek(const uint64_t *box, uint64_t *word0);
 
+/* ONE launch per externally driven step of a house shard: the per-step exchange of the records path (mdr_env_step_begin_records,
+ * an all-gather of the records, mdr_env_step_end_records) through the mailbox of the persistent rollout.  Every house workgroup
+ * (1024 houses; 256 when nb_houses % 4 != 0) steps its houses with the caller's action plane (MDR_ACTIONS_EXTERNAL) or an
+ * in-kernel controller, keeps the new state in registers and pushes its record into every rank's mailbox; one reducer
+ * workgroup per env re-sums the world * records records in the order of mdr_env_step_end_records and publishes the totals;
+ * the house workgroups then write state, rewards, observation planes, P and (controllers) the actions - all bit for bit what
+ * the records path leaves.  Tags count steps over the handle's life and share one space with mdr_env_rollout_persistent: the
+ * two may be mixed on one env and one mailbox.  All ranks call in lockstep, as they would a collective; not capturable.
+ *
+ * Guards: the mailbox checks of mdr_env_rollout_persistent; MDR_ERR_UNSUPPORTED (nothing launched) when (records + 1) x nb_envs
+ * workgroups x co_resident exceed what the device holds at once; MDR_ERR_INVALID while mdr_env_interp_due().  Every wait is
+ * bounded by `timeout_us` microseconds of the device's constant-rate clock (0 = 2 s); on expiry the waiter writes
+ * {tag, kind << 28 | workgroup} into word 0 of every rank's mailbox (kind 3: a house workgroup waiting for the totals, 4: the
+ * reducer waiting for records, 5: a halo pull) and NOTHING is written to the env's buffers.  A launch that finds word 0 set
+ * returns without writing; the caller reads word 0 (mdr_mailbox_peek) when the stream has drained - non-zero: rebuild the env.
+ *
+ * The halo of the sharded observation (the neighbour-message records that cross shard edges) through the same mailboxes: a
+ * region of mdr_mailbox_halo_bytes(world, count) bytes allocated BEHIND the mdr_mailbox_bytes(nb_envs, ...) of every rank.
+ * _push writes this rank's `count` floats (its padded export records) as tagged granules into every rank's halo; _pull waits,
+ * bounded as above, until the `count` floats of every rank carry `tag` and unpacks them into out[world][count].  `tag` >= 1
+ * counts the exchanges; all ranks call both in lockstep with the same count. */
+int mdr_env_step_mailbox(mdr_env_t *env, uint8_t *actions, int action_source, const mdr_mailbox_t *mailbox, uint32_t timeout_us,
+                         void *stream);
+int64_t mdr_mailbox_halo_bytes(int32_t world, int64_t count);
+int mdr_mailbox_halo_push(const mdr_mailbox_t *mailbox, int32_t nb_envs, const float *records, int64_t count, uint32_t tag, void *stream);
+int mdr_mailbox_halo_pull(const mdr_mailbox_t *mailbox, int32_t nb_envs, float *out, int64_t count, uint32_t tag, uint32_t timeout_us,
+                          void *stream);
+
 /* Sharded houses with base_power_mode "interpolation": PowerGrid.interpolatePower (env 1195-1234) averages up to
  * interp_nb_agents houses drawn from the WHOLE env (env 1209-1215), so the update at episode start and every
  * ceil(interp_update_period / time_step) steps (env 1250-1255) needs one more exchange.  After mdr_env_begin_episode /

@@ -142,6 +142,7 @@ EXPORTS = (
     "mdr_env_graph_room", "mdr_env_graph_replayed", "mdr_env_pack", "mdr_env_cursor", "mdr_env_set_cursor", "mdr_env_active_tables",
     "mdr_env_set_controller", "mdr_env_greedy_myopic_actions", "mdr_mailbox_bytes", "mdr_persist_records", "mdr_env_rollout_persistent",
     "mdr_mailbox_alloc", "mdr_mailbox_free", "mdr_mailbox_export", "mdr_mailbox_open", "mdr_mailbox_close", "mdr_mailbox_peek",
+    "mdr_env_step_mailbox", "mdr_mailbox_halo_bytes", "mdr_mailbox_halo_push", "mdr_mailbox_halo_pull",
     # include/mdr_policy.h
     "mdr_actor_steps1", "mdr_actor_steps1_order", "mdr_actor_steps2", "mdr_actor_frag1_floats", "mdr_actor_frag2_floats", "mdr_actor_sample", "mdr_env_actor_sample", "mdr_env_actor_sample_links",
     "mdr_discounted_returns",
@@ -232,6 +233,10 @@ def load():
         "mdr_mailbox_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "mdr_mailbox_close": (C.c_int, [vp]),
         "mdr_mailbox_peek": (C.c_int, [vp, C.POINTER(u64)]),
+        "mdr_env_step_mailbox": (C.c_int, [vp, vp, C.c_int, C.POINTER(MdrMailbox), u32, vp]),
+        "mdr_mailbox_halo_bytes": (i64, [i32, i64]),
+        "mdr_mailbox_halo_push": (C.c_int, [C.POINTER(MdrMailbox), i32, vp, i64, u32, vp]),
+        "mdr_mailbox_halo_pull": (C.c_int, [C.POINTER(MdrMailbox), i32, vp, i64, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

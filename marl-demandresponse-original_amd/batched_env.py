@@ -45,7 +45,7 @@ class BatchedDemandResponseEnv:
                  house_shard: Optional[Tuple[int, int]] = None, process_group=None,
                  stagger_bytes: int = 2304, interp_grid=None, regenerate_missing_grid: bool = True,
                  graph_mode: bool = False, exchange_always: bool = False, partial_records: Optional[int] = None,
-                 obs_planes: bool = True, prefetch_tables: bool = True):
+                 obs_planes: bool = True, prefetch_tables: bool = True, exchange=None):
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedDemandResponseEnv needs a ROCm device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
@@ -97,6 +97,10 @@ class BatchedDemandResponseEnv:
         if self.spec.base_power_mode == 1:
             self._install_interp_grid(interp_grid)
         self.done = torch.zeros((self.nb_envs, self.nb_houses), dtype=torch.bool, device=self.device)
+        # exchange: the object that carries the sharded-houses exchanges (None: sharding.TorchDistExchange over process_group;
+        # sharding.MailboxExchange: one launch per step through peer mailboxes)
+        if exchange is not None:
+            self._exchange_impl = exchange
 
     # ------------------------------------------------------------------ setup
     def _make_config(self) -> nat.MdrConfig:
@@ -312,6 +316,7 @@ class BatchedDemandResponseEnv:
 
     def reset(self, seed: Optional[int] = None, episode: Optional[int] = None) -> torch.Tensor:
         """MADemandResponseEnv.reset (env 135-172): re-samples every house and the start date, on the device."""
+        self._exchange_check()
         self._reset_local(seed, episode)
         self._begin_episode()
         return self._reset_obs()
@@ -395,6 +400,11 @@ class BatchedDemandResponseEnv:
                 rc = self._lib.mdr_env_step(self._handle, C.c_void_p(ptr), source, self._stream())
                 nat.check(self._lib, self._handle, rc, "mdr_env_step")
             return
+        ex = self._exchange()
+        if getattr(ex, "step_mailbox", None) is not None:
+            ex.step_mailbox(self, ptr, source)      # ONE launch, the exchange through the mailboxes (no collective, no host sync)
+            self._interp_exchange()
+            return
         self._step_begin(ptr, source)
         # TWO launches around ONE collective: step_begin leaves one (power sum, penalty sum, penalty max) record per 1024-house
         # workgroup, the ranks all-gather their record blocks, and every workgroup of step_end re-sums its env's records in one
@@ -434,6 +444,11 @@ class BatchedDemandResponseEnv:
         if n <= 0:
             return
         ex = self._exchange()
+        if getattr(ex, "step_mailbox", None) is not None:
+            for _ in range(n):
+                ex.step_mailbox(self, ptr, source)
+                self._interp_exchange()
+            return
         self._step_begin(ptr, source)
         for _ in range(n - 1):
             records, world = ex.gather_partials(self)
@@ -535,6 +550,7 @@ class BatchedDemandResponseEnv:
             if self.graph_mode and self.spec.base_power_mode != 1 and getattr(self._exchange(), "capturable", False):
                 return self._rollout_sharded_graph(int(nb_steps), self._actions_ptr(actions), source)
             self._steps_sharded(int(nb_steps), self._actions_ptr(actions), source)
+            self._exchange_check()
             return
         src = nat.ACTIONS_EXTERNAL if actions is not None else ctl
         with torch.cuda.device(self.device):
@@ -599,6 +615,30 @@ class BatchedDemandResponseEnv:
             torch.cuda.synchronize(self.device)
             nat.check(self._lib, None, self._lib.mdr_mailbox_peek(C.c_void_p(addr), C.byref(word)), "mdr_mailbox_peek")
         return int(word.value)
+
+    def _uses_mailbox(self) -> bool:
+        return self.sharded and getattr(self._exchange(), "step_mailbox", None) is not None
+
+    def exchange_status(self) -> int:
+        """Word 0 of this rank's mailbox once the stream has drained (sharding.MailboxExchange): 0 while every mailbox launch ran
+        to its end; otherwise raises with the step tag, the kind of wait that gave up and the workgroup.  0 for other exchanges."""
+        if not self._uses_mailbox():
+            return 0
+        word = self._exchange().status(self)
+        if word:
+            kind = (word >> 28) & 0xF
+            what = self.MAILBOX_ERRORS.get(kind, self.PERSIST_ERRORS.get(kind, "kind %d" % kind))
+            raise RuntimeError("mailbox exchange gave up at step tag %d (kind %d, workgroup %d): %s; the env's buffers and its step "
+                               "count no longer agree with its peers - rebuild the env" % ((word >> 32) & 0xFFFFFFFF, kind, word & 0x0FFFFFFF, what))
+        return 0
+
+    def _exchange_check(self) -> None:
+        if self._uses_mailbox():
+            self.exchange_status()
+
+    MAILBOX_ERRORS = {3: "a house workgroup of a mailbox step waited too long for the totals",
+                      4: "the reducer of a mailbox step waited too long for a step's records",
+                      5: "a halo pull waited too long for a peer's message records"}
 
     def _persist_raise(self, word: int):
         kind = (word >> 28) & 0xF
@@ -784,10 +824,8 @@ class BatchedDemandResponseEnv:
         ``planes`` -> float32 [F, E, N] (feature-major), ``rows`` -> float32 [E, N, F] (what Actor(num_state) eats).
         Feature order is normStateDict's; F = 11 (+ optional state columns) + nb_comm * 4 (+ optional message columns)."""
         if self.sharded:      # the messages cross shard edges: message records, ONE gather of the exported ones, ext kernel
-            if out is not None:
-                raise ValueError("obs_vector over sharded houses allocates its own output")
             padded = self._obs_messages()
-            return self._obs_from_gathered(layout, self._exchange().gather_messages(self, padded))
+            return self._obs_from_gathered(layout, self._exchange().gather_messages(self, padded), out)
         spec = self._obs_spec(layout)
         return self._obs_launch(layout, spec, out, None)
 
@@ -870,7 +908,7 @@ class BatchedDemandResponseEnv:
             padded[:, :len(plan.export_idx)] = msg[:, plan.export_dev + plan.local_base]
         return padded
 
-    def _obs_from_gathered(self, layout, gathered) -> torch.Tensor:
+    def _obs_from_gathered(self, layout, gathered, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         plan = self._halo_plan()
         if plan.all_records:
             for (off, cnt), block in zip(plan.ranges, gathered):      # every shard's records to their global slots
@@ -878,7 +916,7 @@ class BatchedDemandResponseEnv:
                     self._msg[:, off:off + cnt] = block[:, :cnt]
         elif plan.halo:
             self._msg[:, plan.n_local:] = plan.pick(gathered)
-        return self._obs_launch(layout, self._obs_spec_sharded(layout, plan), None, self._msg)
+        return self._obs_launch(layout, self._obs_spec_sharded(layout, plan), out, self._msg)
 
     # ------------------------------------------------------------------ views of the state
     def cursor(self) -> Tuple[int, int]:

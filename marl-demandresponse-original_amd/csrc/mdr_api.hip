@@ -967,6 +967,108 @@ int mdr_mailbox_peek(const uint64_t* box, uint64_t* word0) {
 
 int mdr_mailbox_close(uint64_t* box) { return (!box || hipIpcCloseMemHandle(box) == hipSuccess) ? MDR_OK : MDR_ERR_HIP; }
 
+// The mailbox checks of mdr_env_rollout_persistent, for the one-step exchange and the halo (which has no env: `env` may be NULL).
+static int check_mailbox(mdr_env* env, const mdr_mailbox_t* mb) {
+  if (!mb) return fail(env, MDR_ERR_INVALID, "mailbox is NULL");
+  if (mb->struct_size != sizeof(mdr_mailbox_t)) return fail(env, MDR_ERR_INVALID, "mdr_mailbox_t size mismatch (ABI)");
+  if (mb->world < 1 || mb->world > MDR_MAX_SHARDS || mb->rank < 0 || mb->rank >= mb->world)
+    return fail(env, MDR_ERR_INVALID, "mailbox: need 0 <= rank < world <= MDR_MAX_SHARDS");
+  if (mb->co_resident < 1) return fail(env, MDR_ERR_INVALID, "mailbox: co_resident must be >= 1");
+  if (mb->records_per_env < 1) return fail(env, MDR_ERR_INVALID, "mailbox: records_per_env must be >= 1");
+  for (int r = 0; r < mb->world; ++r) {
+    if (mb->records[r] < 1 || mb->records[r] > mb->records_per_env) return fail(env, MDR_ERR_INVALID, "mailbox: records[r] must be in [1, records_per_env]");
+    if (!mb->boxes[r] || ((uintptr_t)mb->boxes[r] & 7u) != 0) return fail(env, MDR_ERR_INVALID, "mailbox: boxes[r] is NULL or not 8-byte aligned");
+  }
+  return MDR_OK;
+}
+
+static mdr::PersistArgs mailbox_args(const mdr_mailbox_t* mb, uint32_t tag) {
+  mdr::PersistArgs m{};
+  for (int q = 0; q < mb->world; ++q) {
+    m.box[q] = mb->boxes[q];
+    m.nrec[q] = mb->records[q];
+  }
+  m.world = mb->world;
+  m.rank = mb->rank;
+  m.stride = mb->records_per_env;
+  m.tag_base = tag;
+  return m;
+}
+
+int mdr_env_step_mailbox(mdr_env_t* env, uint8_t* actions, int action_source, const mdr_mailbox_t* mb, uint32_t timeout_us, void* stream) {
+  if (!env) return MDR_ERR_INVALID;
+  int rc = check_mailbox(env, mb);
+  if (rc != MDR_OK) return rc;
+  if (!env->bound || !env->has_tables) return fail(env, MDR_ERR_UNBOUND, "no episode: call reset/load_episode and begin_episode first");
+  if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin without step_end");
+  if (env->interp_due)
+    return fail(env, MDR_ERR_INVALID, "base power update pending: mdr_env_interp_local, SUM all-reduce of base_power, mdr_env_interp_apply");
+  const mdr_config_t& c = env->cfg;
+  if (c.nb_envs > 65535) return fail(env, MDR_ERR_UNSUPPORTED, "the mailbox step puts the env index on grid.y: nb_envs must be <= 65535");
+  if (mb->world == 1 && sharded(env)) return fail(env, MDR_ERR_INVALID, "mailbox: a shard of the env needs its peers (world > 1)");
+  const int64_t mine = mdr::split_blocks(c.nb_houses, 256);   // one record per 256-thread workgroup: 1024 houses, 256 when nb_houses % 4 != 0
+  if (mb->records[mb->rank] != mine) return fail(env, MDR_ERR_INVALID, "mailbox: records[rank] is not this handle's workgroup count");
+  hipStream_t s = (hipStream_t)stream;
+  if (capturing(s)) return fail(env, MDR_ERR_INVALID, "the mailbox step takes its tag from the host: it cannot be captured");
+  const bool sys = mb->system_scope != 0;
+  int64_t resident = 0;
+  hipError_t e = mdr::mailbox_resident_blocks(c.nb_houses % 4 == 0 ? 4 : 1, sys, &resident);
+  if (e != hipSuccess) return hip_fail(env, e, "occupancy query");
+  const int64_t grid = (mine + 1) * c.nb_envs;   // + one reducer workgroup per env
+  if (grid * mb->co_resident > resident) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "mailbox step: %lld workgroups x %d co-resident launches exceed the %lld the device holds at once",
+             (long long)grid, (int)mb->co_resident, (long long)resident);
+    return fail(env, MDR_ERR_UNSUPPORTED, msg);
+  }
+  mdr::StepArgs a;
+  rc = step_args(env, actions, action_source, s, &a);   // refills the tables if the cursor left them
+  if (rc != MDR_OK) return rc;
+  const mdr::PersistArgs m = mailbox_args(mb, env->mailbox_tag);
+  e = mdr::launch_step_mailbox(a, m, sys, mdr::mailbox_timeout_ticks(timeout_us), s);
+  if (e != hipSuccess) return hip_fail(env, e, "step_mailbox");
+  env->mailbox_tag += 1u;
+  env->k += 1;
+  env->dev_row = env->dev_k = -1;   // graph mode: the device cursor did not move
+  if (interp_mode(env) && env->k % env->interp_steps == 0) {
+    if (!sharded(env)) return interp_boundary(env, s, nullptr);
+    env->interp_due = true;   // the caller runs the exchange: interp_local - all-reduce - interp_apply
+  }
+  return MDR_OK;
+}
+
+int64_t mdr_mailbox_halo_bytes(int32_t world, int64_t count) {
+  if (world < 1 || world > MDR_MAX_SHARDS || count < 0) return 0;
+  return mdr::mailbox_halo_granules(world, count) * 8;
+}
+
+static int64_t halo_base(const mdr_mailbox_t* mb, int32_t nb_envs) {   // granule offset of the halo region: behind the totals
+  return mdr::persist_mailbox_granules(nb_envs, mb->world, mb->records_per_env);
+}
+
+int mdr_mailbox_halo_push(const mdr_mailbox_t* mb, int32_t nb_envs, const float* records, int64_t count, uint32_t tag, void* stream) {
+  int rc = check_mailbox(nullptr, mb);
+  if (rc != MDR_OK) return rc;
+  if (nb_envs < 1 || count < 0 || (count > 0 && !records) || tag == 0) return MDR_ERR_INVALID;
+  if (count == 0) return MDR_OK;
+  if (capturing((hipStream_t)stream)) return MDR_ERR_INVALID;
+  const hipError_t e = mdr::launch_halo_push(mailbox_args(mb, tag), halo_base(mb, nb_envs), records, count, tag, mb->system_scope != 0,
+                                             (hipStream_t)stream);
+  return e == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+int mdr_mailbox_halo_pull(const mdr_mailbox_t* mb, int32_t nb_envs, float* out, int64_t count, uint32_t tag, uint32_t timeout_us,
+                          void* stream) {
+  int rc = check_mailbox(nullptr, mb);
+  if (rc != MDR_OK) return rc;
+  if (nb_envs < 1 || count < 0 || (count > 0 && !out) || tag == 0) return MDR_ERR_INVALID;
+  if (count == 0) return MDR_OK;
+  if (capturing((hipStream_t)stream)) return MDR_ERR_INVALID;
+  const hipError_t e = mdr::launch_halo_pull(mailbox_args(mb, tag), halo_base(mb, nb_envs), out, count, tag, mb->system_scope != 0,
+                                             mdr::mailbox_timeout_ticks(timeout_us), (hipStream_t)stream);
+  return e == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
 int mdr_env_step_begin(mdr_env_t* env, uint8_t* actions, int action_source, void* stream) {
   if (!env) return MDR_ERR_INVALID;
   if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin called twice");

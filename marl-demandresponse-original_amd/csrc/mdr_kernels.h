@@ -218,6 +218,15 @@ int64_t persist_mailbox_granules(int E, int world, int stride);
 hipError_t persist_resident_blocks(int vec, bool system_scope, int depth, int64_t* blocks);   // workgroups of the kernel the device holds at once
 hipError_t launch_rollout_persist(const StepArgs& a, const RolloutArgs& r, const PersistArgs& m, bool system_scope, hipStream_t s);
 hipError_t launch_persist_combine(const PersistArgs& m, int E, double* sq_signal_error_sum, hipStream_t s);   // reducers > 1: adds the partial sums
+// One externally driven step through the mailbox, and the neighbour-message halo through it (mdr_mailbox.hip)
+constexpr uint32_t MAILBOX_DEFAULT_TIMEOUT_US = 2000000;   // a wait gives up after 2 s of the device's constant-rate clock
+hipError_t mailbox_resident_blocks(int vec, bool system_scope, int64_t* blocks);   // workgroups of k_step_mailbox the device holds at once
+uint64_t mailbox_timeout_ticks(uint32_t timeout_us);                                  // 0 = the default
+hipError_t launch_step_mailbox(const StepArgs& a, const PersistArgs& m, bool system_scope, uint64_t timeout_ticks, hipStream_t s);
+int64_t mailbox_halo_granules(int world, int64_t count);
+hipError_t launch_halo_push(const PersistArgs& m, int64_t base, const float* src, int64_t count, uint32_t tag, bool system_scope, hipStream_t s);
+hipError_t launch_halo_pull(const PersistArgs& m, int64_t base, float* out, int64_t count, uint32_t tag, bool system_scope,
+                            uint64_t timeout_ticks, hipStream_t s);
 
 enum StepKind { STEP_FUSED = 0, STEP_GROUP = 1, STEP_SPLIT = 2, STEP_SINGLE = 3, STEP_MULTI = 4, STEP_PACKED = 5 };   // STEP_MULTI: `tiles` envs share a group of `threads` lanes; STEP_PACKED: `tiles` whole envs of `threads` lanes each per wavefront (mdr_multi.hip)
 struct StepPlan {

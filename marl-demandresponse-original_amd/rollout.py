@@ -87,6 +87,13 @@ def _fused_policy(actor, dev, precision: str = "fp32", observe: bool = False, ms
     return cached[1]
 
 
+def _exchange_check(env) -> None:
+    """Sharded houses through sharding.MailboxExchange: raise if a wait inside a mailbox launch gave up (synchronises)."""
+    check = getattr(env, "_exchange_check", None)
+    if check is not None:
+        check()
+
+
 def _observe_act_supported(env, actor) -> bool:
     """Can ``FusedActor.sample_env`` serve this env / actor?  At most 13 senders (fewer than the houses) - the circular neighbours,
     a link table or random_sample - with 4-field messages, any of the optional STATE columns, link defects, at most 64 features,
@@ -250,6 +257,7 @@ def collect_ppo_rollout(env, actor: nn.Module, nb_steps: int, gamma: float = 0.9
         bootstrap[T - 1] = critic(obs).squeeze(1)
     out = {"action": action, "a_prob": a_prob, "reward": reward, "done": done,
            "return": discounted_returns(reward, done, gamma, bootstrap)}
+    _exchange_check(env)
     if store_states:
         out["state"] = states
     if with_others_actions:
@@ -308,6 +316,7 @@ def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float
         if not one_kernel or t == T - 1:
             env.obs_vector("rows", out=state[t + 1].view(E, N, F_len))
         eps = max(eps * float(epsilon_decay), float(min_epsilon))
+    _exchange_check(env)
     return {"state": state, "action": action, "reward": reward, "explored": explored, "epsilon": eps}
 
 
@@ -368,8 +377,11 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
            "sq_temp_error_sum": torch.zeros(E, dtype=torch.float64, device=dev),
            "sq_signal_error_sum": torch.zeros(E, dtype=torch.float64, device=dev)}
     graph_mode = bool(getattr(env, "graph_mode", False))
+    sharded = bool(getattr(env, "sharded", False))
+    if use_graph and sharded:
+        raise ValueError("deploy_policy over sharded houses runs eagerly: capturing the exchanges and halo gathers is not supported")
     if use_graph is None:
-        use_graph = graph_mode
+        use_graph = graph_mode and not sharded
     if use_graph and not graph_mode:
         raise ValueError("use_graph needs an env built with graph_mode=True")
     step0 = 0 if graph_mode else env.steps_taken
@@ -390,6 +402,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     if not use_graph or nb_steps < 3:
         for t in range(nb_steps):
             one_step(0 if graph_mode else t)
+        _exchange_check(env)
         return out
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))

@@ -245,6 +245,194 @@ class TorchDistExchange:
         return self._gathered, world
 
 
+class MailboxExchange(TorchDistExchange):
+    """The per-step exchanges of the sharded-houses layout through peer MAILBOXES instead of collectives: every externally driven
+    step is ONE launch (mdr_env_step_mailbox: the records of every house workgroup pushed into every rank's mailbox, re-summed
+    there in the order of the records path - bit-identical results), and the neighbour-message halo of `obs_vector` goes through
+    a region of the same mailboxes (mdr_mailbox_halo_push / _pull).  The mailboxes are allocated, exported, mapped and agreed on
+    once per env, at its first episode; the rare exchanges stay collectives of the process group (`sum_max_power` once per
+    episode, `sum_base_power` every ceil(300 s / dt) steps, the record-stride agreement and `ranges`).
+
+    A world of one needs no torch.distributed (house_shard=(0, N), exchange_always=True).  Ranks sharing one device count
+    each other in MDR_MAILBOX_CO_RESIDENT.  Waits inside the kernels give up after `timeout_ms` of the device clock and leave an
+    error word that `env.exchange_status()` reports.  Not capturable (the step tag comes from the host), and not for a
+    LocalShardGroup: the shards of one process share its hardware queues, on which spinning launches serialise."""
+
+    HALO_CAP_BYTES = 64 << 20       # per-rank halo region above which an exchange keeps the all-gather (random_sample at scale)
+
+    def __init__(self, process_group=None, timeout_ms: float = 2000):
+        if not timeout_ms > 0:
+            raise ValueError("timeout_ms must be > 0")
+        super().__init__(process_group)
+        self.timeout_us = max(1, min(int(round(float(timeout_ms) * 1000.0)), 0xFFFFFFFF))
+
+    capturable = False
+
+    @staticmethod
+    def _dist(group):
+        import torch.distributed as dist
+        return dist.is_available() and dist.is_initialized(), dist
+
+    def _world_rank(self):
+        on, dist = self._dist(self.process_group)
+        if not on:
+            return 1, 0
+        return dist.get_world_size(self.process_group), dist.get_rank(self.process_group)
+
+    def _check_env(self, env):
+        if isinstance(getattr(env, "_exchange_impl", None), LocalShardGroup):
+            raise RuntimeError("MailboxExchange does not serve a LocalShardGroup: its shards share one process's hardware queues, on "
+                               "which spinning launches serialise")
+
+    # the rare exchanges: collectives of the process group, or nothing to do in a world of one without torch.distributed
+    def agree_partial_records(self, env) -> None:
+        self._check_env(env)
+        if self._dist(self.process_group)[0]:
+            super().agree_partial_records(env)
+        self.persist_mailbox(env)       # once per env: allocation, handles, mapping, barrier - never on the step path
+
+    def sum_max_power(self, env) -> None:
+        if self._dist(self.process_group)[0]:
+            super().sum_max_power(env)
+
+    def sum_base_power(self, env) -> None:
+        if self._dist(self.process_group)[0]:
+            super().sum_base_power(env)
+
+    def ranges(self, env):
+        if self._dist(self.process_group)[0]:
+            return super().ranges(env)
+        if (env.house_offset, env.nb_houses) != (0, env.nb_agents):
+            raise ValueError("a world of one holds every house")
+        return [(0, env.nb_agents)], 0
+
+    def _halo_floats(self, env):
+        """Floats per rank one halo exchange of `env` carries: E * export_max * mf."""
+        import ctypes as C
+        plan = env._halo_plan()
+        spec = env._obs_spec_sharded("rows", plan)
+        mf = int(env._lib.mdr_obs_message_fields(C.byref(spec)))
+        return env.nb_envs * plan.export_max * mf
+
+    def persist_mailbox(self, env, spin_limit: int = 0):
+        """This rank's mailbox and its peers' (allocate zero-filled, export, open, barrier - the sequence of
+        TorchDistExchange.persist_mailbox), with a halo region behind the step region.  Serves the mailbox steps, the halo and
+        `rollout_persistent`; done once per env.  Returns (mdr_mailbox_t, address of this rank's box)."""
+        import ctypes as C
+        import os
+        import torch
+        from . import _native as nat
+        cached = getattr(env, "_persist_dist", None)
+        if cached is not None:
+            cached[0].spin_limit = int(spin_limit)
+            return cached[0], cached[1]
+        self._check_env(env)
+        lib = env._lib
+        world, rank = self._world_rank()
+        if world > nat.MDR_MAX_SHARDS:
+            raise ValueError("the mailbox exchange serves at most %d shards" % nat.MDR_MAX_SHARDS)
+        ranges, _ = self.ranges(env)
+        recs = [env.persist_records(cnt) for _, cnt in ranges]
+        stride = max(recs)
+        step_bytes = int(lib.mdr_mailbox_bytes(env.nb_envs, world, stride))
+        # the halo region: sized for this episode's exchange with room to spare (a 'random_fixed' episode re-draws its links); an
+        # exchange that outgrows it, or would exceed HALO_CAP_BYTES, keeps the all-gather - every rank decides alike
+        halo = 0
+        if world > 1:
+            need = self._halo_floats(env)
+            halo = 2 * need if int(lib.mdr_mailbox_halo_bytes(world, 2 * need)) <= self.HALO_CAP_BYTES else 0
+        nbytes = step_bytes + int(lib.mdr_mailbox_halo_bytes(world, halo))
+        boxes = [None] * world
+        with torch.cuda.device(env.device):
+            if world == 1:      # one device, one process: plain device memory, freed with the env
+                env._mailbox_mem = torch.zeros(nbytes // 8, dtype=torch.int64, device=env.device)
+                own = env._mailbox_mem.data_ptr()
+            else:
+                _, dist = self._dist(self.process_group)
+                ptr = C.c_void_p()
+                fine = 0 if os.environ.get("MDR_MAILBOX_COARSE") == "1" else 1
+                nat.check(lib, None, lib.mdr_mailbox_alloc(nbytes, fine, C.byref(ptr)), "mdr_mailbox_alloc")
+                own = ptr.value
+                handle = C.create_string_buffer(64)
+                nat.check(lib, None, lib.mdr_mailbox_export(C.c_void_p(own), handle), "mdr_mailbox_export")
+                handles = [None] * world
+                dist.all_gather_object(handles, bytes(handle.raw), group=self.process_group)
+                for r in range(world):
+                    if r != rank:
+                        peer = C.c_void_p()
+                        nat.check(lib, None, lib.mdr_mailbox_open(handles[r], C.byref(peer)), "mdr_mailbox_open")
+                        boxes[r] = peer.value
+            boxes[rank] = own
+        mb = nat.MdrMailbox()
+        mb.struct_size = C.sizeof(nat.MdrMailbox)
+        mb.world, mb.rank, mb.records_per_env, mb.spin_limit = world, rank, stride, int(spin_limit)
+        mb.co_resident = int(os.environ.get("MDR_MAILBOX_CO_RESIDENT", "1"))
+        mb.system_scope = 1 if world > 1 else 0
+        for r in range(world):
+            mb.records[r] = recs[r]
+            mb.boxes[r] = boxes[r]
+        if world > 1:
+            self._dist(self.process_group)[1].barrier(group=self.process_group)      # nobody pushes before every mapping exists
+        env._persist_dist = (mb, own, boxes)
+        env._mailbox_addr = own
+        env._halo_capacity = halo
+        env._halo_tag = 0
+        return mb, own
+
+    def step_mailbox(self, env, ptr, source) -> None:
+        """One step of this rank's shard: ONE launch, the exchange through the mailboxes."""
+        import ctypes as C
+        import torch
+        from . import _native as nat
+        mb = self.persist_mailbox(env)[0]
+        with torch.cuda.device(env.device):
+            rc = env._lib.mdr_env_step_mailbox(env._handle, C.c_void_p(ptr), source, C.byref(mb), self.timeout_us, env._stream())
+            nat.check(env._lib, env._handle, rc, "mdr_env_step_mailbox")
+
+    def status(self, env) -> int:
+        """Word 0 of this rank's mailbox after the stream has drained (0: no wait gave up)."""
+        import ctypes as C
+        import torch
+        from . import _native as nat
+        cached = getattr(env, "_persist_dist", None)
+        if cached is None:
+            return 0
+        word = C.c_uint64()
+        with torch.cuda.device(env.device):
+            torch.cuda.synchronize(env.device)
+            nat.check(env._lib, None, env._lib.mdr_mailbox_peek(C.c_void_p(cached[1]), C.byref(word)), "mdr_mailbox_peek")
+        return int(word.value)
+
+    def gather_messages(self, env, padded):
+        """`padded`: this rank's export records [E, export_max, mf] -> every rank's [world, E, export_max, mf], pushed into and
+        pulled from the halo region of the mailboxes (tag = this env's count of halo exchanges; every rank calls in lockstep)."""
+        import ctypes as C
+        import torch
+        from . import _native as nat
+        world, _ = self._world_rank()
+        out = torch.empty((world,) + tuple(padded.shape), dtype=padded.dtype, device=padded.device)
+        if padded.numel() == 0:
+            return out
+        if world == 1:
+            out[0].copy_(padded)
+            return out
+        mb = self.persist_mailbox(env)[0]
+        count = padded.numel()
+        if count > env._halo_capacity:
+            return super().gather_messages(env, padded)
+        src = padded.contiguous()
+        env._halo_tag += 1
+        tag = env._halo_tag
+        with torch.cuda.device(env.device):
+            st = env._stream()
+            nat.check(env._lib, None, env._lib.mdr_mailbox_halo_push(C.byref(mb), env.nb_envs, C.c_void_p(src.data_ptr()), count, tag, st),
+                      "mdr_mailbox_halo_push")
+            nat.check(env._lib, None, env._lib.mdr_mailbox_halo_pull(C.byref(mb), env.nb_envs, C.c_void_p(out.data_ptr()), count, tag,
+                                                                     self.timeout_us, st), "mdr_mailbox_halo_pull")
+        env._halo_keep = src        # alive until the push has read it (the stream orders every later use)
+        return out
+
+
 class LocalShardGroup:
     """All house shards of the same envs driven from ONE process: `nb_shards` BatchedDemandResponseEnv objects, spread
     round-robin over `devices` (a single device rehearses BASELINE config 5's eight 125,000-house shards on one GPU).
@@ -255,6 +443,9 @@ class LocalShardGroup:
 
     def __init__(self, config: dict, nb_envs: int, nb_shards: int, devices: Sequence = ("cuda:0",), seed: int = 0, **kw):
         from .batched_env import BatchedDemandResponseEnv
+        if kw.get("exchange") is not None:
+            raise ValueError("a LocalShardGroup carries its own exchange (MailboxExchange does not serve one: the shards of one "
+                             "process share its hardware queues, on which spinning launches serialise)")
         total = int(config["default_env_prop"]["cluster_prop"]["nb_agents"])
         self.nb_shards, self.nb_envs, self.nb_agents = int(nb_shards), int(nb_envs), total
         self.shards: List = []
