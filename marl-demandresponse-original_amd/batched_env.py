@@ -24,6 +24,7 @@ import torch
 
 from . import _native as nat
 from .config import EnvSpec, flatten_config, from_epoch_seconds
+from .sharding import Exchange, Mailboxes, PlainExchange, TorchDistExchange, decode_error_word, open_mailboxes
 
 OBS_COLUMNS = ("house_temp", "house_mass_temp", "hvac_turned_on", "hvac_lockout",
                "hvac_seconds_since_off", "reg_signal", "cluster_hvac_power")
@@ -97,10 +98,10 @@ class BatchedDemandResponseEnv:
         if self.spec.base_power_mode == 1:
             self._install_interp_grid(interp_grid)
         self.done = torch.zeros((self.nb_envs, self.nb_houses), dtype=torch.bool, device=self.device)
-        # exchange: the object that carries the sharded-houses exchanges (None: sharding.TorchDistExchange over process_group;
-        # sharding.MailboxExchange: one launch per step through peer mailboxes)
-        if exchange is not None:
-            self._exchange_impl = exchange
+        # exchange: the sharding.Exchange that carries the sharded-houses exchanges (None: sharding.TorchDistExchange over
+        # process_group; sharding.MailboxExchange: one launch per step through peer mailboxes)
+        self._exchange_impl = exchange
+        self._mailboxes: Optional[Mailboxes] = None      # this env's mailboxes (rollout_persistent, MailboxExchange), built on first use
 
     # ------------------------------------------------------------------ setup
     def _make_config(self) -> nat.MdrConfig:
@@ -266,13 +267,14 @@ class BatchedDemandResponseEnv:
             pass
 
     # ------------------------------------------------------------------ episode start
-    def _exchange(self):
-        """The object that carries the sharded-houses exchanges (sharding.TorchDistExchange unless a
-        sharding.LocalShardGroup installed its own)."""
-        ex = getattr(self, "_exchange_impl", None)
+    def _exchange(self) -> Exchange:
+        """The object that carries the sharded-houses exchanges (sharding.TorchDistExchange unless one was given or a
+        sharding.LocalShardGroup installed its own; an object without the Exchange base is wrapped in a sharding.PlainExchange)."""
+        ex = self._exchange_impl
         if ex is None:
-            from .sharding import TorchDistExchange
             ex = self._exchange_impl = TorchDistExchange(self.process_group)
+        elif not isinstance(ex, Exchange):
+            ex = self._exchange_impl = PlainExchange(ex)
         return ex
 
     def _begin_episode(self):
@@ -401,7 +403,7 @@ class BatchedDemandResponseEnv:
                 nat.check(self._lib, self._handle, rc, "mdr_env_step")
             return
         ex = self._exchange()
-        if getattr(ex, "step_mailbox", None) is not None:
+        if ex.mailbox_steps:
             ex.step_mailbox(self, ptr, source)      # ONE launch, the exchange through the mailboxes (no collective, no host sync)
             self._interp_exchange()
             return
@@ -444,7 +446,7 @@ class BatchedDemandResponseEnv:
         if n <= 0:
             return
         ex = self._exchange()
-        if getattr(ex, "step_mailbox", None) is not None:
+        if ex.mailbox_steps:
             for _ in range(n):
                 ex.step_mailbox(self, ptr, source)
                 self._interp_exchange()
@@ -547,7 +549,7 @@ class BatchedDemandResponseEnv:
         ctl = getattr(self, "_controller", nat.ACTIONS_BANGBANG)
         if self.sharded:
             source = nat.ACTIONS_EXTERNAL if actions is not None else ctl
-            if self.graph_mode and self.spec.base_power_mode != 1 and getattr(self._exchange(), "capturable", False):
+            if self.graph_mode and self.spec.base_power_mode != 1 and self._exchange().capturable:
                 return self._rollout_sharded_graph(int(nb_steps), self._actions_ptr(actions), source)
             self._steps_sharded(int(nb_steps), self._actions_ptr(actions), source)
             self._exchange_check()
@@ -564,21 +566,8 @@ class BatchedDemandResponseEnv:
         if asked, ``power_trace`` [nb_steps, E].  Shapes without a fused kernel (N > 2048, or N > 512 with N % 4 != 0) are
         stepped one launch at a time inside the library with the same accumulators; sharded houses fall back to
         ``rollout`` and return None."""
-        E, N = self.nb_envs, self.nb_houses
-        out = nat.MdrRolloutOut()
-        out.struct_size = C.sizeof(nat.MdrRolloutOut)
-        res = {}
         with torch.cuda.device(self.device):
-            if accumulate:
-                res["reward_sum"] = torch.zeros((E, N), dtype=torch.float32, device=self.device)
-                res["sq_temp_error_sum"] = torch.zeros(E, dtype=torch.float64, device=self.device)
-                res["sq_signal_error_sum"] = torch.zeros(E, dtype=torch.float64, device=self.device)
-                out.reward_sum = res["reward_sum"].data_ptr()
-                out.sq_temp_error_sum = res["sq_temp_error_sum"].data_ptr()
-                out.sq_signal_error_sum = res["sq_signal_error_sum"].data_ptr()
-            if power_trace:
-                res["power_trace"] = torch.zeros((nb_steps, E), dtype=torch.float64, device=self.device)
-                out.power_trace = res["power_trace"].data_ptr()
+            out, res = self._rollout_out(nb_steps, power_trace, accumulate)
             rc = self._lib.mdr_env_rollout_fused(self._handle, C.c_void_p(self.t["actions"].data_ptr()), int(nb_steps),
                                                  C.byref(out), self._stream())
             if rc == nat.MDR_ERR_UNSUPPORTED:
@@ -587,88 +576,50 @@ class BatchedDemandResponseEnv:
             nat.check(self._lib, self._handle, rc, "mdr_env_rollout_fused")
         return res
 
-    # ------------------------------------------------------------------ persistent rollout (mailbox exchange, no kernel boundary per step)
-    PERSIST_ERRORS = {1: "a house workgroup waited too long for the totals of a step", 2: "a reducer waited too long for a step's records"}
+    def _rollout_out(self, nb_steps: int, power_trace: bool, accumulate: bool):
+        """(mdr_rollout_out_t, dict) over zero-filled accumulators: those of main-deploy.py:124-152 if `accumulate`, the cluster power
+        of every step if `power_trace`."""
+        E, N = self.nb_envs, self.nb_houses
+        res = {}
+        if accumulate:
+            res["reward_sum"] = torch.zeros((E, N), dtype=torch.float32, device=self.device)
+            res["sq_temp_error_sum"] = torch.zeros(E, dtype=torch.float64, device=self.device)
+            res["sq_signal_error_sum"] = torch.zeros(E, dtype=torch.float64, device=self.device)
+        if power_trace:
+            res["power_trace"] = torch.zeros((nb_steps, E), dtype=torch.float64, device=self.device)
+        out = nat.MdrRolloutOut()
+        out.struct_size = C.sizeof(nat.MdrRolloutOut)
+        for name, t in res.items():
+            setattr(out, name, t.data_ptr())
+        return out, res
 
+    # ------------------------------------------------------------------ persistent rollout (mailbox exchange, no kernel boundary per step)
     def persist_records(self, nb_houses: Optional[int] = None) -> int:
         """Records one shard of `nb_houses` houses pushes per env and step (one per 1024-house workgroup)."""
         return int(self._lib.mdr_persist_records(int(self.nb_houses if nb_houses is None else nb_houses)))
 
-    def _persist_mailbox(self, world: int, stride: int) -> torch.Tensor:
-        """This shard's mailbox: zero-filled ONCE, from then on written by the persistent launches only."""
-        box = getattr(self, "_mailbox", None)
-        size = int(self._lib.mdr_mailbox_bytes(self.nb_envs, world, stride)) // 8
-        if box is None or box.numel() != size:
-            box = self._mailbox = torch.zeros(size, dtype=torch.int64, device=self.device)
-        return box
-
     def persist_status(self) -> int:
-        """Word 0 of the mailbox after the stream has drained: 0 = every persistent launch so far ran to its end."""
-        addr = getattr(self, "_mailbox_addr", None)
-        if addr is None:
-            box = getattr(self, "_mailbox", None)
-            if box is None:
-                return 0
-            addr = box.data_ptr()
-        word = C.c_uint64()
-        with torch.cuda.device(self.device):
-            torch.cuda.synchronize(self.device)
-            nat.check(self._lib, None, self._lib.mdr_mailbox_peek(C.c_void_p(addr), C.byref(word)), "mdr_mailbox_peek")
-        return int(word.value)
+        """Word 0 of this env's mailbox after the device has drained: 0 = every mailbox launch so far ran to its end."""
+        return 0 if self._mailboxes is None else self._mailboxes.status()
 
     def _uses_mailbox(self) -> bool:
-        return self.sharded and getattr(self._exchange(), "step_mailbox", None) is not None
+        return self.sharded and self._exchange().mailbox_steps
 
     def exchange_status(self) -> int:
         """Word 0 of this rank's mailbox once the stream has drained (sharding.MailboxExchange): 0 while every mailbox launch ran
         to its end; otherwise raises with the step tag, the kind of wait that gave up and the workgroup.  0 for other exchanges."""
         if not self._uses_mailbox():
             return 0
-        word = self._exchange().status(self)
+        word = self.persist_status()
         if word:
-            kind = (word >> 28) & 0xF
-            what = self.MAILBOX_ERRORS.get(kind, self.PERSIST_ERRORS.get(kind, "kind %d" % kind))
             raise RuntimeError("mailbox exchange gave up at step tag %d (kind %d, workgroup %d): %s; the env's buffers and its step "
-                               "count no longer agree with its peers - rebuild the env" % ((word >> 32) & 0xFFFFFFFF, kind, word & 0x0FFFFFFF, what))
+                               "count no longer agree with its peers - rebuild the env" % decode_error_word(word))
         return 0
 
     def _exchange_check(self) -> None:
+        """Sharded houses through sharding.MailboxExchange: raise if a wait inside a mailbox launch gave up (synchronises)."""
         if self._uses_mailbox():
             self.exchange_status()
-
-    MAILBOX_ERRORS = {3: "a house workgroup of a mailbox step waited too long for the totals",
-                      4: "the reducer of a mailbox step waited too long for a step's records",
-                      5: "a halo pull waited too long for a peer's message records"}
-
-    def _persist_raise(self, word: int):
-        kind = (word >> 28) & 0xF
-        raise RuntimeError("persistent rollout gave up at step tag %d (workgroup %d): %s; the buffers hold the state before the launch, "
-                           "the handle's step count does not - rebuild the env" % ((word >> 32) & 0xFFFFFFFF, word & 0x0FFFFFFF,
-                                                                                  self.PERSIST_ERRORS.get(kind, "kind %d" % kind)))
-
-    def _persist_call(self, nb_steps: int, mailbox: "nat.MdrMailbox", power_trace: bool, accumulate: bool, stream=None):
-        E, N = self.nb_envs, self.nb_houses
-        out = nat.MdrRolloutOut()
-        out.struct_size = C.sizeof(nat.MdrRolloutOut)
-        res = {}
-        with torch.cuda.device(self.device):
-            if accumulate:
-                res["reward_sum"] = torch.zeros((E, N), dtype=torch.float32, device=self.device)
-                res["sq_temp_error_sum"] = torch.zeros(E, dtype=torch.float64, device=self.device)
-                res["sq_signal_error_sum"] = torch.zeros(E, dtype=torch.float64, device=self.device)
-                out.reward_sum = res["reward_sum"].data_ptr()
-                out.sq_temp_error_sum = res["sq_temp_error_sum"].data_ptr()
-                out.sq_signal_error_sum = res["sq_signal_error_sum"].data_ptr()
-            if power_trace:
-                res["power_trace"] = torch.zeros((nb_steps, E), dtype=torch.float64, device=self.device)
-                out.power_trace = res["power_trace"].data_ptr()
-            if stream is not None:      # a side stream (LocalShardGroup): behind the accumulators' zero fills
-                stream.wait_stream(torch.cuda.current_stream(self.device))
-            st = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
-            rc = self._lib.mdr_env_rollout_persistent(self._handle, C.c_void_p(self.t["actions"].data_ptr()), int(nb_steps), C.byref(out),
-                                                      C.byref(mailbox), st)
-            nat.check(self._lib, self._handle, rc, "mdr_env_rollout_persistent")
-        return res
 
     def rollout_persistent(self, nb_steps: int, power_trace: bool = False, accumulate: bool = True, check: bool = True,
                            spin_limit: int = 0):
@@ -677,23 +628,26 @@ class BatchedDemandResponseEnv:
         device - the split path's 1 env x 1,000,000 houses included - and, over torch.distributed, the sharded-houses layout
         with peer mailboxes instead of the per-step all-gather.  Same results and accumulators as `rollout_fused`; `check`
         synchronises and raises if a wait inside the kernel gave up (check=False: poll `persist_status()` yourself)."""
-        if self.sharded and hasattr(self._exchange(), "persist_mailbox"):
-            mb, self._mailbox_addr = self._exchange().persist_mailbox(self, spin_limit)
-        else:
+        boxes = self._mailboxes
+        if boxes is None and self.sharded:
+            boxes = self._exchange().mailboxes(self)
+        if boxes is None:
             if self.sharded and not self._exchange_always:
                 raise RuntimeError("rollout_persistent over sharded houses needs an exchange that hands out peer mailboxes")
-            n = self.persist_records()
-            box = self._persist_mailbox(1, n)
-            mb = nat.MdrMailbox()
-            mb.struct_size = C.sizeof(nat.MdrMailbox)
-            mb.world, mb.rank, mb.records_per_env, mb.co_resident, mb.spin_limit = 1, 0, n, 1, int(spin_limit)
-            mb.records[0] = n
-            mb.boxes[0] = box.data_ptr()
-        res = self._persist_call(int(nb_steps), mb, power_trace, accumulate)
+            boxes = self._mailboxes = open_mailboxes(self, [self.persist_records()], 0, plain=True)   # zero-filled ONCE
+        mb = boxes.mb
+        mb.spin_limit = int(spin_limit)
+        with torch.cuda.device(self.device):
+            out, res = self._rollout_out(int(nb_steps), power_trace, accumulate)
+            rc = self._lib.mdr_env_rollout_persistent(self._handle, C.c_void_p(self.t["actions"].data_ptr()), int(nb_steps), C.byref(out),
+                                                      C.byref(mb), self._stream())
+            nat.check(self._lib, self._handle, rc, "mdr_env_rollout_persistent")
         if check:
             word = self.persist_status()
             if word:
-                self._persist_raise(word)
+                tag, _, workgroup, what = decode_error_word(word)
+                raise RuntimeError("persistent rollout gave up at step tag %d (workgroup %d): %s; the buffers hold the state before the "
+                                   "launch, the handle's step count does not - rebuild the env" % (tag, workgroup, what))
         return res
 
     def pack_env(self, env_index: int = 0) -> np.ndarray:

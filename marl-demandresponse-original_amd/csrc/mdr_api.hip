@@ -842,31 +842,65 @@ int64_t mdr_mailbox_bytes(int32_t nb_envs, int32_t world, int32_t records_per_en
 
 int64_t mdr_persist_records(int32_t nb_houses) { return nb_houses < 1 ? 0 : mdr::split_blocks(nb_houses, 256); }
 
-int mdr_env_rollout_persistent(mdr_env_t* env, uint8_t* actions, int32_t nb_steps, const mdr_rollout_out_t* out, const mdr_mailbox_t* mb,
-                               void* stream) {
-  if (!env) return MDR_ERR_INVALID;
+// The mailbox's own checks, for both launchers and the halo (which has no env: `env` may be NULL).
+static int check_mailbox(mdr_env* env, const mdr_mailbox_t* mb) {
   if (!mb) return fail(env, MDR_ERR_INVALID, "mailbox is NULL");
   if (mb->struct_size != sizeof(mdr_mailbox_t)) return fail(env, MDR_ERR_INVALID, "mdr_mailbox_t size mismatch (ABI)");
-  if (out && out->struct_size != sizeof(mdr_rollout_out_t)) return fail(env, MDR_ERR_INVALID, "mdr_rollout_out_t size mismatch (ABI)");
-  if (nb_steps < 0) return fail(env, MDR_ERR_INVALID, "nb_steps must be >= 0");
-  if (!env->bound || !env->has_tables) return fail(env, MDR_ERR_UNBOUND, "no episode: call reset/load_episode and begin_episode first");
-  if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin without step_end");
-  if (interp_mode(env)) return fail(env, MDR_ERR_UNSUPPORTED, "interpolated base power: the update is host work between steps");
-  const mdr_config_t& c = env->cfg;
-  if (c.nb_envs > 65535) return fail(env, MDR_ERR_UNSUPPORTED, "the persistent rollout puts the env index on grid.y: nb_envs must be <= 65535");
   if (mb->world < 1 || mb->world > MDR_MAX_SHARDS || mb->rank < 0 || mb->rank >= mb->world)
     return fail(env, MDR_ERR_INVALID, "mailbox: need 0 <= rank < world <= MDR_MAX_SHARDS");
-  if (mb->world == 1 && sharded(env)) return fail(env, MDR_ERR_INVALID, "mailbox: a shard of the env needs its peers (world > 1)");
   if (mb->co_resident < 1) return fail(env, MDR_ERR_INVALID, "mailbox: co_resident must be >= 1");
-  const int64_t mine = mdr::split_blocks(c.nb_houses, 256);   // one record per 256-thread workgroup: 1024 houses, 256 when nb_houses % 4 != 0
-  if (mb->records[mb->rank] != mine) return fail(env, MDR_ERR_INVALID, "mailbox: records[rank] is not this handle's workgroup count");
+  if (mb->records_per_env < 1) return fail(env, MDR_ERR_INVALID, "mailbox: records_per_env must be >= 1");
   for (int r = 0; r < mb->world; ++r) {
     if (mb->records[r] < 1 || mb->records[r] > mb->records_per_env) return fail(env, MDR_ERR_INVALID, "mailbox: records[r] must be in [1, records_per_env]");
     if (!mb->boxes[r] || ((uintptr_t)mb->boxes[r] & 7u) != 0) return fail(env, MDR_ERR_INVALID, "mailbox: boxes[r] is NULL or not 8-byte aligned");
   }
-  if (nb_steps == 0) return MDR_OK;
+  return MDR_OK;
+}
+
+static mdr::PersistArgs mailbox_args(const mdr_mailbox_t* mb, uint32_t tag) {
+  mdr::PersistArgs m{};
+  for (int q = 0; q < mb->world; ++q) {
+    m.box[q] = mb->boxes[q];
+    m.nrec[q] = mb->records[q];
+  }
+  m.world = mb->world;
+  m.rank = mb->rank;
+  m.stride = mb->records_per_env;
+  m.tag_base = tag;
+  return m;
+}
+
+// What both mailbox launchers refuse besides their own arguments: an env without an episode or with a step pending, more envs than
+// grid.y holds, a mailbox that does not describe this handle, a capturing stream (the step tags come from the host), and `grid`
+// workgroups x co_resident launches beyond the `resident` ones the device holds at once (a wait for a workgroup that never starts
+// would never end).  `grid` 0: nothing is launched, so only the env and the mailbox are checked.
+static int check_mailbox_launch(mdr_env* env, const mdr_mailbox_t* mb, const std::string& what, int64_t grid, int64_t resident,
+                                hipStream_t s) {
+  if (!env->bound || !env->has_tables) return fail(env, MDR_ERR_UNBOUND, "no episode: call reset/load_episode and begin_episode first");
+  if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin without step_end");
+  if (env->cfg.nb_envs > 65535) return fail(env, MDR_ERR_UNSUPPORTED, "the " + what + " puts the env index on grid.y: nb_envs must be <= 65535");
+  if (mb->world == 1 && sharded(env)) return fail(env, MDR_ERR_INVALID, "mailbox: a shard of the env needs its peers (world > 1)");
+  // one record per 256-thread workgroup: 1024 houses, 256 when nb_houses % 4 != 0
+  if (mb->records[mb->rank] != mdr::split_blocks(env->cfg.nb_houses, 256))
+    return fail(env, MDR_ERR_INVALID, "mailbox: records[rank] is not this handle's workgroup count");
+  if (grid == 0) return MDR_OK;
+  if (capturing(s)) return fail(env, MDR_ERR_INVALID, "the " + what + " takes its step tags from the host: it cannot be captured");
+  if (grid * mb->co_resident > resident)
+    return fail(env, MDR_ERR_UNSUPPORTED, what + ": " + std::to_string(grid) + " workgroups x " + std::to_string(mb->co_resident) +
+                                              " co-resident launches exceed the " + std::to_string(resident) + " the device holds at once");
+  return MDR_OK;
+}
+
+int mdr_env_rollout_persistent(mdr_env_t* env, uint8_t* actions, int32_t nb_steps, const mdr_rollout_out_t* out, const mdr_mailbox_t* mb,
+                               void* stream) {
+  if (!env) return MDR_ERR_INVALID;
+  int rc = check_mailbox(env, mb);
+  if (rc != MDR_OK) return rc;
+  if (out && out->struct_size != sizeof(mdr_rollout_out_t)) return fail(env, MDR_ERR_INVALID, "mdr_rollout_out_t size mismatch (ABI)");
+  if (nb_steps < 0) return fail(env, MDR_ERR_INVALID, "nb_steps must be >= 0");
+  if (interp_mode(env)) return fail(env, MDR_ERR_UNSUPPORTED, "interpolated base power: the update is host work between steps");
+  const mdr_config_t& c = env->cfg;
   hipStream_t s = (hipStream_t)stream;
-  if (capturing(s)) return fail(env, MDR_ERR_INVALID, "the persistent rollout counts its steps on the host: it cannot be captured");
   const bool sys = mb->system_scope != 0;
   // how far the houses run ahead of the totals: deeper hides more of the exchange latency (each level costs 4 KB of LDS per workgroup)
   static const int depth = [] { const char* t = getenv("MDR_PERSIST_DEPTH"); const int v = t ? atoi(t) : mdr::PERSIST_MAX_DEPTH; return std::max(1, std::min(v, mdr::PERSIST_MAX_DEPTH)); }();
@@ -878,17 +912,13 @@ int mdr_env_rollout_persistent(mdr_env_t* env, uint8_t* actions, int32_t nb_step
   int reducers = std::min(mdr::persist_reducers(all_records), depth);
   // (their partial sums of the squared signal error go through `partials`, the split path's scratch: [E][...][3] doubles, idle here)
   if (reducers > 1 && (!env->buf.partials || (int64_t)reducers > mdr_partials_per_env(c.nb_houses) * 3)) reducers = 1;
-  const int64_t grid = (mine + reducers) * c.nb_envs;
-  if (grid * mb->co_resident > resident) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "persistent rollout: %lld workgroups x %d co-resident launches exceed the %lld the device holds at once",
-             (long long)grid, (int)mb->co_resident, (long long)resident);
-    return fail(env, MDR_ERR_UNSUPPORTED, msg);
-  }
+  const int64_t grid = nb_steps == 0 ? 0 : (mb->records[mb->rank] + reducers) * (int64_t)c.nb_envs;
+  rc = check_mailbox_launch(env, mb, "persistent rollout", grid, resident, s);
+  if (rc != MDR_OK || nb_steps == 0) return rc;
   int32_t done = 0;
   while (done < nb_steps) {
     mdr::StepArgs a;
-    int rc = step_args(env, actions, env->controller, s, &a);   // refills the tables if the cursor left them
+    rc = step_args(env, actions, env->controller, s, &a);   // refills the tables if the cursor left them
     if (rc != MDR_OK) return rc;
     const int64_t room = c.table_steps - (env->k - env->j0);
     mdr::RolloutArgs r{};
@@ -899,15 +929,7 @@ int mdr_env_rollout_persistent(mdr_env_t* env, uint8_t* actions, int32_t nb_step
       r.sq_temp_error_sum = out->sq_temp_error_sum;
       r.sq_signal_error_sum = out->sq_signal_error_sum;
     }
-    mdr::PersistArgs m{};
-    for (int q = 0; q < mb->world; ++q) {
-      m.box[q] = mb->boxes[q];
-      m.nrec[q] = mb->records[q];
-    }
-    m.world = mb->world;
-    m.rank = mb->rank;
-    m.stride = mb->records_per_env;
-    m.tag_base = env->mailbox_tag;
+    mdr::PersistArgs m = mailbox_args(mb, env->mailbox_tag);
     m.spin_limit = mb->spin_limit ? mb->spin_limit : (1u << 20);
     m.depth = depth;
     m.reducers = reducers;
@@ -967,60 +989,20 @@ int mdr_mailbox_peek(const uint64_t* box, uint64_t* word0) {
 
 int mdr_mailbox_close(uint64_t* box) { return (!box || hipIpcCloseMemHandle(box) == hipSuccess) ? MDR_OK : MDR_ERR_HIP; }
 
-// The mailbox checks of mdr_env_rollout_persistent, for the one-step exchange and the halo (which has no env: `env` may be NULL).
-static int check_mailbox(mdr_env* env, const mdr_mailbox_t* mb) {
-  if (!mb) return fail(env, MDR_ERR_INVALID, "mailbox is NULL");
-  if (mb->struct_size != sizeof(mdr_mailbox_t)) return fail(env, MDR_ERR_INVALID, "mdr_mailbox_t size mismatch (ABI)");
-  if (mb->world < 1 || mb->world > MDR_MAX_SHARDS || mb->rank < 0 || mb->rank >= mb->world)
-    return fail(env, MDR_ERR_INVALID, "mailbox: need 0 <= rank < world <= MDR_MAX_SHARDS");
-  if (mb->co_resident < 1) return fail(env, MDR_ERR_INVALID, "mailbox: co_resident must be >= 1");
-  if (mb->records_per_env < 1) return fail(env, MDR_ERR_INVALID, "mailbox: records_per_env must be >= 1");
-  for (int r = 0; r < mb->world; ++r) {
-    if (mb->records[r] < 1 || mb->records[r] > mb->records_per_env) return fail(env, MDR_ERR_INVALID, "mailbox: records[r] must be in [1, records_per_env]");
-    if (!mb->boxes[r] || ((uintptr_t)mb->boxes[r] & 7u) != 0) return fail(env, MDR_ERR_INVALID, "mailbox: boxes[r] is NULL or not 8-byte aligned");
-  }
-  return MDR_OK;
-}
-
-static mdr::PersistArgs mailbox_args(const mdr_mailbox_t* mb, uint32_t tag) {
-  mdr::PersistArgs m{};
-  for (int q = 0; q < mb->world; ++q) {
-    m.box[q] = mb->boxes[q];
-    m.nrec[q] = mb->records[q];
-  }
-  m.world = mb->world;
-  m.rank = mb->rank;
-  m.stride = mb->records_per_env;
-  m.tag_base = tag;
-  return m;
-}
-
 int mdr_env_step_mailbox(mdr_env_t* env, uint8_t* actions, int action_source, const mdr_mailbox_t* mb, uint32_t timeout_us, void* stream) {
   if (!env) return MDR_ERR_INVALID;
   int rc = check_mailbox(env, mb);
   if (rc != MDR_OK) return rc;
-  if (!env->bound || !env->has_tables) return fail(env, MDR_ERR_UNBOUND, "no episode: call reset/load_episode and begin_episode first");
-  if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin without step_end");
   if (env->interp_due)
     return fail(env, MDR_ERR_INVALID, "base power update pending: mdr_env_interp_local, SUM all-reduce of base_power, mdr_env_interp_apply");
-  const mdr_config_t& c = env->cfg;
-  if (c.nb_envs > 65535) return fail(env, MDR_ERR_UNSUPPORTED, "the mailbox step puts the env index on grid.y: nb_envs must be <= 65535");
-  if (mb->world == 1 && sharded(env)) return fail(env, MDR_ERR_INVALID, "mailbox: a shard of the env needs its peers (world > 1)");
-  const int64_t mine = mdr::split_blocks(c.nb_houses, 256);   // one record per 256-thread workgroup: 1024 houses, 256 when nb_houses % 4 != 0
-  if (mb->records[mb->rank] != mine) return fail(env, MDR_ERR_INVALID, "mailbox: records[rank] is not this handle's workgroup count");
   hipStream_t s = (hipStream_t)stream;
-  if (capturing(s)) return fail(env, MDR_ERR_INVALID, "the mailbox step takes its tag from the host: it cannot be captured");
   const bool sys = mb->system_scope != 0;
   int64_t resident = 0;
-  hipError_t e = mdr::mailbox_resident_blocks(c.nb_houses % 4 == 0 ? 4 : 1, sys, &resident);
+  hipError_t e = mdr::mailbox_resident_blocks(env->cfg.nb_houses % 4 == 0 ? 4 : 1, sys, &resident);
   if (e != hipSuccess) return hip_fail(env, e, "occupancy query");
-  const int64_t grid = (mine + 1) * c.nb_envs;   // + one reducer workgroup per env
-  if (grid * mb->co_resident > resident) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "mailbox step: %lld workgroups x %d co-resident launches exceed the %lld the device holds at once",
-             (long long)grid, (int)mb->co_resident, (long long)resident);
-    return fail(env, MDR_ERR_UNSUPPORTED, msg);
-  }
+  const int64_t grid = (mb->records[mb->rank] + 1) * (int64_t)env->cfg.nb_envs;   // + one reducer workgroup per env
+  rc = check_mailbox_launch(env, mb, "mailbox step", grid, resident, s);
+  if (rc != MDR_OK) return rc;
   mdr::StepArgs a;
   rc = step_args(env, actions, action_source, s, &a);   // refills the tables if the cursor left them
   if (rc != MDR_OK) return rc;
@@ -1069,14 +1051,21 @@ int mdr_mailbox_halo_pull(const mdr_mailbox_t* mb, int32_t nb_envs, float* out, 
   return e == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
-int mdr_env_step_begin(mdr_env_t* env, uint8_t* actions, int action_source, void* stream) {
+// The preconditions of both step_begin forms.
+static int check_step_begin(mdr_env_t* env) {
   if (!env) return MDR_ERR_INVALID;
   if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin called twice");
   if (env->interp_due)
     return fail(env, MDR_ERR_INVALID, "base power update pending: mdr_env_interp_local, SUM all-reduce of base_power, mdr_env_interp_apply");
   if (env->bound && !env->buf.partials) return fail(env, MDR_ERR_UNBOUND, "buffer 'partials' is NULL");
+  return MDR_OK;
+}
+
+int mdr_env_step_begin(mdr_env_t* env, uint8_t* actions, int action_source, void* stream) {
+  int rc = check_step_begin(env);
+  if (rc != MDR_OK) return rc;
   mdr::StepArgs a;
-  int rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);
+  rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);
   if (rc != MDR_OK) return rc;
   hipError_t e = mdr::launch_step_begin_split(a, true, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "step_begin");
@@ -1085,14 +1074,11 @@ int mdr_env_step_begin(mdr_env_t* env, uint8_t* actions, int action_source, void
 }
 
 int mdr_env_step_begin_records(mdr_env_t* env, uint8_t* actions, int action_source, int32_t records_per_env, void* stream) {
-  if (!env) return MDR_ERR_INVALID;
-  if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin called twice");
-  if (env->interp_due)
-    return fail(env, MDR_ERR_INVALID, "base power update pending: mdr_env_interp_local, SUM all-reduce of base_power, mdr_env_interp_apply");
-  if (env->bound && !env->buf.partials) return fail(env, MDR_ERR_UNBOUND, "buffer 'partials' is NULL");
+  int rc = check_step_begin(env);
+  if (rc != MDR_OK) return rc;
   if (records_per_env < env->nblk) return fail(env, MDR_ERR_INVALID, "records_per_env smaller than mdr_env_partial_records()");
   mdr::StepArgs a;
-  int rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);
+  rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);
   if (rc != MDR_OK) return rc;
   a.nblk = records_per_env;
   if (graph_mode(env)) {   // graph mode: begin - collective - end can be captured as ONE hipGraph node sequence and replayed

@@ -49,52 +49,6 @@ __device__ __forceinline__ gu64* abort_lane_ptr(const PersistArgs& m) {
   return p;
 }
 
-// step_vec_rows (mdr_step_common.h) without the stores: the same loads, commands and house_step, the outputs left in registers
-template <int VEC>
-__device__ __forceinline__ void step_vec_regs(const StepArgs& a, int64_t i, float od_old, float solar, HouseOut* out, int* lockout,
-                                              unsigned* act) {
-  float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];
-  int sso[VEC];
-  unsigned fl[VEC];
-  load_vec<VEC>(a.Ta, i, Ta);
-  load_vec<VEC>(a.Tm, i, Tm);
-  load_vec<VEC>(a.sso, i, sso);
-  load_bytes<VEC>(a.flags, i, fl);
-  if (a.action_source == MDR_ACTIONS_EXTERNAL) load_bytes<VEC>(a.actions, i, act);
-  load_param<VEC>(a.k01, i, k01);
-  load_param<VEC>(a.s0, i, s0);
-  load_param<VEC>(a.k10, i, k10);
-  load_param<VEC>(a.s1, i, s1);
-  load_param<VEC>(a.inv_Ua, i, iu);
-  load_param<VEC>(a.Q_hvac, i, q);
-  load_param<VEC>(a.P_max, i, pm);
-  load_param<VEC>(a.target, i, tg);
-  load_param<VEC>(a.deadband, i, db);
-  load_vec<VEC>(a.lockout, i, lockout);
-  bool cmds[VEC];
-  if (a.action_source == MDR_ACTIONS_EXTERNAL) {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) cmds[v] = act[v] != 0u;
-  } else if (a.action_source == MDR_ACTIONS_BANGBANG) {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      cmds[v] = Ta[v] > tg[v];
-      act[v] = cmds[v] ? 1u : 0u;
-    }
-  } else {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      cmds[v] = controller_cmd(a.action_source, Ta[v], tg[v], db[v], (fl[v] & 1u) != 0u);
-      act[v] = cmds[v] ? 1u : 0u;
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    HouseIn h{Ta[v], Tm[v], sso[v], fl[v], k01[v], s0[v], k10[v], s1[v], iu[v], q[v], pm[v], tg[v], db[v], lockout[v]};
-    out[v] = house_step(h, cmds[v], od_old, solar, a.dt);
-  }
-}
-
 // s_flag: 0 = go on, 1 = the error word was found set (another waiter gave up), 2 = this workgroup's wait gave up
 template <int VEC, bool SYS>
 __global__ __launch_bounds__(256) void k_step_mailbox(StepArgs a, PersistArgs m, uint64_t timeout_ticks) {
@@ -171,7 +125,14 @@ __global__ __launch_bounds__(256) void k_step_mailbox(StepArgs a, PersistArgs m,
   unsigned act[VEC];
   Red3 acc{0.0, 0.0, 0.0f};
   if (live) {
-    step_vec_regs<VEC>(a, i, a.od_old[e], a.solar_new[e], o, lk, act);
+    const float od_e = a.od_old[e], so_e = a.solar_new[e];
+    float od[VEC], so[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      od[v] = od_e;
+      so[v] = so_e;
+    }
+    house_step_vec<VEC>(a, i, od, so, o, lk, act);
     float p = 0.0f, ps = 0.0f;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {   // partial_block's arithmetic (mdr_kernels.hip)

@@ -212,6 +212,55 @@ __device__ __forceinline__ void controller_cmds(int src, const HouseIn* hs, cons
   }
 }
 
+// step_vec_rows without the stores: a lane's VEC houses at i loaded, commanded and stepped with per-lane outdoor temperature and
+// solar gain; the outputs, the lockouts and the action bits stay in registers (k_step_mailbox stores them once the totals arrive).
+// step_vec_rows and k_step_single_house keep their own copies: written through this helper they compile to different code.
+template <int VEC>
+__device__ __forceinline__ void house_step_vec(const StepArgs& a, int64_t i, const float* od_old, const float* solar, HouseOut* out,
+                                               int* lockout, unsigned* act) {
+  float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];
+  int sso[VEC];
+  unsigned fl[VEC];
+  load_vec<VEC>(a.Ta, i, Ta);
+  load_vec<VEC>(a.Tm, i, Tm);
+  load_vec<VEC>(a.sso, i, sso);
+  load_bytes<VEC>(a.flags, i, fl);
+  if (a.action_source == MDR_ACTIONS_EXTERNAL) load_bytes<VEC>(a.actions, i, act);
+  load_param<VEC>(a.k01, i, k01);
+  load_param<VEC>(a.s0, i, s0);
+  load_param<VEC>(a.k10, i, k10);
+  load_param<VEC>(a.s1, i, s1);
+  load_param<VEC>(a.inv_Ua, i, iu);
+  load_param<VEC>(a.Q_hvac, i, q);
+  load_param<VEC>(a.P_max, i, pm);
+  load_param<VEC>(a.target, i, tg);
+  load_param<VEC>(a.deadband, i, db);
+  load_vec<VEC>(a.lockout, i, lockout);
+  // the in-kernel controllers act on the pre-step observation (agents/bangbang_controllers.py); three wave-uniform arms
+  bool cmds[VEC];
+  if (a.action_source == MDR_ACTIONS_EXTERNAL) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) cmds[v] = act[v] != 0u;
+  } else if (a.action_source == MDR_ACTIONS_BANGBANG) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      cmds[v] = Ta[v] > tg[v];
+      act[v] = cmds[v] ? 1u : 0u;
+    }
+  } else {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      cmds[v] = controller_cmd(a.action_source, Ta[v], tg[v], db[v], (fl[v] & 1u) != 0u);
+      act[v] = cmds[v] ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    HouseIn h{Ta[v], Tm[v], sso[v], fl[v], k01[v], s0[v], k10[v], s1[v], iu[v], q[v], pm[v], tg[v], db[v], lockout[v]};
+    out[v] = house_step(h, cmds[v], od_old[v], solar[v], a.dt);
+  }
+}
+
 template <int VEC>
 __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, const float* od_old, const float* solar, HouseOut* out, int* lockout) {
   float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];

@@ -87,13 +87,6 @@ def _fused_policy(actor, dev, precision: str = "fp32", observe: bool = False, ms
     return cached[1]
 
 
-def _exchange_check(env) -> None:
-    """Sharded houses through sharding.MailboxExchange: raise if a wait inside a mailbox launch gave up (synchronises)."""
-    check = getattr(env, "_exchange_check", None)
-    if check is not None:
-        check()
-
-
 def _observe_act_supported(env, actor) -> bool:
     """Can ``FusedActor.sample_env`` serve this env / actor?  At most 13 senders (fewer than the houses) - the circular neighbours,
     a link table or random_sample - with 4-field messages, any of the optional STATE columns, link defects, at most 64 features,
@@ -257,7 +250,7 @@ def collect_ppo_rollout(env, actor: nn.Module, nb_steps: int, gamma: float = 0.9
         bootstrap[T - 1] = critic(obs).squeeze(1)
     out = {"action": action, "a_prob": a_prob, "reward": reward, "done": done,
            "return": discounted_returns(reward, done, gamma, bootstrap)}
-    _exchange_check(env)
+    env._exchange_check()
     if store_states:
         out["state"] = states
     if with_others_actions:
@@ -316,7 +309,7 @@ def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float
         if not one_kernel or t == T - 1:
             env.obs_vector("rows", out=state[t + 1].view(E, N, F_len))
         eps = max(eps * float(epsilon_decay), float(min_epsilon))
-    _exchange_check(env)
+    env._exchange_check()
     return {"state": state, "action": action, "reward": reward, "explored": explored, "epsilon": eps}
 
 
@@ -402,7 +395,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     if not use_graph or nb_steps < 3:
         for t in range(nb_steps):
             one_step(0 if graph_mode else t)
-        _exchange_check(env)
+        env._exchange_check()
         return out
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))

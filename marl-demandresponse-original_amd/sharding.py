@@ -115,10 +115,156 @@ def np_contig(a):
     return np.ascontiguousarray(a)
 
 
-class TorchDistExchange:
-    """The exchanges of the sharded-houses layout over torch.distributed (RCCL on the GPU box, gloo in CPU tests):
-    one SUM all-reduce of `max_power` per episode and ONE all-gather of the per-workgroup partial records per step."""
+# Kinds of a mailbox's error word {tag << 32 | kind << 28 | workgroup} (csrc/mdr_mailbox.h)
+MAILBOX_ERRORS = {1: "a house workgroup waited too long for the totals of a step", 2: "a reducer waited too long for a step's records",
+                  3: "a house workgroup of a mailbox step waited too long for the totals",
+                  4: "the reducer of a mailbox step waited too long for a step's records",
+                  5: "a halo pull waited too long for a peer's message records"}
 
+
+def decode_error_word(word: int) -> Tuple[int, int, int, str]:
+    """(step tag, kind, workgroup, what gave up) of a mailbox error word."""
+    kind = (word >> 28) & 0xF
+    return (word >> 32) & 0xFFFFFFFF, kind, word & 0x0FFFFFFF, MAILBOX_ERRORS.get(kind, "kind %d" % kind)
+
+
+class Mailboxes:
+    """This rank's mailbox and its peers' for one env (`env._mailboxes`, built by `open_mailboxes`): the mdr_mailbox_t the mailbox
+    launches take (`mb`), every rank's box address (`boxes`; this rank's is `own`), the tensor behind `own` when it is plain device
+    memory (`mem`, freed with the env), and the halo region's capacity in floats with the count of halo exchanges so far."""
+
+    def __init__(self, env, mb, boxes, mem=None, halo_capacity: int = 0):
+        self.mb, self.boxes, self.own, self.mem = mb, boxes, boxes[mb.rank], mem
+        self.halo_capacity, self.halo_tag, self.halo_keep = int(halo_capacity), 0, None
+        self._lib, self.device = env._lib, env.device
+
+    def status(self) -> int:
+        """Word 0 of this rank's box once the device has drained (0: no wait inside a mailbox launch gave up)."""
+        import ctypes as C
+        import torch
+        from . import _native as nat
+        word = C.c_uint64()
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize(self.device)
+            nat.check(self._lib, None, self._lib.mdr_mailbox_peek(C.c_void_p(self.own), C.byref(word)), "mdr_mailbox_peek")
+        return int(word.value)
+
+
+def open_mailboxes(env, records: Sequence[int], rank: int, group=None, plain: bool = False, co_resident: int = 1,
+                   halo: int = 0) -> Mailboxes:
+    """This rank's mailbox for `env`, zero-filled, with a region of `halo` floats behind the step region - `plain`: torch device
+    memory; else mdr_mailbox_alloc, fine-grained (unless MDR_MAILBOX_COARSE=1) so that a peer device's stores become visible inside
+    the running kernel - and, in a world > 1, its peers': the 64-byte inter-process handles travel through one all_gather_object of
+    `group`, every rank maps the others' boxes, and a barrier holds everyone until every mapping exists.  `records[r]`: rank r's
+    records per env and step (env.persist_records of its houses)."""
+    import ctypes as C
+    import os
+    import torch
+    from . import _native as nat
+    lib, world = env._lib, len(records)
+    if world > nat.MDR_MAX_SHARDS:
+        raise ValueError("the mailbox exchange serves at most %d shards" % nat.MDR_MAX_SHARDS)
+    stride = max(records)
+    nbytes = int(lib.mdr_mailbox_bytes(env.nb_envs, world, stride)) + int(lib.mdr_mailbox_halo_bytes(world, halo))
+    mem, boxes = None, [None] * world
+    with torch.cuda.device(env.device):
+        if plain:
+            mem = torch.zeros(nbytes // 8, dtype=torch.int64, device=env.device)
+            own = mem.data_ptr()
+        else:
+            ptr = C.c_void_p()
+            fine = 0 if os.environ.get("MDR_MAILBOX_COARSE") == "1" else 1
+            nat.check(lib, None, lib.mdr_mailbox_alloc(nbytes, fine, C.byref(ptr)), "mdr_mailbox_alloc")
+            own = ptr.value
+        if world > 1:
+            import torch.distributed as dist
+            handle = C.create_string_buffer(64)
+            nat.check(lib, None, lib.mdr_mailbox_export(C.c_void_p(own), handle), "mdr_mailbox_export")
+            handles = [None] * world
+            dist.all_gather_object(handles, bytes(handle.raw), group=group)
+            for r in range(world):
+                if r != rank:
+                    peer = C.c_void_p()
+                    nat.check(lib, None, lib.mdr_mailbox_open(handles[r], C.byref(peer)), "mdr_mailbox_open")
+                    boxes[r] = peer.value
+        boxes[rank] = own
+    mb = nat.MdrMailbox()
+    mb.struct_size = C.sizeof(nat.MdrMailbox)
+    mb.world, mb.rank, mb.records_per_env, mb.co_resident = world, rank, stride, int(co_resident)
+    mb.system_scope = 1 if world > 1 else 0
+    for r in range(world):
+        mb.records[r] = records[r]
+        mb.boxes[r] = boxes[r]
+    if world > 1:
+        dist.barrier(group=group)      # nobody pushes before every mapping exists
+    return Mailboxes(env, mb, boxes, mem, halo)
+
+
+class Exchange:
+    """What BatchedDemandResponseEnv asks of the object that carries the exchanges of the sharded-houses layout (its `exchange=`
+    argument; TorchDistExchange over `process_group` by default).  The six methods are the exchanges; the attributes and `mailboxes`
+    say how the env may drive them."""
+
+    capturable = False       # may the exchanges sit inside a hipGraph capture (`rollout` in graph mode)?
+    mailbox_steps = False    # True: the env hands every step to `step_mailbox(env, ptr, source)` - one launch, no gather_partials
+
+    def agree_partial_records(self, env) -> None:
+        """Once per env: raise the record stride of `partials` to what every rank gathers (env._grow_partials)."""
+        raise NotImplementedError
+
+    def sum_max_power(self, env) -> None:
+        """SUM of env.t['max_power'] over the ranks, once per episode."""
+        raise NotImplementedError
+
+    def sum_base_power(self, env) -> None:
+        """SUM of env.t['base_power'] over the ranks (interpolated base power)."""
+        raise NotImplementedError
+
+    def gather_partials(self, env):
+        """Every rank's `partials` [E][R][3] on every rank: ([world][E][R][3], world)."""
+        raise NotImplementedError
+
+    def ranges(self, env):
+        """([(house_offset, nb_houses)] of every rank, this rank's index)."""
+        raise NotImplementedError
+
+    def gather_messages(self, env, padded):
+        """This rank's export records [E, export_max, mf] -> every rank's [world, E, export_max, mf]."""
+        raise NotImplementedError
+
+    def mailboxes(self, env) -> Optional[Mailboxes]:
+        """The mailboxes `rollout_persistent` exchanges through across the ranks, or None (then only an env that holds every house
+        runs it, with a box of its own)."""
+        return None
+
+
+class PlainExchange(Exchange):
+    """A plain object with the exchange methods but without the Exchange base (a stand-in of one's own) under the base's
+    defaults: the records path, not capturable, no mailboxes.  BatchedDemandResponseEnv._exchange wraps such an object once."""
+
+    def __init__(self, impl):
+        self.impl = impl
+
+    def agree_partial_records(self, env) -> None:
+        self.impl.agree_partial_records(env)
+
+    def sum_max_power(self, env) -> None:
+        self.impl.sum_max_power(env)
+
+    def sum_base_power(self, env) -> None:
+        self.impl.sum_base_power(env)
+
+    def gather_partials(self, env):
+        return self.impl.gather_partials(env)
+
+    def ranges(self, env):
+        return self.impl.ranges(env)
+
+    def gather_messages(self, env, padded):
+        return self.impl.gather_messages(env, padded)
+
+
+class TorchDistExchange(Exchange):
     @property
     def capturable(self) -> bool:
         """May its collectives sit inside a hipGraph capture?  RCCL's may (BatchedDemandResponseEnv.rollout captures begin -
@@ -128,7 +274,6 @@ class TorchDistExchange:
 
     def __init__(self, process_group=None):
         self.process_group = process_group
-        self._gathered = None
         self._records = None
 
     def agree_partial_records(self, env) -> None:
@@ -181,68 +326,18 @@ class TorchDistExchange:
         dist.all_gather_into_tensor(out.view(world * padded.shape[0], padded.shape[1], padded.shape[2]), padded, group=self.process_group)
         return out
 
-    def persist_mailbox(self, env, spin_limit: int = 0):
-        """The mailboxes of the persistent rollout (mdr_env_rollout_persistent) across processes: every rank allocates its own
-        (zero-filled, fine-grained so that a peer device's stores become visible inside the running kernel), the 64-byte
-        inter-process handles travel through one all_gather_object, and every rank maps its peers' boxes.  Done once per env;
-        returns (mdr_mailbox_t, address of this rank's box)."""
-        import ctypes as C
-        import os
-        import torch.distributed as dist
-        from . import _native as nat
-        cached = getattr(env, "_persist_dist", None)
-        if cached is not None:
-            cached[0].spin_limit = int(spin_limit)
-            return cached[0], cached[1]
-        lib = env._lib
-        world, rank = dist.get_world_size(self.process_group), dist.get_rank(self.process_group)
-        if world > nat.MDR_MAX_SHARDS:
-            raise ValueError("the mailbox exchange serves at most %d shards" % nat.MDR_MAX_SHARDS)
-        ranges, _ = self.ranges(env)
-        recs = [env.persist_records(cnt) for _, cnt in ranges]
-        stride = max(recs)
-        nbytes = int(lib.mdr_mailbox_bytes(env.nb_envs, world, stride))
-        own = C.c_void_p()
-        import torch
-        with torch.cuda.device(env.device):
-            fine = 0 if os.environ.get("MDR_MAILBOX_COARSE") == "1" else 1
-            nat.check(lib, None, lib.mdr_mailbox_alloc(nbytes, fine, C.byref(own)), "mdr_mailbox_alloc")
-            handle = C.create_string_buffer(64)
-            boxes = [None] * world
-            if world > 1:
-                nat.check(lib, None, lib.mdr_mailbox_export(own, handle), "mdr_mailbox_export")
-                handles = [None] * world
-                dist.all_gather_object(handles, bytes(handle.raw), group=self.process_group)
-                for r in range(world):
-                    if r == rank:
-                        continue
-                    peer = C.c_void_p()
-                    nat.check(lib, None, lib.mdr_mailbox_open(handles[r], C.byref(peer)), "mdr_mailbox_open")
-                    boxes[r] = peer.value
-            boxes[rank] = own.value
-        mb = nat.MdrMailbox()
-        mb.struct_size = C.sizeof(nat.MdrMailbox)
-        mb.world, mb.rank, mb.records_per_env, mb.co_resident, mb.spin_limit = world, rank, stride, 1, int(spin_limit)
-        # ranks of one device (the one-GPU rehearsal) crowd the same compute units: count them all for the residency check
-        mb.co_resident = int(os.environ.get("MDR_MAILBOX_CO_RESIDENT", "1"))
-        mb.system_scope = 1 if world > 1 else 0
-        for r in range(world):
-            mb.records[r] = recs[r]
-            mb.boxes[r] = boxes[r]
-        if world > 1:
-            dist.barrier(group=self.process_group)      # nobody pushes before every mapping exists
-        env._persist_dist = (mb, own.value, boxes)
-        return mb, own.value
+    def mailboxes(self, env) -> Mailboxes:
+        """The mailboxes of the persistent rollout across the ranks (mdr_mailbox_alloc at every world); built at the first call."""
+        if env._mailboxes is None:
+            env._mailboxes = self._open_mailboxes(env)
+        return env._mailboxes
 
-    def gather_totals(self, env):
-        import torch
-        import torch.distributed as dist
-        world = dist.get_world_size(self.process_group)
-        if self._gathered is None or self._gathered.shape[0] != world:
-            self._gathered = torch.empty((world, 3, env.nb_envs), dtype=torch.float64, device=env.device)
-        # concatenation form [world * 3, E] (same memory as [world][3][E]): accepted by RCCL and by gloo alike
-        dist.all_gather_into_tensor(self._gathered.view(world * 3, env.nb_envs), env.t["tot"], group=self.process_group)
-        return self._gathered, world
+    def _open_mailboxes(self, env, plain: bool = False, halo: int = 0) -> Mailboxes:
+        import os
+        ranges, rank = self.ranges(env)
+        # ranks of one device (the one-GPU rehearsal) crowd the same compute units: count them all for the residency check
+        return open_mailboxes(env, [env.persist_records(cnt) for _, cnt in ranges], rank, self.process_group, plain=plain,
+                              co_resident=int(os.environ.get("MDR_MAILBOX_CO_RESIDENT", "1")), halo=halo)
 
 
 class MailboxExchange(TorchDistExchange):
@@ -267,6 +362,7 @@ class MailboxExchange(TorchDistExchange):
         self.timeout_us = max(1, min(int(round(float(timeout_ms) * 1000.0)), 0xFFFFFFFF))
 
     capturable = False
+    mailbox_steps = True
 
     @staticmethod
     def _dist(group):
@@ -280,7 +376,7 @@ class MailboxExchange(TorchDistExchange):
         return dist.get_world_size(self.process_group), dist.get_rank(self.process_group)
 
     def _check_env(self, env):
-        if isinstance(getattr(env, "_exchange_impl", None), LocalShardGroup):
+        if isinstance(env._exchange_impl, LocalShardGroup):
             raise RuntimeError("MailboxExchange does not serve a LocalShardGroup: its shards share one process's hardware queues, on "
                                "which spinning launches serialise")
 
@@ -289,7 +385,7 @@ class MailboxExchange(TorchDistExchange):
         self._check_env(env)
         if self._dist(self.process_group)[0]:
             super().agree_partial_records(env)
-        self.persist_mailbox(env)       # once per env: allocation, handles, mapping, barrier - never on the step path
+        self.mailboxes(env)             # once per env: allocation, handles, mapping, barrier - never on the step path
 
     def sum_max_power(self, env) -> None:
         if self._dist(self.process_group)[0]:
@@ -314,94 +410,29 @@ class MailboxExchange(TorchDistExchange):
         mf = int(env._lib.mdr_obs_message_fields(C.byref(spec)))
         return env.nb_envs * plan.export_max * mf
 
-    def persist_mailbox(self, env, spin_limit: int = 0):
-        """This rank's mailbox and its peers' (allocate zero-filled, export, open, barrier - the sequence of
-        TorchDistExchange.persist_mailbox), with a halo region behind the step region.  Serves the mailbox steps, the halo and
-        `rollout_persistent`; done once per env.  Returns (mdr_mailbox_t, address of this rank's box)."""
-        import ctypes as C
-        import os
-        import torch
-        from . import _native as nat
-        cached = getattr(env, "_persist_dist", None)
-        if cached is not None:
-            cached[0].spin_limit = int(spin_limit)
-            return cached[0], cached[1]
-        self._check_env(env)
-        lib = env._lib
-        world, rank = self._world_rank()
-        if world > nat.MDR_MAX_SHARDS:
-            raise ValueError("the mailbox exchange serves at most %d shards" % nat.MDR_MAX_SHARDS)
-        ranges, _ = self.ranges(env)
-        recs = [env.persist_records(cnt) for _, cnt in ranges]
-        stride = max(recs)
-        step_bytes = int(lib.mdr_mailbox_bytes(env.nb_envs, world, stride))
-        # the halo region: sized for this episode's exchange with room to spare (a 'random_fixed' episode re-draws its links); an
-        # exchange that outgrows it, or would exceed HALO_CAP_BYTES, keeps the all-gather - every rank decides alike
-        halo = 0
-        if world > 1:
-            need = self._halo_floats(env)
-            halo = 2 * need if int(lib.mdr_mailbox_halo_bytes(world, 2 * need)) <= self.HALO_CAP_BYTES else 0
-        nbytes = step_bytes + int(lib.mdr_mailbox_halo_bytes(world, halo))
-        boxes = [None] * world
-        with torch.cuda.device(env.device):
-            if world == 1:      # one device, one process: plain device memory, freed with the env
-                env._mailbox_mem = torch.zeros(nbytes // 8, dtype=torch.int64, device=env.device)
-                own = env._mailbox_mem.data_ptr()
-            else:
-                _, dist = self._dist(self.process_group)
-                ptr = C.c_void_p()
-                fine = 0 if os.environ.get("MDR_MAILBOX_COARSE") == "1" else 1
-                nat.check(lib, None, lib.mdr_mailbox_alloc(nbytes, fine, C.byref(ptr)), "mdr_mailbox_alloc")
-                own = ptr.value
-                handle = C.create_string_buffer(64)
-                nat.check(lib, None, lib.mdr_mailbox_export(C.c_void_p(own), handle), "mdr_mailbox_export")
-                handles = [None] * world
-                dist.all_gather_object(handles, bytes(handle.raw), group=self.process_group)
-                for r in range(world):
-                    if r != rank:
-                        peer = C.c_void_p()
-                        nat.check(lib, None, lib.mdr_mailbox_open(handles[r], C.byref(peer)), "mdr_mailbox_open")
-                        boxes[r] = peer.value
-            boxes[rank] = own
-        mb = nat.MdrMailbox()
-        mb.struct_size = C.sizeof(nat.MdrMailbox)
-        mb.world, mb.rank, mb.records_per_env, mb.spin_limit = world, rank, stride, int(spin_limit)
-        mb.co_resident = int(os.environ.get("MDR_MAILBOX_CO_RESIDENT", "1"))
-        mb.system_scope = 1 if world > 1 else 0
-        for r in range(world):
-            mb.records[r] = recs[r]
-            mb.boxes[r] = boxes[r]
-        if world > 1:
-            self._dist(self.process_group)[1].barrier(group=self.process_group)      # nobody pushes before every mapping exists
-        env._persist_dist = (mb, own, boxes)
-        env._mailbox_addr = own
-        env._halo_capacity = halo
-        env._halo_tag = 0
-        return mb, own
+    def mailboxes(self, env) -> Mailboxes:
+        """This rank's mailbox and its peers' (open_mailboxes; plain device memory in a world of one) with a halo region behind the
+        step region.  Serves the mailbox steps, the halo and `rollout_persistent`; built once per env, at its first episode."""
+        if env._mailboxes is None:
+            self._check_env(env)
+            world = self._world_rank()[0]
+            # the halo region: sized for this episode's exchange with room to spare (a 'random_fixed' episode re-draws its links); an
+            # exchange that outgrows it, or would exceed HALO_CAP_BYTES, keeps the all-gather - every rank decides alike
+            halo = 2 * self._halo_floats(env) if world > 1 else 0
+            if int(env._lib.mdr_mailbox_halo_bytes(world, halo)) > self.HALO_CAP_BYTES:
+                halo = 0
+            env._mailboxes = self._open_mailboxes(env, plain=world == 1, halo=halo)
+        return env._mailboxes
 
     def step_mailbox(self, env, ptr, source) -> None:
         """One step of this rank's shard: ONE launch, the exchange through the mailboxes."""
         import ctypes as C
         import torch
         from . import _native as nat
-        mb = self.persist_mailbox(env)[0]
+        mb = self.mailboxes(env).mb
         with torch.cuda.device(env.device):
             rc = env._lib.mdr_env_step_mailbox(env._handle, C.c_void_p(ptr), source, C.byref(mb), self.timeout_us, env._stream())
             nat.check(env._lib, env._handle, rc, "mdr_env_step_mailbox")
-
-    def status(self, env) -> int:
-        """Word 0 of this rank's mailbox after the stream has drained (0: no wait gave up)."""
-        import ctypes as C
-        import torch
-        from . import _native as nat
-        cached = getattr(env, "_persist_dist", None)
-        if cached is None:
-            return 0
-        word = C.c_uint64()
-        with torch.cuda.device(env.device):
-            torch.cuda.synchronize(env.device)
-            nat.check(env._lib, None, env._lib.mdr_mailbox_peek(C.c_void_p(cached[1]), C.byref(word)), "mdr_mailbox_peek")
-        return int(word.value)
 
     def gather_messages(self, env, padded):
         """`padded`: this rank's export records [E, export_max, mf] -> every rank's [world, E, export_max, mf], pushed into and
@@ -416,24 +447,24 @@ class MailboxExchange(TorchDistExchange):
         if world == 1:
             out[0].copy_(padded)
             return out
-        mb = self.persist_mailbox(env)[0]
+        boxes = self.mailboxes(env)
         count = padded.numel()
-        if count > env._halo_capacity:
+        if count > boxes.halo_capacity:
             return super().gather_messages(env, padded)
         src = padded.contiguous()
-        env._halo_tag += 1
-        tag = env._halo_tag
+        boxes.halo_tag += 1
+        tag, mb = boxes.halo_tag, boxes.mb
         with torch.cuda.device(env.device):
             st = env._stream()
             nat.check(env._lib, None, env._lib.mdr_mailbox_halo_push(C.byref(mb), env.nb_envs, C.c_void_p(src.data_ptr()), count, tag, st),
                       "mdr_mailbox_halo_push")
             nat.check(env._lib, None, env._lib.mdr_mailbox_halo_pull(C.byref(mb), env.nb_envs, C.c_void_p(out.data_ptr()), count, tag,
                                                                      self.timeout_us, st), "mdr_mailbox_halo_pull")
-        env._halo_keep = src        # alive until the push has read it (the stream orders every later use)
+        boxes.halo_keep = src       # alive until the push has read it (the stream orders every later use)
         return out
 
 
-class LocalShardGroup:
+class LocalShardGroup(Exchange):
     """All house shards of the same envs driven from ONE process: `nb_shards` BatchedDemandResponseEnv objects, spread
     round-robin over `devices` (a single device rehearses BASELINE config 5's eight 125,000-house shards on one GPU).
     The per-step exchange is a stack of the shards' partial-record blocks copied to each shard's device - the peer-copy
@@ -462,7 +493,7 @@ class LocalShardGroup:
     def sum_max_power(self, env):
         raise RuntimeError("shards of a LocalShardGroup are stepped through the group, not one by one")
 
-    gather_totals = gather_partials = sum_base_power = sum_max_power
+    gather_partials = sum_base_power = sum_max_power
 
     def agree_partial_records(self, env):
         pass                                             # the constructor gave every shard the largest shard's count

@@ -202,23 +202,23 @@ def test_a_missing_peer_ends_in_an_error_word_not_a_hang():
     word (kind 3 / 4: the step path) lands in both mailboxes, the env keeps its state, and later launches write nothing."""
     import mdr_amd
     from mdr_amd import _native as nat
-    from mdr_amd.sharding import MailboxExchange
+    from mdr_amd.sharding import MailboxExchange, Mailboxes
     N = 12000
     env = mdr_amd.BatchedDemandResponseEnv(_cfg(N), nb_envs=1, device="cuda:0", seed=3, house_shard=(0, N), exchange_always=True,
                                            exchange=MailboxExchange(timeout_ms=5))
     env.reset(episode=0)
-    mb, own, boxes = env._persist_dist
-    ghost = torch.zeros_like(env._mailbox_mem)
+    one = env._mailboxes
+    ghost = torch.zeros_like(one.mem)
     two = nat.MdrMailbox()
-    C.memmove(C.byref(two), C.byref(mb), C.sizeof(nat.MdrMailbox))
+    C.memmove(C.byref(two), C.byref(one.mb), C.sizeof(nat.MdrMailbox))
     two.world = 2
-    two.records[1] = mb.records[0]
+    two.records[1] = one.mb.records[0]
     two.boxes[1] = ghost.data_ptr()
-    env._persist_dist = (two, own, [own, ghost.data_ptr()])
+    env._mailboxes = Mailboxes(env, two, [one.own, ghost.data_ptr()], one.mem)
     before = {k: env.t[k].clone() for k in ("Ta", "Tm", "sso", "flags", "reward")}
     act = torch.ones((1, N), dtype=torch.uint8, device="cuda:0")
     env.step(act)                                     # returns; the wait inside is bounded
-    word = env._exchange().status(env)
+    word = env.persist_status()
     assert word != 0
     assert (word >> 28) & 0xF in (3, 4)
     assert int(ghost[0].item()) != 0                  # the peer is told as well

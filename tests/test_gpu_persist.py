@@ -167,28 +167,29 @@ def test_a_missing_peer_ends_in_an_error_word_not_a_hang():
     buffers still hold the state before the launch (nothing is written back)."""
     import mdr_amd
     from mdr_amd import _native as nat
+    from mdr_amd.sharding import Mailboxes
     N = 12000
     env = mdr_amd.BatchedDemandResponseEnv(_cfg(2 * N), nb_envs=1, device="cuda:0", seed=3, house_shard=(0, N))
     env._exchange_impl = _OneShard(env)
     env.reset(episode=0)
     before = {k: env.t[k].clone() for k in ("Ta", "Tm", "sso", "flags", "reward")}
     n = env.persist_records()
-    box = env._persist_mailbox(2, n)
+    box = torch.zeros(int(env._lib.mdr_mailbox_bytes(env.nb_envs, 2, n)) // 8, dtype=torch.int64, device="cuda:0")
     ghost = torch.zeros_like(box)
     mb = nat.MdrMailbox()
     mb.struct_size = C.sizeof(nat.MdrMailbox)
-    mb.world, mb.rank, mb.records_per_env, mb.co_resident, mb.spin_limit = 2, 0, n, 1, 2000
+    mb.world, mb.rank, mb.records_per_env, mb.co_resident = 2, 0, n, 1
     mb.records[0] = mb.records[1] = n
     mb.boxes[0], mb.boxes[1] = box.data_ptr(), ghost.data_ptr()
-    env._persist_call(8, mb, False, True)
+    env._mailboxes = Mailboxes(env, mb, [box.data_ptr(), ghost.data_ptr()], box)
+    with pytest.raises(RuntimeError, match="gave up"):
+        env.rollout_persistent(8, spin_limit=2000)
     word = env.persist_status()
     assert word != 0
     assert (word >> 28) & 0xF in (1, 2)
     assert int(ghost[0].item()) != 0          # the peer is told as well
     for k, v in before.items():
         assert torch.equal(env.t[k], v), k
-    with pytest.raises(RuntimeError, match="gave up"):
-        env._persist_raise(word)
 
 
 def test_a_grid_that_cannot_be_resident_is_refused():
