@@ -92,7 +92,10 @@ int64_t mdr_actor_frag1_floats(int32_t layout, int32_t num_state);  /* size of f
 int64_t mdr_actor_frag2_floats(int32_t layout, int32_t hidden1);    /* size of frag2 in 4-byte units */
 
 /* For every agent a < nb_agents: probs = softmax(actor(obs[a])), u = Philox4x32-10(key = seed, counter = (a, step, stream))
- * uniform in (0,1), action = u < probs[0] ? 0 : 1  (Categorical(probs).sample()), a_prob = probs[action].
+ * uniform in (0,1), action = u < probs[0] ? 0 : 1  (Categorical(probs).sample()), a_prob = probs[action].  The counter is (a low word,
+ * a high word, step low word + *step_dev, TAG_ACTION ^ step high word), u = min(((float)(x >> 8) + 0.5f) * 2^-24, 0x1.fffffep-1f) of
+ * the first output word x: the clamp keeps the top cell (x >> 8 == 0xFFFFFF, whose centre rounds to 1.0f) below 1, so an action of
+ * probability 0 is never drawn.  `step_dev` is added to the low word of `step` modulo 2^32 and does not carry into the high word.
  * `obs`: observation rows [nb_agents][F] when obs_plane_stride == 0 (mdr_env_obs_vector MDR_OBS_ROWS), or feature planes
  * [F][obs_plane_stride] with obs_plane_stride >= nb_agents (MDR_OBS_PLANES: the lanes of a wavefront then read consecutive
  * floats instead of one cache line each).  `action` uint8 [nb_agents], `a_prob` float [nb_agents] (may be NULL), `probs`

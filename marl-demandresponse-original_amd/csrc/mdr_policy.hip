@@ -71,6 +71,21 @@ __device__ __forceinline__ int tile_local(int x) {
   return x;
 }
 
+// The draw behind an agent's action (include/mdr_policy.h), the one place every actor kernel takes it from: word 0 of
+// Philox4x32-10 with key = seed and counter = (agent lo, agent hi, step lo + *step_dev, TAG_ACTION ^ step hi).  `agent` is the index
+// in the whole batch.  The device-side step is added to the low word only (mod 2^32, no carry into the high word).
+__device__ __forceinline__ uint32_t action_bits(const ActorArgs& a, int64_t agent) {
+  return philox4x32_10((uint32_t)agent, (uint32_t)((uint64_t)agent >> 32), a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u),
+                       TAG_ACTION ^ a.step_hi, loop_local(a.k0), loop_local(a.k1)).x;
+}
+
+// ... and its uniform in (0,1): the centre of one of 2^24 cells.  The top cell's centre, 16777215.5, is no fp32 number and ties to
+// 2^24, i.e. u = 1.0f, which `u < p0` fails even for p0 == 1.0f (an action of probability 0); the clamp maps that one cell to the
+// largest float below 1 and changes no other draw.
+__device__ __forceinline__ float action_uniform(uint32_t bits) {
+  return fminf(((float)(bits >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+}
+
 // max(x, 0) in ONE instruction: on the bit pattern, as a signed integer (v_max_i32) - every negative float, -0 included, is a
 // negative integer, every non-negative float keeps its bits.  fmaxf costs a canonicalising v_max_f32 x, x before the v_max_f32
 // x, 0, and hipcc folds v_med3_f32(x, 0, inf) into that very pair (r02: 2442 relus of this file compiled to 4884 v_max_f32).
@@ -183,8 +198,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_actor_sample(ActorArgs a) {
     const float p0 = 1.0f / (1.0f + expf(-d));
     const float p1 = 1.0f / (1.0f + expf(d));
     if (h == 0 && valid) {
-      const u32x4 rnd = philox4x32_10((uint32_t)agent, (uint32_t)((uint64_t)agent >> 32), a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u), TAG_ACTION ^ a.step_hi, loop_local(a.k0), loop_local(a.k1));
-      const float u = ((float)(rnd.x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+      const uint32_t rnd = action_bits(a, agent);
+      const float u = action_uniform(rnd);
       const int act = a.greedy ? (d >= 0.0f ? 0 : 1) : (u < p0 ? 0 : 1);   // argmax keeps the first maximum, as torch.argmax
       a.action[agent] = (uint8_t)act;
       if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
@@ -283,7 +298,7 @@ __global__ __launch_bounds__(64 * WAVES16) void k_actor_sample16(ActorArgs a) {
     const bool valid = agent < a.A;
     if ((it & 3) == 0) {
       const int64_t ag = a.agent0 + (t + tile_local(g) * nwaves) * 16 + r;
-      rnd = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u), TAG_ACTION ^ a.step_hi, loop_local(a.k0), loop_local(a.k1)).x;
+      rnd = action_bits(a, ag);
     }
     f32x4 acc[MB];
 #pragma unroll
@@ -336,7 +351,7 @@ __global__ __launch_bounds__(64 * WAVES16) void k_actor_sample16(ActorArgs a) {
     const float p1 = e > 1e30f ? 1.0f : e * p0;
     const uint32_t draw = (uint32_t)__shfl((int)rnd, r + 16 * (it & 3));   // the group that drew for this tile
     if (g == 0 && valid) {
-      const float u = ((float)(draw >> 8) + 0.5f) * (1.0f / 16777216.0f);
+      const float u = action_uniform(draw);
       const int act = a.greedy ? (d >= 0.0f ? 0 : 1) : (u < p0 ? 0 : 1);   // argmax keeps the first maximum, as torch.argmax
       a.action[agent] = (uint8_t)act;
       if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
@@ -444,8 +459,7 @@ __global__ __launch_bounds__(64 * WAVESB) void k_actor_sample_bf16(ActorArgs a) 
 #pragma unroll
       for (int c = 0; c < NCB; ++c) {
         const int64_t ag = ((t + tile_local(g) * nwaves) * NCB + c) * 16 + r;
-        rnd[c] = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u),
-                               TAG_ACTION ^ a.step_hi, loop_local(a.k0), loop_local(a.k1)).x;
+        rnd[c] = action_bits(a, ag);
       }
     }
     f32x4 acc[NCB][MB];
@@ -573,7 +587,7 @@ __global__ __launch_bounds__(64 * WAVESB) void k_actor_sample_bf16(ActorArgs a) 
       const float p1 = e > 1e30f ? 1.0f : e * p0;
       const uint32_t draw = (uint32_t)__shfl((int)rnd[c], r + 16 * (it & 3));   // the group that drew for this tile
       if (g == 0 && valid) {
-        const float u = ((float)(draw >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float u = action_uniform(draw);
         const int act = a.greedy ? (d >= 0.0f ? 0 : 1) : (u < p0 ? 0 : 1);   // argmax keeps the first maximum, as torch.argmax
         a.action[agent] = (uint8_t)act;
         if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
@@ -1156,8 +1170,7 @@ __global__ __launch_bounds__(64 * WAVESB) void k_actor_observe_bf16(ActorArgs a,
 #pragma unroll
       for (int c = 0; c < NCB; ++c) {
         const int64_t ag = (((int64_t)t + (int64_t)tile_local(g) * nwaves) * NCB + c) * 16 + r;
-        rnd[c] = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u),
-                               TAG_ACTION ^ a.step_hi, loop_local(a.k0), loop_local(a.k1)).x;
+        rnd[c] = action_bits(a, ag);
       }
     }
     // the next tile's compact state: issued now, consumed between the k-steps of layer 2
@@ -1250,7 +1263,7 @@ __global__ __launch_bounds__(64 * WAVESB) void k_actor_observe_bf16(ActorArgs a,
       const float p1 = e > 1e30f ? 1.0f : e * p0;
       const uint32_t draw = (uint32_t)__shfl((int)rnd[c], r + 16 * (it & 3));
       if (g == 0 && valid) {
-        const float u = ((float)(draw >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float u = action_uniform(draw);
         const int act = a.greedy ? (d >= 0.0f ? 0 : 1) : (u < p0 ? 0 : 1);
         a.action[agent] = (uint8_t)act;
         if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
@@ -1351,7 +1364,7 @@ __global__ __launch_bounds__(64 * (EXTK ? WAVES16_EXT : WAVES16)) void k_actor_o
     const bool valid = agent < a.A;
     if ((it & 3) == 0) {
       const int64_t ag = (t + tile_local(g) * nwaves) * 16 + r;
-      rnd = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u), TAG_ACTION ^ a.step_hi, loop_local(a.k0), loop_local(a.k1)).x;
+      rnd = action_bits(a, ag);
     }
     const bool more = t + nwaves < a.ntiles;
     tc.next();
@@ -1413,7 +1426,7 @@ __global__ __launch_bounds__(64 * (EXTK ? WAVES16_EXT : WAVES16)) void k_actor_o
     const float p1 = e > 1e30f ? 1.0f : e * p0;
     const uint32_t draw = (uint32_t)__shfl((int)rnd, r + 16 * (it & 3));
     if (g == 0 && valid) {
-      const float u = ((float)(draw >> 8) + 0.5f) * (1.0f / 16777216.0f);
+      const float u = action_uniform(draw);
       const int act = a.greedy ? (d >= 0.0f ? 0 : 1) : (u < p0 ? 0 : 1);
       a.action[agent] = (uint8_t)act;
       if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
