@@ -139,6 +139,40 @@ int mdr_env_actor_sample_links(mdr_env_t *env, const mdr_obs_spec_t *spec, const
 int mdr_discounted_returns(const float *reward, const uint8_t *done, const float *bootstrap, float gamma, int32_t nb_steps,
                            int64_t nb_agents, float *out, void *stream);
 
+/* ---- TarMAC-PPO actor (agents/network.py:103-238, TarMAC_Comm / TarMAC_Actor): the attention and the head's last step.  The
+ * actor's five small per-agent MLPs are library GEMMs on the caller's side (mdr_amd/tarmac.py); these two kernels are what no
+ * GEMM covers. */
+enum mdr_tarmac_mode {
+  MDR_TARMAC_NEIGHBOURS = 0, /* tarmac_comm_mode "neighbours": the circular band of make_masks (network.py:146-165) */
+  MDR_TARMAC_NONE = 1        /* "none": an all-zero mask WITHOUT diagonal - the reference's 0 / 0 -> NaN -> 0: out = 0 */
+};
+
+/* Banded masked attention of TarMAC_Comm.forward (network.py:187-198) for every agent a = env * nb_houses + house at once.
+ * `query` / `key` float rows of num_key floats, `value` / `out` rows of num_value floats, each with its own leading dimension in
+ * floats (ldq, ldk, ldv, ldo): one packed projection buffer [A][K + K + V] can be handed over without copies, and `out` may be
+ * a column block of a wider buffer (the other columns are not touched).  c = min(nb_comm, nb_houses - 1); receiver r hears itself
+ * and the senders r + o (mod nb_houses) for the first c offsets of +1, -1, +2, -2, ... :
+ *   score_s = query_r . key_s / sqrt(num_key),  attn = softmax over those c + 1 senders,  out_r = sum_s attn_s value_s.
+ * The maximum subtracted inside the softmax is the band's own (the reference subtracts the maximum of the unmasked row: the same
+ * quotient except where the reference underflows to 0 / 0 -> 0).  c = 0: out = value, bit for bit.
+ * defect_prob > 0 (make_masks 159-165): sender s is silenced for every receiver but itself iff u < defect_prob in float32, u the
+ * uniform of mdr_actor_sample taken of word `hop` (0..3) of Philox4x32-10 with key = seed and counter = (s low word, s high word,
+ * step low word + *step_dev, 0x544D4331 ^ step high word), s the sender's agent index in the whole batch: one draw per env, step and
+ * hop.  defect_prob == 0 draws nothing.
+ * Limits: num_key a multiple of 4 and <= 32, num_value a multiple of 4 and <= 64, c <= 64 after the clamp (-4 otherwise); all four
+ * pointers 16-byte aligned and all leading dimensions multiples of 4 floats (-1 otherwise).  Every element of every out row is
+ * written, in mode MDR_TARMAC_NONE too.  Returns 0, or -1 / -3 / -4 with nothing launched. */
+int mdr_tarmac_comm(const float *query, int64_t ldq, const float *key, int64_t ldk, const float *value, int64_t ldv, int32_t nb_envs,
+                    int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob,
+                    uint64_t seed, uint64_t step, const int32_t *step_dev, int32_t hop, float *out, int64_t ldo, void *stream);
+
+/* The policy head's last step for two logits per agent (`logits` float [nb_agents][ld], ld >= 2, columns 0 and 1):
+ * d = l0 - l1, p0 = 1 / (1 + exp(-d)), p1 = 1 / (1 + exp(d)), then the draw, `action`, `a_prob`, `probs` and `step_dev` exactly as
+ * mdr_actor_sample: for equal probabilities the same (seed, step, agent) draws the same action.  greedy != 0: argmax, the first
+ * maximum on ties, no draw. */
+int mdr_logits_sample(const float *logits, int64_t ld, int64_t nb_agents, uint64_t seed, uint64_t step, const int32_t *step_dev,
+                      int32_t greedy, uint8_t *action, float *a_prob, float *probs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

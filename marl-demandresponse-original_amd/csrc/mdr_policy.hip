@@ -24,17 +24,18 @@
 #include "../../include/mdr.h"
 #include "../../include/mdr_policy.h"
 #include "mdr_device.h"
+#include "mdr_draw.h"
 #include "mdr_kernels.h"
 
 namespace {
 
+using mdr::action_uniform;
 using mdr::philox4x32_10;
 using mdr::u32x4;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WAVES = 8;   // per workgroup: two per SIMD, one hides the other's loads and VALU epilogue
-constexpr uint32_t TAG_ACTION = 0x41435431u;
 
 struct ActorArgs {
   const float* frag1;
@@ -55,14 +56,6 @@ struct ActorArgs {
   float* rows_out;           // observe -> act only, optional: the observation rows [A][51] in normStateDict order (the transition buffer's `state`)
 };
 
-// The Philox key of a draw, hidden from loop-invariant code motion: hipcc otherwise keeps the ten round keys (k + n W) of both
-// words in 20 scalar registers for the whole kernel - beyond the scalar file, so they are parked in the lanes of a vector
-// register and fetched back one v_readlane at a time.  Re-deriving them where a draw is made is 20 scalar adds.
-__device__ __forceinline__ uint32_t loop_local(uint32_t x) {
-  asm volatile("" : "+s"(x));
-  return x;
-}
-
 // A lane-dependent value hidden from loop-invariant code motion: what is derived from it (LDS addresses of the row copy, 64-bit
 // products for the Philox counter) is then re-derived where it is used - one or two vector instructions - instead of being
 // hoisted out of the tile loop into registers the loop does not have (r02: those were the kernels' scratch spills).
@@ -71,19 +64,10 @@ __device__ __forceinline__ int tile_local(int x) {
   return x;
 }
 
-// The draw behind an agent's action (include/mdr_policy.h), the one place every actor kernel takes it from: word 0 of
-// Philox4x32-10 with key = seed and counter = (agent lo, agent hi, step lo + *step_dev, TAG_ACTION ^ step hi).  `agent` is the index
-// in the whole batch.  The device-side step is added to the low word only (mod 2^32, no carry into the high word).
+// The draw behind an agent's action (include/mdr_policy.h), the one place every actor kernel takes it from: mdr_draw.h's
+// action_word on this launch's seed and step.  `agent` is the index in the whole batch.
 __device__ __forceinline__ uint32_t action_bits(const ActorArgs& a, int64_t agent) {
-  return philox4x32_10((uint32_t)agent, (uint32_t)((uint64_t)agent >> 32), a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u),
-                       TAG_ACTION ^ a.step_hi, loop_local(a.k0), loop_local(a.k1)).x;
-}
-
-// ... and its uniform in (0,1): the centre of one of 2^24 cells.  The top cell's centre, 16777215.5, is no fp32 number and ties to
-// 2^24, i.e. u = 1.0f, which `u < p0` fails even for p0 == 1.0f (an action of probability 0); the clamp maps that one cell to the
-// largest float below 1 and changes no other draw.
-__device__ __forceinline__ float action_uniform(uint32_t bits) {
-  return fminf(((float)(bits >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+  return mdr::action_word(agent, a.step_lo, a.step_hi, a.step_dev, a.k0, a.k1);
 }
 
 // max(x, 0) in ONE instruction: on the bit pattern, as a signed integer (v_max_i32) - every negative float, -0 included, is a

@@ -259,6 +259,61 @@ def collect_ppo_rollout(env, actor: nn.Module, nb_steps: int, gamma: float = 0.9
 
 
 @torch.no_grad()
+def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, critic: Optional[nn.Module] = None, seed: int = 0,
+                           store_states: bool = True) -> Dict[str, torch.Tensor]:
+    """The interaction loop of train_tarmacPPO.py:62-119 for all envs at once: every step ``env.obs_vector("rows")`` ->
+    ``TarMACActor.sample`` (TarmacPPO.select_actions, agents/tarmac_ppo.py:83-95: each agent attends to the hidden states of the other
+    agents of ITS env, hence observations as [E, N, F]) -> ``env.step``.  Same keys and flattened [T, E*N] layout as
+    ``collect_ppo_rollout``: ``state`` [T+1, E*N, F] (omitted without ``store_states``), ``action`` int64, ``a_prob``, ``reward``,
+    ``done`` (True on the last step) and ``return``; the bootstrap through ``critic`` (a ``TarMACCritic``) is its [E, N] value of the
+    last next-state (tarmac_ppo.py:136-141).  The env steps without writing its observation planes during the collection and brings
+    them up to date once at the end.  House-sharded envs are refused: attention across shards needs a halo exchange of keys and values."""
+    from .tarmac import TarMACActor
+    if not isinstance(actor, TarMACActor):
+        raise ValueError("collect_tarmac_rollout takes a TarMACActor")
+    if getattr(env, "sharded", False):
+        raise ValueError("TarMAC over house-sharded envs is not supported: the attention needs the keys and values of the neighbouring shard")
+    E, N = env.nb_envs, env.nb_houses
+    F_len = env.obs_vector_length()
+    dev = env.device
+    T = int(nb_steps)
+    states = torch.empty((T + 1, E * N, F_len), dtype=torch.float32, device=dev) if store_states else None
+    act_u8 = torch.empty((T, E * N), dtype=torch.uint8, device=dev)
+    a_prob = torch.empty((T, E * N), dtype=torch.float32, device=dev)
+    reward = torch.empty((T, E * N), dtype=torch.float32, device=dev)
+    scratch = None if store_states else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
+
+    def observe(t):
+        return env.obs_vector("rows", out=states[t].view(E, N, F_len) if store_states else scratch)
+
+    planes_were_on = bool(getattr(env, "_obs_planes_on", True))
+    if planes_were_on:
+        env.set_obs_planes(False)
+    obs = observe(0)
+    step0 = env.steps_taken
+    for t in range(T):
+        actor.sample(obs, seed, step0 + t, action=act_u8[t], a_prob=a_prob[t])
+        _, r, _, _ = env.step(act_u8[t].view(E, N))
+        reward[t] = r.reshape(-1)
+        obs = observe(t + 1)
+    if planes_were_on and not env._obs_planes_on:
+        env.set_obs_planes(True)
+    done = torch.zeros((T, E * N), dtype=torch.bool, device=dev)
+    bootstrap = None
+    if T > 0:
+        done[T - 1] = True
+        if critic is not None:
+            bootstrap = torch.zeros((T, E * N), dtype=torch.float32, device=dev)
+            bootstrap[T - 1] = critic(obs).reshape(-1)
+    out = {"action": act_u8.to(torch.int64), "a_prob": a_prob, "reward": reward, "done": done,
+           "return": discounted_returns(reward, done, gamma, bootstrap)}
+    env._exchange_check()
+    if store_states:
+        out["state"] = states
+    return out
+
+
+@torch.no_grad()
 def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float = 1.0, epsilon_decay: float = 1.0,
                             min_epsilon: float = 0.0, seed: int = 0, policy_precision: str = "fp32") -> Dict[str, torch.Tensor]:
     """The interaction loop of train_dqn.py:55-91 for all envs at once, transitions kept on the GPU: every step the epsilon-greedy
@@ -347,7 +402,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     [E, N], ``sq_temp_error_sum`` [E] (sum over steps and houses of (house_temp - target)^2), ``sq_signal_error_sum`` [E] (sum over
     steps of (reg_signal - cluster_hvac_power)^2).
 
-    ``policy``: the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
+    ``policy``: a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused), the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
     here, and observation and policy are then ONE kernel wherever ``collect_ppo_rollout`` would make them one (no observation rows at
     all) - or a ready ``FusedActor``: one packed with ``feature_order=FEATURES_OBSERVE`` takes the same one-kernel path, any other
     gets observation rows.
@@ -355,10 +410,18 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     ``use_graph`` (default: when the env was built with ``graph_mode=True``): the step is captured once in a
     ``torch.cuda.CUDAGraph`` and replayed - the launch-bound regime of small batches."""
     from .policy import FEATURES_OBSERVE
+    from .tarmac import TarMACActor
     E, N = env.nb_envs, env.nb_houses
     dev = env.device
     F_len = env.obs_vector_length()
-    if isinstance(policy, nn.Module):
+    tarmac = isinstance(policy, TarMACActor)
+    if tarmac:
+        if use_graph:
+            raise ValueError("deploy_policy runs a TarMACActor eagerly: its GEMMs and kernels are not captured")
+        if getattr(env, "sharded", False):
+            raise ValueError("TarMAC over house-sharded envs is not supported")
+        use_graph = False
+    elif isinstance(policy, nn.Module):
         if not _fusable(policy):
             raise ValueError("deploy_policy takes Linear(F,H1) - Linear(H1,H2) - Linear(H2,2) networks on the device (or a FusedActor)")
         policy = _fused_policy(policy, dev, policy_precision, observe=_observe_act_supported(env, policy),
@@ -383,6 +446,9 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     def one_step(t):
         if observe_act:      # normStateDict + act for all agents in one kernel: no observation rows
             policy.sample_env(env, seed, step0 + t, action=act, step_dev=step_dev)
+        elif tarmac:         # TarmacPPOAgent.act (agents/rl_controllers.py:86-122): the agents of an env attend to each other
+            env.obs_vector("rows", out=obs)
+            policy.sample(obs, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act)
         else:
             env.obs_vector("rows", out=obs)
             policy.sample(obs.view(E * N, F_len), seed, step0 + t, action=act, step_dev=step_dev)

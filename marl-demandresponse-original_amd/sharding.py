@@ -165,7 +165,10 @@ def open_mailboxes(env, records: Sequence[int], rank: int, group=None, plain: bo
     if world > nat.MDR_MAX_SHARDS:
         raise ValueError("the mailbox exchange serves at most %d shards" % nat.MDR_MAX_SHARDS)
     stride = max(records)
-    nbytes = int(lib.mdr_mailbox_bytes(env.nb_envs, world, stride)) + int(lib.mdr_mailbox_halo_bytes(world, halo))
+    # the kernels index records and totals by the DESCRIPTOR's world: a box opened for a world of one keeps room for a second rank's
+    # record block, so that a descriptor re-pointed at a two-rank world (a peer that never shows up: the bounded waits must end in
+    # the error word) stays inside the allocation instead of reading 8 E SLOTS stride G bytes past it
+    nbytes = int(lib.mdr_mailbox_bytes(env.nb_envs, max(world, 2), stride)) + int(lib.mdr_mailbox_halo_bytes(world, halo))
     mem, boxes = None, [None] * world
     with torch.cuda.device(env.device):
         if plain:

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""TarMAC-PPO actor: mdr_tarmac_comm alone against its traffic floor and against the dense torch attention, and its share of one full
+TarMACActor.sample step.  HIP events after warm-up; one JSON line per measurement.
+
+    python tools/bench_tarmac.py [--shapes 4096x1024,83886x50] [--iters 50] [--warmup 5] [--out FILE]
+
+Floor: 4 (2 K + 2 V) algorithmic bytes per agent (query, key, value read once, comm written once: 192 B at K = 8, V = 16) over the
+5.25 TB/s out-of-cache rate of DESIGN.md section 7.  The dense comparator is TarMAC_Comm.forward's formula (agents x agents scores,
+masked softmax, attn @ value) on the same device: on all envs where its temporaries fit, else on the largest env count that does."""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import mdr_amd  # noqa: E402
+from mdr_amd.tarmac import TarMACActor  # noqa: E402
+
+OUT_OF_CACHE_BPS = 5.25e12
+K, V, COMM, F_OBS = 8, 16, 10, 51
+DEV = "cuda:0"
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3      # us
+
+
+def dense_attention(q, k, v, mask):
+    s = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(q.shape[-1])
+    s = s - s.max(dim=-1, keepdim=True)[0]
+    e = torch.exp(s) * mask
+    a = e / e.sum(dim=-1, keepdim=True)
+    return torch.matmul(torch.where(torch.isnan(a), torch.zeros_like(a), a), v)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="4096x1024,83886x50")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_tarmac.py needs a GPU"
+    lib = mdr_amd.load_native()
+    lines = []
+
+    def emit(**rec):
+        lines.append(json.dumps(rec))
+        print(lines[-1], flush=True)
+
+    for shape in args.shapes.split(","):
+        E, N = (int(x) for x in shape.split("x"))
+        A = E * N
+        g = torch.Generator(device=DEV).manual_seed(1)
+        qkv = torch.randn((A, K + K + V), device=DEV, generator=g)
+        out = torch.empty((A, V), device=DEV)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def band():
+            rc = lib.mdr_tarmac_comm(C.c_void_p(qkv.data_ptr()), K + K + V, C.c_void_p(qkv.data_ptr() + 4 * K), K + K + V,
+                                     C.c_void_p(qkv.data_ptr() + 8 * K), K + K + V, E, N, K, V, COMM, 0, C.c_float(0.0), C.c_uint64(0),
+                                     C.c_uint64(0), None, 0, C.c_void_p(out.data_ptr()), V, stream)
+            assert rc == 0, rc
+
+        us = timed(band, args.iters, args.warmup)
+        floor_us = A * 4 * (2 * K + 2 * V) / OUT_OF_CACHE_BPS * 1e6
+        emit(what="mdr_tarmac_comm", envs=E, houses=N, agents=A, us=round(us, 2), floor_us=round(floor_us, 2), times_floor=round(us / floor_us, 3),
+             algorithmic_GBps=round(A * 4 * (2 * K + 2 * V) / us * 1e-3, 1))
+
+        # dense torch attention on the same inputs: all envs if five [E, N, N] temporaries fit in half of the free memory
+        free = torch.cuda.mem_get_info()[0]
+        E_d = int(min(E, max(1, (free // 2) // (5 * 4 * N * N))))
+        mask = TarMACActor(F_OBS).band_mask(N, DEV).float()
+        qd, kd, vd = (t.reshape(E, N, -1)[:E_d].contiguous() for t in (qkv[:, :K], qkv[:, K:2 * K], qkv[:, 2 * K:]))
+        us_dense = timed(lambda: dense_attention(qd, kd, vd, mask), max(3, args.iters // 10), 2)
+        ref = dense_attention(qd, kd, vd, mask)
+        err = float((ref - out.view(E, N, V)[:E_d]).abs().max())
+        emit(what="dense torch attention", envs=E_d, houses=N, us=round(us_dense, 2), us_per_env=round(us_dense / E_d, 4),
+             band_us_per_env=round(us / E, 4), band_speedup_per_env=round((us_dense / E_d) / (us / E), 1), max_abs_diff_to_band=err)
+        del qd, kd, vd, ref, mask
+
+        # one full actor.sample step (GEMMs + attention + head); the attention's share sizes a later MLP fusion
+        torch.manual_seed(0)
+        actor = TarMACActor(F_OBS).to(DEV)
+        obs = torch.randn((E, N, F_OBS), device=DEV, generator=g)
+        action = torch.empty(A, dtype=torch.uint8, device=DEV)
+        a_prob = torch.empty(A, dtype=torch.float32, device=DEV)
+        us_step = timed(lambda: actor.sample(obs, 0, 0, action=action, a_prob=a_prob), max(3, args.iters // 5), 2)
+        emit(what="TarMACActor.sample", envs=E, houses=N, us=round(us_step, 2), attention_share=round(us / us_step, 4),
+             agent_steps_per_s=round(A / us_step * 1e6))
+        del actor, obs, qkv, out
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
