@@ -140,8 +140,8 @@ int mdr_discounted_returns(const float *reward, const uint8_t *done, const float
                            int64_t nb_agents, float *out, void *stream);
 
 /* ---- TarMAC-PPO actor (agents/network.py:103-238, TarMAC_Comm / TarMAC_Actor): the attention and the head's last step.  The
- * actor's five small per-agent MLPs are library GEMMs on the caller's side (mdr_amd/tarmac.py); these two kernels are what no
- * GEMM covers. */
+ * actor's five small per-agent MLPs are either library GEMMs on the caller's side (mdr_amd/tarmac.py TarMACActor; these two kernels
+ * are what no GEMM covers) or the matrix-core kernels of mdr_tarmac_actor_sample below, which runs the whole actor. */
 enum mdr_tarmac_mode {
   MDR_TARMAC_NEIGHBOURS = 0, /* tarmac_comm_mode "neighbours": the circular band of make_masks (network.py:146-165) */
   MDR_TARMAC_NONE = 1        /* "none": an all-zero mask WITHOUT diagonal - the reference's 0 / 0 -> NaN -> 0: out = 0 */
@@ -172,6 +172,72 @@ int mdr_tarmac_comm(const float *query, int64_t ldq, const float *key, int64_t l
  * maximum on ties, no draw. */
 int mdr_logits_sample(const float *logits, int64_t ld, int64_t nb_agents, uint64_t seed, uint64_t step, const int32_t *step_dev,
                       int32_t greedy, uint8_t *action, float *a_prob, float *probs, void *stream);
+
+/* ---- The whole TarMAC actor through the C ABI: its per-agent MLPs on the matrix cores (csrc/mdr_tarmac_mlp.hip), exact fp32 on
+ * v_mfma_f32_16x16x4_f32 with 16 agents per wavefront, the attention through the kernel behind the attention entry point above, once per hop.
+ *
+ * Notation: F = num_state, H = hidden, K = num_key, V = num_value, M = H + V; nb(n) = ceil(n / 16) blocks of 16 units, nbH = nb(H),
+ * nbV = nb(V), nbM = nb(M); lane = 0..63, r = lane & 15, g = lane >> 4.  Wz is a torch weight matrix [out][in] zero-padded to whole
+ * blocks of rows and to the columns a fragment asks for.  A FRAGMENT of a layer with S k-steps and nbO output blocks holds, for
+ * k-step s, the lane's weight for every output block, the blocks in chunks of four - chunk j holds w_j = min(4, nbO - 4 j) blocks:
+ *   frag[s][j][lane][i < w_j] = Wz[16 (4 j + i) + r][col(s, g)]          (64 nbO floats per k-step, chunk j starts 256 j floats in)
+ * with col(s, g) one of
+ *   rows(S, c0): c0 + g S + s          the input is read from memory, lane group g holding S consecutive floats of its agent's row
+ *   regs:        16 (s >> 2) + 4 g + (s & 3)   the input is the previous layer's accumulator (S = 4 x that layer's blocks)
+ *
+ *   frag_encode = obs2hidden.0  rows(ceil(F / 4), 0), nbH blocks  |  obs2hidden.2  regs (4 nbH steps), nbH blocks
+ *   frag_proj   = hidden2query.0 | hidden2key.0 | hidden2value.0  each regs (4 nbH), nbH blocks
+ *               | hidden2query.2  regs (4 nbH), 1 block | hidden2key.2  regs (4 nbH), 1 block | hidden2value.2  regs (4 nbH), nbV blocks
+ *   frag_msg    = msg_state2state.0: V / 4 steps rows(V / 4, 0) - the comm columns of the concatenation [comm, h] - then H / 4 steps
+ *                 rows(H / 4, V), nbM blocks  |  msg_state2state.2  regs (4 nbM), nbH blocks
+ *   frag_head   = comm_hidden2action.0  rows(M / 4, 0), nbH blocks - the row [x, comm]; without communication hidden2action.0
+ *                 rows(H / 4, 0)
+ *   vec         = every bias zero-padded to whole blocks, in unit order, then the head:
+ *                 obs2hidden.0 [16 nbH] | obs2hidden.2 [16 nbH] | hidden2query.0 | hidden2key.0 | hidden2value.0 [16 nbH each]
+ *                 | hidden2query.2 [16] | hidden2key.2 [16] | hidden2value.2 [16 nbV] | msg_state2state.0 [16 nbM] | msg_state2state.2 [16 nbH]
+ *                 | head.0 [16 nbH] | W3[0][u] - W3[1][u], u < 16 nbH | b3[0] - b3[1], 0, 0, 0      (W3, b3: the head's last layer)
+ * Parts an actor does not have (no communication: frag_proj, frag_msg; one hop: frag_msg) may be NULL; their slots in vec are zeros.
+ * All five pointers are device memory, 16-byte aligned. */
+typedef struct mdr_tarmac_actor {
+  uint32_t struct_size;
+  int32_t num_state;   /* F <= 64 */
+  int32_t hidden;      /* H: a multiple of 4, <= 64 */
+  int32_t num_key;     /* K: a multiple of 4, <= 16 */
+  int32_t num_value;   /* V: a multiple of 4, <= 32 */
+  int32_t nb_comm;     /* number_agents_comm before the clamp to nb_houses - 1; <= 64 after it */
+  int32_t mode;        /* mdr_tarmac_mode */
+  int32_t num_hops;    /* 1..4 */
+  int32_t with_comm;   /* 0: obs2hidden -> hidden2action, no attention */
+  float defect_prob;   /* comm_defect_prob, drawn as the attention entry point documents */
+  int32_t greedy;      /* argmax, the first maximum on ties, no draw */
+  int32_t reserved0;
+  const float *frag_encode;
+  const float *frag_proj;
+  const float *frag_msg;
+  const float *frag_head;
+  const float *vec;
+} mdr_tarmac_actor_t;
+
+/* Sizes in floats of the five arrays (-1: a shape no fragment exists for) */
+int64_t mdr_tarmac_frag_encode_floats(int32_t num_state, int32_t hidden);
+int64_t mdr_tarmac_frag_proj_floats(int32_t hidden, int32_t num_value);
+int64_t mdr_tarmac_frag_msg_floats(int32_t hidden, int32_t num_value);
+int64_t mdr_tarmac_frag_head_floats(int32_t hidden, int32_t num_value, int32_t with_comm);
+int64_t mdr_tarmac_vec_floats(int32_t hidden, int32_t num_value);
+/* Bytes of device scratch a sample of nb_agents = nb_envs * nb_houses agents needs (reads the shape fields only): the head's input
+ * [A][H + V], the packed projections [A][K + K + V] and, with more than one hop, the state [A][H]. */
+int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t *actor, int64_t nb_agents);
+
+/* TarmacPPO.select_actions (agents/tarmac_ppo.py:83-95) for every env at once: `obs` float rows [nb_envs * nb_houses][F] ->
+ * `action` uint8 [A], `a_prob` float [A] (may be NULL), `probs` float [A][2] (may be NULL).  Enqueues 1 + hops + (hops - 1) + 1
+ * kernels on `stream` (two without communication) and never synchronises or allocates; `workspace`: 16-byte aligned device memory
+ * of the size above, owned by the caller, its contents free between calls.  The attention, its defect draws, the action draw,
+ * `step_dev` and greedy are those of the two entry points above for the same (seed, step, agent).  Returns 0, -1 (invalid argument:
+ * a NULL or misaligned pointer, a struct_size that is not this header's), -3 (HIP error) or -4 (a shape outside the limits in the
+ * struct above, or c > 64 after the clamp); on -1 and -4 nothing was launched and no output touched. */
+int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t *actor, const float *obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed,
+                            uint64_t step, const int32_t *step_dev, void *workspace, uint8_t *action, float *a_prob, float *probs,
+                            void *stream);
 
 #ifdef __cplusplus
 }

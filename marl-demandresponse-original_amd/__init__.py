@@ -19,7 +19,7 @@ def __getattr__(name):
     if name == "BatchedMetrics":
         from .metrics import BatchedMetrics
         return BatchedMetrics
-    if name in ("TarMACActor", "TarMACCritic"):
+    if name in ("TarMACActor", "TarMACCritic", "FusedTarMACActor"):
         from . import tarmac
         return getattr(tarmac, name)
     if name == "MADemandResponseEnv":

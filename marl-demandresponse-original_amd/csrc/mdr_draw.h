@@ -1,4 +1,4 @@
-// The draw behind a sampled action, shared by every kernel that samples one (mdr_policy.hip, mdr_tarmac.hip): gfx950 only.
+// The draw behind a sampled action, shared by every kernel that samples one (mdr_policy.hip, mdr_tarmac.hip, mdr_tarmac_mlp.hip): gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>

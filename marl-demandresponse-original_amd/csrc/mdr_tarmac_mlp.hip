@@ -1,0 +1,510 @@
+// TarMAC-PPO actor, the per-agent MLPs on the matrix cores (include/mdr_policy.h: mdr_tarmac_actor_t, mdr_tarmac_actor_sample).
+//
+// Reference: TarMAC_Actor.forward / TarMAC_Comm.forward (agents/network.py:103-238).  Everything an agent computes on its own is a
+// chain of dense layers; the chain is cut only where the attention needs the rows of other agents (mdr_tarmac_comm, mdr_tarmac.hip,
+// used unchanged).  Exact fp32 on v_mfma_f32_16x16x4_f32, 16 agents per wavefront, agents on the MFMA column index, units on the row
+// index, as k_actor_sample16 (mdr_policy.hip): C/D col = lane & 15, row = 4 (lane >> 4) + reg, so the accumulator a lane holds after
+// one layer - units 16 kb + 4 g + reg of its own agent - IS the B operand of the next layer's k-step q = 4 kb + reg when the weight
+// columns are stored in that order.  No LDS and no lane movement for the activations; the biases start the accumulators.
+//
+//   k_tarmac_encode  obs rows -> obs2hidden (F -> H relu -> H) = x -> cat[:, 0:H]; from the same registers hidden2query | hidden2key |
+//                    hidden2value (H -> H tanh -> K | K | V) -> qkv [A][K + K + V], the buffer mdr_tarmac_comm reads in place
+//   k_tarmac_rehop   hops >= 1: [comm, h] -> msg_state2state (H + V -> H + V tanh -> H) = h' -> state; the same projections -> qkv
+//   k_tarmac_head    cat = [x, comm] -> comm_hidden2action (H + V -> H relu -> 2) (hidden2action on x without communication), the
+//                    two-logit softmax and the action draw of mdr_logits_sample (mdr_draw.h)
+//
+// A sample step is 1 + hops + (hops - 1) + 1 launches.  Each kernel is a persistent grid of min(ceil(tiles / waves), CUs) workgroups
+// that stage their weights ONCE into LDS in fragment order (up to ~125 KB: one workgroup per CU) and stride over the tiles.  Rows
+// are addressed with 64-bit offsets: no 4 GiB slicing.
+//
+// Two instantiations per kernel: the block counts of the reference's sizes (H = 64, K <= 16, V <= 16: 4 / 1 / 5 blocks of 16 units
+// for H / V / H + V) with compile-time fragment strides, 16 waves per workgroup in under 128 registers and no scratch; and a general
+// form compiled for the largest covered shape whose loops stop at the run-time block counts, 8 waves per workgroup.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/mdr.h"
+#include "../../include/mdr_policy.h"
+#include "mdr_device.h"
+#include "mdr_draw.h"
+
+namespace {
+
+using mdr::action_uniform;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int WAVES = 16;        // per workgroup, the forms of the reference's sizes: four per SIMD in 128 registers
+constexpr int WAVES_GEN = 8;     // the general forms: two per SIMD in 256 registers
+constexpr int MAX_F = 64, MAX_H = 64, MAX_K = 16, MAX_V = 32, MAX_HOPS = 4, MAX_C = 64;
+
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+
+__host__ __device__ inline int blocks(int n) { return (n + 15) / 16; }
+
+// Offsets (floats) into mdr_tarmac_actor_t.vec: every bias zero-padded to whole 16-unit blocks, in unit order - lane group g reads
+// the four units 16 mb + 4 g + reg of block mb as one float4.
+struct VecLayout {
+  int o1, o2, p1, q2, k2, v2, m1, m2, h1, wd, b3, total;
+};
+
+__host__ __device__ inline VecLayout vec_layout(int mbh, int mbv, int mbm) {
+  VecLayout L;
+  const int nH = 16 * mbh;
+  L.o1 = 0;
+  L.o2 = nH;
+  L.p1 = 2 * nH;             // query | key | value, first layers
+  L.q2 = 5 * nH;
+  L.k2 = L.q2 + 16;
+  L.v2 = L.k2 + 16;
+  L.m1 = L.v2 + 16 * mbv;
+  L.m2 = L.m1 + 16 * mbm;
+  L.h1 = L.m2 + nH;
+  L.wd = L.h1 + nH;          // W3[0] - W3[1]
+  L.b3 = L.wd + nH;          // b3[0] - b3[1], 0, 0, 0
+  L.total = L.b3 + 4;
+  return L;
+}
+
+struct MlpArgs {
+  const float* fa;        // encode: frag_encode; rehop: frag_msg; head: frag_head
+  const float* fp;        // frag_proj
+  const float* vec;
+  const float* in0;       // encode: obs rows; rehop: the comm columns of cat; head: cat
+  const float* in1;       // rehop: h (cat's x columns for the first re-hop, state afterwards)
+  int64_t ld0, ld1;
+  float* cat;
+  float* qkv;
+  float* state;
+  int64_t ldcat, ldqkv;
+  uint8_t* action;
+  float* a_prob;
+  float* probs;
+  int64_t A, ntiles;
+  int D0, S0, S1;         // floats per in0 row that are features; k-steps fed from in0 / in1 (lane group g holds features [g S, g S + S))
+  int vec0, vec1;         // the group's S features are whole aligned float4s
+  int H, K, V;
+  int mbh, mbv, mbm;
+  int with_comm, greedy;
+  int na, np, nvec;       // floats staged from fa / fp / vec
+  uint32_t k0, k1, step_lo, step_hi;
+  const int32_t* step_dev;
+};
+
+// A lane-dependent value hidden from loop-invariant code motion (mdr_policy.hip): every LDS read of the tile loop - weights and
+// biases, none of which change after the staging - is addressed from it, so that hipcc re-reads them where they are used instead
+// of hoisting a hundred of them out of the loop into registers the loop does not have.
+__device__ __forceinline__ int tile_local(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+__device__ __forceinline__ float relu(float x) {      // mdr_policy.hip: max on the bit pattern, one instruction
+  const int b = __builtin_bit_cast(int, x);
+  return __builtin_bit_cast(float, b > 0 ? b : 0);
+}
+
+// tanh to a few ulp at every magnitude: 1 - 2 / (exp(2 |x|) + 1) has an ABSOLUTE error of ~1e-7 (the fast exponential's relative
+// error |2 x| 2^-24 is damped by 2 e / (e + 1)^2 <= 1 / 2), which near 0 would be a large relative one - there the odd series
+// x (1 - x^2 / 3 + 2 x^4 / 15) is used, whose first dropped term 17 x^6 / 315 is below 2^-24 for |x| < 0.1.
+__device__ __forceinline__ float tanh_f(float x) {
+  const float ax = fabsf(x);
+  const float x2 = x * x;
+  const float small = x * fmaf(x2, fmaf(x2, 2.0f / 15.0f, -1.0f / 3.0f), 1.0f);
+  const float e = __expf(2.0f * ax);                        // inf beyond ~44: 2 / inf = 0, tanh = 1
+  const float big = copysignf(1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f), x);
+  return ax < 0.1f ? small : big;
+}
+
+template <int ACT>
+__device__ __forceinline__ float activate(float x) {
+  return ACT == ACT_RELU ? relu(x) : (ACT == ACT_TANH ? tanh_f(x) : x);
+}
+
+__device__ __forceinline__ void stage(float* dst, const float* src, int n, int tid) {
+  const int stride = (int)blockDim.x * 4;      // n a multiple of 4, both 16-byte aligned
+  for (int i = tid * 4; i < n; i += stride) *reinterpret_cast<float4*>(dst + i) = *reinterpret_cast<const float4*>(src + i);
+}
+
+// The A operands of one k-step: a lane's weight for each of the mb output blocks.  Stored in chunks of four blocks,
+// [chunk j][lane][i < w_j], w_j = min(4, mb - 4 j): a full chunk is one ds_read_b128 per lane, a chunk of one block has consecutive
+// lanes on consecutive banks.
+template <int MB, bool EXACT>
+__device__ __forceinline__ void load_w(const float* step, int mb, int lane, float (&w)[MB]) {
+#pragma unroll
+  for (int j = 0; j < (MB + 3) / 4; ++j) {
+    const int wj = EXACT ? (MB - 4 * j < 4 ? MB - 4 * j : 4) : (mb - 4 * j < 4 ? mb - 4 * j : 4);
+    if (!EXACT && wj <= 0) break;
+    const float* p = step + 256 * j + lane * wj;
+    if (wj == 4) {
+      const float4 v = *reinterpret_cast<const float4*>(p);
+      w[4 * j] = v.x;
+      if (4 * j + 1 < MB) w[4 * j + 1 < MB ? 4 * j + 1 : 0] = v.y;
+      if (4 * j + 2 < MB) w[4 * j + 2 < MB ? 4 * j + 2 : 0] = v.z;
+      if (4 * j + 3 < MB) w[4 * j + 3 < MB ? 4 * j + 3 : 0] = v.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if (i < wj && 4 * j + i < MB) w[4 * j + i < MB ? 4 * j + i : 0] = p[i];
+    }
+  }
+}
+
+template <int MB>
+__device__ __forceinline__ void init_bias(const float* bias, int g, int mb, f32x4 (&out)[MB]) {
+#pragma unroll
+  for (int b = 0; b < MB; ++b) {
+    if (b < mb)
+      out[b] = *reinterpret_cast<const f32x4*>(bias + 16 * b + 4 * g);
+    else
+      out[b] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+}
+
+// out += W . act(in): the B operand of k-step q = 4 kb + reg is register [kb][reg] of the previous layer as it is
+template <int MBI, int MBO, bool EXACT, int ACT>
+__device__ __forceinline__ void layer_regs(const float* frag, const f32x4 (&in)[MBI], int mbi, f32x4 (&out)[MBO], int mbo, int lane) {
+#pragma unroll
+  for (int q = 0; q < 4 * MBI; ++q) {
+    if (EXACT || q < 4 * mbi) {
+      const float b = activate<ACT>(in[q >> 2][q & 3]);
+      float w[MBO];
+      load_w<MBO, EXACT>(frag + q * 64 * mbo, mbo, lane, w);
+#pragma unroll
+      for (int mb = 0; mb < MBO; ++mb)
+        if (EXACT || mb < mbo) out[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[mb], b, out[mb], 0, 0, 0);
+    }
+  }
+}
+
+// out += W . x for k-steps fed from the lane's feature registers
+template <int XS, int MBO, bool EXACT>
+__device__ __forceinline__ void layer_feats(const float* frag, const float (&xr)[XS], int S, f32x4 (&out)[MBO], int mbo, int lane) {
+#pragma unroll
+  for (int s = 0; s < XS; ++s) {
+    if (s < S) {
+      float w[MBO];
+      load_w<MBO, EXACT>(frag + s * 64 * mbo, mbo, lane, w);
+#pragma unroll
+      for (int mb = 0; mb < MBO; ++mb)
+        if (EXACT || mb < mbo) out[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[mb], xr[s], out[mb], 0, 0, 0);
+    }
+  }
+}
+
+// Features [first, first + S) of a row of D floats into the lane's registers; indices past the row are read at D - 1 and meet zero
+// weights.  `vec`: S is a multiple of 4, first + S <= D and the row is 16-byte aligned.
+template <int XS>
+__device__ __forceinline__ void load_feats(const float* row, int first, int S, int D, int vec, float (&xr)[XS]) {
+  if (vec) {
+#pragma unroll
+    for (int j = 0; j < XS / 4; ++j)
+      if (4 * j < S) {
+        const float4 v = *reinterpret_cast<const float4*>(row + first + 4 * j);
+        xr[4 * j] = v.x, xr[4 * j + 1] = v.y, xr[4 * j + 2] = v.z, xr[4 * j + 3] = v.w;
+      }
+  } else {
+#pragma unroll
+    for (int s = 0; s < XS; ++s)
+      if (s < S) xr[s] = row[min(first + s, D - 1)];
+  }
+}
+
+// hidden2query | hidden2key | hidden2value on the hidden state a lane holds, written packed to its agent's qkv row.
+// frag_proj: the three first layers [p < 3][4 mbh steps][64 mbh], then the second layers of query (1 block), key (1), value (mbv).
+template <int MBH, int MBV, bool EXACT>
+__device__ __forceinline__ void projections(const float* fp, const float* vec, const VecLayout& L, const f32x4 (&h)[MBH], int mbh, int mbv,
+                                            int K, int V, float* qkv_row, bool valid, int lane) {
+  const int g = lane >> 4;
+  const int steps = 4 * mbh;
+  const int n1 = steps * 64 * mbh;
+  const float* f2 = fp + 3 * n1;
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    f32x4 t[MBH];
+    init_bias<MBH>(vec + L.p1 + p * 16 * mbh, g, mbh, t);
+    layer_regs<MBH, MBH, EXACT, ACT_NONE>(fp + p * n1, h, mbh, t, mbh, lane);
+    if (p < 2) {
+      f32x4 o[1];
+      init_bias<1>(vec + (p == 0 ? L.q2 : L.k2), g, 1, o);
+      layer_regs<MBH, 1, EXACT, ACT_TANH>(f2 + p * steps * 64, t, mbh, o, 1, lane);
+      if (valid && 4 * g < K) *reinterpret_cast<f32x4*>(qkv_row + p * K + 4 * g) = o[0];
+    } else {
+      f32x4 o[MBV];
+      init_bias<MBV>(vec + L.v2, g, mbv, o);
+      layer_regs<MBH, MBV, EXACT, ACT_TANH>(f2 + 2 * steps * 64, t, mbh, o, mbv, lane);
+#pragma unroll
+      for (int mb = 0; mb < MBV; ++mb)
+        if (valid && 16 * mb + 4 * g < V) *reinterpret_cast<f32x4*>(qkv_row + 2 * K + 16 * mb + 4 * g) = o[mb];
+    }
+  }
+}
+
+template <int MBH, int MBV, bool EXACT>
+__global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_encode(MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* fa = lds;
+  float* fp = fa + a.na;
+  float* vec = fp + a.np;
+  const int tid = threadIdx.x;
+  stage(fa, a.fa, a.na, tid);
+  if (a.with_comm) stage(fp, a.fp, a.np, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  __syncthreads();
+  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
+  const VecLayout L = vec_layout(mbh, mbv, a.mbm);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  constexpr int NW = EXACT ? WAVES : WAVES_GEN;
+  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
+  const float* f2 = fa + a.S0 * 64 * mbh;
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const int64_t agent = t * 16 + r;
+    const bool valid = agent < a.A;
+    const int64_t ac = valid ? agent : a.A - 1;
+    float xr[16];
+    load_feats<16>(a.in0 + ac * a.ld0, g * a.S0, a.S0, a.D0, a.vec0, xr);
+    f32x4 t1[MBH], x[MBH];
+    init_bias<MBH>(vec + L.o1, g, mbh, t1);
+    layer_feats<16, MBH, EXACT>(fa, xr, a.S0, t1, mbh, lane);
+    init_bias<MBH>(vec + L.o2, g, mbh, x);
+    layer_regs<MBH, MBH, EXACT, ACT_RELU>(f2, t1, mbh, x, mbh, lane);
+    float* cat_row = a.cat + ac * a.ldcat;
+#pragma unroll
+    for (int mb = 0; mb < MBH; ++mb)
+      if (valid && 16 * mb + 4 * g < a.H) *reinterpret_cast<f32x4*>(cat_row + 16 * mb + 4 * g) = x[mb];
+    if (a.with_comm) projections<MBH, MBV, EXACT>(fp, vec, L, x, mbh, mbv, a.K, a.V, a.qkv + ac * a.ldqkv, valid, lane);
+  }
+}
+
+// frag_msg: layer 1 [V / 4 + H / 4 steps][64 mbm] - the comm columns of the concatenation [comm, h] first - then layer 2
+// [4 mbm steps][64 mbh]
+template <int MBH, int MBV, int MBM, bool EXACT>
+__global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_rehop(MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* fa = lds;
+  float* fp = fa + a.na;
+  float* vec = fp + a.np;
+  const int tid = threadIdx.x;
+  stage(fa, a.fa, a.na, tid);
+  stage(fp, a.fp, a.np, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  __syncthreads();
+  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv, mbm = EXACT ? MBM : a.mbm;
+  const VecLayout L = vec_layout(mbh, mbv, mbm);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  constexpr int NW = EXACT ? WAVES : WAVES_GEN;
+  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
+  const float* f1h = fa + a.S0 * 64 * mbm;
+  const float* f2 = f1h + a.S1 * 64 * mbm;
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const int64_t agent = t * 16 + r;
+    const bool valid = agent < a.A;
+    const int64_t ac = valid ? agent : a.A - 1;
+    float xc[4 * MBV], xh[4 * MBH];
+    load_feats<4 * MBV>(a.in0 + ac * a.ld0, g * a.S0, a.S0, a.V, a.vec0, xc);
+    load_feats<4 * MBH>(a.in1 + ac * a.ld1, g * a.S1, a.S1, a.H, a.vec1, xh);
+    f32x4 m[MBM], h[MBH];
+    init_bias<MBM>(vec + L.m1, g, mbm, m);
+    layer_feats<4 * MBV, MBM, EXACT>(fa, xc, a.S0, m, mbm, lane);
+    layer_feats<4 * MBH, MBM, EXACT>(f1h, xh, a.S1, m, mbm, lane);
+    init_bias<MBH>(vec + L.m2, g, mbh, h);
+    layer_regs<MBM, MBH, EXACT, ACT_TANH>(f2, m, mbm, h, mbh, lane);
+    float* st_row = a.state + ac * (int64_t)a.H;
+#pragma unroll
+    for (int mb = 0; mb < MBH; ++mb)
+      if (valid && 16 * mb + 4 * g < a.H) *reinterpret_cast<f32x4*>(st_row + 16 * mb + 4 * g) = h[mb];
+    projections<MBH, MBV, EXACT>(fp, vec, L, h, mbh, mbv, a.K, a.V, a.qkv + ac * a.ldqkv, valid, lane);
+  }
+}
+
+// frag_head: [D / 4 steps][64 mbh], D = H + V (H without communication): the row [x, comm] as it lies in cat
+template <int MBH, int XS, bool EXACT>
+__global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_head(MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* fa = lds;
+  float* vec = fa + a.na;
+  const int tid = threadIdx.x;
+  stage(fa, a.fa, a.na, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  __syncthreads();
+  const int mbh = EXACT ? MBH : a.mbh;
+  const VecLayout L = vec_layout(mbh, a.mbv, a.mbm);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  constexpr int NW = EXACT ? WAVES : WAVES_GEN;
+  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
+  const float bias3 = vec[L.b3];
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const int64_t agent = t * 16 + r;
+    const bool valid = agent < a.A;
+    const int64_t ac = valid ? agent : a.A - 1;
+    float xr[XS];
+    load_feats<XS>(a.in0 + ac * a.ld0, g * a.S0, a.S0, a.D0, a.vec0, xr);
+    f32x4 acc[MBH];
+    init_bias<MBH>(vec + L.h1, g, mbh, acc);
+    layer_feats<XS, MBH, EXACT>(fa, xr, a.S0, acc, mbh, lane);
+    float d = 0.0f;
+#pragma unroll
+    for (int mb = 0; mb < MBH; ++mb)
+      if (EXACT || mb < mbh) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(vec + L.wd + 16 * mb + 4 * g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d = fmaf(w[i], relu(acc[mb][i]), d);
+      }
+    d += __shfl_xor(d, 16);
+    d += __shfl_xor(d, 32);
+    d += bias3;
+    const float p0 = 1.0f / (1.0f + expf(-d));      // mdr_logits_sample's softmax over two logits
+    const float p1 = 1.0f / (1.0f + expf(d));
+    if (g == 0 && valid) {
+      int act;
+      if (a.greedy) {
+        act = d >= 0.0f ? 0 : 1;      // argmax keeps the first maximum, as torch.argmax
+      } else {
+        const float u = action_uniform(mdr::action_word(agent, a.step_lo, a.step_hi, a.step_dev, a.k0, a.k1));
+        act = u < p0 ? 0 : 1;
+      }
+      a.action[agent] = (uint8_t)act;
+      if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
+      if (a.probs) {
+        a.probs[agent * 2] = p0;
+        a.probs[agent * 2 + 1] = p1;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------- host
+
+bool shape_positive(int F, int H, int K, int V) { return F > 0 && H > 0 && K > 0 && V > 0; }
+bool shape_covered(int F, int H, int K, int V) {
+  return F <= MAX_F && H % 4 == 0 && H <= MAX_H && K % 4 == 0 && K <= MAX_K && V % 4 == 0 && V <= MAX_V;
+}
+
+int64_t encode_floats(int F, int H) { return ((int64_t)(F + 3) / 4 + 4 * blocks(H)) * 64 * blocks(H); }
+int64_t proj_floats(int H, int V) { return (int64_t)4 * blocks(H) * 64 * (3 * blocks(H) + 2 + blocks(V)); }
+int64_t msg_floats(int H, int V) { return (int64_t)((V + H) / 4) * 64 * blocks(H + V) + (int64_t)4 * blocks(H + V) * 64 * blocks(H); }
+int64_t head_floats(int H, int V, int with_comm) { return (int64_t)((H + (with_comm ? V : 0)) / 4) * 64 * blocks(H); }
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+template <typename K>
+int launch(K kernel, int waves, const MlpArgs& a, int lds_floats, int cus, hipStream_t s) {
+  const size_t lds_bytes = (size_t)lds_floats * sizeof(float);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+    return MDR_ERR_HIP;
+  const int64_t want = (a.ntiles + waves - 1) / waves;
+  const unsigned grid = (unsigned)(want < cus ? want : cus);      // persistent: the weights are staged once per workgroup
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds_bytes, s, a);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mdr_tarmac_frag_encode_floats(int32_t num_state, int32_t hidden) {
+  return (num_state > 0 && hidden > 0 && num_state <= MAX_F && hidden <= MAX_H) ? encode_floats(num_state, hidden) : -1;
+}
+int64_t mdr_tarmac_frag_proj_floats(int32_t hidden, int32_t num_value) {
+  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V) ? proj_floats(hidden, num_value) : -1;
+}
+int64_t mdr_tarmac_frag_msg_floats(int32_t hidden, int32_t num_value) {
+  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V && hidden % 4 == 0 && num_value % 4 == 0) ? msg_floats(hidden, num_value) : -1;
+}
+int64_t mdr_tarmac_frag_head_floats(int32_t hidden, int32_t num_value, int32_t with_comm) {
+  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V && hidden % 4 == 0 && num_value % 4 == 0)
+             ? head_floats(hidden, num_value, with_comm) : -1;
+}
+int64_t mdr_tarmac_vec_floats(int32_t hidden, int32_t num_value) {
+  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V) ? vec_layout(blocks(hidden), blocks(num_value), blocks(hidden + num_value)).total : -1;
+}
+
+int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t* actor, int64_t nb_agents) {
+  if (!actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || nb_agents < 0) return -1;
+  const int H = actor->hidden, K = actor->num_key, V = actor->num_value;
+  if (!shape_positive(1, H, K, V)) return -1;
+  int64_t floats = H;
+  if (actor->with_comm) floats += V + K + K + V + (actor->num_hops > 1 ? H : 0);
+  return nb_agents * floats * (int64_t)sizeof(float);
+}
+
+int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed, uint64_t step,
+                            const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, void* stream) {
+  if (!actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || !obs || !workspace || !action) return MDR_ERR_INVALID;
+  if (nb_envs < 0 || nb_houses <= 0) return MDR_ERR_INVALID;
+  const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value;
+  const int hops = actor->num_hops, wc = actor->with_comm != 0;
+  if (!shape_positive(F, H, K, V) || hops < 1 || actor->nb_comm < 0) return MDR_ERR_INVALID;
+  if (actor->mode != MDR_TARMAC_NEIGHBOURS && actor->mode != MDR_TARMAC_NONE) return MDR_ERR_INVALID;
+  if (!(actor->defect_prob >= 0.0f && actor->defect_prob <= 1.0f)) return MDR_ERR_INVALID;
+  if (!actor->frag_encode || !actor->frag_head || !actor->vec) return MDR_ERR_INVALID;
+  if (wc && (!actor->frag_proj || (hops > 1 && !actor->frag_msg))) return MDR_ERR_INVALID;
+  if (!aligned16(workspace) || !aligned16(actor->frag_encode) || !aligned16(actor->frag_head) || !aligned16(actor->vec) ||
+      !aligned16(actor->frag_proj) || !aligned16(actor->frag_msg) || ((uintptr_t)obs & 3u))
+    return MDR_ERR_INVALID;
+  if (!shape_covered(F, H, K, V) || hops > MAX_HOPS) return MDR_ERR_UNSUPPORTED;
+  const int c = actor->nb_comm < nb_houses - 1 ? actor->nb_comm : nb_houses - 1;
+  if (wc && actor->mode == MDR_TARMAC_NEIGHBOURS && c > MAX_C) return MDR_ERR_UNSUPPORTED;
+  const int64_t A = (int64_t)nb_envs * nb_houses;
+  if (A >= ((int64_t)1 << 35)) return MDR_ERR_UNSUPPORTED;      // the grids of mdr_tarmac_comm
+  if (A == 0) return MDR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+
+  const int mbh = blocks(H), mbv = blocks(V), mbm = blocks(H + V);
+  const VecLayout L = vec_layout(mbh, mbv, mbm);
+  const bool exact = mbh == 4 && mbv == 1 && (!wc || hops == 1 || mbm == 5);
+  const int64_t ldcat = wc ? H + V : H, ldqkv = K + K + V;
+  float* cat = static_cast<float*>(workspace);
+  float* qkv = cat + A * ldcat;
+  float* state = qkv + A * ldqkv;
+
+  MlpArgs a{};
+  a.vec = actor->vec, a.nvec = L.total;
+  a.cat = cat, a.qkv = qkv, a.state = state, a.ldcat = ldcat, a.ldqkv = ldqkv;
+  a.action = action, a.a_prob = a_prob, a.probs = probs;
+  a.A = A, a.ntiles = (A + 15) / 16;
+  a.H = H, a.K = K, a.V = V, a.mbh = mbh, a.mbv = mbv, a.mbm = mbm;
+  a.with_comm = wc, a.greedy = actor->greedy != 0;
+  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.step_lo = (uint32_t)step, a.step_hi = (uint32_t)(step >> 32);
+  a.step_dev = step_dev;
+  a.np = wc ? (int)proj_floats(H, V) : 0;
+  auto whole4 = [](int S, int D) { return (S % 4 == 0 && 4 * S == D) ? 1 : 0; };
+
+  // ---- obs -> x (-> qkv)
+  a.fa = actor->frag_encode, a.fp = actor->frag_proj, a.na = (int)encode_floats(F, H);
+  a.in0 = obs, a.ld0 = F, a.D0 = F, a.S0 = (F + 3) / 4;
+  a.vec0 = whole4(a.S0, F) && aligned16(obs);
+  int rc = exact ? launch(k_tarmac_encode<4, 1, true>, WAVES, a, a.na + a.np + a.nvec, cus, s)
+                 : launch(k_tarmac_encode<4, 2, false>, WAVES_GEN, a, a.na + a.np + a.nvec, cus, s);
+  if (rc != MDR_OK) return rc;
+  if (wc) {
+    for (int hop = 0; hop < hops; ++hop) {
+      if (hop > 0) {      // [comm, h] -> h' -> qkv
+        a.fa = actor->frag_msg, a.na = (int)msg_floats(H, V);
+        a.in0 = cat + H, a.ld0 = ldcat, a.D0 = V, a.S0 = V / 4;
+        a.in1 = hop == 1 ? cat : state, a.ld1 = hop == 1 ? ldcat : H, a.S1 = H / 4;
+        a.vec0 = whole4(a.S0, V), a.vec1 = whole4(a.S1, H);
+        rc = exact ? launch(k_tarmac_rehop<4, 1, 5, true>, WAVES, a, a.na + a.np + a.nvec, cus, s)
+                   : launch(k_tarmac_rehop<4, 2, 6, false>, WAVES_GEN, a, a.na + a.np + a.nvec, cus, s);
+        if (rc != MDR_OK) return rc;
+      }
+      rc = mdr_tarmac_comm(qkv, ldqkv, qkv + K, ldqkv, qkv + 2 * K, ldqkv, nb_envs, nb_houses, K, V, actor->nb_comm, actor->mode, actor->defect_prob,
+                           seed, step, step_dev, hop, cat + H, ldcat, stream);
+      if (rc != MDR_OK) return rc;
+    }
+  }
+  // ---- [x, comm] -> logits -> action
+  a.fa = actor->frag_head, a.na = (int)head_floats(H, V, wc);
+  a.in0 = cat, a.ld0 = ldcat, a.D0 = (int)ldcat, a.S0 = (int)ldcat / 4;
+  a.vec0 = whole4(a.S0, (int)ldcat);
+  return (mbh == 4 && a.S0 <= 20) ? launch(k_tarmac_head<4, 20, true>, WAVES, a, a.na + a.nvec, cus, s)
+                                  : launch(k_tarmac_head<4, 24, false>, WAVES_GEN, a, a.na + a.nvec, cus, s);
+}
+
+}  // extern "C"

@@ -262,15 +262,15 @@ def collect_ppo_rollout(env, actor: nn.Module, nb_steps: int, gamma: float = 0.9
 def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, critic: Optional[nn.Module] = None, seed: int = 0,
                            store_states: bool = True) -> Dict[str, torch.Tensor]:
     """The interaction loop of train_tarmacPPO.py:62-119 for all envs at once: every step ``env.obs_vector("rows")`` ->
-    ``TarMACActor.sample`` (TarmacPPO.select_actions, agents/tarmac_ppo.py:83-95: each agent attends to the hidden states of the other
+    ``TarMACActor.sample`` or ``FusedTarMACActor.sample`` (TarmacPPO.select_actions, agents/tarmac_ppo.py:83-95: each agent attends to the hidden states of the other
     agents of ITS env, hence observations as [E, N, F]) -> ``env.step``.  Same keys and flattened [T, E*N] layout as
     ``collect_ppo_rollout``: ``state`` [T+1, E*N, F] (omitted without ``store_states``), ``action`` int64, ``a_prob``, ``reward``,
     ``done`` (True on the last step) and ``return``; the bootstrap through ``critic`` (a ``TarMACCritic``) is its [E, N] value of the
     last next-state (tarmac_ppo.py:136-141).  The env steps without writing its observation planes during the collection and brings
     them up to date once at the end.  House-sharded envs are refused: attention across shards needs a halo exchange of keys and values."""
-    from .tarmac import TarMACActor
-    if not isinstance(actor, TarMACActor):
-        raise ValueError("collect_tarmac_rollout takes a TarMACActor")
+    from .tarmac import FusedTarMACActor, TarMACActor
+    if not isinstance(actor, (TarMACActor, FusedTarMACActor)):
+        raise ValueError("collect_tarmac_rollout takes a TarMACActor or a FusedTarMACActor")
     if getattr(env, "sharded", False):
         raise ValueError("TarMAC over house-sharded envs is not supported: the attention needs the keys and values of the neighbouring shard")
     E, N = env.nb_envs, env.nb_houses
@@ -402,7 +402,9 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     [E, N], ``sq_temp_error_sum`` [E] (sum over steps and houses of (house_temp - target)^2), ``sq_signal_error_sum`` [E] (sum over
     steps of (reg_signal - cluster_hvac_power)^2).
 
-    ``policy``: a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused), the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
+    ``policy``: a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused), a
+    ``FusedTarMACActor`` (the same agent as one chain of HIP kernels: observation rows, the chain with ``step_dev =
+    env.device_time_index``, ``env.step`` - one stream, no parallel branches, so ``use_graph=True`` captures it), the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
     here, and observation and policy are then ONE kernel wherever ``collect_ppo_rollout`` would make them one (no observation rows at
     all) - or a ready ``FusedActor``: one packed with ``feature_order=FEATURES_OBSERVE`` takes the same one-kernel path, any other
     gets observation rows.
@@ -410,17 +412,19 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     ``use_graph`` (default: when the env was built with ``graph_mode=True``): the step is captured once in a
     ``torch.cuda.CUDAGraph`` and replayed - the launch-bound regime of small batches."""
     from .policy import FEATURES_OBSERVE
-    from .tarmac import TarMACActor
+    from .tarmac import FusedTarMACActor, TarMACActor
     E, N = env.nb_envs, env.nb_houses
     dev = env.device
     F_len = env.obs_vector_length()
-    tarmac = isinstance(policy, TarMACActor)
+    fused_tarmac = isinstance(policy, FusedTarMACActor)
+    tarmac = fused_tarmac or isinstance(policy, TarMACActor)
     if tarmac:
-        if use_graph:
+        if use_graph and not fused_tarmac:
             raise ValueError("deploy_policy runs a TarMACActor eagerly: its GEMMs and kernels are not captured")
         if getattr(env, "sharded", False):
             raise ValueError("TarMAC over house-sharded envs is not supported")
-        use_graph = False
+        if not fused_tarmac:
+            use_graph = False
     elif isinstance(policy, nn.Module):
         if not _fusable(policy):
             raise ValueError("deploy_policy takes Linear(F,H1) - Linear(H1,H2) - Linear(H2,2) networks on the device (or a FusedActor)")
@@ -429,6 +433,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     observe_act = getattr(policy, "feature_order", 0) == FEATURES_OBSERVE
     obs = None if observe_act else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
     act = torch.empty(E * N, dtype=torch.uint8, device=dev)
+    act_prob = torch.empty(E * N, dtype=torch.float32, device=dev) if tarmac else None      # no allocation inside a captured step
     out = {"reward_sum": torch.zeros((E, N), dtype=torch.float32, device=dev),
            "sq_temp_error_sum": torch.zeros(E, dtype=torch.float64, device=dev),
            "sq_signal_error_sum": torch.zeros(E, dtype=torch.float64, device=dev)}
@@ -448,7 +453,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
             policy.sample_env(env, seed, step0 + t, action=act, step_dev=step_dev)
         elif tarmac:         # TarmacPPOAgent.act (agents/rl_controllers.py:86-122): the agents of an env attend to each other
             env.obs_vector("rows", out=obs)
-            policy.sample(obs, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act)
+            policy.sample(obs, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act, a_prob=act_prob)
         else:
             env.obs_vector("rows", out=obs)
             policy.sample(obs.view(E * N, F_len), seed, step0 + t, action=act, step_dev=step_dev)

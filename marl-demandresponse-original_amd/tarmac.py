@@ -11,6 +11,10 @@ Two ways to evaluate the attention of ``TarMAC_Comm.forward``:
                        O(E N c) and runs as ONE HIP kernel per hop (``mdr_tarmac_comm``, include/mdr_policy.h) on keys / values
                        staged in LDS; the five small per-agent MLPs stay library GEMMs into buffers allocated once, the softmax
                        over the two logits and ``Categorical.sample`` are ``mdr_logits_sample``.  Inference only.
+
+``FusedTarMACActor.from_module(actor)`` evaluates the same actor WITHOUT library GEMMs: the per-agent MLPs run as HIP kernels on the
+matrix cores in exact fp32 (``mdr_tarmac_actor_sample``, csrc/mdr_tarmac_mlp.hip) around the same attention kernel - three launches per
+step for one hop, capturable in a graph, reachable through the C ABI alone.
 """
 from __future__ import annotations
 
@@ -298,6 +302,215 @@ class TarMACActor(nn.Module):
             logits = self.dense_logits(obs, dead).reshape(-1, 2).float().contiguous()
         action, a_prob, probs = self._head(logits, seed, step, step_dev, greedy, want_probs, action, a_prob)
         return (action, a_prob, probs) if want_probs else (action, a_prob)
+
+
+# ------------------------------------------------------------------------------------------------------------ fused actor
+FUSED_MAX_OBS, FUSED_MAX_HIDDEN, FUSED_MAX_KEY, FUSED_MAX_VALUE = 64, 64, 16, 32
+
+
+class MdrTarmacActor(C.Structure):
+    """``mdr_tarmac_actor_t`` (include/mdr_policy.h), field for field."""
+    _fields_ = [("struct_size", C.c_uint32), ("num_state", C.c_int32), ("hidden", C.c_int32), ("num_key", C.c_int32),
+                ("num_value", C.c_int32), ("nb_comm", C.c_int32), ("mode", C.c_int32), ("num_hops", C.c_int32),
+                ("with_comm", C.c_int32), ("defect_prob", C.c_float), ("greedy", C.c_int32), ("reserved0", C.c_int32),
+                ("frag_encode", C.c_void_p), ("frag_proj", C.c_void_p), ("frag_msg", C.c_void_p), ("frag_head", C.c_void_p),
+                ("vec", C.c_void_p)]
+
+
+def _blocks(n: int) -> int:
+    return (int(n) + 15) // 16
+
+
+def _fragment(w, steps: int, nb_out: int, col):
+    """One layer in MFMA fragment order (include/mdr_policy.h): ``w`` [out, in] -> float32 [steps * 64 * nb_out];
+    ``col(s, g)`` -> (column of ``w`` for k-step s and lane group g, first column that is no longer this segment's)."""
+    import numpy as np
+    w = np.asarray(w, dtype=np.float32)
+    out = np.zeros((steps, 64 * nb_out), dtype=np.float32)
+    lane = np.arange(64)
+    r, g = lane & 15, lane >> 4
+    for s in range(steps):
+        c, end = col(s, g)
+        for j in range((nb_out + 3) // 4):
+            wj = min(4, nb_out - 4 * j)
+            for i in range(wj):
+                row = 16 * (4 * j + i) + r
+                ok = (row < w.shape[0]) & (c < min(end, w.shape[1]))
+                out[s, 256 * j + lane * wj + i] = np.where(ok, w[np.minimum(row, w.shape[0] - 1), np.minimum(c, w.shape[1] - 1)], 0.0)
+    return out.reshape(-1)
+
+
+def _from_rows(steps: int, first: int, length: int):
+    return lambda s, g: (first + g * steps + s, first + length)
+
+
+def _from_regs(n_in: int):
+    return lambda s, g: (16 * (s >> 2) + 4 * g + (s & 3), n_in)
+
+
+def pack_tarmac_fragments(sd, num_obs: int, hidden: int, num_key: int, num_value: int, num_hops: int = 1, with_comm: bool = True):
+    """A TarMAC actor's state_dict (numpy / torch, CPU) -> the five float32 arrays of ``mdr_tarmac_actor_t`` as a dict
+    ``frag_encode, frag_proj, frag_msg, frag_head, vec``; parts the actor does not have are None."""
+    import numpy as np
+    sd = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float32) for k, v in sd.items()}
+    F_, H, K, V = int(num_obs), int(hidden), int(num_key), int(num_value)
+    nbh, nbv, nbm = _blocks(H), _blocks(V), _blocks(H + V)
+    s1 = (F_ + 3) // 4
+
+    def padded(name, n):
+        out = np.zeros(n, dtype=np.float32)
+        if name is not None and name in sd:
+            out[:sd[name].shape[0]] = sd[name]
+        return out
+
+    res = {"frag_proj": None, "frag_msg": None}
+    res["frag_encode"] = np.concatenate([_fragment(sd["obs2hidden.0.weight"], s1, nbh, _from_rows(s1, 0, F_)),
+                                         _fragment(sd["obs2hidden.2.weight"], 4 * nbh, nbh, _from_regs(H))])
+    names = ("query", "key", "value")
+    if with_comm:
+        first = [_fragment(sd["comm.hidden2%s.0.weight" % n], 4 * nbh, nbh, _from_regs(H)) for n in names]
+        second = [_fragment(sd["comm.hidden2%s.2.weight" % n], 4 * nbh, nbv if n == "value" else 1, _from_regs(H)) for n in names]
+        res["frag_proj"] = np.concatenate(first + second)
+        if num_hops > 1:
+            w = sd["comm.msg_state2state.0.weight"]      # columns: comm (V) first, then h (H)
+            res["frag_msg"] = np.concatenate([_fragment(w, V // 4, nbm, _from_rows(V // 4, 0, V)),
+                                              _fragment(w, H // 4, nbm, _from_rows(H // 4, V, H)),
+                                              _fragment(sd["comm.msg_state2state.2.weight"], 4 * nbm, nbh, _from_regs(H + V))])
+        head, d_in = "comm_hidden2action", H + V
+    else:
+        head, d_in = "hidden2action", H
+    res["frag_head"] = _fragment(sd[head + ".0.weight"], d_in // 4, nbh, _from_rows(d_in // 4, 0, d_in))
+    w3, b3 = sd[head + ".2.weight"], sd[head + ".2.bias"]
+    wd = np.zeros(16 * nbh, dtype=np.float32)
+    wd[:H] = w3[0] - w3[1]
+    c = "comm." if with_comm else None
+    m = c if num_hops > 1 else None
+    res["vec"] = np.concatenate([
+        padded("obs2hidden.0.bias", 16 * nbh), padded("obs2hidden.2.bias", 16 * nbh),
+        *[padded(c and c + "hidden2%s.0.bias" % n, 16 * nbh) for n in names],
+        padded(c and c + "hidden2query.2.bias", 16), padded(c and c + "hidden2key.2.bias", 16), padded(c and c + "hidden2value.2.bias", 16 * nbv),
+        padded(m and m + "msg_state2state.0.bias", 16 * nbm), padded(m and m + "msg_state2state.2.bias", 16 * nbh),
+        padded(head + ".0.bias", 16 * nbh), wd, np.array([b3[0] - b3[1], 0.0, 0.0, 0.0], dtype=np.float32)])
+    return res
+
+
+class FusedTarMACActor:
+    """A ``TarMACActor`` evaluated by ``mdr_tarmac_actor_sample`` (include/mdr_policy.h): the per-agent MLPs as three kinds of HIP
+    kernels on the matrix cores in exact fp32 (csrc/mdr_tarmac_mlp.hip) around the banded attention kernel - 1 + hops + (hops - 1)
+    + 1 launches per step, no library GEMM, no allocation after the first call, capturable in a graph.  Inference only; to
+    ``TarMACActor`` what ``FusedActor`` is to ``ActorMLP``.  Covers num_obs <= 64, hidden_state_size a multiple of 4 <= 64, num_key
+    a multiple of 4 <= 16, num_value a multiple of 4 <= 32, two actions, the modes 'neighbours' and 'none'; anything else is a
+    ValueError (the eager band path of ``TarMACActor`` remains for those)."""
+
+    def __init__(self, actor: "TarMACActor"):
+        self.actor = actor
+        self._check_shapes()
+        self._packed_key = None
+        self._tensors = None
+        self._struct = None
+        self._workspace_for = None
+        self._workspace = None
+
+    @classmethod
+    def from_module(cls, actor: "TarMACActor") -> "FusedTarMACActor":
+        return cls(actor)
+
+    def _shape(self):
+        a = self.actor
+        K, V = (a.num_key, a.num_value) if a.with_comm else (4, 4)      # no projections: the fields only have to be valid
+        return a.num_obs, a.hidden, K, V
+
+    def _check_shapes(self):
+        a = self.actor
+        if not isinstance(a, TarMACActor):
+            raise ValueError("FusedTarMACActor.from_module takes a TarMACActor")
+        F_, H, K, V = self._shape()
+        if a.num_action != 2:
+            raise ValueError("the fused TarMAC actor samples between two actions")
+        if a.comm_mode not in MODES:
+            raise ValueError("the fused TarMAC actor covers the comm modes 'neighbours' and 'none'")
+        if not 1 <= a.num_hops <= MAX_HOPS:
+            raise ValueError("num_hops must be 1..%d" % MAX_HOPS)
+        if not 1 <= F_ <= FUSED_MAX_OBS:
+            raise ValueError("the fused TarMAC actor covers num_obs <= %d (the eager band path has no such limit)" % FUSED_MAX_OBS)
+        if H < 4 or H % 4 or H > FUSED_MAX_HIDDEN or K < 4 or K % 4 or K > FUSED_MAX_KEY or V < 4 or V % 4 or V > FUSED_MAX_VALUE:
+            raise ValueError("the fused TarMAC actor covers hidden_state_size a multiple of 4 <= %d, num_key a multiple of 4 <= %d and "
+                             "num_value a multiple of 4 <= %d" % (FUSED_MAX_HIDDEN, FUSED_MAX_KEY, FUSED_MAX_VALUE))
+
+    def _pack(self):
+        """Fragments on the parameters' device; re-packed only when a parameter changed."""
+        a = self.actor
+        params = list(a.parameters())
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        if self._packed_key != key:
+            dev = params[0].device
+            if dev.type != "cuda":
+                raise ValueError("the fused TarMAC actor runs on the GPU: move the TarMACActor there first")
+            F_, H, K, V = self._shape()
+            host = pack_tarmac_fragments(a.state_dict(), F_, H, K, V, a.num_hops, a.with_comm)
+            self._tensors = {n: (torch.from_numpy(v).to(dev) if v is not None else None) for n, v in host.items()}
+            st = MdrTarmacActor()
+            st.struct_size = C.sizeof(MdrTarmacActor)
+            st.num_state, st.hidden, st.num_key, st.num_value = F_, H, K, V
+            st.nb_comm, st.mode, st.num_hops, st.with_comm = a.number_agents_comm, MODES[a.comm_mode], a.num_hops, int(a.with_comm)
+            st.defect_prob = a.comm_defect_prob
+            for n, t in self._tensors.items():
+                setattr(st, n, t.data_ptr() if t is not None else None)
+            self._struct = st
+            self._packed_key = key
+            self._device = dev
+        return self._struct
+
+    def workspace(self, nb_agents: int, dev) -> torch.Tensor:
+        """The device scratch of a sample of ``nb_agents`` agents, allocated once per (nb_agents, device)."""
+        if self._workspace_for != (nb_agents, dev):
+            n = nat.load().mdr_tarmac_actor_workspace_bytes(C.byref(self._pack()), nb_agents)
+            if n < 0:
+                raise RuntimeError("mdr_tarmac_actor_workspace_bytes refused the actor")
+            self._workspace = torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
+            self._workspace_for = (nb_agents, dev)
+        return self._workspace
+
+    @torch.no_grad()
+    def sample(self, obs: torch.Tensor, seed: int, step: int, step_dev: Optional[torch.Tensor] = None, greedy: bool = False,
+               want_probs: bool = False, action: Optional[torch.Tensor] = None, a_prob: Optional[torch.Tensor] = None):
+        """As ``TarMACActor.sample``: ``obs`` float32 [E, N, F] on the GPU -> (action uint8 [E * N], a_prob float32 [E * N][, probs
+        [E * N, 2]])."""
+        a = self.actor
+        if obs.dim() != 3 or obs.shape[2] != a.num_obs or obs.dtype != torch.float32 or not obs.is_cuda or not obs.is_contiguous():
+            raise ValueError("obs must be a contiguous float32 [E, N, %d] tensor on the GPU" % a.num_obs)
+        st = self._pack()
+        dev = obs.device
+        if dev != self._device:
+            raise ValueError("obs and the actor's parameters must be on the same device")
+        if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.device != dev):
+            raise ValueError("step_dev must be an int32 tensor on the device (env.device_time_index)")
+        E, N, _ = obs.shape
+        A = E * N
+        if a.with_comm and a.comm_mode == "neighbours" and min(a.number_agents_comm, N - 1) > MAX_COMM:
+            raise ValueError("band attention covers at most %d senders per receiver" % MAX_COMM)
+        for name, t, dt in (("action", action, torch.uint8), ("a_prob", a_prob, torch.float32)):
+            if t is not None and (t.dtype != dt or t.device != dev or t.numel() != A or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous %s tensor of E * N elements on the device" % (name, dt))
+        lib = nat.load()
+        ws = self.workspace(A, dev)
+        action = torch.empty(A, dtype=torch.uint8, device=dev) if action is None else action
+        a_prob = torch.empty(A, dtype=torch.float32, device=dev) if a_prob is None else a_prob
+        probs = torch.empty((A, 2), dtype=torch.float32, device=dev) if want_probs else None
+        st.greedy = int(bool(greedy))
+        with torch.cuda.device(dev):
+            rc = lib.mdr_tarmac_actor_sample(C.byref(st), C.c_void_p(obs.data_ptr()), E, N, C.c_uint64(seed & (2 ** 64 - 1)),
+                                             C.c_uint64(step & (2 ** 64 - 1)), C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None,
+                                             C.c_void_p(ws.data_ptr()), C.c_void_p(action.data_ptr()), C.c_void_p(a_prob.data_ptr()),
+                                             C.c_void_p(probs.data_ptr()) if want_probs else None,
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError("mdr_tarmac_actor_sample failed: %s" % lib.mdr_status_string(rc).decode())
+        return (action, a_prob, probs) if want_probs else (action, a_prob)
+
+    def probs(self, obs: torch.Tensor, seed: int = 0, step: int = 0, step_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``obs`` [E, N, F] -> probabilities [E, N, 2] (``seed`` / ``step`` key the defect draws)."""
+        return self.sample(obs, seed, step, step_dev, want_probs=True)[2].view(obs.shape[0], obs.shape[1], 2)
 
 
 class TarMACCritic(nn.Module):

@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
-"""TarMAC-PPO actor: mdr_tarmac_comm alone against its traffic floor and against the dense torch attention, and its share of one full
-TarMACActor.sample step.  HIP events after warm-up; one JSON line per measurement.
+"""TarMAC-PPO actor: mdr_tarmac_comm alone against its traffic floor and against the dense torch attention, its share of one full
+TarMACActor.sample step, and - in the same run on the same device - the same step through FusedTarMACActor (csrc/mdr_tarmac_mlp.hip)
+with the two floors of each of its kernels.  HIP events after warm-up; one JSON line per measurement.
 
-    python tools/bench_tarmac.py [--shapes 4096x1024,83886x50] [--iters 50] [--warmup 5] [--out FILE]
+    python tools/bench_tarmac.py [--shapes 4096x1024,83886x50] [--iters 50] [--warmup 5] [--hops 1] [--skip-attention] [--out FILE]
+
+Per-kernel times of the fused step come from `rocprofv3 --kernel-trace --stats -- python tools/bench_tarmac.py --skip-attention`; the
+floors to hold them against are the "floors" record: matrix time = the kernel's own count of v_mfma_f32_16x16x4_f32 per 16-agent tile x
+15.0 ns per SIMD (tools/probe, mdr_policy.hip) over 1024 SIMDs, traffic = algorithmic bytes per agent at the rate below.
 
 Floor: 4 (2 K + 2 V) algorithmic bytes per agent (query, key, value read once, comm written once: 192 B at K = 8, V = 16) over the
 5.25 TB/s out-of-cache rate of DESIGN.md section 7.  The dense comparator is TarMAC_Comm.forward's formula (agents x agents scores,
@@ -17,10 +22,24 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import mdr_amd  # noqa: E402
-from mdr_amd.tarmac import TarMACActor  # noqa: E402
+from mdr_amd.tarmac import FusedTarMACActor, TarMACActor  # noqa: E402
 
 OUT_OF_CACHE_BPS = 5.25e12
-K, V, COMM, F_OBS = 8, 16, 10, 51
+K, V, COMM, F_OBS, HID = 8, 16, 10, 51, 64
+MFMA_NS, SIMDS = 15.0, 1024
+
+
+def fused_floors(A, hops):
+    """name -> (MFMAs per tile, algorithmic bytes per agent, matrix floor us, traffic floor us) for the kernels of one fused step."""
+    nbh, nbv, nbm = (HID + 15) // 16, (V + 15) // 16, (HID + V + 15) // 16
+    proj = 3 * 4 * nbh * nbh + 4 * nbh * (2 + nbv)
+    kernels = {"k_tarmac_encode": ((F_OBS + 3) // 4 * nbh + 4 * nbh * nbh + proj, 4 * (F_OBS + HID + K + K + V)),
+               "k_tarmac_head": ((HID + V) // 4 * nbh, 4 * (HID + V) + 1 + 4)}
+    if hops > 1:
+        kernels["k_tarmac_rehop"] = ((HID + V) // 4 * nbm + 4 * nbm * nbh + proj, 4 * (V + HID + HID + K + K + V))
+    tiles = (A + 15) // 16
+    return {n: dict(mfma_per_tile=m, bytes_per_agent=b, matrix_floor_us=round(m * MFMA_NS * 1e-3 * tiles / SIMDS, 1),
+                    traffic_floor_us=round(A * b / OUT_OF_CACHE_BPS * 1e6, 1)) for n, (m, b) in kernels.items()}
 DEV = "cuda:0"
 
 
@@ -50,6 +69,8 @@ def main():
     ap.add_argument("--shapes", default="4096x1024,83886x50")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--hops", type=int, default=1)
+    ap.add_argument("--skip-attention", action="store_true", help="only the two full steps (the run to put under rocprofv3)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_tarmac.py needs a GPU"
@@ -74,33 +95,43 @@ def main():
                                      C.c_uint64(0), None, 0, C.c_void_p(out.data_ptr()), V, stream)
             assert rc == 0, rc
 
-        us = timed(band, args.iters, args.warmup)
-        floor_us = A * 4 * (2 * K + 2 * V) / OUT_OF_CACHE_BPS * 1e6
-        emit(what="mdr_tarmac_comm", envs=E, houses=N, agents=A, us=round(us, 2), floor_us=round(floor_us, 2), times_floor=round(us / floor_us, 3),
-             algorithmic_GBps=round(A * 4 * (2 * K + 2 * V) / us * 1e-3, 1))
+        us = None
+        if not args.skip_attention:
+            us = timed(band, args.iters, args.warmup)
+            floor_us = A * 4 * (2 * K + 2 * V) / OUT_OF_CACHE_BPS * 1e6
+            emit(what="mdr_tarmac_comm", envs=E, houses=N, agents=A, us=round(us, 2), floor_us=round(floor_us, 2), times_floor=round(us / floor_us, 3),
+                 algorithmic_GBps=round(A * 4 * (2 * K + 2 * V) / us * 1e-3, 1))
 
-        # dense torch attention on the same inputs: all envs if five [E, N, N] temporaries fit in half of the free memory
-        free = torch.cuda.mem_get_info()[0]
-        E_d = int(min(E, max(1, (free // 2) // (5 * 4 * N * N))))
-        mask = TarMACActor(F_OBS).band_mask(N, DEV).float()
-        qd, kd, vd = (t.reshape(E, N, -1)[:E_d].contiguous() for t in (qkv[:, :K], qkv[:, K:2 * K], qkv[:, 2 * K:]))
-        us_dense = timed(lambda: dense_attention(qd, kd, vd, mask), max(3, args.iters // 10), 2)
-        ref = dense_attention(qd, kd, vd, mask)
-        err = float((ref - out.view(E, N, V)[:E_d]).abs().max())
-        emit(what="dense torch attention", envs=E_d, houses=N, us=round(us_dense, 2), us_per_env=round(us_dense / E_d, 4),
-             band_us_per_env=round(us / E, 4), band_speedup_per_env=round((us_dense / E_d) / (us / E), 1), max_abs_diff_to_band=err)
-        del qd, kd, vd, ref, mask
+            # dense torch attention on the same inputs: all envs if five [E, N, N] temporaries fit in half of the free memory
+            free = torch.cuda.mem_get_info()[0]
+            E_d = int(min(E, max(1, (free // 2) // (5 * 4 * N * N))))
+            mask = TarMACActor(F_OBS).band_mask(N, DEV).float()
+            qd, kd, vd = (t.reshape(E, N, -1)[:E_d].contiguous() for t in (qkv[:, :K], qkv[:, K:2 * K], qkv[:, 2 * K:]))
+            us_dense = timed(lambda: dense_attention(qd, kd, vd, mask), max(3, args.iters // 10), 2)
+            ref = dense_attention(qd, kd, vd, mask)
+            err = float((ref - out.view(E, N, V)[:E_d]).abs().max())
+            emit(what="dense torch attention", envs=E_d, houses=N, us=round(us_dense, 2), us_per_env=round(us_dense / E_d, 4),
+                 band_us_per_env=round(us / E, 4), band_speedup_per_env=round((us_dense / E_d) / (us / E), 1), max_abs_diff_to_band=err)
+            del qd, kd, vd, ref, mask
 
         # one full actor.sample step (GEMMs + attention + head); the attention's share sizes a later MLP fusion
         torch.manual_seed(0)
-        actor = TarMACActor(F_OBS).to(DEV)
+        actor = TarMACActor(F_OBS, num_hops=args.hops).to(DEV)
         obs = torch.randn((E, N, F_OBS), device=DEV, generator=g)
         action = torch.empty(A, dtype=torch.uint8, device=DEV)
         a_prob = torch.empty(A, dtype=torch.float32, device=DEV)
         us_step = timed(lambda: actor.sample(obs, 0, 0, action=action, a_prob=a_prob), max(3, args.iters // 5), 2)
-        emit(what="TarMACActor.sample", envs=E, houses=N, us=round(us_step, 2), attention_share=round(us / us_step, 4),
-             agent_steps_per_s=round(A / us_step * 1e6))
-        del actor, obs, qkv, out
+        emit(what="TarMACActor.sample", envs=E, houses=N, hops=args.hops, us=round(us_step, 2),
+             attention_share=round(us / us_step, 4) if us is not None else None, agent_steps_per_s=round(A / us_step * 1e6))
+        # the same step as one chain of HIP kernels; the same-run eager time above is what it has to beat
+        fused = FusedTarMACActor.from_module(actor)
+        action_f, a_prob_f = torch.empty_like(action), torch.empty_like(a_prob)
+        us_fused = timed(lambda: fused.sample(obs, 0, 0, action=action_f, a_prob=a_prob_f), max(3, args.iters // 5), 2)
+        emit(what="FusedTarMACActor.sample", envs=E, houses=N, hops=args.hops, us=round(us_fused, 2), eager_us=round(us_step, 2),
+             speedup=round(us_step / us_fused, 2), agent_steps_per_s=round(A / us_fused * 1e6),
+             actions_differ=int((action != action_f).sum()), max_abs_a_prob_diff=float((a_prob - a_prob_f).abs().max()))
+        emit(what="floors", envs=E, houses=N, hops=args.hops, **fused_floors(A, args.hops))
+        del actor, fused, obs, qkv, out
         torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
