@@ -18,6 +18,9 @@
  *   - temperatures in device buffers are stored RELATIVE to mdr_config.temp_ref (deg C), see DESIGN.md.
  *
  * Layout: all per-house arrays are row-major [nb_envs][nb_houses] (house index fastest).
+ *
+ * ABI 5: mdr_buffers_t ends in the optional `param_uniform` word (per-house parameter columns that hold one value for every
+ * house are not streamed by the step kernels); new entry point mdr_env_params_changed.
  */
 #ifndef MDR_H
 #define MDR_H
@@ -28,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MDR_ABI_VERSION 4
+#define MDR_ABI_VERSION 5
 #define MDR_MAX_SINUSOIDS 8
 #define MDR_MAX_CAPACITIES 16
 #define MDR_OBS_COLUMNS 7
@@ -182,6 +185,17 @@ typedef struct mdr_buffers {
    * mdr_env_active_tables() says which set the current window reads: 0 = tab_*, 1 = tab2_*. */
   float *tab2_od, *tab2_solar;
   double *tab2_signal, *tab2_abs_noise;
+  /* Optional (NULL = off: every column is streamed): ONE device word that says which per-house parameter columns hold one value
+   * for all nb_envs * nb_houses houses: bit 0 `target`, bit 1 `deadband`, bit 2 `lockout` (bitwise equal to element [0]: -0.0
+   * against +0.0 or differing NaN payloads leave a column streamed).  The single-step kernels (mdr_env_step, the records pair,
+   * mdr_env_step_mailbox) then take a set column's value from element [0] instead of streaming it: 4 B per house-step and column
+   * less - every configuration the reference trains with has all three uniform (12 of 99 B).  The library writes the word where
+   * it writes the arrays: mdr_env_reset, mdr_env_load_episode - and mdr_env_params_changed; mdr_env_bind does not touch it.  So
+   * the three arrays are READ at reset, at load and at params_changed: a caller that writes `target`, `deadband` or `lockout`
+   * itself in between must call mdr_env_params_changed before the next step.  The arrays stay fully written either way (the
+   * other kernels read them), and the word lives with the buffers: cloning the buffers clones a consistent word, a captured
+   * step reads it at replay time, no host ever reads it. */
+  uint32_t *param_uniform;
 } mdr_buffers_t;
 
 /* Raw episode parameters for mdr_env_load_episode (replay of an episode sampled elsewhere).
@@ -246,6 +260,9 @@ int mdr_env_reset(mdr_env_t *env, uint64_t seed, uint32_t episode, void *stream)
 /* Same, but from caller-supplied raw parameters instead of sampling. */
 int mdr_env_load_episode(mdr_env_t *env, const mdr_episode_t *episode, uint64_t seed, uint32_t episode_index,
                          void *stream);
+/* The caller wrote `target`, `deadband` or `lockout` of the bound buffers itself: re-derives mdr_buffers_t.param_uniform from the
+ * arrays (one pass over the three columns on `stream`).  Nothing to do, MDR_OK, when the word is not bound. */
+int mdr_env_params_changed(mdr_env_t *env, void *stream);
 /* Optional: replace ClusterHouses.compute_OD_temp (env 1057-1081, incl. its random.gauss draw 1079) by a table, double [rows][E] deg C (row = time index);
  * NULL restores the model.  Takes effect at the next mdr_env_begin_episode / table refill; mdr_env_reset (a freshly sampled
  * episode) drops it. */

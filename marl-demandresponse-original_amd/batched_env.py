@@ -46,7 +46,7 @@ class BatchedDemandResponseEnv:
                  house_shard: Optional[Tuple[int, int]] = None, process_group=None,
                  stagger_bytes: int = 2304, interp_grid=None, regenerate_missing_grid: bool = True,
                  graph_mode: bool = False, exchange_always: bool = False, partial_records: Optional[int] = None,
-                 obs_planes: bool = True, prefetch_tables: bool = True, exchange=None):
+                 obs_planes: bool = True, prefetch_tables: bool = True, exchange=None, uniform_params: bool = True):
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedDemandResponseEnv needs a ROCm device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
@@ -84,6 +84,10 @@ class BatchedDemandResponseEnv:
         # a second set of time tables: the next window's tables are built on a side stream of the library while this window's steps
         # run (mdr_buffers_t.tab2_*); not in graph mode / interpolation mode, where refills stay in place
         self._prefetch_tables = bool(prefetch_tables) and not self.graph_mode and self.spec.base_power_mode != 1
+        # uniform_params: bind mdr_buffers_t.param_uniform - the step kernels then do not stream the columns among target /
+        # deadband / lockout that hold one value for every house (found on the device at reset / load_episode / params_changed());
+        # False binds NULL: every column is streamed
+        self._uniform_params = bool(uniform_params)
         self._handle = C.c_void_p()
         self._cfg = self._make_config()
         rc = self._lib.mdr_env_create(C.byref(self._cfg), C.byref(self._handle))
@@ -160,6 +164,8 @@ class BatchedDemandResponseEnv:
         items += [("cursor", torch.int32, (8,))]      # graph mode: {table row, time index, row note 0, arrival counter, row note 1, -} on the device
         # split path (sharded houses, N > 4096): the houses' own penalties between the partial and the finish kernel; else NULL
         items += [("pen_stash", torch.float32, (E, N) if (self.sharded or N > 4096) else (0,))]
+        # bit 0 target, 1 deadband, 2 lockout: the column holds one value for every house (in the slab whether bound or not: one layout)
+        items += [("param_uniform", torch.int32, (1,))]
         return items
 
     def _allocate(self):
@@ -199,6 +205,8 @@ class BatchedDemandResponseEnv:
                 continue                                    # NULL: launch arguments carry the table rows
             if fname == "obs" and not self._obs_planes_on:
                 continue                                    # NULL: the step kernels do not write the planes
+            if fname == "param_uniform" and not self._uniform_params:
+                continue                                    # NULL: every parameter column is streamed
             setattr(b, fname, self.t[fname].data_ptr() if self.t[fname].numel() else None)      # an empty optional buffer is NULL
         self._buffers = b
         nat.check(self._lib, self._handle, self._lib.mdr_env_bind(self._handle, C.byref(b)), "mdr_env_bind")
@@ -357,6 +365,13 @@ class BatchedDemandResponseEnv:
             self._begin_episode()
             torch.cuda.current_stream(self.device).synchronize()  # `keep` may be freed after this
             return self._reset_obs()
+
+    def params_changed(self) -> None:
+        """Call after writing ``t['target']``, ``t['deadband']`` or ``t['lockout']`` yourself: the library reads the three arrays
+        at reset, at load_episode and here to find the columns that hold one value for every house (which the step kernels then do
+        not stream).  One pass over the three columns on the current stream; no host sync."""
+        with torch.cuda.device(self.device):
+            nat.check(self._lib, self._handle, self._lib.mdr_env_params_changed(self._handle, self._stream()), "mdr_env_params_changed")
 
     def set_od_table(self, od_table):
         if od_table is None:
@@ -948,11 +963,12 @@ class BatchedDemandResponseEnv:
         rc = self._lib.mdr_env_set_cursor(self._handle, C.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF),
                                           C.c_uint32(max(self.episode, 0) & 0xFFFFFFFF), sd["k"], sd["j0"])
         nat.check(self._lib, self._handle, rc, "mdr_env_set_cursor")
+        self.params_changed()      # the slab brought its parameter arrays: the uniformity word is derived from them again
 
     def __deepcopy__(self, memo):
         other = BatchedDemandResponseEnv(copy.deepcopy(self.config, memo), nb_envs=self.nb_envs, device=self.device,
                                          seed=self.seed, test=self.test, table_steps=self.table_steps, obs_planes=self._obs_planes_alloc,
-                                         prefetch_tables=self._prefetch_tables,
+                                         prefetch_tables=self._prefetch_tables, uniform_params=self._uniform_params,
                                          env_offset=self.env_offset,
                                          house_shard=(self.house_offset, self.nb_houses) if self.sharded else None,
                                          exchange_always=self._exchange_always, partial_records=self._partial_records,

@@ -124,6 +124,7 @@ std::string check_buffers(const mdr_buffers_t& b, bool need_partials) {
     if (((uintptr_t)p & 15u) != 0) return "per-house float/int buffers must be 16-byte aligned";
   if (((uintptr_t)b.flags & 3u) != 0) return "flags must be 4-byte aligned";
   if (((uintptr_t)b.pen_stash & 15u) != 0) return "pen_stash must be 16-byte aligned";
+  if (((uintptr_t)b.param_uniform & 3u) != 0) return "param_uniform must be 4-byte aligned";
   return "";
 }
 
@@ -376,6 +377,7 @@ int step_args(mdr_env* env, uint8_t* actions, int action_source, hipStream_t s, 
   a.Ta = b.Ta; a.Tm = b.Tm; a.sso = b.sso; a.flags = b.flags;
   a.k01 = b.k01; a.s0 = b.s0; a.k10 = b.k10; a.s1 = b.s1; a.inv_Ua = b.inv_Ua; a.Q_hvac = b.Q_hvac; a.P_max = b.P_max;
   a.target = b.target; a.deadband = b.deadband; a.lockout = b.lockout;
+  a.param_uniform = b.param_uniform;
   a.actions = actions;
   a.reward = b.reward; a.obs = b.obs;
   a.P = b.P; a.tot_sum = b.tot_sum; a.tot_max = b.tot_max; a.partials = b.partials;
@@ -519,6 +521,8 @@ int mdr_env_reset(mdr_env_t* env, uint64_t seed, uint32_t episode, void* stream)
   if (settle_prefetch(env, (hipStream_t)stream) != MDR_OK) return MDR_ERR_HIP;
   hipError_t e = mdr::launch_sample(episode_args(*env), (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "reset");
+  e = mdr::launch_detect_uniform(env->buf, (int64_t)env->cfg.nb_envs * env->cfg.nb_houses, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(env, e, "reset: detect_uniform");
   env->has_episode = true;
   env->k = 0;
   return MDR_OK;
@@ -540,8 +544,18 @@ int mdr_env_load_episode(mdr_env_t* env, const mdr_episode_t* ep, uint64_t seed,
   if (settle_prefetch(env, (hipStream_t)stream) != MDR_OK) return MDR_ERR_HIP;
   hipError_t e = mdr::launch_load(episode_args(*env), *ep, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "load_episode");
+  e = mdr::launch_detect_uniform(env->buf, (int64_t)env->cfg.nb_envs * env->cfg.nb_houses, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(env, e, "load_episode: detect_uniform");
   env->has_episode = true;
   env->k = 0;
+  return MDR_OK;
+}
+
+int mdr_env_params_changed(mdr_env_t* env, void* stream) {
+  if (!env) return MDR_ERR_INVALID;
+  if (!env->bound) return fail(env, MDR_ERR_UNBOUND, "buffers not bound");
+  const hipError_t e = mdr::launch_detect_uniform(env->buf, (int64_t)env->cfg.nb_envs * env->cfg.nb_houses, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(env, e, "params_changed");
   return MDR_OK;
 }
 

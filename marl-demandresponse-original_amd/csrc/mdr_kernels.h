@@ -103,6 +103,7 @@ struct StepArgs {
   double c_sig;                        // alpha_sig / norm_sig_penalty
   double inv_n_total;                  // 1 / nb_agents
   double inv_obs_norm;                 // 1 / (norm_reg_sig * nb_agents)
+  const uint32_t* param_uniform;       // mdr_buffers_t.param_uniform: bit 0 target, 1 deadband, 2 lockout hold ONE value (element [0]) for every house; nullptr = stream all
 };
 
 // utils.normStateDict for all houses (k_obs_vector)
@@ -240,6 +241,7 @@ int64_t split_blocks(int N, int threads);     // workgroups (= partial records) 
 
 hipError_t launch_sample(const EpisodeArgs& a, hipStream_t s);
 hipError_t launch_load(const EpisodeArgs& a, const mdr_episode_t& ep, hipStream_t s);
+hipError_t launch_detect_uniform(const mdr_buffers_t& b, int64_t n, hipStream_t s);   // b.param_uniform <- which of target / deadband / lockout hold one value in all n houses
 hipError_t launch_tables(const TableArgs& a, hipStream_t s);
 hipError_t launch_interp_base(const InterpArgs& a, hipStream_t s);
 hipError_t launch_patch_signal_plane(const StepArgs& a, hipStream_t s);   // obs plane 5 <- sig_old row

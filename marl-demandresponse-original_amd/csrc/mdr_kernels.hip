@@ -94,6 +94,40 @@ __global__ __launch_bounds__(256) void k_load_envs(EpisodeArgs a, mdr_episode_t 
   a.b.ratio[e] = ep.ratio ? ep.ratio[e] : a.artificial_ratio;
 }
 
+// mdr_buffers_t.param_uniform: which of target / deadband / lockout hold one value in all n = E * N houses.  The word starts at 7
+// (set by the launcher, ahead on the stream); one grid-stride pass compares every element BITWISE with element [0] - so -0.0
+// against +0.0 or differing NaN payloads leave a column streamed - and a wave that saw a mismatch clears the column's bit.
+// 12 B per house once per episode against 12 B per house saved in every step.
+__global__ __launch_bounds__(256) void k_detect_uniform(const uint32_t* __restrict__ target, const uint32_t* __restrict__ deadband,
+                                                        const uint32_t* __restrict__ lockout, int64_t n, uint32_t* word) {
+  const uint32_t t0 = target[0], d0 = deadband[0], l0 = lockout[0];
+  const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t bad = 0u;
+  for (int64_t j = first; j < n4; j += stride) {   // the arrays are 16-byte aligned (mdr_env_bind)
+    const uint4 t = reinterpret_cast<const uint4*>(target)[j], d = reinterpret_cast<const uint4*>(deadband)[j],
+                l = reinterpret_cast<const uint4*>(lockout)[j];
+    bad |= (t.x != t0 || t.y != t0 || t.z != t0 || t.w != t0) ? 1u : 0u;
+    bad |= (d.x != d0 || d.y != d0 || d.z != d0 || d.w != d0) ? 2u : 0u;
+    bad |= (l.x != l0 || l.y != l0 || l.z != l0 || l.w != l0) ? 4u : 0u;
+  }
+  for (int64_t i = n4 * 4 + first; i < n; i += stride)
+    bad |= (target[i] != t0 ? 1u : 0u) | (deadband[i] != d0 ? 2u : 0u) | (lockout[i] != l0 ? 4u : 0u);
+  const uint32_t wave_bad = (__builtin_amdgcn_ballot_w64((bad & 1u) != 0u) != 0ull ? 1u : 0u) |
+                            (__builtin_amdgcn_ballot_w64((bad & 2u) != 0u) != 0ull ? 2u : 0u) |
+                            (__builtin_amdgcn_ballot_w64((bad & 4u) != 0u) != 0ull ? 4u : 0u);
+  if (wave_bad != 0u && (threadIdx.x & 63u) == 0u) atomicAnd(word, ~wave_bad);
+}
+
+hipError_t launch_detect_uniform(const mdr_buffers_t& b, int64_t n, hipStream_t s) {
+  if (b.param_uniform == nullptr || n < 1) return hipSuccess;
+  hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.param_uniform), 7, 1, s);
+  if (e != hipSuccess) return e;
+  const int64_t blocks = std::min<int64_t>(((n + 3) / 4 + 255) / 256, 2048);
+  hipLaunchKernelGGL(k_detect_uniform, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(b.target),
+                     reinterpret_cast<const uint32_t*>(b.deadband), reinterpret_cast<const uint32_t*>(b.lockout), n, b.param_uniform);
+  return hipGetLastError();
+}
+
 // Local sum of max consumption per env (ClusterHouses.__init__, env 796-802); P <- 0.  The sum is EXACT in fp64 whatever the order
 // (fp32 addends within a factor of 8 of each other: 24 + log2(N) significant bits), so an env of more than 65,536 houses is summed by
 // several workgroups through atomic adds - one workgroup took 0.98 ms for 1,000,000 houses at every episode start.

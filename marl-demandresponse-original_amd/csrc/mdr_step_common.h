@@ -147,6 +147,32 @@ __device__ __forceinline__ void load_param(const float* __restrict__ p, int64_t 
   load_vec<VEC>(p, i, out);
 #endif
 }
+// Per-house parameter columns that hold ONE value for every house of the batch (mdr_buffers_t.param_uniform: bit 0 target, bit 1
+// deadband, bit 2 lockout - every configuration the reference trains with has all three): the single-step kernels take such a
+// column from element [0] (a scalar load) instead of streaming it, 4 B per house-step and column less.  The word and the bit are
+// wave-uniform: a plain branch, and both arms leave the same bits in the same registers, so the arithmetic behind is one copy.
+constexpr uint32_t UNIFORM_TARGET = 1u, UNIFORM_DEADBAND = 2u, UNIFORM_LOCKOUT = 4u;
+__device__ __forceinline__ uint32_t uniform_word(const StepArgs& a) { return a.param_uniform != nullptr ? a.param_uniform[0] : 0u; }
+template <int VEC>
+__device__ __forceinline__ void load_param_or_first(bool uniform, const float* __restrict__ p, int64_t i, float* out) {
+  if (uniform) {
+    const float x = p[0];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) out[v] = x;
+  } else {
+    load_param<VEC>(p, i, out);
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void load_vec_or_first(bool uniform, const int* __restrict__ p, int64_t i, int* out) {
+  if (uniform) {
+    const int x = p[0];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) out[v] = x;
+  } else {
+    load_vec<VEC>(p, i, out);
+  }
+}
 template <int VEC>
 __device__ __forceinline__ void store_bytes(uint8_t* __restrict__ p, int64_t i, const unsigned* v) {
   if constexpr (VEC == 4) {
@@ -221,6 +247,7 @@ __device__ __forceinline__ void house_step_vec(const StepArgs& a, int64_t i, con
   float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];
   int sso[VEC];
   unsigned fl[VEC];
+  const uint32_t uni = uniform_word(a);
   load_vec<VEC>(a.Ta, i, Ta);
   load_vec<VEC>(a.Tm, i, Tm);
   load_vec<VEC>(a.sso, i, sso);
@@ -233,9 +260,9 @@ __device__ __forceinline__ void house_step_vec(const StepArgs& a, int64_t i, con
   load_param<VEC>(a.inv_Ua, i, iu);
   load_param<VEC>(a.Q_hvac, i, q);
   load_param<VEC>(a.P_max, i, pm);
-  load_param<VEC>(a.target, i, tg);
-  load_param<VEC>(a.deadband, i, db);
-  load_vec<VEC>(a.lockout, i, lockout);
+  load_param_or_first<VEC>((uni & UNIFORM_TARGET) != 0u, a.target, i, tg);
+  load_param_or_first<VEC>((uni & UNIFORM_DEADBAND) != 0u, a.deadband, i, db);
+  load_vec_or_first<VEC>((uni & UNIFORM_LOCKOUT) != 0u, a.lockout, i, lockout);
   // the in-kernel controllers act on the pre-step observation (agents/bangbang_controllers.py); three wave-uniform arms
   bool cmds[VEC];
   if (a.action_source == MDR_ACTIONS_EXTERNAL) {
@@ -266,6 +293,7 @@ __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, cons
   float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];
   int sso[VEC];
   unsigned fl[VEC], act[VEC];
+  const uint32_t uni = uniform_word(a);
   load_vec<VEC>(a.Ta, i, Ta);
   load_vec<VEC>(a.Tm, i, Tm);
   load_vec<VEC>(a.sso, i, sso);
@@ -278,9 +306,9 @@ __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, cons
   load_param<VEC>(a.inv_Ua, i, iu);
   load_param<VEC>(a.Q_hvac, i, q);
   load_param<VEC>(a.P_max, i, pm);
-  load_param<VEC>(a.target, i, tg);
-  load_param<VEC>(a.deadband, i, db);
-  load_vec<VEC>(a.lockout, i, lockout);
+  load_param_or_first<VEC>((uni & UNIFORM_TARGET) != 0u, a.target, i, tg);
+  load_param_or_first<VEC>((uni & UNIFORM_DEADBAND) != 0u, a.deadband, i, db);
+  load_vec_or_first<VEC>((uni & UNIFORM_LOCKOUT) != 0u, a.lockout, i, lockout);
   float nTa[VEC], nTm[VEC];
   int nsso[VEC];
   unsigned nfl[VEC];
