@@ -166,6 +166,30 @@ int mdr_tarmac_comm(const float *query, int64_t ldq, const float *key, int64_t l
                     int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob,
                     uint64_t seed, uint64_t step, const int32_t *step_dev, int32_t hop, float *out, int64_t ldo, void *stream);
 
+/* The gradient of the attention above (the training path).  The operands up to `hop` are the forward call's; `out` is what that call wrote,
+ * `grad_out` (rows of num_value floats) the gradient g of a scalar loss with respect to it.  With S(r) the live senders of receiver r
+ * and p_rs its softmax weights:
+ *   delta_r = g_r . out_r,   ds_rs = p_rs (g_r . value_s - delta_r),
+ *   grad_query_r = sum_{s in S(r)} ds_rs key_s / sqrt(num_key),   grad_key_s = sum_{r: s in S(r)} ds_rs query_r / sqrt(num_key),
+ *   grad_value_s = sum_{r: s in S(r)} p_rs g_r
+ * (sender s is heard by the receivers s - o).  The dead-sender flags are redrawn from the same Philox counter: a call with the forward's
+ * (seed, step, *step_dev, hop) sees the forward's mask, no mask is stored.  Every element of the three results is written (the caller
+ * does not zero them), each through its own leading dimension; the sums are gathered per row in a fixed order, without floating-point
+ * atomics, so the same operands give the same bits.  MDR_TARMAC_NONE writes exact zeros; c = 0: grad_value = grad_out bit for bit
+ * and grad_query = grad_key = 0.  `workspace`: 16-byte aligned device memory of mdr_tarmac_comm_backward_workspace_bytes() bytes,
+ * owned by the caller, contents irrelevant before and after (not needed, and may be NULL, in mode MDR_TARMAC_NONE).  Limits and
+ * status codes as the forward's, for all eight pointers and leading dimensions; a missing or unaligned workspace is -1.  Returns 0,
+ * or -1 / -3 / -4 with nothing launched and nothing written. */
+int mdr_tarmac_comm_backward(const float *query, int64_t ldq, const float *key, int64_t ldk, const float *value, int64_t ldv,
+                             int32_t nb_envs, int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode,
+                             float defect_prob, uint64_t seed, uint64_t step, const int32_t *step_dev, int32_t hop, const float *out,
+                             int64_t ldo, const float *grad_out, int64_t ldg, float *grad_query, int64_t ldgq, float *grad_key,
+                             int64_t ldgk, float *grad_value, int64_t ldgv, void *workspace, void *stream);
+
+/* Bytes of `workspace` for nb_agents = nb_envs * nb_houses agents (one float4 of softmax statistics per receiver); -1 for
+ * negative or zero sizes of the rows. */
+int64_t mdr_tarmac_comm_backward_workspace_bytes(int64_t nb_agents, int32_t num_key, int32_t num_value);
+
 /* The policy head's last step for two logits per agent (`logits` float [nb_agents][ld], ld >= 2, columns 0 and 1):
  * d = l0 - l1, p0 = 1 / (1 + exp(-d)), p1 = 1 / (1 + exp(d)), then the draw, `action`, `a_prob`, `probs` and `step_dev` exactly as
  * mdr_actor_sample: for equal probabilities the same (seed, step, agent) draws the same action.  greedy != 0: argmax, the first

@@ -146,7 +146,7 @@ EXPORTS = (
     "mdr_env_step_mailbox", "mdr_mailbox_halo_bytes", "mdr_mailbox_halo_push", "mdr_mailbox_halo_pull",
     # include/mdr_policy.h
     "mdr_actor_steps1", "mdr_actor_steps1_order", "mdr_actor_steps2", "mdr_actor_frag1_floats", "mdr_actor_frag2_floats", "mdr_actor_sample", "mdr_env_actor_sample", "mdr_env_actor_sample_links",
-    "mdr_discounted_returns", "mdr_tarmac_comm", "mdr_logits_sample",
+    "mdr_discounted_returns", "mdr_tarmac_comm", "mdr_logits_sample", "mdr_tarmac_comm_backward", "mdr_tarmac_comm_backward_workspace_bytes",
     "mdr_tarmac_frag_encode_floats", "mdr_tarmac_frag_proj_floats", "mdr_tarmac_frag_msg_floats", "mdr_tarmac_frag_head_floats",
     "mdr_tarmac_vec_floats", "mdr_tarmac_actor_workspace_bytes", "mdr_tarmac_actor_sample",
 )
@@ -227,6 +227,9 @@ def load():
         "mdr_discounted_returns": (C.c_int, [vp, vp, vp, C.c_float, i32, i64, vp, vp]),
         "mdr_tarmac_comm": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, u64, u64, vp, i32, vp, i64, vp]),
         "mdr_logits_sample": (C.c_int, [vp, i64, i64, u64, u64, vp, i32, vp, vp, vp, vp]),
+        "mdr_tarmac_comm_backward": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, u64, u64, vp, i32, vp, i64,
+                                               vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
+        "mdr_tarmac_comm_backward_workspace_bytes": (i64, [i64, i32, i32]),
         "mdr_tarmac_frag_encode_floats": (i64, [i32, i32]),
         "mdr_tarmac_frag_proj_floats": (i64, [i32, i32]),
         "mdr_tarmac_frag_msg_floats": (i64, [i32, i32]),

@@ -10,7 +10,22 @@ Two ways to evaluate the attention of ``TarMAC_Comm.forward``:
 ``attention="band"``   CUDA: in mode "neighbours" the mask is a circular band of c + 1 senders per receiver, so the attention is
                        O(E N c) and runs as ONE HIP kernel per hop (``mdr_tarmac_comm``, include/mdr_policy.h) on keys / values
                        staged in LDS; the five small per-agent MLPs stay library GEMMs into buffers allocated once, the softmax
-                       over the two logits and ``Categorical.sample`` are ``mdr_logits_sample``.  Inference only.
+                       over the two logits and ``Categorical.sample`` are ``mdr_logits_sample``.  No gradients by default;
+                       ``forward(..., differentiable=True)`` is the training path: the same MLPs as autograd ops around
+                       ``band_attention``, whose backward is ``mdr_tarmac_comm_backward`` - O(E N c) as the forward.
+
+The update step of the reference's learner (agents/tarmac_ppo.py:152-191) on a batch of ``collect_tarmac_rollout``, T steps of E envs::
+
+    state = ro["state"][:-1].view(T * E, N, F)                         # one stored env-step per batch row
+    action, old = ro["action"].view(T * E, N), ro["a_prob"].view(T * E, N)
+    for index in minibatches(T * E):                                   # the caller's sampler, optimiser and loss terms
+        probs = actor(state[index], seed=seed, step=update, differentiable=True)          # [B, N, 2], carries a grad_fn
+        ratio = probs.gather(2, action[index].unsqueeze(2)).squeeze(2) / old[index]       # tarmac_ppo.py:168-186
+        ...
+
+With ``comm_defect_prob > 0`` the defects of an update are fresh draws keyed by ``(seed, step)``, the batch row standing for the env -
+not the mask the rollout saw (the reference, too, redraws its mask at every forward call).  The backward of one forward call redraws
+that call's mask from the same key.
 
 ``FusedTarMACActor.from_module(actor)`` evaluates the same actor WITHOUT library GEMMs: the per-agent MLPs run as HIP kernels on the
 matrix cores in exact fp32 (``mdr_tarmac_actor_sample``, csrc/mdr_tarmac_mlp.hip) around the same attention kernel - three launches per
@@ -39,6 +54,110 @@ def band_offsets(nb_comm: int):
 
 def _mlp(n_in, n_hidden, n_out, act):
     return nn.Sequential(nn.Linear(n_in, n_hidden), act(), nn.Linear(n_hidden, n_out))
+
+
+_WORKSPACES = {}      # (agents, device) -> uint8 tensor: the statistics mdr_tarmac_comm_backward passes between its two kernels
+
+
+def _backward_workspace(nb_agents: int, num_key: int, num_value: int, dev) -> torch.Tensor:
+    key = (int(nb_agents), dev)
+    ws = _WORKSPACES.get(key)
+    n = nat.load().mdr_tarmac_comm_backward_workspace_bytes(nb_agents, num_key, num_value)
+    if n < 0:
+        raise RuntimeError("mdr_tarmac_comm_backward_workspace_bytes refused the shape")
+    if ws is None or ws.numel() < n:
+        ws = _WORKSPACES[key] = torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _ld(t: torch.Tensor) -> int:
+    """The stride in floats from one agent's row of ``t`` [E, N, D] to the next."""
+    E, N, D = t.shape
+    return t.stride(1) if N > 1 else t.stride(0) if E > 1 else D
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` [E, N, D] as the kernels read it, in place where they can: unit inner stride, one row stride over all agents that is a
+    multiple of 4 floats, 16-byte aligned rows.  Anything else is made contiguous first."""
+    E, N, D = t.shape
+    ld = _ld(t)
+    ok = t.stride(2) == 1 and ld >= D and ld % 4 == 0 and t.data_ptr() % 16 == 0 and (E == 1 or N == 1 or t.stride(0) == N * ld)
+    return t if ok else t.contiguous()
+
+
+class _BandAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, query, key, value, nb_comm, mode, defect_prob, seed, step, step_dev, hop):
+        E, N, K = query.shape
+        V = value.shape[2]
+        dev = query.device
+        q, k, v = _rows(query.detach()), _rows(key.detach()), _rows(value.detach())
+        out = torch.empty((E, N, V), dtype=torch.float32, device=dev)
+        # the backward redraws the mask from the forward's key: keep the value the counter offset had
+        step_dev = step_dev.clone() if step_dev is not None else None
+        ctx.key = (int(nb_comm), int(mode), float(defect_prob), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(hop))
+        ctx.step_dev = step_dev
+        lib = nat.load()
+        with torch.cuda.device(dev):
+            rc = lib.mdr_tarmac_comm(C.c_void_p(q.data_ptr()), _ld(q), C.c_void_p(k.data_ptr()), _ld(k), C.c_void_p(v.data_ptr()), _ld(v),
+                                     E, N, K, V, ctx.key[0], ctx.key[1], C.c_float(ctx.key[2]), C.c_uint64(ctx.key[3]), C.c_uint64(ctx.key[4]),
+                                     C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, ctx.key[5],
+                                     C.c_void_p(out.data_ptr()), V, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        nat.check(lib, None, rc, "mdr_tarmac_comm")
+        ctx.save_for_backward(q, k, v, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, out = ctx.saved_tensors
+        E, N, K = q.shape
+        V = v.shape[2]
+        dev = q.device
+        g = _rows(grad_out if grad_out.dtype == torch.float32 else grad_out.float())
+        dq, dk = torch.empty((E, N, K), dtype=torch.float32, device=dev), torch.empty((E, N, K), dtype=torch.float32, device=dev)
+        dv = torch.empty((E, N, V), dtype=torch.float32, device=dev)
+        ws = _backward_workspace(E * N, K, V, dev)
+        nb_comm, mode, prob, seed, step, hop = ctx.key
+        step_dev = ctx.step_dev
+        lib = nat.load()
+        with torch.cuda.device(dev):
+            rc = lib.mdr_tarmac_comm_backward(C.c_void_p(q.data_ptr()), _ld(q), C.c_void_p(k.data_ptr()), _ld(k), C.c_void_p(v.data_ptr()), _ld(v),
+                                              E, N, K, V, nb_comm, mode, C.c_float(prob), C.c_uint64(seed), C.c_uint64(step),
+                                              C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, hop,
+                                              C.c_void_p(out.data_ptr()), V, C.c_void_p(g.data_ptr()), _ld(g), C.c_void_p(dq.data_ptr()), K,
+                                              C.c_void_p(dk.data_ptr()), K, C.c_void_p(dv.data_ptr()), V, C.c_void_p(ws.data_ptr()),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        nat.check(lib, None, rc, "mdr_tarmac_comm_backward")
+        return dq, dk, dv, None, None, None, None, None, None, None
+
+
+def band_attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, nb_comm: int, mode: str = "neighbours",
+                   defect_prob: float = 0.0, seed: int = 0, step: int = 0, step_dev: Optional[torch.Tensor] = None,
+                   hop: int = 0) -> torch.Tensor:
+    """The banded masked attention of ``TarMAC_Comm.forward`` with a gradient: float32 CUDA ``query``, ``key`` [E, N, K] and
+    ``value`` [E, N, V] -> [E, N, V].  Forward ``mdr_tarmac_comm``, backward ``mdr_tarmac_comm_backward`` (include/mdr_policy.h; once
+    differentiable), both O(E N c); the backward redraws the forward's dead-sender mask from ``(seed, step, step_dev, hop)``, nothing
+    is stored but the operands and the result.  Views with unit inner stride and 16-byte aligned rows - the column blocks of a
+    packed projection - are read in place through their row stride; anything else is made contiguous first.  The backward's
+    workspace is cached per (agent count, device): run backwards of equal size on one stream at a time."""
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3:
+            raise ValueError("%s must be a float32 CUDA tensor [E, N, D]" % name)
+    if key.shape != query.shape or value.shape[:2] != query.shape[:2] or key.device != query.device or value.device != query.device:
+        raise ValueError("query and key [E, N, K] and value [E, N, V] must agree in E, N, K and share a device")
+    K, V = query.shape[2], value.shape[2]
+    if K == 0 or K % 4 or K > MAX_KEY or V == 0 or V % 4 or V > MAX_VALUE or query.shape[1] == 0:
+        raise ValueError("band attention: K a multiple of 4 <= %d, V a multiple of 4 <= %d, at least one agent" % (MAX_KEY, MAX_VALUE))
+    if mode not in MODES:
+        raise ValueError("mode must be 'neighbours' or 'none'")
+    if int(nb_comm) < 0 or not 0.0 <= float(defect_prob) <= 1.0 or not 0 <= int(hop) < MAX_HOPS:
+        raise ValueError("nb_comm >= 0, defect_prob in [0, 1], hop in 0..%d" % (MAX_HOPS - 1))
+    if mode == "neighbours" and min(int(nb_comm), query.shape[1] - 1) > MAX_COMM:
+        raise ValueError("band attention covers at most %d senders per receiver" % MAX_COMM)
+    if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.device != query.device):
+        raise ValueError("step_dev must be an int32 tensor on the device (env.device_time_index)")
+    return _BandAttention.apply(query, key, value, int(nb_comm), MODES[mode], float(defect_prob), seed, step, step_dev, int(hop))
 
 
 class TarMACComm(nn.Module):
@@ -251,6 +370,24 @@ class TarMACActor(nn.Module):
         self._lin(self.comm_hidden2action[0], cat, b["t"], torch.relu_)
         return self._lin(self.comm_hidden2action[2], b["t"], b["logits"])
 
+    def _band_logits_grad(self, obs: torch.Tensor, seed: int, step: int, step_dev) -> torch.Tensor:
+        """The band path as autograd ops: ``obs`` float32 [E, N, F] on the GPU -> logits [E, N, 2] with a grad_fn.  The MLPs are the
+        modules themselves (F.linear + activation, fresh tensors), every hop's attention is ``band_attention`` with the defects of
+        ``(seed, step, hop)``."""
+        if obs.dim() != 3 or obs.shape[2] != self.num_obs or obs.dtype != torch.float32:
+            raise ValueError("obs must be float32 [E, N, %d]" % self.num_obs)
+        self._check_band(obs.shape[1])
+        x = self.obs2hidden(obs)
+        if not self.with_comm:
+            return self.hidden2action(x)
+        h, comm = x, None
+        for hop in range(self.num_hops):
+            if hop > 0:
+                h = self.comm.msg_state2state(torch.cat([comm, h], dim=2))
+            key, value, query = self.comm.hidden2key(h), self.comm.hidden2value(h), self.comm.hidden2query(h)
+            comm = band_attention(query, key, value, self.number_agents_comm, self.comm_mode, self.comm_defect_prob, seed, step, step_dev, hop)
+        return self.comm_hidden2action(torch.cat([x, comm], dim=2))
+
     def _head(self, logits, seed, step, step_dev, greedy, want_probs, action=None, a_prob=None):
         dev = logits.device
         A = logits.shape[0]
@@ -271,12 +408,17 @@ class TarMACActor(nn.Module):
         return action, a_prob, probs
 
     # ----------------------------------------------------------------------------------------------------------------- public
-    def forward(self, obs: torch.Tensor, dead=None, seed: int = 0, step: int = 0, step_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``obs`` [E, N, F] -> probabilities [E, N, 2] (TarMAC_Actor.forward).  Band path: float32 on the GPU, no gradients;
-        ``seed`` / ``step`` key the defect draws.  Dense path: differentiable; ``dead`` as in ``dense_logits``."""
+    def forward(self, obs: torch.Tensor, dead=None, seed: int = 0, step: int = 0, step_dev: Optional[torch.Tensor] = None,
+                differentiable: bool = False) -> torch.Tensor:
+        """``obs`` [E, N, F] -> probabilities [E, N, 2] (TarMAC_Actor.forward).  Band path: float32 on the GPU, ``seed`` / ``step``
+        key the defect draws; no gradients unless ``differentiable`` - then the result backpropagates into every parameter and into
+        ``obs`` through ``band_attention`` (the update step: see the module docstring; with defects, fresh draws keyed by
+        ``(seed, step)`` with the batch row as the env).  Dense path: differentiable either way; ``dead`` as in ``dense_logits``."""
         if obs.dim() != 3:
             raise ValueError("TarMAC attends over the agents of an env: obs must be [E, N, F]")
         if dead is None and self._use_band(obs):
+            if differentiable:
+                return F.softmax(self._band_logits_grad(obs, seed, step, step_dev), dim=-1)
             logits = self._band_logits(obs, seed, step, step_dev)
             return self._head(logits, seed, step, step_dev, False, True)[2].view(obs.shape[0], obs.shape[1], 2)
         return F.softmax(self.dense_logits(obs, dead), dim=-1)
