@@ -142,6 +142,14 @@ int mdr_discounted_returns(const float *reward, const uint8_t *done, const float
 /* ---- TarMAC-PPO actor (agents/network.py:103-238, TarMAC_Comm / TarMAC_Actor): the attention and the head's last step.  The
  * actor's five small per-agent MLPs are either library GEMMs on the caller's side (mdr_amd/tarmac.py TarMACActor; these two kernels
  * are what no GEMM covers) or the matrix-core kernels of mdr_tarmac_actor_sample below, which runs the whole actor. */
+enum mdr_tarmac_precision {
+  MDR_TARMAC_FP32 = 0,  /* exact fp32 MLPs: the frag_* arrays hold floats in the order given at mdr_tarmac_actor_t */
+  MDR_TARMAC_BF16X3 = 1 /* every product of the MLPs' matrix layers as wh xh + wl xh + wh xl on operands split into a bf16 head and
+                           tail, fp32 accumulation from the fp32 bias (as MDR_ACTOR_BF16X3: probabilities within the bf16x3 contract,
+                           2e-3 relative + 2e-5, of the fp64 forward); activations, the head's last layer, the softmax, the draw and
+                           the attention stay fp32.  The frag_* arrays hold bf16 fragments */
+};
+
 enum mdr_tarmac_mode {
   MDR_TARMAC_NEIGHBOURS = 0, /* tarmac_comm_mode "neighbours": the circular band of make_masks (network.py:146-165) */
   MDR_TARMAC_NONE = 1        /* "none": an all-zero mask WITHOUT diagonal - the reference's 0 / 0 -> NaN -> 0: out = 0 */
@@ -197,8 +205,9 @@ int64_t mdr_tarmac_comm_backward_workspace_bytes(int64_t nb_agents, int32_t num_
 int mdr_logits_sample(const float *logits, int64_t ld, int64_t nb_agents, uint64_t seed, uint64_t step, const int32_t *step_dev,
                       int32_t greedy, uint8_t *action, float *a_prob, float *probs, void *stream);
 
-/* ---- The whole TarMAC actor through the C ABI: its per-agent MLPs on the matrix cores (csrc/mdr_tarmac_mlp.hip), exact fp32 on
- * v_mfma_f32_16x16x4_f32 with 16 agents per wavefront, the attention through the kernel behind the attention entry point above, once per hop.
+/* ---- The whole TarMAC actor through the C ABI: its per-agent MLPs on the matrix cores - exact fp32 on v_mfma_f32_16x16x4_f32 with
+ * 16 agents per wavefront (csrc/mdr_tarmac_mlp.hip), or bf16x3 on v_mfma_f32_16x16x32_bf16 with 32 (csrc/mdr_tarmac_mlp_bf16.hip), see
+ * mdr_tarmac_precision - and the attention through the kernel behind the attention entry point above, in fp32, once per hop.
  *
  * Notation: F = num_state, H = hidden, K = num_key, V = num_value, M = H + V; nb(n) = ceil(n / 16) blocks of 16 units, nbH = nb(H),
  * nbV = nb(V), nbM = nb(M); lane = 0..63, r = lane & 15, g = lane >> 4.  Wz is a torch weight matrix [out][in] zero-padded to whole
@@ -221,7 +230,22 @@ int mdr_logits_sample(const float *logits, int64_t ld, int64_t nb_agents, uint64
  *                 | hidden2query.2 [16] | hidden2key.2 [16] | hidden2value.2 [16 nbV] | msg_state2state.0 [16 nbM] | msg_state2state.2 [16 nbH]
  *                 | head.0 [16 nbH] | W3[0][u] - W3[1][u], u < 16 nbH | b3[0] - b3[1], 0, 0, 0      (W3, b3: the head's last layer)
  * Parts an actor does not have (no communication: frag_proj, frag_msg; one hop: frag_msg) may be NULL; their slots in vec are zeros.
- * All five pointers are device memory, 16-byte aligned. */
+ * All five pointers are device memory, 16-byte aligned.
+ *
+ * precision = MDR_TARMAC_BF16X3: vec is unchanged (fp32); the four frag_* arrays hold the same layers in the same sequence as bf16
+ * head / tail fragments of 8 bf16 (4-byte words, as mdr_actor_t's MDR_ACTOR_BF16X3).  A layer with S k-steps and nbO output blocks is
+ *   frag[s][mb < nbO][t][lane][j < 8] = split_t(Wz[16 mb + r][col(s, g, j)]),  t = 0 head / 1 tail     (512 words per (s, mb) pair)
+ * split_0(w) = bf16(w), split_1(w) = bf16(w - split_0(w)), round to nearest even; bf16 j of a lane in the low (even j) / high (odd j)
+ * half of word j / 2; a k-step covers 32 inputs, col(s, g, j) one of
+ *   rows(n, c0): c0 + 32 s + 8 g + j     S = ceil(n / 32): the input is n consecutive floats of the agent's row; zero where 32 s + 8 g + j >= n
+ *   regs(nbI):   16 (2 s + (j >> 2)) + 4 g + (j & 3)     S = ceil(nbI / 2): the input is the previous layer's accumulator of nbI blocks;
+ *                zero where 2 s + (j >> 2) >= nbI (the unused half of an odd last k-step) and past the layer's inputs
+ *   frag_encode = obs2hidden.0  rows(F, 0), nbH blocks  |  obs2hidden.2  regs(nbH), nbH blocks
+ *   frag_proj   = hidden2query.0 | hidden2key.0 | hidden2value.0  each regs(nbH), nbH blocks
+ *               | hidden2query.2  regs(nbH), 1 block | hidden2key.2  regs(nbH), 1 block | hidden2value.2  regs(nbH), nbV blocks
+ *   frag_msg    = msg_state2state.0: the k-steps rows(V, 0) - the comm columns - then, in k-steps of their own, rows(H, V), nbM blocks
+ *               | msg_state2state.2  regs(nbM), nbH blocks
+ *   frag_head   = comm_hidden2action.0  rows(M, 0), nbH blocks; without communication hidden2action.0  rows(H, 0) */
 typedef struct mdr_tarmac_actor {
   uint32_t struct_size;
   int32_t num_state;   /* F <= 64 */
@@ -234,7 +258,7 @@ typedef struct mdr_tarmac_actor {
   int32_t with_comm;   /* 0: obs2hidden -> hidden2action, no attention */
   float defect_prob;   /* comm_defect_prob, drawn as the attention entry point documents */
   int32_t greedy;      /* argmax, the first maximum on ties, no draw */
-  int32_t reserved0;
+  int32_t precision;   /* mdr_tarmac_precision; 0 (a zeroed field) = MDR_TARMAC_FP32.  Any other value: -1 from mdr_tarmac_actor_sample */
   const float *frag_encode;
   const float *frag_proj;
   const float *frag_msg;
@@ -248,6 +272,10 @@ int64_t mdr_tarmac_frag_proj_floats(int32_t hidden, int32_t num_value);
 int64_t mdr_tarmac_frag_msg_floats(int32_t hidden, int32_t num_value);
 int64_t mdr_tarmac_frag_head_floats(int32_t hidden, int32_t num_value, int32_t with_comm);
 int64_t mdr_tarmac_vec_floats(int32_t hidden, int32_t num_value);
+/* Size in 4-byte words of frag_encode (part 0), frag_proj (1), frag_msg (2) or frag_head (3) for the struct's shape, with_comm and
+ * precision (reads those fields only; host-only, no device call): with MDR_TARMAC_FP32 what the four helpers above return.  -1: a
+ * shape outside the struct's limits, another part or precision, a struct_size that is not this header's. */
+int64_t mdr_tarmac_frag_words(const mdr_tarmac_actor_t *actor, int32_t part);
 /* Bytes of device scratch a sample of nb_agents = nb_envs * nb_houses agents needs (reads the shape fields only): the head's input
  * [A][H + V], the packed projections [A][K + K + V] and, with more than one hop, the state [A][H]. */
 int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t *actor, int64_t nb_agents);
@@ -256,8 +284,9 @@ int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t *actor, int64_
  * `action` uint8 [A], `a_prob` float [A] (may be NULL), `probs` float [A][2] (may be NULL).  Enqueues 1 + hops + (hops - 1) + 1
  * kernels on `stream` (two without communication) and never synchronises or allocates; `workspace`: 16-byte aligned device memory
  * of the size above, owned by the caller, its contents free between calls.  The attention, its defect draws, the action draw,
- * `step_dev` and greedy are those of the two entry points above for the same (seed, step, agent).  Returns 0, -1 (invalid argument:
- * a NULL or misaligned pointer, a struct_size that is not this header's), -3 (HIP error) or -4 (a shape outside the limits in the
+ * `step_dev` and greedy are those of the two entry points above for the same (seed, step, agent), in either precision: the action is the
+ * draw compared with the kernel's own probs[0].  Returns 0, -1 (invalid argument:
+ * a NULL or misaligned pointer, a struct_size that is not this header's, a precision that is neither of the two), -3 (HIP error) or -4 (a shape outside the limits in the
  * struct above, or c > 64 after the clamp); on -1 and -4 nothing was launched and no output touched. */
 int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t *actor, const float *obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed,
                             uint64_t step, const int32_t *step_dev, void *workspace, uint8_t *action, float *a_prob, float *probs,

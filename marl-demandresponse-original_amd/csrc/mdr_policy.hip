@@ -23,6 +23,7 @@
 
 #include "../../include/mdr.h"
 #include "../../include/mdr_policy.h"
+#include "mdr_bf16_split.h"
 #include "mdr_device.h"
 #include "mdr_draw.h"
 #include "mdr_kernels.h"
@@ -353,38 +354,8 @@ __global__ __launch_bounds__(64 * WAVES16) void k_actor_sample16(ActorArgs a) {
 // k-step.  A[row = lane & 15][k = 8 (lane >> 4) + j], B[k = 8 (lane >> 4) + j][col = lane & 15], j < 8; C/D as 16x16x4.
 // Layer 1: k-step s, lane group g, element j <-> input feature (4 s + g) 8 + j (a contiguous run per lane).
 // Layer 2: k-step s covers the row blocks 2 s and 2 s + 1 of layer 1: element j <-> row 16 (2 s + (j >> 2)) + 4 g + (j & 3),
-// i.e. register [2 s + (j >> 2)][j & 3] of the lane itself - again no LDS and no lane movement for the activations.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// (bf16(hi) << 16) | bf16(lo), round to nearest even.  Inline assembly is opaque to hipcc's hazard recogniser: a VGPR written here and
-// read as an MFMA operand by the very next instruction needs two wait states that nobody else inserts (round 1 shipped this
-// statement without them; the stale-operand reads surfaced when a new kernel variant changed the instruction schedule:
-// half the agents of the second column block came out with garbage logits).  Hence the `s_nop 1` INSIDE the string.  The
-// plain vector conversion (__builtin_convertvector to bf16x2) is hazard-safe too and selects the same instruction, but lets the
-// scheduler hoist the conversions until k_actor_sample_bf16 spills (1.1 KB of scratch per lane, 6x slower).
-// four packed conversions in ONE statement: the last write is two wait states away from whatever follows the statement, the
-// earlier ones further - one `s_nop 1` instead of four
-__device__ __forceinline__ void cvt_pk_bf16_x4(const float* v, uint32_t* out) {
-  asm("v_cvt_pk_bf16_f32 %0, %4, %5\n\tv_cvt_pk_bf16_f32 %1, %6, %7\n\tv_cvt_pk_bf16_f32 %2, %8, %9\n\tv_cvt_pk_bf16_f32 %3, %10, %11\n\ts_nop 1"
-      : "=&v"(out[0]), "=&v"(out[1]), "=&v"(out[2]), "=&v"(out[3])
-      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
-}
-
-// eight fp32 values -> their bf16 head and tail fragments
-__device__ __forceinline__ void split8(const float* v, uint4& hi, uint4& lo) {
-  uint32_t h[4], l[4];
-  cvt_pk_bf16_x4(v, h);
-  float res[8];
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {   // x - float(bf16(x)); scalar subtractions: packed f32 VALU issues slowly beside MFMAs (MI355X_MICROARCH.md)
-    res[2 * p] = v[2 * p] - __uint_as_float(h[p] << 16);
-    res[2 * p + 1] = v[2 * p + 1] - __uint_as_float(h[p] & 0xFFFF0000u);
-  }
-  cvt_pk_bf16_x4(res, l);
-  hi = uint4{h[0], h[1], h[2], h[3]};
-  lo = uint4{l[0], l[1], l[2], l[3]};
-}
-
+// i.e. register [2 s + (j >> 2)][j & 3] of the lane itself - again no LDS and no lane movement for the activations.  The split
+// itself (cvt_pk_bf16_x4, split8) is mdr_bf16_split.h's.
 constexpr int WAVESB = 8;    // 2 per SIMD: two column blocks of accumulators (~200 registers per lane)
 constexpr int NCB = 2;       // 16-agent column blocks per wavefront: every weight fragment read from LDS feeds NCB MFMAs (with one block
                              // the fragment reads, 84 KB per 16 agents, kept the LDS busier than the matrix pipe)

@@ -17,6 +17,8 @@
 // that stage their weights ONCE into LDS in fragment order (up to ~125 KB: one workgroup per CU) and stride over the tiles.  Rows
 // are addressed with 64-bit offsets: no 4 GiB slicing.
 //
+// mdr_tarmac_actor_t.precision = MDR_TARMAC_BF16X3 takes the same chain through the kernels of mdr_tarmac_mlp_bf16.hip.
+//
 // Two instantiations per kernel: the block counts of the reference's sizes (H = 64, K <= 16, V <= 16: 4 / 1 / 5 blocks of 16 units
 // for H / V / H + V) with compile-time fragment strides, 16 waves per workgroup in under 128 registers and no scratch; and a general
 // form compiled for the largest covered shape whose loops stop at the run-time block counts, 8 waves per workgroup.
@@ -24,108 +26,9 @@
 
 #include <cstdint>
 
-#include "../../include/mdr.h"
-#include "../../include/mdr_policy.h"
-#include "mdr_device.h"
-#include "mdr_draw.h"
+#include "mdr_tarmac_mlp.h"
 
 namespace {
-
-using mdr::action_uniform;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int WAVES = 16;        // per workgroup, the forms of the reference's sizes: four per SIMD in 128 registers
-constexpr int WAVES_GEN = 8;     // the general forms: two per SIMD in 256 registers
-constexpr int MAX_F = 64, MAX_H = 64, MAX_K = 16, MAX_V = 32, MAX_HOPS = 4, MAX_C = 64;
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
-
-__host__ __device__ inline int blocks(int n) { return (n + 15) / 16; }
-
-// Offsets (floats) into mdr_tarmac_actor_t.vec: every bias zero-padded to whole 16-unit blocks, in unit order - lane group g reads
-// the four units 16 mb + 4 g + reg of block mb as one float4.
-struct VecLayout {
-  int o1, o2, p1, q2, k2, v2, m1, m2, h1, wd, b3, total;
-};
-
-__host__ __device__ inline VecLayout vec_layout(int mbh, int mbv, int mbm) {
-  VecLayout L;
-  const int nH = 16 * mbh;
-  L.o1 = 0;
-  L.o2 = nH;
-  L.p1 = 2 * nH;             // query | key | value, first layers
-  L.q2 = 5 * nH;
-  L.k2 = L.q2 + 16;
-  L.v2 = L.k2 + 16;
-  L.m1 = L.v2 + 16 * mbv;
-  L.m2 = L.m1 + 16 * mbm;
-  L.h1 = L.m2 + nH;
-  L.wd = L.h1 + nH;          // W3[0] - W3[1]
-  L.b3 = L.wd + nH;          // b3[0] - b3[1], 0, 0, 0
-  L.total = L.b3 + 4;
-  return L;
-}
-
-struct MlpArgs {
-  const float* fa;        // encode: frag_encode; rehop: frag_msg; head: frag_head
-  const float* fp;        // frag_proj
-  const float* vec;
-  const float* in0;       // encode: obs rows; rehop: the comm columns of cat; head: cat
-  const float* in1;       // rehop: h (cat's x columns for the first re-hop, state afterwards)
-  int64_t ld0, ld1;
-  float* cat;
-  float* qkv;
-  float* state;
-  int64_t ldcat, ldqkv;
-  uint8_t* action;
-  float* a_prob;
-  float* probs;
-  int64_t A, ntiles;
-  int D0, S0, S1;         // floats per in0 row that are features; k-steps fed from in0 / in1 (lane group g holds features [g S, g S + S))
-  int vec0, vec1;         // the group's S features are whole aligned float4s
-  int H, K, V;
-  int mbh, mbv, mbm;
-  int with_comm, greedy;
-  int na, np, nvec;       // floats staged from fa / fp / vec
-  uint32_t k0, k1, step_lo, step_hi;
-  const int32_t* step_dev;
-};
-
-// A lane-dependent value hidden from loop-invariant code motion (mdr_policy.hip): every LDS read of the tile loop - weights and
-// biases, none of which change after the staging - is addressed from it, so that hipcc re-reads them where they are used instead
-// of hoisting a hundred of them out of the loop into registers the loop does not have.
-__device__ __forceinline__ int tile_local(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-__device__ __forceinline__ float relu(float x) {      // mdr_policy.hip: max on the bit pattern, one instruction
-  const int b = __builtin_bit_cast(int, x);
-  return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
-
-// tanh to a few ulp at every magnitude: 1 - 2 / (exp(2 |x|) + 1) has an ABSOLUTE error of ~1e-7 (the fast exponential's relative
-// error |2 x| 2^-24 is damped by 2 e / (e + 1)^2 <= 1 / 2), which near 0 would be a large relative one - there the odd series
-// x (1 - x^2 / 3 + 2 x^4 / 15) is used, whose first dropped term 17 x^6 / 315 is below 2^-24 for |x| < 0.1.
-__device__ __forceinline__ float tanh_f(float x) {
-  const float ax = fabsf(x);
-  const float x2 = x * x;
-  const float small = x * fmaf(x2, fmaf(x2, 2.0f / 15.0f, -1.0f / 3.0f), 1.0f);
-  const float e = __expf(2.0f * ax);                        // inf beyond ~44: 2 / inf = 0, tanh = 1
-  const float big = copysignf(1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f), x);
-  return ax < 0.1f ? small : big;
-}
-
-template <int ACT>
-__device__ __forceinline__ float activate(float x) {
-  return ACT == ACT_RELU ? relu(x) : (ACT == ACT_TANH ? tanh_f(x) : x);
-}
-
-__device__ __forceinline__ void stage(float* dst, const float* src, int n, int tid) {
-  const int stride = (int)blockDim.x * 4;      // n a multiple of 4, both 16-byte aligned
-  for (int i = tid * 4; i < n; i += stride) *reinterpret_cast<float4*>(dst + i) = *reinterpret_cast<const float4*>(src + i);
-}
 
 // The A operands of one k-step: a lane's weight for each of the mb output blocks.  Stored in chunks of four blocks,
 // [chunk j][lane][i < w_j], w_j = min(4, mb - 4 j): a full chunk is one ds_read_b128 per lane, a chunk of one block has consecutive
@@ -389,19 +292,6 @@ int64_t proj_floats(int H, int V) { return (int64_t)4 * blocks(H) * 64 * (3 * bl
 int64_t msg_floats(int H, int V) { return (int64_t)((V + H) / 4) * 64 * blocks(H + V) + (int64_t)4 * blocks(H + V) * 64 * blocks(H); }
 int64_t head_floats(int H, int V, int with_comm) { return (int64_t)((H + (with_comm ? V : 0)) / 4) * 64 * blocks(H); }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-template <typename K>
-int launch(K kernel, int waves, const MlpArgs& a, int lds_floats, int cus, hipStream_t s) {
-  const size_t lds_bytes = (size_t)lds_floats * sizeof(float);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-    return MDR_ERR_HIP;
-  const int64_t want = (a.ntiles + waves - 1) / waves;
-  const unsigned grid = (unsigned)(want < cus ? want : cus);      // persistent: the weights are staged once per workgroup
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds_bytes, s, a);
-  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
-}
-
 }  // namespace
 
 extern "C" {
@@ -423,6 +313,17 @@ int64_t mdr_tarmac_vec_floats(int32_t hidden, int32_t num_value) {
   return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V) ? vec_layout(blocks(hidden), blocks(num_value), blocks(hidden + num_value)).total : -1;
 }
 
+int64_t mdr_tarmac_frag_words(const mdr_tarmac_actor_t* actor, int32_t part) {
+  if (!actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || part < 0 || part > 3) return -1;
+  const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value, wc = actor->with_comm != 0;
+  if (!shape_positive(F, H, K, V) || !shape_covered(F, H, K, V)) return -1;
+  if (actor->precision == MDR_TARMAC_FP32)
+    return part == 0 ? encode_floats(F, H) : part == 1 ? proj_floats(H, V) : part == 2 ? msg_floats(H, V) : head_floats(H, V, wc);
+  if (actor->precision == MDR_TARMAC_BF16X3)
+    return part == 0 ? encode_words(F, H) : part == 1 ? proj_words(H, V) : part == 2 ? msg_words(H, V) : head_words(H, V, wc);
+  return -1;
+}
+
 int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t* actor, int64_t nb_agents) {
   if (!actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || nb_agents < 0) return -1;
   const int H = actor->hidden, K = actor->num_key, V = actor->num_value;
@@ -441,6 +342,7 @@ int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, i
   if (!shape_positive(F, H, K, V) || hops < 1 || actor->nb_comm < 0) return MDR_ERR_INVALID;
   if (actor->mode != MDR_TARMAC_NEIGHBOURS && actor->mode != MDR_TARMAC_NONE) return MDR_ERR_INVALID;
   if (!(actor->defect_prob >= 0.0f && actor->defect_prob <= 1.0f)) return MDR_ERR_INVALID;
+  if (actor->precision != MDR_TARMAC_FP32 && actor->precision != MDR_TARMAC_BF16X3) return MDR_ERR_INVALID;
   if (!actor->frag_encode || !actor->frag_head || !actor->vec) return MDR_ERR_INVALID;
   if (wc && (!actor->frag_proj || (hops > 1 && !actor->frag_msg))) return MDR_ERR_INVALID;
   if (!aligned16(workspace) || !aligned16(actor->frag_encode) || !aligned16(actor->frag_head) || !aligned16(actor->vec) ||
@@ -455,6 +357,8 @@ int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, i
   hipStream_t s = (hipStream_t)stream;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  if (actor->precision == MDR_TARMAC_BF16X3)
+    return mdr::tarmac_sample_bf16(actor, obs, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, cus, stream);
 
   const int mbh = blocks(H), mbv = blocks(V), mbm = blocks(H + V);
   const VecLayout L = vec_layout(mbh, mbv, mbm);

@@ -1,0 +1,423 @@
+// TarMAC-PPO actor, the per-agent MLPs of mdr_tarmac_mlp.hip on v_mfma_f32_16x16x32_bf16 (mdr_tarmac_actor_t.precision =
+// MDR_TARMAC_BF16X3): every product is Wh xh + Wl xh + Wh xl on operands split into a bf16 head and tail (mdr_bf16_split.h), fp32
+// accumulators that start from the fp32 bias, as k_actor_sample_bf16 (mdr_policy.hip).  Activations, the head's last layer, the
+// softmax and the draw are the fp32 vector code of the exact forms; mdr_tarmac_comm runs unchanged on the fp32 workspace.
+//
+// Operand layout: A[row = lane & 15][k = 8 g + j], B[k = 8 g + j][col = lane & 15], g = lane >> 4, j < 8; C/D col = lane & 15, row =
+// 4 g + reg.  A k-step fed from memory covers 32 consecutive floats of the agent's row, lane group g its floats [32 s + 8 g, + 8).  A
+// k-step fed from registers covers the output blocks 2 s and 2 s + 1 of the previous layer: element j is the lane's own accumulator
+// register [2 s + (j >> 2)][j & 3] - no LDS and no lane movement for the activations.  Whatever a k-step covers past the end of its
+// input (a row's tail, the second half of an odd block count) is an explicit zero on both sides: the fragments carry zero weights
+// there, and the lane builds a zero operand instead of reading on.
+//
+// A wavefront takes NCOL = 2 column blocks of 16 agents per tile: every weight fragment read from LDS feeds two sets of MFMAs.
+// Fragments in LDS: 2 KiB per (k-step, output block) pair, [t = head | tail][lane][8 bf16] - 94 KB (encode) and 117 KB (rehop) at
+// the reference's sizes, 98 / 127 KB at the largest covered shape: one workgroup of 8 waves per CU, two waves per SIMD.
+//
+// Two instantiations per kernel, as the fp32 forms: the block counts of the reference's sizes (H = 64, V <= 16) at compile time, and a
+// general form compiled for the largest covered shape whose loops stop at the run-time block counts.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "mdr_bf16_split.h"
+#include "mdr_tarmac_mlp.h"
+
+namespace {
+
+constexpr int WAVES_BF16 = 8;      // per workgroup: two per SIMD, up to 256 registers
+constexpr int NCOL = 2;         // 16-agent column blocks per wavefront and tile
+
+template <int MB>
+__device__ __forceinline__ void init_bias(const float* bias, int g, int mb, f32x4 (&out)[NCOL][MB]) {
+#pragma unroll
+  for (int b = 0; b < MB; ++b) {
+    const f32x4 v = b < mb ? *reinterpret_cast<const f32x4*>(bias + 16 * b + 4 * g) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) out[c][b] = v;
+  }
+}
+
+// out += W . B for one k-step: `step` -> its mbo (k-step, block) pairs, each [head | tail][64 lanes] fragments of 8 bf16
+template <int MBO, bool EXACT>
+__device__ __forceinline__ void mma_step(const uint4* step, int mbo, int lane, const bf16x8 (&Bh)[NCOL], const bf16x8 (&Bl)[NCOL],
+                                         f32x4 (&out)[NCOL][MBO]) {
+#pragma unroll
+  for (int mb = 0; mb < MBO; ++mb) {
+    if (EXACT || mb < mbo) {
+      const bf16x8 Ah = __builtin_bit_cast(bf16x8, step[(mb * 2 + 0) * 64 + lane]);
+      const bf16x8 Al = __builtin_bit_cast(bf16x8, step[(mb * 2 + 1) * 64 + lane]);
+#pragma unroll
+      for (int c = 0; c < NCOL; ++c) {
+        out[c][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bh[c], out[c][mb], 0, 0, 0);
+        out[c][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, Bh[c], out[c][mb], 0, 0, 0);
+        out[c][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bl[c], out[c][mb], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// The B operands of k-step s fed from the previous layer's accumulators: blocks 2 s and 2 s + 1, zero past the last block
+template <int MBI, int ACT>
+__device__ __forceinline__ void split_regs(const f32x4 (&in)[NCOL][MBI], int s, bf16x8 (&Bh)[NCOL], bf16x8 (&Bl)[NCOL]) {
+#pragma unroll
+  for (int c = 0; c < NCOL; ++c) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int b = 2 * s + (j >> 2);
+      v[j] = b < MBI ? activate<ACT>(in[c][b < MBI ? b : 0][j & 3]) : 0.0f;
+    }
+    uint4 bh, bl;
+    split8(v, bh, bl);
+    Bh[c] = __builtin_bit_cast(bf16x8, bh);
+    Bl[c] = __builtin_bit_cast(bf16x8, bl);
+  }
+}
+
+// The B operands of a k-step fed from memory: floats [first, first + 8) of each column block's row of D floats, zero past the row.
+// `vec`: every row is 16-byte aligned (first is a multiple of 8).
+__device__ __forceinline__ void split_rows(const float* const (&row)[NCOL], int first, int D, int vec, bf16x8 (&Bh)[NCOL], bf16x8 (&Bl)[NCOL]) {
+#pragma unroll
+  for (int c = 0; c < NCOL; ++c) {
+    float v[8];
+    if (vec && first + 8 <= D) {
+      const float4 lo = *reinterpret_cast<const float4*>(row[c] + first);
+      const float4 hi = *reinterpret_cast<const float4*>(row[c] + first + 4);
+      v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w, v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = first + j < D ? row[c][first + j] : 0.0f;
+    }
+    uint4 bh, bl;
+    split8(v, bh, bl);
+    Bh[c] = __builtin_bit_cast(bf16x8, bh);
+    Bl[c] = __builtin_bit_cast(bf16x8, bl);
+  }
+}
+
+// The agents of tile t: column block c holds agents (t NCOL + c) 16 + r; rows past the last agent are read at the last agent's
+struct Tile {
+  int64_t agent[NCOL], ac[NCOL];
+  bool valid[NCOL];
+};
+
+__device__ __forceinline__ Tile tile_of(int64_t t, int r, int64_t A) {
+  Tile T;
+#pragma unroll
+  for (int c = 0; c < NCOL; ++c) {
+    T.agent[c] = (t * NCOL + c) * 16 + r;
+    T.valid[c] = T.agent[c] < A;
+    T.ac[c] = T.valid[c] ? T.agent[c] : A - 1;
+  }
+  return T;
+}
+
+template <int MB>
+__device__ __forceinline__ void store_blocks(const f32x4 (&x)[NCOL][MB], float* const (&row)[NCOL], const bool (&valid)[NCOL], int n, int g) {
+#pragma unroll
+  for (int c = 0; c < NCOL; ++c)
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+      if (valid[c] && 16 * mb + 4 * g < n) *reinterpret_cast<f32x4*>(row[c] + 16 * mb + 4 * g) = x[c][mb];
+}
+
+// hidden2query | hidden2key | hidden2value on the hidden state a lane holds, which is split ONCE for the three first layers.
+// frag_proj: the three first layers [p < 3][sh k-steps][mbh pairs], then the second layers of query (1 block), key (1), value (mbv).
+template <int MBH, int MBV, bool EXACT>
+__device__ __forceinline__ void projections(const uint4* fp, const float* vec, const VecLayout& L, const f32x4 (&h)[NCOL][MBH], int mbh, int mbv,
+                                            int K, int V, float* const (&qkv_row)[NCOL], const bool (&valid)[NCOL], int lane) {
+  constexpr int SH = (MBH + 1) / 2;
+  const int g = lane >> 4;
+  const int sh = EXACT ? SH : ksteps_regs(mbh);
+  bf16x8 Hh[SH][NCOL], Hl[SH][NCOL];
+#pragma unroll
+  for (int s = 0; s < SH; ++s)
+    if (EXACT || s < sh) split_regs<MBH, ACT_NONE>(h, s, Hh[s], Hl[s]);
+  const int n1 = sh * mbh * 128;      // uint4 of one first layer
+  const uint4* f2 = fp + 3 * n1;
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    f32x4 t[NCOL][MBH];
+    init_bias<MBH>(vec + L.p1 + p * 16 * mbh, g, mbh, t);
+#pragma unroll
+    for (int s = 0; s < SH; ++s)
+      if (EXACT || s < sh) mma_step<MBH, EXACT>(fp + p * n1 + s * mbh * 128, mbh, lane, Hh[s], Hl[s], t);
+    if (p < 2) {
+      f32x4 o[NCOL][1];
+      init_bias<1>(vec + (p == 0 ? L.q2 : L.k2), g, 1, o);
+#pragma unroll
+      for (int s = 0; s < SH; ++s)
+        if (EXACT || s < sh) {
+          bf16x8 Bh[NCOL], Bl[NCOL];
+          split_regs<MBH, ACT_TANH>(t, s, Bh, Bl);
+          mma_step<1, true>(f2 + (p * sh + s) * 128, 1, lane, Bh, Bl, o);
+        }
+      float* dst[NCOL];
+#pragma unroll
+      for (int c = 0; c < NCOL; ++c) dst[c] = qkv_row[c] + p * K;
+      store_blocks<1>(o, dst, valid, K, g);
+    } else {
+      f32x4 o[NCOL][MBV];
+      init_bias<MBV>(vec + L.v2, g, mbv, o);
+#pragma unroll
+      for (int s = 0; s < SH; ++s)
+        if (EXACT || s < sh) {
+          bf16x8 Bh[NCOL], Bl[NCOL];
+          split_regs<MBH, ACT_TANH>(t, s, Bh, Bl);
+          mma_step<MBV, EXACT>(f2 + (2 * sh + s * mbv) * 128, mbv, lane, Bh, Bl, o);
+        }
+      float* dst[NCOL];
+#pragma unroll
+      for (int c = 0; c < NCOL; ++c) dst[c] = qkv_row[c] + 2 * K;
+      store_blocks<MBV>(o, dst, valid, V, g);
+    }
+  }
+}
+
+// frag_encode: obs2hidden.0 [S0 = ceil(F / 32) k-steps fed from the obs row][mbh pairs], then obs2hidden.2 [ceil(mbh / 2)][mbh]
+template <int MBH, int MBV, bool EXACT>
+__global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_bf16(MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* fa = lds;
+  float* fp = fa + a.na;
+  float* vec = fp + a.np;
+  const int tid = threadIdx.x;
+  stage(fa, a.fa, a.na, tid);
+  if (a.with_comm) stage(fp, a.fp, a.np, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  __syncthreads();
+  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
+  const uint4* fp4 = reinterpret_cast<const uint4*>(fp);
+  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
+  constexpr int SH = (MBH + 1) / 2;
+  const int sh = EXACT ? SH : ksteps_regs(mbh);
+  const VecLayout L = vec_layout(mbh, mbv, a.mbm);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  const int64_t wave = (int64_t)blockIdx.x * WAVES_BF16 + (tid >> 6), nwaves = (int64_t)gridDim.x * WAVES_BF16;
+  const uint4* f2 = fa4 + a.S0 * mbh * 128;
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const Tile T = tile_of(t, r, a.A);
+    const float* row[NCOL];
+    float* cat_row[NCOL];
+    float* qkv_row[NCOL];
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) {
+      row[c] = a.in0 + T.ac[c] * a.ld0;
+      cat_row[c] = a.cat + T.ac[c] * a.ldcat;
+      qkv_row[c] = a.qkv + T.ac[c] * a.ldqkv;
+    }
+    f32x4 t1[NCOL][MBH], x[NCOL][MBH];
+    init_bias<MBH>(vec + L.o1, g, mbh, t1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      if (s < a.S0) {
+        bf16x8 Bh[NCOL], Bl[NCOL];
+        split_rows(row, 32 * s + 8 * g, a.D0, a.vec0, Bh, Bl);
+        mma_step<MBH, EXACT>(fa4 + s * mbh * 128, mbh, lane, Bh, Bl, t1);
+      }
+    init_bias<MBH>(vec + L.o2, g, mbh, x);
+#pragma unroll
+    for (int s = 0; s < SH; ++s)
+      if (EXACT || s < sh) {
+        bf16x8 Bh[NCOL], Bl[NCOL];
+        split_regs<MBH, ACT_RELU>(t1, s, Bh, Bl);
+        mma_step<MBH, EXACT>(f2 + s * mbh * 128, mbh, lane, Bh, Bl, x);
+      }
+    store_blocks<MBH>(x, cat_row, T.valid, a.H, g);
+    if (a.with_comm) projections<MBH, MBV, EXACT>(fp4, vec, L, x, mbh, mbv, a.K, a.V, qkv_row, T.valid, lane);
+  }
+}
+
+// frag_msg: msg_state2state.0 [S0 = ceil(V / 32) k-steps fed from the comm columns, then S1 = ceil(H / 32) fed from h][mbm pairs],
+// then msg_state2state.2 [ceil(mbm / 2)][mbh]
+template <int MBH, int MBV, int MBM, bool EXACT>
+__global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_rehop_bf16(MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* fa = lds;
+  float* fp = fa + a.na;
+  float* vec = fp + a.np;
+  const int tid = threadIdx.x;
+  stage(fa, a.fa, a.na, tid);
+  stage(fp, a.fp, a.np, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  __syncthreads();
+  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
+  const uint4* fp4 = reinterpret_cast<const uint4*>(fp);
+  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv, mbm = EXACT ? MBM : a.mbm;
+  constexpr int SM = (MBM + 1) / 2;
+  const int sm = EXACT ? SM : ksteps_regs(mbm);
+  const VecLayout L = vec_layout(mbh, mbv, mbm);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  const int64_t wave = (int64_t)blockIdx.x * WAVES_BF16 + (tid >> 6), nwaves = (int64_t)gridDim.x * WAVES_BF16;
+  const uint4* f1h = fa4 + a.S0 * mbm * 128;
+  const uint4* f2 = f1h + a.S1 * mbm * 128;
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const Tile T = tile_of(t, r, a.A);
+    const float* rc[NCOL];
+    const float* rh[NCOL];
+    float* st_row[NCOL];
+    float* qkv_row[NCOL];
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) {
+      rc[c] = a.in0 + T.ac[c] * a.ld0;
+      rh[c] = a.in1 + T.ac[c] * a.ld1;
+      st_row[c] = a.state + T.ac[c] * (int64_t)a.H;
+      qkv_row[c] = a.qkv + T.ac[c] * a.ldqkv;
+    }
+    f32x4 m[NCOL][MBM], h[NCOL][MBH];
+    init_bias<MBM>(vec + L.m1, g, mbm, m);
+    {
+      bf16x8 Bh[NCOL], Bl[NCOL];      // V <= 32: one k-step
+      split_rows(rc, 8 * g, a.V, a.vec0, Bh, Bl);
+      mma_step<MBM, EXACT>(fa4, mbm, lane, Bh, Bl, m);
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      if (s < a.S1) {
+        bf16x8 Bh[NCOL], Bl[NCOL];
+        split_rows(rh, 32 * s + 8 * g, a.H, a.vec1, Bh, Bl);
+        mma_step<MBM, EXACT>(f1h + s * mbm * 128, mbm, lane, Bh, Bl, m);
+      }
+    init_bias<MBH>(vec + L.m2, g, mbh, h);
+#pragma unroll
+    for (int s = 0; s < SM; ++s)
+      if (EXACT || s < sm) {
+        bf16x8 Bh[NCOL], Bl[NCOL];
+        split_regs<MBM, ACT_TANH>(m, s, Bh, Bl);
+        mma_step<MBH, EXACT>(f2 + s * mbh * 128, mbh, lane, Bh, Bl, h);
+      }
+    store_blocks<MBH>(h, st_row, T.valid, a.H, g);
+    projections<MBH, MBV, EXACT>(fp4, vec, L, h, mbh, mbv, a.K, a.V, qkv_row, T.valid, lane);
+  }
+}
+
+// frag_head: [S0 = ceil(D / 32) k-steps fed from the row [x, comm] as it lies in cat][mbh pairs], D = H + V (H without communication)
+template <int MBH, bool EXACT>
+__global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_head_bf16(MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* fa = lds;
+  float* vec = fa + a.na;
+  const int tid = threadIdx.x;
+  stage(fa, a.fa, a.na, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  __syncthreads();
+  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
+  const int mbh = EXACT ? MBH : a.mbh;
+  const VecLayout L = vec_layout(mbh, a.mbv, a.mbm);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  const int64_t wave = (int64_t)blockIdx.x * WAVES_BF16 + (tid >> 6), nwaves = (int64_t)gridDim.x * WAVES_BF16;
+  const float bias3 = vec[L.b3];
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const Tile T = tile_of(t, r, a.A);
+    const float* row[NCOL];
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) row[c] = a.in0 + T.ac[c] * a.ld0;
+    f32x4 acc[NCOL][MBH];
+    init_bias<MBH>(vec + L.h1, g, mbh, acc);
+#pragma unroll
+    for (int s = 0; s < 3; ++s)      // D <= 96
+      if (s < a.S0) {
+        bf16x8 Bh[NCOL], Bl[NCOL];
+        split_rows(row, 32 * s + 8 * g, a.D0, a.vec0, Bh, Bl);
+        mma_step<MBH, EXACT>(fa4 + s * mbh * 128, mbh, lane, Bh, Bl, acc);
+      }
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) {      // the last layer, the softmax and the draw: the fp32 form's vector code
+      float d = 0.0f;
+#pragma unroll
+      for (int mb = 0; mb < MBH; ++mb)
+        if (EXACT || mb < mbh) {
+          const f32x4 w = *reinterpret_cast<const f32x4*>(vec + L.wd + 16 * mb + 4 * g);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) d = fmaf(w[i], relu(acc[c][mb][i]), d);
+        }
+      d += __shfl_xor(d, 16);
+      d += __shfl_xor(d, 32);
+      d += bias3;
+      const float p0 = 1.0f / (1.0f + expf(-d));      // mdr_logits_sample's softmax over two logits
+      const float p1 = 1.0f / (1.0f + expf(d));
+      if (g == 0 && T.valid[c]) {
+        const int64_t agent = T.agent[c];
+        int act;
+        if (a.greedy) {
+          act = d >= 0.0f ? 0 : 1;      // argmax keeps the first maximum, as torch.argmax
+        } else {
+          const float u = action_uniform(mdr::action_word(agent, a.step_lo, a.step_hi, a.step_dev, a.k0, a.k1));
+          act = u < p0 ? 0 : 1;
+        }
+        a.action[agent] = (uint8_t)act;
+        if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
+        if (a.probs) {
+          a.probs[agent * 2] = p0;
+          a.probs[agent * 2 + 1] = p1;
+        }
+      }
+    }
+  }
+}
+
+}  // namespace
+
+namespace mdr {
+
+int tarmac_sample_bf16(const mdr_tarmac_actor_t* actor, const float* obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed, uint64_t step,
+                       const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, int cus, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value;
+  const int hops = actor->num_hops, wc = actor->with_comm != 0;
+  const int64_t A = (int64_t)nb_envs * nb_houses;
+  const int mbh = blocks(H), mbv = blocks(V), mbm = blocks(H + V);
+  const VecLayout L = vec_layout(mbh, mbv, mbm);
+  const bool exact = mbh == 4 && mbv == 1 && (!wc || hops == 1 || mbm == 5);
+  const int64_t ldcat = wc ? H + V : H, ldqkv = K + K + V;
+  float* cat = static_cast<float*>(workspace);
+  float* qkv = cat + A * ldcat;
+  float* state = qkv + A * ldqkv;
+
+  MlpArgs a{};
+  a.vec = actor->vec, a.nvec = L.total;
+  a.cat = cat, a.qkv = qkv, a.state = state, a.ldcat = ldcat, a.ldqkv = ldqkv;
+  a.action = action, a.a_prob = a_prob, a.probs = probs;
+  a.A = A, a.ntiles = (A + 16 * NCOL - 1) / (16 * NCOL);
+  a.H = H, a.K = K, a.V = V, a.mbh = mbh, a.mbv = mbv, a.mbm = mbm;
+  a.with_comm = wc, a.greedy = actor->greedy != 0;
+  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.step_lo = (uint32_t)step, a.step_hi = (uint32_t)(step >> 32);
+  a.step_dev = step_dev;
+  a.np = wc ? (int)proj_words(H, V) : 0;
+
+  // ---- obs -> x (-> qkv)
+  a.fa = actor->frag_encode, a.fp = actor->frag_proj, a.na = (int)encode_words(F, H);
+  a.in0 = obs, a.ld0 = F, a.D0 = F, a.S0 = ksteps_rows(F);
+  a.vec0 = F % 4 == 0 && aligned16(obs);
+  int rc = exact ? launch(k_tarmac_encode_bf16<4, 1, true>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s)
+                 : launch(k_tarmac_encode_bf16<4, 2, false>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s);
+  if (rc != MDR_OK) return rc;
+  if (wc) {
+    for (int hop = 0; hop < hops; ++hop) {
+      if (hop > 0) {      // [comm, h] -> h' -> qkv
+        a.fa = actor->frag_msg, a.na = (int)msg_words(H, V);
+        a.in0 = cat + H, a.ld0 = ldcat, a.D0 = V, a.S0 = ksteps_rows(V);
+        a.in1 = hop == 1 ? cat : state, a.ld1 = hop == 1 ? ldcat : H, a.S1 = ksteps_rows(H);
+        a.vec0 = a.vec1 = 1;      // H, V and both leading dimensions are multiples of 4 floats, the workspace is 16-byte aligned
+        rc = exact ? launch(k_tarmac_rehop_bf16<4, 1, 5, true>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s)
+                   : launch(k_tarmac_rehop_bf16<4, 2, 6, false>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s);
+        if (rc != MDR_OK) return rc;
+      }
+      rc = mdr_tarmac_comm(qkv, ldqkv, qkv + K, ldqkv, qkv + 2 * K, ldqkv, nb_envs, nb_houses, K, V, actor->nb_comm, actor->mode, actor->defect_prob,
+                           seed, step, step_dev, hop, cat + H, ldcat, stream);
+      if (rc != MDR_OK) return rc;
+    }
+  }
+  // ---- [x, comm] -> logits -> action
+  a.fa = actor->frag_head, a.na = (int)head_words(H, V, wc);
+  a.in0 = cat, a.ld0 = ldcat, a.D0 = (int)ldcat, a.S0 = ksteps_rows((int)ldcat);
+  a.vec0 = 1;
+  return mbh == 4 ? launch(k_tarmac_head_bf16<4, true>, WAVES_BF16, a, a.na + a.nvec, cus, s)
+                  : launch(k_tarmac_head_bf16<4, false>, WAVES_BF16, a, a.na + a.nvec, cus, s);
+}
+
+}  // namespace mdr

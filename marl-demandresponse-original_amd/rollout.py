@@ -262,7 +262,7 @@ def collect_ppo_rollout(env, actor: nn.Module, nb_steps: int, gamma: float = 0.9
 def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, critic: Optional[nn.Module] = None, seed: int = 0,
                            store_states: bool = True) -> Dict[str, torch.Tensor]:
     """The interaction loop of train_tarmacPPO.py:62-119 for all envs at once: every step ``env.obs_vector("rows")`` ->
-    ``TarMACActor.sample`` or ``FusedTarMACActor.sample`` (TarmacPPO.select_actions, agents/tarmac_ppo.py:83-95: each agent attends to the hidden states of the other
+    ``TarMACActor.sample`` or ``FusedTarMACActor.sample`` (in either precision, "fp32" or "bf16x3": the object carries it; TarmacPPO.select_actions, agents/tarmac_ppo.py:83-95: each agent attends to the hidden states of the other
     agents of ITS env, hence observations as [E, N, F]) -> ``env.step``.  Same keys and flattened [T, E*N] layout as
     ``collect_ppo_rollout``: ``state`` [T+1, E*N, F] (omitted without ``store_states``), ``action`` int64, ``a_prob``, ``reward``,
     ``done`` (True on the last step) and ``return``; the bootstrap through ``critic`` (a ``TarMACCritic``) is its [E, N] value of the
@@ -403,7 +403,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     steps of (reg_signal - cluster_hvac_power)^2).
 
     ``policy``: a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused), a
-    ``FusedTarMACActor`` (the same agent as one chain of HIP kernels: observation rows, the chain with ``step_dev =
+    ``FusedTarMACActor`` (the same agent as one chain of HIP kernels, exact fp32 or ``precision="bf16x3"``: observation rows, the chain with ``step_dev =
     env.device_time_index``, ``env.step`` - one stream, no parallel branches, so ``use_graph=True`` captures it), the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
     here, and observation and policy are then ONE kernel wherever ``collect_ppo_rollout`` would make them one (no observation rows at
     all) - or a ready ``FusedActor``: one packed with ``feature_order=FEATURES_OBSERVE`` takes the same one-kernel path, any other

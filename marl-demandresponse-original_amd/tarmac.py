@@ -29,7 +29,8 @@ that call's mask from the same key.
 
 ``FusedTarMACActor.from_module(actor)`` evaluates the same actor WITHOUT library GEMMs: the per-agent MLPs run as HIP kernels on the
 matrix cores in exact fp32 (``mdr_tarmac_actor_sample``, csrc/mdr_tarmac_mlp.hip) around the same attention kernel - three launches per
-step for one hop, capturable in a graph, reachable through the C ABI alone.
+step for one hop, capturable in a graph, reachable through the C ABI alone.  ``precision="bf16x3"`` runs the same chain with every
+matrix product on bf16 matrix instructions, both operands split into a bf16 head and tail (csrc/mdr_tarmac_mlp_bf16.hip).
 """
 from __future__ import annotations
 
@@ -454,7 +455,7 @@ class MdrTarmacActor(C.Structure):
     """``mdr_tarmac_actor_t`` (include/mdr_policy.h), field for field."""
     _fields_ = [("struct_size", C.c_uint32), ("num_state", C.c_int32), ("hidden", C.c_int32), ("num_key", C.c_int32),
                 ("num_value", C.c_int32), ("nb_comm", C.c_int32), ("mode", C.c_int32), ("num_hops", C.c_int32),
-                ("with_comm", C.c_int32), ("defect_prob", C.c_float), ("greedy", C.c_int32), ("reserved0", C.c_int32),
+                ("with_comm", C.c_int32), ("defect_prob", C.c_float), ("greedy", C.c_int32), ("precision", C.c_int32),
                 ("frag_encode", C.c_void_p), ("frag_proj", C.c_void_p), ("frag_msg", C.c_void_p), ("frag_head", C.c_void_p),
                 ("vec", C.c_void_p)]
 
@@ -490,21 +491,80 @@ def _from_regs(n_in: int):
     return lambda s, g: (16 * (s >> 2) + 4 * g + (s & 3), n_in)
 
 
-def pack_tarmac_fragments(sd, num_obs: int, hidden: int, num_key: int, num_value: int, num_hops: int = 1, with_comm: bool = True):
-    """A TarMAC actor's state_dict (numpy / torch, CPU) -> the five float32 arrays of ``mdr_tarmac_actor_t`` as a dict
-    ``frag_encode, frag_proj, frag_msg, frag_head, vec``; parts the actor does not have are None."""
+PRECISIONS = {"fp32": 0, "bf16x3": 1}      # mdr_tarmac_precision
+
+
+def bf16_split(x):
+    """float32 array -> (head, tail) bf16 bit patterns as uint16: head = bf16(x), tail = bf16(x - head), round to nearest even."""
     import numpy as np
-    sd = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float32) for k, v in sd.items()}
-    F_, H, K, V = int(num_obs), int(hidden), int(num_key), int(num_value)
+
+    def bits(v):
+        u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+        return ((u + (((u >> np.uint32(16)) & np.uint32(1)) + np.uint32(0x7FFF))) >> np.uint32(16)).astype(np.uint16)
+
+    x = np.asarray(x, dtype=np.float32)
+    head = bits(x)
+    tail = bits(x - (head.astype(np.uint32) << np.uint32(16)).view(np.float32))
+    return head, tail
+
+
+def _fragment_bf16(w, steps: int, nb_out: int, col):
+    """One layer as bf16 head / tail fragments (include/mdr_policy.h): ``w`` [out, in] -> uint32 [steps * nb_out * 512];
+    ``col(s, g, j)`` -> (column of ``w`` for element j of lane group g in k-step s, whether that element is an input at all)."""
+    import numpy as np
+    w = np.asarray(w, dtype=np.float32)
+    lane = np.arange(64)
+    r, g, j = (lane & 15)[:, None], (lane >> 4)[:, None], np.arange(8)[None, :]
+    vals = np.zeros((steps, nb_out, 64, 8), dtype=np.float32)
+    for s in range(steps):
+        c, live = col(s, g, j)
+        live = live & (c < w.shape[1])
+        for mb in range(nb_out):
+            row = np.broadcast_to(16 * mb + r, (64, 8))
+            ok = live & (row < w.shape[0])
+            vals[s, mb] = np.where(ok, w[np.minimum(row, w.shape[0] - 1), np.clip(c, 0, w.shape[1] - 1)], 0.0)
+    head, tail = bf16_split(vals)
+    return np.ascontiguousarray(np.stack([head, tail], axis=2)).view(np.uint32).reshape(-1)      # [s][mb][t][lane][j]
+
+
+def _bf16_rows(first: int, length: int):
+    return lambda s, g, j: (first + 32 * s + 8 * g + j, 32 * s + 8 * g + j < length)
+
+
+def _bf16_regs(nb_in: int):
+    import numpy as np
+    return lambda s, g, j: (16 * (2 * s + (j >> 2)) + 4 * g + (j & 3), np.broadcast_to(2 * s + (j >> 2) < nb_in, (g.shape[0], j.shape[1])))
+
+
+def _pack_bf16_fragments(sd, F_, H, K, V, num_hops, with_comm):
+    import numpy as np
+    nbh, nbv, nbm = _blocks(H), _blocks(V), _blocks(H + V)
+
+    def rows(w, n, c0, nbo):
+        return _fragment_bf16(w, (n + 31) // 32, nbo, _bf16_rows(c0, n))
+
+    def regs(w, nbi, nbo):
+        return _fragment_bf16(w, (nbi + 1) // 2, nbo, _bf16_regs(nbi))
+
+    res = {"frag_proj": None, "frag_msg": None}
+    res["frag_encode"] = np.concatenate([rows(sd["obs2hidden.0.weight"], F_, 0, nbh), regs(sd["obs2hidden.2.weight"], nbh, nbh)])
+    names = ("query", "key", "value")
+    if with_comm:
+        res["frag_proj"] = np.concatenate([regs(sd["comm.hidden2%s.0.weight" % n], nbh, nbh) for n in names] +
+                                          [regs(sd["comm.hidden2%s.2.weight" % n], nbh, nbv if n == "value" else 1) for n in names])
+        if num_hops > 1:
+            w = sd["comm.msg_state2state.0.weight"]      # columns: comm (V) first, then h (H)
+            res["frag_msg"] = np.concatenate([rows(w, V, 0, nbm), rows(w, H, V, nbm), regs(sd["comm.msg_state2state.2.weight"], nbm, nbh)])
+        res["frag_head"] = rows(sd["comm_hidden2action.0.weight"], H + V, 0, nbh)
+    else:
+        res["frag_head"] = rows(sd["hidden2action.0.weight"], H, 0, nbh)
+    return res
+
+
+def _pack_fp32_fragments(sd, F_, H, K, V, num_hops, with_comm):
+    import numpy as np
     nbh, nbv, nbm = _blocks(H), _blocks(V), _blocks(H + V)
     s1 = (F_ + 3) // 4
-
-    def padded(name, n):
-        out = np.zeros(n, dtype=np.float32)
-        if name is not None and name in sd:
-            out[:sd[name].shape[0]] = sd[name]
-        return out
-
     res = {"frag_proj": None, "frag_msg": None}
     res["frag_encode"] = np.concatenate([_fragment(sd["obs2hidden.0.weight"], s1, nbh, _from_rows(s1, 0, F_)),
                                          _fragment(sd["obs2hidden.2.weight"], 4 * nbh, nbh, _from_regs(H))])
@@ -522,6 +582,31 @@ def pack_tarmac_fragments(sd, num_obs: int, hidden: int, num_key: int, num_value
     else:
         head, d_in = "hidden2action", H
     res["frag_head"] = _fragment(sd[head + ".0.weight"], d_in // 4, nbh, _from_rows(d_in // 4, 0, d_in))
+    return res
+
+
+def pack_tarmac_fragments(sd, num_obs: int, hidden: int, num_key: int, num_value: int, num_hops: int = 1, with_comm: bool = True,
+                          precision: str = "fp32"):
+    """A TarMAC actor's state_dict (numpy / torch, CPU) -> the five arrays of ``mdr_tarmac_actor_t`` as a dict ``frag_encode,
+    frag_proj, frag_msg, frag_head, vec``; parts the actor does not have are None.  ``precision="fp32"``: float32 arrays;
+    ``"bf16x3"``: the four ``frag_*`` as uint32 words of bf16 head / tail fragments, ``vec`` the same float32 array."""
+    import numpy as np
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be 'fp32' or 'bf16x3'")
+    sd = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float32) for k, v in sd.items()}
+    F_, H, K, V = int(num_obs), int(hidden), int(num_key), int(num_value)
+    nbh, nbv, nbm = _blocks(H), _blocks(V), _blocks(H + V)
+    names = ("query", "key", "value")
+
+    def padded(name, n):
+        out = np.zeros(n, dtype=np.float32)
+        if name is not None and name in sd:
+            out[:sd[name].shape[0]] = sd[name]
+        return out
+
+    pack = _pack_bf16_fragments if precision == "bf16x3" else _pack_fp32_fragments
+    res = pack(sd, F_, H, K, V, num_hops, with_comm)
+    head = "comm_hidden2action" if with_comm else "hidden2action"
     w3, b3 = sd[head + ".2.weight"], sd[head + ".2.bias"]
     wd = np.zeros(16 * nbh, dtype=np.float32)
     wd[:H] = w3[0] - w3[1]
@@ -538,14 +623,20 @@ def pack_tarmac_fragments(sd, num_obs: int, hidden: int, num_key: int, num_value
 
 class FusedTarMACActor:
     """A ``TarMACActor`` evaluated by ``mdr_tarmac_actor_sample`` (include/mdr_policy.h): the per-agent MLPs as three kinds of HIP
-    kernels on the matrix cores in exact fp32 (csrc/mdr_tarmac_mlp.hip) around the banded attention kernel - 1 + hops + (hops - 1)
-    + 1 launches per step, no library GEMM, no allocation after the first call, capturable in a graph.  Inference only; to
+    kernels on the matrix cores around the banded attention kernel - 1 + hops + (hops - 1) + 1 launches per step, no library GEMM,
+    no allocation after the first call, capturable in a graph.  ``precision="fp32"``: exact fp32 (csrc/mdr_tarmac_mlp.hip);
+    ``"bf16x3"``: every matrix product on bf16 matrix instructions with both operands split into a bf16 head and tail
+    (csrc/mdr_tarmac_mlp_bf16.hip; probabilities within 2e-3 relative + 2e-5 of an fp64 forward, the attention, the activations and
+    the draw unchanged) - the same split as ``FusedActor``'s BF16X3 layout; the ``.precision`` attribute says which.  Inference only; to
     ``TarMACActor`` what ``FusedActor`` is to ``ActorMLP``.  Covers num_obs <= 64, hidden_state_size a multiple of 4 <= 64, num_key
     a multiple of 4 <= 16, num_value a multiple of 4 <= 32, two actions, the modes 'neighbours' and 'none'; anything else is a
     ValueError (the eager band path of ``TarMACActor`` remains for those)."""
 
-    def __init__(self, actor: "TarMACActor"):
+    def __init__(self, actor: "TarMACActor", precision: str = "fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be 'fp32' or 'bf16x3'")
         self.actor = actor
+        self.precision = precision
         self._check_shapes()
         self._packed_key = None
         self._tensors = None
@@ -554,8 +645,8 @@ class FusedTarMACActor:
         self._workspace = None
 
     @classmethod
-    def from_module(cls, actor: "TarMACActor") -> "FusedTarMACActor":
-        return cls(actor)
+    def from_module(cls, actor: "TarMACActor", precision: str = "fp32") -> "FusedTarMACActor":
+        return cls(actor, precision)
 
     def _shape(self):
         a = self.actor
@@ -589,13 +680,16 @@ class FusedTarMACActor:
             if dev.type != "cuda":
                 raise ValueError("the fused TarMAC actor runs on the GPU: move the TarMACActor there first")
             F_, H, K, V = self._shape()
-            host = pack_tarmac_fragments(a.state_dict(), F_, H, K, V, a.num_hops, a.with_comm)
+            import numpy as np
+            host = pack_tarmac_fragments(a.state_dict(), F_, H, K, V, a.num_hops, a.with_comm, precision=self.precision)
+            host = {n: (v.view(np.int32) if v is not None and v.dtype == np.uint32 else v) for n, v in host.items()}      # 4-byte words
             self._tensors = {n: (torch.from_numpy(v).to(dev) if v is not None else None) for n, v in host.items()}
             st = MdrTarmacActor()
             st.struct_size = C.sizeof(MdrTarmacActor)
             st.num_state, st.hidden, st.num_key, st.num_value = F_, H, K, V
             st.nb_comm, st.mode, st.num_hops, st.with_comm = a.number_agents_comm, MODES[a.comm_mode], a.num_hops, int(a.with_comm)
             st.defect_prob = a.comm_defect_prob
+            st.precision = PRECISIONS[self.precision]
             for n, t in self._tensors.items():
                 setattr(st, n, t.data_ptr() if t is not None else None)
             self._struct = st
