@@ -20,7 +20,8 @@
  * Layout: all per-house arrays are row-major [nb_envs][nb_houses] (house index fastest).
  *
  * ABI 5: mdr_buffers_t ends in the optional `param_uniform` word (per-house parameter columns that hold one value for every
- * house are not streamed by the step kernels); new entry point mdr_env_params_changed.
+ * house are not streamed by the step kernels); new entry point mdr_env_params_changed.  Added under ABI 5 (a new function, nothing
+ * existing changes): mdr_env_bind_hvac_code - the (Q_hvac, P_max) pair of a house as one byte into a 16-entry dictionary.
  */
 #ifndef MDR_H
 #define MDR_H
@@ -34,6 +35,9 @@ extern "C" {
 #define MDR_ABI_VERSION 5
 #define MDR_MAX_SINUSOIDS 8
 #define MDR_MAX_CAPACITIES 16
+#define MDR_HVAC_DICT_ENTRIES 16   /* mdr_env_bind_hvac_code: (Q_hvac, P_max) pairs the dictionary holds (= MDR_MAX_CAPACITIES) */
+#define MDR_HVAC_DICT_COUNT 32     /* ... index of its count word: words [0, 32) are the pairs, entry c = {Q_hvac bits, P_max bits} at [2c], [2c + 1] */
+#define MDR_HVAC_DICT_WORDS 36     /* ... uint32 words the caller allocates: pairs, count, and three words the detection kernel works in */
 #define MDR_OBS_COLUMNS 7
 #define MDR_INTERP_AXES 10
 #define MDR_INTERP_MAX_AXIS 16
@@ -261,8 +265,24 @@ int mdr_env_reset(mdr_env_t *env, uint64_t seed, uint32_t episode, void *stream)
 int mdr_env_load_episode(mdr_env_t *env, const mdr_episode_t *episode, uint64_t seed, uint32_t episode_index,
                          void *stream);
 /* The caller wrote `target`, `deadband` or `lockout` of the bound buffers itself: re-derives mdr_buffers_t.param_uniform from the
- * arrays (one pass over the three columns on `stream`).  Nothing to do, MDR_OK, when the word is not bound. */
+ * arrays (one pass over the three columns on `stream`).  A caller that wrote `Q_hvac` or `P_max` calls it too: with a code bound
+ * (mdr_env_bind_hvac_code) it rebuilds the dictionary and the class plane from those two arrays (one more pass).  Nothing to do,
+ * MDR_OK, when neither the word nor the code is bound. */
 int mdr_env_params_changed(mdr_env_t *env, void *stream);
+/* Optional: dictionary-codes the two HVAC power columns for the single-step kernels (mdr_env_step, the records pair,
+ * mdr_env_step_mailbox).  `Q_hvac` and `P_max` derive from (capacity, COP, latent), and capacity is drawn from at most
+ * MDR_MAX_CAPACITIES values, so the pair takes a handful of bit patterns over the whole batch (5 in the benchmark).
+ *   hvac_class  uint8 [nb_envs][nb_houses], 16-byte aligned: the house's index into the dictionary
+ *   hvac_dict   uint32 [MDR_HVAC_DICT_WORDS], 128-byte aligned: the pairs as raw bits and, at [MDR_HVAC_DICT_COUNT], how many there
+ *               are; a count of 0 means "not coded": the kernels stream the two columns as without a code.  Hand it over zeroed.
+ * The library fills both on the caller's stream where it fills mdr_buffers_t.param_uniform: mdr_env_reset, mdr_env_load_episode and
+ * mdr_env_params_changed, from the bound `Q_hvac` / `P_max` arrays, comparing raw bits (-0.0 is not +0.0, NaN payloads count; equal
+ * Q_hvac with different P_max are two entries).  More than MDR_HVAC_DICT_ENTRIES distinct pairs - or the one pair of all-ones words
+ * the kernel marks free slots with - give a count of 0.  With a count > 0 a step reads 1 B per house instead of 8 B and does NOT
+ * read the two columns: a caller that writes `Q_hvac` or `P_max` itself must call mdr_env_params_changed before the next step.
+ * The arrays stay fully written (every other kernel reads them).  NULL for both turns the coding off; mdr_env_bind drops the
+ * binding (bind the code again after it; the contents of the two buffers stay valid across a re-bind of the same arrays). */
+int mdr_env_bind_hvac_code(mdr_env_t *env, uint8_t *hvac_class, uint32_t *hvac_dict);
 /* Optional: replace ClusterHouses.compute_OD_temp (env 1057-1081, incl. its random.gauss draw 1079) by a table, double [rows][E] deg C (row = time index);
  * NULL restores the model.  Takes effect at the next mdr_env_begin_episode / table refill; mdr_env_reset (a freshly sampled
  * episode) drops it. */

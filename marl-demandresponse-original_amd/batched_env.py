@@ -46,7 +46,7 @@ class BatchedDemandResponseEnv:
                  house_shard: Optional[Tuple[int, int]] = None, process_group=None,
                  stagger_bytes: int = 2304, interp_grid=None, regenerate_missing_grid: bool = True,
                  graph_mode: bool = False, exchange_always: bool = False, partial_records: Optional[int] = None,
-                 obs_planes: bool = True, prefetch_tables: bool = True, exchange=None, uniform_params: bool = True):
+                 obs_planes: bool = True, prefetch_tables: bool = True, exchange=None, uniform_params: bool = True, hvac_code: bool = True):
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedDemandResponseEnv needs a ROCm device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
@@ -88,6 +88,10 @@ class BatchedDemandResponseEnv:
         # deadband / lockout that hold one value for every house (found on the device at reset / load_episode / params_changed());
         # False binds NULL: every column is streamed
         self._uniform_params = bool(uniform_params)
+        # hvac_code: bind a class plane and a 16-entry dictionary (mdr_env_bind_hvac_code) - the step kernels then read one byte per
+        # house instead of the Q_hvac and P_max columns whenever the batch holds at most 16 distinct (Q_hvac, P_max) pairs (found on
+        # the device at reset / load_episode / params_changed()); False binds nothing: the two columns are streamed
+        self._hvac_code = bool(hvac_code)
         self._handle = C.c_void_p()
         self._cfg = self._make_config()
         rc = self._lib.mdr_env_create(C.byref(self._cfg), C.byref(self._handle))
@@ -185,6 +189,9 @@ class BatchedDemandResponseEnv:
         for name, (o, nbytes, dtype, shape) in offsets.items():
             self.t[name] = self._slab[o:o + nbytes].view(dtype).view(*shape)
         self.t["tot_sum"], self.t["tot_max"] = self.t["tot"][0:2], self.t["tot"][2]
+        if self._hvac_code:      # derived from Q_hvac / P_max, never part of a snapshot: outside the slab, whose layout stays what it was
+            self.t["hvac_class"] = torch.zeros((self.nb_envs, self.nb_houses), dtype=torch.uint8, device=self.device)
+            self.t["hvac_dict"] = torch.zeros((nat.MDR_HVAC_DICT_WORDS,), dtype=torch.int32, device=self.device)      # count 0: not coded yet
 
     def _grow_partials(self, records: int) -> None:
         """Raise the record stride of `partials` to the group's maximum (a fresh zero-filled scratch buffer, re-bound)."""
@@ -210,6 +217,9 @@ class BatchedDemandResponseEnv:
             setattr(b, fname, self.t[fname].data_ptr() if self.t[fname].numel() else None)      # an empty optional buffer is NULL
         self._buffers = b
         nat.check(self._lib, self._handle, self._lib.mdr_env_bind(self._handle, C.byref(b)), "mdr_env_bind")
+        if self._hvac_code:      # mdr_env_bind drops the code; the two buffers' contents stay valid over a re-bind of the same arrays
+            rc = self._lib.mdr_env_bind_hvac_code(self._handle, self.t["hvac_class"].data_ptr(), self.t["hvac_dict"].data_ptr())
+            nat.check(self._lib, self._handle, rc, "mdr_env_bind_hvac_code")
 
     def set_obs_planes(self, on: bool) -> None:
         """Switch the seven per-step observation planes on or off (a re-bind: mdr_buffers_t.obs = NULL skips their 28 B per
@@ -367,9 +377,10 @@ class BatchedDemandResponseEnv:
             return self._reset_obs()
 
     def params_changed(self) -> None:
-        """Call after writing ``t['target']``, ``t['deadband']`` or ``t['lockout']`` yourself: the library reads the three arrays
-        at reset, at load_episode and here to find the columns that hold one value for every house (which the step kernels then do
-        not stream).  One pass over the three columns on the current stream; no host sync."""
+        """Call after writing ``t['target']``, ``t['deadband']``, ``t['lockout']``, ``t['Q_hvac']`` or ``t['P_max']`` yourself: the
+        library reads the first three at reset, at load_episode and here to find the columns that hold one value for every house
+        (which the step kernels then do not stream), and with ``hvac_code`` the last two to rebuild the dictionary and the class
+        plane the step kernels read in their place.  One pass over the columns on the current stream; no host sync."""
         with torch.cuda.device(self.device):
             nat.check(self._lib, self._handle, self._lib.mdr_env_params_changed(self._handle, self._stream()), "mdr_env_params_changed")
 
@@ -963,12 +974,12 @@ class BatchedDemandResponseEnv:
         rc = self._lib.mdr_env_set_cursor(self._handle, C.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF),
                                           C.c_uint32(max(self.episode, 0) & 0xFFFFFFFF), sd["k"], sd["j0"])
         nat.check(self._lib, self._handle, rc, "mdr_env_set_cursor")
-        self.params_changed()      # the slab brought its parameter arrays: the uniformity word is derived from them again
+        self.params_changed()      # the slab brought its parameter arrays: the uniformity word and the HVAC code are derived from them again
 
     def __deepcopy__(self, memo):
         other = BatchedDemandResponseEnv(copy.deepcopy(self.config, memo), nb_envs=self.nb_envs, device=self.device,
                                          seed=self.seed, test=self.test, table_steps=self.table_steps, obs_planes=self._obs_planes_alloc,
-                                         prefetch_tables=self._prefetch_tables, uniform_params=self._uniform_params,
+                                         prefetch_tables=self._prefetch_tables, uniform_params=self._uniform_params, hvac_code=self._hvac_code,
                                          env_offset=self.env_offset,
                                          house_shard=(self.house_offset, self.nb_houses) if self.sharded else None,
                                          exchange_always=self._exchange_always, partial_records=self._partial_records,

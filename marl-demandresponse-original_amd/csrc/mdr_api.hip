@@ -14,6 +14,8 @@ struct mdr_env {
   mdr_config_t cfg;
   mdr_buffers_t buf;
   bool bound = false;
+  uint8_t* hvac_class = nullptr;   // mdr_env_bind_hvac_code; mdr_env_bind drops both
+  uint32_t* hvac_dict = nullptr;
   bool has_episode = false;   // per-house parameters present
   bool has_tables = false;    // begin_episode done
   bool split_pending = false; // step_begin issued, step_end outstanding
@@ -126,6 +128,14 @@ std::string check_buffers(const mdr_buffers_t& b, bool need_partials) {
   if (((uintptr_t)b.pen_stash & 15u) != 0) return "pen_stash must be 16-byte aligned";
   if (((uintptr_t)b.param_uniform & 3u) != 0) return "param_uniform must be 4-byte aligned";
   return "";
+}
+
+// What the step kernels take from a summary of the parameter arrays instead of the arrays: the uniformity word and the HVAC code
+hipError_t detect_params(const mdr_env* env, hipStream_t s) {
+  const int64_t n = (int64_t)env->cfg.nb_envs * env->cfg.nb_houses;
+  const hipError_t e = mdr::launch_detect_uniform(env->buf, n, s);
+  if (e != hipSuccess) return e;
+  return mdr::launch_hvac_code(env->buf, n, env->hvac_class, env->hvac_dict, s);
 }
 
 mdr::EpisodeArgs episode_args(const mdr_env& env) {
@@ -378,6 +388,7 @@ int step_args(mdr_env* env, uint8_t* actions, int action_source, hipStream_t s, 
   a.k01 = b.k01; a.s0 = b.s0; a.k10 = b.k10; a.s1 = b.s1; a.inv_Ua = b.inv_Ua; a.Q_hvac = b.Q_hvac; a.P_max = b.P_max;
   a.target = b.target; a.deadband = b.deadband; a.lockout = b.lockout;
   a.param_uniform = b.param_uniform;
+  a.hvac_class = env->hvac_class; a.hvac_dict = env->hvac_dict;
   a.actions = actions;
   a.reward = b.reward; a.obs = b.obs;
   a.P = b.P; a.tot_sum = b.tot_sum; a.tot_max = b.tot_max; a.partials = b.partials;
@@ -492,6 +503,8 @@ int mdr_env_bind(mdr_env_t* env, const mdr_buffers_t* buffers) {
   const bool same_tables = env->bound && memcmp(&t0, &env->tabs[0], sizeof t0) == 0 && memcmp(&t1, &env->tabs[1], sizeof t1) == 0;
   if (!same_tables && env->prefetched && env->ev_fill) (void)hipEventSynchronize(env->ev_fill);   // a prefetch into the old buffers: let it land
   env->buf = *buffers;
+  env->hvac_class = nullptr;   // the code belongs to the arrays it was bound over: mdr_env_bind_hvac_code again
+  env->hvac_dict = nullptr;
   env->tabs[0] = t0;
   env->tabs[1] = t1;
   env->has_alt = all2;
@@ -521,8 +534,8 @@ int mdr_env_reset(mdr_env_t* env, uint64_t seed, uint32_t episode, void* stream)
   if (settle_prefetch(env, (hipStream_t)stream) != MDR_OK) return MDR_ERR_HIP;
   hipError_t e = mdr::launch_sample(episode_args(*env), (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "reset");
-  e = mdr::launch_detect_uniform(env->buf, (int64_t)env->cfg.nb_envs * env->cfg.nb_houses, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(env, e, "reset: detect_uniform");
+  e = detect_params(env, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(env, e, "reset: detect_uniform / hvac_code");
   env->has_episode = true;
   env->k = 0;
   return MDR_OK;
@@ -544,8 +557,8 @@ int mdr_env_load_episode(mdr_env_t* env, const mdr_episode_t* ep, uint64_t seed,
   if (settle_prefetch(env, (hipStream_t)stream) != MDR_OK) return MDR_ERR_HIP;
   hipError_t e = mdr::launch_load(episode_args(*env), *ep, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "load_episode");
-  e = mdr::launch_detect_uniform(env->buf, (int64_t)env->cfg.nb_envs * env->cfg.nb_houses, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(env, e, "load_episode: detect_uniform");
+  e = detect_params(env, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(env, e, "load_episode: detect_uniform / hvac_code");
   env->has_episode = true;
   env->k = 0;
   return MDR_OK;
@@ -554,8 +567,19 @@ int mdr_env_load_episode(mdr_env_t* env, const mdr_episode_t* ep, uint64_t seed,
 int mdr_env_params_changed(mdr_env_t* env, void* stream) {
   if (!env) return MDR_ERR_INVALID;
   if (!env->bound) return fail(env, MDR_ERR_UNBOUND, "buffers not bound");
-  const hipError_t e = mdr::launch_detect_uniform(env->buf, (int64_t)env->cfg.nb_envs * env->cfg.nb_houses, (hipStream_t)stream);
+  const hipError_t e = detect_params(env, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "params_changed");
+  return MDR_OK;
+}
+
+int mdr_env_bind_hvac_code(mdr_env_t* env, uint8_t* hvac_class, uint32_t* hvac_dict) {
+  if (!env) return MDR_ERR_INVALID;
+  if (!env->bound) return fail(env, MDR_ERR_UNBOUND, "buffers not bound");
+  if ((hvac_class == nullptr) != (hvac_dict == nullptr)) return fail(env, MDR_ERR_INVALID, "hvac_class and hvac_dict go together");
+  if (((uintptr_t)hvac_class & 15u) != 0) return fail(env, MDR_ERR_INVALID, "hvac_class must be 16-byte aligned");
+  if (((uintptr_t)hvac_dict & 127u) != 0) return fail(env, MDR_ERR_INVALID, "hvac_dict must be 128-byte aligned");
+  env->hvac_class = hvac_class;
+  env->hvac_dict = hvac_dict;
   return MDR_OK;
 }
 

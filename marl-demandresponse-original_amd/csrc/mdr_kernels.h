@@ -104,6 +104,9 @@ struct StepArgs {
   double inv_n_total;                  // 1 / nb_agents
   double inv_obs_norm;                 // 1 / (norm_reg_sig * nb_agents)
   const uint32_t* param_uniform;       // mdr_buffers_t.param_uniform: bit 0 target, 1 deadband, 2 lockout hold ONE value (element [0]) for every house; nullptr = stream all
+  // mdr_env_bind_hvac_code: a house's (Q_hvac, P_max) as one byte into a 16-entry table; hvac_dict[MDR_HVAC_DICT_COUNT] == 0 or nullptr = stream the two columns
+  const uint8_t* hvac_class;
+  const uint32_t* hvac_dict;
 };
 
 // utils.normStateDict for all houses (k_obs_vector)
@@ -242,6 +245,8 @@ int64_t split_blocks(int N, int threads);     // workgroups (= partial records) 
 hipError_t launch_sample(const EpisodeArgs& a, hipStream_t s);
 hipError_t launch_load(const EpisodeArgs& a, const mdr_episode_t& ep, hipStream_t s);
 hipError_t launch_detect_uniform(const mdr_buffers_t& b, int64_t n, hipStream_t s);   // b.param_uniform <- which of target / deadband / lockout hold one value in all n houses
+// hvac_dict / hvac_class <- the distinct (Q_hvac, P_max) bit pairs of all n houses and each house's index among them (count 0: more than 16)
+hipError_t launch_hvac_code(const mdr_buffers_t& b, int64_t n, uint8_t* hvac_class, uint32_t* hvac_dict, hipStream_t s);
 hipError_t launch_tables(const TableArgs& a, hipStream_t s);
 hipError_t launch_interp_base(const InterpArgs& a, hipStream_t s);
 hipError_t launch_patch_signal_plane(const StepArgs& a, hipStream_t s);   // obs plane 5 <- sig_old row

@@ -128,6 +128,117 @@ hipError_t launch_detect_uniform(const mdr_buffers_t& b, int64_t n, hipStream_t 
   return hipGetLastError();
 }
 
+// mdr_env_bind_hvac_code: the distinct (Q_hvac, P_max) bit pairs of all n houses into the 16 slots of hvac_dict - a slot is the
+// 64-bit key, Q_hvac in the low word, so the slots ARE the table the step kernels look up - and each house's slot into hvac_class.
+// The launcher fills the slots with HVAC_FREE (all ones) and zeroes the four words behind them ahead on the stream.  A key is
+// inserted by a 64-bit compare-and-swap on the first slot that is free or already holds it, tried in slot order: the taken slots are
+// always a prefix, and a key lands in one slot whoever races.  Which slot is a matter of arrival order - it is not an output.
+// One lane per wave and missing key does the insert; the wave keeps a copy of the table in registers (lane l: slot l & 15) and
+// looks every house up there first, so once the few keys are in (the first waves) nobody sends an atomic any more.  Every lane
+// of a wave stays active throughout (loop bounds are wave-uniform, `valid` is a predicate): readlane / ballot see all of them.
+// A 17th key, or a key equal to HVAC_FREE, raises the overflow word; the last workgroup to finish (`last` launch; a ticket: atomics only, read
+// back with agent-scope loads) writes the count, 0 on overflow.  9 B per house once per episode against 7 B less in every step.
+constexpr unsigned long long HVAC_FREE = ~0ull;
+constexpr int HVAC_OVERFLOW = MDR_HVAC_DICT_COUNT + 1, HVAC_TICKET = MDR_HVAC_DICT_COUNT + 2;
+
+__device__ __forceinline__ unsigned long long slot_load(const unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long readlane64(unsigned long long x, int lane) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// the slot of `key` for every valid lane; `cache`: this wave's copy of the table, refreshed after an insert
+__device__ __forceinline__ unsigned hvac_classify(unsigned long long key, bool valid, unsigned long long& cache, unsigned long long* slots, uint32_t* dict) {
+  const int lane = (int)(threadIdx.x & 63u);
+  int c = -1;
+  for (;;) {
+    for (int s = 0; s < MDR_HVAC_DICT_ENTRIES; ++s) {
+      const unsigned long long ks = readlane64(cache, s);
+      if (ks == HVAC_FREE) break;   // wave-uniform: the taken slots are a prefix
+      if (key == ks) c = s;
+    }
+    const uint64_t pending = __builtin_amdgcn_ballot_w64(valid && c < 0);
+    if (pending == 0ull) break;
+    const int leader = __builtin_ctzll(pending);
+    const unsigned long long kk = readlane64(key, leader);
+    int got = -1;
+    if (lane == leader) {
+      if (kk != HVAC_FREE) {
+        for (int s = 0; s < MDR_HVAC_DICT_ENTRIES; ++s) {
+          unsigned long long prev = slot_load(slots + s);   // a load first: the swap only where the slot still looks free
+          if (prev == HVAC_FREE) prev = atomicCAS(slots + s, HVAC_FREE, kk);
+          if (prev == HVAC_FREE || prev == kk) {
+            got = s;
+            break;
+          }
+        }
+      }
+      if (got < 0) atomicOr(dict + HVAC_OVERFLOW, 1u);
+    }
+    got = __builtin_amdgcn_readlane(got, leader);
+    if (valid && c < 0 && key == kk) c = got < 0 ? 0 : got;   // on overflow the plane is not used: any class
+    cache = slot_load(slots + (lane & (MDR_HVAC_DICT_ENTRIES - 1)));
+  }
+  return (unsigned)(c < 0 ? 0 : c);
+}
+
+__global__ __launch_bounds__(256) void k_hvac_code(const uint32_t* __restrict__ Q, const uint32_t* __restrict__ PM, int64_t n,
+                                                   uint8_t* __restrict__ cls, uint32_t* dict, int last) {
+  unsigned long long* slots = reinterpret_cast<unsigned long long*>(dict);
+  const int lane = (int)(threadIdx.x & 63u);
+  unsigned long long cache = slot_load(slots + (lane & (MDR_HVAC_DICT_ENTRIES - 1)));
+  const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t wave_first = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u);
+  for (int64_t j0 = wave_first; j0 < n4; j0 += stride) {   // the arrays are 16-byte aligned (mdr_env_bind)
+    const int64_t j = j0 + lane;
+    const bool valid = j < n4;
+    uint4 q = make_uint4(0u, 0u, 0u, 0u), p = q;
+    if (valid) {
+      q = reinterpret_cast<const uint4*>(Q)[j];
+      p = reinterpret_cast<const uint4*>(PM)[j];
+    }
+    const unsigned c0 = hvac_classify(((unsigned long long)p.x << 32) | q.x, valid, cache, slots, dict);
+    const unsigned c1 = hvac_classify(((unsigned long long)p.y << 32) | q.y, valid, cache, slots, dict);
+    const unsigned c2 = hvac_classify(((unsigned long long)p.z << 32) | q.z, valid, cache, slots, dict);
+    const unsigned c3 = hvac_classify(((unsigned long long)p.w << 32) | q.w, valid, cache, slots, dict);
+    if (valid) reinterpret_cast<uchar4*>(cls)[j] = make_uchar4((unsigned char)c0, (unsigned char)c1, (unsigned char)c2, (unsigned char)c3);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64u) {   // the n % 4 houses behind the last whole uint4
+    const int64_t i = n4 * 4 + lane;
+    const bool valid = i < n;
+    const uint32_t q = valid ? Q[i] : 0u, p = valid ? PM[i] : 0u;
+    const unsigned c = hvac_classify(((unsigned long long)p << 32) | q, valid, cache, slots, dict);
+    if (valid) cls[i] = (uint8_t)c;
+  }
+  if (!last) return;   // the launcher's first pass over a prefix of the houses: the keys are in, the count is the second pass's
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (atomicAdd(dict + HVAC_TICKET, 1u) != gridDim.x - 1u) return;   // (its inserts came back before the barrier: atomics that return a value)
+  uint32_t count = 0u;
+  for (int s = 0; s < MDR_HVAC_DICT_ENTRIES; ++s) count += slot_load(slots + s) != HVAC_FREE ? 1u : 0u;
+  const uint32_t overflow = __hip_atomic_load(dict + HVAC_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  dict[MDR_HVAC_DICT_COUNT] = overflow != 0u ? 0u : count;
+}
+
+hipError_t launch_hvac_code(const mdr_buffers_t& b, int64_t n, uint8_t* hvac_class, uint32_t* hvac_dict, hipStream_t s) {
+  if (hvac_class == nullptr || hvac_dict == nullptr || n < 1) return hipSuccess;
+  hipError_t e = hipMemsetD8Async(reinterpret_cast<hipDeviceptr_t>(hvac_dict), 0xFF, MDR_HVAC_DICT_ENTRIES * 8, s);
+  if (e != hipSuccess) return e;
+  e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(hvac_dict + MDR_HVAC_DICT_COUNT), 0, MDR_HVAC_DICT_WORDS - MDR_HVAC_DICT_COUNT, s);
+  if (e != hipSuccess) return e;
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(b.Q_hvac);
+  const uint32_t* p = reinterpret_cast<const uint32_t*>(b.P_max);
+  const int64_t blocks = std::max<int64_t>(std::min<int64_t>((n / 4 + 255) / 256, 1024), 1);
+  // Every wave of a grid that starts on an empty table inserts every key it meets: thousands of compare-and-swaps on one cache
+  // line, which take their turn one by one (measured at C3, 4096 waves: 413 us).  So one workgroup goes over the first 4096
+  // houses first - in the sampled episodes they hold every pair - and the grid behind it finds the keys in the table it loads.
+  if (blocks > 1) hipLaunchKernelGGL(k_hvac_code, dim3(1), dim3(256), 0, s, q, p, std::min<int64_t>(n, 4096), hvac_class, hvac_dict, 0);
+  hipLaunchKernelGGL(k_hvac_code, dim3((unsigned)blocks), dim3(256), 0, s, q, p, n, hvac_class, hvac_dict, 1);
+  return hipGetLastError();
+}
+
 // Local sum of max consumption per env (ClusterHouses.__init__, env 796-802); P <- 0.  The sum is EXACT in fp64 whatever the order
 // (fp32 addends within a factor of 8 of each other: 24 + log2(N) significant bits), so an env of more than 65,536 houses is summed by
 // several workgroups through atomic adds - one workgroup took 0.98 ms for 1,000,000 houses at every episode start.

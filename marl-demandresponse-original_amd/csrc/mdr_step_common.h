@@ -173,6 +173,41 @@ __device__ __forceinline__ void load_vec_or_first(bool uniform, const int* __res
     load_vec<VEC>(p, i, out);
   }
 }
+// The two HVAC power columns, dictionary-coded (mdr_env_bind_hvac_code): hvac_dict[MDR_HVAC_DICT_COUNT] > 0 says that every house's
+// (Q_hvac, P_max) bit pair is entry hvac_class[i] of the table at hvac_dict[0 .. 31] - 1 B per house-step streamed instead of 8.
+// The count is wave-uniform (a scalar load, like the uniformity word): one branch, and both arms leave the same bits in the same
+// registers.  The lookup is each lane's own 8-byte load from the 128-byte table - one cache line, resident in the CU's L1 after the
+// first wave.  It needs no other lane, so it is right under any EXEC mask: every caller runs the loaders inside a divergent guard
+// (`h < a.N`, the group forms' `active`), where a cross-lane exchange (ds_bpermute from lanes 0-15 holding the table) would read
+// inactive lanes - in k_step_group<8,4> at N = 20 lanes 5-7 of every 8 are off, and with them every copy of entries 5-7.
+// The index is masked to the table: a stale class byte can select a wrong pair, never an address outside the table.
+__device__ __forceinline__ uint32_t hvac_coded(const StepArgs& a) { return a.hvac_dict != nullptr ? a.hvac_dict[MDR_HVAC_DICT_COUNT] : 0u; }
+template <int VEC>
+__device__ __forceinline__ void load_hvac(const StepArgs& a, bool coded, int64_t i, float* q, float* pm) {
+  if (coded) {
+    unsigned c[VEC];
+    load_bytes<VEC>(a.hvac_class, i, c);
+#if defined(MDR_HVAC_LOOKUP_BPERMUTE) && MDR_HVAC_LOOKUP_BPERMUTE   // experiment build, right ONLY where lanes 0-15 are active at the call (C3: N = 1024): profiles/r06_README.md
+    const uint2 mine = reinterpret_cast<const uint2*>(a.hvac_dict)[threadIdx.x & (unsigned)(MDR_HVAC_DICT_ENTRIES - 1)];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const int from = (int)((c[v] & (unsigned)(MDR_HVAC_DICT_ENTRIES - 1)) << 2);
+      q[v] = __int_as_float(__builtin_amdgcn_ds_bpermute(from, (int)mine.x));
+      pm[v] = __int_as_float(__builtin_amdgcn_ds_bpermute(from, (int)mine.y));
+    }
+#else
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const uint2 e = reinterpret_cast<const uint2*>(a.hvac_dict)[c[v] & (unsigned)(MDR_HVAC_DICT_ENTRIES - 1)];
+      q[v] = __uint_as_float(e.x);
+      pm[v] = __uint_as_float(e.y);
+    }
+#endif
+  } else {
+    load_param<VEC>(a.Q_hvac, i, q);
+    load_param<VEC>(a.P_max, i, pm);
+  }
+}
 template <int VEC>
 __device__ __forceinline__ void store_bytes(uint8_t* __restrict__ p, int64_t i, const unsigned* v) {
   if constexpr (VEC == 4) {
@@ -248,6 +283,7 @@ __device__ __forceinline__ void house_step_vec(const StepArgs& a, int64_t i, con
   int sso[VEC];
   unsigned fl[VEC];
   const uint32_t uni = uniform_word(a);
+  const bool coded = hvac_coded(a) != 0u;
   load_vec<VEC>(a.Ta, i, Ta);
   load_vec<VEC>(a.Tm, i, Tm);
   load_vec<VEC>(a.sso, i, sso);
@@ -258,8 +294,7 @@ __device__ __forceinline__ void house_step_vec(const StepArgs& a, int64_t i, con
   load_param<VEC>(a.k10, i, k10);
   load_param<VEC>(a.s1, i, s1);
   load_param<VEC>(a.inv_Ua, i, iu);
-  load_param<VEC>(a.Q_hvac, i, q);
-  load_param<VEC>(a.P_max, i, pm);
+  load_hvac<VEC>(a, coded, i, q, pm);
   load_param_or_first<VEC>((uni & UNIFORM_TARGET) != 0u, a.target, i, tg);
   load_param_or_first<VEC>((uni & UNIFORM_DEADBAND) != 0u, a.deadband, i, db);
   load_vec_or_first<VEC>((uni & UNIFORM_LOCKOUT) != 0u, a.lockout, i, lockout);
@@ -294,6 +329,7 @@ __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, cons
   int sso[VEC];
   unsigned fl[VEC], act[VEC];
   const uint32_t uni = uniform_word(a);
+  const bool coded = hvac_coded(a) != 0u;
   load_vec<VEC>(a.Ta, i, Ta);
   load_vec<VEC>(a.Tm, i, Tm);
   load_vec<VEC>(a.sso, i, sso);
@@ -304,8 +340,7 @@ __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, cons
   load_param<VEC>(a.k10, i, k10);
   load_param<VEC>(a.s1, i, s1);
   load_param<VEC>(a.inv_Ua, i, iu);
-  load_param<VEC>(a.Q_hvac, i, q);
-  load_param<VEC>(a.P_max, i, pm);
+  load_hvac<VEC>(a, coded, i, q, pm);
   load_param_or_first<VEC>((uni & UNIFORM_TARGET) != 0u, a.target, i, tg);
   load_param_or_first<VEC>((uni & UNIFORM_DEADBAND) != 0u, a.deadband, i, db);
   load_vec_or_first<VEC>((uni & UNIFORM_LOCKOUT) != 0u, a.lockout, i, lockout);
