@@ -22,6 +22,7 @@
  * ABI 5: mdr_buffers_t ends in the optional `param_uniform` word (per-house parameter columns that hold one value for every
  * house are not streamed by the step kernels); new entry point mdr_env_params_changed.  Added under ABI 5 (a new function, nothing
  * existing changes): mdr_env_bind_hvac_code - the (Q_hvac, P_max) pair of a house as one byte into a 16-entry dictionary.
+ * Likewise mdr_env_tarmac_actor_sample (mdr_policy.h): the TarMAC actor fed from the env's compact state.
  */
 #ifndef MDR_H
 #define MDR_H

@@ -292,6 +292,22 @@ int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t *actor, const float *obs, i
                             uint64_t step, const int32_t *step_dev, void *workspace, uint8_t *action, float *a_prob, float *probs,
                             void *stream);
 
+/* Observe -> act for the TarMAC actor: mdr_tarmac_actor_sample on the observation of every agent of `env` in its current state,
+ * WITHOUT the observation rows.  The first kernel of the chain builds the 51 normStateDict features of its tile of agents in LDS from
+ * the compact state - the staging of mdr_env_actor_sample - and reads its layer-1 operands from there in the k-step order of
+ * frag_encode: the same fragments serve both entry points, and `action`, `a_prob` and `probs` are bit for bit those of
+ * mdr_tarmac_actor_sample on the rows of mdr_env_obs_vector(MDR_OBS_ROWS) for the same (seed, step, *step_dev), in either precision
+ * (agent index = env * nb_houses + house).  `workspace` (mdr_tarmac_actor_workspace_bytes), `step_dev` and capture in a graph as
+ * there.  `rows_out` as mdr_env_actor_sample (may be NULL): the rows float [nb_agents][51], bit for bit those of mdr_env_obs_vector.
+ * Covers what the default form of mdr_env_actor_sample covers - every optional state / message column off, agents_comm_mode
+ * "neighbours" with nb_agents_comm = 10, no link defects, unsharded houses, nb_houses >= 11 - and actor->num_state = 51; the actor's
+ * own nb_comm, mode, defect_prob and num_hops are the attention's and unrelated to the env's message senders: every value
+ * mdr_tarmac_actor_sample takes is taken.  Anything else returns MDR_ERR_UNSUPPORTED (-4) with nothing launched and nothing
+ * written: fall back to mdr_env_obs_vector + mdr_tarmac_actor_sample.  -1 / -3 as mdr_tarmac_actor_sample. */
+int mdr_env_tarmac_actor_sample(mdr_env_t *env, const mdr_obs_spec_t *spec, const mdr_tarmac_actor_t *actor, uint64_t seed, uint64_t step,
+                                const int32_t *step_dev, void *workspace, uint8_t *action, float *a_prob, float *probs, float *rows_out,
+                                void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,7 @@ EXPORTS = (
     "mdr_discounted_returns", "mdr_tarmac_comm", "mdr_logits_sample", "mdr_tarmac_comm_backward", "mdr_tarmac_comm_backward_workspace_bytes",
     "mdr_tarmac_frag_encode_floats", "mdr_tarmac_frag_proj_floats", "mdr_tarmac_frag_msg_floats", "mdr_tarmac_frag_head_floats",
     "mdr_tarmac_vec_floats", "mdr_tarmac_frag_words", "mdr_tarmac_actor_workspace_bytes", "mdr_tarmac_actor_sample",
+    "mdr_env_tarmac_actor_sample",
 )
 
 _lib = None
@@ -240,6 +241,7 @@ def load():
         "mdr_tarmac_frag_words": (i64, [vp, i32]),
         "mdr_tarmac_actor_workspace_bytes": (i64, [vp, i64]),
         "mdr_tarmac_actor_sample": (C.c_int, [vp, vp, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp]),
+        "mdr_env_tarmac_actor_sample": (C.c_int, [vp, C.POINTER(MdrObsSpec), vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "mdr_env_pack": (C.c_int, [vp, i32, vp, vp]),
         "mdr_env_graph_room": (i64, [vp]),
         "mdr_env_graph_replayed": (C.c_int, [vp, i64, vp]),

@@ -1366,11 +1366,9 @@ int mdr_env_obs_vector_ext(mdr_env_t* env, const mdr_obs_spec_t* spec, const flo
   return MDR_OK;
 }
 
-// msg_scratch / senders_scratch: the caller's scratch of mdr_env_actor_sample_links, NULL for mdr_env_actor_sample
-static int actor_sample_impl(mdr_env_t* env, const mdr_obs_spec_t* spec, const mdr_actor_t* actor, float* msg_scratch, int32_t* senders_scratch,
-                             uint64_t seed, uint64_t step, const int32_t* step_dev, uint8_t* action, float* a_prob, float* probs, float* rows_out,
-                             void* stream) {
-  if (!env || !spec || !actor || !action) return MDR_ERR_INVALID;
+// What the observe -> act kernels read of the env in its current state, for mdr_env_actor_sample[_links] and mdr_env_tarmac_actor_sample.
+// msg_scratch / senders_scratch: the caller's scratch of mdr_env_actor_sample_links, NULL otherwise
+static int observe_args(mdr_env_t* env, const mdr_obs_spec_t* spec, float* msg_scratch, int32_t* senders_scratch, void* stream, mdr::ObserveArgs* out) {
   if (env->cfg.nb_houses_total != env->cfg.nb_houses) return fail(env, MDR_ERR_UNSUPPORTED, "observe -> act needs unsharded houses");
   mdr::ObsArgs a;
   int rc = obs_args(env, spec, false, &a);
@@ -1384,7 +1382,8 @@ static int actor_sample_impl(mdr_env_t* env, const mdr_obs_spec_t* spec, const m
   if (table && !msg_scratch)
     return fail(env, MDR_ERR_UNSUPPORTED, "observe -> act with a link table or random_sample senders gathers message records: call mdr_env_actor_sample_links with its scratch");
   if (table && spec->random_links && !senders_scratch) return fail(env, MDR_ERR_INVALID, "random_sample: senders_scratch is NULL");
-  mdr::ObserveArgs o{};
+  mdr::ObserveArgs& o = *out;
+  o = mdr::ObserveArgs{};
   o.Ta = a.Ta; o.Tm = a.Tm; o.target = a.target; o.deadband = a.deadband; o.capacity = a.capacity; o.P_max = a.P_max;
   o.sso = a.sso; o.lockout = a.lockout; o.flags = a.flags; o.P = a.P; o.sig_now = a.sig_now;
   o.cursor = a.cursor; o.cursor_max = a.cursor_max;
@@ -1428,6 +1427,16 @@ static int actor_sample_impl(mdr_env_t* env, const mdr_obs_spec_t* spec, const m
       o.links_env_stride = (int64_t)env->cfg.nb_houses * spec->nb_comm;
     }
   }
+  return MDR_OK;
+}
+
+static int actor_sample_impl(mdr_env_t* env, const mdr_obs_spec_t* spec, const mdr_actor_t* actor, float* msg_scratch, int32_t* senders_scratch,
+                             uint64_t seed, uint64_t step, const int32_t* step_dev, uint8_t* action, float* a_prob, float* probs, float* rows_out,
+                             void* stream) {
+  if (!env || !spec || !actor || !action) return MDR_ERR_INVALID;
+  mdr::ObserveArgs o;
+  int rc = observe_args(env, spec, msg_scratch, senders_scratch, stream, &o);
+  if (rc != MDR_OK) return rc;
   rc = mdr::launch_actor_observe(actor, o, seed, step, step_dev, action, a_prob, probs, rows_out, (hipStream_t)stream);
   if (rc == MDR_ERR_UNSUPPORTED) return fail(env, rc, "observe -> act: shape or actor layout without a kernel (nb_houses > nb_comm <= 13, at most 64 features, FRAG16 / BF16X3 packed in MDR_FEATURES_OBSERVE order for this nb_comm)");
   if (rc != MDR_OK) return fail(env, rc, "actor_observe launch failed");
@@ -1444,6 +1453,26 @@ int mdr_env_actor_sample_links(mdr_env_t* env, const mdr_obs_spec_t* spec, const
                                float* rows_out, void* stream) {
   if (!msg_scratch || ((uintptr_t)msg_scratch & 15u) != 0) return env ? fail(env, MDR_ERR_INVALID, "msg_scratch must be a 16-byte aligned device buffer of nb_envs * nb_houses * 4 floats") : MDR_ERR_INVALID;
   return actor_sample_impl(env, spec, actor, msg_scratch, senders_scratch, seed, step, step_dev, action, a_prob, probs, rows_out, stream);
+}
+
+int mdr_env_tarmac_actor_sample(mdr_env_t* env, const mdr_obs_spec_t* spec, const mdr_tarmac_actor_t* actor, uint64_t seed, uint64_t step,
+                                const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, float* rows_out, void* stream) {
+  if (!env || !spec || !actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || !workspace || !action) return MDR_ERR_INVALID;
+  // the default observation alone (the default form of mdr_env_actor_sample), decided before anything touches the device
+  if (env->cfg.nb_houses_total != env->cfg.nb_houses) return fail(env, MDR_ERR_UNSUPPORTED, "observe -> act needs unsharded houses");
+  if (spec->state_hour || spec->state_day || spec->state_solar_gain || spec->state_thermal || spec->state_hvac || spec->message_thermal ||
+      spec->message_hvac || spec->nb_comm != 10 || spec->links != nullptr || spec->random_links || spec->comm_defect_prob > 0.0)
+    return fail(env, MDR_ERR_UNSUPPORTED, "TarMAC observe -> act covers the default observation: no optional column, 10 circular neighbours, no link defects");
+  if (env->cfg.nb_houses < 11 || actor->num_state != 51)
+    return fail(env, MDR_ERR_UNSUPPORTED, "TarMAC observe -> act covers 51 features: nb_houses >= 11 and an actor with num_state = 51");
+  mdr::ObserveArgs o;
+  int rc = observe_args(env, spec, nullptr, nullptr, stream, &o);
+  if (rc != MDR_OK) return rc;
+  if (o.ext) return fail(env, MDR_ERR_UNSUPPORTED, "TarMAC observe -> act covers the default observation");
+  rc = mdr::tarmac_sample_observe(actor, o, seed, step, step_dev, workspace, action, a_prob, probs, rows_out, (hipStream_t)stream);
+  if (rc == MDR_ERR_UNSUPPORTED) return fail(env, rc, "TarMAC observe -> act: actor shape or cluster size without a kernel");
+  if (rc != MDR_OK) return fail(env, rc, "mdr_env_tarmac_actor_sample: invalid actor or launch failed");
+  return MDR_OK;
 }
 
 int mdr_env_comm_draws(mdr_env_t* env, const mdr_obs_spec_t* spec, int32_t* senders, uint8_t* keep, void* stream) {

@@ -272,6 +272,10 @@ int obs_message_fields(const mdr_obs_spec_t& s);
 // the policy kernels of csrc/mdr_policy.hip on the compact state; actor / step_dev etc. as mdr_actor_sample
 int launch_actor_observe(const struct mdr_actor* actor, const ObserveArgs& o, uint64_t seed, uint64_t step, const int32_t* step_dev,
                          uint8_t* action, float* a_prob, float* probs, float* rows_out, hipStream_t s);
+// The TarMAC actor's launch chain with the observe form of its encode kernel (mdr_tarmac_mlp.hip): mdr_tarmac_actor_sample's checks
+// and results, MDR_ERR_UNSUPPORTED with nothing launched for what tarmac_observe_covered (mdr_tarmac_mlp.h) rules out
+int tarmac_sample_observe(const struct mdr_tarmac_actor* actor, const ObserveArgs& o, uint64_t seed, uint64_t step, const int32_t* step_dev,
+                          void* workspace, uint8_t* action, float* a_prob, float* probs, float* rows_out, hipStream_t s);
 int obs_vector_length(const mdr_obs_spec_t& spec);
 hipError_t launch_step_begin_split(const StepArgs& a, bool reduce, hipStream_t s);
 hipError_t launch_step_end_split(const StepArgs& a, hipStream_t s);

@@ -10,6 +10,7 @@
 #include "../../include/mdr_policy.h"
 #include "mdr_device.h"
 #include "mdr_draw.h"
+#include "mdr_observe.h"
 
 namespace {
 
@@ -74,14 +75,6 @@ struct MlpArgs {
   const int32_t* step_dev;
 };
 
-// A lane-dependent value hidden from loop-invariant code motion (mdr_policy.hip): every LDS read of the tile loop - weights and
-// biases, none of which change after the staging - is addressed from it, so that hipcc re-reads them where they are used instead
-// of hoisting a hundred of them out of the loop into registers the loop does not have.
-__device__ __forceinline__ int tile_local(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
 __device__ __forceinline__ float relu(float x) {      // mdr_policy.hip: max on the bit pattern, one instruction
   const int b = __builtin_bit_cast(int, x);
   return __builtin_bit_cast(float, b > 0 ? b : 0);
@@ -122,6 +115,27 @@ int launch(K kernel, int waves, const MlpArgs& a, int lds_floats, int cus, hipSt
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
+// ---- observe -> act (mdr_env_tarmac_actor_sample): the encode kernels' forms that build their features in LDS (mdr_observe.h)
+constexpr int TARMAC_OBS_ROW = 60;      // floats per staged row (k_tarmac_encode_obs says why)
+constexpr size_t LDS_PER_CU = 160 * 1024;
+
+// LDS: the staged weights, then one window of `tile` rows per wave and, with rows_out, the row table of observe_store_rows.  A form
+// whose windows do not fit beside its weights runs with fewer waves per workgroup, whole waves per SIMD.
+template <typename K>
+int launch_observe(K kernel, int waves, int tile, const MlpArgs& a, const mdr::ObserveArgs& o, float* rows_out, int cus, hipStream_t s) {
+  const size_t fixed = (size_t)(a.na + a.np + a.nvec) * sizeof(float) + (rows_out ? (size_t)tile * 51 * sizeof(uint16_t) : 0);
+  const size_t window = (size_t)tile * TARMAC_OBS_ROW * sizeof(float);
+  while (waves > 4 && fixed + waves * window > LDS_PER_CU) waves -= 4;
+  const size_t lds_bytes = fixed + waves * window;
+  if (lds_bytes > LDS_PER_CU) return MDR_ERR_UNSUPPORTED;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+    return MDR_ERR_HIP;
+  const int64_t want = (a.ntiles + waves - 1) / waves;
+  const unsigned grid = (unsigned)(want < cus ? want : cus);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds_bytes, s, a, o, rows_out);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
 // ---- the bf16x3 fragments (include/mdr_policy.h): 512 4-byte words per (k-step, output block) pair - head and tail, 64 lanes, 8 bf16
 constexpr int PAIR_WORDS = 512;
 __host__ __device__ inline int ksteps_rows(int n) { return (n + 31) / 32; }      // 32 floats of a row per k-step
@@ -137,6 +151,15 @@ inline int64_t head_words(int H, int V, int with_comm) { return (int64_t)PAIR_WO
 
 namespace mdr {
 // The launch chain of mdr_tarmac_actor_sample for MDR_TARMAC_BF16X3, after that entry point's argument checks (mdr_tarmac_mlp_bf16.hip)
-int tarmac_sample_bf16(const mdr_tarmac_actor_t* actor, const float* obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed, uint64_t step,
-                       const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, int cus, void* stream);
+// (`o` != nullptr: the observe form of the encode kernel on the env's compact state instead of `obs`, `rows_out` optional)
+int tarmac_sample_bf16(const mdr_tarmac_actor_t* actor, const float* obs, const ObserveArgs* o, float* rows_out, int32_t nb_envs, int32_t nb_houses,
+                       uint64_t seed, uint64_t step, const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, int cus,
+                       void* stream);
+
+// What the observe forms cover: the default observation (51 features: ten circular neighbours, no optional column, no link defect)
+// of unsharded envs of at least 11 houses whose tiles of `tile` agents fit the staging lanes of a wave
+inline bool tarmac_observe_covered(const ObserveArgs& o, int num_state, int tile) {
+  if (o.ext || num_state != 51 || o.N < 11 || o.E < 0) return false;
+  return o.N % tile == 0 || observe_window_lanes(o.N, 10, tile) <= 64;
+}
 }  // namespace mdr

@@ -9,6 +9,8 @@
 //
 //   k_tarmac_encode  obs rows -> obs2hidden (F -> H relu -> H) = x -> cat[:, 0:H]; from the same registers hidden2query | hidden2key |
 //                    hidden2value (H -> H tanh -> K | K | V) -> qkv [A][K + K + V], the buffer mdr_tarmac_comm reads in place
+//   k_tarmac_encode_obs  the same from the env's compact state: the features are built in the wave's LDS window (mdr_observe.h)
+//                    instead of being read from observation rows - mdr_env_tarmac_actor_sample
 //   k_tarmac_rehop   hops >= 1: [comm, h] -> msg_state2state (H + V -> H + V tanh -> H) = h' -> state; the same projections -> qkv
 //   k_tarmac_head    cat = [x, comm] -> comm_hidden2action (H + V -> H relu -> 2) (hidden2action on x without communication), the
 //                    two-logit softmax and the action draw of mdr_logits_sample (mdr_draw.h)
@@ -181,6 +183,108 @@ __global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_enc
   }
 }
 
+// Observe -> act (mdr_env_tarmac_actor_sample): k_tarmac_encode with its 13 features per lane read from the wave's LDS window
+// instead of an observation row.  The window is staged from the env's compact state by the helpers of mdr_observe.h exactly as
+// k_actor_observe16 (mdr_policy.hip) stages it for the default observation - 16 consecutive agents per wave, one window per wave -
+// and holds normStateDict feature n of tile row r at float ROW r + (n < 11 ? 40 + n : n - 11).  Lane group g takes the features
+// 13 g + s of its agent, the k-step order of frag_encode, so the MFMA sequence and its operands are those of the rows path; index
+// 51, the pad of group 3's last k-step, reads feature 50 as the rows path does (against a zero weight).
+// Row stride: TARMAC_OBS_ROW = 60 floats.  The features are read with 4-byte LDS loads in which the 16 lanes of a group address the
+// same column of 16 consecutive rows, on 32 banks of 4 bytes.  The stride has to stay a multiple of 4 floats for the 16-byte stores
+// of the staging (an odd one would be conflict-free); 60 = 28 (mod 32) puts the 16 rows on 8 banks, two lanes each, where OBS_ROW = 56
+// = 24 (mod 32) - chosen for 16-byte reads - folds them onto 4, four lanes each.  The window has no pad behind its rows: no read
+// goes past float 52 of a row.  16 windows of 3840 bytes beside the ~94 KB of weights: 157 KB with the row table, under the 160 KB.
+// The loads of a wave's next tile are issued before the tile's matrix work and land during it; its rows are staged behind layer 1,
+// once the features of the current tile are consumed, and gathered at the end of the tile.
+template <int MBH, int MBV, bool EXACT, bool STORE, bool GEN>
+__global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_encode_obs(MlpArgs a, mdr::ObserveArgs o, float* rows_out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int TILE = 16, ROW = TARMAC_OBS_ROW, WIN = TILE * ROW;
+  float* fa = lds;
+  float* fp = fa + a.na;
+  float* vec = fp + a.np;
+  const int tid = threadIdx.x;
+  const int NW = (int)(blockDim.x >> 6);      // as many of the form's waves as the windows leave room for
+  float* rows = vec + a.nvec + (tid >> 6) * WIN;
+  uint16_t* table = reinterpret_cast<uint16_t*>(vec + a.nvec + NW * WIN);      // [TILE * 51] (only when rows are stored)
+  stage(fa, a.fa, a.na, tid);
+  if (a.with_comm) stage(fp, a.fp, a.np, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  for (int i = lane0; i < WIN; i += 64) rows[i] = 0.0f;
+  if (STORE) observe_build_table<TILE, ROW>(table, tid, 64 * NW);
+  __syncthreads();
+  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
+  const VecLayout L = vec_layout(mbh, mbv, a.mbm);
+  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
+  const float* f2 = fa + a.S0 * 64 * mbh;
+  const double* sig_row = observe_sig_row(o);
+  TileCursor tc;
+  tc.init(wave * TILE, nwaves * TILE, o.N);
+  float xr[16] = {};
+  auto gather = [&](int64_t first_agent) {
+    const int g = lane0 >> 4;
+    float* row = rows + r * ROW;
+    const float lock = row[4 * OBS_C + 11], y = row[4 * OBS_C + 12];
+    // the senders' seconds_since_off become quotients by the RECEIVER's lockout, in place: lane group g takes the messages g, g + 4
+    // and g + 8 of its agent's row (k_actor_observe16)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int m = g + 4 * i;
+      if (m < OBS_C) row[4 * m + 1] = mdr::div_by_lockout(row[4 * m + 1], lock, y);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+    for (int s = 0; s < 13; ++s) {
+      const int n = min(13 * g + s, 50);
+      xr[s] = row[n < 11 ? 4 * OBS_C + n : n - 11];
+    }
+    if (STORE)
+      observe_store_rows<TILE>(rows, table, rows_out + first_agent * 51, lane0,
+                               GEN ? (int)((a.A - first_agent) < (int64_t)TILE ? (a.A - first_agent) : (int64_t)TILE) : TILE);
+  };
+  SegSlot slot{};
+  if (wave < a.ntiles) {
+    if (GEN) {
+      const HouseRegs first = observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, wave * TILE, a.A, lane0, slot);
+      observe_stage_gen<false, ROW>(o, first, slot, rows);
+    } else {
+      const HouseRegs first = observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
+      observe_stage<TILE, false, ROW>(o, first, rows, lane0);
+    }
+    observe_window_fence();
+    gather(wave * TILE);
+  }
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const int64_t agent = t * 16 + r;
+    const bool valid = agent < a.A;
+    const int64_t ac = valid ? agent : a.A - 1;
+    const bool more = t + nwaves < a.ntiles;
+    tc.next();
+    HouseRegs nxt{};
+    if (more) nxt = GEN ? observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, (t + nwaves) * TILE, a.A, lane0, slot) : observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
+    f32x4 t1[MBH], x[MBH];
+    init_bias<MBH>(vec + L.o1, g, mbh, t1);
+    layer_feats<16, MBH, EXACT>(fa, xr, a.S0, t1, mbh, lane);
+    if (more) {      // the features are in the MFMA pipeline: the window is free for the next tile's rows
+      if (GEN) observe_stage_gen<false, ROW>(o, nxt, slot, rows);
+      else observe_stage<TILE, false, ROW>(o, nxt, rows, lane0);
+    }
+    init_bias<MBH>(vec + L.o2, g, mbh, x);
+    layer_regs<MBH, MBH, EXACT, ACT_RELU>(f2, t1, mbh, x, mbh, lane);
+    float* cat_row = a.cat + ac * a.ldcat;
+#pragma unroll
+    for (int mb = 0; mb < MBH; ++mb)
+      if (valid && 16 * mb + 4 * g < a.H) *reinterpret_cast<f32x4*>(cat_row + 16 * mb + 4 * g) = x[mb];
+    if (a.with_comm) projections<MBH, MBV, EXACT>(fp, vec, L, x, mbh, mbv, a.K, a.V, a.qkv + ac * a.ldqkv, valid, lane);
+    if (more) {
+      observe_window_fence();
+      gather((t + nwaves) * TILE);
+    }
+  }
+}
+
 // frag_msg: layer 1 [V / 4 + H / 4 steps][64 mbm] - the comm columns of the concatenation [comm, h] first - then layer 2
 // [4 mbm steps][64 mbh]
 template <int MBH, int MBV, int MBM, bool EXACT>
@@ -333,9 +437,12 @@ int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t* actor, int64_
   return nb_agents * floats * (int64_t)sizeof(float);
 }
 
-int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed, uint64_t step,
-                            const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, void* stream) {
-  if (!actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || !obs || !workspace || !action) return MDR_ERR_INVALID;
+// The launch chain of a sample.  `o` == nullptr: from the observation rows `obs`; else from the env's compact state (`obs` unused),
+// `rows_out` optional.  Every refusal comes before the first launch.
+static int sample_chain(const mdr_tarmac_actor_t* actor, const float* obs, const mdr::ObserveArgs* o, float* rows_out, int32_t nb_envs,
+                        int32_t nb_houses, uint64_t seed, uint64_t step, const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob,
+                        float* probs, void* stream) {
+  if (!actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || (!obs && !o) || !workspace || !action) return MDR_ERR_INVALID;
   if (nb_envs < 0 || nb_houses <= 0) return MDR_ERR_INVALID;
   const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value;
   const int hops = actor->num_hops, wc = actor->with_comm != 0;
@@ -346,9 +453,10 @@ int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, i
   if (!actor->frag_encode || !actor->frag_head || !actor->vec) return MDR_ERR_INVALID;
   if (wc && (!actor->frag_proj || (hops > 1 && !actor->frag_msg))) return MDR_ERR_INVALID;
   if (!aligned16(workspace) || !aligned16(actor->frag_encode) || !aligned16(actor->frag_head) || !aligned16(actor->vec) ||
-      !aligned16(actor->frag_proj) || !aligned16(actor->frag_msg) || ((uintptr_t)obs & 3u))
+      !aligned16(actor->frag_proj) || !aligned16(actor->frag_msg) || ((uintptr_t)obs & 3u) || ((uintptr_t)rows_out & 3u))
     return MDR_ERR_INVALID;
   if (!shape_covered(F, H, K, V) || hops > MAX_HOPS) return MDR_ERR_UNSUPPORTED;
+  if (o && !mdr::tarmac_observe_covered(*o, F, actor->precision == MDR_TARMAC_BF16X3 ? 32 : 16)) return MDR_ERR_UNSUPPORTED;
   const int c = actor->nb_comm < nb_houses - 1 ? actor->nb_comm : nb_houses - 1;
   if (wc && actor->mode == MDR_TARMAC_NEIGHBOURS && c > MAX_C) return MDR_ERR_UNSUPPORTED;
   const int64_t A = (int64_t)nb_envs * nb_houses;
@@ -358,7 +466,7 @@ int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, i
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
   if (actor->precision == MDR_TARMAC_BF16X3)
-    return mdr::tarmac_sample_bf16(actor, obs, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, cus, stream);
+    return mdr::tarmac_sample_bf16(actor, obs, o, rows_out, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, cus, stream);
 
   const int mbh = blocks(H), mbv = blocks(V), mbm = blocks(H + V);
   const VecLayout L = vec_layout(mbh, mbv, mbm);
@@ -384,8 +492,21 @@ int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, i
   a.fa = actor->frag_encode, a.fp = actor->frag_proj, a.na = (int)encode_floats(F, H);
   a.in0 = obs, a.ld0 = F, a.D0 = F, a.S0 = (F + 3) / 4;
   a.vec0 = whole4(a.S0, F) && aligned16(obs);
-  int rc = exact ? launch(k_tarmac_encode<4, 1, true>, WAVES, a, a.na + a.np + a.nvec, cus, s)
-                 : launch(k_tarmac_encode<4, 2, false>, WAVES_GEN, a, a.na + a.np + a.nvec, cus, s);
+  int rc;
+  if (o) {      // the same layers on features built in LDS: whole-tile staging where no tile of 16 leaves its env
+    const bool gen = o->N % 16 != 0;
+#define MDR_TARMAC_OBS(...)                                                                                                  \
+  (rows_out ? (gen ? launch_observe(k_tarmac_encode_obs<__VA_ARGS__, true, true>, waves, 16, a, *o, rows_out, cus, s)       \
+                   : launch_observe(k_tarmac_encode_obs<__VA_ARGS__, true, false>, waves, 16, a, *o, rows_out, cus, s))     \
+            : (gen ? launch_observe(k_tarmac_encode_obs<__VA_ARGS__, false, true>, waves, 16, a, *o, rows_out, cus, s)      \
+                   : launch_observe(k_tarmac_encode_obs<__VA_ARGS__, false, false>, waves, 16, a, *o, rows_out, cus, s)))
+    const int waves = exact ? WAVES : WAVES_GEN;
+    rc = exact ? MDR_TARMAC_OBS(4, 1, true) : MDR_TARMAC_OBS(4, 2, false);
+#undef MDR_TARMAC_OBS
+  } else {
+    rc = exact ? launch(k_tarmac_encode<4, 1, true>, WAVES, a, a.na + a.np + a.nvec, cus, s)
+               : launch(k_tarmac_encode<4, 2, false>, WAVES_GEN, a, a.na + a.np + a.nvec, cus, s);
+  }
   if (rc != MDR_OK) return rc;
   if (wc) {
     for (int hop = 0; hop < hops; ++hop) {
@@ -411,4 +532,19 @@ int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, i
                                   : launch(k_tarmac_head<4, 24, false>, WAVES_GEN, a, a.na + a.nvec, cus, s);
 }
 
+int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed, uint64_t step,
+                            const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, void* stream) {
+  if (!obs) return MDR_ERR_INVALID;
+  return sample_chain(actor, obs, nullptr, nullptr, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, stream);
+}
+
 }  // extern "C"
+
+namespace mdr {
+
+int tarmac_sample_observe(const mdr_tarmac_actor_t* actor, const ObserveArgs& o, uint64_t seed, uint64_t step, const int32_t* step_dev,
+                          void* workspace, uint8_t* action, float* a_prob, float* probs, float* rows_out, hipStream_t stream) {
+  return sample_chain(actor, nullptr, &o, rows_out, o.E, o.N, seed, step, step_dev, workspace, action, a_prob, probs, (void*)stream);
+}
+
+}  // namespace mdr

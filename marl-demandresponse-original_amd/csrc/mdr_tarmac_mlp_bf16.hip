@@ -230,6 +230,153 @@ __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_bf16(MlpArgs 
   }
 }
 
+// Observe -> act (mdr_env_tarmac_actor_sample): k_tarmac_encode_bf16 with the floats of its two row-fed k-steps read from the wave's
+// LDS window instead of observation rows, as k_tarmac_encode_obs (mdr_tarmac_mlp.hip) does for the fp32 form.  A tile is 32
+// consecutive agents - column block c holds the tile rows 16 c + r - staged as k_actor_observe_bf16 (mdr_policy.hip) stages its
+// tiles of 32; element j of lane group g in k-step s is normStateDict feature n = 32 s + 8 g + j at window float ROW row + (n < 11 ?
+// 40 + n : n - 11), and an explicit zero from n = 51 on, as split_rows builds it.  Row stride: TARMAC_OBS_ROW = 60 for the same
+// 4-byte reads of one column of 16 consecutive rows.  8 windows of 7680 bytes beside ~95 KB of fragments: 158 KB with the row table.
+// The loads of the next tile are issued before the tile's matrix work; its rows are staged once both k-steps have been split.  The
+// general form has no registers left to carry them, or the next tile's features, across the layers (it spills with them): it loads
+// and stages at the tile's end and reads its features when the tile starts.
+template <int MBH, int MBV, bool EXACT, bool STORE, bool GEN>
+__global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_obs_bf16(MlpArgs a, mdr::ObserveArgs o, float* rows_out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int TILE = 16 * NCOL, ROW = TARMAC_OBS_ROW, WIN = TILE * ROW;
+  constexpr bool OVERLAP = EXACT;
+  float* fa = lds;
+  float* fp = fa + a.na;
+  float* vec = fp + a.np;
+  const int tid = threadIdx.x;
+  const int NW = (int)(blockDim.x >> 6);      // as many of the form's waves as the windows leave room for
+  float* rows = vec + a.nvec + (tid >> 6) * WIN;
+  uint16_t* table = reinterpret_cast<uint16_t*>(vec + a.nvec + NW * WIN);      // [TILE * 51] (only when rows are stored)
+  stage(fa, a.fa, a.na, tid);
+  if (a.with_comm) stage(fp, a.fp, a.np, tid);
+  stage(vec, a.vec, a.nvec, tid);
+  const int lane0 = tid & 63, r = lane0 & 15;
+  for (int i = lane0; i < WIN; i += 64) rows[i] = 0.0f;
+  if (STORE) observe_build_table<TILE, ROW>(table, tid, 64 * NW);
+  __syncthreads();
+  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
+  const uint4* fp4 = reinterpret_cast<const uint4*>(fp);
+  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
+  constexpr int SH = (MBH + 1) / 2;
+  const int sh = EXACT ? SH : ksteps_regs(mbh);
+  const VecLayout L = vec_layout(mbh, mbv, a.mbm);
+  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
+  const uint4* f2 = fa4 + a.S0 * mbh * 128;
+  const double* sig_row = observe_sig_row(o);
+  TileCursor tc;
+  tc.init(wave * TILE, nwaves * TILE, o.N);
+  float xr[NCOL][16];      // element j of k-step s: [8 s + j]
+  auto gather = [&](int64_t first_agent) {
+    const int g = lane0 >> 4;
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) {      // the senders' seconds_since_off by the RECEIVER's lockout, in place (k_tarmac_encode_obs)
+      float* row = rows + (16 * c + r) * ROW;
+      const float lock = row[4 * OBS_C + 11], y = row[4 * OBS_C + 12];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int m = g + 4 * i;
+        if (m < OBS_C) row[4 * m + 1] = mdr::div_by_lockout(row[4 * m + 1], lock, y);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (STORE)
+      observe_store_rows<TILE>(rows, table, rows_out + first_agent * 51, lane0,
+                               GEN ? (int)((a.A - first_agent) < (int64_t)TILE ? (a.A - first_agent) : (int64_t)TILE) : TILE);
+  };
+  auto feats = [&]() {
+    const int g = lane0 >> 4;
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) {
+      const float* row = rows + (16 * c + r) * ROW;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int n = 32 * (k >> 3) + 8 * g + (k & 7);
+        const int nc = min(n, 50);
+        const float v = row[nc < 11 ? 4 * OBS_C + nc : nc - 11];
+        xr[c][k] = n < 51 ? v : 0.0f;
+      }
+    }
+  };
+  SegSlot slot{};
+  if (wave < a.ntiles) {
+    if (GEN) {
+      const HouseRegs first = observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, wave * TILE, a.A, lane0, slot);
+      observe_stage_gen<false, ROW>(o, first, slot, rows);
+    } else {
+      const HouseRegs first = observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
+      observe_stage<TILE, false, ROW>(o, first, rows, lane0);
+    }
+    observe_window_fence();
+    gather(wave * TILE);
+    if (OVERLAP) feats();
+  }
+  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
+    const int lane = tile_local(lane0), g = lane >> 4;
+    const Tile T = tile_of(t, r, a.A);
+    if (!OVERLAP) feats();
+    float* cat_row[NCOL];
+    float* qkv_row[NCOL];
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) {
+      cat_row[c] = a.cat + T.ac[c] * a.ldcat;
+      qkv_row[c] = a.qkv + T.ac[c] * a.ldqkv;
+    }
+    const bool more = t + nwaves < a.ntiles;
+    tc.next();
+    HouseRegs nxt{};
+    auto load_next = [&]() {
+      nxt = GEN ? observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, (t + nwaves) * TILE, a.A, lane0, slot) : observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
+    };
+    auto stage_next = [&]() {
+      if (GEN) observe_stage_gen<false, ROW>(o, nxt, slot, rows);
+      else observe_stage<TILE, false, ROW>(o, nxt, rows, lane0);
+    };
+    if (OVERLAP && more) load_next();
+    f32x4 t1[NCOL][MBH], x[NCOL][MBH];
+    init_bias<MBH>(vec + L.o1, g, mbh, t1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      if (s < a.S0) {
+        bf16x8 Bh[NCOL], Bl[NCOL];
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c) {
+          float v[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = xr[c][8 * s + j];
+          uint4 bh, bl;
+          split8(v, bh, bl);
+          Bh[c] = __builtin_bit_cast(bf16x8, bh);
+          Bl[c] = __builtin_bit_cast(bf16x8, bl);
+        }
+        mma_step<MBH, EXACT>(fa4 + s * mbh * 128, mbh, lane, Bh, Bl, t1);
+      }
+    if (OVERLAP && more) stage_next();      // the features are split and in the MFMA pipeline: the window is free for the next tile's rows
+    init_bias<MBH>(vec + L.o2, g, mbh, x);
+#pragma unroll
+    for (int s = 0; s < SH; ++s)
+      if (EXACT || s < sh) {
+        bf16x8 Bh[NCOL], Bl[NCOL];
+        split_regs<MBH, ACT_RELU>(t1, s, Bh, Bl);
+        mma_step<MBH, EXACT>(f2 + s * mbh * 128, mbh, lane, Bh, Bl, x);
+      }
+    store_blocks<MBH>(x, cat_row, T.valid, a.H, g);
+    if (a.with_comm) projections<MBH, MBV, EXACT>(fp4, vec, L, x, mbh, mbv, a.K, a.V, qkv_row, T.valid, lane);
+    if (more) {
+      if (!OVERLAP) {
+        load_next();
+        stage_next();
+      }
+      observe_window_fence();
+      gather((t + nwaves) * TILE);
+      if (OVERLAP) feats();
+    }
+  }
+}
+
 // frag_msg: msg_state2state.0 [S0 = ceil(V / 32) k-steps fed from the comm columns, then S1 = ceil(H / 32) fed from h][mbm pairs],
 // then msg_state2state.2 [ceil(mbm / 2)][mbh]
 template <int MBH, int MBV, int MBM, bool EXACT>
@@ -364,8 +511,9 @@ __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_head_bf16(MlpArgs a)
 
 namespace mdr {
 
-int tarmac_sample_bf16(const mdr_tarmac_actor_t* actor, const float* obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed, uint64_t step,
-                       const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, int cus, void* stream) {
+int tarmac_sample_bf16(const mdr_tarmac_actor_t* actor, const float* obs, const ObserveArgs* o, float* rows_out, int32_t nb_envs, int32_t nb_houses,
+                       uint64_t seed, uint64_t step, const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, int cus,
+                       void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value;
   const int hops = actor->num_hops, wc = actor->with_comm != 0;
@@ -393,8 +541,20 @@ int tarmac_sample_bf16(const mdr_tarmac_actor_t* actor, const float* obs, int32_
   a.fa = actor->frag_encode, a.fp = actor->frag_proj, a.na = (int)encode_words(F, H);
   a.in0 = obs, a.ld0 = F, a.D0 = F, a.S0 = ksteps_rows(F);
   a.vec0 = F % 4 == 0 && aligned16(obs);
-  int rc = exact ? launch(k_tarmac_encode_bf16<4, 1, true>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s)
-                 : launch(k_tarmac_encode_bf16<4, 2, false>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s);
+  int rc;
+  if (o) {      // the same layers on features built in LDS: whole-tile staging where no tile of 32 leaves its env
+    const bool gen = o->N % (16 * NCOL) != 0;
+#define MDR_TARMAC_OBS(...)                                                                                                                    \
+  (rows_out ? (gen ? launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, true, true>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s)        \
+                   : launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, true, false>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s))      \
+            : (gen ? launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, false, true>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s)       \
+                   : launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, false, false>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s)))
+    rc = exact ? MDR_TARMAC_OBS(4, 1, true) : MDR_TARMAC_OBS(4, 2, false);
+#undef MDR_TARMAC_OBS
+  } else {
+    rc = exact ? launch(k_tarmac_encode_bf16<4, 1, true>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s)
+               : launch(k_tarmac_encode_bf16<4, 2, false>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s);
+  }
   if (rc != MDR_OK) return rc;
   if (wc) {
     for (int hop = 0; hop < hops; ++hop) {

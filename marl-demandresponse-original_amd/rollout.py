@@ -258,16 +258,29 @@ def collect_ppo_rollout(env, actor: nn.Module, nb_steps: int, gamma: float = 0.9
     return out
 
 
+def _tarmac_observe_act(env, actor, observe_act: Optional[bool]) -> bool:
+    """``observe_act`` of collect_tarmac_rollout / deploy_policy resolved: None -> wherever ``FusedTarMACActor.sample_env`` serves
+    the env, False -> observation rows, True -> required (ValueError where it cannot be)."""
+    from .tarmac import FusedTarMACActor
+    can = isinstance(actor, FusedTarMACActor) and actor.observe_supported(env)
+    if observe_act and not can:
+        raise ValueError("observe_act=True needs a FusedTarMACActor and an env its sample_env covers (FusedTarMACActor.observe_supported)")
+    return can if observe_act is None else bool(observe_act)
+
+
 @torch.no_grad()
 def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, critic: Optional[nn.Module] = None, seed: int = 0,
-                           store_states: bool = True) -> Dict[str, torch.Tensor]:
+                           store_states: bool = True, observe_act: Optional[bool] = None) -> Dict[str, torch.Tensor]:
     """The interaction loop of train_tarmacPPO.py:62-119 for all envs at once: every step ``env.obs_vector("rows")`` ->
     ``TarMACActor.sample`` or ``FusedTarMACActor.sample`` (in either precision, "fp32" or "bf16x3": the object carries it; TarmacPPO.select_actions, agents/tarmac_ppo.py:83-95: each agent attends to the hidden states of the other
     agents of ITS env, hence observations as [E, N, F]) -> ``env.step``.  Same keys and flattened [T, E*N] layout as
     ``collect_ppo_rollout``: ``state`` [T+1, E*N, F] (omitted without ``store_states``), ``action`` int64, ``a_prob``, ``reward``,
     ``done`` (True on the last step) and ``return``; the bootstrap through ``critic`` (a ``TarMACCritic``) is its [E, N] value of the
     last next-state (tarmac_ppo.py:136-141).  The env steps without writing its observation planes during the collection and brings
-    them up to date once at the end.  House-sharded envs are refused: attention across shards needs a halo exchange of keys and values."""
+    them up to date once at the end.  House-sharded envs are refused: attention across shards needs a halo exchange of keys and values.
+    ``observe_act`` (default: whenever ``actor`` is a ``FusedTarMACActor`` whose ``observe_supported(env)`` holds): the steps go
+    through ``FusedTarMACActor.sample_env`` - no observation rows; with ``store_states`` the rows of step t are written into
+    ``state[t]`` on the side by the same kernel.  The same tensors bit for bit either way; False: always rows; True: required."""
     from .tarmac import FusedTarMACActor, TarMACActor
     if not isinstance(actor, (TarMACActor, FusedTarMACActor)):
         raise ValueError("collect_tarmac_rollout takes a TarMACActor or a FusedTarMACActor")
@@ -281,7 +294,9 @@ def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, criti
     act_u8 = torch.empty((T, E * N), dtype=torch.uint8, device=dev)
     a_prob = torch.empty((T, E * N), dtype=torch.float32, device=dev)
     reward = torch.empty((T, E * N), dtype=torch.float32, device=dev)
-    scratch = None if store_states else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
+    observe_act = _tarmac_observe_act(env, actor, observe_act)
+    need_last = store_states or critic is not None      # the next-state of the last transition / the critic's bootstrap input
+    scratch = None if store_states or (observe_act and not need_last) else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
 
     def observe(t):
         return env.obs_vector("rows", out=states[t].view(E, N, F_len) if store_states else scratch)
@@ -289,13 +304,19 @@ def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, criti
     planes_were_on = bool(getattr(env, "_obs_planes_on", True))
     if planes_were_on:
         env.set_obs_planes(False)
-    obs = observe(0)
+    obs = None if observe_act else observe(0)
     step0 = env.steps_taken
     for t in range(T):
-        actor.sample(obs, seed, step0 + t, action=act_u8[t], a_prob=a_prob[t])
+        if observe_act:      # normStateDict + select_actions without observation rows; `state` stored on the side if wanted
+            actor.sample_env(env, seed, step0 + t, action=act_u8[t], a_prob=a_prob[t], rows_out=states[t] if store_states else None)
+        else:
+            actor.sample(obs, seed, step0 + t, action=act_u8[t], a_prob=a_prob[t])
         _, r, _, _ = env.step(act_u8[t].view(E, N))
         reward[t] = r.reshape(-1)
-        obs = observe(t + 1)
+        if not observe_act:
+            obs = observe(t + 1)
+    if observe_act and need_last:
+        obs = observe(T)
     if planes_were_on and not env._obs_planes_on:
         env.set_obs_planes(True)
     done = torch.zeros((T, E * N), dtype=torch.bool, device=dev)
@@ -396,7 +417,7 @@ def deploy_controller(env, kind: str, nb_steps: int) -> Dict[str, torch.Tensor]:
 
 
 def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional[bool] = None, policy_precision: str = "fp32",
-                  greedy: bool = False) -> Dict[str, torch.Tensor]:
+                  greedy: bool = False, observe_act: Optional[bool] = None) -> Dict[str, torch.Tensor]:
     """The evaluation loop of main-deploy.py:99-152 with a learned agent (PPOAgent / DQNAgent, agents/rl_controllers.py) for all
     envs at once: every step observation -> ``policy`` -> ``env.step``, with the metrics the script accumulates: ``reward_sum``
     [E, N], ``sq_temp_error_sum`` [E] (sum over steps and houses of (house_temp - target)^2), ``sq_signal_error_sum`` [E] (sum over
@@ -407,7 +428,9 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     env.device_time_index``, ``env.step`` - one stream, no parallel branches, so ``use_graph=True`` captures it), the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
     here, and observation and policy are then ONE kernel wherever ``collect_ppo_rollout`` would make them one (no observation rows at
     all) - or a ready ``FusedActor``: one packed with ``feature_order=FEATURES_OBSERVE`` takes the same one-kernel path, any other
-    gets observation rows.
+    gets observation rows.  ``observe_act`` concerns a ``FusedTarMACActor`` only: None (default) - ``sample_env`` instead of rows +
+    ``sample`` wherever ``observe_supported(env)`` holds, the same actions bit for bit, captured in the graph like the rows path;
+    False - always rows; True - required (ValueError otherwise, and for every other kind of policy).
 
     ``use_graph`` (default: when the env was built with ``graph_mode=True``): the step is captured once in a
     ``torch.cuda.CUDAGraph`` and replayed - the launch-bound regime of small batches."""
@@ -430,8 +453,9 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
             raise ValueError("deploy_policy takes Linear(F,H1) - Linear(H1,H2) - Linear(H2,2) networks on the device (or a FusedActor)")
         policy = _fused_policy(policy, dev, policy_precision, observe=_observe_act_supported(env, policy),
                                msg_floats=4 * _observe_senders(env), greedy=greedy)
-    observe_act = getattr(policy, "feature_order", 0) == FEATURES_OBSERVE
-    obs = None if observe_act else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
+    tarmac_observe = _tarmac_observe_act(env, policy, observe_act)
+    one_kernel = getattr(policy, "feature_order", 0) == FEATURES_OBSERVE
+    obs = None if one_kernel or tarmac_observe else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
     act = torch.empty(E * N, dtype=torch.uint8, device=dev)
     act_prob = torch.empty(E * N, dtype=torch.float32, device=dev) if tarmac else None      # no allocation inside a captured step
     out = {"reward_sum": torch.zeros((E, N), dtype=torch.float32, device=dev),
@@ -449,8 +473,10 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     step_dev = env.device_time_index if graph_mode else None
 
     def one_step(t):
-        if observe_act:      # normStateDict + act for all agents in one kernel: no observation rows
+        if one_kernel:       # normStateDict + act for all agents in one kernel: no observation rows
             policy.sample_env(env, seed, step0 + t, action=act, step_dev=step_dev)
+        elif tarmac_observe:  # the fused TarMAC chain fed from the compact state: no observation rows either
+            policy.sample_env(env, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act, a_prob=act_prob)
         elif tarmac:         # TarmacPPOAgent.act (agents/rl_controllers.py:86-122): the agents of an env attend to each other
             env.obs_vector("rows", out=obs)
             policy.sample(obs, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act, a_prob=act_prob)

@@ -43,6 +43,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
+from .policy import OBSERVE_NUM_STATE, observe_feature_order
 
 MODES = {"neighbours": 0, "none": 1}      # mdr_tarmac_mode
 MAX_HOPS, MAX_KEY, MAX_VALUE, MAX_COMM = 4, 32, 64, 64
@@ -494,6 +495,15 @@ def _from_regs(n_in: int):
 PRECISIONS = {"fp32": 0, "bf16x3": 1}      # mdr_tarmac_precision
 
 
+def observe_window_positions():
+    """Float of a staged LDS row that holds normStateDict feature n of the default observation, for n < 51: the ten message records
+    first, then the 11 own features (n < 11 -> 40 + n, else n - 11) - the inverse of ``policy.observe_feature_order()``, the order
+    MDR_FEATURES_OBSERVE actors are packed in.  ``FusedTarMACActor.sample_env`` keeps its fragments in normStateDict order and reads
+    feature n at this position instead."""
+    import numpy as np
+    return np.argsort(observe_feature_order(OBSERVE_NUM_STATE, 40))
+
+
 def bf16_split(x):
     """float32 array -> (head, tail) bf16 bit patterns as uint16: head = bf16(x), tail = bf16(x - head), round to nearest even."""
     import numpy as np
@@ -630,7 +640,8 @@ class FusedTarMACActor:
     the draw unchanged) - the same split as ``FusedActor``'s BF16X3 layout; the ``.precision`` attribute says which.  Inference only; to
     ``TarMACActor`` what ``FusedActor`` is to ``ActorMLP``.  Covers num_obs <= 64, hidden_state_size a multiple of 4 <= 64, num_key
     a multiple of 4 <= 16, num_value a multiple of 4 <= 32, two actions, the modes 'neighbours' and 'none'; anything else is a
-    ValueError (the eager band path of ``TarMACActor`` remains for those)."""
+    ValueError (the eager band path of ``TarMACActor`` remains for those).  ``sample_env(env, ...)`` is ``sample`` without the
+    observation rows, bit for bit, for the default observation (``observe_supported``)."""
 
     def __init__(self, actor: "TarMACActor", precision: str = "fp32"):
         if precision not in PRECISIONS:
@@ -742,6 +753,75 @@ class FusedTarMACActor:
                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc != 0:
             raise RuntimeError("mdr_tarmac_actor_sample failed: %s" % lib.mdr_status_string(rc).decode())
+        return (action, a_prob, probs) if want_probs else (action, a_prob)
+
+    def _observe_refusal(self, env) -> Optional[str]:
+        """Why ``sample_env`` cannot serve ``env`` (None: it can) - the conditions ``mdr_env_tarmac_actor_sample`` checks, decided on
+        the host before anything is launched."""
+        if self.actor.num_obs != OBSERVE_NUM_STATE:
+            return "the actor takes %d features, observe -> act builds the default observation of %d" % (self.actor.num_obs, OBSERVE_NUM_STATE)
+        if getattr(env, "sharded", False):
+            return "house-sharded envs are not covered"
+        spec = env._obs_spec("rows")
+        if spec.state_hour or spec.state_day or spec.state_solar_gain or spec.state_thermal or spec.state_hvac or spec.message_thermal or spec.message_hvac:
+            return "an optional state or message column is on"
+        if spec.nb_comm != 10 or spec.links or spec.random_links:
+            return "the env's agents_comm_mode must be 'neighbours' with nb_agents_comm = 10"
+        if spec.comm_defect_prob > 0.0:
+            return "link defects on the env's messages are not covered"
+        if env.nb_houses < 11:
+            return "10 distinct neighbours need at least 11 houses"
+        return None
+
+    def observe_supported(self, env) -> bool:
+        """Can ``sample_env`` serve ``env``?  The default observation of 51 features (no optional state / message column, ten circular
+        neighbours, no link defects) of an unsharded env of at least 11 houses, and an actor with ``num_obs == 51``; the actor's own
+        ``number_agents_comm``, ``comm_mode``, ``comm_defect_prob`` and hop count are the attention's and do not matter here."""
+        return self._observe_refusal(env) is None
+
+    @torch.no_grad()
+    def sample_env(self, env, seed: int, step: int, step_dev: Optional[torch.Tensor] = None, greedy: bool = False, want_probs: bool = False,
+                   action: Optional[torch.Tensor] = None, a_prob: Optional[torch.Tensor] = None, rows_out: Optional[torch.Tensor] = None):
+        """Observe -> act (``mdr_env_tarmac_actor_sample``): ``sample(env.obs_vector("rows"), ...)`` without the rows - the first
+        kernel of the chain builds the 51 features of its agents in LDS from the env's compact state.  Returns what ``sample`` returns,
+        bit for bit.  ``rows_out`` (float32, contiguous, A * 51 elements): also receives the rows, bit for bit ``env.obs_vector("rows")``
+        (the transition buffer's ``state``).  ``ValueError`` before any launch for an env or actor the kernel does not cover
+        (``observe_supported``); no allocation after the first call when ``action`` and ``a_prob`` are passed."""
+        why = self._observe_refusal(env)
+        if why is not None:
+            raise ValueError("FusedTarMACActor.sample_env: " + why)
+        a = self.actor
+        st = self._pack()
+        dev = env.device
+        if dev != self._device:
+            raise ValueError("the env and the actor's parameters must be on the same device")
+        if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.device != dev):
+            raise ValueError("step_dev must be an int32 tensor on the device (env.device_time_index)")
+        E, N = env.nb_envs, env.nb_houses
+        A = E * N
+        if a.with_comm and a.comm_mode == "neighbours" and min(a.number_agents_comm, N - 1) > MAX_COMM:
+            raise ValueError("band attention covers at most %d senders per receiver" % MAX_COMM)
+        for name, t, dt, n in (("action", action, torch.uint8, A), ("a_prob", a_prob, torch.float32, A),
+                               ("rows_out", rows_out, torch.float32, A * OBSERVE_NUM_STATE)):
+            if t is not None and (t.dtype != dt or t.device != dev or t.numel() != n or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous %s tensor of %d elements on the device" % (name, dt, n))
+        lib = nat.load()
+        ws = self.workspace(A, dev)
+        action = torch.empty(A, dtype=torch.uint8, device=dev) if action is None else action
+        a_prob = torch.empty(A, dtype=torch.float32, device=dev) if a_prob is None else a_prob
+        probs = torch.empty((A, 2), dtype=torch.float32, device=dev) if want_probs else None
+        st.greedy = int(bool(greedy))
+        spec = env._obs_spec("rows")
+        with torch.cuda.device(dev):
+            rc = lib.mdr_env_tarmac_actor_sample(env._handle, C.byref(spec), C.byref(st), C.c_uint64(seed & (2 ** 64 - 1)),
+                                                 C.c_uint64(step & (2 ** 64 - 1)), C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None,
+                                                 C.c_void_p(ws.data_ptr()), C.c_void_p(action.data_ptr()), C.c_void_p(a_prob.data_ptr()),
+                                                 C.c_void_p(probs.data_ptr()) if want_probs else None,
+                                                 C.c_void_p(rows_out.data_ptr()) if rows_out is not None else None,
+                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc == nat.MDR_ERR_UNSUPPORTED:
+            raise ValueError("FusedTarMACActor.sample_env: " + lib.mdr_last_error(env._handle).decode())
+        nat.check(lib, env._handle, rc, "mdr_env_tarmac_actor_sample")
         return (action, a_prob, probs) if want_probs else (action, a_prob)
 
     def probs(self, obs: torch.Tensor, seed: int = 0, step: int = 0, step_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
