@@ -308,6 +308,56 @@ int mdr_env_tarmac_actor_sample(mdr_env_t *env, const mdr_obs_spec_t *spec, cons
                                 const int32_t *step_dev, void *workspace, uint8_t *action, float *a_prob, float *probs, float *rows_out,
                                 void *stream);
 
+/* ---- PPO's update step for the MLP actor and critic (PPO.update, agents/ppo.py:139-188): loss and gradient of one minibatch.
+ *
+ * One network of agents/network.py:14-57 - Linear(F,H1) - ReLU - Linear(H1,H2) - ReLU - Linear(H2,O) - in torch's own layout,
+ * w[out][in] contiguous, device memory, read as it is on every call (an optimiser step changes it between any two calls: there is
+ * nothing to repack).  Limits: F <= 64, H1 <= 128, H2 <= 128, O = 2 (actor) or 1 (critic); MAPPO's critic (state + others' actions)
+ * and the observations with message columns (81..121 features) are outside them. */
+typedef struct mdr_mlp {
+  uint32_t struct_size;
+  int32_t num_state, hidden1, hidden2, num_out;
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+} mdr_mlp_t;
+
+/* Floats of the flat gradient dW1 [H1][F] | db1 [H1] | dW2 [H2][H1] | db2 [H2] | dW3 [O][H2] | db3 [O] - torch's parameter order and
+ * layout (reads the shape fields only; host-only, no device call).  -1: a shape outside the limits, a struct_size that is not this
+ * header's. */
+int64_t mdr_mlp_grad_floats(const mdr_mlp_t *net);
+/* Bytes of device scratch one gradient call over nb_rows minibatch rows with this max_workgroups needs: one partial gradient per
+ * workgroup (host-only, no device call; with max_workgroups = 0 enough for the library's own grid on any device).  -1 as above, or
+ * nb_rows < 0, max_workgroups < 0. */
+int64_t mdr_mlp_grad_workspace_bytes(const mdr_mlp_t *net, int64_t nb_rows, int32_t max_workgroups);
+
+/* The clipped surrogate of agents/ppo.py:153-166 and its gradient.  Minibatch row i < nb_rows is transition j = index ? index[i] : i
+ * (`index` device int64, may be NULL: BatchSampler's indices into the buffer); `state` + j * ld_state its F floats (ld_state >= F),
+ * `action[j]` (int64, nonzero = action 1), `old_prob[j]` the stored probability of the taken action - whole-buffer arrays read through
+ * `index` -, `advantage[i]` in minibatch order.  p = softmax(actor(state_j)), ratio_i = p[action_j] / old_prob_j,
+ *   loss = -(1 / nb_rows) sum_i min(ratio_i A_i, clamp(ratio_i, 1 - clip_param, 1 + clip_param) A_i)
+ * and `grad` (mdr_mlp_grad_floats floats) = d loss / d parameters as torch's autograd takes it: d loss / d ratio_i = -A_i / nb_rows
+ * where 1 - clip <= ratio_i <= 1 + clip (bounds included) or ratio_i A_i < clamp(ratio_i) A_i, else 0; relu'(z) = 1 iff z > 0.
+ * old_prob = 0 gives inf / NaN as in the reference.  `loss`: one float on the device.  `ratio` (may be NULL): float [nb_rows].
+ * Exact fp32 on the matrix cores; a persistent grid of min(tiles of 16 rows, max_workgroups) workgroups (0: the library's choice,
+ * min(tiles, compute units, 512)) each leaves one partial gradient in `workspace`, a second launch adds them in workgroup order and
+ * divides by nb_rows: no floating-point atomics, the same inputs and the same max_workgroups give the same bits on every call.
+ * Every float of `grad`, `loss` and `ratio` is written by every successful call; nb_rows == 0 writes zeros to `grad` and `loss`.
+ * Stream-ordered, never synchronises, allocates nothing; `workspace`: 16-byte aligned device memory of
+ * mdr_mlp_grad_workspace_bytes, owned by the caller, its contents free before and after the call.
+ * Returns 0; -1 (a NULL required pointer, ld_state < F, nb_rows < 0, max_workgroups < 0, clip_param outside [0, 1), a struct_size
+ * that is not this header's, a missing or misaligned workspace); -3 (HIP error); -4 (a shape outside the limits, num_out != 2).  On
+ * -1 and -4 nothing was launched and nothing written. */
+int mdr_ppo_actor_grad(const mdr_mlp_t *actor, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                       const int64_t *action, const float *old_prob, const float *advantage, float clip_param,
+                       int32_t max_workgroups, void *workspace, float *grad, float *loss, float *ratio, void *stream);
+
+/* The value loss of agents/ppo.py:149-150, 173: V_i = critic(state_j), loss = (1 / nb_rows) sum_i (target_j - V_i)^2 (F.mse_loss),
+ * `target` a whole-buffer array read through `index`.  `value` (may be NULL): V_i; `advantage` (may be NULL): target_j - V_i, the
+ * detached delta mdr_ppo_actor_grad takes; both float [nb_rows] in minibatch order.  Everything else - rows, `grad`, `loss`,
+ * workspace, grid, determinism, return codes (-4: num_out != 1) - as mdr_ppo_actor_grad. */
+int mdr_ppo_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                        const float *target, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
+                        float *advantage, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

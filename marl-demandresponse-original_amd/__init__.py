@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("BatchedDemandResponseEnv", "OBS_COLUMNS"):
         from . import batched_env
         return getattr(batched_env, name)
-    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
+    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "BatchedMetrics":
@@ -22,6 +22,9 @@ def __getattr__(name):
     if name in ("TarMACActor", "TarMACCritic", "FusedTarMACActor"):
         from . import tarmac
         return getattr(tarmac, name)
+    if name == "PPOLearner":
+        from .ppo import PPOLearner
+        return PPOLearner
     if name == "MADemandResponseEnv":
         from .env import MADemandResponseEnv
         return MADemandResponseEnv

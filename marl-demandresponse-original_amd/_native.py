@@ -132,6 +132,13 @@ class MdrMailbox(C.Structure):
     ]
 
 
+class MdrMlp(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("num_state", C.c_int32), ("hidden1", C.c_int32), ("hidden2", C.c_int32), ("num_out", C.c_int32),
+        ("w1", _f32p), ("b1", _f32p), ("w2", _f32p), ("b2", _f32p), ("w3", _f32p), ("b3", _f32p),
+    ]
+
+
 OBS_PLANES, OBS_ROWS = 0, 1
 
 EXPORTS = (
@@ -151,6 +158,7 @@ EXPORTS = (
     "mdr_tarmac_frag_encode_floats", "mdr_tarmac_frag_proj_floats", "mdr_tarmac_frag_msg_floats", "mdr_tarmac_frag_head_floats",
     "mdr_tarmac_vec_floats", "mdr_tarmac_frag_words", "mdr_tarmac_actor_workspace_bytes", "mdr_tarmac_actor_sample",
     "mdr_env_tarmac_actor_sample",
+    "mdr_mlp_grad_floats", "mdr_mlp_grad_workspace_bytes", "mdr_ppo_actor_grad", "mdr_ppo_critic_grad",
 )
 
 _lib = None
@@ -242,6 +250,10 @@ def load():
         "mdr_tarmac_actor_workspace_bytes": (i64, [vp, i64]),
         "mdr_tarmac_actor_sample": (C.c_int, [vp, vp, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp]),
         "mdr_env_tarmac_actor_sample": (C.c_int, [vp, C.POINTER(MdrObsSpec), vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "mdr_mlp_grad_floats": (i64, [C.POINTER(MdrMlp)]),
+        "mdr_mlp_grad_workspace_bytes": (i64, [C.POINTER(MdrMlp), i64, i32]),
+        "mdr_ppo_actor_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp]),
+        "mdr_ppo_critic_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
         "mdr_env_pack": (C.c_int, [vp, i32, vp, vp]),
         "mdr_env_graph_room": (i64, [vp]),
         "mdr_env_graph_replayed": (C.c_int, [vp, i64, vp]),

@@ -1,0 +1,498 @@
+// PPO's update step for the MLP actor and critic (include/mdr_policy.h: mdr_mlp_t, mdr_ppo_actor_grad, mdr_ppo_critic_grad).
+//
+// Reference: PPO.update (agents/ppo.py:139-188) evaluates, per minibatch, Actor / Critic (agents/network.py:14-57: Linear(F,H1) - ReLU -
+// Linear(H1,H2) - ReLU - Linear(H2,O)), forms the clipped surrogate (ppo.py:157-166) or F.mse_loss(Gt, V) (ppo.py:173) and calls
+// backward().  Here one launch does forward, loss and backward of one network for a minibatch and leaves the loss and the flat gradient
+// dW1 | db1 | dW2 | db2 | dW3 | db3 in torch's [out][in] layout; a second small launch sums the workgroups' partials in one fixed order
+// and scales by 1 / B.  No floating-point atomics: the same inputs and the same grid give the same bits.
+//
+// Exact fp32 on v_mfma_f32_16x16x4_f32 (A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15], C/D: col = l & 15, row = 4 (l >> 4) +
+// reg).  At 32 cycles per instruction and SIMD the matrix pipe leaves room for two LDS operand reads per MFMA, so every operand comes
+// from LDS and the work of a tile of 16 minibatch rows is split over the 8 waves of a persistent workgroup by 16-unit OUTPUT block:
+// wave w owns block w of both hidden layers (H <= 128: at most 8 blocks) through the whole launch.
+//
+//   stage    W1 [H1p][ld1], W2 [H2p][ld2] in torch's layout, zero-padded to whole blocks, ld = 4 (mod 32): the 64 lanes of an A read
+//            (W[16 w + m][4 q + g], forward) fall two on each bank; the transposed read of the backward (W2[4 q + g][16 w + m]) at
+//            most four.  Biases and W3 behind them.  Once per workgroup.
+//   x        the tile's state rows, gathered through `index`, transposed into xT [feature][row] (row stride LT = 20: the reads
+//            [16 b + n][4 s + g] of the weight-gradient products fall two on each bank, the forward's [4 q + g][r] at most three)
+//   F1       z1 block w = b1 + W1 x (units on the MFMA row index, the tile's rows on the column index)      -> h1T = relu(z1)
+//   F2       z2 block w = b2 + W2 h1                                                                       -> h2T
+//            and the block's share of the O logits from the same registers (four fmas per lane, two shuffles)      -> lp
+//   head     every wave: the logits of the 16 rows = the blocks' shares in block order + b3, the loss term and dlogits of its
+//            row on the vector unit; dz2 block w = relu'(z2) (dlogits . W3)                                -> dz2T
+//            and, from the block it has just written: dW2 rows of block w += dz2^T h1 (k = the tile's rows), db2 (the same
+//            product against ones), dW3 / db3 columns of block w on the vector unit
+//   B2       dh1 block w = W2^T dz2 (A = W2 read transposed), dz1 = relu'(z1) dh1                           -> dz1T
+//            and dW1 rows of block w += dz1^T x, db1
+// Five barriers per tile.  The accumulators of the three weight gradients stay in registers for the whole launch (dW2 8 blocks, dW1
+// 4 blocks, two bias blocks, one head register: 57 registers); each workgroup writes its partial once.  relu'(z) = 1 iff z > 0.
+// Rows past the minibatch are forwarded as zero states and given zero dlogits: they add exact zeros.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/mdr.h"
+#include "../../include/mdr_policy.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int NW = 8;                 // waves per workgroup = the most 16-unit blocks of a hidden layer
+constexpr int TILE = 16;              // minibatch rows per tile
+constexpr int LT = 20;                // row stride of the transposed tile images
+constexpr int MAX_F = 64, MAX_H = 128;
+constexpr int LIB_MAX_WG = 512;       // the library's own grid: min(tiles, CUs, this)
+constexpr size_t LDS_LIMIT = 160 * 1024;
+
+__host__ __device__ inline int blocks16(int n) { return (n + 15) / 16; }
+// smallest stride >= n that is 4 (mod 32)
+__host__ __device__ inline int ld_for(int n) { return ((n + 27) / 32) * 32 + 4; }
+
+struct Shape {
+  int F, H1, H2, O;
+  int nbf, nb1, nb2;            // 16-blocks of F, H1, H2
+  int ld1, ld2;
+  int oW1, ob1, oW2, ob2, oW3, ob3, G;      // offsets into the flat gradient; G floats
+  int stride;                   // floats per workgroup partial: G + 1 (the loss), rounded up to 4
+  // LDS offsets (floats)
+  int sW1, sW2, sb1, sb2, sW3, sb3, sx, sh1, sh2, sdz2, sdz1, sdl, slp, lds;
+};
+
+__host__ __device__ inline Shape make_shape(int F, int H1, int H2, int O) {
+  Shape s;
+  s.F = F, s.H1 = H1, s.H2 = H2, s.O = O;
+  s.nbf = blocks16(F), s.nb1 = blocks16(H1), s.nb2 = blocks16(H2);
+  s.ld1 = ld_for(4 * ((F + 3) / 4)), s.ld2 = ld_for(16 * s.nb1);
+  s.oW1 = 0, s.ob1 = H1 * F, s.oW2 = s.ob1 + H1, s.ob2 = s.oW2 + H2 * H1, s.oW3 = s.ob2 + H2, s.ob3 = s.oW3 + O * H2, s.G = s.ob3 + O;
+  s.stride = (s.G + 1 + 3) & ~3;
+  const int H1p = 16 * s.nb1, H2p = 16 * s.nb2;
+  s.sW1 = 0;
+  s.sW2 = s.sW1 + H1p * s.ld1;
+  s.sb1 = s.sW2 + H2p * s.ld2;
+  s.sb2 = s.sb1 + H1p;
+  s.sW3 = s.sb2 + H2p;
+  s.sb3 = s.sW3 + 2 * H2p;
+  s.sx = s.sb3 + 4;
+  s.sh1 = s.sx + 16 * s.nbf * LT;
+  s.sh2 = s.sh1 + H1p * LT;
+  s.sdz2 = s.sh2 + H2p * LT;
+  s.sdz1 = s.sdz2 + H2p * LT;
+  s.sdl = s.sdz1 + H1p * LT;
+  s.slp = s.sdl + NW * TILE * 2;
+  s.lds = s.slp + NW * TILE * 2;
+  return s;
+}
+
+struct GradArgs {
+  Shape s;
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+  const float* state;
+  int64_t ld_state;
+  const int64_t* index;
+  int64_t B, ntiles;
+  const int64_t* action;      // actor
+  const float* old_prob;      // actor
+  const float* adv_in;        // actor, minibatch order
+  const float* target;        // critic
+  float clip_lo, clip_hi;
+  float* part;                // [gridDim.x][stride]
+  float* out0;                // actor: ratio; critic: value           (minibatch order, may be null)
+  float* out1;                // critic: advantage                     (may be null)
+};
+
+__device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
+
+// dst [rows_p][ld] <- src [rows][cols] (torch layout), zeros in the padding
+__device__ __forceinline__ void stage_matrix(float* dst, const float* src, int rows, int cols, int rows_p, int ld, int tid) {
+  for (int i = tid; i < rows_p * ld; i += 64 * NW) {
+    const int r = i / ld, c = i - r * ld;
+    dst[i] = (r < rows && c < cols) ? src[(int64_t)r * cols + c] : 0.0f;
+  }
+}
+
+template <bool ACTOR>
+__global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Shape& s = a.s;
+  constexpr int O = ACTOR ? 2 : 1;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
+  const int nb1 = s.nb1, nb2 = s.nb2, nbf = s.nbf;
+  const int H1p = 16 * nb1, H2p = 16 * nb2, Fp = 16 * nbf;
+  float* W1s = lds + s.sW1;
+  float* W2s = lds + s.sW2;
+  float* b1s = lds + s.sb1;
+  float* b2s = lds + s.sb2;
+  float* W3s = lds + s.sW3;      // [2][H2p]
+  float* b3s = lds + s.sb3;
+  float* xT = lds + s.sx;
+  float* h1T = lds + s.sh1;
+  float* h2T = lds + s.sh2;
+  float* dz2T = lds + s.sdz2;
+  float* dz1T = lds + s.sdz1;
+  float* dl = lds + s.sdl + w * (TILE * 2);      // the wave's own copy of the tile's dlogits [row][2]
+  float* lp = lds + s.slp;                       // [wave][row][2]: the logits' partial sums over the wave's block of h2
+
+  stage_matrix(W1s, a.w1, s.H1, s.F, H1p, s.ld1, tid);
+  stage_matrix(W2s, a.w2, s.H2, s.H1, H2p, s.ld2, tid);
+  for (int i = tid; i < H1p; i += 64 * NW) b1s[i] = i < s.H1 ? a.b1[i] : 0.0f;
+  for (int i = tid; i < H2p; i += 64 * NW) b2s[i] = i < s.H2 ? a.b2[i] : 0.0f;
+  for (int i = tid; i < 2 * H2p; i += 64 * NW) {
+    const int o = i / H2p, u = i - o * H2p;
+    W3s[i] = (o < O && u < s.H2) ? a.w3[o * s.H2 + u] : 0.0f;
+  }
+  if (tid < 4) b3s[tid] = tid < O ? a.b3[tid] : 0.0f;
+
+  // the tile's states: element e = tid + 512 i of the [row][Fp] image, two per thread at most (16 x 64 / 512)
+  float xn[2];
+  auto load_x = [&](int64_t t) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int e = tid + 64 * NW * i;
+      const int r = e / Fp, f = e - r * Fp;
+      const int64_t row = t * TILE + r;
+      xn[i] = 0.0f;
+      if (r < TILE && f < s.F && row < a.B) {
+        const int64_t j = a.index ? a.index[row] : row;
+        xn[i] = a.state[j * a.ld_state + f];
+      }
+    }
+  };
+  auto store_x = [&]() {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int e = tid + 64 * NW * i;
+      const int r = e / Fp, f = e - r * Fp;
+      if (r < TILE) xT[f * LT + r] = xn[i];
+    }
+  };
+
+  f32x4 dW2[NW], dW1[MAX_F / 16], db2 = {0, 0, 0, 0}, db1 = {0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < NW; ++i) dW2[i] = f32x4{0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < MAX_F / 16; ++i) dW1[i] = f32x4{0, 0, 0, 0};
+  float acc3 = 0.0f;      // lane (g < O, c): dW3[g][16 w + c];  lane (g == 2, c < O): db3[c]
+  float loss = 0.0f;      // wave 0, lanes g == 0: the terms of the rows = c (mod 16) of this workgroup's tiles
+
+  const int64_t first = blockIdx.x;
+  if (first < a.ntiles) load_x(first);
+  else xn[0] = xn[1] = 0.0f;
+  store_x();
+  __syncthreads();
+
+  for (int64_t t = first; t < a.ntiles; t += gridDim.x) {
+    const bool more = t + gridDim.x < a.ntiles;
+    if (more) load_x(t + gridDim.x);      // lands during the tile's matrix work
+    const int64_t row = t * TILE + c;
+    const bool valid = row < a.B;
+
+    // ---- F1
+    f32x4 z1 = {0, 0, 0, 0};
+    if (w < nb1) {
+      z1 = *reinterpret_cast<const f32x4*>(b1s + 16 * w + 4 * g);
+      const float* wa = W1s + (16 * w + c) * s.ld1 + g;
+      const float* xb = xT + g * LT + c;
+      const int ks = (s.F + 3) >> 2;
+      f32x4 odd = {0, 0, 0, 0};      // two chains (even / odd k-steps): 40 cycles of dependent latency against 32 of issue; measured no gain at two waves per SIMD
+      for (int q0 = 0; q0 < ks; q0 += 4) {      // four k-steps' operands in flight
+#pragma unroll
+        for (int q = q0; q < q0 + 4; q += 2) {
+          if (q < ks) z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[4 * q], xb[4 * q * LT], z1, 0, 0, 0);
+          if (q + 1 < ks) odd = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[4 * q + 4], xb[(4 * q + 4) * LT], odd, 0, 0, 0);
+        }
+      }
+      z1 += odd;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) h1T[(16 * w + 4 * g + i) * LT + c] = fmaxf(z1[i], 0.0f);
+    }
+    __syncthreads();
+
+    // ---- F2
+    f32x4 z2 = {0, 0, 0, 0};
+    if (w < nb2) {
+      z2 = *reinterpret_cast<const f32x4*>(b2s + 16 * w + 4 * g);
+      const float* wa = W2s + (16 * w + c) * s.ld2 + g;
+      const float* hb = h1T + g * LT + c;
+      const int ks = 4 * nb1;
+      f32x4 odd = {0, 0, 0, 0};
+      for (int q0 = 0; q0 < ks; q0 += 4) {
+#pragma unroll
+        for (int q = q0; q < q0 + 4; q += 2) {
+          z2 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[4 * q], hb[4 * q * LT], z2, 0, 0, 0);
+          odd = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[4 * q + 4], hb[(4 * q + 4) * LT], odd, 0, 0, 0);
+        }
+      }
+      z2 += odd;
+      // the block's share of the logits from the lane's own registers: four units per lane, the four lane groups by two shuffles
+      const f32x4 w30 = *reinterpret_cast<const f32x4*>(W3s + 16 * w + 4 * g);
+      const f32x4 w31 = *reinterpret_cast<const f32x4*>(W3s + H2p + 16 * w + 4 * g);
+      float p0 = 0.0f, p1 = 0.0f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float h = fmaxf(z2[i], 0.0f);
+        h2T[(16 * w + 4 * g + i) * LT + c] = h;
+        p0 = fmaf(w30[i], h, p0);
+        if (ACTOR) p1 = fmaf(w31[i], h, p1);
+      }
+      p0 += __shfl_xor(p0, 16);
+      p0 += __shfl_xor(p0, 32);
+      if (ACTOR) {
+        p1 += __shfl_xor(p1, 16);
+        p1 += __shfl_xor(p1, 32);
+      }
+      if (g == 0) {
+        lp[(w * TILE + c) * 2] = p0;
+        lp[(w * TILE + c) * 2 + 1] = p1;
+      }
+    }
+    __syncthreads();
+
+    // ---- head: logits of row c, every wave for itself (the same bits in all of them)
+    float l0 = 0.0f, l1 = 0.0f;
+#pragma unroll
+    for (int b = 0; b < NW; ++b)      // the blocks' partial sums in block order
+      if (b < nb2) {
+        l0 += lp[(b * TILE + c) * 2];
+        if (ACTOR) l1 += lp[(b * TILE + c) * 2 + 1];
+      }
+    l0 += b3s[0];
+    if (ACTOR) l1 += b3s[1];
+    float d0 = 0.0f, d1 = 0.0f, term = 0.0f;      // dlogits (before the 1 / B of the reduction) and the row's loss term
+    if (valid) {
+      const int64_t j = a.index ? a.index[row] : row;
+      if (ACTOR) {
+        // agents/ppo.py:153-166: ratio = pi(a) / old_prob, L = -min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A); torch passes the
+        // gradient through min to the first argument unless the second is smaller, and through clamp inside the closed range
+        const bool act = a.action[j] != 0;
+        const float d = act ? l1 - l0 : l0 - l1;
+        const float pa = 1.0f / (1.0f + expf(-d)), pb = 1.0f / (1.0f + expf(d));
+        const float ratio = pa / a.old_prob[j];
+        const float adv = a.adv_in[row];
+        const float s1 = ratio * adv, s2 = fminf(fmaxf(ratio, a.clip_lo), a.clip_hi) * adv;
+        term = -fminf(s1, s2);
+        const bool active = (ratio >= a.clip_lo && ratio <= a.clip_hi) || s1 < s2;
+        const float da = active ? (-adv * ratio) * pb : 0.0f;      // d term / d logit[a]; the other logit takes the negative
+        d0 = act ? -da : da;
+        d1 = act ? da : -da;
+        if (w == 0 && g == 0 && a.out0) a.out0[row] = ratio;
+      } else {
+        // agents/ppo.py:149-150, 173: delta = Gt - V, value loss = mean(delta^2)
+        const float adv = a.target[j] - l0;
+        term = adv * adv;
+        d0 = -2.0f * adv;
+        if (w == 0 && g == 0) {
+          if (a.out0) a.out0[row] = l0;
+          if (a.out1) a.out1[row] = adv;
+        }
+      }
+    }
+    if (w == 0 && g == 0) loss += term;
+    if (g == 0) {
+      dl[2 * c] = d0;
+      dl[2 * c + 1] = d1;
+    }
+    if (w < nb2) {
+      const f32x4 w30 = *reinterpret_cast<const f32x4*>(W3s + 16 * w + 4 * g);
+      const f32x4 w31 = *reinterpret_cast<const f32x4*>(W3s + H2p + 16 * w + 4 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float dh = ACTOR ? fmaf(d0, w30[i], d1 * w31[i]) : d0 * w30[i];
+        dz2T[(16 * w + 4 * g + i) * LT + c] = z2[i] > 0.0f ? dh : 0.0f;
+      }
+    }
+    wave_lds_fence();
+    if (w < nb2) {
+      // dW2[16 w + m][16 ib + n] += sum_r dz2[r][16 w + m] h1[r][16 ib + n]
+      const float* da = dz2T + (16 * w + c) * LT + g;
+      const float* hb = h1T + c * LT + g;
+#pragma unroll
+      for (int q = 0; q < TILE / 4; ++q) {
+        const float av = da[4 * q];
+        db2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, 1.0f, db2, 0, 0, 0);
+#pragma unroll
+        for (int ib = 0; ib < NW; ++ib)
+          if (ib < nb1) dW2[ib] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hb[16 * ib * LT + 4 * q], dW2[ib], 0, 0, 0);
+      }
+      // the head's gradient, columns of block w: a chain over the tile's rows
+      if (g < O) {
+        const float* hr = h2T + (16 * w + c) * LT;
+#pragma unroll
+        for (int r = 0; r < TILE; ++r) acc3 = fmaf(dl[2 * r + g], hr[r], acc3);
+      } else if (g == 2 && c < O) {
+#pragma unroll
+        for (int r = 0; r < TILE; ++r) acc3 += dl[2 * r + c];
+      }
+    }
+    __syncthreads();
+
+    // ---- B2
+    if (w < nb1) {
+      f32x4 dh = {0, 0, 0, 0};
+      const float* wa = W2s + g * s.ld2 + 16 * w + c;
+      const float* db = dz2T + g * LT + c;
+      const int ks = 4 * nb2;
+      f32x4 odd = {0, 0, 0, 0};
+      for (int q0 = 0; q0 < ks; q0 += 4) {
+#pragma unroll
+        for (int q = q0; q < q0 + 4; q += 2) {
+          dh = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[4 * q * s.ld2], db[4 * q * LT], dh, 0, 0, 0);
+          odd = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[(4 * q + 4) * s.ld2], db[(4 * q + 4) * LT], odd, 0, 0, 0);
+        }
+      }
+      dh += odd;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) dz1T[(16 * w + 4 * g + i) * LT + c] = z1[i] > 0.0f ? dh[i] : 0.0f;
+      wave_lds_fence();
+      const float* da = dz1T + (16 * w + c) * LT + g;
+      const float* xb = xT + c * LT + g;
+#pragma unroll
+      for (int q = 0; q < TILE / 4; ++q) {
+        const float av = da[4 * q];
+        db1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, 1.0f, db1, 0, 0, 0);
+#pragma unroll
+        for (int ib = 0; ib < MAX_F / 16; ++ib)
+          if (ib < nbf) dW1[ib] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xb[16 * ib * LT + 4 * q], dW1[ib], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+    if (more) {
+      store_x();
+      __syncthreads();
+    }
+  }
+
+  // ---- the workgroup's partial: every float of [0, G] exactly once
+  float* part = a.part + (int64_t)blockIdx.x * s.stride;
+  if (w < nb1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int u = 16 * w + 4 * g + i;
+      if (u < s.H1) {
+#pragma unroll
+        for (int ib = 0; ib < MAX_F / 16; ++ib)
+          if (ib < nbf && 16 * ib + c < s.F) part[s.oW1 + u * s.F + 16 * ib + c] = dW1[ib][i];
+        if (c == 0) part[s.ob1 + u] = db1[i];
+      }
+    }
+  }
+  if (w < nb2) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int u = 16 * w + 4 * g + i;
+      if (u < s.H2) {
+#pragma unroll
+        for (int ib = 0; ib < NW; ++ib)
+          if (ib < nb1 && 16 * ib + c < s.H1) part[s.oW2 + u * s.H1 + 16 * ib + c] = dW2[ib][i];
+        if (c == 0) part[s.ob2 + u] = db2[i];
+      }
+    }
+    if (g < O && 16 * w + c < s.H2) part[s.oW3 + g * s.H2 + 16 * w + c] = acc3;
+  }
+  if (w == 0) {
+    if (g == 2 && c < O) part[s.ob3 + c] = acc3;
+    // the loss: the 16 lanes' sums in lane order
+    if (g == 0) dl[c] = loss;
+    wave_lds_fence();
+    if (lane == 0) {
+      float sum = 0.0f;
+      for (int i = 0; i < TILE; ++i) sum += dl[i];
+      part[s.G] = sum;
+    }
+  }
+}
+
+// grad[i] = (sum over the partials in workgroup order) / B, the loss behind it; no partials (B == 0): zeros
+__global__ void k_ppo_grad_reduce(const float* part, int nparts, int stride, int G, float denom, float* grad, float* loss) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > G) return;
+  float sum = 0.0f;
+  for (int p = 0; p < nparts; ++p) sum += part[(int64_t)p * stride + i];
+  const float v = nparts > 0 ? sum / denom : 0.0f;
+  if (i < G) grad[i] = v;
+  else *loss = v;
+}
+
+bool net_fields_ok(const mdr_mlp_t* n) {
+  return n && n->struct_size == sizeof(mdr_mlp_t) && n->num_state > 0 && n->hidden1 > 0 && n->hidden2 > 0 && n->num_out > 0;
+}
+bool net_covered(const mdr_mlp_t* n) {
+  return n->num_state <= MAX_F && n->hidden1 <= MAX_H && n->hidden2 <= MAX_H && (n->num_out == 1 || n->num_out == 2);
+}
+
+int64_t grid_for(int64_t nb_rows, int32_t max_workgroups, int cus) {
+  const int64_t ntiles = (nb_rows + TILE - 1) / TILE;
+  int64_t cap = max_workgroups > 0 ? max_workgroups : (cus < LIB_MAX_WG ? cus : LIB_MAX_WG);
+  const int64_t grid = ntiles < cap ? ntiles : cap;
+  return grid > 0 ? grid : 1;
+}
+
+int run(bool is_actor, const mdr_mlp_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+        const int64_t* action, const float* old_prob, const float* adv_in, const float* target, float clip, int32_t max_workgroups,
+        void* workspace, float* grad, float* loss, float* out0, float* out1, void* stream) {
+  if (!net_fields_ok(net) || !state || !grad || !loss || !workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
+  if (!net->w1 || !net->b1 || !net->w2 || !net->b2 || !net->w3 || !net->b3) return MDR_ERR_INVALID;
+  if (is_actor ? (!action || !old_prob || !adv_in || !(clip >= 0.0f && clip < 1.0f)) : !target) return MDR_ERR_INVALID;
+  if (nb_rows < 0 || ld_state < net->num_state || max_workgroups < 0) return MDR_ERR_INVALID;
+  if (!net_covered(net) || net->num_out != (is_actor ? 2 : 1)) return MDR_ERR_UNSUPPORTED;
+  GradArgs a{};
+  a.s = make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out);
+  const size_t lds_bytes = (size_t)a.s.lds * sizeof(float);
+  if (lds_bytes > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  int grid = 0;
+  if (nb_rows > 0) {
+    int dev = 0, cus = 256;
+    if (max_workgroups == 0 &&
+        (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess))
+      cus = 256;
+    grid = (int)grid_for(nb_rows, max_workgroups, cus);
+    a.w1 = net->w1, a.b1 = net->b1, a.w2 = net->w2, a.b2 = net->b2, a.w3 = net->w3, a.b3 = net->b3;
+    a.state = state, a.ld_state = ld_state, a.index = index, a.B = nb_rows, a.ntiles = (nb_rows + TILE - 1) / TILE;
+    a.action = action, a.old_prob = old_prob, a.adv_in = adv_in, a.target = target;
+    a.clip_lo = (float)(1.0 - (double)clip), a.clip_hi = (float)(1.0 + (double)clip);
+    a.part = static_cast<float*>(workspace), a.out0 = out0, a.out1 = out1;
+    auto kernel = is_actor ? k_ppo_grad<true> : k_ppo_grad<false>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+      return MDR_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * NW), lds_bytes, st, a);
+    if (hipGetLastError() != hipSuccess) return MDR_ERR_HIP;
+  }
+  const int n = a.s.G + 1;
+  hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), grid,
+                     a.s.stride, a.s.G, (float)nb_rows, grad, loss);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mdr_mlp_grad_floats(const mdr_mlp_t* net) {
+  if (!net_fields_ok(net) || !net_covered(net)) return -1;
+  return make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out).G;
+}
+
+int64_t mdr_mlp_grad_workspace_bytes(const mdr_mlp_t* net, int64_t nb_rows, int32_t max_workgroups) {
+  if (!net_fields_ok(net) || !net_covered(net) || nb_rows < 0 || max_workgroups < 0) return -1;
+  const Shape s = make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out);
+  // max_workgroups == 0: room for the library's grid on any device (no device call here)
+  return grid_for(nb_rows, max_workgroups, LIB_MAX_WG) * s.stride * (int64_t)sizeof(float);
+}
+
+int mdr_ppo_actor_grad(const mdr_mlp_t* actor, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                       const int64_t* action, const float* old_prob, const float* advantage, float clip_param, int32_t max_workgroups,
+                       void* workspace, float* grad, float* loss, float* ratio, void* stream) {
+  return run(true, actor, state, ld_state, index, nb_rows, action, old_prob, advantage, nullptr, clip_param, max_workgroups, workspace, grad,
+             loss, ratio, nullptr, stream);
+}
+
+int mdr_ppo_critic_grad(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                        const float* target, int32_t max_workgroups, void* workspace, float* grad, float* loss, float* value,
+                        float* advantage, void* stream) {
+  return run(false, critic, state, ld_state, index, nb_rows, nullptr, nullptr, nullptr, target, 0.0f, max_workgroups, workspace, grad, loss,
+             value, advantage, stream);
+}
+
+}  // extern "C"
