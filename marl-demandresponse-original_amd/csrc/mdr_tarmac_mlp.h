@@ -1,6 +1,7 @@
 // What the TarMAC actor's matrix-core kernels share between the exact-fp32 forms (mdr_tarmac_mlp.hip) and the bf16x3 forms
-// (mdr_tarmac_mlp_bf16.hip): the limits, the layout of mdr_tarmac_actor_t.vec, the kernel arguments, the activations, the LDS staging
-// and the persistent-grid launch.
+// (mdr_tarmac_mlp_bf16.hip): the limits, the layout of mdr_tarmac_actor_t.vec, the kernel arguments, the activations, the kernels'
+// prologue (stage_weights), the head's tail (head_finish), the observe forms' LDS window (ObserveWindow), the fragment sizes, the
+// persistent-grid launch and the launch chain of a sample (run_chain<Forms>).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -98,54 +99,223 @@ __device__ __forceinline__ float activate(float x) {
 }
 
 __device__ __forceinline__ void stage(float* dst, const float* src, int n, int tid) {
-  const int stride = (int)blockDim.x * 4;      // n a multiple of 4, both 16-byte aligned
+  // n a multiple of 4, both 16-byte aligned.  The builtin, not blockDim.x: read inside a helper of a helper, the library call behind
+  // blockDim is no longer folded to the uniform workgroup size and the stride ends up in a vector register
+  const int stride = (int)__builtin_amdgcn_workgroup_size_x() * 4;
   for (int i = tid * 4; i < n; i += stride) *reinterpret_cast<float4*>(dst + i) = *reinterpret_cast<const float4*>(src + i);
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-template <typename K>
-int launch(K kernel, int waves, const MlpArgs& a, int lds_floats, int cus, hipStream_t s) {
-  const size_t lds_bytes = (size_t)lds_floats * sizeof(float);
+// ---- what every kernel opens with: the staged weights in LDS, fa | fp | vec, and which tiles the wavefront takes.  The helpers take
+// what they need of MlpArgs as values the kernel has read: handed the argument block by reference, the kernel's registers move.
+struct Fragments {      // fp == nullptr: no frag_proj in LDS (head)
+  const float *fa, *fp, *vec;
+  int na, np, nvec;
+};
+
+struct Staged {
+  float *fa, *fp, *vec;
+  int lane0, r;
+  int64_t wave, nwaves;
+};
+
+struct NoHooks {      // of a kernel or feature source with nothing to do there: no windows before the barrier, no staging between layers
+  __device__ __forceinline__ void operator()() const {}
+  __device__ __forceinline__ void carve(float*, int) {}
+  __device__ __forceinline__ void prime(int64_t, int64_t) {}
+  __device__ __forceinline__ void after_layer1() {}
+  __device__ __forceinline__ void end() {}
+};
+
+// `nw` waves per workgroup; `before_sync()`: what else a kernel leaves in LDS before the barrier (the observe forms' windows)
+template <class F = NoHooks>
+__device__ __forceinline__ Staged stage_weights(float* lds, const Fragments w, bool stage_fp, int nw, F&& before_sync = F{}) {
+  Staged S;
+  S.fa = lds;
+  S.fp = S.fa + w.na;
+  S.vec = S.fp + w.np;
+  const int tid = threadIdx.x;
+  S.lane0 = tid & 63, S.r = S.lane0 & 15;
+  S.wave = (int64_t)blockIdx.x * nw + (tid >> 6), S.nwaves = (int64_t)gridDim.x * nw;      // read ahead of the barrier, not behind it
+  stage(S.fa, w.fa, w.na, tid);
+  if (stage_fp) stage(S.fp, w.fp, w.np, tid);
+  stage(S.vec, w.vec, w.nvec, tid);
+  before_sync();
+  __syncthreads();
+  return S;
+}
+
+// ---- the head's tail, on the accumulators acc of comm_hidden2action's first layer that lane group g holds for `agent`: the last
+// layer as one dot product with W3[0] - W3[1], the two-logit softmax, the action draw of mdr_logits_sample (mdr_draw.h), the writes
+struct DrawArgs {
+  uint8_t* action;
+  float *a_prob, *probs;
+  int greedy;
+  uint32_t k0, k1, step_lo, step_hi;
+  const int32_t* step_dev;
+};
+
+template <int MBH, bool EXACT>
+__device__ __forceinline__ void head_finish(const f32x4 (&acc)[MBH], const float* vec, const VecLayout& L, int mbh, int g, float bias3,
+                                            const DrawArgs a, int64_t agent, bool valid) {
+  float d = 0.0f;
+#pragma unroll
+  for (int mb = 0; mb < MBH; ++mb)
+    if (EXACT || mb < mbh) {
+      const f32x4 w = *reinterpret_cast<const f32x4*>(vec + L.wd + 16 * mb + 4 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) d = fmaf(w[i], relu(acc[mb][i]), d);
+    }
+  d += __shfl_xor(d, 16);
+  d += __shfl_xor(d, 32);
+  d += bias3;
+  const float p0 = 1.0f / (1.0f + expf(-d));      // mdr_logits_sample's softmax over two logits
+  const float p1 = 1.0f / (1.0f + expf(d));
+  if (g == 0 && valid) {
+    int act;
+    if (a.greedy) {
+      act = d >= 0.0f ? 0 : 1;      // argmax keeps the first maximum, as torch.argmax
+    } else {
+      const float u = action_uniform(mdr::action_word(agent, a.step_lo, a.step_hi, a.step_dev, a.k0, a.k1));
+      act = u < p0 ? 0 : 1;
+    }
+    a.action[agent] = (uint8_t)act;
+    if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
+    if (a.probs) {
+      a.probs[agent * 2] = p0;
+      a.probs[agent * 2 + 1] = p1;
+    }
+  }
+}
+
+// ---- what the observe source of an encode kernel takes beside MlpArgs, as a second kernel argument (the rows source: none)
+struct WindowArgs {
+  mdr::ObserveArgs o;
+  float* rows_out;
+};
+
+// ---- observe -> act (mdr_env_tarmac_actor_sample): the encode kernels' forms that build their features in LDS (mdr_observe.h)
+constexpr int TARMAC_OBS_ROW = 60;      // floats per staged row (ObserveSource, mdr_tarmac_mlp.hip, says why)
+constexpr size_t LDS_PER_CU = 160 * 1024;
+
+// The window of one wavefront behind the staged weights: TILE consecutive agents' rows, staged from the env's compact state by the
+// helpers of mdr_observe.h exactly as k_actor_observe16 / k_actor_observe_bf16 (mdr_policy.hip) stage theirs for the default
+// observation, and what the two precisions do with it alike.  GEN: tiles that may leave their env (N no multiple of TILE).  STORE:
+// the rows are also written to rows_out through the workgroup's offset table.
+template <int TILE, bool STORE, bool GEN>
+struct ObserveWindow {
+  static constexpr int ROW = TARMAC_OBS_ROW, WIN = TILE * ROW;
+  const mdr::ObserveArgs& o;
+  float* rows_out;
+  int64_t A, ntiles;
+  float* rows;
+  uint16_t* table;      // [TILE * 51] (only when rows are stored)
+  const double* sig_row;
+  int lane0;
+  TileCursor tc;
+  SegSlot slot;
+  HouseRegs nxt;
+  int64_t next_tile, stride;      // the wavefront's tile after this one
+  bool more;                      // ... is there
+
+  // normStateDict feature n of a tile row sits at this float of the row
+  static __device__ __forceinline__ int at(int n) { return n < 11 ? 4 * OBS_C + n : n - 11; }
+
+  // before the workgroup's barrier: `nw` = as many of the form's waves as the windows leave room for
+  __device__ __forceinline__ void carve(float* behind_weights, int nw) {
+    const int tid = threadIdx.x;
+    rows = behind_weights + (tid >> 6) * WIN;
+    table = reinterpret_cast<uint16_t*>(behind_weights + nw * WIN);
+    lane0 = tid & 63;
+    for (int i = lane0; i < WIN; i += 64) rows[i] = 0.0f;
+    if (STORE) observe_build_table<TILE, ROW>(table, tid, 64 * nw);
+  }
+  __device__ __forceinline__ void start(int64_t wave, int64_t nwaves) {
+    sig_row = observe_sig_row(o);
+    tc.init(wave * TILE, nwaves * TILE, o.N);
+    slot = SegSlot{};
+    stride = nwaves;
+  }
+  __device__ __forceinline__ void advance(int64_t t) {
+    next_tile = t + stride;
+    more = next_tile < ntiles;
+    tc.next();
+    nxt = HouseRegs{};
+  }
+  // the compact state of the tile at the cursor, which starts at first_agent, into registers / from them into the window
+  __device__ __forceinline__ void load(int64_t first_agent) {
+    nxt = GEN ? observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, first_agent, A, lane0, slot) : observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
+  }
+  __device__ __forceinline__ void stage_rows() {
+    if (GEN) observe_stage_gen<false, ROW>(o, nxt, slot, rows);
+    else observe_stage<TILE, false, ROW>(o, nxt, rows, lane0);
+  }
+  // the senders' seconds_since_off become quotients by the RECEIVER's lockout, in place: lane group g takes the messages g, g + 4
+  // and g + 8 of tile row `r` (k_actor_observe16)
+  __device__ __forceinline__ void lockout_quotients(int r, int g) {
+    float* row = rows + r * ROW;
+    const float lock = row[4 * OBS_C + 11], y = row[4 * OBS_C + 12];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int m = g + 4 * i;
+      if (m < OBS_C) row[4 * m + 1] = mdr::div_by_lockout(row[4 * m + 1], lock, y);
+    }
+  }
+  __device__ __forceinline__ void store_rows(int64_t first_agent) {
+    if (STORE)
+      observe_store_rows<TILE>(rows, table, rows_out + first_agent * 51, lane0,
+                               GEN ? (int)((A - first_agent) < (int64_t)TILE ? (A - first_agent) : (int64_t)TILE) : TILE);
+  }
+};
+
+// ---- host: the launches.  Each kernel is a persistent grid: the weights are staged once per workgroup
+template <typename K, typename... Extra>
+int launch(K kernel, int waves, size_t lds_bytes, const MlpArgs& a, int cus, hipStream_t s, const Extra&... extra) {
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
     return MDR_ERR_HIP;
   const int64_t want = (a.ntiles + waves - 1) / waves;
-  const unsigned grid = (unsigned)(want < cus ? want : cus);      // persistent: the weights are staged once per workgroup
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds_bytes, s, a);
+  const unsigned grid = (unsigned)(want < cus ? want : cus);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds_bytes, s, a, extra...);
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
-// ---- observe -> act (mdr_env_tarmac_actor_sample): the encode kernels' forms that build their features in LDS (mdr_observe.h)
-constexpr int TARMAC_OBS_ROW = 60;      // floats per staged row (k_tarmac_encode_obs says why)
-constexpr size_t LDS_PER_CU = 160 * 1024;
+inline size_t weights_bytes(const MlpArgs& a, bool proj) { return (size_t)(a.na + (proj ? a.np : 0) + a.nvec) * sizeof(float); }
 
 // LDS: the staged weights, then one window of `tile` rows per wave and, with rows_out, the row table of observe_store_rows.  A form
 // whose windows do not fit beside its weights runs with fewer waves per workgroup, whole waves per SIMD.
 template <typename K>
 int launch_observe(K kernel, int waves, int tile, const MlpArgs& a, const mdr::ObserveArgs& o, float* rows_out, int cus, hipStream_t s) {
-  const size_t fixed = (size_t)(a.na + a.np + a.nvec) * sizeof(float) + (rows_out ? (size_t)tile * 51 * sizeof(uint16_t) : 0);
+  const size_t fixed = weights_bytes(a, true) + (rows_out ? (size_t)tile * 51 * sizeof(uint16_t) : 0);
   const size_t window = (size_t)tile * TARMAC_OBS_ROW * sizeof(float);
   while (waves > 4 && fixed + waves * window > LDS_PER_CU) waves -= 4;
-  const size_t lds_bytes = fixed + waves * window;
-  if (lds_bytes > LDS_PER_CU) return MDR_ERR_UNSUPPORTED;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-    return MDR_ERR_HIP;
-  const int64_t want = (a.ntiles + waves - 1) / waves;
-  const unsigned grid = (unsigned)(want < cus ? want : cus);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds_bytes, s, a, o, rows_out);
-  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+  if (fixed + waves * window > LDS_PER_CU) return MDR_ERR_UNSUPPORTED;
+  return launch(kernel, waves, fixed + waves * window, a, cus, s, WindowArgs{o, rows_out});
 }
 
-// ---- the bf16x3 fragments (include/mdr_policy.h): 512 4-byte words per (k-step, output block) pair - head and tail, 64 lanes, 8 bf16
+// ---- the fragment sizes (include/mdr_policy.h), in 4-byte words.  fp32: a k-step is 4 inputs, 64 lanes x one float per output block
+struct FragFloats {
+  static int64_t encode(int F, int H) { return ((int64_t)(F + 3) / 4 + 4 * blocks(H)) * 64 * blocks(H); }
+  static int64_t proj(int H, int V) { return (int64_t)4 * blocks(H) * 64 * (3 * blocks(H) + 2 + blocks(V)); }
+  static int64_t msg(int H, int V) { return (int64_t)((V + H) / 4) * 64 * blocks(H + V) + (int64_t)4 * blocks(H + V) * 64 * blocks(H); }
+  static int64_t head(int H, int V, int with_comm) { return (int64_t)((H + (with_comm ? V : 0)) / 4) * 64 * blocks(H); }
+};
+
+// bf16x3: 512 words per (k-step, output block) pair - head and tail, 64 lanes, 8 bf16
 constexpr int PAIR_WORDS = 512;
 __host__ __device__ inline int ksteps_rows(int n) { return (n + 31) / 32; }      // 32 floats of a row per k-step
 __host__ __device__ inline int ksteps_regs(int mbi) { return (mbi + 1) / 2; }     // two blocks of the previous layer per k-step
-inline int64_t encode_words(int F, int H) { return (int64_t)PAIR_WORDS * (ksteps_rows(F) + ksteps_regs(blocks(H))) * blocks(H); }
-inline int64_t proj_words(int H, int V) { return (int64_t)PAIR_WORDS * ksteps_regs(blocks(H)) * (3 * blocks(H) + 2 + blocks(V)); }
-inline int64_t msg_words(int H, int V) {
-  return (int64_t)PAIR_WORDS * ((ksteps_rows(V) + ksteps_rows(H)) * blocks(H + V) + ksteps_regs(blocks(H + V)) * blocks(H));
-}
-inline int64_t head_words(int H, int V, int with_comm) { return (int64_t)PAIR_WORDS * ksteps_rows(H + (with_comm ? V : 0)) * blocks(H); }
+struct FragWords {
+  static int64_t encode(int F, int H) { return (int64_t)PAIR_WORDS * (ksteps_rows(F) + ksteps_regs(blocks(H))) * blocks(H); }
+  static int64_t proj(int H, int V) { return (int64_t)PAIR_WORDS * ksteps_regs(blocks(H)) * (3 * blocks(H) + 2 + blocks(V)); }
+  static int64_t msg(int H, int V) {
+    return (int64_t)PAIR_WORDS * ((ksteps_rows(V) + ksteps_rows(H)) * blocks(H + V) + ksteps_regs(blocks(H + V)) * blocks(H));
+  }
+  static int64_t head(int H, int V, int with_comm) { return (int64_t)PAIR_WORDS * ksteps_rows(H + (with_comm ? V : 0)) * blocks(H); }
+};
+
+using MlpKernel = void (*)(MlpArgs);
+using MlpObserveKernel = void (*)(MlpArgs, WindowArgs);
 
 }  // namespace
 
@@ -163,3 +333,75 @@ inline bool tarmac_observe_covered(const ObserveArgs& o, int num_state, int tile
   return o.N % tile == 0 || observe_window_lanes(o.N, 10, tile) <= 64;
 }
 }  // namespace mdr
+
+namespace {
+
+// The launch chain of a sample, after the argument checks of mdr_tarmac_actor_sample (mdr_tarmac_mlp.hip): 1 + hops + (hops - 1) + 1
+// launches.  `o` == nullptr: from the observation rows `obs`; else from the env's compact state (`obs` unused), `rows_out` optional.
+// Forms is what a precision brings: TILE agents per wavefront and tile, waves(exact) per workgroup, the fragment sizes encode / proj /
+// msg / head in 4-byte words, row_steps(n) k-steps fed from a row of n floats (lane group g holds the features [g S, g S + S) of
+// fp32's k-steps), whole_vectors(S, D) - such a row is read as aligned float4s - head_exact(mbh, S), and its kernels.
+template <class Forms>
+int run_chain(const mdr_tarmac_actor_t* actor, const float* obs, const mdr::ObserveArgs* o, float* rows_out, int32_t nb_envs, int32_t nb_houses,
+              uint64_t seed, uint64_t step, const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, int cus,
+              void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value;
+  const int hops = actor->num_hops, wc = actor->with_comm != 0;
+  const int64_t A = (int64_t)nb_envs * nb_houses;
+  const int mbh = blocks(H), mbv = blocks(V), mbm = blocks(H + V);
+  const VecLayout L = vec_layout(mbh, mbv, mbm);
+  const bool exact = mbh == 4 && mbv == 1 && (!wc || hops == 1 || mbm == 5);
+  const int waves = Forms::waves(exact);
+  const int64_t ldcat = wc ? H + V : H, ldqkv = K + K + V;
+  float* cat = static_cast<float*>(workspace);
+  float* qkv = cat + A * ldcat;
+  float* state = qkv + A * ldqkv;
+
+  MlpArgs a{};
+  a.vec = actor->vec, a.nvec = L.total;
+  a.cat = cat, a.qkv = qkv, a.state = state, a.ldcat = ldcat, a.ldqkv = ldqkv;
+  a.action = action, a.a_prob = a_prob, a.probs = probs;
+  a.A = A, a.ntiles = (A + Forms::TILE - 1) / Forms::TILE;
+  a.H = H, a.K = K, a.V = V, a.mbh = mbh, a.mbv = mbv, a.mbm = mbm;
+  a.with_comm = wc, a.greedy = actor->greedy != 0;
+  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.step_lo = (uint32_t)step, a.step_hi = (uint32_t)(step >> 32);
+  a.step_dev = step_dev;
+  a.np = wc ? (int)Forms::proj(H, V) : 0;
+
+  // ---- obs -> x (-> qkv)
+  a.fa = actor->frag_encode, a.fp = actor->frag_proj, a.na = (int)Forms::encode(F, H);
+  a.in0 = obs, a.ld0 = F, a.D0 = F, a.S0 = Forms::row_steps(F);
+  a.vec0 = Forms::whole_vectors(a.S0, F) && aligned16(obs);
+  int rc;
+  if (o)      // the same layers on features built in LDS: whole-tile staging where no tile leaves its env
+    rc = launch_observe(Forms::encode_observe_kernel(exact, rows_out != nullptr, o->N % Forms::TILE != 0), waves, Forms::TILE, a, *o,
+                        rows_out, cus, s);
+  else
+    rc = launch(Forms::encode_kernel(exact), waves, weights_bytes(a, true), a, cus, s);
+  if (rc != MDR_OK) return rc;
+  if (wc) {
+    for (int hop = 0; hop < hops; ++hop) {
+      if (hop > 0) {      // [comm, h] -> h' -> qkv
+        a.fa = actor->frag_msg, a.na = (int)Forms::msg(H, V);
+        a.in0 = cat + H, a.ld0 = ldcat, a.D0 = V, a.S0 = Forms::row_steps(V);
+        a.in1 = hop == 1 ? cat : state, a.ld1 = hop == 1 ? ldcat : H, a.S1 = Forms::row_steps(H);
+        // H, V and both leading dimensions are multiples of 4 floats, the workspace is 16-byte aligned
+        a.vec0 = Forms::whole_vectors(a.S0, V), a.vec1 = Forms::whole_vectors(a.S1, H);
+        rc = launch(Forms::rehop_kernel(exact), waves, weights_bytes(a, true), a, cus, s);
+        if (rc != MDR_OK) return rc;
+      }
+      rc = mdr_tarmac_comm(qkv, ldqkv, qkv + K, ldqkv, qkv + 2 * K, ldqkv, nb_envs, nb_houses, K, V, actor->nb_comm, actor->mode, actor->defect_prob,
+                           seed, step, step_dev, hop, cat + H, ldcat, stream);
+      if (rc != MDR_OK) return rc;
+    }
+  }
+  // ---- [x, comm] -> logits -> action
+  a.fa = actor->frag_head, a.na = (int)Forms::head(H, V, wc);
+  a.in0 = cat, a.ld0 = ldcat, a.D0 = (int)ldcat, a.S0 = Forms::row_steps((int)ldcat);
+  a.vec0 = Forms::whole_vectors(a.S0, (int)ldcat);
+  const bool head_exact = Forms::head_exact(mbh, a.S0);
+  return launch(Forms::head_kernel(head_exact), Forms::waves(head_exact), weights_bytes(a, false), a, cus, s);
+}
+
+}  // namespace

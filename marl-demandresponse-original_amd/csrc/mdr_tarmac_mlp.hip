@@ -7,13 +7,17 @@
 // one layer - units 16 kb + 4 g + reg of its own agent - IS the B operand of the next layer's k-step q = 4 kb + reg when the weight
 // columns are stored in that order.  No LDS and no lane movement for the activations; the biases start the accumulators.
 //
-//   k_tarmac_encode  obs rows -> obs2hidden (F -> H relu -> H) = x -> cat[:, 0:H]; from the same registers hidden2query | hidden2key |
-//                    hidden2value (H -> H tanh -> K | K | V) -> qkv [A][K + K + V], the buffer mdr_tarmac_comm reads in place
-//   k_tarmac_encode_obs  the same from the env's compact state: the features are built in the wave's LDS window (mdr_observe.h)
-//                    instead of being read from observation rows - mdr_env_tarmac_actor_sample
+//   k_tarmac_encode  features -> obs2hidden (F -> H relu -> H) = x -> cat[:, 0:H]; from the same registers hidden2query | hidden2key |
+//                    hidden2value (H -> H tanh -> K | K | V) -> qkv [A][K + K + V], the buffer mdr_tarmac_comm reads in place.
+//                    One kernel over a feature source: <..., RowsSource> reads the observation rows, <..., ObserveSource<STORE, GEN>>
+//                    builds the features from the env's compact state in the wave's LDS window (ObserveWindow, mdr_tarmac_mlp.h;
+//                    mdr_observe.h) - mdr_env_tarmac_actor_sample
 //   k_tarmac_rehop   hops >= 1: [comm, h] -> msg_state2state (H + V -> H + V tanh -> H) = h' -> state; the same projections -> qkv
-//   k_tarmac_head    cat = [x, comm] -> comm_hidden2action (H + V -> H relu -> 2) (hidden2action on x without communication), the
-//                    two-logit softmax and the action draw of mdr_logits_sample (mdr_draw.h)
+//   k_tarmac_head    cat = [x, comm] -> comm_hidden2action (H + V -> H relu -> 2) (hidden2action on x without communication), then
+//                    head_finish (mdr_tarmac_mlp.h): the two-logit softmax and the action draw of mdr_logits_sample (mdr_draw.h)
+//
+// Every kernel opens with stage_weights (mdr_tarmac_mlp.h).  The host side is one chain for both precisions, run_chain<Forms>
+// (mdr_tarmac_mlp.h), behind the argument checks of sample_chain below; Fp32Forms is what this file brings to it.
 //
 // A sample step is 1 + hops + (hops - 1) + 1 launches.  Each kernel is a persistent grid of min(ceil(tiles / waves), CUs) workgroups
 // that stage their weights ONCE into LDS in fragment order (up to ~125 KB: one workgroup per CU) and stride over the tiles.  Rows
@@ -146,49 +150,20 @@ __device__ __forceinline__ void projections(const float* fp, const float* vec, c
   }
 }
 
-template <int MBH, int MBV, bool EXACT>
-__global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_encode(MlpArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* fa = lds;
-  float* fp = fa + a.na;
-  float* vec = fp + a.np;
-  const int tid = threadIdx.x;
-  stage(fa, a.fa, a.na, tid);
-  if (a.with_comm) stage(fp, a.fp, a.np, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  __syncthreads();
-  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
-  const VecLayout L = vec_layout(mbh, mbv, a.mbm);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  constexpr int NW = EXACT ? WAVES : WAVES_GEN;
-  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
-  const float* f2 = fa + a.S0 * 64 * mbh;
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const int64_t agent = t * 16 + r;
-    const bool valid = agent < a.A;
-    const int64_t ac = valid ? agent : a.A - 1;
-    float xr[16];
-    load_feats<16>(a.in0 + ac * a.ld0, g * a.S0, a.S0, a.D0, a.vec0, xr);
-    f32x4 t1[MBH], x[MBH];
-    init_bias<MBH>(vec + L.o1, g, mbh, t1);
-    layer_feats<16, MBH, EXACT>(fa, xr, a.S0, t1, mbh, lane);
-    init_bias<MBH>(vec + L.o2, g, mbh, x);
-    layer_regs<MBH, MBH, EXACT, ACT_RELU>(f2, t1, mbh, x, mbh, lane);
-    float* cat_row = a.cat + ac * a.ldcat;
-#pragma unroll
-    for (int mb = 0; mb < MBH; ++mb)
-      if (valid && 16 * mb + 4 * g < a.H) *reinterpret_cast<f32x4*>(cat_row + 16 * mb + 4 * g) = x[mb];
-    if (a.with_comm) projections<MBH, MBV, EXACT>(fp, vec, L, x, mbh, mbv, a.K, a.V, a.qkv + ac * a.ldqkv, valid, lane);
+// Where k_tarmac_encode's 16 agents get their features, 13 per lane: lane group g takes the features 13 g + s of its agent, the
+// k-step order of frag_encode.  begin() -> the lane's features for tile t; after_layer1() once they are in the MFMA pipeline; end().
+struct RowsSource : NoHooks {      // the agent's observation row
+  static constexpr bool WINDOWS = false;
+  __device__ __forceinline__ RowsSource(int64_t, int64_t) {}
+  __device__ __forceinline__ const float (&begin(int64_t, const float* row, int first, int S, int D, int vec, float (&xr)[16]))[16] {
+    load_feats<16>(row, first, S, D, vec, xr);
+    return xr;
   }
-}
+};
 
-// Observe -> act (mdr_env_tarmac_actor_sample): k_tarmac_encode with its 13 features per lane read from the wave's LDS window
-// instead of an observation row.  The window is staged from the env's compact state by the helpers of mdr_observe.h exactly as
-// k_actor_observe16 (mdr_policy.hip) stages it for the default observation - 16 consecutive agents per wave, one window per wave -
-// and holds normStateDict feature n of tile row r at float ROW r + (n < 11 ? 40 + n : n - 11).  Lane group g takes the features
-// 13 g + s of its agent, the k-step order of frag_encode, so the MFMA sequence and its operands are those of the rows path; index
-// 51, the pad of group 3's last k-step, reads feature 50 as the rows path does (against a zero weight).
+// Observe -> act (mdr_env_tarmac_actor_sample), k_tarmac_encode<..., ObserveSource<STORE, GEN>>: the features are read from the
+// wave's LDS window (ObserveWindow, mdr_tarmac_mlp.h) - 16 consecutive agents per wave, one window per wave - so the MFMA sequence and
+// its operands are those of the rows path; index 51, the pad of group 3's last k-step, reads feature 50 (against a zero weight).
 // Row stride: TARMAC_OBS_ROW = 60 floats.  The features are read with 4-byte LDS loads in which the 16 lanes of a group address the
 // same column of 16 consecutive rows, on 32 banks of 4 bytes.  The stride has to stay a multiple of 4 floats for the 16-byte stores
 // of the staging (an odd one would be conflict-free); 60 = 28 (mod 32) puts the 16 rows on 8 banks, two lanes each, where OBS_ROW = 56
@@ -196,92 +171,84 @@ __global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_enc
 // goes past float 52 of a row.  16 windows of 3840 bytes beside the ~94 KB of weights: 157 KB with the row table, under the 160 KB.
 // The loads of a wave's next tile are issued before the tile's matrix work and land during it; its rows are staged behind layer 1,
 // once the features of the current tile are consumed, and gathered at the end of the tile.
-template <int MBH, int MBV, bool EXACT, bool STORE, bool GEN>
-__global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_encode_obs(MlpArgs a, mdr::ObserveArgs o, float* rows_out) {
+template <bool STORE, bool GEN>
+struct ObserveSource : ObserveWindow<16, STORE, GEN> {
+  using W = ObserveWindow<16, STORE, GEN>;
+  static constexpr bool WINDOWS = true;
+  static constexpr int TILE = 16;
+  float xr[16];
+
+  __device__ __forceinline__ ObserveSource(int64_t A, int64_t ntiles, const WindowArgs& x) : W{x.o, x.rows_out, A, ntiles} {}
+
+  __device__ __forceinline__ void gather(int64_t first_agent) {
+    const int g = this->lane0 >> 4, r = this->lane0 & 15;
+    this->lockout_quotients(r, g);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const float* row = this->rows + r * W::ROW;
+#pragma unroll
+    for (int s = 0; s < 13; ++s) xr[s] = row[W::at(min(13 * g + s, 50))];
+    this->store_rows(first_agent);
+  }
+  __device__ __forceinline__ void prime(int64_t wave, int64_t nwaves) {
+    this->start(wave, nwaves);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) xr[s] = 0.0f;
+    if (wave < this->ntiles) {
+      this->load(wave * TILE);
+      this->stage_rows();
+      observe_window_fence();
+      gather(wave * TILE);
+    }
+  }
+  __device__ __forceinline__ const float (&begin(int64_t t, const float*, int, int, int, int, float (&)[16]))[16] {
+    this->advance(t);
+    if (this->more) this->load(this->next_tile * TILE);
+    return xr;
+  }
+  __device__ __forceinline__ void after_layer1() {      // the window is free for the next tile's rows
+    if (this->more) this->stage_rows();
+  }
+  __device__ __forceinline__ void end() {
+    if (this->more) {
+      observe_window_fence();
+      gather(this->next_tile * TILE);
+    }
+  }
+};
+
+// obs2hidden on the source's features, x -> cat, the projections -> qkv.  The observe source runs with as many of the form's waves as
+// its windows leave room for.
+template <int MBH, int MBV, bool EXACT, class Source, class... SourceArgs>
+__global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_encode(MlpArgs a, SourceArgs... x) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int TILE = 16, ROW = TARMAC_OBS_ROW, WIN = TILE * ROW;
-  float* fa = lds;
-  float* fp = fa + a.na;
-  float* vec = fp + a.np;
-  const int tid = threadIdx.x;
-  const int NW = (int)(blockDim.x >> 6);      // as many of the form's waves as the windows leave room for
-  float* rows = vec + a.nvec + (tid >> 6) * WIN;
-  uint16_t* table = reinterpret_cast<uint16_t*>(vec + a.nvec + NW * WIN);      // [TILE * 51] (only when rows are stored)
-  stage(fa, a.fa, a.na, tid);
-  if (a.with_comm) stage(fp, a.fp, a.np, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  for (int i = lane0; i < WIN; i += 64) rows[i] = 0.0f;
-  if (STORE) observe_build_table<TILE, ROW>(table, tid, 64 * NW);
-  __syncthreads();
+  Source src(a.A, a.ntiles, x...);
+  const int nw = Source::WINDOWS ? (int)(blockDim.x >> 6) : (EXACT ? WAVES : WAVES_GEN);
+  const Staged S = stage_weights(lds, Fragments{a.fa, a.fp, a.vec, a.na, a.np, a.nvec}, a.with_comm != 0, nw,
+                                 [&]() { src.carve(lds + a.na + a.np + a.nvec, nw); });
+  src.prime(S.wave, S.nwaves);
+  const float *fa = S.fa, *fp = S.fp, *vec = S.vec;
   const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
   const VecLayout L = vec_layout(mbh, mbv, a.mbm);
-  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
   const float* f2 = fa + a.S0 * 64 * mbh;
-  const double* sig_row = observe_sig_row(o);
-  TileCursor tc;
-  tc.init(wave * TILE, nwaves * TILE, o.N);
-  float xr[16] = {};
-  auto gather = [&](int64_t first_agent) {
-    const int g = lane0 >> 4;
-    float* row = rows + r * ROW;
-    const float lock = row[4 * OBS_C + 11], y = row[4 * OBS_C + 12];
-    // the senders' seconds_since_off become quotients by the RECEIVER's lockout, in place: lane group g takes the messages g, g + 4
-    // and g + 8 of its agent's row (k_actor_observe16)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int m = g + 4 * i;
-      if (m < OBS_C) row[4 * m + 1] = mdr::div_by_lockout(row[4 * m + 1], lock, y);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-    for (int s = 0; s < 13; ++s) {
-      const int n = min(13 * g + s, 50);
-      xr[s] = row[n < 11 ? 4 * OBS_C + n : n - 11];
-    }
-    if (STORE)
-      observe_store_rows<TILE>(rows, table, rows_out + first_agent * 51, lane0,
-                               GEN ? (int)((a.A - first_agent) < (int64_t)TILE ? (a.A - first_agent) : (int64_t)TILE) : TILE);
-  };
-  SegSlot slot{};
-  if (wave < a.ntiles) {
-    if (GEN) {
-      const HouseRegs first = observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, wave * TILE, a.A, lane0, slot);
-      observe_stage_gen<false, ROW>(o, first, slot, rows);
-    } else {
-      const HouseRegs first = observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
-      observe_stage<TILE, false, ROW>(o, first, rows, lane0);
-    }
-    observe_window_fence();
-    gather(wave * TILE);
-  }
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const int64_t agent = t * 16 + r;
+  for (int64_t t = S.wave; t < a.ntiles; t += S.nwaves) {
+    const int lane = tile_local(S.lane0), g = lane >> 4;
+    const int64_t agent = t * 16 + S.r;
     const bool valid = agent < a.A;
     const int64_t ac = valid ? agent : a.A - 1;
-    const bool more = t + nwaves < a.ntiles;
-    tc.next();
-    HouseRegs nxt{};
-    if (more) nxt = GEN ? observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, (t + nwaves) * TILE, a.A, lane0, slot) : observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
-    f32x4 t1[MBH], x[MBH];
+    float fresh[16];      // the rows source fills it for every tile; the observe source carries its own from the previous tile's end
+    const float (&xr)[16] = src.begin(t, a.in0 + ac * a.ld0, g * a.S0, a.S0, a.D0, a.vec0, fresh);
+    f32x4 t1[MBH], x1[MBH];
     init_bias<MBH>(vec + L.o1, g, mbh, t1);
     layer_feats<16, MBH, EXACT>(fa, xr, a.S0, t1, mbh, lane);
-    if (more) {      // the features are in the MFMA pipeline: the window is free for the next tile's rows
-      if (GEN) observe_stage_gen<false, ROW>(o, nxt, slot, rows);
-      else observe_stage<TILE, false, ROW>(o, nxt, rows, lane0);
-    }
-    init_bias<MBH>(vec + L.o2, g, mbh, x);
-    layer_regs<MBH, MBH, EXACT, ACT_RELU>(f2, t1, mbh, x, mbh, lane);
+    src.after_layer1();
+    init_bias<MBH>(vec + L.o2, g, mbh, x1);
+    layer_regs<MBH, MBH, EXACT, ACT_RELU>(f2, t1, mbh, x1, mbh, lane);
     float* cat_row = a.cat + ac * a.ldcat;
 #pragma unroll
     for (int mb = 0; mb < MBH; ++mb)
-      if (valid && 16 * mb + 4 * g < a.H) *reinterpret_cast<f32x4*>(cat_row + 16 * mb + 4 * g) = x[mb];
-    if (a.with_comm) projections<MBH, MBV, EXACT>(fp, vec, L, x, mbh, mbv, a.K, a.V, a.qkv + ac * a.ldqkv, valid, lane);
-    if (more) {
-      observe_window_fence();
-      gather((t + nwaves) * TILE);
-    }
+      if (valid && 16 * mb + 4 * g < a.H) *reinterpret_cast<f32x4*>(cat_row + 16 * mb + 4 * g) = x1[mb];
+    if (a.with_comm) projections<MBH, MBV, EXACT>(fp, vec, L, x1, mbh, mbv, a.K, a.V, a.qkv + ac * a.ldqkv, valid, lane);
+    src.end();
   }
 }
 
@@ -290,24 +257,15 @@ __global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_enc
 template <int MBH, int MBV, int MBM, bool EXACT>
 __global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_rehop(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* fa = lds;
-  float* fp = fa + a.na;
-  float* vec = fp + a.np;
-  const int tid = threadIdx.x;
-  stage(fa, a.fa, a.na, tid);
-  stage(fp, a.fp, a.np, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  __syncthreads();
+  const Staged S = stage_weights(lds, Fragments{a.fa, a.fp, a.vec, a.na, a.np, a.nvec}, true, EXACT ? WAVES : WAVES_GEN);
+  const float *fa = S.fa, *fp = S.fp, *vec = S.vec;
   const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv, mbm = EXACT ? MBM : a.mbm;
   const VecLayout L = vec_layout(mbh, mbv, mbm);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  constexpr int NW = EXACT ? WAVES : WAVES_GEN;
-  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
   const float* f1h = fa + a.S0 * 64 * mbm;
   const float* f2 = f1h + a.S1 * 64 * mbm;
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const int64_t agent = t * 16 + r;
+  for (int64_t t = S.wave; t < a.ntiles; t += S.nwaves) {
+    const int lane = tile_local(S.lane0), g = lane >> 4;
+    const int64_t agent = t * 16 + S.r;
     const bool valid = agent < a.A;
     const int64_t ac = valid ? agent : a.A - 1;
     float xc[4 * MBV], xh[4 * MBH];
@@ -331,21 +289,15 @@ __global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_reh
 template <int MBH, int XS, bool EXACT>
 __global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_head(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* fa = lds;
-  float* vec = fa + a.na;
-  const int tid = threadIdx.x;
-  stage(fa, a.fa, a.na, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  __syncthreads();
+  const Staged S = stage_weights(lds, Fragments{a.fa, nullptr, a.vec, a.na, 0, a.nvec}, false, EXACT ? WAVES : WAVES_GEN);
+  const float *fa = S.fa, *vec = S.vec;
   const int mbh = EXACT ? MBH : a.mbh;
   const VecLayout L = vec_layout(mbh, a.mbv, a.mbm);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  constexpr int NW = EXACT ? WAVES : WAVES_GEN;
-  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
   const float bias3 = vec[L.b3];
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const int64_t agent = t * 16 + r;
+  const DrawArgs draw{a.action, a.a_prob, a.probs, a.greedy, a.k0, a.k1, a.step_lo, a.step_hi, a.step_dev};
+  for (int64_t t = S.wave; t < a.ntiles; t += S.nwaves) {
+    const int lane = tile_local(S.lane0), g = lane >> 4;
+    const int64_t agent = t * 16 + S.r;
     const bool valid = agent < a.A;
     const int64_t ac = valid ? agent : a.A - 1;
     float xr[XS];
@@ -353,34 +305,7 @@ __global__ __launch_bounds__(64 * (EXACT ? WAVES : WAVES_GEN)) void k_tarmac_hea
     f32x4 acc[MBH];
     init_bias<MBH>(vec + L.h1, g, mbh, acc);
     layer_feats<XS, MBH, EXACT>(fa, xr, a.S0, acc, mbh, lane);
-    float d = 0.0f;
-#pragma unroll
-    for (int mb = 0; mb < MBH; ++mb)
-      if (EXACT || mb < mbh) {
-        const f32x4 w = *reinterpret_cast<const f32x4*>(vec + L.wd + 16 * mb + 4 * g);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d = fmaf(w[i], relu(acc[mb][i]), d);
-      }
-    d += __shfl_xor(d, 16);
-    d += __shfl_xor(d, 32);
-    d += bias3;
-    const float p0 = 1.0f / (1.0f + expf(-d));      // mdr_logits_sample's softmax over two logits
-    const float p1 = 1.0f / (1.0f + expf(d));
-    if (g == 0 && valid) {
-      int act;
-      if (a.greedy) {
-        act = d >= 0.0f ? 0 : 1;      // argmax keeps the first maximum, as torch.argmax
-      } else {
-        const float u = action_uniform(mdr::action_word(agent, a.step_lo, a.step_hi, a.step_dev, a.k0, a.k1));
-        act = u < p0 ? 0 : 1;
-      }
-      a.action[agent] = (uint8_t)act;
-      if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
-      if (a.probs) {
-        a.probs[agent * 2] = p0;
-        a.probs[agent * 2 + 1] = p1;
-      }
-    }
+    head_finish<MBH, EXACT>(acc, vec, L, mbh, g, bias3, draw, agent, valid);
   }
 }
 
@@ -391,27 +316,45 @@ bool shape_covered(int F, int H, int K, int V) {
   return F <= MAX_F && H % 4 == 0 && H <= MAX_H && K % 4 == 0 && K <= MAX_K && V % 4 == 0 && V <= MAX_V;
 }
 
-int64_t encode_floats(int F, int H) { return ((int64_t)(F + 3) / 4 + 4 * blocks(H)) * 64 * blocks(H); }
-int64_t proj_floats(int H, int V) { return (int64_t)4 * blocks(H) * 64 * (3 * blocks(H) + 2 + blocks(V)); }
-int64_t msg_floats(int H, int V) { return (int64_t)((V + H) / 4) * 64 * blocks(H + V) + (int64_t)4 * blocks(H + V) * 64 * blocks(H); }
-int64_t head_floats(int H, int V, int with_comm) { return (int64_t)((H + (with_comm ? V : 0)) / 4) * 64 * blocks(H); }
+struct Fp32Forms : FragFloats {
+  static constexpr int TILE = 16;
+  static int waves(bool exact) { return exact ? WAVES : WAVES_GEN; }
+  static int row_steps(int n) { return (n + 3) / 4; }
+  static int whole_vectors(int S, int D) { return (S % 4 == 0 && 4 * S == D) ? 1 : 0; }
+  static bool head_exact(int mbh, int S) { return mbh == 4 && S <= 20; }
+  static MlpKernel encode_kernel(bool exact) { return exact ? k_tarmac_encode<4, 1, true, RowsSource> : k_tarmac_encode<4, 2, false, RowsSource>; }
+  template <bool EXACT, bool STORE, bool GEN>
+  static MlpObserveKernel observe_form() {
+    return k_tarmac_encode<4, EXACT ? 1 : 2, EXACT, ObserveSource<STORE, GEN>, WindowArgs>;
+  }
+  template <bool EXACT>
+  static MlpObserveKernel observe_form(bool store, bool gen) {
+    return store ? (gen ? observe_form<EXACT, true, true>() : observe_form<EXACT, true, false>())
+                 : (gen ? observe_form<EXACT, false, true>() : observe_form<EXACT, false, false>());
+  }
+  static MlpObserveKernel encode_observe_kernel(bool exact, bool store, bool gen) {
+    return exact ? observe_form<true>(store, gen) : observe_form<false>(store, gen);
+  }
+  static MlpKernel rehop_kernel(bool exact) { return exact ? k_tarmac_rehop<4, 1, 5, true> : k_tarmac_rehop<4, 2, 6, false>; }
+  static MlpKernel head_kernel(bool exact) { return exact ? k_tarmac_head<4, 20, true> : k_tarmac_head<4, 24, false>; }
+};
 
 }  // namespace
 
 extern "C" {
 
 int64_t mdr_tarmac_frag_encode_floats(int32_t num_state, int32_t hidden) {
-  return (num_state > 0 && hidden > 0 && num_state <= MAX_F && hidden <= MAX_H) ? encode_floats(num_state, hidden) : -1;
+  return (num_state > 0 && hidden > 0 && num_state <= MAX_F && hidden <= MAX_H) ? Fp32Forms::encode(num_state, hidden) : -1;
 }
 int64_t mdr_tarmac_frag_proj_floats(int32_t hidden, int32_t num_value) {
-  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V) ? proj_floats(hidden, num_value) : -1;
+  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V) ? Fp32Forms::proj(hidden, num_value) : -1;
 }
 int64_t mdr_tarmac_frag_msg_floats(int32_t hidden, int32_t num_value) {
-  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V && hidden % 4 == 0 && num_value % 4 == 0) ? msg_floats(hidden, num_value) : -1;
+  return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V && hidden % 4 == 0 && num_value % 4 == 0) ? Fp32Forms::msg(hidden, num_value) : -1;
 }
 int64_t mdr_tarmac_frag_head_floats(int32_t hidden, int32_t num_value, int32_t with_comm) {
   return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V && hidden % 4 == 0 && num_value % 4 == 0)
-             ? head_floats(hidden, num_value, with_comm) : -1;
+             ? Fp32Forms::head(hidden, num_value, with_comm) : -1;
 }
 int64_t mdr_tarmac_vec_floats(int32_t hidden, int32_t num_value) {
   return (hidden > 0 && num_value > 0 && hidden <= MAX_H && num_value <= MAX_V) ? vec_layout(blocks(hidden), blocks(num_value), blocks(hidden + num_value)).total : -1;
@@ -421,11 +364,8 @@ int64_t mdr_tarmac_frag_words(const mdr_tarmac_actor_t* actor, int32_t part) {
   if (!actor || actor->struct_size != sizeof(mdr_tarmac_actor_t) || part < 0 || part > 3) return -1;
   const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value, wc = actor->with_comm != 0;
   if (!shape_positive(F, H, K, V) || !shape_covered(F, H, K, V)) return -1;
-  if (actor->precision == MDR_TARMAC_FP32)
-    return part == 0 ? encode_floats(F, H) : part == 1 ? proj_floats(H, V) : part == 2 ? msg_floats(H, V) : head_floats(H, V, wc);
-  if (actor->precision == MDR_TARMAC_BF16X3)
-    return part == 0 ? encode_words(F, H) : part == 1 ? proj_words(H, V) : part == 2 ? msg_words(H, V) : head_words(H, V, wc);
-  return -1;
+  auto words = [&](auto frag) { return part == 0 ? frag.encode(F, H) : part == 1 ? frag.proj(H, V) : part == 2 ? frag.msg(H, V) : frag.head(H, V, wc); };
+  return actor->precision == MDR_TARMAC_FP32 ? words(FragFloats{}) : actor->precision == MDR_TARMAC_BF16X3 ? words(FragWords{}) : -1;
 }
 
 int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t* actor, int64_t nb_agents) {
@@ -437,8 +377,8 @@ int64_t mdr_tarmac_actor_workspace_bytes(const mdr_tarmac_actor_t* actor, int64_
   return nb_agents * floats * (int64_t)sizeof(float);
 }
 
-// The launch chain of a sample.  `o` == nullptr: from the observation rows `obs`; else from the env's compact state (`obs` unused),
-// `rows_out` optional.  Every refusal comes before the first launch.
+// The argument checks of a sample, then its launch chain (run_chain, mdr_tarmac_mlp.h) in the actor's precision.  `o` == nullptr: from the
+// observation rows `obs`; else from the env's compact state (`obs` unused), `rows_out` optional.  Every refusal comes before the first launch.
 static int sample_chain(const mdr_tarmac_actor_t* actor, const float* obs, const mdr::ObserveArgs* o, float* rows_out, int32_t nb_envs,
                         int32_t nb_houses, uint64_t seed, uint64_t step, const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob,
                         float* probs, void* stream) {
@@ -462,74 +402,11 @@ static int sample_chain(const mdr_tarmac_actor_t* actor, const float* obs, const
   const int64_t A = (int64_t)nb_envs * nb_houses;
   if (A >= ((int64_t)1 << 35)) return MDR_ERR_UNSUPPORTED;      // the grids of mdr_tarmac_comm
   if (A == 0) return MDR_OK;
-  hipStream_t s = (hipStream_t)stream;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  if (actor->precision == MDR_TARMAC_BF16X3)
-    return mdr::tarmac_sample_bf16(actor, obs, o, rows_out, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, cus, stream);
-
-  const int mbh = blocks(H), mbv = blocks(V), mbm = blocks(H + V);
-  const VecLayout L = vec_layout(mbh, mbv, mbm);
-  const bool exact = mbh == 4 && mbv == 1 && (!wc || hops == 1 || mbm == 5);
-  const int64_t ldcat = wc ? H + V : H, ldqkv = K + K + V;
-  float* cat = static_cast<float*>(workspace);
-  float* qkv = cat + A * ldcat;
-  float* state = qkv + A * ldqkv;
-
-  MlpArgs a{};
-  a.vec = actor->vec, a.nvec = L.total;
-  a.cat = cat, a.qkv = qkv, a.state = state, a.ldcat = ldcat, a.ldqkv = ldqkv;
-  a.action = action, a.a_prob = a_prob, a.probs = probs;
-  a.A = A, a.ntiles = (A + 15) / 16;
-  a.H = H, a.K = K, a.V = V, a.mbh = mbh, a.mbv = mbv, a.mbm = mbm;
-  a.with_comm = wc, a.greedy = actor->greedy != 0;
-  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.step_lo = (uint32_t)step, a.step_hi = (uint32_t)(step >> 32);
-  a.step_dev = step_dev;
-  a.np = wc ? (int)proj_floats(H, V) : 0;
-  auto whole4 = [](int S, int D) { return (S % 4 == 0 && 4 * S == D) ? 1 : 0; };
-
-  // ---- obs -> x (-> qkv)
-  a.fa = actor->frag_encode, a.fp = actor->frag_proj, a.na = (int)encode_floats(F, H);
-  a.in0 = obs, a.ld0 = F, a.D0 = F, a.S0 = (F + 3) / 4;
-  a.vec0 = whole4(a.S0, F) && aligned16(obs);
-  int rc;
-  if (o) {      // the same layers on features built in LDS: whole-tile staging where no tile of 16 leaves its env
-    const bool gen = o->N % 16 != 0;
-#define MDR_TARMAC_OBS(...)                                                                                                  \
-  (rows_out ? (gen ? launch_observe(k_tarmac_encode_obs<__VA_ARGS__, true, true>, waves, 16, a, *o, rows_out, cus, s)       \
-                   : launch_observe(k_tarmac_encode_obs<__VA_ARGS__, true, false>, waves, 16, a, *o, rows_out, cus, s))     \
-            : (gen ? launch_observe(k_tarmac_encode_obs<__VA_ARGS__, false, true>, waves, 16, a, *o, rows_out, cus, s)      \
-                   : launch_observe(k_tarmac_encode_obs<__VA_ARGS__, false, false>, waves, 16, a, *o, rows_out, cus, s)))
-    const int waves = exact ? WAVES : WAVES_GEN;
-    rc = exact ? MDR_TARMAC_OBS(4, 1, true) : MDR_TARMAC_OBS(4, 2, false);
-#undef MDR_TARMAC_OBS
-  } else {
-    rc = exact ? launch(k_tarmac_encode<4, 1, true>, WAVES, a, a.na + a.np + a.nvec, cus, s)
-               : launch(k_tarmac_encode<4, 2, false>, WAVES_GEN, a, a.na + a.np + a.nvec, cus, s);
-  }
-  if (rc != MDR_OK) return rc;
-  if (wc) {
-    for (int hop = 0; hop < hops; ++hop) {
-      if (hop > 0) {      // [comm, h] -> h' -> qkv
-        a.fa = actor->frag_msg, a.na = (int)msg_floats(H, V);
-        a.in0 = cat + H, a.ld0 = ldcat, a.D0 = V, a.S0 = V / 4;
-        a.in1 = hop == 1 ? cat : state, a.ld1 = hop == 1 ? ldcat : H, a.S1 = H / 4;
-        a.vec0 = whole4(a.S0, V), a.vec1 = whole4(a.S1, H);
-        rc = exact ? launch(k_tarmac_rehop<4, 1, 5, true>, WAVES, a, a.na + a.np + a.nvec, cus, s)
-                   : launch(k_tarmac_rehop<4, 2, 6, false>, WAVES_GEN, a, a.na + a.np + a.nvec, cus, s);
-        if (rc != MDR_OK) return rc;
-      }
-      rc = mdr_tarmac_comm(qkv, ldqkv, qkv + K, ldqkv, qkv + 2 * K, ldqkv, nb_envs, nb_houses, K, V, actor->nb_comm, actor->mode, actor->defect_prob,
-                           seed, step, step_dev, hop, cat + H, ldcat, stream);
-      if (rc != MDR_OK) return rc;
-    }
-  }
-  // ---- [x, comm] -> logits -> action
-  a.fa = actor->frag_head, a.na = (int)head_floats(H, V, wc);
-  a.in0 = cat, a.ld0 = ldcat, a.D0 = (int)ldcat, a.S0 = (int)ldcat / 4;
-  a.vec0 = whole4(a.S0, (int)ldcat);
-  return (mbh == 4 && a.S0 <= 20) ? launch(k_tarmac_head<4, 20, true>, WAVES, a, a.na + a.nvec, cus, s)
-                                  : launch(k_tarmac_head<4, 24, false>, WAVES_GEN, a, a.na + a.nvec, cus, s);
+  return actor->precision == MDR_TARMAC_BF16X3
+             ? mdr::tarmac_sample_bf16(actor, obs, o, rows_out, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, cus, stream)
+             : run_chain<Fp32Forms>(actor, obs, o, rows_out, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, cus, stream);
 }
 
 int mdr_tarmac_actor_sample(const mdr_tarmac_actor_t* actor, const float* obs, int32_t nb_envs, int32_t nb_houses, uint64_t seed, uint64_t step,

@@ -175,149 +175,132 @@ __device__ __forceinline__ void projections(const uint4* fp, const float* vec, c
   }
 }
 
-// frag_encode: obs2hidden.0 [S0 = ceil(F / 32) k-steps fed from the obs row][mbh pairs], then obs2hidden.2 [ceil(mbh / 2)][mbh]
-template <int MBH, int MBV, bool EXACT>
-__global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_bf16(MlpArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* fa = lds;
-  float* fp = fa + a.na;
-  float* vec = fp + a.np;
-  const int tid = threadIdx.x;
-  stage(fa, a.fa, a.na, tid);
-  if (a.with_comm) stage(fp, a.fp, a.np, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  __syncthreads();
-  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
-  const uint4* fp4 = reinterpret_cast<const uint4*>(fp);
-  const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
-  constexpr int SH = (MBH + 1) / 2;
-  const int sh = EXACT ? SH : ksteps_regs(mbh);
-  const VecLayout L = vec_layout(mbh, mbv, a.mbm);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  const int64_t wave = (int64_t)blockIdx.x * WAVES_BF16 + (tid >> 6), nwaves = (int64_t)gridDim.x * WAVES_BF16;
-  const uint4* f2 = fa4 + a.S0 * mbh * 128;
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const Tile T = tile_of(t, r, a.A);
-    const float* row[NCOL];
-    float* cat_row[NCOL];
-    float* qkv_row[NCOL];
+// The two halves of a split k-step of 8 floats per column block
+__device__ __forceinline__ void split_cols(const float (&v)[NCOL][8], bf16x8 (&Bh)[NCOL], bf16x8 (&Bl)[NCOL]) {
 #pragma unroll
-    for (int c = 0; c < NCOL; ++c) {
-      row[c] = a.in0 + T.ac[c] * a.ld0;
-      cat_row[c] = a.cat + T.ac[c] * a.ldcat;
-      qkv_row[c] = a.qkv + T.ac[c] * a.ldqkv;
-    }
-    f32x4 t1[NCOL][MBH], x[NCOL][MBH];
-    init_bias<MBH>(vec + L.o1, g, mbh, t1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-      if (s < a.S0) {
-        bf16x8 Bh[NCOL], Bl[NCOL];
-        split_rows(row, 32 * s + 8 * g, a.D0, a.vec0, Bh, Bl);
-        mma_step<MBH, EXACT>(fa4 + s * mbh * 128, mbh, lane, Bh, Bl, t1);
-      }
-    init_bias<MBH>(vec + L.o2, g, mbh, x);
-#pragma unroll
-    for (int s = 0; s < SH; ++s)
-      if (EXACT || s < sh) {
-        bf16x8 Bh[NCOL], Bl[NCOL];
-        split_regs<MBH, ACT_RELU>(t1, s, Bh, Bl);
-        mma_step<MBH, EXACT>(f2 + s * mbh * 128, mbh, lane, Bh, Bl, x);
-      }
-    store_blocks<MBH>(x, cat_row, T.valid, a.H, g);
-    if (a.with_comm) projections<MBH, MBV, EXACT>(fp4, vec, L, x, mbh, mbv, a.K, a.V, qkv_row, T.valid, lane);
+  for (int c = 0; c < NCOL; ++c) {
+    uint4 bh, bl;
+    split8(v[c], bh, bl);
+    Bh[c] = __builtin_bit_cast(bf16x8, bh);
+    Bl[c] = __builtin_bit_cast(bf16x8, bl);
   }
 }
 
-// Observe -> act (mdr_env_tarmac_actor_sample): k_tarmac_encode_bf16 with the floats of its two row-fed k-steps read from the wave's
-// LDS window instead of observation rows, as k_tarmac_encode_obs (mdr_tarmac_mlp.hip) does for the fp32 form.  A tile is 32
-// consecutive agents - column block c holds the tile rows 16 c + r - staged as k_actor_observe_bf16 (mdr_policy.hip) stages its
-// tiles of 32; element j of lane group g in k-step s is normStateDict feature n = 32 s + 8 g + j at window float ROW row + (n < 11 ?
-// 40 + n : n - 11), and an explicit zero from n = 51 on, as split_rows builds it.  Row stride: TARMAC_OBS_ROW = 60 for the same
-// 4-byte reads of one column of 16 consecutive rows.  8 windows of 7680 bytes beside ~95 KB of fragments: 158 KB with the row table.
-// The loads of the next tile are issued before the tile's matrix work; its rows are staged once both k-steps have been split.  The
-// general form has no registers left to carry them, or the next tile's features, across the layers (it spills with them): it loads
-// and stages at the tile's end and reads its features when the tile starts.
-template <int MBH, int MBV, bool EXACT, bool STORE, bool GEN>
-__global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_obs_bf16(MlpArgs a, mdr::ObserveArgs o, float* rows_out) {
+// Where k_tarmac_encode_bf16's 32 agents get the floats of the two row-fed k-steps.  begin() for tile t; operands(s) -> the B operands
+// of k-step s; after_layer1() once both are split; end().
+struct RowsSource : NoHooks {      // the agents' observation rows
+  static constexpr bool WINDOWS = false;
+  const float* row[NCOL];
+  int D, vec;
+  __device__ __forceinline__ RowsSource(int64_t, int64_t) {}
+  __device__ __forceinline__ void begin(int64_t, const Tile& T, const float* in0, int64_t ld0, int D0, int vec0) {
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) row[c] = in0 + T.ac[c] * ld0;
+    D = D0, vec = vec0;
+  }
+  __device__ __forceinline__ void operands(int s, int g, bf16x8 (&Bh)[NCOL], bf16x8 (&Bl)[NCOL]) { split_rows(row, 32 * s + 8 * g, D, vec, Bh, Bl); }
+};
+
+// Observe -> act (mdr_env_tarmac_actor_sample): the floats are read from the wave's LDS window (ObserveWindow, mdr_tarmac_mlp.h)
+// instead of observation rows, as ObserveSource of mdr_tarmac_mlp.hip does for the fp32 form.  A tile is 32 consecutive agents -
+// column block c holds the tile rows 16 c + r - staged as k_actor_observe_bf16 (mdr_policy.hip) stages its tiles of 32; element j of
+// lane group g in k-step s is normStateDict feature n = 32 s + 8 g + j, and an explicit zero from n = 51 on, as split_rows builds it.
+// Row stride: TARMAC_OBS_ROW = 60 for the same 4-byte reads of one column of 16 consecutive rows.  8 windows of 7680 bytes beside
+// ~95 KB of fragments: 158 KB with the row table.
+// OVERLAP: the loads of the next tile are issued before the tile's matrix work; its rows are staged once both k-steps have been
+// split.  The general form has no registers left to carry them, or the next tile's features, across the layers (it spills with
+// them): it loads and stages at the tile's end and reads its features when the tile starts.
+template <bool OVERLAP, bool STORE, bool GEN>
+struct ObserveSource : ObserveWindow<16 * NCOL, STORE, GEN> {
+  using W = ObserveWindow<16 * NCOL, STORE, GEN>;
+  static constexpr bool WINDOWS = true;
+  static constexpr int TILE = 16 * NCOL;
+  float xr[NCOL][16];      // element j of k-step s: [8 s + j]
+
+  __device__ __forceinline__ ObserveSource(int64_t A, int64_t ntiles, const WindowArgs& x) : W{x.o, x.rows_out, A, ntiles} {}
+
+  __device__ __forceinline__ void gather(int64_t first_agent) {
+    const int g = this->lane0 >> 4, r = this->lane0 & 15;
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) this->lockout_quotients(16 * c + r, g);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    this->store_rows(first_agent);
+  }
+  __device__ __forceinline__ void feats() {
+    const int g = this->lane0 >> 4, r = this->lane0 & 15;
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) {
+      const float* row = this->rows + (16 * c + r) * W::ROW;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int n = 32 * (k >> 3) + 8 * g + (k & 7);
+        const float v = row[W::at(min(n, 50))];
+        xr[c][k] = n < 51 ? v : 0.0f;
+      }
+    }
+  }
+  __device__ __forceinline__ void prime(int64_t wave, int64_t nwaves) {
+    this->start(wave, nwaves);
+    if (wave < this->ntiles) {
+      this->load(wave * TILE);
+      this->stage_rows();
+      observe_window_fence();
+      gather(wave * TILE);
+      if (OVERLAP) feats();
+    }
+  }
+  __device__ __forceinline__ void begin(int64_t t, const Tile&, const float*, int64_t, int, int) {
+    if (!OVERLAP) feats();
+    this->advance(t);
+    if (OVERLAP && this->more) this->load(this->next_tile * TILE);
+  }
+  __device__ __forceinline__ void operands(int s, int, bf16x8 (&Bh)[NCOL], bf16x8 (&Bl)[NCOL]) {
+    float v[NCOL][8];
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[c][j] = xr[c][8 * s + j];
+    split_cols(v, Bh, Bl);
+  }
+  __device__ __forceinline__ void after_layer1() {      // the window is free for the next tile's rows
+    if (OVERLAP && this->more) this->stage_rows();
+  }
+  __device__ __forceinline__ void end() {
+    if (this->more) {
+      if (!OVERLAP) {
+        this->load(this->next_tile * TILE);
+        this->stage_rows();
+      }
+      observe_window_fence();
+      gather(this->next_tile * TILE);
+      if (OVERLAP) feats();
+    }
+  }
+};
+
+// obs2hidden on the source's floats, x -> cat, the projections -> qkv.  The observe source runs with as many of the form's waves as
+// its windows leave room for.
+// frag_encode: obs2hidden.0 [S0 = ceil(F / 32) k-steps fed from the obs row][mbh pairs], then obs2hidden.2 [ceil(mbh / 2)][mbh]
+template <int MBH, int MBV, bool EXACT, class Source, class... SourceArgs>
+__global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_bf16(MlpArgs a, SourceArgs... x) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int TILE = 16 * NCOL, ROW = TARMAC_OBS_ROW, WIN = TILE * ROW;
-  constexpr bool OVERLAP = EXACT;
-  float* fa = lds;
-  float* fp = fa + a.na;
-  float* vec = fp + a.np;
-  const int tid = threadIdx.x;
-  const int NW = (int)(blockDim.x >> 6);      // as many of the form's waves as the windows leave room for
-  float* rows = vec + a.nvec + (tid >> 6) * WIN;
-  uint16_t* table = reinterpret_cast<uint16_t*>(vec + a.nvec + NW * WIN);      // [TILE * 51] (only when rows are stored)
-  stage(fa, a.fa, a.na, tid);
-  if (a.with_comm) stage(fp, a.fp, a.np, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  for (int i = lane0; i < WIN; i += 64) rows[i] = 0.0f;
-  if (STORE) observe_build_table<TILE, ROW>(table, tid, 64 * NW);
-  __syncthreads();
-  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
-  const uint4* fp4 = reinterpret_cast<const uint4*>(fp);
+  Source src(a.A, a.ntiles, x...);
+  const int nw = Source::WINDOWS ? (int)(blockDim.x >> 6) : WAVES_BF16;
+  const Staged S = stage_weights(lds, Fragments{a.fa, a.fp, a.vec, a.na, a.np, a.nvec}, a.with_comm != 0, nw,
+                                 [&]() { src.carve(lds + a.na + a.np + a.nvec, nw); });
+  src.prime(S.wave, S.nwaves);
+  const float* vec = S.vec;
+  const uint4* fa4 = reinterpret_cast<const uint4*>(S.fa);
+  const uint4* fp4 = reinterpret_cast<const uint4*>(S.fp);
   const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv;
   constexpr int SH = (MBH + 1) / 2;
   const int sh = EXACT ? SH : ksteps_regs(mbh);
   const VecLayout L = vec_layout(mbh, mbv, a.mbm);
-  const int64_t wave = (int64_t)blockIdx.x * NW + (tid >> 6), nwaves = (int64_t)gridDim.x * NW;
   const uint4* f2 = fa4 + a.S0 * mbh * 128;
-  const double* sig_row = observe_sig_row(o);
-  TileCursor tc;
-  tc.init(wave * TILE, nwaves * TILE, o.N);
-  float xr[NCOL][16];      // element j of k-step s: [8 s + j]
-  auto gather = [&](int64_t first_agent) {
-    const int g = lane0 >> 4;
-#pragma unroll
-    for (int c = 0; c < NCOL; ++c) {      // the senders' seconds_since_off by the RECEIVER's lockout, in place (k_tarmac_encode_obs)
-      float* row = rows + (16 * c + r) * ROW;
-      const float lock = row[4 * OBS_C + 11], y = row[4 * OBS_C + 12];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int m = g + 4 * i;
-        if (m < OBS_C) row[4 * m + 1] = mdr::div_by_lockout(row[4 * m + 1], lock, y);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (STORE)
-      observe_store_rows<TILE>(rows, table, rows_out + first_agent * 51, lane0,
-                               GEN ? (int)((a.A - first_agent) < (int64_t)TILE ? (a.A - first_agent) : (int64_t)TILE) : TILE);
-  };
-  auto feats = [&]() {
-    const int g = lane0 >> 4;
-#pragma unroll
-    for (int c = 0; c < NCOL; ++c) {
-      const float* row = rows + (16 * c + r) * ROW;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int n = 32 * (k >> 3) + 8 * g + (k & 7);
-        const int nc = min(n, 50);
-        const float v = row[nc < 11 ? 4 * OBS_C + nc : nc - 11];
-        xr[c][k] = n < 51 ? v : 0.0f;
-      }
-    }
-  };
-  SegSlot slot{};
-  if (wave < a.ntiles) {
-    if (GEN) {
-      const HouseRegs first = observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, wave * TILE, a.A, lane0, slot);
-      observe_stage_gen<false, ROW>(o, first, slot, rows);
-    } else {
-      const HouseRegs first = observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
-      observe_stage<TILE, false, ROW>(o, first, rows, lane0);
-    }
-    observe_window_fence();
-    gather(wave * TILE);
-    if (OVERLAP) feats();
-  }
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const Tile T = tile_of(t, r, a.A);
-    if (!OVERLAP) feats();
+  for (int64_t t = S.wave; t < a.ntiles; t += S.nwaves) {
+    const int lane = tile_local(S.lane0), g = lane >> 4;
+    const Tile T = tile_of(t, S.r, a.A);
+    src.begin(t, T, a.in0, a.ld0, a.D0, a.vec0);
     float* cat_row[NCOL];
     float* qkv_row[NCOL];
 #pragma unroll
@@ -325,55 +308,27 @@ __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_obs_bf16(MlpA
       cat_row[c] = a.cat + T.ac[c] * a.ldcat;
       qkv_row[c] = a.qkv + T.ac[c] * a.ldqkv;
     }
-    const bool more = t + nwaves < a.ntiles;
-    tc.next();
-    HouseRegs nxt{};
-    auto load_next = [&]() {
-      nxt = GEN ? observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, (t + nwaves) * TILE, a.A, lane0, slot) : observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
-    };
-    auto stage_next = [&]() {
-      if (GEN) observe_stage_gen<false, ROW>(o, nxt, slot, rows);
-      else observe_stage<TILE, false, ROW>(o, nxt, rows, lane0);
-    };
-    if (OVERLAP && more) load_next();
-    f32x4 t1[NCOL][MBH], x[NCOL][MBH];
+    f32x4 t1[NCOL][MBH], x1[NCOL][MBH];
     init_bias<MBH>(vec + L.o1, g, mbh, t1);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
       if (s < a.S0) {
         bf16x8 Bh[NCOL], Bl[NCOL];
-#pragma unroll
-        for (int c = 0; c < NCOL; ++c) {
-          float v[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = xr[c][8 * s + j];
-          uint4 bh, bl;
-          split8(v, bh, bl);
-          Bh[c] = __builtin_bit_cast(bf16x8, bh);
-          Bl[c] = __builtin_bit_cast(bf16x8, bl);
-        }
+        src.operands(s, g, Bh, Bl);
         mma_step<MBH, EXACT>(fa4 + s * mbh * 128, mbh, lane, Bh, Bl, t1);
       }
-    if (OVERLAP && more) stage_next();      // the features are split and in the MFMA pipeline: the window is free for the next tile's rows
-    init_bias<MBH>(vec + L.o2, g, mbh, x);
+    src.after_layer1();
+    init_bias<MBH>(vec + L.o2, g, mbh, x1);
 #pragma unroll
     for (int s = 0; s < SH; ++s)
       if (EXACT || s < sh) {
         bf16x8 Bh[NCOL], Bl[NCOL];
         split_regs<MBH, ACT_RELU>(t1, s, Bh, Bl);
-        mma_step<MBH, EXACT>(f2 + s * mbh * 128, mbh, lane, Bh, Bl, x);
+        mma_step<MBH, EXACT>(f2 + s * mbh * 128, mbh, lane, Bh, Bl, x1);
       }
-    store_blocks<MBH>(x, cat_row, T.valid, a.H, g);
-    if (a.with_comm) projections<MBH, MBV, EXACT>(fp4, vec, L, x, mbh, mbv, a.K, a.V, qkv_row, T.valid, lane);
-    if (more) {
-      if (!OVERLAP) {
-        load_next();
-        stage_next();
-      }
-      observe_window_fence();
-      gather((t + nwaves) * TILE);
-      if (OVERLAP) feats();
-    }
+    store_blocks<MBH>(x1, cat_row, T.valid, a.H, g);
+    if (a.with_comm) projections<MBH, MBV, EXACT>(fp4, vec, L, x1, mbh, mbv, a.K, a.V, qkv_row, T.valid, lane);
+    src.end();
   }
 }
 
@@ -382,27 +337,19 @@ __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_encode_obs_bf16(MlpA
 template <int MBH, int MBV, int MBM, bool EXACT>
 __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_rehop_bf16(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* fa = lds;
-  float* fp = fa + a.na;
-  float* vec = fp + a.np;
-  const int tid = threadIdx.x;
-  stage(fa, a.fa, a.na, tid);
-  stage(fp, a.fp, a.np, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  __syncthreads();
-  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
-  const uint4* fp4 = reinterpret_cast<const uint4*>(fp);
+  const Staged S = stage_weights(lds, Fragments{a.fa, a.fp, a.vec, a.na, a.np, a.nvec}, true, WAVES_BF16);
+  const float* vec = S.vec;
+  const uint4* fa4 = reinterpret_cast<const uint4*>(S.fa);
+  const uint4* fp4 = reinterpret_cast<const uint4*>(S.fp);
   const int mbh = EXACT ? MBH : a.mbh, mbv = EXACT ? MBV : a.mbv, mbm = EXACT ? MBM : a.mbm;
   constexpr int SM = (MBM + 1) / 2;
   const int sm = EXACT ? SM : ksteps_regs(mbm);
   const VecLayout L = vec_layout(mbh, mbv, mbm);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  const int64_t wave = (int64_t)blockIdx.x * WAVES_BF16 + (tid >> 6), nwaves = (int64_t)gridDim.x * WAVES_BF16;
   const uint4* f1h = fa4 + a.S0 * mbm * 128;
   const uint4* f2 = f1h + a.S1 * mbm * 128;
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const Tile T = tile_of(t, r, a.A);
+  for (int64_t t = S.wave; t < a.ntiles; t += S.nwaves) {
+    const int lane = tile_local(S.lane0), g = lane >> 4;
+    const Tile T = tile_of(t, S.r, a.A);
     const float* rc[NCOL];
     const float* rh[NCOL];
     float* st_row[NCOL];
@@ -445,21 +392,16 @@ __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_rehop_bf16(MlpArgs a
 template <int MBH, bool EXACT>
 __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_head_bf16(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* fa = lds;
-  float* vec = fa + a.na;
-  const int tid = threadIdx.x;
-  stage(fa, a.fa, a.na, tid);
-  stage(vec, a.vec, a.nvec, tid);
-  __syncthreads();
-  const uint4* fa4 = reinterpret_cast<const uint4*>(fa);
+  const Staged S = stage_weights(lds, Fragments{a.fa, nullptr, a.vec, a.na, 0, a.nvec}, false, WAVES_BF16);
+  const float* vec = S.vec;
+  const uint4* fa4 = reinterpret_cast<const uint4*>(S.fa);
   const int mbh = EXACT ? MBH : a.mbh;
   const VecLayout L = vec_layout(mbh, a.mbv, a.mbm);
-  const int lane0 = tid & 63, r = lane0 & 15;
-  const int64_t wave = (int64_t)blockIdx.x * WAVES_BF16 + (tid >> 6), nwaves = (int64_t)gridDim.x * WAVES_BF16;
   const float bias3 = vec[L.b3];
-  for (int64_t t = wave; t < a.ntiles; t += nwaves) {
-    const int lane = tile_local(lane0), g = lane >> 4;
-    const Tile T = tile_of(t, r, a.A);
+  const DrawArgs draw{a.action, a.a_prob, a.probs, a.greedy, a.k0, a.k1, a.step_lo, a.step_hi, a.step_dev};
+  for (int64_t t = S.wave; t < a.ntiles; t += S.nwaves) {
+    const int lane = tile_local(S.lane0), g = lane >> 4;
+    const Tile T = tile_of(t, S.r, a.A);
     const float* row[NCOL];
 #pragma unroll
     for (int c = 0; c < NCOL; ++c) row[c] = a.in0 + T.ac[c] * a.ld0;
@@ -473,39 +415,39 @@ __global__ __launch_bounds__(64 * WAVES_BF16) void k_tarmac_head_bf16(MlpArgs a)
         mma_step<MBH, EXACT>(fa4 + s * mbh * 128, mbh, lane, Bh, Bl, acc);
       }
 #pragma unroll
-    for (int c = 0; c < NCOL; ++c) {      // the last layer, the softmax and the draw: the fp32 form's vector code
-      float d = 0.0f;
+    for (int c = 0; c < NCOL; ++c) {
+      f32x4 col[MBH];      // a copy the compiler sees through: acc itself stays out of the helper's hands and in separate registers
 #pragma unroll
-      for (int mb = 0; mb < MBH; ++mb)
-        if (EXACT || mb < mbh) {
-          const f32x4 w = *reinterpret_cast<const f32x4*>(vec + L.wd + 16 * mb + 4 * g);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) d = fmaf(w[i], relu(acc[c][mb][i]), d);
-        }
-      d += __shfl_xor(d, 16);
-      d += __shfl_xor(d, 32);
-      d += bias3;
-      const float p0 = 1.0f / (1.0f + expf(-d));      // mdr_logits_sample's softmax over two logits
-      const float p1 = 1.0f / (1.0f + expf(d));
-      if (g == 0 && T.valid[c]) {
-        const int64_t agent = T.agent[c];
-        int act;
-        if (a.greedy) {
-          act = d >= 0.0f ? 0 : 1;      // argmax keeps the first maximum, as torch.argmax
-        } else {
-          const float u = action_uniform(mdr::action_word(agent, a.step_lo, a.step_hi, a.step_dev, a.k0, a.k1));
-          act = u < p0 ? 0 : 1;
-        }
-        a.action[agent] = (uint8_t)act;
-        if (a.a_prob) a.a_prob[agent] = act ? p1 : p0;
-        if (a.probs) {
-          a.probs[agent * 2] = p0;
-          a.probs[agent * 2 + 1] = p1;
-        }
-      }
+      for (int mb = 0; mb < MBH; ++mb) col[mb] = acc[c][mb];
+      head_finish<MBH, EXACT>(col, vec, L, mbh, g, bias3, draw, T.agent[c], T.valid[c]);
     }
   }
 }
+
+struct Bf16Forms : FragWords {
+  static constexpr int TILE = 16 * NCOL;
+  static int waves(bool) { return WAVES_BF16; }
+  static int row_steps(int n) { return ksteps_rows(n); }
+  static int whole_vectors(int, int D) { return D % 4 == 0; }
+  static bool head_exact(int mbh, int) { return mbh == 4; }
+  static MlpKernel encode_kernel(bool exact) {
+    return exact ? k_tarmac_encode_bf16<4, 1, true, RowsSource> : k_tarmac_encode_bf16<4, 2, false, RowsSource>;
+  }
+  template <bool EXACT, bool STORE, bool GEN>
+  static MlpObserveKernel observe_form() {
+    return k_tarmac_encode_bf16<4, EXACT ? 1 : 2, EXACT, ObserveSource<EXACT, STORE, GEN>, WindowArgs>;
+  }
+  template <bool EXACT>
+  static MlpObserveKernel observe_form(bool store, bool gen) {
+    return store ? (gen ? observe_form<EXACT, true, true>() : observe_form<EXACT, true, false>())
+                 : (gen ? observe_form<EXACT, false, true>() : observe_form<EXACT, false, false>());
+  }
+  static MlpObserveKernel encode_observe_kernel(bool exact, bool store, bool gen) {
+    return exact ? observe_form<true>(store, gen) : observe_form<false>(store, gen);
+  }
+  static MlpKernel rehop_kernel(bool exact) { return exact ? k_tarmac_rehop_bf16<4, 1, 5, true> : k_tarmac_rehop_bf16<4, 2, 6, false>; }
+  static MlpKernel head_kernel(bool exact) { return exact ? k_tarmac_head_bf16<4, true> : k_tarmac_head_bf16<4, false>; }
+};
 
 }  // namespace
 
@@ -514,70 +456,7 @@ namespace mdr {
 int tarmac_sample_bf16(const mdr_tarmac_actor_t* actor, const float* obs, const ObserveArgs* o, float* rows_out, int32_t nb_envs, int32_t nb_houses,
                        uint64_t seed, uint64_t step, const int32_t* step_dev, void* workspace, uint8_t* action, float* a_prob, float* probs, int cus,
                        void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int F = actor->num_state, H = actor->hidden, K = actor->num_key, V = actor->num_value;
-  const int hops = actor->num_hops, wc = actor->with_comm != 0;
-  const int64_t A = (int64_t)nb_envs * nb_houses;
-  const int mbh = blocks(H), mbv = blocks(V), mbm = blocks(H + V);
-  const VecLayout L = vec_layout(mbh, mbv, mbm);
-  const bool exact = mbh == 4 && mbv == 1 && (!wc || hops == 1 || mbm == 5);
-  const int64_t ldcat = wc ? H + V : H, ldqkv = K + K + V;
-  float* cat = static_cast<float*>(workspace);
-  float* qkv = cat + A * ldcat;
-  float* state = qkv + A * ldqkv;
-
-  MlpArgs a{};
-  a.vec = actor->vec, a.nvec = L.total;
-  a.cat = cat, a.qkv = qkv, a.state = state, a.ldcat = ldcat, a.ldqkv = ldqkv;
-  a.action = action, a.a_prob = a_prob, a.probs = probs;
-  a.A = A, a.ntiles = (A + 16 * NCOL - 1) / (16 * NCOL);
-  a.H = H, a.K = K, a.V = V, a.mbh = mbh, a.mbv = mbv, a.mbm = mbm;
-  a.with_comm = wc, a.greedy = actor->greedy != 0;
-  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.step_lo = (uint32_t)step, a.step_hi = (uint32_t)(step >> 32);
-  a.step_dev = step_dev;
-  a.np = wc ? (int)proj_words(H, V) : 0;
-
-  // ---- obs -> x (-> qkv)
-  a.fa = actor->frag_encode, a.fp = actor->frag_proj, a.na = (int)encode_words(F, H);
-  a.in0 = obs, a.ld0 = F, a.D0 = F, a.S0 = ksteps_rows(F);
-  a.vec0 = F % 4 == 0 && aligned16(obs);
-  int rc;
-  if (o) {      // the same layers on features built in LDS: whole-tile staging where no tile of 32 leaves its env
-    const bool gen = o->N % (16 * NCOL) != 0;
-#define MDR_TARMAC_OBS(...)                                                                                                                    \
-  (rows_out ? (gen ? launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, true, true>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s)        \
-                   : launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, true, false>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s))      \
-            : (gen ? launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, false, true>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s)       \
-                   : launch_observe(k_tarmac_encode_obs_bf16<__VA_ARGS__, false, false>, WAVES_BF16, 16 * NCOL, a, *o, rows_out, cus, s)))
-    rc = exact ? MDR_TARMAC_OBS(4, 1, true) : MDR_TARMAC_OBS(4, 2, false);
-#undef MDR_TARMAC_OBS
-  } else {
-    rc = exact ? launch(k_tarmac_encode_bf16<4, 1, true>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s)
-               : launch(k_tarmac_encode_bf16<4, 2, false>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s);
-  }
-  if (rc != MDR_OK) return rc;
-  if (wc) {
-    for (int hop = 0; hop < hops; ++hop) {
-      if (hop > 0) {      // [comm, h] -> h' -> qkv
-        a.fa = actor->frag_msg, a.na = (int)msg_words(H, V);
-        a.in0 = cat + H, a.ld0 = ldcat, a.D0 = V, a.S0 = ksteps_rows(V);
-        a.in1 = hop == 1 ? cat : state, a.ld1 = hop == 1 ? ldcat : H, a.S1 = ksteps_rows(H);
-        a.vec0 = a.vec1 = 1;      // H, V and both leading dimensions are multiples of 4 floats, the workspace is 16-byte aligned
-        rc = exact ? launch(k_tarmac_rehop_bf16<4, 1, 5, true>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s)
-                   : launch(k_tarmac_rehop_bf16<4, 2, 6, false>, WAVES_BF16, a, a.na + a.np + a.nvec, cus, s);
-        if (rc != MDR_OK) return rc;
-      }
-      rc = mdr_tarmac_comm(qkv, ldqkv, qkv + K, ldqkv, qkv + 2 * K, ldqkv, nb_envs, nb_houses, K, V, actor->nb_comm, actor->mode, actor->defect_prob,
-                           seed, step, step_dev, hop, cat + H, ldcat, stream);
-      if (rc != MDR_OK) return rc;
-    }
-  }
-  // ---- [x, comm] -> logits -> action
-  a.fa = actor->frag_head, a.na = (int)head_words(H, V, wc);
-  a.in0 = cat, a.ld0 = ldcat, a.D0 = (int)ldcat, a.S0 = ksteps_rows((int)ldcat);
-  a.vec0 = 1;
-  return mbh == 4 ? launch(k_tarmac_head_bf16<4, true>, WAVES_BF16, a, a.na + a.nvec, cus, s)
-                  : launch(k_tarmac_head_bf16<4, false>, WAVES_BF16, a, a.na + a.nvec, cus, s);
+  return run_chain<Bf16Forms>(actor, obs, o, rows_out, nb_envs, nb_houses, seed, step, step_dev, workspace, action, a_prob, probs, cus, stream);
 }
 
 }  // namespace mdr
