@@ -358,6 +358,85 @@ int mdr_ppo_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_
                         const float *target, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
                         float *advantage, void *stream);
 
+/* ---- TarMAC-PPO's update step for the actor (TarmacPPO.update, agents/tarmac_ppo.py:168-186): loss and gradient of one minibatch.
+ *
+ * The actor's weights in torch's own layout - every layer w[out][in] contiguous and its bias, device memory, read as they are on
+ * every call (the optimiser changes them between any two calls: no fragments, nothing to repack).  Activations as the reference:
+ * ReLU inside obs2hidden and the head, tanh inside the three projections.  Limits (mdr_tarmac_actor_t's): F <= 64, H a multiple of
+ * 4 <= 64, K a multiple of 4 <= 16, V a multiple of 4 <= 32, c = min(nb_comm, nb_houses - 1) <= 64, modes MDR_TARMAC_NEIGHBOURS
+ * and MDR_TARMAC_NONE, num_hops == 1 (comm.msg_state2state is not evaluated).  with_comm == 0: obs2hidden -> hidden2action; K, V,
+ * nb_comm, mode, defect_prob and the six projection layers are ignored (their pointers may be NULL). */
+typedef struct mdr_tarmac_net {
+  uint32_t struct_size;
+  int32_t num_state;   /* F */
+  int32_t hidden;      /* H */
+  int32_t num_key;     /* K */
+  int32_t num_value;   /* V */
+  int32_t nb_comm;     /* number_agents_comm before the clamp to nb_houses - 1 */
+  int32_t mode;        /* mdr_tarmac_mode */
+  int32_t num_hops;    /* 1; anything else is MDR_ERR_UNSUPPORTED */
+  int32_t with_comm;   /* 0 or 1 */
+  float defect_prob;   /* comm_defect_prob, drawn as mdr_tarmac_comm documents */
+  const float *encode_w0, *encode_b0, *encode_w2, *encode_b2; /* obs2hidden.0 [H][F], obs2hidden.2 [H][H] */
+  const float *head_w0, *head_b0, *head_w2, *head_b2;         /* comm_hidden2action.0 [H][H + V] (columns: x, then comm), .2 [2][H];
+                                                                  with_comm == 0: hidden2action.0 [H][H], .2 [2][H] */
+  const float *key_w0, *key_b0, *key_w2, *key_b2;             /* comm.hidden2key.0 [H][H], .2 [K][H] */
+  const float *value_w0, *value_b0, *value_w2, *value_b2;     /* comm.hidden2value.0 [H][H], .2 [V][H] */
+  const float *query_w0, *query_b0, *query_w2, *query_b2;     /* comm.hidden2query.0 [H][H], .2 [K][H] */
+} mdr_tarmac_net_t;
+
+/* Floats of the flat gradient: the order of TarMACActor.parameters() (the reference's module order, network.py:201-222) restricted
+ * to the tensors a one-hop evaluation reaches, each in torch's layout -
+ *   obs2hidden.0.weight [H][F] | .0.bias [H] | .2.weight [H][H] | .2.bias [H]
+ *   | comm_hidden2action.0.weight [H][H + V] | .0.bias [H] | .2.weight [2][H] | .2.bias [2]
+ *   | comm.hidden2key.0.weight [H][H] | .0.bias [H] | .2.weight [K][H] | .2.bias [K]
+ *   | comm.hidden2value.0.weight [H][H] | .0.bias [H] | .2.weight [V][H] | .2.bias [V]
+ *   | comm.hidden2query.0.weight [H][H] | .0.bias [H] | .2.weight [K][H] | .2.bias [K]
+ * comm.msg_state2state.* follows them in parameters() and is NOT part of it (one hop never evaluates it: autograd leaves its .grad
+ * None).  with_comm == 0: obs2hidden's four, then hidden2action.0.weight [H][H] | .0.bias | .2.weight [2][H] | .2.bias [2].
+ * Reads the shape fields, num_hops and with_comm only; host-only.  -1: a shape outside the limits, num_hops != 1, a struct_size
+ * that is not this header's. */
+int64_t mdr_tarmac_net_grad_floats(const mdr_tarmac_net_t *net);
+
+/* Bytes of device scratch one gradient call over nb_rows env-steps of nb_houses agents (A = nb_rows * nb_houses) needs, in this
+ * order, every part 16-byte aligned: one partial gradient (and loss) per tile slot - 2 slots per workgroup of the grid
+ * min(ceil(A / 32), max_workgroups), with max_workgroups == 0 enough for the library's own grid on any device - | the head's input
+ * [x | comm] [A][H + V] | d[x | comm] [A][H + V] | packed q | k | v [A][2 K + V] | packed dq | dk | dv [A][2 K + V] | the attention
+ * backward's statistics, mdr_tarmac_comm_backward_workspace_bytes(A, K, V), reserved inside: there is ONE workspace pointer.
+ * with_comm == 0: the partials | x [A][H] | dx [A][H].  Host-only.  -1 as above, or nb_rows < 0, nb_houses <= 0, max_workgroups < 0,
+ * A >= 2^31 - 16. */
+int64_t mdr_tarmac_ppo_workspace_bytes(const mdr_tarmac_net_t *net, int64_t nb_rows, int32_t nb_houses, int32_t max_workgroups);
+
+/* The clipped surrogate of agents/tarmac_ppo.py:168-182 and its gradient.  Minibatch row i < nb_rows is the stored env-step
+ * j = index ? index[i] : i (`index` device int64, may be NULL); its N = nb_houses agents are rows j * N + n of `state` (F floats each,
+ * ld_state >= F), of `action` (int64, nonzero = action 1) and of `old_prob` (the stored probability of the taken action) -
+ * whole-buffer arrays read in place through `index`; `advantage` float [nb_rows][N] in minibatch order.
+ * p = softmax(actor(state_j)) - the row's N agents attend to each other -, ratio_in = p_n[action] / old_prob,
+ *   loss = -(1 / (nb_rows N)) sum_in min(ratio_in A_in, clamp(ratio_in, 1 - clip_param, 1 + clip_param) A_in)
+ * and `grad` (mdr_tarmac_net_grad_floats floats) = d loss / d parameters as torch's autograd takes it: d loss / d ratio =
+ * -A / (nb_rows N) where 1 - clip <= ratio <= 1 + clip (bounds included) or ratio A < clamp(ratio) A, else 0; relu'(z) = 1 iff
+ * z > 0.  old_prob = 0 gives inf / NaN as in the reference.  `loss`: one float on the device.  `ratio` (may be NULL): float
+ * [nb_rows][N].  Dead senders (defect_prob > 0): minibatch row i stands for the env in the Philox key of mdr_tarmac_comm, the forward
+ * and the backward attention of one call use the same (seed, step, hop 0) - the evaluation TarMACActor.forward(state[index], seed =
+ * seed, step = step, differentiable = True) makes.
+ * Exact fp32 on v_mfma_f32_16x16x4_f32, no library GEMM.  The chain (csrc/mdr_tarmac_ppo_grad.hip): obs2hidden forward, projections
+ * forward, mdr_tarmac_comm, the head's forward + loss + backward, mdr_tarmac_comm_backward, projections backward (tanh recomputed
+ * from x), obs2hidden backward (relu recomputed from the observation rows), one reduction; without communication obs2hidden
+ * forward, head, obs2hidden backward, reduction.  Every compute kernel runs on the same persistent grid of min(ceil(A / 32),
+ * max_workgroups) workgroups (0: the library's choice, min(.., compute units, 512)), each leaving two partial gradients in
+ * `workspace`; the reduction adds them in slot order and divides by nb_rows N: no floating-point atomics, the same inputs and the
+ * same max_workgroups give the same bits on every call.  Every float of `grad`, `loss` and `ratio` is written by every successful
+ * call; nb_rows == 0 writes zeros to `grad` and `loss`.  Stream-ordered, never synchronises, allocates nothing; `workspace`:
+ * 16-byte aligned device memory of mdr_tarmac_ppo_workspace_bytes, owned by the caller, its contents free before and after.
+ * Returns 0; -1 (a NULL required pointer, ld_state < F, nb_rows < 0, nb_houses <= 0, nb_comm < 0, max_workgroups < 0, clip_param
+ * outside [0, 1), defect_prob outside [0, 1], a struct_size that is not this header's, a missing or misaligned workspace); -3 (HIP
+ * error); -4 (a shape outside the limits, another mode, num_hops != 1, c > 64, A >= 2^31 - 16).  On -1 and -4 nothing was launched
+ * and nothing written. */
+int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t *net, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                              int32_t nb_houses, const int64_t *action, const float *old_prob, const float *advantage, float clip_param,
+                              uint64_t seed, uint64_t step, int32_t max_workgroups, void *workspace, float *grad, float *loss,
+                              float *ratio, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

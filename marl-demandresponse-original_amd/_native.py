@@ -139,6 +139,18 @@ class MdrMlp(C.Structure):
     ]
 
 
+class MdrTarmacNet(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("num_state", C.c_int32), ("hidden", C.c_int32), ("num_key", C.c_int32), ("num_value", C.c_int32),
+        ("nb_comm", C.c_int32), ("mode", C.c_int32), ("num_hops", C.c_int32), ("with_comm", C.c_int32), ("defect_prob", C.c_float),
+        ("encode_w0", _f32p), ("encode_b0", _f32p), ("encode_w2", _f32p), ("encode_b2", _f32p),
+        ("head_w0", _f32p), ("head_b0", _f32p), ("head_w2", _f32p), ("head_b2", _f32p),
+        ("key_w0", _f32p), ("key_b0", _f32p), ("key_w2", _f32p), ("key_b2", _f32p),
+        ("value_w0", _f32p), ("value_b0", _f32p), ("value_w2", _f32p), ("value_b2", _f32p),
+        ("query_w0", _f32p), ("query_b0", _f32p), ("query_w2", _f32p), ("query_b2", _f32p),
+    ]
+
+
 OBS_PLANES, OBS_ROWS = 0, 1
 
 EXPORTS = (
@@ -159,6 +171,7 @@ EXPORTS = (
     "mdr_tarmac_vec_floats", "mdr_tarmac_frag_words", "mdr_tarmac_actor_workspace_bytes", "mdr_tarmac_actor_sample",
     "mdr_env_tarmac_actor_sample",
     "mdr_mlp_grad_floats", "mdr_mlp_grad_workspace_bytes", "mdr_ppo_actor_grad", "mdr_ppo_critic_grad",
+    "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
 )
 
 _lib = None
@@ -254,6 +267,10 @@ def load():
         "mdr_mlp_grad_workspace_bytes": (i64, [C.POINTER(MdrMlp), i64, i32]),
         "mdr_ppo_actor_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp]),
         "mdr_ppo_critic_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "mdr_tarmac_net_grad_floats": (i64, [C.POINTER(MdrTarmacNet)]),
+        "mdr_tarmac_ppo_workspace_bytes": (i64, [C.POINTER(MdrTarmacNet), i64, i32, i32]),
+        "mdr_tarmac_ppo_actor_grad": (C.c_int, [C.POINTER(MdrTarmacNet), vp, i64, vp, i64, i32, vp, vp, vp, C.c_float, u64, u64, i32, vp, vp, vp,
+                                                vp, vp]),
         "mdr_env_pack": (C.c_int, [vp, i32, vp, vp]),
         "mdr_env_graph_room": (i64, [vp]),
         "mdr_env_graph_replayed": (C.c_int, [vp, i64, vp]),

@@ -34,6 +34,7 @@
 
 #include "../../include/mdr.h"
 #include "../../include/mdr_policy.h"
+#include "mdr_grad_reduce.h"
 
 namespace {
 
@@ -403,16 +404,7 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
   }
 }
 
-// grad[i] = (sum over the partials in workgroup order) / B, the loss behind it; no partials (B == 0): zeros
-__global__ void k_ppo_grad_reduce(const float* part, int nparts, int stride, int G, float denom, float* grad, float* loss) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > G) return;
-  float sum = 0.0f;
-  for (int p = 0; p < nparts; ++p) sum += part[(int64_t)p * stride + i];
-  const float v = nparts > 0 ? sum / denom : 0.0f;
-  if (i < G) grad[i] = v;
-  else *loss = v;
-}
+// k_ppo_grad_reduce (mdr_grad_reduce.h): grad = (sum over the partials in workgroup order) / B, the loss behind it; B == 0: zeros
 
 bool net_fields_ok(const mdr_mlp_t* n) {
   return n && n->struct_size == sizeof(mdr_mlp_t) && n->num_state > 0 && n->hidden1 > 0 && n->hidden2 > 0 && n->num_out > 0;

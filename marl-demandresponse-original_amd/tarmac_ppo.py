@@ -1,0 +1,250 @@
+"""TarMAC-PPO's update step on the GPU (include/mdr_policy.h: mdr_tarmac_ppo_actor_grad).
+
+The other half of the reference's train_tarmacPPO.py: ``TarmacPPO.update`` (agents/tarmac_ppo.py:152-207) on the transitions
+``collect_tarmac_rollout`` leaves on the device.  Per minibatch of stored env-steps the reference evaluates the centralised critic and
+the TarMAC actor, forms the value loss and the clipped surrogate, calls ``backward()`` twice, clips both gradients and takes two
+Adam steps - the actor's before the critic's.  ``actor_loss_backward`` is the actor's forward, loss and backward as hand-written HIP
+kernels on the matrix cores in exact fp32 around the two banded-attention kernels (csrc/mdr_tarmac_ppo_grad.hip, no library GEMM);
+it fills the ``.grad`` of a one-hop ``TarMACActor``.  torch keeps the gradient clipping, the optimisers and the critic.
+``TarMACPPOLearner`` is the loop.  Nothing on the call path synchronises with the host.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _native as nat
+from .ppo import PPOLearner, _workspace
+from .tarmac import FUSED_MAX_HIDDEN, FUSED_MAX_KEY, FUSED_MAX_OBS, FUSED_MAX_VALUE, MAX_COMM, MODES, TarMACActor
+
+# backend="auto": the kernels from this many env-steps per minibatch on (profiles/tarmac_ppo_README.md: they measured faster than
+# forward(differentiable=True) + backward() at every size tried, the reference's 256 x 20 included)
+AUTO_MIN_ENV_STEPS = 1
+
+
+def _head(actor):
+    return actor.comm_hidden2action if actor.with_comm else actor.hidden2action
+
+
+def _refusal(actor, nb_houses: Optional[int] = None) -> Optional[str]:
+    """Why the kernels do not take ``actor`` (None: they do)."""
+    if not isinstance(actor, TarMACActor):
+        return "the kernels cover a TarMACActor"
+    if actor.num_hops != 1:
+        return "num_hops = %d: the kernels cover one hop (forward(differentiable=True) covers more)" % actor.num_hops
+    if actor.num_action != 2:
+        return "the kernels cover two actions"
+    F_, H = actor.num_obs, actor.hidden
+    if not 1 <= F_ <= FUSED_MAX_OBS:
+        return "num_obs = %d: the kernels cover at most %d features" % (F_, FUSED_MAX_OBS)
+    if H < 4 or H % 4 or H > FUSED_MAX_HIDDEN:
+        return "hidden_state_size = %d: the kernels cover a multiple of 4 <= %d" % (H, FUSED_MAX_HIDDEN)
+    if actor.with_comm:
+        K, V = actor.num_key, actor.num_value
+        if K < 4 or K % 4 or K > FUSED_MAX_KEY or V < 4 or V % 4 or V > FUSED_MAX_VALUE:
+            return "num_key = %d, num_value = %d: the kernels cover multiples of 4 <= %d and <= %d" % (K, V, FUSED_MAX_KEY, FUSED_MAX_VALUE)
+        if actor.comm_mode not in MODES:
+            return "the kernels cover the comm modes 'neighbours' and 'none'"
+        if nb_houses is not None and actor.comm_mode == "neighbours" and min(actor.number_agents_comm, nb_houses - 1) > MAX_COMM:
+            return "band attention covers at most %d senders per receiver" % MAX_COMM
+    for p in _params(actor):
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+            return "parameters must be contiguous float32 tensors on the GPU"
+    return None
+
+
+def supported(actor) -> bool:
+    """Do the gradient kernels take this actor?  A one-hop ``TarMACActor`` inside ``FusedTarMACActor``'s limits (num_obs <= 64,
+    hidden_state_size a multiple of 4 <= 64, num_key a multiple of 4 <= 16, num_value a multiple of 4 <= 32, the modes 'neighbours'
+    and 'none', with or without communication), float32 on the GPU."""
+    return _refusal(actor) is None
+
+
+def _params(actor) -> List[torch.Tensor]:
+    """The parameters a one-hop evaluation reaches, in the order of ``actor.parameters()`` - the order of the flat gradient
+    (``comm.msg_state2state`` follows them and is not reached)."""
+    mods = [actor.obs2hidden, _head(actor)]
+    if actor.with_comm:
+        mods += [actor.comm.hidden2key, actor.comm.hidden2value, actor.comm.hidden2query]
+    return [p for m in mods for p in (m[0].weight, m[0].bias, m[2].weight, m[2].bias)]
+
+
+def _desc(actor) -> nat.MdrTarmacNet:
+    ptr = [C.c_void_p(p.data_ptr()) for p in _params(actor)]
+    ptr += [None] * (20 - len(ptr))
+    K, V = (actor.num_key, actor.num_value) if actor.with_comm else (4, 4)
+    return nat.MdrTarmacNet(C.sizeof(nat.MdrTarmacNet), actor.num_obs, actor.hidden, K, V, actor.number_agents_comm, MODES[actor.comm_mode],
+                            actor.num_hops, int(actor.with_comm), actor.comm_defect_prob, *ptr)
+
+
+def _flat_grad(actor, lib, desc) -> torch.Tensor:
+    """The flat gradient buffer the kernels write, kept with the module; the reached ``.grad`` are views of it."""
+    dev = actor.obs2hidden[0].weight.device
+    flat = getattr(actor, "_mdr_flat_grad", None)
+    n = int(lib.mdr_tarmac_net_grad_floats(C.byref(desc)))
+    if flat is None or flat.numel() != n or flat.device != dev:
+        flat = torch.empty(n, dtype=torch.float32, device=dev)
+        actor._mdr_flat_grad = flat
+    return flat
+
+
+def _publish(actor, flat: torch.Tensor) -> None:
+    off = 0
+    for p in _params(actor):
+        view = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+        if p.grad is None:
+            p.grad = view
+        elif p.grad.data_ptr() != view.data_ptr():
+            p.grad.copy_(view)
+
+
+def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_prob: torch.Tensor, advantage: torch.Tensor,
+                        clip_param: float = 0.2, index: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0,
+                        want_ratio: bool = False, max_workgroups: int = 0):
+    """The clipped surrogate of agents/tarmac_ppo.py:168-182 and ``backward()``: fills ``p.grad`` of every parameter of ``actor`` a
+    one-hop evaluation reaches (allocated where None, overwritten otherwise; ``comm.msg_state2state`` keeps whatever ``.grad`` it had)
+    and returns the loss (0-dim device tensor) [and the ratios, float32 [B, N]].  ``state`` float32 [M, N, F] (contiguous env-steps,
+    any row stride >= F), ``action`` int64 [M, N], ``old_prob`` float32 [M, N]: the stored env-steps, read in place through ``index``
+    (int64 [B] on the device; None: every env-step in order, B = M); ``advantage`` float32 [B, N] in minibatch order.  With
+    ``comm_defect_prob > 0`` the dead senders are those of ``actor(state[index], seed=seed, step=step, differentiable=True)``."""
+    what = "tarmac_ppo.actor_loss_backward"
+    if not isinstance(state, torch.Tensor) or state.dim() != 3:
+        raise ValueError("%s: state must be [M, N, F]" % what)
+    M, N, F_len = (int(x) for x in state.shape)
+    if N < 1:
+        raise ValueError("%s: at least one agent per env-step" % what)
+    why = _refusal(actor, N)
+    if why:
+        raise ValueError("%s: %s" % (what, why))
+    dev = actor.obs2hidden[0].weight.device
+    if F_len != actor.num_obs or state.dtype != torch.float32 or state.device != dev:
+        raise ValueError("%s: state must be a float32 [M, N, %d] tensor on %s" % (what, actor.num_obs, dev))
+    ld = int(state.stride(1)) if N > 1 else (int(state.stride(0)) if M > 1 else F_len)
+    if (F_len > 1 and state.stride(2) != 1) or ld < F_len or (M > 1 and N > 1 and state.stride(0) != N * ld):
+        raise ValueError("%s: state rows need unit inner stride and one row stride >= F over all agents" % what)
+    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.device != dev or not index.is_contiguous()):
+        raise ValueError("%s: index must be a contiguous int64 [B] tensor on the device" % what)
+    B = int(index.shape[0]) if index is not None else M
+    for name, t, dt, n in (("action", action, torch.int64, M * N), ("old_prob", old_prob, torch.float32, M * N),
+                           ("advantage", advantage, torch.float32, B * N)):
+        if t.dtype != dt or t.device != dev or t.numel() != n or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s tensor of %d elements on the device" % (what, name, str(dt).replace("torch.", ""), n))
+    if not 0.0 <= float(clip_param) < 1.0:
+        raise ValueError("%s: clip_param must lie in [0, 1)" % what)
+    lib = nat.load()
+    desc = _desc(actor)
+    flat = _flat_grad(actor, lib, desc)
+    nbytes = int(lib.mdr_tarmac_ppo_workspace_bytes(C.byref(desc), B, N, max_workgroups))
+    if nbytes < 0:
+        raise ValueError("%s: mdr_tarmac_ppo_workspace_bytes refused the sizes" % what)
+    ws = _workspace(dev, nbytes)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    ratio = torch.empty((B, N), dtype=torch.float32, device=dev) if want_ratio else None
+    with torch.cuda.device(dev):
+        rc = lib.mdr_tarmac_ppo_actor_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None,
+                                           B, N, C.c_void_p(action.data_ptr()), C.c_void_p(old_prob.data_ptr()), C.c_void_p(advantage.data_ptr()),
+                                           C.c_float(clip_param), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(step & (2 ** 64 - 1)), max_workgroups,
+                                           C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
+                                           C.c_void_p(ratio.data_ptr()) if want_ratio else None,
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, "mdr_tarmac_ppo_actor_grad")
+    _publish(actor, flat)
+    return (loss, ratio) if want_ratio else loss
+
+
+class TarMACPPOLearner:
+    """``TarmacPPO.update`` (agents/tarmac_ppo.py:152-207) on the dict ``collect_tarmac_rollout`` returns.
+
+    ``backend="hip"``: the actor's loss and gradient from the kernels (ValueError for an actor they refuse); ``"torch"``:
+    ``forward(differentiable=True)`` under autograd (the dense formula on the CPU or with ``attention="dense"``) - the comparator, the
+    CPU path and the fallback for two or more hops; ``"auto"``: the kernels where ``supported(actor)`` holds and the minibatch has at
+    least ``AUTO_MIN_ENV_STEPS`` env-steps, torch otherwise.  The centralised critic (N F inputs, up to thousands wide - outside any
+    kernel of this library) stays torch autograd with every backend."""
+
+    def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
+                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam):
+        if backend not in ("auto", "hip", "torch"):
+            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        if backend == "hip":
+            why = _refusal(actor)
+            if why:
+                raise ValueError("TarMACPPOLearner(backend='hip'): " + why)
+        self.actor, self.critic = actor, critic
+        self.clip_param, self.max_grad_norm = float(clip_param), float(max_grad_norm)
+        self.ppo_update_time, self.batch_size = int(ppo_update_time), int(batch_size)
+        self.backend = backend
+        self.actor_optimizer = optimizer(actor.parameters(), lr_actor)
+        self.critic_optimizer = optimizer(critic.parameters(), lr_critic)
+        self.training_step = 0
+
+    @classmethod
+    def from_config(cls, tarmac_ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam) -> "TarMACPPOLearner":
+        """From the reference's ``config_dict["TarMAC_PPO_prop"]`` (agents/tarmac_ppo.py:39-45)."""
+        p = tarmac_ppo_prop
+        return cls(actor, critic, p["lr_actor"], p["lr_critic"], clip_param=p["clip_param"], max_grad_norm=p["max_grad_norm"],
+                   ppo_update_time=p["ppo_update_time"], batch_size=p["batch_size"], backend=backend, optimizer=optimizer)
+
+    def uses_kernels(self, nb_env_steps: int) -> bool:
+        if self.backend == "auto":
+            return _refusal(self.actor) is None and nb_env_steps >= AUTO_MIN_ENV_STEPS
+        return self.backend == "hip"
+
+    minibatches = PPOLearner.minibatches      # the sampler, over the stored env-steps: needs self.actor and self.batch_size only
+
+    def step_minibatch(self, state, action, old_prob, target, index, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One minibatch of agents/tarmac_ppo.py:159-207.  ``state`` [M, N, F], ``action``, ``old_prob``, ``target`` [M, N]: the whole
+        buffers; ``index`` picks the env-steps.  The critic's value gives the advantage, the actor's loss is clipped and stepped, then
+        the critic's.  The defects of ``comm_defect_prob > 0`` are keyed by ``(seed, training_step)``.  -> (actor loss, critic loss)."""
+        delta = target[index] - self.critic(state[index])                       # [B, N]
+        advantage = delta.detach()
+        if self.uses_kernels(int(index.shape[0])):
+            action_loss = actor_loss_backward(self.actor, state, action, old_prob, advantage.contiguous(), self.clip_param, index=index,
+                                              seed=seed, step=self.training_step)
+        else:
+            kw = dict(seed=seed, step=self.training_step, differentiable=True) if state.is_cuda and self.actor.attention != "dense" else {}
+            action_prob = self.actor(state[index], **kw).gather(2, action[index].unsqueeze(2)).squeeze(2)
+            ratio = action_prob / old_prob[index]
+            surr1 = ratio * advantage
+            surr2 = torch.clamp(ratio, 1 - self.clip_param, 1 + self.clip_param) * advantage
+            action_loss = -torch.min(surr1, surr2).mean()
+            self.actor_optimizer.zero_grad()
+            action_loss.backward()
+            action_loss = action_loss.detach()
+        nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad_norm)
+        self.actor_optimizer.step()
+        value_loss = torch.pow(delta, 2).mean(0).mean(0)
+        self.critic_optimizer.zero_grad()
+        value_loss.backward()
+        nn.utils.clip_grad_norm_(self.critic.parameters(), self.max_grad_norm)
+        self.critic_optimizer.step()
+        self.training_step += 1
+        return action_loss, value_loss.detach()
+
+    def update(self, batch: Dict[str, torch.Tensor], seed: int = 0, nb_houses: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """``ppo_update_time`` epochs over ``batch`` (``state`` [T+1, E*N, F], ``action``, ``a_prob``, ``return`` [T, E*N]): the T E
+        stored env-steps are ``batch["state"][:-1]`` viewed as [T E, N, F] and read in place, Gt is ``batch["return"]``.  ``nb_houses``
+        (N): default the critic's number of agents.  -> (mean actor loss, mean critic loss - device tensors -, number of minibatches)."""
+        states = batch["state"]
+        N = int(nb_houses) if nb_houses is not None else int(self.critic.critic[-1].out_features)
+        T = states.shape[0] - 1
+        if states.shape[1] % N:
+            raise ValueError("TarMACPPOLearner.update: %d agents per step are no whole number of envs of %d houses" % (states.shape[1], N))
+        state = states[:T].reshape(-1, N, states.shape[-1])      # a view: the first T slabs of a contiguous buffer
+        action = batch["action"].reshape(-1, N)
+        old_prob = batch["a_prob"].reshape(-1, N)
+        target = batch["return"].reshape(-1, N)
+        n = state.shape[0]
+        a_sum = torch.zeros((), dtype=torch.float32, device=state.device)
+        c_sum = torch.zeros((), dtype=torch.float32, device=state.device)
+        count = 0
+        for epoch in range(self.ppo_update_time):
+            for index in self.minibatches(n, seed, epoch):
+                a_loss, c_loss = self.step_minibatch(state, action, old_prob, target, index, seed=seed)
+                a_sum += a_loss
+                c_sum += c_loss
+                count += 1
+        return a_sum / max(count, 1), c_sum / max(count, 1), count

@@ -31,3 +31,16 @@ batch = collect_ppo_rollout(env, actor, nb_steps=8, store_states=False)
 dm = deploy_policy(env, FusedActor.from_module(actor), nb_steps=10)
 torch.cuda.synchronize()
 print("policy ok", sorted(batch), tuple(batch["action"].shape), sorted(dm), float(dm["reward_sum"].mean()))
+
+from mdr_amd.rollout import collect_tarmac_rollout  # noqa: E402
+from mdr_amd.tarmac import TarMACActor, TarMACCritic  # noqa: E402
+from mdr_amd.tarmac_ppo import TarMACPPOLearner  # noqa: E402
+small = mdr_amd.BatchedDemandResponseEnv(cfg, nb_envs=64, device="cuda:0", seed=1)
+small.reset()
+tarmac = TarMACActor(small.obs_vector_length()).cuda()
+tarmac_critic = TarMACCritic(small.nb_houses, small.obs_vector_length()).cuda()
+tbatch = collect_tarmac_rollout(small, tarmac, nb_steps=8, critic=tarmac_critic)
+tarmac_learner = TarMACPPOLearner(tarmac, tarmac_critic, lr_actor=1e-3, lr_critic=1e-3, ppo_update_time=2)
+a_loss, c_loss, n_mb = tarmac_learner.update(tbatch, seed=0)
+torch.cuda.synchronize()
+print("tarmac update ok", float(a_loss), float(c_loss), n_mb, tarmac_learner.uses_kernels(256))
