@@ -358,6 +358,48 @@ int mdr_ppo_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_
                         const float *target, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
                         float *advantage, void *stream);
 
+/* ---- DQN's / DDQN's update step on the same network (DQN.update, agents/dqn.py:84-112; DDQN.update, :119-146): the TD target of a
+ * minibatch, then the Huber loss and its clamped gradient.  Both nets are DQN_network (agents/network.py:58-77, raw Q-values) as
+ * mdr_mlp_t with num_out = 2 and the limits above.
+ *
+ * The TD target.  Minibatch row i < nb_rows is transition j = index ? index[i] : i (`index` device int64, may be NULL: the replay
+ * buffer's sampled positions); `next_state` + j * ld_state its F floats (ld_state >= F) and `reward[j]` - whole-buffer arrays read
+ * through `index`.  With (Q0, Q1) = target_net(next_state_j):
+ *   policy_net == NULL (DQN, dqn.py:96):   next_q[i] = max(Q0, Q1), next_action[i] (when given) = Q1 > Q0, the target net's own argmax
+ *   policy_net != NULL (DDQN, dqn.py:129-132): next_action[i] = argmax policy_net(next_state_j), next_q[i] = Q[next_action[i]]
+ *   y[i] = reward[j] + gamma * next_q[i]   (dqn.py:99; the product and the sum each rounded to fp32, no fma)
+ * A tie gives action 0, the first maximal index, as torch.argmax does; a NaN Q1 is taken as the maximum (torch.max).  There is no
+ * terminal mask: the reference's env never ends.  The reference's DDQN adds reward [B, 1] to next_q [B, 1, 1] and so broadcasts the
+ * target to [B, B, 1] (dqn.py:132-135); this is the per-row target that line evidently means.  `y`, `next_q` (may be NULL): float
+ * [nb_rows]; `next_action`: uint8 [nb_rows], required for DDQN, else may be NULL; all in minibatch order.
+ * Forward only, exact fp32 on the matrix cores: the gradient kernels' staging, two hidden layers and logits on a persistent grid of
+ * min(tiles of 16 rows, max_workgroups) workgroups (0: the library's choice, min(tiles, compute units, 512)), nothing else - no
+ * workspace.  DDQN makes two such launches, policy_net first (it writes next_action), target_net second (it reads it): the two weight
+ * sets do not fit the 160 KB of LDS together.  Every element of every given output is written by every successful call; nb_rows == 0
+ * launches nothing.  The same inputs give the same bits on every call.  Stream-ordered, never synchronises, allocates nothing.
+ * Returns 0; -1 (a NULL required pointer - DDQN without next_action included -, ld_state < F, nb_rows < 0, max_workgroups < 0, gamma
+ * not finite, a struct_size that is not this header's); -3 (HIP error); -4 (a shape outside the limits, num_out != 2, for DDQN two
+ * nets of different shapes).  On -1 and -4 nothing was launched and nothing written. */
+int mdr_dqn_target(const mdr_mlp_t *target_net, const mdr_mlp_t *policy_net, const float *next_state, int64_t ld_state,
+                   const int64_t *index, int64_t nb_rows, const float *reward, float gamma, int32_t max_workgroups, float *y,
+                   float *next_q, uint8_t *next_action, void *stream);
+
+/* nn.SmoothL1Loss() of dqn.py:93, 102-109 and its gradient.  Rows, `state`, `index` as above; `action[j]` (int64, nonzero = action 1) a
+ * whole-buffer array read through `index`, `y[i]` (mdr_dqn_target's, detached) in minibatch order.  q_i = policy_net(state_j)[action_j],
+ * delta_i = q_i - y_i,
+ *   loss = (1 / nb_rows) sum_i (|delta_i| < 1 ? delta_i^2 / 2 : |delta_i| - 1 / 2)
+ * and `grad` (mdr_mlp_grad_floats floats) = d loss / d parameters as torch's autograd takes it - d loss / d q_i = (delta_i < -1 ? -1 :
+ * delta_i > 1 ? 1 : delta_i) / nb_rows, the other Q-value's gradient 0, relu'(z) = 1 iff z > 0 - with every element then clamped to
+ * [-grad_clamp, grad_clamp] (param.grad.data.clamp_(-1, 1)): v < -c ? -c : v > c ? c : v, so a NaN stays a NaN as under clamp_;
+ * INFINITY clamps nothing.  The clamp is part of the reduction launch and never touches `loss`.  `q` (may be NULL): float [nb_rows],
+ * q_i.  Everything else - `grad`, `loss`, workspace (mdr_mlp_grad_workspace_bytes), grid, determinism, zero rows - as
+ * mdr_ppo_actor_grad.  Returns 0; -1 (a NULL required pointer, ld_state < F, nb_rows < 0, max_workgroups < 0, grad_clamp NaN or <= 0,
+ * a struct_size that is not this header's, a missing or misaligned workspace); -3 (HIP error); -4 (a shape outside the limits,
+ * num_out != 2).  On -1 and -4 nothing was launched and nothing written. */
+int mdr_dqn_grad(const mdr_mlp_t *policy_net, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                 const int64_t *action, const float *y, float grad_clamp, int32_t max_workgroups, void *workspace, float *grad,
+                 float *loss, float *q, void *stream);
+
 /* ---- TarMAC-PPO's update step for the actor (TarmacPPO.update, agents/tarmac_ppo.py:168-186): loss and gradient of one minibatch.
  *
  * The actor's weights in torch's own layout - every layer w[out][in] contiguous and its bias, device memory, read as they are on

@@ -1,4 +1,5 @@
-// PPO's update step for the MLP actor and critic (include/mdr_policy.h: mdr_mlp_t, mdr_ppo_actor_grad, mdr_ppo_critic_grad).
+// PPO's update step for the MLP actor and critic (include/mdr_policy.h: mdr_mlp_t, mdr_ppo_actor_grad, mdr_ppo_critic_grad) and DQN's /
+// DDQN's on the same network (mdr_dqn_target, mdr_dqn_grad): one kernel body, four heads.
 //
 // Reference: PPO.update (agents/ppo.py:139-188) evaluates, per minibatch, Actor / Critic (agents/network.py:14-57: Linear(F,H1) - ReLU -
 // Linear(H1,H2) - ReLU - Linear(H2,O)), forms the clipped surrogate (ppo.py:157-166) or F.mse_loss(Gt, V) (ppo.py:173) and calls
@@ -28,8 +29,15 @@
 // Five barriers per tile.  The accumulators of the three weight gradients stay in registers for the whole launch (dW2 8 blocks, dW1
 // 4 blocks, two bias blocks, one head register: 57 registers); each workgroup writes its partial once.  relu'(z) = 1 iff z > 0.
 // Rows past the minibatch are forwarded as zero states and given zero dlogits: they add exact zeros.
+//
+// DQN.update / DDQN.update (agents/dqn.py:84-146) take two more heads of the same body.  HEAD_TARGET is forward only - staging, F1, F2
+// and the logits as above, then wave 0 writes next_q = max(Q0, Q1) (or Q[pick], DDQN's gather), y = reward + gamma next_q and the
+// argmax; no h2T / dz images, no accumulators, no partials, three barriers per tile.  HEAD_HUBER is the actor's chain with
+// nn.SmoothL1Loss (beta = 1) on the taken action's Q-value against y.  Its reduction clamps every gradient element (dqn.py:108-109).
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
+#include <cmath>
 #include <cstdint>
 
 #include "../../include/mdr.h"
@@ -61,7 +69,8 @@ struct Shape {
   int sW1, sW2, sb1, sb2, sW3, sb3, sx, sh1, sh2, sdz2, sdz1, sdl, slp, lds;
 };
 
-__host__ __device__ inline Shape make_shape(int F, int H1, int H2, int O) {
+// backward == false (HEAD_TARGET): no h2T, dz2T, dz1T and dlogits images
+__host__ __device__ inline Shape make_shape(int F, int H1, int H2, int O, bool backward = true) {
   Shape s;
   s.F = F, s.H1 = H1, s.H2 = H2, s.O = O;
   s.nbf = blocks16(F), s.nb1 = blocks16(H1), s.nb2 = blocks16(H2);
@@ -78,10 +87,10 @@ __host__ __device__ inline Shape make_shape(int F, int H1, int H2, int O) {
   s.sx = s.sb3 + 4;
   s.sh1 = s.sx + 16 * s.nbf * LT;
   s.sh2 = s.sh1 + H1p * LT;
-  s.sdz2 = s.sh2 + H2p * LT;
-  s.sdz1 = s.sdz2 + H2p * LT;
-  s.sdl = s.sdz1 + H1p * LT;
-  s.slp = s.sdl + NW * TILE * 2;
+  s.sdz2 = s.sh2 + (backward ? H2p * LT : 0);
+  s.sdz1 = s.sdz2 + (backward ? H2p * LT : 0);
+  s.sdl = s.sdz1 + (backward ? H1p * LT : 0);
+  s.slp = s.sdl + (backward ? NW * TILE * 2 : 0);
   s.lds = s.slp + NW * TILE * 2;
   return s;
 }
@@ -93,15 +102,21 @@ struct GradArgs {
   int64_t ld_state;
   const int64_t* index;
   int64_t B, ntiles;
-  const int64_t* action;      // actor
+  const int64_t* action;      // actor, Huber
   const float* old_prob;      // actor
-  const float* adv_in;        // actor, minibatch order
-  const float* target;        // critic
+  const float* adv_in;        // actor: the advantage; Huber: y.  Minibatch order
+  const float* target;        // critic: Gt; TD target: reward.  Read through index
   float clip_lo, clip_hi;
   float* part;                // [gridDim.x][stride]
-  float* out0;                // actor: ratio; critic: value           (minibatch order, may be null)
-  float* out1;                // critic: advantage                     (may be null)
+  float* out0;                // actor: ratio; critic: value; TD target: y; Huber: q      (minibatch order, may be null)
+  float* out1;                // critic: advantage; TD target: next_q                     (may be null)
+  // behind the fields of the PPO heads, which keep their offsets
+  const uint8_t* pick;        // TD target: the action whose Q-value is taken (minibatch order); null: the larger one
+  uint8_t* amax;              // TD target: Q1 > Q0 (minibatch order, may be null)
+  float gamma;                // TD target
 };
+
+enum Head : int { HEAD_CRITIC = 0, HEAD_ACTOR = 1, HEAD_TARGET = 2, HEAD_HUBER = 3 };
 
 __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
@@ -113,11 +128,13 @@ __device__ __forceinline__ void stage_matrix(float* dst, const float* src, int r
   }
 }
 
-template <bool ACTOR>
+template <Head HEAD>
 __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Shape& s = a.s;
-  constexpr int O = ACTOR ? 2 : 1;
+  constexpr int O = HEAD == HEAD_CRITIC ? 1 : 2;
+  constexpr bool TWO = O == 2;                        // a second logit
+  constexpr bool BACKWARD = HEAD != HEAD_TARGET;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
   const int nb1 = s.nb1, nb2 = s.nb2, nbf = s.nbf;
   const int H1p = 16 * nb1, H2p = 16 * nb2, Fp = 16 * nbf;
@@ -233,13 +250,13 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float h = fmaxf(z2[i], 0.0f);
-        h2T[(16 * w + 4 * g + i) * LT + c] = h;
+        if (BACKWARD) h2T[(16 * w + 4 * g + i) * LT + c] = h;
         p0 = fmaf(w30[i], h, p0);
-        if (ACTOR) p1 = fmaf(w31[i], h, p1);
+        if (TWO) p1 = fmaf(w31[i], h, p1);
       }
       p0 += __shfl_xor(p0, 16);
       p0 += __shfl_xor(p0, 32);
-      if (ACTOR) {
+      if (TWO) {
         p1 += __shfl_xor(p1, 16);
         p1 += __shfl_xor(p1, 32);
       }
@@ -256,14 +273,49 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
     for (int b = 0; b < NW; ++b)      // the blocks' partial sums in block order
       if (b < nb2) {
         l0 += lp[(b * TILE + c) * 2];
-        if (ACTOR) l1 += lp[(b * TILE + c) * 2 + 1];
+        if (TWO) l1 += lp[(b * TILE + c) * 2 + 1];
       }
     l0 += b3s[0];
-    if (ACTOR) l1 += b3s[1];
+    if (TWO) l1 += b3s[1];
+    if constexpr (HEAD == HEAD_TARGET) {
+      // agents/dqn.py:96-99 (DQN), 129-135 (DDQN): next_q = max_a Q(s', a) or Q(s', pick), y = reward + gamma next_q.  A tie takes
+      // action 0 (torch.argmax: the first maximal index); a NaN Q1 is the maximum, as torch.max has it.  The product and the sum
+      // are two statements: each rounds on its own (-ffp-contract=on fuses inside one expression only).
+      if (valid && w == 0 && g == 0) {
+        const bool top = l1 > l0;
+        const bool take = a.pick ? a.pick[row] != 0 : (top || l1 != l1);
+        const float nq = take ? l1 : l0;
+        if (a.amax) a.amax[row] = top ? 1 : 0;
+        if (a.out1) a.out1[row] = nq;
+        if (a.out0) {
+          const int64_t j = a.index ? a.index[row] : row;
+          const float discounted = a.gamma * nq;
+          a.out0[row] = a.target[j] + discounted;
+        }
+      }
+      // xT was last read in F1, two barriers ago; lp is next written after the next tile's first barrier
+      if (more) {
+        store_x();
+        __syncthreads();
+      }
+      continue;
+    }
     float d0 = 0.0f, d1 = 0.0f, term = 0.0f;      // dlogits (before the 1 / B of the reduction) and the row's loss term
     if (valid) {
       const int64_t j = a.index ? a.index[row] : row;
-      if (ACTOR) {
+      if constexpr (HEAD == HEAD_HUBER) {
+        // agents/dqn.py:93, 102-103: nn.SmoothL1Loss() (beta = 1) of Q(s, action) against y; the gradient as torch's
+        // smooth_l1_loss_backward takes it (delta itself on [-1, 1], a NaN included), the other logit's is 0
+        const bool act = a.action[j] != 0;
+        const float q = act ? l1 : l0;
+        const float delta = q - a.adv_in[row];
+        const float ad = fabsf(delta);
+        term = ad < 1.0f ? 0.5f * delta * delta : ad - 0.5f;
+        const float dq = delta < -1.0f ? -1.0f : (delta > 1.0f ? 1.0f : delta);
+        d0 = act ? 0.0f : dq;
+        d1 = act ? dq : 0.0f;
+        if (w == 0 && g == 0 && a.out0) a.out0[row] = q;
+      } else if constexpr (HEAD == HEAD_ACTOR) {
         // agents/ppo.py:153-166: ratio = pi(a) / old_prob, L = -min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A); torch passes the
         // gradient through min to the first argument unless the second is smaller, and through clamp inside the closed range
         const bool act = a.action[j] != 0;
@@ -299,7 +351,7 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
       const f32x4 w31 = *reinterpret_cast<const f32x4*>(W3s + H2p + 16 * w + 4 * g);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float dh = ACTOR ? fmaf(d0, w30[i], d1 * w31[i]) : d0 * w30[i];
+        const float dh = TWO ? fmaf(d0, w30[i], d1 * w31[i]) : d0 * w30[i];
         dz2T[(16 * w + 4 * g + i) * LT + c] = z2[i] > 0.0f ? dh : 0.0f;
       }
     }
@@ -364,6 +416,7 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
     }
   }
 
+  if constexpr (!BACKWARD) return;
   // ---- the workgroup's partial: every float of [0, G] exactly once
   float* part = a.part + (int64_t)blockIdx.x * s.stride;
   if (w < nb1) {
@@ -420,40 +473,66 @@ int64_t grid_for(int64_t nb_rows, int32_t max_workgroups, int cus) {
   return grid > 0 ? grid : 1;
 }
 
-int run(bool is_actor, const mdr_mlp_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
-        const int64_t* action, const float* old_prob, const float* adv_in, const float* target, float clip, int32_t max_workgroups,
-        void* workspace, float* grad, float* loss, float* out0, float* out1, void* stream) {
+// the library's grid for nb_rows > 0 (max_workgroups == 0: one workgroup per compute unit, LIB_MAX_WG at most)
+int launch_grid(int64_t nb_rows, int32_t max_workgroups) {
+  int dev = 0, cus = 256;
+  if (max_workgroups == 0 &&
+      (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess))
+    cus = 256;
+  return (int)grid_for(nb_rows, max_workgroups, cus);
+}
+
+void fill_rows(GradArgs& a, const mdr_mlp_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows) {
+  a.w1 = net->w1, a.b1 = net->b1, a.w2 = net->w2, a.b2 = net->b2, a.w3 = net->w3, a.b3 = net->b3;
+  a.state = state, a.ld_state = ld_state, a.index = index, a.B = nb_rows, a.ntiles = (nb_rows + TILE - 1) / TILE;
+}
+
+int launch(Head head, const GradArgs& a, int grid, hipStream_t st) {
+  auto kernel = head == HEAD_ACTOR ? k_ppo_grad<HEAD_ACTOR>
+              : head == HEAD_CRITIC ? k_ppo_grad<HEAD_CRITIC>
+              : head == HEAD_TARGET ? k_ppo_grad<HEAD_TARGET>
+                                    : k_ppo_grad<HEAD_HUBER>;
+  const size_t lds_bytes = (size_t)a.s.lds * sizeof(float);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+    return MDR_ERR_HIP;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * NW), lds_bytes, st, a);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+bool net_pointers_ok(const mdr_mlp_t* n) { return n->w1 && n->b1 && n->w2 && n->b2 && n->w3 && n->b3; }
+
+// the three heads with a backward: HEAD_ACTOR, HEAD_CRITIC, HEAD_HUBER (adv_in = y, grad_clamp > 0; 0 for the PPO heads: no clamp)
+int run(Head head, const mdr_mlp_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+        const int64_t* action, const float* old_prob, const float* adv_in, const float* target, float clip, float grad_clamp,
+        int32_t max_workgroups, void* workspace, float* grad, float* loss, float* out0, float* out1, void* stream) {
   if (!net_fields_ok(net) || !state || !grad || !loss || !workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
-  if (!net->w1 || !net->b1 || !net->w2 || !net->b2 || !net->w3 || !net->b3) return MDR_ERR_INVALID;
-  if (is_actor ? (!action || !old_prob || !adv_in || !(clip >= 0.0f && clip < 1.0f)) : !target) return MDR_ERR_INVALID;
+  if (!net_pointers_ok(net)) return MDR_ERR_INVALID;
+  if (head == HEAD_ACTOR ? (!action || !old_prob || !adv_in || !(clip >= 0.0f && clip < 1.0f))
+      : head == HEAD_HUBER ? (!action || !adv_in || !(grad_clamp > 0.0f))
+                           : !target)
+    return MDR_ERR_INVALID;
   if (nb_rows < 0 || ld_state < net->num_state || max_workgroups < 0) return MDR_ERR_INVALID;
-  if (!net_covered(net) || net->num_out != (is_actor ? 2 : 1)) return MDR_ERR_UNSUPPORTED;
+  if (!net_covered(net) || net->num_out != (head == HEAD_CRITIC ? 1 : 2)) return MDR_ERR_UNSUPPORTED;
   GradArgs a{};
   a.s = make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out);
-  const size_t lds_bytes = (size_t)a.s.lds * sizeof(float);
-  if (lds_bytes > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
+  if ((size_t)a.s.lds * sizeof(float) > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   int grid = 0;
   if (nb_rows > 0) {
-    int dev = 0, cus = 256;
-    if (max_workgroups == 0 &&
-        (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess))
-      cus = 256;
-    grid = (int)grid_for(nb_rows, max_workgroups, cus);
-    a.w1 = net->w1, a.b1 = net->b1, a.w2 = net->w2, a.b2 = net->b2, a.w3 = net->w3, a.b3 = net->b3;
-    a.state = state, a.ld_state = ld_state, a.index = index, a.B = nb_rows, a.ntiles = (nb_rows + TILE - 1) / TILE;
+    grid = launch_grid(nb_rows, max_workgroups);
+    fill_rows(a, net, state, ld_state, index, nb_rows);
     a.action = action, a.old_prob = old_prob, a.adv_in = adv_in, a.target = target;
     a.clip_lo = (float)(1.0 - (double)clip), a.clip_hi = (float)(1.0 + (double)clip);
     a.part = static_cast<float*>(workspace), a.out0 = out0, a.out1 = out1;
-    auto kernel = is_actor ? k_ppo_grad<true> : k_ppo_grad<false>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-      return MDR_ERR_HIP;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * NW), lds_bytes, st, a);
-    if (hipGetLastError() != hipSuccess) return MDR_ERR_HIP;
+    if (launch(head, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
   }
   const int n = a.s.G + 1;
-  hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), grid,
-                     a.s.stride, a.s.G, (float)nb_rows, grad, loss);
+  if (head == HEAD_HUBER)
+    hipLaunchKernelGGL(k_grad_reduce_clamped, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), grid,
+                       a.s.stride, a.s.G, (float)nb_rows, grad_clamp, grad, loss);
+  else
+    hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), grid,
+                       a.s.stride, a.s.G, (float)nb_rows, grad, loss);
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
@@ -476,15 +555,50 @@ int64_t mdr_mlp_grad_workspace_bytes(const mdr_mlp_t* net, int64_t nb_rows, int3
 int mdr_ppo_actor_grad(const mdr_mlp_t* actor, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
                        const int64_t* action, const float* old_prob, const float* advantage, float clip_param, int32_t max_workgroups,
                        void* workspace, float* grad, float* loss, float* ratio, void* stream) {
-  return run(true, actor, state, ld_state, index, nb_rows, action, old_prob, advantage, nullptr, clip_param, max_workgroups, workspace, grad,
-             loss, ratio, nullptr, stream);
+  return run(HEAD_ACTOR, actor, state, ld_state, index, nb_rows, action, old_prob, advantage, nullptr, clip_param, 0.0f, max_workgroups,
+             workspace, grad, loss, ratio, nullptr, stream);
 }
 
 int mdr_ppo_critic_grad(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
                         const float* target, int32_t max_workgroups, void* workspace, float* grad, float* loss, float* value,
                         float* advantage, void* stream) {
-  return run(false, critic, state, ld_state, index, nb_rows, nullptr, nullptr, nullptr, target, 0.0f, max_workgroups, workspace, grad, loss,
-             value, advantage, stream);
+  return run(HEAD_CRITIC, critic, state, ld_state, index, nb_rows, nullptr, nullptr, nullptr, target, 0.0f, 0.0f, max_workgroups, workspace,
+             grad, loss, value, advantage, stream);
+}
+
+int mdr_dqn_target(const mdr_mlp_t* target_net, const mdr_mlp_t* policy_net, const float* next_state, int64_t ld_state,
+                   const int64_t* index, int64_t nb_rows, const float* reward, float gamma, int32_t max_workgroups, float* y, float* next_q,
+                   uint8_t* next_action, void* stream) {
+  if (!net_fields_ok(target_net) || !net_pointers_ok(target_net) || !next_state || !reward || !y) return MDR_ERR_INVALID;
+  if (policy_net && (!net_fields_ok(policy_net) || !net_pointers_ok(policy_net) || !next_action)) return MDR_ERR_INVALID;
+  if (nb_rows < 0 || ld_state < target_net->num_state || max_workgroups < 0 || !(fabsf(gamma) <= FLT_MAX)) return MDR_ERR_INVALID;
+  if (!net_covered(target_net) || target_net->num_out != 2) return MDR_ERR_UNSUPPORTED;
+  if (policy_net && (policy_net->num_state != target_net->num_state || policy_net->hidden1 != target_net->hidden1 ||
+                     policy_net->hidden2 != target_net->hidden2 || policy_net->num_out != 2))
+    return MDR_ERR_UNSUPPORTED;
+  GradArgs a{};
+  a.s = make_shape(target_net->num_state, target_net->hidden1, target_net->hidden2, 2, false);
+  if ((size_t)a.s.lds * sizeof(float) > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
+  if (nb_rows == 0) return MDR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = launch_grid(nb_rows, max_workgroups);
+  if (policy_net) {      // DDQN (agents/dqn.py:129): the policy net's argmax on the next states first - the two weight sets do not share LDS
+    fill_rows(a, policy_net, next_state, ld_state, index, nb_rows);
+    a.amax = next_action;
+    if (launch(HEAD_TARGET, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
+  }
+  fill_rows(a, target_net, next_state, ld_state, index, nb_rows);
+  a.target = reward, a.gamma = gamma, a.out0 = y, a.out1 = next_q;
+  a.pick = policy_net ? next_action : nullptr;
+  a.amax = policy_net ? nullptr : next_action;
+  return launch(HEAD_TARGET, a, grid, st);
+}
+
+int mdr_dqn_grad(const mdr_mlp_t* policy_net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                 const int64_t* action, const float* y, float grad_clamp, int32_t max_workgroups, void* workspace, float* grad, float* loss,
+                 float* q, void* stream) {
+  return run(HEAD_HUBER, policy_net, state, ld_state, index, nb_rows, action, nullptr, y, nullptr, 0.0f, grad_clamp, max_workgroups, workspace,
+             grad, loss, q, nullptr, stream);
 }
 
 }  // extern "C"

@@ -44,3 +44,9 @@ tarmac_learner = TarMACPPOLearner(tarmac, tarmac_critic, lr_actor=1e-3, lr_criti
 a_loss, c_loss, n_mb = tarmac_learner.update(tbatch, seed=0)
 torch.cuda.synchronize()
 print("tarmac update ok", float(a_loss), float(c_loss), n_mb, tarmac_learner.uses_kernels(256))
+
+from mdr_amd.dqn import DQNLearner, QNetworkMLP, train_dqn  # noqa: E402
+dqn_learner = DQNLearner(QNetworkMLP(small.obs_vector_length()).cuda(), lr=1e-3, buffer_capacity=4096)
+losses, epsilon = train_dqn(small, dqn_learner, nb_steps=4)
+torch.cuda.synchronize()
+print("dqn update ok", [round(float(x), 4) for x in losses], epsilon, len(dqn_learner.buffer), dqn_learner.uses_kernels(256))
