@@ -312,8 +312,9 @@ int mdr_env_tarmac_actor_sample(mdr_env_t *env, const mdr_obs_spec_t *spec, cons
  *
  * One network of agents/network.py:14-57 - Linear(F,H1) - ReLU - Linear(H1,H2) - ReLU - Linear(H2,O) - in torch's own layout,
  * w[out][in] contiguous, device memory, read as it is on every call (an optimiser step changes it between any two calls: there is
- * nothing to repack).  Limits: F <= 64, H1 <= 128, H2 <= 128, O = 2 (actor) or 1 (critic); MAPPO's critic (state + others' actions)
- * and the observations with message columns (81..121 features) are outside them. */
+ * nothing to repack).  Limits: F <= 64, H1 <= 128, H2 <= 128, O = 2 (actor) or 1 (critic); the observations with message columns
+ * (81..121 features) are outside them.  MAPPO's critic on state + others' actions has an entry point of its own with a wider input
+ * (mdr_mappo_critic_grad below: up to 128 joint features). */
 typedef struct mdr_mlp {
   uint32_t struct_size;
   int32_t num_state, hidden1, hidden2, num_out;
@@ -357,6 +358,39 @@ int mdr_ppo_actor_grad(const mdr_mlp_t *actor, const float *state, int64_t ld_st
 int mdr_ppo_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
                         const float *target, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
                         float *advantage, void *stream);
+
+/* ---- MAPPO's update step (MAPPO.update, agents/mappo.py:60-119).  Its actor step is PPO's line for line (mappo.py:92-110 against
+ * ppo.py:153-169): mdr_ppo_actor_grad serves it.  Its critic is Critic(num_state + nb_agents - 1) on torch.cat((state, others_actions))
+ * (mappo.py:21, 87): an mdr_mlp_t with num_state = J = F + (nb_agents - 1) and num_out = 1, parameters in torch's own layout.
+ *
+ * Floats of the joint critic's flat gradient dW1 [H1][J] | db1 [H1] | dW2 [H2][H1] | db2 [H2] | dW3 [1][H2] | db3 [1] (host-only, no
+ * device call).  -1: nb_agents < 1, J - (nb_agents - 1) < 1, num_out != 1, J > 128, a hidden layer > 128, a shape whose LDS layout does
+ * not fit (hidden 100-100 fits up to J = 100, 128-128 up to J = 68, 64-64 at J = 128), a struct_size that is not this header's. */
+int64_t mdr_mappo_critic_grad_floats(const mdr_mlp_t *critic, int32_t nb_agents);
+/* Bytes of device scratch one mdr_mappo_critic_grad call needs, as mdr_mlp_grad_workspace_bytes (host-only).  -1 as above, or
+ * nb_rows < 0, max_workgroups < 0. */
+int64_t mdr_mappo_critic_workspace_bytes(const mdr_mlp_t *critic, int32_t nb_agents, int64_t nb_rows, int32_t max_workgroups);
+
+/* The value loss of agents/mappo.py:85-88, 113 and its gradient.  Minibatch row i < nb_rows is transition j = index ? index[i] : i of
+ * a buffer of nb_transitions transitions in collect_ppo_rollout's flat layout: the agent index runs fastest, so transition j is agent
+ * a = j % nb_agents and its env-mates are the nb_agents transitions from j - a on (nb_transitions a multiple of nb_agents).  The
+ * critic's input is the F = J - (nb_agents - 1) floats at `state` + j * ld_state (ld_state >= F) followed by the others' actions,
+ *   input[F + k] = action[j - a + k + (k >= a)] != 0 ? 1 : 0,   k < nb_agents - 1
+ * (train_mappo.py:79-84: the step's action dict without agent a, in agent order), gathered from the whole-buffer `action` (int64
+ * [nb_transitions]) while the tile is staged: no others_actions tensor is read or needed.  V_i = critic(input_i),
+ *   loss = (1 / nb_rows) sum_i (target_j - V_i)^2
+ * and `grad` (mdr_mappo_critic_grad_floats floats) = d loss / d parameters as torch's autograd takes it; `target` a whole-buffer array
+ * read through `index`; `value` (may be NULL): V_i; `advantage` (may be NULL): target_j - V_i; both float [nb_rows] in minibatch
+ * order.  Every element of `grad`, `loss` and the given `value` / `advantage` is written by every successful call; nb_rows == 0 writes
+ * zeros to `grad` and `loss`.  Exact fp32 on the matrix cores, grid, partials in `workspace` (mdr_mappo_critic_workspace_bytes, 16-byte
+ * aligned), determinism (no floating-point atomics) and the stream contract as mdr_ppo_critic_grad.
+ * Returns 0; -1 (a NULL required pointer, nb_agents < 1, critic->num_state - (nb_agents - 1) < 1, ld_state < F, nb_transitions not a
+ * multiple of nb_agents, nb_rows < 0, max_workgroups < 0, a struct_size that is not this header's, a missing or misaligned
+ * workspace); -3 (HIP error); -4 (num_out != 1, J > 128, a hidden layer > 128, an LDS layout that does not fit).  On -1 and -4
+ * nothing was launched and nothing written. */
+int mdr_mappo_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *action, int64_t nb_transitions,
+                          int32_t nb_agents, const int64_t *index, int64_t nb_rows, const float *target, int32_t max_workgroups,
+                          void *workspace, float *grad, float *loss, float *value, float *advantage, void *stream);
 
 /* ---- DQN's / DDQN's update step on the same network (DQN.update, agents/dqn.py:84-112; DDQN.update, :119-146): the TD target of a
  * minibatch, then the Huber loss and its clamped gradient.  Both nets are DQN_network (agents/network.py:58-77, raw Q-values) as

@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("BatchedDemandResponseEnv", "OBS_COLUMNS"):
         from . import batched_env
         return getattr(batched_env, name)
-    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
+    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "BatchedMetrics":
@@ -25,6 +25,9 @@ def __getattr__(name):
     if name == "PPOLearner":
         from .ppo import PPOLearner
         return PPOLearner
+    if name == "MAPPOLearner":
+        from .mappo import MAPPOLearner
+        return MAPPOLearner
     if name in ("DQNLearner", "QNetworkMLP", "DeviceReplayBuffer"):
         from . import dqn
         return getattr(dqn, name)

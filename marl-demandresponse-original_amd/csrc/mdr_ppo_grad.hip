@@ -1,5 +1,6 @@
-// PPO's update step for the MLP actor and critic (include/mdr_policy.h: mdr_mlp_t, mdr_ppo_actor_grad, mdr_ppo_critic_grad) and DQN's /
-// DDQN's on the same network (mdr_dqn_target, mdr_dqn_grad): one kernel body, four heads.
+// PPO's update step for the MLP actor and critic (include/mdr_policy.h: mdr_mlp_t, mdr_ppo_actor_grad, mdr_ppo_critic_grad), DQN's /
+// DDQN's on the same network (mdr_dqn_target, mdr_dqn_grad) and MAPPO's centralised critic (mdr_mappo_critic_grad): one kernel body,
+// five heads.
 //
 // Reference: PPO.update (agents/ppo.py:139-188) evaluates, per minibatch, Actor / Critic (agents/network.py:14-57: Linear(F,H1) - ReLU -
 // Linear(H1,H2) - ReLU - Linear(H2,O)), forms the clipped surrogate (ppo.py:157-166) or F.mse_loss(Gt, V) (ppo.py:173) and calls
@@ -34,6 +35,14 @@
 // and the logits as above, then wave 0 writes next_q = max(Q0, Q1) (or Q[pick], DDQN's gather), y = reward + gamma next_q and the
 // argmax; no h2T / dz images, no accumulators, no partials, three barriers per tile.  HEAD_HUBER is the actor's chain with
 // nn.SmoothL1Loss (beta = 1) on the taken action's Q-value against y.  Its reduction clamps every gradient element (dqn.py:108-109).
+//
+// MAPPO.update (agents/mappo.py:85-89, 113-116) evaluates Critic(num_state + nb_agents - 1) on torch.cat((state, others_actions)).
+// HEAD_JOINT is HEAD_CRITIC's chain on that joint input of J = F + (N - 1) <= 128 features; only the tile image differs: rows 0..F-1
+// of xT are the state's, row F + k of transition j is the action of the k-th OTHER agent of j's env (train_mappo.py:79-84: the step's
+// action dict without agent a = j % N, in agent order), read from the `action` buffer while the tile is staged - the env-mates of
+// row j are the N entries from j - a on (collect_ppo_rollout's flat layout: the agent index runs fastest).  No others_actions
+// tensor is read or needed.  The width is a compile-time property of the instantiation (MAXF: 8 dW1 blocks per wave, 4 tile
+// elements per thread); the other heads keep 4 and 2.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -52,6 +61,7 @@ constexpr int NW = 8;                 // waves per workgroup = the most 16-unit 
 constexpr int TILE = 16;              // minibatch rows per tile
 constexpr int LT = 20;                // row stride of the transposed tile images
 constexpr int MAX_F = 64, MAX_H = 128;
+constexpr int MAX_J = 128;           // HEAD_JOINT: state + others' actions
 constexpr int LIB_MAX_WG = 512;       // the library's own grid: min(tiles, CUs, this)
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
@@ -114,9 +124,10 @@ struct GradArgs {
   const uint8_t* pick;        // TD target: the action whose Q-value is taken (minibatch order); null: the larger one
   uint8_t* amax;              // TD target: Q1 > Q0 (minibatch order, may be null)
   float gamma;                // TD target
+  int32_t Fs, N;              // joint critic: the state's features (s.F = Fs + N - 1) and the agents per env; `action` the whole buffer
 };
 
-enum Head : int { HEAD_CRITIC = 0, HEAD_ACTOR = 1, HEAD_TARGET = 2, HEAD_HUBER = 3 };
+enum Head : int { HEAD_CRITIC = 0, HEAD_ACTOR = 1, HEAD_TARGET = 2, HEAD_HUBER = 3, HEAD_JOINT = 4 };
 
 __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
@@ -132,7 +143,10 @@ template <Head HEAD>
 __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Shape& s = a.s;
-  constexpr int O = HEAD == HEAD_CRITIC ? 1 : 2;
+  constexpr bool JOINT = HEAD == HEAD_JOINT;
+  constexpr int O = (HEAD == HEAD_CRITIC || JOINT) ? 1 : 2;
+  constexpr int MAXF = JOINT ? MAX_J : MAX_F;         // input features of this instantiation
+  constexpr int NX = MAXF * TILE / (64 * NW);         // tile elements per thread
   constexpr bool TWO = O == 2;                        // a second logit
   constexpr bool BACKWARD = HEAD != HEAD_TARGET;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
@@ -162,41 +176,56 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
   }
   if (tid < 4) b3s[tid] = tid < O ? a.b3[tid] : 0.0f;
 
-  // the tile's states: element e = tid + 512 i of the [row][Fp] image, two per thread at most (16 x 64 / 512)
-  float xn[2];
+  // the tile's states: element e = tid + 512 i of the [row][Fp] image, NX per thread at most (16 x 64 / 512 = 2; joint: 16 x 128 / 512 = 4)
+  float xn[NX];
   auto load_x = [&](int64_t t) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NX; ++i) {
       const int e = tid + 64 * NW * i;
       const int r = e / Fp, f = e - r * Fp;
       const int64_t row = t * TILE + r;
       xn[i] = 0.0f;
       if (r < TILE && f < s.F && row < a.B) {
         const int64_t j = a.index ? a.index[row] : row;
-        xn[i] = a.state[j * a.ld_state + f];
+        if constexpr (JOINT) {
+          if (f < a.Fs) {
+            xn[i] = a.state[j * a.ld_state + f];
+          } else {
+            // train_mappo.py:79-84: the k-th other agent of agent ag is agent k (k < ag) or k + 1 (k >= ag) of the same env
+            const int k = f - a.Fs;
+            const int64_t ag = j % a.N;
+            xn[i] = a.action[j - ag + k + (k >= ag ? 1 : 0)] != 0 ? 1.0f : 0.0f;
+          }
+        } else {
+          xn[i] = a.state[j * a.ld_state + f];
+        }
       }
     }
   };
   auto store_x = [&]() {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NX; ++i) {
       const int e = tid + 64 * NW * i;
       const int r = e / Fp, f = e - r * Fp;
       if (r < TILE) xT[f * LT + r] = xn[i];
     }
   };
 
-  f32x4 dW2[NW], dW1[MAX_F / 16], db2 = {0, 0, 0, 0}, db1 = {0, 0, 0, 0};
+  f32x4 dW2[NW], dW1[MAXF / 16], db2 = {0, 0, 0, 0}, db1 = {0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < NW; ++i) dW2[i] = f32x4{0, 0, 0, 0};
 #pragma unroll
-  for (int i = 0; i < MAX_F / 16; ++i) dW1[i] = f32x4{0, 0, 0, 0};
+  for (int i = 0; i < MAXF / 16; ++i) dW1[i] = f32x4{0, 0, 0, 0};
   float acc3 = 0.0f;      // lane (g < O, c): dW3[g][16 w + c];  lane (g == 2, c < O): db3[c]
   float loss = 0.0f;      // wave 0, lanes g == 0: the terms of the rows = c (mod 16) of this workgroup's tiles
 
   const int64_t first = blockIdx.x;
-  if (first < a.ntiles) load_x(first);
-  else xn[0] = xn[1] = 0.0f;
+  if (first < a.ntiles) {
+    load_x(first);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xn[i] = 0.0f;
+  }
   store_x();
   __syncthreads();
 
@@ -331,7 +360,7 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
         d1 = act ? da : -da;
         if (w == 0 && g == 0 && a.out0) a.out0[row] = ratio;
       } else {
-        // agents/ppo.py:149-150, 173: delta = Gt - V, value loss = mean(delta^2)
+        // agents/ppo.py:149-150, 173 (agents/mappo.py:85-88, 113): delta = Gt - V, value loss = mean(delta^2)
         const float adv = a.target[j] - l0;
         term = adv * adv;
         d0 = -2.0f * adv;
@@ -405,7 +434,7 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
         const float av = da[4 * q];
         db1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, 1.0f, db1, 0, 0, 0);
 #pragma unroll
-        for (int ib = 0; ib < MAX_F / 16; ++ib)
+        for (int ib = 0; ib < MAXF / 16; ++ib)
           if (ib < nbf) dW1[ib] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xb[16 * ib * LT + 4 * q], dW1[ib], 0, 0, 0);
       }
     }
@@ -425,7 +454,7 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
       const int u = 16 * w + 4 * g + i;
       if (u < s.H1) {
 #pragma unroll
-        for (int ib = 0; ib < MAX_F / 16; ++ib)
+        for (int ib = 0; ib < MAXF / 16; ++ib)
           if (ib < nbf && 16 * ib + c < s.F) part[s.oW1 + u * s.F + 16 * ib + c] = dW1[ib][i];
         if (c == 0) part[s.ob1 + u] = db1[i];
       }
@@ -491,6 +520,7 @@ int launch(Head head, const GradArgs& a, int grid, hipStream_t st) {
   auto kernel = head == HEAD_ACTOR ? k_ppo_grad<HEAD_ACTOR>
               : head == HEAD_CRITIC ? k_ppo_grad<HEAD_CRITIC>
               : head == HEAD_TARGET ? k_ppo_grad<HEAD_TARGET>
+              : head == HEAD_JOINT  ? k_ppo_grad<HEAD_JOINT>
                                     : k_ppo_grad<HEAD_HUBER>;
   const size_t lds_bytes = (size_t)a.s.lds * sizeof(float);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
@@ -536,6 +566,16 @@ int run(Head head, const mdr_mlp_t* net, const float* state, int64_t ld_state, c
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
+// the joint critic's argument checks that need no device: MDR_OK, MDR_ERR_INVALID or MDR_ERR_UNSUPPORTED (the LDS fit included)
+int joint_shape(const mdr_mlp_t* critic, int32_t nb_agents, Shape* out) {
+  if (!net_fields_ok(critic) || nb_agents < 1 || (int64_t)critic->num_state - (nb_agents - 1) < 1) return MDR_ERR_INVALID;
+  if (critic->num_out != 1 || critic->num_state > MAX_J || critic->hidden1 > MAX_H || critic->hidden2 > MAX_H) return MDR_ERR_UNSUPPORTED;
+  const Shape s = make_shape(critic->num_state, critic->hidden1, critic->hidden2, 1);
+  if ((size_t)s.lds * sizeof(float) > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
+  if (out) *out = s;
+  return MDR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -564,6 +604,44 @@ int mdr_ppo_critic_grad(const mdr_mlp_t* critic, const float* state, int64_t ld_
                         float* advantage, void* stream) {
   return run(HEAD_CRITIC, critic, state, ld_state, index, nb_rows, nullptr, nullptr, nullptr, target, 0.0f, 0.0f, max_workgroups, workspace,
              grad, loss, value, advantage, stream);
+}
+
+int64_t mdr_mappo_critic_grad_floats(const mdr_mlp_t* critic, int32_t nb_agents) {
+  Shape s;
+  return joint_shape(critic, nb_agents, &s) == MDR_OK ? s.G : -1;
+}
+
+int64_t mdr_mappo_critic_workspace_bytes(const mdr_mlp_t* critic, int32_t nb_agents, int64_t nb_rows, int32_t max_workgroups) {
+  Shape s;
+  if (joint_shape(critic, nb_agents, &s) != MDR_OK || nb_rows < 0 || max_workgroups < 0) return -1;
+  return grid_for(nb_rows, max_workgroups, LIB_MAX_WG) * s.stride * (int64_t)sizeof(float);
+}
+
+int mdr_mappo_critic_grad(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* action, int64_t nb_transitions,
+                          int32_t nb_agents, const int64_t* index, int64_t nb_rows, const float* target, int32_t max_workgroups,
+                          void* workspace, float* grad, float* loss, float* value, float* advantage, void* stream) {
+  if (!net_fields_ok(critic) || !net_pointers_ok(critic) || !state || !action || !target || !grad || !loss || !workspace ||
+      ((uintptr_t)workspace & 15u))
+    return MDR_ERR_INVALID;
+  GradArgs a{};
+  const int rc = joint_shape(critic, nb_agents, &a.s);
+  if (rc == MDR_ERR_INVALID) return rc;
+  const int F = critic->num_state - (nb_agents - 1);
+  if (ld_state < F || nb_transitions < 0 || nb_transitions % nb_agents != 0 || nb_rows < 0 || max_workgroups < 0) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  int grid = 0;
+  if (nb_rows > 0) {
+    grid = launch_grid(nb_rows, max_workgroups);
+    fill_rows(a, critic, state, ld_state, index, nb_rows);
+    a.action = action, a.target = target, a.Fs = F, a.N = nb_agents;
+    a.part = static_cast<float*>(workspace), a.out0 = value, a.out1 = advantage;
+    if (launch(HEAD_JOINT, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
+  }
+  const int n = a.s.G + 1;
+  hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), grid,
+                     a.s.stride, a.s.G, (float)nb_rows, grad, loss);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
 int mdr_dqn_target(const mdr_mlp_t* target_net, const mdr_mlp_t* policy_net, const float* next_state, int64_t ld_state,

@@ -1,0 +1,169 @@
+"""MAPPO's update step on the GPU (include/mdr_policy.h: mdr_mappo_critic_grad, mdr_ppo_actor_grad).
+
+``MAPPO.update`` (agents/mappo.py:60-119) on the transitions ``collect_ppo_rollout(..., with_others_actions=True)`` leaves on the
+device.  Its actor step is PPO's line for line (mappo.py:92-110), so ``ppo.actor_loss_backward`` serves it unchanged; its critic is
+``Critic(num_state + nb_agents - 1)`` on ``torch.cat((state, others_actions))`` (mappo.py:21, 87).  ``joint_critic_loss_backward`` is
+forward, F.mse_loss and backward of that critic in ONE HIP kernel, which gathers the other agents' actions of a transition from the
+``action`` buffer while it stages the tile (they are the transition's env-mates): the int64 [T, E N, N - 1] ``others_actions`` tensor is
+neither read nor needed.  ``MAPPOLearner`` is the loop; clipping and Adam stay torch.  Nothing on the call path synchronises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import torch
+
+from . import _native as nat
+from . import ppo
+from .ppo import PPOLearner
+
+MAX_JOINT, MAX_HIDDEN = 128, ppo.MAX_HIDDEN      # the joint head's limits (include/mdr_policy.h: mdr_mappo_critic_grad)
+# backend="auto": the kernels from this many minibatch rows on (profiles/mappo_update_README.md: where they measured faster than the
+# torch backend)
+AUTO_MIN_ROWS = 1
+
+
+def _joint_refusal(critic, num_state: int) -> Optional[str]:
+    """Why the joint-input kernel does not take ``critic`` over states of ``num_state`` features (None: it does)."""
+    why = ppo._refusal(critic, 1, max_state=MAX_JOINT)
+    if why:
+        return why
+    J = critic.fc[0].in_features
+    nb_agents = J - int(num_state) + 1
+    if num_state < 1 or nb_agents < 1:
+        return "a critic of %d inputs over states of %d features leaves no whole number of other agents" % (J, num_state)
+    if nat.load().mdr_mappo_critic_grad_floats(C.byref(ppo._desc(critic)), nb_agents) < 0:
+        return ("%d joint inputs with hidden layers of %d and %d units do not fit the kernel's LDS layout"
+                % (J, critic.fc[0].out_features, critic.fc[1].out_features))
+    return None
+
+
+def supported(critic, num_state: int) -> bool:
+    """Does the joint-input kernel take this critic over states of ``num_state`` features?  A ``CriticMLP(num_state + N - 1)`` of two
+    hidden layers with at most 128 joint inputs, hidden layers of at most 128 units and an LDS layout that fits (hidden 100-100: up
+    to 100 inputs; 128-128: up to 68; 64-64: 128), float32 on the GPU."""
+    return _joint_refusal(critic, num_state) is None
+
+
+def gather_others(action: torch.Tensor, nb_agents: int, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``others_actions`` (train_mappo.py:79-84) of the transitions ``index`` (None: all) from the flat ``action`` buffer of
+    ``collect_ppo_rollout`` (the agent index runs fastest): [B, nb_agents - 1], entry k of transition j the action of agent k
+    (k < j % N) or k + 1 of the same env-step.  What the torch backend takes when the batch carries no ``others_actions``."""
+    N = int(nb_agents)
+    j = torch.arange(action.numel(), device=action.device) if index is None else index
+    a = (j % N)[:, None]
+    k = torch.arange(N - 1, device=action.device)[None, :]
+    return action.reshape(-1)[(j[:, None] - a) + k + (k >= a).to(k.dtype)]
+
+
+def joint_critic_loss_backward(critic, state: torch.Tensor, action: torch.Tensor, target: torch.Tensor, nb_agents: Optional[int] = None,
+                               index: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """F.mse_loss(Gt, V) of agents/mappo.py:85-88, 113 with V = critic(cat(state, others_actions)) and ``backward()`` in one kernel:
+    fills ``p.grad`` of ``critic`` and returns (loss 0-dim, value float32 [B], advantage float32 [B] = target - value, detached).
+    ``state`` float32 [M, F] (any row stride >= F), ``action`` int64 [M], ``target`` float32 [M]: the transition buffer in
+    ``collect_ppo_rollout``'s flat order (M a multiple of ``nb_agents``, default ``critic.fc[0].in_features - F + 1``), read in place
+    through ``index`` (int64 [B] on the device; None: every row in order).  The others' actions are gathered from ``action``."""
+    what = "joint_critic_loss_backward"
+    if state.dim() != 2:
+        raise ValueError("%s: state must be a float32 [M, F] tensor" % what)
+    F_len = int(state.shape[1])
+    fc = ppo._layers(critic)
+    if nb_agents is None and fc is not None:
+        nb_agents = fc[0].in_features - F_len + 1
+    why = _joint_refusal(critic, F_len)
+    if why:
+        raise ValueError("%s: %s" % (what, why))
+    if int(nb_agents) != fc[0].in_features - F_len + 1:
+        raise ValueError("%s: a critic of %d inputs over states of %d features has %d agents, not %d"
+                         % (what, fc[0].in_features, F_len, fc[0].in_features - F_len + 1, nb_agents))
+    N = int(nb_agents)
+    dev, M, ld, B = ppo._check_rows(critic, state, index, what, num_state=F_len)
+    if M % N:
+        raise ValueError("%s: a buffer of %d transitions is no whole number of env-steps of %d agents" % (what, M, N))
+    ppo._whole(action, torch.int64, M, dev, what, "action")
+    ppo._whole(target, torch.float32, M, dev, what, "target")
+    lib = nat.load()
+    desc = ppo._desc(critic)
+    flat = ppo._flat_grad(critic, lib, desc, floats=lib.mdr_mappo_critic_grad_floats(C.byref(desc), N))
+    ws = ppo._workspace(dev, int(lib.mdr_mappo_critic_workspace_bytes(C.byref(desc), N, B, max_workgroups)))
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    value = torch.empty(B, dtype=torch.float32, device=dev)
+    adv = torch.empty(B, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mdr_mappo_critic_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(action.data_ptr()), M, N,
+                                       C.c_void_p(index.data_ptr()) if index is not None else None, B, C.c_void_p(target.data_ptr()),
+                                       max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
+                                       C.c_void_p(value.data_ptr()), C.c_void_p(adv.data_ptr()),
+                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, "mdr_mappo_critic_grad")
+    ppo._publish(critic, flat)
+    return loss, value, adv
+
+
+class MAPPOLearner(PPOLearner):
+    """``MAPPO.update`` (agents/mappo.py:60-119) on the dict ``collect_ppo_rollout(..., with_others_actions=True)`` returns.
+
+    The critic is ``CriticMLP(F + nb_agents - 1)``: the number of agents comes from its width.  ``backend="hip"``: the joint critic
+    kernel, then ``ppo.actor_loss_backward`` with its advantage (ValueError for networks they refuse); ``"torch"``: the reference's
+    expressions under autograd on ``torch.cat((state[index], others[index].float()), 1)`` - the comparator and the fallback;
+    ``"auto"``: the kernels where they take both networks and the minibatch has at least ``AUTO_MIN_ROWS`` rows."""
+
+    def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
+                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam):
+        if backend not in ("auto", "hip", "torch"):
+            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        afc, cfc = ppo._layers(actor), ppo._layers(critic)
+        if afc is None or cfc is None:
+            raise ValueError("MAPPOLearner: actor and critic must be Linear-ReLU-Linear-ReLU-Linear (an `fc` ModuleList of three biased Linear layers)")
+        self.num_state = afc[0].in_features
+        self.nb_agents = cfc[0].in_features - self.num_state + 1
+        if self.nb_agents < 1:
+            raise ValueError("MAPPOLearner: the critic takes num_state + nb_agents - 1 = %d + N - 1 inputs, not %d" % (self.num_state, cfc[0].in_features))
+        if backend == "hip":
+            why = ppo._refusal(actor, 2) or _joint_refusal(critic, self.num_state)
+            if why:
+                raise ValueError("MAPPOLearner(backend='hip'): " + why)
+        # the base class checks PPO's critic (over the state alone) for "hip": this one's is checked above
+        super().__init__(actor, critic, lr_actor, lr_critic, clip_param=clip_param, max_grad_norm=max_grad_norm, ppo_update_time=ppo_update_time,
+                         batch_size=batch_size, backend="auto" if backend == "hip" else backend, optimizer=optimizer)
+        self.backend = backend
+        self._others = None      # the batch's others_actions [M, N - 1] during an update of the torch backend, where it has them
+
+    @classmethod
+    def from_config(cls, mappo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam) -> "MAPPOLearner":
+        """From the reference's ``config_dict["MAPPO_prop"]`` (agents/mappo.py:23-29)."""
+        return cls(actor, critic, mappo_prop["lr_actor"], mappo_prop["lr_critic"], clip_param=mappo_prop["clip_param"],
+                   max_grad_norm=mappo_prop["max_grad_norm"], ppo_update_time=mappo_prop["ppo_update_time"],
+                   batch_size=mappo_prop["batch_size"], backend=backend, optimizer=optimizer)
+
+    def uses_kernels(self, nb_rows: int) -> bool:
+        if self.backend == "auto":
+            return ppo._refusal(self.actor, 2) is None and _joint_refusal(self.critic, self.num_state) is None and nb_rows >= AUTO_MIN_ROWS
+        return self.backend == "hip"
+
+    def critic_backward(self, state, action, target, index):
+        return joint_critic_loss_backward(self.critic, state, action, target, nb_agents=self.nb_agents, index=index)
+
+    def critic_input(self, state, action, index) -> torch.Tensor:
+        """agents/mappo.py:87: torch.cat((state[index], others_actions[index]), dim=1)."""
+        others = self._others[index] if self._others is not None else gather_others(action, self.nb_agents, index)
+        return torch.cat((state[index], others.float()), 1)
+
+    def update(self, batch: Dict[str, torch.Tensor], seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """``ppo_update_time`` epochs over ``batch`` as ``PPOLearner.update``; ``batch["others_actions"]`` [T, A, N - 1] is optional and
+        read by the torch backend alone (without it that backend gathers each minibatch's from ``batch["action"]``)."""
+        A = int(batch["action"].shape[1])
+        if A % self.nb_agents:
+            raise ValueError("MAPPOLearner.update: %d agents per step are no whole number of envs of %d agents (the critic's width)" % (A, self.nb_agents))
+        if int(batch["state"].shape[-1]) != self.num_state:
+            raise ValueError("MAPPOLearner.update: states of %d features, the actor takes %d" % (batch["state"].shape[-1], self.num_state))
+        if self.backend != "hip" and "others_actions" in batch:
+            others = batch["others_actions"]
+            if others.shape[-1] != self.nb_agents - 1:
+                raise ValueError("MAPPOLearner.update: others_actions of %d columns, the critic's width asks for %d" % (others.shape[-1], self.nb_agents - 1))
+            self._others = others.reshape(-1, self.nb_agents - 1)
+        try:
+            return super().update(batch, seed)
+        finally:
+            self._others = None

@@ -30,15 +30,15 @@ def _layers(net) -> Optional[List[nn.Linear]]:
     return list(fc)
 
 
-def _refusal(net, num_out: Optional[int] = None) -> Optional[str]:
-    """Why the kernels do not take ``net`` (None: they do)."""
+def _refusal(net, num_out: Optional[int] = None, max_state: int = MAX_STATE) -> Optional[str]:
+    """Why the kernels do not take ``net`` (None: they do).  ``max_state``: the input width of the head asked for."""
     fc = _layers(net)
     if fc is None:
         return "the kernels cover Linear-ReLU-Linear-ReLU-Linear (an `fc` ModuleList of three biased Linear layers)"
     if fc[1].in_features != fc[0].out_features or fc[2].in_features != fc[1].out_features:
         return "the three layers do not chain"
-    if fc[0].in_features > MAX_STATE:
-        return "num_state = %d: the kernels cover at most %d input features" % (fc[0].in_features, MAX_STATE)
+    if fc[0].in_features > max_state:
+        return "num_state = %d: the kernels cover at most %d input features" % (fc[0].in_features, max_state)
     if fc[0].out_features > MAX_HIDDEN or fc[1].out_features > MAX_HIDDEN:
         return "hidden layers of %d and %d units: the kernels cover at most %d" % (fc[0].out_features, fc[1].out_features, MAX_HIDDEN)
     outs = (1, 2) if num_out is None else (num_out,)
@@ -78,12 +78,12 @@ def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
     return ws
 
 
-def _flat_grad(net, lib, desc) -> torch.Tensor:
+def _flat_grad(net, lib, desc, floats: Optional[int] = None) -> torch.Tensor:
     """The flat gradient buffer the kernels write, kept with the module; the six ``.grad`` are views of it (assigned where a
     parameter has none or another tensor of its own, which is then overwritten by a copy after the call)."""
     params = _params(net)
     flat = getattr(net, "_mdr_flat_grad", None)
-    n = int(lib.mdr_mlp_grad_floats(C.byref(desc)))
+    n = int(lib.mdr_mlp_grad_floats(C.byref(desc))) if floats is None else int(floats)
     if flat is None or flat.numel() != n or flat.device != params[0].device:
         flat = torch.empty(n, dtype=torch.float32, device=params[0].device)
         net._mdr_flat_grad = flat
@@ -101,11 +101,12 @@ def _publish(net, flat: torch.Tensor) -> None:
             p.grad.copy_(view)
 
 
-def _check_rows(net, state, index, what):
+def _check_rows(net, state, index, what, num_state: Optional[int] = None):
     fc = _layers(net)
     dev = fc[0].weight.device
-    if state.dim() != 2 or state.shape[1] != fc[0].in_features or state.dtype != torch.float32 or state.device != dev:
-        raise ValueError("%s: state must be a float32 [M, %d] tensor on %s" % (what, fc[0].in_features, dev))
+    width = fc[0].in_features if num_state is None else num_state      # of the state rows (the joint critic's input is wider)
+    if state.dim() != 2 or state.shape[1] != width or state.dtype != torch.float32 or state.device != dev:
+        raise ValueError("%s: state must be a float32 [M, %d] tensor on %s" % (what, width, dev))
     F_len, M = int(state.shape[1]), int(state.shape[0])
     if (F_len > 1 and state.stride(1) != 1) or (M > 1 and state.stride(0) < F_len):
         raise ValueError("%s: state rows need unit inner stride and a row stride >= F" % what)
@@ -229,15 +230,23 @@ class PPOLearner:
         perm = torch.randperm(int(nb_transitions), generator=gen, device=dev)
         return list(torch.split(perm, self.batch_size))
 
+    def critic_backward(self, state, action, target, index):
+        """The critic's kernel call of one minibatch -> (loss, value, advantage); MAPPOLearner's takes the joint input."""
+        return critic_loss_backward(self.critic, state, target, index=index)
+
+    def critic_input(self, state, action, index) -> torch.Tensor:
+        """The critic's input rows of one minibatch on the torch backend."""
+        return state[index]
+
     def step_minibatch(self, state, action, old_prob, target, index) -> Tuple[torch.Tensor, torch.Tensor]:
         """One minibatch of agents/ppo.py:146-188: critic, actor with the critic's advantage, gradient clipping on each network, both
         optimiser steps.  The arguments are the whole flattened buffers; ``index`` picks the minibatch.  -> (actor loss, critic loss)."""
         if self.uses_kernels(int(index.shape[0])):
-            value_loss, _, advantage = critic_loss_backward(self.critic, state, target, index=index)
+            value_loss, _, advantage = self.critic_backward(state, action, target, index)
             action_loss = actor_loss_backward(self.actor, state, action, old_prob, advantage, self.clip_param, index=index)
         else:
             Gt_index = target[index].view(-1, 1)
-            V = self.critic(state[index])
+            V = self.critic(self.critic_input(state, action, index))
             advantage = (Gt_index - V).detach()
             action_prob = self.actor(state[index]).gather(1, action[index].view(-1, 1))
             ratio = action_prob / old_prob[index].view(-1, 1)
