@@ -513,6 +513,58 @@ int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t *net, const float *state, i
                               uint64_t seed, uint64_t step, int32_t max_workgroups, void *workspace, float *grad, float *loss,
                               float *ratio, void *stream);
 
+/* ---- The optimiser tail of every update: clamp, norm clip, Adam and the target blend in one launch (csrc/mdr_optim.hip).
+ *
+ * A network's tensors as a table of segments: `param` (device float [count], updated in place), `grad` (device float [count], read
+ * only; NULL: the segment is skipped entirely, as torch.optim.Adam skips p.grad is None - its parameter, moments and target stay
+ * untouched and it is no part of the norm), `target` (device float [count], NULL where no blend is asked for).  Any float alignment:
+ * slices of one flat gradient buffer and separately allocated tensors are both fine. */
+#define MDR_ADAM_MAX_SEGMENTS 32
+typedef struct mdr_adam_segment {
+  float *param;
+  const float *grad;
+  float *target;
+  int64_t count;
+} mdr_adam_segment_t;
+
+typedef struct mdr_adam_segments {
+  uint32_t struct_size;
+  int32_t nb_segments; /* <= MDR_ADAM_MAX_SEGMENTS */
+  mdr_adam_segment_t seg[MDR_ADAM_MAX_SEGMENTS];
+} mdr_adam_segments_t;
+
+/* Bytes of device scratch a call over segments of total_floats elements in all may need (the chunk sums of the two-launch form),
+ * a multiple of 16.  Host-only.  -1: total_floats < 0. */
+int64_t mdr_adam_workspace_bytes(int64_t total_floats);
+
+/* One step of torch.optim.Adam (betas, eps as given; no weight decay, no amsgrad) on every live segment, from the gradient on the
+ * device, with nothing read back.  `exp_avg`, `exp_avg_sq`: device float [sum of all counts], the segments' moments one after the
+ * other in segment order (dead segments keep their place).  Per element, in fp32:
+ *   g = grad clamped to [-grad_clamp, grad_clamp] by comparisons (v < -c ? -c : v > c ? c : v: a NaN stays a NaN; INFINITY: no clamp)
+ *   max_grad_norm > 0 and finite: total_norm = sqrt(sum g^2) over the live segments, coef = max_grad_norm / (total_norm + 1e-6),
+ *     at most 1 (c > 1 ? 1 : c: a NaN total_norm gives a NaN coef), g = coef g - nn.utils.clip_grad_norm_ with
+ *     error_if_nonfinite=False; <= 0 or INFINITY: no clip
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   param = param - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *   tau > 0: target = (1 - tau) target + tau param, with the new param (agents/dqn.py:77-82); <= 0: no blend
+ * The constants (1 - beta, the two bias corrections, 1 - tau) are formed on the host in double and passed as floats.  `grad` is
+ * NEVER written: after the call it still holds the unclipped, unclamped gradient - the one visible difference from
+ * clip_grad_norm_, which scales .grad in place.  `total_norm_out` (may be NULL): one device float, total_norm (of the clamped
+ * gradient; written with or without a clip).
+ * The norm is deterministic, no floating-point atomics: chunks of 1024 consecutive elements of one live segment (the last of a
+ * segment ragged), each summed by one wave in a fixed order, the chunk sums added in chunk order - the same bits whatever the grid
+ * and whichever form ran.  Forms: the sum of all counts <= max_fused_floats (0: the library's measured default) - ONE launch, every
+ * workgroup recomputes the norm and steps its own chunks; larger - TWO launches, chunk sums into `workspace`
+ * (mdr_adam_workspace_bytes, 16-byte aligned, required by this form only), then sum and step.  Neither clip nor total_norm_out: no
+ * norm pass, one launch at any size.  Stream-ordered, never synchronises, allocates nothing.
+ * Returns 0; -1 (a NULL segments / exp_avg / exp_avg_sq / param pointer, a struct_size that is not this header's, nb_segments < 0,
+ * a negative count, step < 1, tau > 0 with a live segment without target, tau > 1, betas outside [0, 1), eps < 0, grad_clamp NaN
+ * or <= 0, max_fused_floats < 0, a missing or misaligned workspace for the two-launch form); -3 (HIP error); -4 (more than
+ * MDR_ADAM_MAX_SEGMENTS segments, 2^30 chunks or more).  On -1 and -4 nothing was launched and nothing written. */
+int mdr_adam_step(const mdr_adam_segments_t *segments, float *exp_avg, float *exp_avg_sq, double lr, double beta1, double beta2,
+                  double eps, int64_t step, double max_grad_norm, double grad_clamp, double tau, void *workspace,
+                  float *total_norm_out, int32_t max_fused_floats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

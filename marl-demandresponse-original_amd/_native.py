@@ -151,6 +151,17 @@ class MdrTarmacNet(C.Structure):
     ]
 
 
+MDR_ADAM_MAX_SEGMENTS = 32
+
+
+class MdrAdamSegment(C.Structure):
+    _fields_ = [("param", _f32p), ("grad", _f32p), ("target", _f32p), ("count", C.c_int64)]
+
+
+class MdrAdamSegments(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nb_segments", C.c_int32), ("seg", MdrAdamSegment * MDR_ADAM_MAX_SEGMENTS)]
+
+
 OBS_PLANES, OBS_ROWS = 0, 1
 
 EXPORTS = (
@@ -173,6 +184,7 @@ EXPORTS = (
     "mdr_mlp_grad_floats", "mdr_mlp_grad_workspace_bytes", "mdr_ppo_actor_grad", "mdr_ppo_critic_grad", "mdr_dqn_target", "mdr_dqn_grad",
     "mdr_mappo_critic_grad_floats", "mdr_mappo_critic_workspace_bytes", "mdr_mappo_critic_grad",
     "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
+    "mdr_adam_workspace_bytes", "mdr_adam_step",
 )
 
 _lib = None
@@ -277,6 +289,9 @@ def load():
         "mdr_tarmac_ppo_workspace_bytes": (i64, [C.POINTER(MdrTarmacNet), i64, i32, i32]),
         "mdr_tarmac_ppo_actor_grad": (C.c_int, [C.POINTER(MdrTarmacNet), vp, i64, vp, i64, i32, vp, vp, vp, C.c_float, u64, u64, i32, vp, vp, vp,
                                                 vp, vp]),
+        "mdr_adam_workspace_bytes": (i64, [i64]),
+        "mdr_adam_step": (C.c_int, [C.POINTER(MdrAdamSegments), vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, i64, C.c_double, C.c_double,
+                                    C.c_double, vp, vp, i32, vp]),
         "mdr_env_pack": (C.c_int, [vp, i32, vp, vp]),
         "mdr_env_graph_room": (i64, [vp]),
         "mdr_env_graph_replayed": (C.c_int, [vp, i64, vp]),

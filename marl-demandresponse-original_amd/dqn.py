@@ -6,7 +6,7 @@ evaluates the target net on the next states (DDQN: the policy net too), forms ``
 the states, takes ``nn.SmoothL1Loss``, calls ``backward()``, clamps every gradient element to [-1, 1], takes an Adam step and blends
 the target net towards the policy net.  Here the target is ONE forward-only HIP kernel on the matrix cores (two for DDQN) and forward,
 Huber loss, backward and the clamp are one more plus its reduction: ``td_target`` / ``q_loss_backward``.  torch keeps the optimiser
-and the blend.  ``DeviceReplayBuffer`` is the reference's ``ReplayBuffer`` as preallocated device tensors the kernels read in place
+and the blend by default; ``optimizer=FusedAdam`` (optim.py) makes them one more launch.  ``DeviceReplayBuffer`` is the reference's ``ReplayBuffer`` as preallocated device tensors the kernels read in place
 through the sampled indices, ``DQNLearner`` the update, ``train_dqn`` the loop.  Nothing on the call path synchronises with the host.
 
 Two places leave the reference's text on purpose:
@@ -27,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
+from .optim import FusedAdam
 from .ppo import _check_rows, _desc, _flat_grad, _publish, _refusal, _whole, _workspace
 
 # backend="auto": the kernels from this many minibatch rows on (profiles/dqn_update_README.md: where they measured faster than autograd)
@@ -185,7 +186,8 @@ class DQNLearner:
     the target net alone after an update, as the reference's DDQN does.  ``backend="hip"``: target, loss and clamped gradient from
     the kernels (ValueError for networks they refuse); ``"torch"``: the reference's expressions under autograd with
     ``p.grad.clamp_(-1, 1)`` - the comparator and the fallback; ``"auto"``: the kernels where ``supported()`` holds and the minibatch
-    has at least ``AUTO_MIN_ROWS`` rows, torch otherwise.  The optimiser step and the target blend are torch on every backend."""
+    has at least ``AUTO_MIN_ROWS`` rows, torch otherwise.  The optimiser step and the target blend are torch on every backend unless
+    ``optimizer=mdr_amd.optim.FusedAdam``: then, with ``soft_update``, both are one ``FusedAdam.step(target=..., tau=...)``."""
 
     GRAD_CLAMP = 1.0      # agents/dqn.py:108-109
 
@@ -209,6 +211,11 @@ class DQNLearner:
         self.backend = backend
         self.buffer = DeviceReplayBuffer(buffer_capacity, fc[0].in_features, dev)
         self.optimizer = optimizer(policy_net.parameters(), lr)
+        # FusedAdam blends in its own launch where the optimiser's parameters are exactly the six the target net mirrors
+        mine = [p for lin in fc for p in (lin.weight, lin.bias)]
+        held = list(policy_net.parameters())
+        same = len(held) == len(mine) and all(a is b for a, b in zip(held, mine))
+        self._fused_target = [p for lin in self.target_net.fc for p in (lin.weight, lin.bias)] if same else None
         self.training_step = 0
         self.before_step = None      # optional callable(learner): runs after the backward (and the clamp) of an update, before the optimiser
 
@@ -275,9 +282,12 @@ class DQNLearner:
         loss = self.loss_backward(self.sample(seed))
         if self.before_step is not None:
             self.before_step(self)
-        self.optimizer.step()
-        if self.soft_update:
-            self.update_target_network()
+        if self.soft_update and isinstance(self.optimizer, FusedAdam) and self._fused_target is not None:
+            self.optimizer.step(target=self._fused_target, tau=self.tau)      # Adam and the blend in one launch
+        else:
+            self.optimizer.step()
+            if self.soft_update:
+                self.update_target_network()
         self.training_step += 1
         return loss
 

@@ -1,0 +1,200 @@
+"""Adam on the GPU from a gradient on the GPU (include/mdr_policy.h: mdr_adam_step).
+
+What every learner does with the gradient its kernels leave - ``clip_grad_norm_`` (DQN: an elementwise clamp), ``optimizer.step()``
+(torch's Adam: nine ``multi_tensor_apply`` launches over 6-20 tensors) and, in DQN, the target blend - as ONE launch of
+csrc/mdr_optim.hip: ``FusedAdam`` is a ``torch.optim.Optimizer`` that drops into the ``optimizer=`` hook of ``PPOLearner``,
+``MAPPOLearner``, ``TarMACPPOLearner`` and ``DQNLearner``.  It is opt-in: the learners' default stays ``torch.optim.Adam``.
+
+Parameters, gradients and targets stay where torch holds them: the kernel takes a table of {param, grad, target, count} segments,
+so the gradients may be slices of a flat buffer (the gradient kernels') or autograd's own tensors.  The two moments are flat
+buffers owned by the optimiser; ``state[p]["exp_avg"]`` / ``["exp_avg_sq"]`` are views of them, so ``state_dict()`` and
+``load_state_dict()`` interchange with ``torch.optim.Adam``'s.
+
+One visible difference from ``clip_grad_norm_`` + ``Adam.step()``: the gradient is never written.  After ``step(max_grad_norm=...)``
+``p.grad`` still holds the unclipped gradient (``clip_grad_norm_`` scales ``.grad`` in place).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import _native as nat
+
+MAX_TENSORS = nat.MDR_ADAM_MAX_SEGMENTS
+
+
+def _refusal(params: Sequence[torch.Tensor]) -> Optional[str]:
+    """Why the kernel does not take these parameters (None: it does)."""
+    params = list(params)
+    if not params:
+        return "no parameters"
+    if len(params) > MAX_TENSORS:
+        return "%d tensors: the kernel's segment table holds at most %d" % (len(params), MAX_TENSORS)
+    for p in params:
+        if not isinstance(p, torch.Tensor):
+            return "parameters must be tensors"
+        if p.dtype != torch.float32:
+            return "parameters must be float32 (got %s)" % str(p.dtype).replace("torch.", "")
+        if not p.is_contiguous():
+            return "parameters must be contiguous"
+    for p in params:
+        if not p.is_cuda:
+            return "parameters must be on the GPU (got a %s tensor)" % p.device.type
+        if p.device != params[0].device:
+            return "parameters must be on one GPU (got %s and %s)" % (params[0].device, p.device)
+    return None
+
+
+def supported(params) -> bool:
+    """Does the kernel take these parameters?  At most 32 contiguous float32 tensors on one GPU."""
+    return _refusal(list(params)) is None
+
+
+class FusedAdam(torch.optim.Optimizer):
+    """``torch.optim.Adam`` with its defaults other than ``lr``, ``betas`` and ``eps`` (no weight decay, no amsgrad, no maximize), one
+    param group, at most 32 contiguous float32 tensors on one GPU; anything else raises ``ValueError``.  ``FusedAdam(params, lr)`` is the
+    call the learners' ``optimizer=`` hook makes.
+
+    ``max_fused_floats``: up to this many parameters in all the clipped step is one launch, above it two (0: the library's measured
+    default, profiles/optim_step_README.md); both forms give the same bits."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_fused_floats: int = 0):
+        if not 0.0 <= float(lr):
+            raise ValueError("FusedAdam: invalid learning rate %r" % (lr,))
+        if not (0.0 <= float(betas[0]) < 1.0 and 0.0 <= float(betas[1]) < 1.0):
+            raise ValueError("FusedAdam: betas must lie in [0, 1), got %r" % (betas,))
+        if not 0.0 <= float(eps):
+            raise ValueError("FusedAdam: invalid eps %r" % (eps,))
+        if int(max_fused_floats) < 0:
+            raise ValueError("FusedAdam: max_fused_floats must be >= 0 (0: the library's default)")
+        # the param group carries torch.optim.Adam's own keys (this torch's), so that either optimiser loads the other's state_dict
+        defaults = dict(torch.optim.Adam([torch.zeros(1)]).defaults)
+        defaults.update(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps))
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError("FusedAdam: one param group only (got %d)" % len(self.param_groups))
+        self._params: List[torch.Tensor] = list(self.param_groups[0]["params"])
+        why = _refusal(self._params)
+        if why:
+            raise ValueError("FusedAdam: " + why)
+        self.max_fused_floats = int(max_fused_floats)
+        dev = self._params[0].device
+        self._device = dev
+        self._counts = [p.numel() for p in self._params]
+        total = sum(self._counts)
+        self._exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._m_views, self._v_views, off = [], [], 0
+        for p, n in zip(self._params, self._counts):
+            self._m_views.append(self._exp_avg[off:off + n].view_as(p))
+            self._v_views.append(self._exp_avg_sq[off:off + n].view_as(p))
+            off += n
+        self._lib = nat.load()
+        self._workspace = torch.empty(max(int(self._lib.mdr_adam_workspace_bytes(total)), 16), dtype=torch.uint8, device=dev)
+        self._norm = torch.zeros((), dtype=torch.float32, device=dev)
+        self._table = nat.MdrAdamSegments()
+        self._table.struct_size = C.sizeof(nat.MdrAdamSegments)
+        self._table.nb_segments = len(self._params)
+        self._key = None      # the pointers the table was built from
+        self._live: List[int] = []
+        self._steps: List[torch.Tensor] = []
+        self._t = 0      # the step count of the live parameters
+
+    # -- state ---------------------------------------------------------------------------------------------------------------------
+    def _adopt(self, i: int, step: Optional[torch.Tensor] = None) -> dict:
+        """``state[p]`` of parameter i as views of the flat moments (created on its first gradient, as torch.optim.Adam does)."""
+        p = self._params[i]
+        st = self.state[p]
+        st["step"] = step if step is not None else torch.tensor(0.0, dtype=torch.float32)
+        st["exp_avg"], st["exp_avg_sq"] = self._m_views[i], self._v_views[i]
+        return st
+
+    def load_state_dict(self, state_dict) -> None:
+        """``torch.optim.Adam``'s (or this class's) ``state_dict()``: the moments are copied into the flat buffers."""
+        super().load_state_dict(state_dict)
+        now = self.param_groups[0]["params"] if len(self.param_groups) == 1 else []
+        if len(now) != len(self._params) or any(a is not b for a, b in zip(now, self._params)):
+            raise ValueError("FusedAdam.load_state_dict: one param group over the same parameters")
+        for i, p in enumerate(self._params):
+            st = self.state.get(p)
+            if not st:
+                self._m_views[i].zero_()
+                self._v_views[i].zero_()
+                continue
+            if "max_exp_avg_sq" in st:
+                raise ValueError("FusedAdam.load_state_dict: amsgrad state is not supported")
+            self._m_views[i].copy_(st["exp_avg"])
+            self._v_views[i].copy_(st["exp_avg_sq"])
+            step = torch.as_tensor(st["step"]).detach().to(device="cpu", dtype=torch.float32).reshape(()).clone()
+            self._adopt(i, step)
+        self._key = None
+
+    def _check_group(self) -> dict:
+        g = self.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+            raise ValueError("FusedAdam: weight_decay, amsgrad and maximize are not offered")
+        return g
+
+    # -- the step ------------------------------------------------------------------------------------------------------------------
+    def _build(self, key, grads, target) -> None:
+        seg = self._table.seg
+        self._live = []
+        for i, p in enumerate(self._params):
+            g = grads[i]
+            if g is not None:
+                if not g.is_cuda or g.device != self._device or g.dtype != torch.float32 or g.shape != p.shape or not g.is_contiguous():
+                    raise ValueError("FusedAdam.step: gradients must be contiguous float32 tensors of the parameter's shape on its GPU")
+                self._live.append(i)
+            seg[i].param, seg[i].grad, seg[i].count = key[3 * i], key[3 * i + 1] or None, self._counts[i]
+            seg[i].target = key[3 * i + 2] or None
+        if target is not None:
+            for p, t in zip(self._params, target):
+                if t is not None and (t.device != self._device or t.dtype != torch.float32 or t.shape != p.shape or not t.is_contiguous()):
+                    raise ValueError("FusedAdam.step: targets must be contiguous float32 tensors of the parameter's shape on its GPU")
+        self._steps = [(self.state[self._params[i]] or self._adopt(i))["step"] for i in self._live]
+        counts = {int(s) for s in self._steps}      # host tensors: read here, once per table, and mirrored in self._t
+        if len(counts) > 1:
+            raise ValueError("FusedAdam.step: the parameters are at different step counts (one launch takes one bias correction)")
+        self._t = counts.pop() if counts else 0
+        self._key = key
+
+    @torch.no_grad()
+    def step(self, max_grad_norm: Optional[float] = None, grad_clamp: Optional[float] = None, target: Optional[Sequence[torch.Tensor]] = None,
+             tau: Optional[float] = None, want_norm: bool = False) -> Optional[torch.Tensor]:
+        """clamp -> norm clip -> Adam -> blend for every parameter that has a gradient, in one launch on the current stream; never
+        synchronises.  ``max_grad_norm``: ``clip_grad_norm_``'s (None: no clip); ``grad_clamp``: ``p.grad.clamp_(-c, c)`` first (None: no
+        clamp); ``target`` (tensors parallel to the parameters) with ``tau``: ``target = (1 - tau) target + tau p`` from the new p.
+        ``p.grad`` is NOT modified (module docstring).  -> the total norm of the (clamped) gradient, a 0-dim device tensor overwritten
+        by the next call, with ``want_norm``; None otherwise."""
+        group = self._check_group()
+        blend = target is not None and tau is not None and float(tau) > 0.0
+        if (target is None) != (tau is None):
+            raise ValueError("FusedAdam.step: target and tau go together")
+        if blend and len(target) != len(self._params):
+            raise ValueError("FusedAdam.step: target must list one tensor per parameter (%d), got %d" % (len(self._params), len(target)))
+        grads = [p.grad for p in self._params]
+        key = []
+        for i, p in enumerate(self._params):
+            g = grads[i]
+            t = target[i] if blend else None
+            key += [p.data_ptr(), g.data_ptr() if g is not None else 0, t.data_ptr() if t is not None else 0]
+        if key != self._key:      # autograd reallocates .grad: the table is rebuilt only when a pointer moved
+            self._build(key, grads, target if blend else None)
+        if not self._live:
+            return self._norm.zero_() if want_norm else None
+        t = self._t + 1
+        beta1, beta2 = group["betas"]
+        dev = self._device
+        with torch.cuda.device(dev):
+            rc = self._lib.mdr_adam_step(C.byref(self._table), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(), float(group["lr"]), float(beta1),
+                                         float(beta2), float(group["eps"]), t, float(max_grad_norm) if max_grad_norm is not None else 0.0,
+                                         float(grad_clamp) if grad_clamp is not None else math.inf, float(tau) if blend else 0.0,
+                                         self._workspace.data_ptr(), self._norm.data_ptr() if want_norm else None, self.max_fused_floats,
+                                         torch.cuda.current_stream(dev).cuda_stream)
+        nat.check(self._lib, None, rc, "mdr_adam_step")
+        self._t = t
+        torch._foreach_add_(self._steps, 1)      # host tensors, as torch.optim.Adam keeps them
+        return self._norm if want_norm else None

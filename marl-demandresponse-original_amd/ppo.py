@@ -4,7 +4,7 @@ The other half of the reference's train_ppo.py: ``PPO.update`` (agents/ppo.py:13
 leaves on the device.  Per minibatch the reference evaluates critic and actor, forms F.mse_loss and the clipped surrogate, calls
 ``backward()`` twice, clips both gradients and takes two Adam steps.  Here forward, loss and backward of one network are ONE HIP
 kernel on the matrix cores in exact fp32 (plus a small reduction): ``critic_loss_backward`` / ``actor_loss_backward`` fill the
-``.grad`` of an ``ActorMLP`` / ``CriticMLP``, torch keeps the gradient clipping and the optimiser.  ``PPOLearner`` is the loop.
+``.grad`` of an ``ActorMLP`` / ``CriticMLP``, torch keeps the gradient clipping and the optimiser (``optimizer=FusedAdam``, optim.py: one launch for both).  ``PPOLearner`` is the loop.
 Nothing on the call path synchronises with the host.
 """
 from __future__ import annotations
@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
+from .optim import FusedAdam
 
 MAX_STATE, MAX_HIDDEN = 64, 128      # the kernels' limits (include/mdr_policy.h: mdr_mlp_t)
 # backend="auto": the kernels from this many minibatch rows on (profiles/ppo_update_README.md: where they measured faster than autograd)
@@ -188,7 +189,9 @@ class PPOLearner:
 
     ``backend="hip"``: both losses and gradients from the kernels (ValueError for networks they refuse); ``"torch"``: the
     reference's expressions under autograd - the comparator and the fallback; ``"auto"``: the kernels where ``supported()`` holds
-    for both networks and the minibatch has at least ``AUTO_MIN_ROWS`` rows, torch otherwise."""
+    for both networks and the minibatch has at least ``AUTO_MIN_ROWS`` rows, torch otherwise.  ``optimizer``: called as
+    ``optimizer(params, lr)`` for each network; an optimiser that is a ``mdr_amd.optim.FusedAdam`` clips and steps in one launch
+    (``.grad`` then keeps the unclipped gradient), any other one is stepped after ``clip_grad_norm_``."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
                  ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam):
@@ -261,10 +264,19 @@ class PPOLearner:
             action_loss, value_loss = action_loss.detach(), value_loss.detach()
         if self.before_clip is not None:
             self.before_clip(self)
-        nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad_norm)
-        nn.utils.clip_grad_norm_(self.critic.parameters(), self.max_grad_norm)
-        self.actor_optimizer.step()
-        self.critic_optimizer.step()
+        fused_actor, fused_critic = isinstance(self.actor_optimizer, FusedAdam), isinstance(self.critic_optimizer, FusedAdam)
+        if not fused_actor:
+            nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad_norm)
+        if not fused_critic:
+            nn.utils.clip_grad_norm_(self.critic.parameters(), self.max_grad_norm)
+        if fused_actor:      # clip and step in one launch; .grad keeps the unclipped gradient (optim.py)
+            self.actor_optimizer.step(max_grad_norm=self.max_grad_norm)
+        else:
+            self.actor_optimizer.step()
+        if fused_critic:
+            self.critic_optimizer.step(max_grad_norm=self.max_grad_norm)
+        else:
+            self.critic_optimizer.step()
         self.training_step += 1
         return action_loss, value_loss
 

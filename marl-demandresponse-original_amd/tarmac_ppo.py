@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from .optim import FusedAdam
 from .ppo import PPOLearner, _workspace
 from .tarmac import FUSED_MAX_HIDDEN, FUSED_MAX_KEY, FUSED_MAX_OBS, FUSED_MAX_VALUE, MAX_COMM, MODES, TarMACActor
 
@@ -214,13 +215,19 @@ class TarMACPPOLearner:
             self.actor_optimizer.zero_grad()
             action_loss.backward()
             action_loss = action_loss.detach()
-        nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad_norm)
-        self.actor_optimizer.step()
+        if isinstance(self.actor_optimizer, FusedAdam):      # clip and step in one launch; .grad keeps the unclipped gradient (optim.py)
+            self.actor_optimizer.step(max_grad_norm=self.max_grad_norm)
+        else:
+            nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad_norm)
+            self.actor_optimizer.step()
         value_loss = torch.pow(delta, 2).mean(0).mean(0)
         self.critic_optimizer.zero_grad()
         value_loss.backward()
-        nn.utils.clip_grad_norm_(self.critic.parameters(), self.max_grad_norm)
-        self.critic_optimizer.step()
+        if isinstance(self.critic_optimizer, FusedAdam):      # autograd's own gradient tensors: the segment table covers them
+            self.critic_optimizer.step(max_grad_norm=self.max_grad_norm)
+        else:
+            nn.utils.clip_grad_norm_(self.critic.parameters(), self.max_grad_norm)
+            self.critic_optimizer.step()
         self.training_step += 1
         return action_loss, value_loss.detach()
 
