@@ -434,6 +434,80 @@ int mdr_dqn_grad(const mdr_mlp_t *policy_net, const float *state, int64_t ld_sta
                  const int64_t *action, const float *y, float grad_clamp, int32_t max_workgroups, void *workspace, float *grad,
                  float *loss, float *q, void *stream);
 
+/* ---- MADDPG's update step (MADDPG.update, agents/ddpg.py:305-339) with one shared actor, critic and target of each: for agent a the
+ * TD target through both target nets, the joint critic's mse loss and gradient, the gumbel-softmax actor's loss and gradient.  All
+ * four nets are DDPG_Network (agents/network.py:80-100) as mdr_mlp_t in torch's own layout, read as they are on every call.  The
+ * actor: num_state = F <= 64, num_out = 2.  The critic: num_state = J = nb_agents (F + 2) <= 1280, num_out = 1.  Every hidden layer
+ * <= 256 units, any size (no multiple of 16 needed): the reference's 20 x (51 + 2) = 1060 inputs with 256-256 hidden units and
+ * nb_agents = 1 are inside.  The weights do not fit LDS at these sizes, so this family streams them from L2 (mdr_maddpg_grad.hip) and
+ * is separate from the entry points above, whose limits and code are unchanged.
+ *
+ * Rows.  Minibatch row i < nb_rows is stored env-step j = index ? index[i] : i (`index` device int64, may be NULL).  An env-step
+ * holds `state` + j * ld_state: nb_agents F contiguous floats in agent order (ld_state >= nb_agents F); `action[j * nb_agents + k]`
+ * (int64, nonzero = action 1); `reward[j * nb_agents + k]`.  The critic's joint input is
+ *   x = state_j (nb_agents F floats) | onehot(action[j][0]) | ... | onehot(action[j][nb_agents - 1]),
+ * column nb_agents F + 2 k + c = (action[j][k] != 0) == c, gathered while a tile is staged and again by the weight gradient: no joint
+ * tensor is read or stored.  Gumbel noise is an input (float32, drawn by the caller as -log(Exp(1))): no kernel draws random numbers.
+ * The pick of logits l with noise g: t_c = (l_c + g_c) / tau, action 1 iff t_1 > t_0 (a tie: action 0, as max(dim)[1]); its forward
+ * value is the exact one-hot (torch's y_hard - y_soft.detach() + y_soft has the same bits in fp32).
+ *
+ * Common to the three calls: exact fp32 on v_mfma_f32_16x16x4_f32, no floating-point atomics, the same inputs and the same
+ * max_workgroups give the same bits on every call; every element of every given output is written by every successful call.  A row
+ * pass (one workgroup of 1024 threads per tile of 16 rows, a persistent grid of min(tiles, max_workgroups) workgroups; 0: the
+ * library's choice, min(tiles, compute units, 512)) does everything of a row; the gradient calls follow it with a weight pass, one
+ * wave per 16 x 16 block of a weight gradient, summing over the minibatch rows in row order (at most max_workgroups workgroups of
+ * four waves; 0: one wave per block).  Stream-ordered, never synchronise, allocate nothing.  There is no terminal mask: the
+ * reference's env never ends.
+ *
+ * Floats of the flat gradient of one net, dW1 | db1 | dW2 | db2 | dW3 | db3 in torch's parameter order and layout (host-only).  -1:
+ * num_state > 1280, a hidden layer > 256, num_out not 1 or 2, a struct_size that is not this header's. */
+int64_t mdr_maddpg_grad_floats(const mdr_mlp_t *net);
+/* Bytes of device scratch mdr_maddpg_critic_grad or mdr_maddpg_actor_grad needs over nb_rows rows (the larger of the two; h1, h2,
+ * dz1, dz2 of the differentiated net, dlogits and the rows' loss terms; host-only, independent of max_workgroups).  -1: shapes
+ * outside the limits or that do not fit each other (critic->num_state != nb_agents (actor->num_state + 2)), nb_rows < 0,
+ * max_workgroups < 0. */
+int64_t mdr_maddpg_workspace_bytes(const mdr_mlp_t *actor, const mdr_mlp_t *critic, int32_t nb_agents, int64_t nb_rows,
+                                   int32_t max_workgroups);
+
+/* The TD target of agent `agent` (ddpg.py:132-142, 282-284, 317-322).  next_action[i][k] = the pick on tgt_actor(next_state_j's F
+ * floats of agent k) with noise[i][k][0..1]; x' = next_state_j | onehot(next_action[i][.]); next_q[i] = tgt_critic(x');
+ *   y[i] = reward[j][agent] + gamma * next_q[i]      (the product and the sum each rounded to fp32, no fma)
+ * `y` float [nb_rows], `next_q` (may be NULL) float [nb_rows], `next_action` uint8 [nb_rows][nb_agents] (required: the second launch
+ * reads what the first wrote).  Two launches: the picks over the nb_rows nb_agents actor rows, then the critic's forward.  No
+ * workspace.  nb_rows == 0 launches nothing.
+ * Returns 0; -1 (a NULL required pointer, nb_agents < 1, nets that do not fit each other, ld_state < nb_agents F, agent outside
+ * [0, nb_agents), nb_rows < 0, max_workgroups < 0, tau <= 0 or not finite, gamma not finite, a struct_size that is not this
+ * header's); -3 (HIP error); -4 (a shape outside the limits).  On -1 and -4 nothing was launched and nothing written. */
+int mdr_maddpg_target(const mdr_mlp_t *tgt_actor, const mdr_mlp_t *tgt_critic, const float *next_state, int64_t ld_state,
+                      const float *reward, const int64_t *index, int64_t nb_rows, int32_t nb_agents, int32_t agent, const float *noise,
+                      float tau, float gamma, int32_t max_workgroups, float *y, float *next_q, uint8_t *next_action, void *stream);
+
+/* The critic's step (ddpg.py:312-327): q_i = critic(x_i), loss = (1 / nb_rows) sum_i (q_i - y_i)^2 (F.mse_loss), `grad`
+ * (mdr_maddpg_grad_floats(critic) floats) = d loss / d parameters as autograd takes it, relu'(z) = 1 iff z > 0.  `y` float [nb_rows]
+ * in minibatch order (mdr_maddpg_target's, detached); `q` (may be NULL) float [nb_rows].  `loss`: one float on the device.
+ * `workspace`: 16-byte aligned device memory of mdr_maddpg_workspace_bytes, owned by the caller, its contents free before and after
+ * the call.  Two launches: row pass, weight pass.  nb_rows == 0 writes zeros to `grad` and `loss` (the weight pass alone).
+ * Returns 0; -1 (a NULL required pointer, nb_agents < 1, critic->num_state not nb_agents (F + 2) with F >= 1, ld_state < nb_agents F,
+ * nb_rows < 0, max_workgroups < 0, a struct_size that is not this header's, a missing or misaligned workspace); -3; -4 (a shape
+ * outside the limits, num_out != 1).  On -1 and -4 nothing was launched and nothing written. */
+int mdr_maddpg_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *action, const int64_t *index,
+                           int64_t nb_rows, int32_t nb_agents, const float *y, int32_t max_workgroups, void *workspace, float *grad,
+                           float *loss, float *q, void *stream);
+
+/* The actor's step for agent a = `agent` (ddpg.py:331-339).  l = actor(state_j's F floats of agent a), t = (l + noise[i][0..1]) / tau,
+ * p = softmax(t), h the pick; x_i with columns nb_agents F + 2 a, + 1 replaced by onehot(h); Q_i = critic(x_i);
+ *   loss = -(1 / nb_rows) sum_i Q_i + pse (1 / (2 nb_rows)) sum_i (l_0^2 + l_1^2)      (the reference: pse = 1e-3)
+ * and `grad` (mdr_maddpg_grad_floats(actor) floats) = d loss / d the ACTOR's parameters through the straight-through estimator: with
+ * c_o = d loss / d x_i[nb_agents F + 2 a + o] (the critic's backward down to those two input columns only),
+ *   dl_0 = p_0 p_1 (c_0 - c_1) / tau + pse l_0 / nb_rows,   dl_1 = -p_0 p_1 (c_0 - c_1) / tau + pse l_1 / nb_rows.
+ * The critic is only read: no gradient of it is written.  `q` (may be NULL) float [nb_rows]: Q_i; `logits` (may be NULL) float
+ * [nb_rows][2].  `workspace`, launches (two), zero rows and return codes as mdr_maddpg_critic_grad; -1 also for agent outside
+ * [0, nb_agents), tau <= 0 or not finite, pse not finite, nets that do not fit each other; -4 also for actor->num_out != 2. */
+int mdr_maddpg_actor_grad(const mdr_mlp_t *actor, const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *action,
+                          const int64_t *index, int64_t nb_rows, int32_t nb_agents, int32_t agent, const float *noise, float tau,
+                          float pse, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *q, float *logits,
+                          void *stream);
+
 /* ---- TarMAC-PPO's update step for the actor (TarmacPPO.update, agents/tarmac_ppo.py:168-186): loss and gradient of one minibatch.
  *
  * The actor's weights in torch's own layout - every layer w[out][in] contiguous and its bias, device memory, read as they are on

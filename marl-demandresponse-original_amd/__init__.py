@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("BatchedDemandResponseEnv", "OBS_COLUMNS"):
         from . import batched_env
         return getattr(batched_env, name)
-    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "optim"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
+    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "maddpg", "optim"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "BatchedMetrics":
@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ("DQNLearner", "QNetworkMLP", "DeviceReplayBuffer"):
         from . import dqn
         return getattr(dqn, name)
+    if name in ("MADDPGLearner", "DDPGNetworkMLP", "JointReplayBuffer", "GreedyDDPGActor", "train_maddpg"):
+        from . import maddpg
+        return getattr(maddpg, name)
     if name == "TarMACPPOLearner":
         from .tarmac_ppo import TarMACPPOLearner
         return TarMACPPOLearner

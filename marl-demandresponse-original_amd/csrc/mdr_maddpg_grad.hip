@@ -1,0 +1,645 @@
+// MADDPG's update step (include/mdr_policy.h: mdr_maddpg_target, mdr_maddpg_critic_grad, mdr_maddpg_actor_grad): the wide joint critic
+// and the gumbel-softmax actor of agents/ddpg.py:305-339, weights streamed from L2.
+//
+// Reference: MADDPG.update evaluates, per agent a, the target actor on every agent's next state (a hard gumbel-softmax pick each), the
+// target critic on cat(next states, picks), the critic's mse loss against y = r_a + gamma Q', and the actor's loss -mean Q(states,
+// actions with a's replaced by its own straight-through sample) + 1e-3 mean(logits^2).  Both nets are DDPG_Network
+// (agents/network.py:80-100): Linear - ReLU - Linear - ReLU - Linear with 256 hidden units, the critic on J = N (F + 2) inputs - 1060 at
+// the reference's 20 agents.  W1 is then 1 MB and W2 256 KB: neither fits the 160 KB of LDS mdr_ppo_grad.hip keeps its weights in, and one
+// partial gradient per workgroup would be 1.4 MB each.  So this family has two kinds of kernel:
+//
+//   row pass     one workgroup of 16 waves per tile of 16 minibatch rows.  Wave w owns the 16-unit block w of every hidden layer (H <=
+//                256: at most 16 blocks).  The MFMA A operand - the weights, torch's [out][in] layout - comes from global memory (L2): a
+//                workgroup meets every weight once per tile, so staging it in LDS buys no reuse.  The B operand - the tile's activations,
+//                transposed [unit][row] with row stride LT = 20 - comes from LDS; the joint input is staged in chunks of KC = 128
+//                columns while the first layer's accumulators stay in registers.  Everything of a row happens here: forward, the head
+//                (pick / TD target / mse / the actor's loss), the backward down to dz1.  What the weight gradients need - h1, h2, dz1,
+//                dz2 [row][unit], dlogits, the rows' loss terms - is left in the workspace.
+//   weight pass  one wave per 16 x 16 block of a weight gradient: dW[m][n] = sum_r dz[r][m] in[r][n] over the minibatch rows in row
+//                order, k = the rows on v_mfma_f32_16x16x4_f32 - no partials, no floating-point atomics, the same bits whatever the
+//                grid.  The first layer's input is gathered again from `state` / `action` through `index`, never stored.  The blocks
+//                of column 0 also take the bias (the same product against ones); one more wave sums the loss terms.
+//
+// Exact fp32 on v_mfma_f32_16x16x4_f32 (A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15], C/D: col = l & 15, row = 4 (l >> 4) +
+// reg).  relu'(z) = 1 iff z > 0 iff relu(z) > 0, so the backward reads the activations, not z.  Rows past the minibatch are forwarded as
+// zero inputs and given zero dlogits: they add exact zeros.  The 1 / B of the mean sits in dlogits, as autograd has it.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/mdr.h"
+#include "../../include/mdr_policy.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int NW = 16;                // waves per row-pass workgroup = the most 16-unit blocks of a hidden layer
+constexpr int TILE = 16;              // minibatch rows per tile
+constexpr int LT = 20;                // row stride of the transposed tile images
+constexpr int KC = 128;               // joint-input columns staged at a time
+constexpr int MAX_F = 64, MAX_H = 256, MAX_J = 1280;
+constexpr int LIB_MAX_WG = 512;       // the library's own grid: min(work items, CUs, this)
+constexpr int WW = 4;                 // waves per weight-pass workgroup
+constexpr int UNR_W = 8;              // weight pass: MFMA k-steps whose global operands are loaded together
+
+// LDS of the row pass (floats): the input chunk, four activation images, the heads' partial sums, the tile's picks
+constexpr int S_X = 0, S_A0 = S_X + KC * LT, S_A1 = S_A0 + MAX_H * LT, S_C0 = S_A1 + MAX_H * LT, S_C1 = S_C0 + MAX_H * LT,
+              S_LP = S_C1 + MAX_H * LT, S_PK = S_LP + NW * TILE * 2, S_END = S_PK + TILE;
+
+__host__ __device__ inline int blocks16(int n) { return (n + 15) / 16; }
+
+struct Net {
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+  int K, H1, H2, O;
+};
+
+enum Mode : int { MODE_PICK = 0, MODE_TARGET = 1, MODE_CRITIC = 2, MODE_ACTOR = 3 };
+
+struct RowArgs {
+  Net actor, critic;
+  const float* state;         // the buffer's state (next_state for the target): env-step j at state + j * ld
+  int64_t ld;
+  const int64_t* action;      // [env-steps][N]
+  const int64_t* index;
+  int64_t B;                  // minibatch rows
+  int64_t R, ntiles;          // rows of this launch (MODE_PICK: B * N) and its tiles
+  int N, F, agent;
+  const float* noise;         // MODE_PICK: [B][N][2]; MODE_ACTOR: [B][2]
+  float tau, gamma, pse, invB;
+  const float* reward;        // [env-steps][N]
+  const float* y;             // MODE_CRITIC: [B]
+  uint8_t* picks;             // [B][N]: MODE_PICK writes, MODE_TARGET reads
+  float *out0, *out1;         // TARGET: y, next_q; CRITIC: q; ACTOR: q, logits
+  float *h1, *h2, *dz1, *dz2, *dl, *term;      // workspace of the net whose gradient is taken: [Rp][H1p], [Rp][H2p], ..., [Rp][2], [Rp]
+};
+
+__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// acc[unit u0 + 4 g + i][row c] += sum_{k < kn} W[u0 + m][k0 + k] inT[k][row]; inT zero from kn up to the next multiple of 4
+template <int UNR>
+__device__ __forceinline__ void fwd_accum(f32x4& acc, const float* __restrict__ W, int ldw, int H, int u0, int k0, int kn, const float* inT,
+                                          int c, int g) {
+  const int u = u0 + c;
+  const bool uok = u < H;
+  const float* wr = W + (int64_t)(uok ? u : 0) * ldw + k0;
+  const int ks = (kn + 3) >> 2;
+  for (int q0 = 0; q0 < ks; q0 += UNR) {      // UNR k-steps' weights asked for together
+    float av[UNR];
+#pragma unroll
+    for (int i = 0; i < UNR; ++i) {
+      const int kk = 4 * (q0 + i) + g;
+      av[i] = (uok && kk < kn) ? wr[kk] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < UNR; ++i)
+      if (q0 + i < ks) acc = mfma(av[i], inT[(4 * (q0 + i) + g) * LT + c], acc);
+  }
+}
+
+__device__ __forceinline__ f32x4 bias_block(const float* __restrict__ b, int H, int u0, int g) {
+  f32x4 acc;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) acc[i] = (u0 + 4 * g + i < H) ? b[u0 + 4 * g + i] : 0.0f;
+  return acc;
+}
+
+// the block's values into the LDS image and, where asked, the workspace [row][Hp]
+__device__ __forceinline__ void store_block(const f32x4& v, float* imgT, float* ws, int Hp, int64_t row, int u0, int c, int g) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) imgT[(u0 + 4 * g + i) * LT + c] = v[i];
+  if (ws) *reinterpret_cast<f32x4*>(ws + row * Hp + u0 + 4 * g) = v;
+}
+
+// dzin[k0 + 4 g + i][row c] = relu'(hin) sum_{u < Hout} W[u][k0 + m] dzout[u][row], in place of hin's image
+template <int UNR>
+__device__ __forceinline__ void bwd_block(const float* __restrict__ W, int Hout, int Hin, int k0, const float* dzoutT, float* hinT, float* ws, int Hp,
+                                          int64_t row, int c, int g) {
+  f32x4 acc = {0, 0, 0, 0};
+  const int kc = k0 + c;
+  const bool kok = kc < Hin;
+  const float* wc = W + (kok ? kc : 0);
+  const int ks = 4 * blocks16(Hout);
+  for (int q0 = 0; q0 < ks; q0 += UNR) {
+    float av[UNR];
+#pragma unroll
+    for (int i = 0; i < UNR; ++i) {
+      const int u = 4 * (q0 + i) + g;
+      av[i] = (kok && u < Hout) ? wc[(int64_t)u * Hin] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < UNR; ++i)
+      if (q0 + i < ks) acc = mfma(av[i], dzoutT[(4 * (q0 + i) + g) * LT + c], acc);      // ks is a multiple of 4, not of UNR
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) acc[i] = hinT[(k0 + 4 * g + i) * LT + c] > 0.0f ? acc[i] : 0.0f;
+  store_block(acc, hinT, ws, Hp, row, k0, c, g);
+}
+
+// the wave's share of two dot products over its block of vT: sum_u coef_o[u * su] vT[u][row c] -> lp[w][row][o]
+__device__ __forceinline__ void dot2_share(const float* vT, const float* __restrict__ coef0, const float* __restrict__ coef1, int64_t su, int H, float* lp,
+                                           int w, int c, int g) {
+  float p0 = 0.0f, p1 = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int u = 16 * w + 4 * g + i;
+    if (u < H) {
+      const float v = vT[u * LT + c];
+      p0 = fmaf(coef0[u * su], v, p0);
+      if (coef1) p1 = fmaf(coef1[u * su], v, p1);
+    }
+  }
+  p0 += __shfl_xor(p0, 16);
+  p0 += __shfl_xor(p0, 32);
+  p1 += __shfl_xor(p1, 16);
+  p1 += __shfl_xor(p1, 32);
+  if (g == 0) {
+    lp[(w * TILE + c) * 2] = p0;
+    lp[(w * TILE + c) * 2 + 1] = p1;
+  }
+}
+
+// the blocks' shares in block order: the same bits in every lane of row c
+__device__ __forceinline__ void dot2_sum(const float* lp, int nb, int c, float& s0, float& s1) {
+  s0 = 0.0f, s1 = 0.0f;
+  for (int b = 0; b < nb; ++b) {
+    s0 += lp[(b * TILE + c) * 2];
+    s1 += lp[(b * TILE + c) * 2 + 1];
+  }
+}
+
+template <Mode MODE>
+__global__ __launch_bounds__(64 * NW) void k_maddpg_rows(RowArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
+  float* xT = lds + S_X;
+  float* a0T = lds + S_A0;      // the actor's h1, then dz1
+  float* a1T = lds + S_A1;      // the actor's h2, then dz2
+  float* c0T = lds + S_C0;      // the critic's h1, then dz1
+  float* c1T = lds + S_C1;      // the critic's h2, then dz2
+  float* lp = lds + S_LP;
+  float* pk = lds + S_PK;       // MODE_ACTOR: the tile's picks of agent a, 0 / 1
+  // weights in flight per wave (MFMA k-steps loaded together); the actor's step holds more live state, so fewer fit its 128 registers
+  constexpr int UNR = MODE == MODE_ACTOR ? 4 : 8;
+  constexpr bool HAS_ACTOR = MODE == MODE_PICK || MODE == MODE_ACTOR;
+  constexpr bool HAS_CRITIC = MODE != MODE_PICK;
+  const Net& A = a.actor;
+  const Net& Cn = a.critic;
+  const int NF = a.N * a.F;
+
+  for (int64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+    const int64_t row = t * TILE + c;      // the row this lane's MFMA column and head work belong to
+    const bool valid = row < a.R;
+    float l0 = 0.0f, l1 = 0.0f, p0 = 0.0f, p1 = 0.0f;
+    bool pick = false;
+
+    if constexpr (HAS_ACTOR) {
+      // ---- the actor's input: F floats of agent k of env-step j
+      for (int e = tid; e < TILE * MAX_F; e += 64 * NW) {
+        const int r = e / MAX_F, f = e - r * MAX_F;
+        const int64_t rr = t * TILE + r;
+        float v = 0.0f;
+        if (f < a.F && rr < a.R) {
+          const int64_t i = MODE == MODE_PICK ? rr / a.N : rr;
+          const int k = MODE == MODE_PICK ? (int)(rr - i * a.N) : a.agent;
+          const int64_t j = a.index ? a.index[i] : i;
+          v = a.state[j * a.ld + (int64_t)k * a.F + f];
+        }
+        xT[f * LT + r] = v;
+      }
+      __syncthreads();
+      const int nb1 = blocks16(A.H1), nb2 = blocks16(A.H2);
+      float* wsh1 = MODE == MODE_ACTOR ? a.h1 : nullptr;
+      float* wsh2 = MODE == MODE_ACTOR ? a.h2 : nullptr;
+      if (w < nb1) {
+        f32x4 acc = bias_block(A.b1, A.H1, 16 * w, g);
+        fwd_accum<UNR>(acc, A.w1, A.K, A.H1, 16 * w, 0, A.K, xT, c, g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fmaxf(acc[i], 0.0f);
+        store_block(acc, a0T, wsh1, 16 * nb1, row, 16 * w, c, g);
+      }
+      __syncthreads();
+      if (w < nb2) {
+        f32x4 acc = bias_block(A.b2, A.H2, 16 * w, g);
+        fwd_accum<UNR>(acc, A.w2, A.H1, A.H2, 16 * w, 0, A.H1, a0T, c, g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fmaxf(acc[i], 0.0f);
+        store_block(acc, a1T, wsh2, 16 * nb2, row, 16 * w, c, g);
+        dot2_share(a1T, A.w3, A.w3 + A.H2, 1, A.H2, lp, w, c, g);      // the lane's own four units: its own stores
+      }
+      __syncthreads();
+      dot2_sum(lp, nb2, c, l0, l1);
+      l0 += A.b3[0];
+      l1 += A.b3[1];
+      // F.gumbel_softmax(logits, tau, hard=True): t = (logits + g) / tau, the pick its argmax (a tie: action 0), p = softmax(t)
+      float t0 = 0.0f, t1 = 0.0f;
+      if (valid) {
+        const float sum0 = l0 + a.noise[row * 2], sum1 = l1 + a.noise[row * 2 + 1];
+        t0 = sum0 / a.tau;
+        t1 = sum1 / a.tau;
+      }
+      pick = t1 > t0;
+      if constexpr (MODE == MODE_PICK) {
+        if (valid && w == 0 && g == 0) a.picks[row] = pick ? 1 : 0;
+        __syncthreads();      // xT, lp and the images are rewritten by the next tile
+        continue;
+      }
+      p1 = 1.0f / (1.0f + expf(t0 - t1));
+      p0 = 1.0f / (1.0f + expf(t1 - t0));
+      if (w == 0 && g == 0) pk[c] = pick ? 1.0f : 0.0f;
+      if (valid && w == 0 && g == 0 && a.out1) {
+        a.out1[row * 2] = l0;
+        a.out1[row * 2 + 1] = l1;
+      }
+    }
+
+    if constexpr (HAS_CRITIC) {
+      const int nb1 = blocks16(Cn.H1), nb2 = blocks16(Cn.H2);
+      const int J = Cn.K;
+      float* wsh1 = MODE == MODE_CRITIC ? a.h1 : nullptr;
+      float* wsh2 = MODE == MODE_CRITIC ? a.h2 : nullptr;
+      // ---- F1 over the joint input x = state_j (N F floats) | onehot(action of agent 0) | ... in chunks of KC columns
+      f32x4 acc = bias_block(Cn.b1, Cn.H1, 16 * w, g);
+      for (int k0 = 0; k0 < J; k0 += KC) {
+        const int kn = J - k0 < KC ? J - k0 : KC;
+        __syncthreads();      // the chunk before (or the actor's input, or pk) is read
+        for (int e = tid; e < TILE * KC; e += 64 * NW) {
+          const int r = e / KC, f = e - r * KC, col = k0 + f;
+          const int64_t rr = t * TILE + r;
+          float v = 0.0f;
+          if (col < J && rr < a.B) {
+            const int64_t j = a.index ? a.index[rr] : rr;
+            if (col < NF) {
+              v = a.state[j * a.ld + col];
+            } else {
+              const int k = (col - NF) >> 1, bit = (col - NF) & 1;
+              int act;
+              if (MODE == MODE_TARGET) act = a.picks[rr * a.N + k] != 0;
+              else if (MODE == MODE_ACTOR && k == a.agent) act = pk[r] != 0.0f;
+              else act = a.action[j * a.N + k] != 0;
+              v = act == bit ? 1.0f : 0.0f;
+            }
+          }
+          xT[f * LT + r] = v;
+        }
+        __syncthreads();
+        if (w < nb1) fwd_accum<UNR>(acc, Cn.w1, J, Cn.H1, 16 * w, k0, kn, xT, c, g);
+      }
+      if (w < nb1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fmaxf(acc[i], 0.0f);
+        store_block(acc, c0T, wsh1, 16 * nb1, row, 16 * w, c, g);
+      }
+      __syncthreads();
+      if (w < nb2) {
+        f32x4 z = bias_block(Cn.b2, Cn.H2, 16 * w, g);
+        fwd_accum<UNR>(z, Cn.w2, Cn.H1, Cn.H2, 16 * w, 0, Cn.H1, c0T, c, g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) z[i] = fmaxf(z[i], 0.0f);
+        store_block(z, c1T, wsh2, 16 * nb2, row, 16 * w, c, g);
+        dot2_share(c1T, Cn.w3, nullptr, 1, Cn.H2, lp, w, c, g);
+      }
+      __syncthreads();
+      float q, unused;
+      dot2_sum(lp, nb2, c, q, unused);
+      q += Cn.b3[0];
+
+      if constexpr (MODE == MODE_TARGET) {
+        // ddpg.py:317-322: y = reward_a + gamma Q'; the product and the sum are two statements, each rounds on its own
+        if (valid && w == 0 && g == 0) {
+          const int64_t j = a.index ? a.index[row] : row;
+          const float discounted = a.gamma * q;
+          a.out0[row] = a.reward[j * a.N + a.agent] + discounted;
+          if (a.out1) a.out1[row] = q;
+        }
+        __syncthreads();
+        continue;
+      }
+
+      // ---- the head: d loss / d q of the row
+      float dq = 0.0f, term = 0.0f;
+      if (valid) {
+        if constexpr (MODE == MODE_CRITIC) {
+          const float delta = q - a.y[row];      // F.mse_loss(q, y)
+          term = delta * delta;
+          const float twice = 2.0f * delta;
+          dq = twice * a.invB;
+        } else {
+          dq = -a.invB;                          // -critic(...).mean()
+        }
+        if (w == 0 && g == 0 && a.out0) a.out0[row] = q;
+      }
+      // dz2 = relu'(z2) dq W3, in place of h2's image
+      if (w < nb2) {
+        f32x4 d;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int u = 16 * w + 4 * g + i;
+          d[i] = (u < Cn.H2 && c1T[u * LT + c] > 0.0f) ? dq * Cn.w3[u] : 0.0f;
+        }
+        store_block(d, c1T, MODE == MODE_CRITIC ? a.dz2 : nullptr, 16 * nb2, row, 16 * w, c, g);
+      }
+      __syncthreads();
+      if (w < nb1) bwd_block<UNR>(Cn.w2, Cn.H2, Cn.H1, 16 * w, c1T, c0T, MODE == MODE_CRITIC ? a.dz1 : nullptr, 16 * nb1, row, c, g);
+
+      if constexpr (MODE == MODE_CRITIC) {
+        if (w == 0 && g == 0) {
+          a.dl[row * 2] = dq;
+          a.dl[row * 2 + 1] = 0.0f;
+          a.term[row] = term;
+        }
+        __syncthreads();
+        continue;
+      }
+
+      if constexpr (MODE == MODE_ACTOR) {
+        // c_o = dz1 . W1[:, N F + 2 a + o]: the two input columns the actor's sample feeds, nothing else of W1^T dz1
+        const float* col0 = Cn.w1 + NF + 2 * a.agent;
+        if (w < nb1) dot2_share(c0T, col0, col0 + 1, J, Cn.H1, lp, w, c, g);      // the lane's own stores of bwd_block
+        __syncthreads();
+        float cc0, cc1;
+        dot2_sum(lp, nb1, c, cc0, cc1);
+        // through y_soft = softmax(t): dl_0 = p0 p1 (c0 - c1) / tau + pse l0 / B, dl_1 the negative + pse l1 / B
+        float d0 = 0.0f, d1 = 0.0f;
+        if (valid) {
+          const float pp = p0 * p1;
+          const float diff = cc0 - cc1;
+          const float s = pp * diff / a.tau;
+          const float r0 = a.pse * l0 * a.invB, r1 = a.pse * l1 * a.invB;
+          d0 = s + r0;
+          d1 = r1 - s;
+          const float sq = l0 * l0 + l1 * l1;
+          term = 0.5f * a.pse * sq - q;
+        }
+        const int nba1 = blocks16(A.H1), nba2 = blocks16(A.H2);
+        if (w < nba2) {
+          f32x4 d;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int u = 16 * w + 4 * g + i;
+            d[i] = (u < A.H2 && a1T[u * LT + c] > 0.0f) ? fmaf(d0, A.w3[u], d1 * A.w3[A.H2 + u]) : 0.0f;
+          }
+          store_block(d, a1T, a.dz2, 16 * nba2, row, 16 * w, c, g);
+        }
+        __syncthreads();
+        if (w < nba1) bwd_block<UNR>(A.w2, A.H2, A.H1, 16 * w, a1T, a0T, a.dz1, 16 * nba1, row, c, g);
+        if (w == 0 && g == 0) {
+          a.dl[row * 2] = d0;
+          a.dl[row * 2 + 1] = d1;
+          a.term[row] = term;
+        }
+        __syncthreads();
+      }
+    }
+  }
+}
+
+// ---- the weight pass
+struct WeightArgs {
+  int K, H1, H2, O;            // of the net whose gradient is taken
+  int H1p, H2p;
+  const float *h1, *h2, *dz1, *dz2, *dl, *term;
+  const float* state;
+  int64_t ld;
+  const int64_t* action;
+  const int64_t* index;
+  int64_t B, Bp;
+  int N, F, agent;             // agent < 0: the joint input (the critic's); else the F floats of that agent (the actor's)
+  float* grad;
+  float* loss;
+  int nbk, nb1, nb2;           // 16-blocks of K, H1, H2
+};
+
+__global__ __launch_bounds__(64 * WW) void k_maddpg_weights(WeightArgs a) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int n1 = a.nb1 * a.nbk, n2 = a.nb2 * a.nb1, n3 = a.nb2;
+  const int total = n1 + n2 + n3 + 1;
+  const int oW1 = 0, ob1 = a.H1 * a.K, oW2 = ob1 + a.H1, ob2 = oW2 + a.H2 * a.H1, oW3 = ob2 + a.H2, ob3 = oW3 + a.O * a.H2;
+  const int NF = a.N * a.F;
+  for (int blk = blockIdx.x * WW + w; blk < total; blk += gridDim.x * WW) {
+    if (blk == total - 1) {
+      // the loss: 64 strided sums, added in lane order
+      float s = 0.0f;
+      for (int64_t r = lane; r < a.B; r += 64) s += a.term[r];
+      float sum = 0.0f;
+      for (int l = 0; l < 64; ++l) sum += __shfl(s, l);
+      if (lane == 0) *a.loss = a.B > 0 ? sum / (float)a.B : 0.0f;
+      continue;
+    }
+    int layer, mb, nbk;
+    if (blk < n1) layer = 0, mb = blk / a.nbk, nbk = blk - mb * a.nbk;
+    else if (blk < n1 + n2) layer = 1, mb = (blk - n1) / a.nb1, nbk = (blk - n1) - mb * a.nb1;
+    else layer = 2, mb = 0, nbk = blk - n1 - n2;
+    const int M = layer == 0 ? a.H1 : layer == 1 ? a.H2 : a.O;
+    const int Nn = layer == 0 ? a.K : layer == 1 ? a.H1 : a.H2;
+    const float* dz = layer == 0 ? a.dz1 : layer == 1 ? a.dz2 : a.dl;
+    const int ldz = layer == 0 ? a.H1p : layer == 1 ? a.H2p : 2;
+    const float* in = layer == 1 ? a.h1 : a.h2;
+    const int lin = layer == 1 ? a.H1p : a.H2p;
+    const int m = 16 * mb + c, n = 16 * nbk + c;
+    const bool mok = m < M, nok = n < Nn;
+    f32x4 acc = {0, 0, 0, 0}, accb = {0, 0, 0, 0};
+    for (int64_t r0 = 0; r0 < a.Bp; r0 += 4 * UNR_W) {      // UNR_W k-steps of four rows, their operands in flight together
+      float av[UNR_W], bv[UNR_W];
+#pragma unroll
+      for (int i = 0; i < UNR_W; ++i) {
+        const int64_t r = r0 + 4 * i + g;
+        av[i] = 0.0f, bv[i] = 0.0f;
+        if (r < a.Bp) {
+          if (mok) av[i] = dz[r * ldz + m];
+          if (layer != 0) {
+            if (nok) bv[i] = in[r * lin + n];
+          } else if (nok && r < a.B) {
+            const int64_t j = a.index ? a.index[r] : r;
+            if (a.agent >= 0) bv[i] = a.state[j * a.ld + (int64_t)a.agent * a.F + n];
+            else if (n < NF) bv[i] = a.state[j * a.ld + n];
+            else bv[i] = ((a.action[j * a.N + ((n - NF) >> 1)] != 0) == (bool)((n - NF) & 1)) ? 1.0f : 0.0f;
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < UNR_W; ++i) {      // rows past Bp add exact zeros
+        acc = mfma(av[i], bv[i], acc);
+        if (nbk == 0) accb = mfma(av[i], 1.0f, accb);
+      }
+    }
+    float* dW = a.grad + (layer == 0 ? oW1 : layer == 1 ? oW2 : oW3);
+    float* db = a.grad + (layer == 0 ? ob1 : layer == 1 ? ob2 : ob3);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int mm = 16 * mb + 4 * g + i;
+      if (mm < M) {
+        if (nok) dW[(int64_t)mm * Nn + n] = acc[i];
+        if (nbk == 0 && c == 0) db[mm] = accb[i];
+      }
+    }
+  }
+}
+
+bool fields_ok(const mdr_mlp_t* n) {
+  return n && n->struct_size == sizeof(mdr_mlp_t) && n->num_state > 0 && n->hidden1 > 0 && n->hidden2 > 0 && n->num_out > 0;
+}
+bool pointers_ok(const mdr_mlp_t* n) { return n->w1 && n->b1 && n->w2 && n->b2 && n->w3 && n->b3; }
+bool covered(const mdr_mlp_t* n) {
+  return n->num_state <= MAX_J && n->hidden1 <= MAX_H && n->hidden2 <= MAX_H && (n->num_out == 1 || n->num_out == 2);
+}
+// MDR_OK, MDR_ERR_INVALID or MDR_ERR_UNSUPPORTED for the pair of nets of one call (actor may be null: the critic's step)
+int pair_shape(const mdr_mlp_t* actor, const mdr_mlp_t* critic, int32_t nb_agents) {
+  if ((actor && !fields_ok(actor)) || !fields_ok(critic) || nb_agents < 1) return MDR_ERR_INVALID;
+  if (critic->num_state % nb_agents != 0 || critic->num_state / nb_agents < 3) return MDR_ERR_INVALID;      // J = N (F + 2), F >= 1
+  const int F = critic->num_state / nb_agents - 2;
+  if (actor && actor->num_state != F) return MDR_ERR_INVALID;
+  if (!covered(critic) || critic->num_out != 1 || F > MAX_F) return MDR_ERR_UNSUPPORTED;
+  if (actor && (!covered(actor) || actor->num_out != 2)) return MDR_ERR_UNSUPPORTED;
+  return MDR_OK;
+}
+
+Net make_net(const mdr_mlp_t* n) { return Net{n->w1, n->b1, n->w2, n->b2, n->w3, n->b3, n->num_state, n->hidden1, n->hidden2, n->num_out}; }
+
+int64_t grad_floats(const mdr_mlp_t* n) {
+  return (int64_t)n->hidden1 * n->num_state + n->hidden1 + (int64_t)n->hidden2 * n->hidden1 + n->hidden2 + (int64_t)n->num_out * n->hidden2 + n->num_out;
+}
+
+int64_t pad16(int64_t n) { return (n + 15) / 16 * 16; }
+
+// floats of the workspace the gradient of `n` over nb_rows rows takes: h1, dz1 [Bp][H1p], h2, dz2 [Bp][H2p], dl [Bp][2], term [Bp]
+int64_t ws_floats(const mdr_mlp_t* n, int64_t nb_rows) {
+  const int64_t Bp = pad16(nb_rows);
+  return Bp * (2 * pad16(n->hidden1) + 2 * pad16(n->hidden2) + 3);
+}
+
+int lib_cap(int32_t max_workgroups) {
+  if (max_workgroups > 0) return max_workgroups;
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  return cus < LIB_MAX_WG ? cus : LIB_MAX_WG;
+}
+
+template <Mode MODE>
+int launch_rows(const RowArgs& a, int cap, hipStream_t st) {
+  const size_t bytes = (size_t)S_END * sizeof(float);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_maddpg_rows<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return MDR_ERR_HIP;
+  const int64_t grid = a.ntiles < cap ? a.ntiles : cap;
+  hipLaunchKernelGGL(k_maddpg_rows<MODE>, dim3((unsigned)grid), dim3(64 * NW), bytes, st, a);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+void carve(RowArgs& r, WeightArgs& wa, const mdr_mlp_t* n, void* workspace, int64_t nb_rows) {
+  const int64_t Bp = pad16(nb_rows), H1p = pad16(n->hidden1), H2p = pad16(n->hidden2);
+  float* p = static_cast<float*>(workspace);
+  r.h1 = p, p += Bp * H1p;
+  r.dz1 = p, p += Bp * H1p;
+  r.h2 = p, p += Bp * H2p;
+  r.dz2 = p, p += Bp * H2p;
+  r.dl = p, p += Bp * 2;
+  r.term = p;
+  wa.K = n->num_state, wa.H1 = n->hidden1, wa.H2 = n->hidden2, wa.O = n->num_out, wa.H1p = (int)H1p, wa.H2p = (int)H2p;
+  wa.h1 = r.h1, wa.h2 = r.h2, wa.dz1 = r.dz1, wa.dz2 = r.dz2, wa.dl = r.dl, wa.term = r.term;
+  wa.B = nb_rows, wa.Bp = Bp;
+  wa.nbk = blocks16(n->num_state), wa.nb1 = blocks16(n->hidden1), wa.nb2 = blocks16(n->hidden2);
+}
+
+int launch_weights(const WeightArgs& wa, int cap, hipStream_t st) {
+  const int total = wa.nb1 * wa.nbk + wa.nb2 * wa.nb1 + wa.nb2 + 1;
+  int grid = (total + WW - 1) / WW;
+  // max_workgroups bounds this pass as well; the library's own choice leaves every block its own wave
+  if (cap > 0 && grid > cap) grid = cap;
+  hipLaunchKernelGGL(k_maddpg_weights, dim3((unsigned)grid), dim3(64 * WW), 0, st, wa);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mdr_maddpg_grad_floats(const mdr_mlp_t* net) {
+  if (!fields_ok(net) || !covered(net)) return -1;
+  return grad_floats(net);
+}
+
+int64_t mdr_maddpg_workspace_bytes(const mdr_mlp_t* actor, const mdr_mlp_t* critic, int32_t nb_agents, int64_t nb_rows, int32_t max_workgroups) {
+  if (!actor || pair_shape(actor, critic, nb_agents) != MDR_OK || nb_rows < 0 || max_workgroups < 0) return -1;
+  const int64_t fa = ws_floats(actor, nb_rows), fc = ws_floats(critic, nb_rows);
+  const int64_t f = fa > fc ? fa : fc;
+  return (f > 4 ? f : 4) * (int64_t)sizeof(float);
+}
+
+int mdr_maddpg_target(const mdr_mlp_t* tgt_actor, const mdr_mlp_t* tgt_critic, const float* next_state, int64_t ld_state, const float* reward,
+                      const int64_t* index, int64_t nb_rows, int32_t nb_agents, int32_t agent, const float* noise, float tau, float gamma,
+                      int32_t max_workgroups, float* y, float* next_q, uint8_t* next_action, void* stream) {
+  if (!tgt_actor || !next_state || !reward || !noise || !y || !next_action) return MDR_ERR_INVALID;
+  const int rc = pair_shape(tgt_actor, tgt_critic, nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  if (!pointers_ok(tgt_actor) || !pointers_ok(tgt_critic)) return MDR_ERR_INVALID;
+  const int F = tgt_actor->num_state;
+  if (nb_rows < 0 || max_workgroups < 0 || ld_state < (int64_t)nb_agents * F || agent < 0 || agent >= nb_agents) return MDR_ERR_INVALID;
+  if (!(tau > 0.0f) || !(fabsf(tau) <= FLT_MAX) || !(fabsf(gamma) <= FLT_MAX)) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  if (nb_rows == 0) return MDR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int cap = lib_cap(max_workgroups);
+  RowArgs a{};
+  a.actor = make_net(tgt_actor), a.critic = make_net(tgt_critic);
+  a.state = next_state, a.ld = ld_state, a.index = index, a.B = nb_rows, a.N = nb_agents, a.F = F, a.agent = agent;
+  a.noise = noise, a.tau = tau, a.gamma = gamma, a.reward = reward, a.picks = next_action, a.out0 = y, a.out1 = next_q;
+  a.R = nb_rows * nb_agents, a.ntiles = (a.R + TILE - 1) / TILE;
+  if (launch_rows<MODE_PICK>(a, cap, st) != MDR_OK) return MDR_ERR_HIP;
+  a.R = nb_rows, a.ntiles = (a.R + TILE - 1) / TILE;
+  return launch_rows<MODE_TARGET>(a, cap, st);
+}
+
+int mdr_maddpg_critic_grad(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* action, const int64_t* index,
+                           int64_t nb_rows, int32_t nb_agents, const float* y, int32_t max_workgroups, void* workspace, float* grad,
+                           float* loss, float* q, void* stream) {
+  if (!state || !action || !y || !grad || !loss || !workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
+  const int rc = pair_shape(nullptr, critic, nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  if (!pointers_ok(critic)) return MDR_ERR_INVALID;
+  const int F = critic->num_state / nb_agents - 2;
+  if (nb_rows < 0 || max_workgroups < 0 || ld_state < (int64_t)nb_agents * F) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int cap = lib_cap(max_workgroups);
+  RowArgs a{};
+  WeightArgs wa{};
+  carve(a, wa, critic, workspace, nb_rows);
+  a.critic = make_net(critic);
+  a.state = state, a.ld = ld_state, a.action = action, a.index = index, a.B = nb_rows, a.N = nb_agents, a.F = F, a.agent = -1;
+  a.y = y, a.out0 = q, a.invB = nb_rows > 0 ? 1.0f / (float)nb_rows : 0.0f;
+  a.R = nb_rows, a.ntiles = (a.R + TILE - 1) / TILE;
+  if (nb_rows > 0 && launch_rows<MODE_CRITIC>(a, cap, st) != MDR_OK) return MDR_ERR_HIP;
+  wa.state = state, wa.ld = ld_state, wa.action = action, wa.index = index, wa.N = nb_agents, wa.F = F, wa.agent = -1;
+  wa.grad = grad, wa.loss = loss;
+  return launch_weights(wa, max_workgroups, st);
+}
+
+int mdr_maddpg_actor_grad(const mdr_mlp_t* actor, const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* action,
+                          const int64_t* index, int64_t nb_rows, int32_t nb_agents, int32_t agent, const float* noise, float tau, float pse,
+                          int32_t max_workgroups, void* workspace, float* grad, float* loss, float* q, float* logits, void* stream) {
+  if (!actor || !state || !action || !noise || !grad || !loss || !workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
+  const int rc = pair_shape(actor, critic, nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  if (!pointers_ok(actor) || !pointers_ok(critic)) return MDR_ERR_INVALID;
+  const int F = actor->num_state;
+  if (nb_rows < 0 || max_workgroups < 0 || ld_state < (int64_t)nb_agents * F || agent < 0 || agent >= nb_agents) return MDR_ERR_INVALID;
+  if (!(tau > 0.0f) || !(fabsf(tau) <= FLT_MAX) || !(fabsf(pse) <= FLT_MAX)) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int cap = lib_cap(max_workgroups);
+  RowArgs a{};
+  WeightArgs wa{};
+  carve(a, wa, actor, workspace, nb_rows);
+  a.actor = make_net(actor), a.critic = make_net(critic);
+  a.state = state, a.ld = ld_state, a.action = action, a.index = index, a.B = nb_rows, a.N = nb_agents, a.F = F, a.agent = agent;
+  a.noise = noise, a.tau = tau, a.pse = pse, a.out0 = q, a.out1 = logits, a.invB = nb_rows > 0 ? 1.0f / (float)nb_rows : 0.0f;
+  a.R = nb_rows, a.ntiles = (a.R + TILE - 1) / TILE;
+  if (nb_rows > 0 && launch_rows<MODE_ACTOR>(a, cap, st) != MDR_OK) return MDR_ERR_HIP;
+  wa.state = state, wa.ld = ld_state, wa.action = action, wa.index = index, wa.N = nb_agents, wa.F = F, wa.agent = agent;
+  wa.grad = grad, wa.loss = loss;
+  return launch_weights(wa, max_workgroups, st);
+}
+
+}  // extern "C"

@@ -1,0 +1,494 @@
+"""MADDPG's update step on the GPU (include/mdr_policy.h: mdr_maddpg_target, mdr_maddpg_critic_grad, mdr_maddpg_actor_grad).
+
+The reference's default trainer (cli.py:38, main.py:38-47; agents/ddpg.py, train_ddpg.py).  ``MADDPG.update`` (ddpg.py:305-339) runs
+once for every agent a: a fresh minibatch of env-steps, every agent's next action from the target actor through a hard
+gumbel-softmax, ``y = reward_a + gamma * tgt_critic(cat(next_states, next_actions))``, the critic's mse step, then the actor's step on
+``-critic(cat(states, actions with a's replaced by its own straight-through sample)).mean() + 1e-3 * logits.pow(2).mean()``; each step
+clips the gradient norm to 0.5 and takes Adam; ``update_target`` then blends both target nets.  The centralised critic reads J =
+N (F + 2) inputs - 1060 at the reference's 20 agents - through 256 hidden units: weights that do not fit LDS, so these kernels stream
+them from L2 (csrc/mdr_maddpg_grad.hip) and leave the other learners' kernels as they are.  ``maddpg_target``,
+``joint_q_loss_backward`` and ``actor_loss_backward`` are two launches each; ``JointReplayBuffer`` holds env-steps as preallocated
+device tensors the kernels read in place through the sampled indices; ``MADDPGLearner`` is the update, ``train_maddpg`` the loop.
+The gumbel noise is an input of every call, drawn by the learner under a seeded generator: every backend sees the same noise.  Nothing
+on the call path synchronises with the host.
+
+Places that leave the reference's text on purpose:
+
+* train_ddpg.py:86-91 and :111-115 store agent 0's observation for every agent.  Here every agent stores its own.
+* The sharing block of ``MADDPG.__init__`` sits outside the loop (ddpg.py:217-223): under ``DDPG_shared: True`` only the last agent
+  shares with agent 0.  Here there is one actor, one critic and one target of each for all agents - what the flag means and what every
+  other learner of this project does.  Unshared per-agent networks are not covered.
+* There is no terminal mask, as in ``mdr_dqn_target``: the reference's env never ends.
+* The actor step does not write the critic's ``.grad``.  The reference pollutes it and zeroes it before its next use: unobservable.
+* The clip norm is the literal 0.5 of ddpg.py:157 and :163; ``DDPG_prop["max_grad_norm"]`` is read by nobody in the reference.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _native as nat
+from .optim import FusedAdam
+from .ppo import _desc, _flat_grad, _publish, _whole, _workspace
+
+MAX_STATE, MAX_HIDDEN, MAX_JOINT = 64, 256, 1280      # the kernels' limits (include/mdr_policy.h: mdr_maddpg_*)
+# backend="auto": the kernels for minibatches of this many rows (profiles/maddpg_update_README.md: they measured 2.3-2.9x faster than
+# autograd per update at 64 and 256 rows and 0.6-0.7x at 4096; nothing between was measured, so auto stays with the largest size they won)
+AUTO_MIN_ROWS = 1
+AUTO_MAX_ROWS = 256
+PSE = 1e-3      # ddpg.py:339
+
+
+class DDPGNetworkMLP(nn.Module):
+    """agents/network.py:80-100 (``DDPG_Network``): Linear - ReLU - Linear - ReLU - Linear in an ``nn.Sequential`` named ``net``, Xavier-
+    uniform weights with the ReLU gain, biases 0.01; state_dict keys ``net.0|2|4.weight|bias``, so the nets of ``saveDDPGDict`` load
+    with ``load_state_dict``."""
+
+    def __init__(self, in_dim: int, out_dim: int, hidden_dim: int = 256):
+        super().__init__()
+        self.net = nn.Sequential(nn.Linear(in_dim, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, hidden_dim), nn.ReLU(),
+                                 nn.Linear(hidden_dim, out_dim))
+        gain = nn.init.calculate_gain("relu")
+        for m in self.net:
+            if isinstance(m, nn.Linear):
+                nn.init.xavier_uniform_(m.weight, gain=gain)
+                m.bias.data.fill_(0.01)
+
+    @property
+    def fc(self):
+        """The three Linear layers, as the gradient helpers of ppo.py index them."""
+        return [self.net[0], self.net[2], self.net[4]]
+
+    def forward(self, x):
+        return self.net(x)
+
+
+def _linears(net):
+    fc = getattr(net, "fc", None)
+    if fc is None or len(fc) != 3 or not all(isinstance(m, nn.Linear) and m.bias is not None for m in fc):
+        return None
+    return list(fc)
+
+
+def _refusal(actor, critic, nb_agents: int) -> Optional[str]:
+    """Why the kernels do not take this pair (None: they do)."""
+    fa, fc = _linears(actor), _linears(critic)
+    if fa is None or fc is None:
+        return "the kernels cover Linear-ReLU-Linear-ReLU-Linear (DDPGNetworkMLP, or an `fc` list of three biased Linear layers)"
+    for f in (fa, fc):
+        if f[1].in_features != f[0].out_features or f[2].in_features != f[1].out_features:
+            return "the three layers do not chain"
+        if f[0].out_features > MAX_HIDDEN or f[1].out_features > MAX_HIDDEN:
+            return "hidden layers of %d and %d units: the kernels cover at most %d" % (f[0].out_features, f[1].out_features, MAX_HIDDEN)
+        for lin in f:
+            for p in (lin.weight, lin.bias):
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                    return "parameters must be contiguous float32 tensors on the GPU"
+    F_len = fa[0].in_features
+    if int(nb_agents) < 1 or fc[0].in_features != int(nb_agents) * (F_len + 2):
+        return "the critic must read nb_agents * (num_state + 2) = %d inputs, not %d" % (int(nb_agents) * (F_len + 2), fc[0].in_features)
+    if F_len > MAX_STATE or fc[0].in_features > MAX_JOINT:
+        return "num_state = %d, joint input = %d: the kernels cover at most %d and %d" % (F_len, fc[0].in_features, MAX_STATE, MAX_JOINT)
+    if fa[2].out_features != 2 or fc[2].out_features != 1:
+        return "the kernels cover an actor of 2 actions and a critic of 1 value"
+    return None
+
+
+def supported(actor, critic, nb_agents: int) -> bool:
+    """Do the kernels take this actor and critic?  Two hidden layers of at most 256 units each (any size), an actor on F <= 64 features
+    with 2 actions, a critic on nb_agents * (F + 2) <= 1280 inputs with 1 value, float32 on the GPU."""
+    return _refusal(actor, critic, nb_agents) is None
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _check_steps(actor, state, index, nb_agents, what):
+    """``state`` [M, N, F] (or [M, N F]) float32 with unit inner strides and an env-step stride >= N F -> (dev, M, ld, B)."""
+    fa = _linears(actor)
+    dev, F_len, N = fa[0].weight.device, fa[0].in_features, int(nb_agents)
+    if state.dim() == 3:
+        ok = state.shape[1:] == (N, F_len) and (F_len == 1 or state.stride(2) == 1) and (N == 1 or state.stride(1) == F_len)
+    else:
+        ok = state.dim() == 2 and state.shape[1] == N * F_len and (N * F_len == 1 or state.stride(1) == 1)
+    if not ok or state.dtype != torch.float32 or state.device != dev:
+        raise ValueError("%s: state must be a float32 [M, %d, %d] tensor on %s with contiguous env-steps" % (what, N, F_len, dev))
+    M = int(state.shape[0])
+    if M > 1 and state.stride(0) < N * F_len:
+        raise ValueError("%s: the env-step stride must be >= nb_agents * F" % what)
+    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.device != dev or not index.is_contiguous()):
+        raise ValueError("%s: index must be a contiguous int64 [B] tensor on the device" % what)
+    ld = int(state.stride(0)) if M > 1 else N * F_len
+    return dev, M, ld, (int(index.shape[0]) if index is not None else M)
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch.Tensor, agent: int, noise: torch.Tensor,
+                  tau: float = 1.0, gamma: float = 0.99, index: Optional[torch.Tensor] = None, max_workgroups: int = 0
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``target_value`` of ddpg.py:317-322 for agent ``agent`` -> (y, next_q - float32 [B] -, next_action uint8 [B, N]).
+    ``next_state`` float32 [M, N, F] and ``reward`` float32 [M, N] are the replay buffer, read in place through ``index`` (int64 [B];
+    None: every env-step in order); ``noise`` float32 [B, N, 2] the gumbel noise of the N picks of every row.  Nothing is
+    differentiated."""
+    what = "maddpg_target"
+    N = int(reward.shape[1]) if reward.dim() == 2 else 0
+    why = _refusal(tgt_actor, tgt_critic, N)
+    if why:
+        raise ValueError("%s: %s" % (what, why))
+    dev, M, ld, B = _check_steps(tgt_actor, next_state, index, N, what)
+    _whole(reward, torch.float32, M * N, dev, what, "reward")
+    _whole(noise, torch.float32, B * N * 2, dev, what, "noise")
+    lib = nat.load()
+    adesc, cdesc = _desc(tgt_actor), _desc(tgt_critic)
+    y = torch.empty(B, dtype=torch.float32, device=dev)
+    next_q = torch.empty(B, dtype=torch.float32, device=dev)
+    next_action = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mdr_maddpg_target(C.byref(adesc), C.byref(cdesc), _ptr(next_state), ld, _ptr(reward), _ptr(index), B, N, int(agent),
+                                   _ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, _ptr(y), _ptr(next_q), _ptr(next_action),
+                                   _stream(dev))
+    nat.check(lib, None, rc, "mdr_maddpg_target")
+    return y, next_q, next_action
+
+
+def joint_q_loss_backward(actor, critic, state: torch.Tensor, action: torch.Tensor, y: torch.Tensor, index: Optional[torch.Tensor] = None,
+                          want_q: bool = False, max_workgroups: int = 0):
+    """``F.mse_loss(critic(cat(states, actions)), y)`` and ``backward()`` of ddpg.py:312-327: fills ``p.grad`` of the six parameters of
+    ``critic`` (allocated where None, overwritten otherwise) and returns the loss (0-dim device tensor) [and q, float32 [B]].  ``state``
+    float32 [M, N, F] and ``action`` int64 [M, N] are the replay buffer, read in place through ``index``; ``y`` float32 [B]
+    (``maddpg_target``'s) in minibatch order.  ``actor`` gives F (it is not evaluated)."""
+    what = "joint_q_loss_backward"
+    N = int(action.shape[1]) if action.dim() == 2 else 0
+    why = _refusal(actor, critic, N)
+    if why:
+        raise ValueError("%s: %s" % (what, why))
+    dev, M, ld, B = _check_steps(actor, state, index, N, what)
+    _whole(action, torch.int64, M * N, dev, what, "action")
+    _whole(y, torch.float32, B, dev, what, "y")
+    lib = nat.load()
+    adesc, cdesc = _desc(actor), _desc(critic)
+    flat = _flat_grad(critic, lib, cdesc, floats=int(lib.mdr_maddpg_grad_floats(C.byref(cdesc))))
+    ws = _workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
+    with torch.cuda.device(dev):
+        rc = lib.mdr_maddpg_critic_grad(C.byref(cdesc), _ptr(state), ld, _ptr(action), _ptr(index), B, N, _ptr(y), max_workgroups, _ptr(ws),
+                                        _ptr(flat), _ptr(loss), _ptr(q), _stream(dev))
+    nat.check(lib, None, rc, "mdr_maddpg_critic_grad")
+    _publish(critic, flat)
+    return (loss, q) if want_q else loss
+
+
+def actor_loss_backward(actor, critic, state: torch.Tensor, action: torch.Tensor, agent: int, noise: torch.Tensor, tau: float = 1.0,
+                        pse: float = PSE, index: Optional[torch.Tensor] = None, want_q: bool = False, max_workgroups: int = 0):
+    """The actor's loss of ddpg.py:331-339 for agent ``agent`` and ``backward()``: fills ``p.grad`` of the six parameters of ``actor``
+    and returns the loss (0-dim device tensor) [and Q float32 [B], logits float32 [B, 2]].  ``noise`` float32 [B, 2]: the gumbel
+    noise of the row's sample.  The critic is read, its ``.grad`` is not touched."""
+    what = "actor_loss_backward"
+    N = int(action.shape[1]) if action.dim() == 2 else 0
+    why = _refusal(actor, critic, N)
+    if why:
+        raise ValueError("%s: %s" % (what, why))
+    dev, M, ld, B = _check_steps(actor, state, index, N, what)
+    _whole(action, torch.int64, M * N, dev, what, "action")
+    _whole(noise, torch.float32, B * 2, dev, what, "noise")
+    lib = nat.load()
+    adesc, cdesc = _desc(actor), _desc(critic)
+    flat = _flat_grad(actor, lib, adesc, floats=int(lib.mdr_maddpg_grad_floats(C.byref(adesc))))
+    ws = _workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
+    logits = torch.empty((B, 2), dtype=torch.float32, device=dev) if want_q else None
+    with torch.cuda.device(dev):
+        rc = lib.mdr_maddpg_actor_grad(C.byref(adesc), C.byref(cdesc), _ptr(state), ld, _ptr(action), _ptr(index), B, N, int(agent),
+                                       _ptr(noise), C.c_float(tau), C.c_float(pse), max_workgroups, _ptr(ws), _ptr(flat), _ptr(loss),
+                                       _ptr(q), _ptr(logits), _stream(dev))
+    nat.check(lib, None, rc, "mdr_maddpg_actor_grad")
+    _publish(actor, flat)
+    return (loss, q, logits) if want_q else loss
+
+
+class JointReplayBuffer:
+    """The N per-agent ``Buffer``s of ddpg.py:208-213, 250-262 (which always hold the same env-steps) as one ring over env-steps on
+    ``device``: ``state`` / ``next_state`` [capacity, N, F], ``action`` int64 [capacity, N], ``reward`` [capacity, N]; the oldest
+    env-steps are overwritten first.  The fill count and the ring position live on the host; no call synchronises."""
+
+    def __init__(self, capacity: int, nb_agents: int, num_state: int, device):
+        if int(capacity) <= 0 or int(nb_agents) <= 0 or int(num_state) <= 0:
+            raise ValueError("JointReplayBuffer: capacity, nb_agents and num_state must be positive")
+        self.capacity, self.nb_agents, self.num_state = int(capacity), int(nb_agents), int(num_state)
+        self.device = torch.device(device)
+        shape = (self.capacity, self.nb_agents)
+        self.state = torch.zeros(shape + (self.num_state,), dtype=torch.float32, device=self.device)
+        self.next_state = torch.zeros(shape + (self.num_state,), dtype=torch.float32, device=self.device)
+        self.action = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        self.reward = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self._len = 0
+        self._pos = 0      # where the next env-step goes
+
+    def __len__(self) -> int:
+        return self._len
+
+    def push(self, state: torch.Tensor, action: torch.Tensor, reward: torch.Tensor, next_state: torch.Tensor) -> None:
+        """``n`` env-steps at once (``state`` / ``next_state`` [n, N, F], ``action`` / ``reward`` [n, N]), in row order, at the ring
+        position with wrap-around; of a push larger than the capacity the last ``capacity`` env-steps stay."""
+        n = int(state.shape[0])
+        s3, s2 = (n, self.nb_agents, self.num_state), (n, self.nb_agents)
+        if state.shape != s3 or next_state.shape != s3 or action.shape != s2 or reward.shape != s2:
+            raise ValueError("JointReplayBuffer.push: state / next_state [n, %d, %d], action and reward [n, %d]" % (s3[1], s3[2], s3[1]))
+        skip = max(n - self.capacity, 0)
+        kept = n - skip
+        first = min(kept, self.capacity - self._pos)      # env-steps up to the end of the ring; the rest wraps to its start
+        for dst, src in zip((self.state, self.next_state, self.action, self.reward), (state, next_state, action, reward)):
+            dst[self._pos:self._pos + first].copy_(src[skip:skip + first])
+            if kept > first:
+                dst[:kept - first].copy_(src[skip + first:])
+        self._pos = (self._pos + kept) % self.capacity
+        self._len = min(self._len + kept, self.capacity)
+
+    def push_batch(self, batch: Dict[str, torch.Tensor]) -> None:
+        """The dict of ``collect_maddpg_transitions`` (``state`` [T + 1, E, N, F], ``action``, ``reward`` [T, E, N]): ``state[t + 1]``
+        is ``next_state[t]``; the T E env-steps are stored in (t, env) order."""
+        states = batch["state"]
+        T = states.shape[0] - 1
+        N, F_len = states.shape[-2], states.shape[-1]
+        self.push(states[:T].reshape(-1, N, F_len), batch["action"].reshape(-1, N), batch["reward"].reshape(-1, N),
+                  states[1:].reshape(-1, N, F_len))
+
+    def chronological(self) -> torch.Tensor:
+        """The positions of the stored env-steps, oldest first (int64 on the device, computed from the host's counters)."""
+        idx = torch.arange(self._len, dtype=torch.int64, device=self.device)
+        return (idx + self._pos) % self.capacity if self._len == self.capacity else idx
+
+    def sample(self, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """``batch_size`` distinct positions (int64 on the device) drawn uniformly from the filled part WITHOUT replacement, as
+        ``np.random.choice(total_num, size=batch_size, replace=False)`` draws them (ddpg.py:268)."""
+        if int(batch_size) > self._len:
+            raise ValueError("JointReplayBuffer.sample: %d env-steps asked of %d" % (int(batch_size), self._len))
+        return torch.randperm(self._len, generator=generator, device=self.device)[:int(batch_size)]
+
+
+class MADDPGLearner:
+    """``MADDPG`` of agents/ddpg.py without the acting half, with shared networks (module docstring): the actor, the critic, a target
+    of each loaded from it (ddpg.py:79-91), the joint replay buffer and the two optimisers; ``store`` and ``update``.
+
+    ``backend="hip"``: target, both losses and both gradients from the kernels (ValueError for networks they refuse); ``"torch"``: the
+    reference's expressions under autograd - the comparator and the fallback; ``"auto"``: the kernels where ``supported()`` holds
+    and the minibatch has ``AUTO_MIN_ROWS`` to ``AUTO_MAX_ROWS`` rows (where they measured faster), torch otherwise.  ``optimizer``: called as ``optimizer(params, lr)`` for
+    each network; with ``mdr_amd.optim.FusedAdam`` every clip + Adam is one ``step(max_grad_norm=0.5)`` and the last step of each net
+    in an ``update()`` carries the target blend (``target=..., tau=soft_tau``)."""
+
+    MAX_GRAD_NORM = 0.5      # ddpg.py:157, 163
+
+    def __init__(self, actor, critic, nb_agents: int, lr_actor: float, lr_critic: float, gamma: float = 0.99, soft_tau: float = 0.01,
+                 gumbel_tau: float = 1.0, batch_size: int = 64, buffer_capacity: int = 524288, backend: str = "auto",
+                 optimizer=torch.optim.Adam):
+        if backend not in ("auto", "hip", "torch"):
+            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        if backend == "hip":
+            why = _refusal(actor, critic, nb_agents)
+            if why:
+                raise ValueError("MADDPGLearner(backend='hip'): " + why)
+        fa, fc = _linears(actor), _linears(critic)
+        if fa is None or fc is None:
+            raise ValueError("MADDPGLearner: actor and critic need the reference's Linear-ReLU-Linear-ReLU-Linear stack (DDPGNetworkMLP)")
+        self.actor, self.critic, self.nb_agents = actor, critic, int(nb_agents)
+        dev = fa[0].weight.device
+        self.num_state = fa[0].in_features
+        if fc[0].in_features != self.nb_agents * (self.num_state + 2):
+            raise ValueError("MADDPGLearner: the critic must read nb_agents * (num_state + 2) inputs")
+        self.tgt_actor = DDPGNetworkMLP(self.num_state, fa[2].out_features, fa[0].out_features).to(dev)
+        self.tgt_critic = DDPGNetworkMLP(fc[0].in_features, fc[2].out_features, fc[0].out_features).to(dev)
+        for tgt, net in ((self.tgt_actor, actor), (self.tgt_critic, critic)):
+            for t, s in zip(tgt.fc, net.fc):
+                if t.weight.shape != s.weight.shape:
+                    raise ValueError("MADDPGLearner: both hidden layers of a net have the same width in the reference")
+                t.weight.data.copy_(s.weight.data)
+                t.bias.data.copy_(s.bias.data)
+        self.gamma, self.soft_tau, self.gumbel_tau = float(gamma), float(soft_tau), float(gumbel_tau)
+        self.batch_size, self.backend = int(batch_size), backend
+        self.buffer = JointReplayBuffer(buffer_capacity, self.nb_agents, self.num_state, dev)
+        self.actor_optimizer = optimizer(actor.parameters(), lr_actor)
+        self.critic_optimizer = optimizer(critic.parameters(), lr_critic)
+        self.training_step = 0
+        self.before_step = None      # optional callable(learner, "critic" | "actor", agent): after a backward, before its clip and step
+
+    @classmethod
+    def from_config(cls, ddpg_prop: dict, actor, critic, nb_agents: int, backend: str = "auto", optimizer=torch.optim.Adam) -> "MADDPGLearner":
+        """From the reference's ``config_dict["DDPG_prop"]`` (agents/ddpg.py:60-70)."""
+        return cls(actor, critic, nb_agents, ddpg_prop["lr_actor"], ddpg_prop["lr_critic"], gamma=ddpg_prop["gamma"],
+                   soft_tau=ddpg_prop["soft_tau"], gumbel_tau=ddpg_prop["gumbel_softmax_tau"], batch_size=ddpg_prop["batch_size"],
+                   buffer_capacity=ddpg_prop["buffer_capacity"], backend=backend, optimizer=optimizer)
+
+    def uses_kernels(self, nb_rows: int) -> bool:
+        if self.backend == "auto":
+            return (_refusal(self.actor, self.critic, self.nb_agents) is None and
+                    _refusal(self.tgt_actor, self.tgt_critic, self.nb_agents) is None and AUTO_MIN_ROWS <= nb_rows <= AUTO_MAX_ROWS)
+        return self.backend == "hip"
+
+    def store(self, batch: Dict[str, torch.Tensor]) -> None:
+        """``MADDPG.push`` (ddpg.py:250-262) for every env-step of a ``collect_maddpg_transitions`` dict."""
+        self.buffer.push_batch(batch)
+
+    def draws(self, seed: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The minibatches and the noise of this update, from one ``torch.Generator`` seeded by (seed, training_step) - the same on
+        every backend: index int64 [N, B] (agent a's fresh minibatch, ddpg.py:307), and in ONE draw the gumbel noise
+        ``-log(Exp(1))`` (what ``F.gumbel_softmax`` draws) float32 [N, B, N + 1, 2]: [a, :, :N] for the target actor's picks of agent
+        a's update, [a, :, N] for the actor's own sample."""
+        dev, N, B = self.buffer.device, self.nb_agents, self.batch_size
+        gen = torch.Generator(device=dev)
+        gen.manual_seed((int(seed) * 1000003 + self.training_step * 7919 + 12345) & (2 ** 63 - 1))
+        index = torch.stack([self.buffer.sample(B, gen) for _ in range(N)])
+        noise = -torch.empty((N, B, N + 1, 2), dtype=torch.float32, device=dev).exponential_(generator=gen).log()
+        return index, noise[:, :, :N].contiguous(), noise[:, :, N].contiguous()
+
+    @staticmethod
+    def _hard(logits: torch.Tensor, noise: torch.Tensor, tau: float) -> torch.Tensor:
+        """``F.gumbel_softmax(logits, tau, hard=True)`` on the given gumbel noise: y_hard - y_soft.detach() + y_soft."""
+        y_soft = ((logits + noise) / tau).softmax(-1)
+        index = y_soft.max(-1, keepdim=True)[1]
+        y_hard = torch.zeros_like(logits).scatter_(-1, index, 1.0)
+        return y_hard - y_soft.detach() + y_soft
+
+    @torch.no_grad()
+    def update_target(self) -> None:
+        """ddpg.py:167-174: to = soft_tau * from + (1 - soft_tau) * to over both pairs of nets."""
+        for tgt, net in ((self.tgt_actor, self.actor), (self.tgt_critic, self.critic)):
+            target = [p for lin in tgt.fc for p in (lin.weight, lin.bias)]
+            new = [p for lin in net.fc for p in (lin.weight, lin.bias)]
+            torch._foreach_mul_(target, 1.0 - self.soft_tau)
+            torch._foreach_add_(target, new, alpha=self.soft_tau)
+
+    def _step(self, opt, net, blend_target) -> None:
+        """clip_grad_norm_(0.5) and the optimiser step of one net; ``blend_target``: the target net whose blend rides on this step."""
+        if isinstance(opt, FusedAdam):
+            if blend_target is not None:
+                opt.step(max_grad_norm=self.MAX_GRAD_NORM, target=[p for lin in blend_target.fc for p in (lin.weight, lin.bias)],
+                         tau=self.soft_tau)
+            else:
+                opt.step(max_grad_norm=self.MAX_GRAD_NORM)
+        else:
+            nn.utils.clip_grad_norm_(net.parameters(), self.MAX_GRAD_NORM)
+            opt.step()
+
+    def critic_backward(self, agent: int, index: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """Target, mse loss and backward of the critic for agent ``agent`` on the env-steps at ``index``: fills the critic's ``.grad``."""
+        buf, N = self.buffer, self.nb_agents
+        if self.uses_kernels(int(index.shape[0])):
+            y, _, _ = maddpg_target(self.tgt_actor, self.tgt_critic, buf.next_state, buf.reward, agent, noise, self.gumbel_tau, self.gamma,
+                                    index=index)
+            return joint_q_loss_backward(self.actor, self.critic, buf.state, buf.action, y, index=index)
+        B = int(index.shape[0])
+        state, next_state = buf.state[index], buf.next_state[index]
+        action = F.one_hot(buf.action[index].clamp(max=1), 2).to(torch.float32)
+        with torch.no_grad():
+            next_action = self._hard(self.tgt_actor(next_state), noise, self.gumbel_tau)
+            next_q = self.tgt_critic(torch.cat((next_state.reshape(B, -1), next_action.reshape(B, -1)), 1)).squeeze(1)
+            target_value = buf.reward[index][:, agent] + self.gamma * next_q
+        critic_value = self.critic(torch.cat((state.reshape(B, -1), action.reshape(B, -1)), 1)).squeeze(1)
+        loss = F.mse_loss(critic_value, target_value, reduction="mean")
+        self.critic_optimizer.zero_grad()
+        loss.backward()
+        return loss.detach()
+
+    def actor_backward(self, agent: int, index: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """The actor's loss and backward for agent ``agent``: fills the actor's ``.grad``."""
+        buf = self.buffer
+        if self.uses_kernels(int(index.shape[0])):
+            return actor_loss_backward(self.actor, self.critic, buf.state, buf.action, agent, noise, self.gumbel_tau, PSE, index=index)
+        B = int(index.shape[0])
+        state = buf.state[index]
+        action = F.one_hot(buf.action[index].clamp(max=1), 2).to(torch.float32)
+        logits = self.actor(state[:, agent])
+        action_ = self._hard(logits, noise, self.gumbel_tau)
+        action = torch.cat((action[:, :agent], action_[:, None], action[:, agent + 1:]), 1)
+        for p in self.critic.parameters():      # the reference lets this backward write the critic's .grad and zeroes it later
+            p.requires_grad_(False)
+        try:
+            actor_loss = -self.critic(torch.cat((state.reshape(B, -1), action.reshape(B, -1)), 1)).squeeze(1).mean()
+            loss = actor_loss + PSE * torch.pow(logits, 2).mean()
+            self.actor_optimizer.zero_grad()
+            loss.backward()
+        finally:
+            for p in self.critic.parameters():
+                p.requires_grad_(True)
+        return loss.detach()
+
+    def update(self, seed: int = 0) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """One ``MADDPG.update()`` (ddpg.py:305-339) and the ``update_target()`` train_ddpg.py:124-131 follows it with: for every agent
+        in order a fresh minibatch, the critic's step, the actor's step; then one blend of both target nets.  -> (actor_loss [N],
+        critic_loss [N]) as device tensors (the actor's loss includes the 1e-3 logits term), or None while the buffer holds fewer
+        than ``batch_size`` env-steps."""
+        if len(self.buffer) < self.batch_size:
+            return None
+        N = self.nb_agents
+        index, noise_t, noise_a = self.draws(seed)
+        fused_a, fused_c = isinstance(self.actor_optimizer, FusedAdam), isinstance(self.critic_optimizer, FusedAdam)
+        a_losses, c_losses = [], []
+        for a in range(N):
+            last = a == N - 1
+            c_losses.append(self.critic_backward(a, index[a], noise_t[a]))
+            if self.before_step is not None:
+                self.before_step(self, "critic", a)
+            self._step(self.critic_optimizer, self.critic, self.tgt_critic if last and fused_c else None)
+            a_losses.append(self.actor_backward(a, index[a], noise_a[a]))
+            if self.before_step is not None:
+                self.before_step(self, "actor", a)
+            self._step(self.actor_optimizer, self.actor, self.tgt_actor if last and fused_a else None)
+        if not (fused_a and fused_c):
+            with torch.no_grad():
+                for tgt, net, done in ((self.tgt_actor, self.actor, fused_a), (self.tgt_critic, self.critic, fused_c)):
+                    if not done:
+                        target = [p for lin in tgt.fc for p in (lin.weight, lin.bias)]
+                        torch._foreach_mul_(target, 1.0 - self.soft_tau)
+                        torch._foreach_add_(target, [p for lin in net.fc for p in (lin.weight, lin.bias)], alpha=self.soft_tau)
+        self.training_step += 1
+        return torch.stack(a_losses), torch.stack(c_losses)
+
+
+class GreedyDDPGActor:
+    """``DDPGAgent.act`` (agents/rl_controllers.py): the argmax of the actor's logits, in the shape ``deploy_policy`` takes through
+    its duck-typed branch - ``.sample(rows, seed, step, action=None, step_dev=None)`` -> uint8 actions."""
+
+    def __init__(self, actor):
+        self.actor = actor
+
+    @torch.no_grad()
+    def sample(self, rows: torch.Tensor, seed: int = 0, step: int = 0, action: Optional[torch.Tensor] = None, step_dev=None) -> torch.Tensor:
+        logits = self.actor(rows)
+        act = logits[:, 1] > logits[:, 0]      # argmax keeps the first maximum
+        if action is None:
+            return act.to(torch.uint8)
+        action.copy_(act)
+        return action
+
+
+def train_maddpg(env, learner: MADDPGLearner, nb_steps: int, update_every: int = 1, random_steps: int = 0, seed: int = 0
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The loop of train_ddpg.py:95-131 on a batched env (reset by the caller): every iteration one ``collect_maddpg_transitions``
+    step of all envs (uniformly random actions while the 1-based step is below ``random_steps``, the actor's gumbel sample after), ``store``, and
+    after every ``update_every``-th step from ``random_steps`` on one ``update()`` (which ends with the target blend).  -> (actor losses
+    [n, N], critic losses [n, N]) of the updates that ran, on the device."""
+    from .rollout import collect_maddpg_transitions
+    a_losses, c_losses = [], []
+    for t in range(int(nb_steps)):
+        step = t + 1      # train_ddpg.py:96-97, 124-127: random while step < random_steps, learn from step >= random_steps on
+        batch = collect_maddpg_transitions(env, learner.actor, 1, random_steps_left=max(int(random_steps) - step, 0),
+                                           seed=(int(seed) * 1000003 + t) & (2 ** 63 - 1))
+        learner.store(batch)
+        if step >= int(random_steps) and step % int(update_every) == 0:
+            out = learner.update(seed=seed)
+            if out is not None:
+                a_losses.append(out[0])
+                c_losses.append(out[1])
+    dev, N = learner.buffer.device, learner.nb_agents
+    empty = torch.empty((0, N), dtype=torch.float32, device=dev)
+    return (torch.stack(a_losses) if a_losses else empty), (torch.stack(c_losses) if c_losses else empty.clone())

@@ -389,6 +389,49 @@ def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float
     return {"state": state, "action": action, "reward": reward, "explored": explored, "epsilon": eps}
 
 
+def collect_maddpg_transitions(env, actor: nn.Module, nb_steps: int, random_steps_left: int = 0, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """The interaction loop of train_ddpg.py:95-116 for all envs at once, env-steps kept on the GPU: every step the actor's logits on
+    every agent's OWN observation (the reference stores agent 0's for all, train_ddpg.py:86-91), the acting action, ``env.step``,
+    and the env-step (state, action, reward, next_state) of ``MADDPG.push``.  ``select_action`` takes the argmax of a hard
+    gumbel-softmax sample (ddpg.py:289-298); an argmax over logits plus gumbel noise is a draw from softmax(logits) whatever tau, so
+    the action is ``mdr_logits_sample`` on the logits - the same distribution from the project's Philox stream.  The first
+    ``random_steps_left`` steps act uniformly at random instead (train_ddpg.py:97-103).  Returns ``state`` [T + 1, E, N, F]
+    (``state[t + 1]`` is ``next_state[t]``), ``action`` int64 and ``reward`` [T, E, N]."""
+    import ctypes as C
+
+    from . import _native as nat
+    E, N = env.nb_envs, env.nb_houses
+    dev = env.device
+    F_len = env.obs_vector_length()
+    T = int(nb_steps)
+    lib = nat.load()
+    state = torch.empty((T + 1, E, N, F_len), dtype=torch.float32, device=dev)
+    action = torch.empty((T, E, N), dtype=torch.int64, device=dev)
+    reward = torch.empty((T, E, N), dtype=torch.float32, device=dev)
+    act = torch.empty(E * N, dtype=torch.uint8, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    env.obs_vector("rows", out=state[0])
+    for t in range(T):
+        if t < int(random_steps_left):
+            act.copy_(torch.randint(0, 2, (E * N,), device=dev, generator=gen, dtype=torch.uint8))
+        else:
+            with torch.no_grad():
+                logits = actor(state[t].view(E * N, F_len)).contiguous()
+            with torch.cuda.device(dev):
+                rc = lib.mdr_logits_sample(C.c_void_p(logits.data_ptr()), logits.stride(0), E * N, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                           C.c_uint64(int(env.steps_taken) & (2 ** 64 - 1)), None, 0, C.c_void_p(act.data_ptr()), None, None,
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc != 0:
+                raise RuntimeError("mdr_logits_sample failed: %s" % lib.mdr_status_string(rc).decode())
+        _, r, _, _ = env.step(act.view(E, N))
+        action[t] = act.view(E, N).to(torch.int64)
+        reward[t] = r.view(E, N)
+        env.obs_vector("rows", out=state[t + 1])
+    env._exchange_check()
+    return {"state": state, "action": action, "reward": reward}
+
+
 def deploy_controller(env, kind: str, nb_steps: int) -> Dict[str, torch.Tensor]:
     """The evaluation loop of main-deploy.py:99-152 under one of the reference's rule-based agents (``agents_dict`` of
     main-deploy.py:22-34) for all envs at once: "bangbang", "deadband", "basic", "always_on" run inside the step kernels
