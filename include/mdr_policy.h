@@ -587,6 +587,59 @@ int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t *net, const float *state, i
                               uint64_t seed, uint64_t step, int32_t max_workgroups, void *workspace, float *grad, float *loss,
                               float *ratio, void *stream);
 
+/* ---- TarMAC-PPO's update step for the centralised critic (TarmacPPO.update, agents/tarmac_ppo.py:159-166, 196-204): value,
+ * advantage, value loss and gradient of one minibatch.
+ *
+ * The critic is TarMAC_Critic (agents/network.py:241-259), Linear(N F, H1) - ReLU - Linear(H1, H2) - ReLU - Linear(H2, N), as
+ * mdr_mlp_t in torch's own layout with num_state = J = N F and num_out = N (the number of agents: one value each), read as it is
+ * on every call.  Limits: J <= 4096 (50 houses of 51 features: 2550), every hidden layer <= 256 units of any size (no multiple of
+ * 16 needed), 1 <= N <= 64.  The weights are streamed from L2 in the manner of the MADDPG calls (csrc/mdr_tarmac_critic_grad.hip;
+ * the device helpers both share are csrc/mdr_stream_mlp.h), whose limits and bits are unchanged.
+ *
+ * Rows.  Minibatch row i < nb_rows is stored env-step j = index ? index[i] : i (`index` device int64, may be NULL); its input is the
+ * J contiguous floats at `state` + j * ld_state (ld_state >= J) - N agents of F floats each in agent order, the buffer
+ * mdr_tarmac_ppo_actor_grad reads with nb_houses = N and ld_state = F: no joint tensor is built.  `target`: the whole return buffer,
+ * float [env-steps][N], gathered through the same `index`.
+ *   V_i = critic(x_i);  delta_ik = target[j][k] - V_ik (rounded once);  advantage_ik = delta_ik;
+ *   loss = (sum_ik delta_ik^2) / (float)(nb_rows N)      (torch.pow(delta, 2).mean(0).mean(0))
+ *   d loss / d V_ik = (-2 delta_ik) inv,  inv = the fp32 value of 1 / (nb_rows N) formed on the host in double: ONE scale where
+ *   autograd's mean(0).mean(0) divides by nb_rows and then by N;  relu'(z) = 1 iff z > 0.
+ * Exact fp32 on v_mfma_f32_16x16x4_f32, no floating-point atomics, no signalling between workgroups; the same inputs and the same
+ * max_workgroups give the same bits on every call, and every element of every given output is written by every successful call.
+ * Row pass: a workgroup of 1024 threads takes floor(16 / nb) tiles of 16 rows at once, nb = the most 16-unit blocks of H1, H2 and N
+ * (four tiles at the reference's 64 hidden units), all against the same streamed weights; a persistent grid of min(ceil(tiles /
+ * tiles per workgroup), max_workgroups) workgroups (0: the library's choice, at most min(compute units, 512)).  A row's bits depend
+ * neither on its place in a workgroup nor on the grid.  Stream-ordered, never synchronise, allocate nothing.
+ *
+ * Floats of the flat gradient, dW1 | db1 | dW2 | db2 | dW3 | db3 in torch's parameter order and layout (host-only).  -1: a NULL net,
+ * num_out < 1, num_state % num_out != 0, a size <= 0, a shape outside the limits, a struct_size that is not this header's. */
+int64_t mdr_tarmac_critic_grad_floats(const mdr_mlp_t *critic);
+/* Bytes of device scratch mdr_tarmac_critic_grad needs over nb_rows rows, with Bp = nb_rows rounded up to 16: h1, dz1 [Bp][pad16(H1)]
+ * | h2, dz2 [Bp][pad16(H2)] | dV [Bp][pad16(N)] | the rows' loss terms [Bp] (host-only, independent of max_workgroups).  -1 as
+ * above, or nb_rows < 0, max_workgroups < 0. */
+int64_t mdr_tarmac_critic_workspace_bytes(const mdr_mlp_t *critic, int64_t nb_rows, int32_t max_workgroups);
+
+/* The forward alone (TarmacPPO.get_value, agents/tarmac_ppo.py:97-104, and the bootstrap): `value` float [nb_rows][N] = V, bit for
+ * bit the `value` of mdr_tarmac_critic_grad on the same rows.  One launch, no workspace; nb_rows == 0 launches nothing.
+ * Returns 0; -1 (a NULL required pointer, num_out < 1, num_state % num_out != 0, a size <= 0, ld_state < J, nb_rows < 0,
+ * max_workgroups < 0, a struct_size that is not this header's); -3 (HIP error); -4 (a shape outside the limits).  On -1 and -4
+ * nothing was launched and nothing written. */
+int mdr_tarmac_critic_value(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                            int32_t max_workgroups, float *value, void *stream);
+
+/* The critic's step: `loss` (one float on the device) and `grad` (mdr_tarmac_critic_grad_floats floats) = d loss / d parameters as
+ * autograd takes it; `value` and `advantage` (each may be NULL) float [nb_rows][N] in minibatch order - `advantage` is what
+ * mdr_tarmac_ppo_actor_grad takes.  A NaN in `target` reaches `advantage`, `loss` and `grad`, never `value`.  `workspace`: 16-byte
+ * aligned device memory of mdr_tarmac_critic_workspace_bytes, owned by the caller, its contents free before and after the call.
+ * Two launches: the row pass, then a weight pass of one wave per 16 x 16 block of a weight gradient, summing over the minibatch rows
+ * in row order (at most max_workgroups workgroups of four waves; 0: one wave per block), one more wave adding the rows' loss terms
+ * in a fixed order.  nb_rows == 0 writes zeros to `grad` and `loss` (the weight pass alone) and leaves `value` and `advantage`.
+ * Returns 0; -1 (as mdr_tarmac_critic_value, or a missing or misaligned workspace); -3; -4.  On -1 and -4 nothing was launched and
+ * nothing written. */
+int mdr_tarmac_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const float *target, const int64_t *index,
+                           int64_t nb_rows, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
+                           float *advantage, void *stream);
+
 /* ---- The optimiser tail of every update: clamp, norm clip, Adam and the target blend in one launch (csrc/mdr_optim.hip).
  *
  * A network's tensors as a table of segments: `param` (device float [count], updated in place), `grad` (device float [count], read

@@ -31,25 +31,21 @@
 
 #include "../../include/mdr.h"
 #include "../../include/mdr_policy.h"
+#include "mdr_stream_mlp.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace mdr_stream;
 
 constexpr int NW = 16;                // waves per row-pass workgroup = the most 16-unit blocks of a hidden layer
 constexpr int TILE = 16;              // minibatch rows per tile
-constexpr int LT = 20;                // row stride of the transposed tile images
-constexpr int KC = 128;               // joint-input columns staged at a time
 constexpr int MAX_F = 64, MAX_H = 256, MAX_J = 1280;
-constexpr int LIB_MAX_WG = 512;       // the library's own grid: min(work items, CUs, this)
 constexpr int WW = 4;                 // waves per weight-pass workgroup
 constexpr int UNR_W = 8;              // weight pass: MFMA k-steps whose global operands are loaded together
 
 // LDS of the row pass (floats): the input chunk, four activation images, the heads' partial sums, the tile's picks
 constexpr int S_X = 0, S_A0 = S_X + KC * LT, S_A1 = S_A0 + MAX_H * LT, S_C0 = S_A1 + MAX_H * LT, S_C1 = S_C0 + MAX_H * LT,
               S_LP = S_C1 + MAX_H * LT, S_PK = S_LP + NW * TILE * 2, S_END = S_PK + TILE;
-
-__host__ __device__ inline int blocks16(int n) { return (n + 15) / 16; }
 
 struct Net {
   const float *w1, *b1, *w2, *b2, *w3, *b3;
@@ -75,68 +71,6 @@ struct RowArgs {
   float *out0, *out1;         // TARGET: y, next_q; CRITIC: q; ACTOR: q, logits
   float *h1, *h2, *dz1, *dz2, *dl, *term;      // workspace of the net whose gradient is taken: [Rp][H1p], [Rp][H2p], ..., [Rp][2], [Rp]
 };
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// acc[unit u0 + 4 g + i][row c] += sum_{k < kn} W[u0 + m][k0 + k] inT[k][row]; inT zero from kn up to the next multiple of 4
-template <int UNR>
-__device__ __forceinline__ void fwd_accum(f32x4& acc, const float* __restrict__ W, int ldw, int H, int u0, int k0, int kn, const float* inT,
-                                          int c, int g) {
-  const int u = u0 + c;
-  const bool uok = u < H;
-  const float* wr = W + (int64_t)(uok ? u : 0) * ldw + k0;
-  const int ks = (kn + 3) >> 2;
-  for (int q0 = 0; q0 < ks; q0 += UNR) {      // UNR k-steps' weights asked for together
-    float av[UNR];
-#pragma unroll
-    for (int i = 0; i < UNR; ++i) {
-      const int kk = 4 * (q0 + i) + g;
-      av[i] = (uok && kk < kn) ? wr[kk] : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < UNR; ++i)
-      if (q0 + i < ks) acc = mfma(av[i], inT[(4 * (q0 + i) + g) * LT + c], acc);
-  }
-}
-
-__device__ __forceinline__ f32x4 bias_block(const float* __restrict__ b, int H, int u0, int g) {
-  f32x4 acc;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i] = (u0 + 4 * g + i < H) ? b[u0 + 4 * g + i] : 0.0f;
-  return acc;
-}
-
-// the block's values into the LDS image and, where asked, the workspace [row][Hp]
-__device__ __forceinline__ void store_block(const f32x4& v, float* imgT, float* ws, int Hp, int64_t row, int u0, int c, int g) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) imgT[(u0 + 4 * g + i) * LT + c] = v[i];
-  if (ws) *reinterpret_cast<f32x4*>(ws + row * Hp + u0 + 4 * g) = v;
-}
-
-// dzin[k0 + 4 g + i][row c] = relu'(hin) sum_{u < Hout} W[u][k0 + m] dzout[u][row], in place of hin's image
-template <int UNR>
-__device__ __forceinline__ void bwd_block(const float* __restrict__ W, int Hout, int Hin, int k0, const float* dzoutT, float* hinT, float* ws, int Hp,
-                                          int64_t row, int c, int g) {
-  f32x4 acc = {0, 0, 0, 0};
-  const int kc = k0 + c;
-  const bool kok = kc < Hin;
-  const float* wc = W + (kok ? kc : 0);
-  const int ks = 4 * blocks16(Hout);
-  for (int q0 = 0; q0 < ks; q0 += UNR) {
-    float av[UNR];
-#pragma unroll
-    for (int i = 0; i < UNR; ++i) {
-      const int u = 4 * (q0 + i) + g;
-      av[i] = (kok && u < Hout) ? wc[(int64_t)u * Hin] : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < UNR; ++i)
-      if (q0 + i < ks) acc = mfma(av[i], dzoutT[(4 * (q0 + i) + g) * LT + c], acc);      // ks is a multiple of 4, not of UNR
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i] = hinT[(k0 + 4 * g + i) * LT + c] > 0.0f ? acc[i] : 0.0f;
-  store_block(acc, hinT, ws, Hp, row, k0, c, g);
-}
 
 // the wave's share of two dot products over its block of vT: sum_u coef_o[u * su] vT[u][row c] -> lp[w][row][o]
 __device__ __forceinline__ void dot2_share(const float* vT, const float* __restrict__ coef0, const float* __restrict__ coef1, int64_t su, int H, float* lp,
@@ -502,19 +436,10 @@ int64_t grad_floats(const mdr_mlp_t* n) {
   return (int64_t)n->hidden1 * n->num_state + n->hidden1 + (int64_t)n->hidden2 * n->hidden1 + n->hidden2 + (int64_t)n->num_out * n->hidden2 + n->num_out;
 }
 
-int64_t pad16(int64_t n) { return (n + 15) / 16 * 16; }
-
 // floats of the workspace the gradient of `n` over nb_rows rows takes: h1, dz1 [Bp][H1p], h2, dz2 [Bp][H2p], dl [Bp][2], term [Bp]
 int64_t ws_floats(const mdr_mlp_t* n, int64_t nb_rows) {
   const int64_t Bp = pad16(nb_rows);
   return Bp * (2 * pad16(n->hidden1) + 2 * pad16(n->hidden2) + 3);
-}
-
-int lib_cap(int32_t max_workgroups) {
-  if (max_workgroups > 0) return max_workgroups;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  return cus < LIB_MAX_WG ? cus : LIB_MAX_WG;
 }
 
 template <Mode MODE>

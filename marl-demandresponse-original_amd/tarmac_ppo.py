@@ -5,8 +5,10 @@ The other half of the reference's train_tarmacPPO.py: ``TarmacPPO.update`` (agen
 the TarMAC actor, forms the value loss and the clipped surrogate, calls ``backward()`` twice, clips both gradients and takes two
 Adam steps - the actor's before the critic's.  ``actor_loss_backward`` is the actor's forward, loss and backward as hand-written HIP
 kernels on the matrix cores in exact fp32 around the two banded-attention kernels (csrc/mdr_tarmac_ppo_grad.hip, no library GEMM);
-it fills the ``.grad`` of a one-hop ``TarMACActor``.  torch keeps the gradient clipping, the optimisers and the critic.
-``TarMACPPOLearner`` is the loop.  Nothing on the call path synchronises with the host.
+it fills the ``.grad`` of a one-hop ``TarMACActor``.  ``critic_loss_backward`` is the centralised critic's value, advantage, value
+loss and gradient in two launches (csrc/mdr_tarmac_critic_grad.hip, include/mdr_policy.h: mdr_tarmac_critic_grad), ``critic_value`` its
+forward alone; the learner takes them with ``critic_backend="hip"``.  torch keeps the gradient clipping and the optimisers (or
+``optimizer=FusedAdam``).  ``TarMACPPOLearner`` is the loop.  Nothing on the call path synchronises with the host.
 """
 from __future__ import annotations
 
@@ -18,12 +20,19 @@ import torch.nn as nn
 
 from . import _native as nat
 from .optim import FusedAdam
-from .ppo import PPOLearner, _workspace
+from .ppo import PPOLearner, _whole, _workspace
 from .tarmac import FUSED_MAX_HIDDEN, FUSED_MAX_KEY, FUSED_MAX_OBS, FUSED_MAX_VALUE, MAX_COMM, MODES, TarMACActor
 
 # backend="auto": the kernels from this many env-steps per minibatch on (profiles/tarmac_ppo_README.md: they measured faster than
 # forward(differentiable=True) + backward() at every size tried, the reference's 256 x 20 included)
 AUTO_MIN_ENV_STEPS = 1
+# the critic kernels' limits (include/mdr_policy.h: mdr_tarmac_critic_*)
+CRITIC_MAX_JOINT, CRITIC_MAX_HIDDEN, CRITIC_MAX_AGENTS = 4096, 256, 64
+# critic_backend="auto": the critic kernels for minibatches of this many env-steps (profiles/tarmac_critic_README.md: the critic's
+# step measured 2.4x faster than autograd at 64 and 256 env-steps of 20 agents and 2.3x at 256 of 50 agents; at 4096 its lead of
+# 1.05x is inside the comparator's spread; nothing between was measured, so auto stays with the largest size they clearly won)
+CRITIC_AUTO_MIN_ENV_STEPS = 1
+CRITIC_AUTO_MAX_ENV_STEPS = 256
 
 
 def _head(actor):
@@ -157,42 +166,185 @@ def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_pr
     return (loss, ratio) if want_ratio else loss
 
 
+def _critic_layers(critic) -> Optional[List[nn.Linear]]:
+    seq = getattr(critic, "critic", None)
+    if not isinstance(seq, nn.Sequential) or len(seq) != 5:
+        return None
+    lin = [seq[0], seq[2], seq[4]]
+    if not all(isinstance(m, nn.Linear) and m.bias is not None for m in lin) or not all(isinstance(seq[i], nn.ReLU) for i in (1, 3)):
+        return None
+    return lin
+
+
+def _critic_params(critic) -> List[torch.Tensor]:
+    return [p for lin in _critic_layers(critic) for p in (lin.weight, lin.bias)]
+
+
+def _critic_refusal(critic) -> Optional[str]:
+    """Why the critic kernels do not take ``critic`` (None: they do)."""
+    lin = _critic_layers(critic)
+    if lin is None:
+        return "the kernels cover a TarMACCritic: `critic` = Sequential(Linear, ReLU, Linear, ReLU, Linear) with biases"
+    if lin[1].in_features != lin[0].out_features or lin[2].in_features != lin[1].out_features:
+        return "the three layers do not chain"
+    J, N = lin[0].in_features, lin[2].out_features
+    if not 1 <= N <= CRITIC_MAX_AGENTS:
+        return "%d agents: the kernels cover 1 to %d" % (N, CRITIC_MAX_AGENTS)
+    if J % N:
+        return "the critic must read num_agents * num_obs inputs: %d is no multiple of %d" % (J, N)
+    if J > CRITIC_MAX_JOINT:
+        return "joint input = %d: the kernels cover at most %d columns" % (J, CRITIC_MAX_JOINT)
+    if lin[0].out_features > CRITIC_MAX_HIDDEN or lin[1].out_features > CRITIC_MAX_HIDDEN:
+        return "hidden layers of %d and %d units: the kernels cover at most %d" % (lin[0].out_features, lin[1].out_features, CRITIC_MAX_HIDDEN)
+    for p in _critic_params(critic):
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+            return "parameters must be contiguous float32 tensors on the GPU"
+    return None
+
+
+def critic_supported(critic) -> bool:
+    """Do the critic kernels take this critic?  A ``TarMACCritic`` on N F <= 4096 inputs with hidden layers of at most 256 units (any
+    size) and 1 <= N <= 64 agents, float32 on the GPU."""
+    return _critic_refusal(critic) is None
+
+
+def _critic_desc(critic) -> nat.MdrMlp:
+    lin = _critic_layers(critic)
+    ptr = [C.c_void_p(p.data_ptr()) for p in _critic_params(critic)]
+    return nat.MdrMlp(C.sizeof(nat.MdrMlp), lin[0].in_features, lin[0].out_features, lin[1].out_features, lin[2].out_features, *ptr)
+
+
+def _critic_steps(critic, state, index, what):
+    """``state`` float32 [M, N, F] with contiguous env-steps (any env-step stride >= N F) -> (dev, M, N, ld, B)."""
+    why = _critic_refusal(critic)
+    if why:
+        raise ValueError("%s: %s" % (what, why))
+    lin = _critic_layers(critic)
+    dev, J, N = lin[0].weight.device, lin[0].in_features, lin[2].out_features
+    F_len = J // N
+    if not isinstance(state, torch.Tensor) or state.dim() != 3 or state.shape[1:] != (N, F_len) or state.dtype != torch.float32 or state.device != dev:
+        raise ValueError("%s: state must be a float32 [M, %d, %d] tensor on %s" % (what, N, F_len, dev))
+    M = int(state.shape[0])
+    if (F_len > 1 and state.stride(2) != 1) or (N > 1 and state.stride(1) != F_len) or (M > 1 and state.stride(0) < J):
+        raise ValueError("%s: state needs contiguous env-steps and an env-step stride >= N F" % what)
+    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.device != dev or not index.is_contiguous()):
+        raise ValueError("%s: index must be a contiguous int64 [B] tensor on the device" % what)
+    ld = int(state.stride(0)) if M > 1 else J
+    return dev, M, N, ld, (int(index.shape[0]) if index is not None else M)
+
+
+def critic_value(critic, state: torch.Tensor, index: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> torch.Tensor:
+    """``critic(state[index])`` (agents/tarmac_ppo.py:97-104) from the kernels -> float32 [B, N], bit for bit the value
+    ``critic_loss_backward(..., want_value=True)`` returns.  Nothing is differentiated."""
+    what = "tarmac_ppo.critic_value"
+    dev, M, N, ld, B = _critic_steps(critic, state, index, what)
+    lib = nat.load()
+    desc = _critic_desc(critic)
+    value = torch.empty((B, N), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mdr_tarmac_critic_value(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None,
+                                         B, max_workgroups, C.c_void_p(value.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, "mdr_tarmac_critic_value")
+    return value
+
+
+def critic_loss_backward(critic, state: torch.Tensor, target: torch.Tensor, index: Optional[torch.Tensor] = None, want_value: bool = False,
+                         max_workgroups: int = 0):
+    """``torch.pow(target[index] - critic(state[index]), 2).mean(0).mean(0)`` and ``backward()`` of agents/tarmac_ppo.py:159-166,
+    196-204: fills ``p.grad`` of the six parameters of ``critic`` (allocated where None, overwritten otherwise: views of one flat
+    buffer kept with the module) and returns (loss - 0-dim device tensor -, advantage float32 [B, N] = target[index] - value, detached
+    [, value float32 [B, N]]).  ``state`` float32 [M, N, F] and ``target`` float32 [M, N] are the stored env-steps and returns, read in
+    place through ``index`` (int64 [B] on the device; None: every env-step in order, B = M)."""
+    what = "tarmac_ppo.critic_loss_backward"
+    dev, M, N, ld, B = _critic_steps(critic, state, index, what)
+    _whole(target, torch.float32, M * N, dev, what, "target")
+    lib = nat.load()
+    desc = _critic_desc(critic)
+    flat = getattr(critic, "_mdr_flat_grad", None)
+    n = int(lib.mdr_tarmac_critic_grad_floats(C.byref(desc)))
+    if flat is None or flat.numel() != n or flat.device != dev:
+        flat = critic._mdr_flat_grad = torch.empty(n, dtype=torch.float32, device=dev)
+    nbytes = int(lib.mdr_tarmac_critic_workspace_bytes(C.byref(desc), B, max_workgroups))
+    if nbytes < 0:
+        raise ValueError("%s: mdr_tarmac_critic_workspace_bytes refused the sizes" % what)
+    ws = _workspace(dev, nbytes)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    advantage = torch.empty((B, N), dtype=torch.float32, device=dev)
+    value = torch.empty((B, N), dtype=torch.float32, device=dev) if want_value else None
+    with torch.cuda.device(dev):
+        rc = lib.mdr_tarmac_critic_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(target.data_ptr()),
+                                        C.c_void_p(index.data_ptr()) if index is not None else None, B, max_workgroups,
+                                        C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
+                                        C.c_void_p(value.data_ptr()) if want_value else None, C.c_void_p(advantage.data_ptr()),
+                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, "mdr_tarmac_critic_grad")
+    off = 0
+    for p in _critic_params(critic):
+        view = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+        if p.grad is None:
+            p.grad = view
+        elif p.grad.data_ptr() != view.data_ptr():
+            p.grad.copy_(view)
+    return (loss, advantage, value) if want_value else (loss, advantage)
+
+
 class TarMACPPOLearner:
     """``TarmacPPO.update`` (agents/tarmac_ppo.py:152-207) on the dict ``collect_tarmac_rollout`` returns.
 
     ``backend="hip"``: the actor's loss and gradient from the kernels (ValueError for an actor they refuse); ``"torch"``:
     ``forward(differentiable=True)`` under autograd (the dense formula on the CPU or with ``attention="dense"``) - the comparator, the
     CPU path and the fallback for two or more hops; ``"auto"``: the kernels where ``supported(actor)`` holds and the minibatch has at
-    least ``AUTO_MIN_ENV_STEPS`` env-steps, torch otherwise.  The centralised critic (N F inputs, up to thousands wide - outside any
-    kernel of this library) stays torch autograd with every backend."""
+    least ``AUTO_MIN_ENV_STEPS`` env-steps, torch otherwise.
+
+    ``critic_backend`` chooses the centralised critic's step on its own: ``"torch"`` (the default) is autograd on
+    ``critic(state[index])``; ``"hip"``: ``critic_loss_backward`` (ValueError for a critic the kernels refuse) - the critic's loss and
+    gradient come first and give the advantage, then the actor's loss, clip and step, then the critic's clip and step, the
+    reference's order; no ``zero_grad()`` on the critic, the kernels overwrite its gradient; ``"auto"``: the kernels where
+    ``critic_supported(critic)`` holds and the minibatch has ``CRITIC_AUTO_MIN_ENV_STEPS`` to ``CRITIC_AUTO_MAX_ENV_STEPS`` env-steps
+    (where they measured faster, profiles/tarmac_critic_README.md), torch otherwise."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
-                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam):
+                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
+                 critic_backend: str = "torch"):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        if critic_backend not in ("auto", "hip", "torch"):
+            raise ValueError("critic_backend must be 'auto', 'hip' or 'torch'")
         if backend == "hip":
             why = _refusal(actor)
             if why:
                 raise ValueError("TarMACPPOLearner(backend='hip'): " + why)
+        if critic_backend == "hip":
+            why = _critic_refusal(critic)
+            if why:
+                raise ValueError("TarMACPPOLearner(critic_backend='hip'): " + why)
         self.actor, self.critic = actor, critic
         self.clip_param, self.max_grad_norm = float(clip_param), float(max_grad_norm)
         self.ppo_update_time, self.batch_size = int(ppo_update_time), int(batch_size)
-        self.backend = backend
+        self.backend, self.critic_backend = backend, critic_backend
         self.actor_optimizer = optimizer(actor.parameters(), lr_actor)
         self.critic_optimizer = optimizer(critic.parameters(), lr_critic)
         self.training_step = 0
 
     @classmethod
-    def from_config(cls, tarmac_ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam) -> "TarMACPPOLearner":
+    def from_config(cls, tarmac_ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam,
+                    critic_backend: str = "torch") -> "TarMACPPOLearner":
         """From the reference's ``config_dict["TarMAC_PPO_prop"]`` (agents/tarmac_ppo.py:39-45)."""
         p = tarmac_ppo_prop
         return cls(actor, critic, p["lr_actor"], p["lr_critic"], clip_param=p["clip_param"], max_grad_norm=p["max_grad_norm"],
-                   ppo_update_time=p["ppo_update_time"], batch_size=p["batch_size"], backend=backend, optimizer=optimizer)
+                   ppo_update_time=p["ppo_update_time"], batch_size=p["batch_size"], backend=backend, optimizer=optimizer,
+                   critic_backend=critic_backend)
 
     def uses_kernels(self, nb_env_steps: int) -> bool:
         if self.backend == "auto":
             return _refusal(self.actor) is None and nb_env_steps >= AUTO_MIN_ENV_STEPS
         return self.backend == "hip"
+
+    def critic_uses_kernels(self, nb_env_steps: int) -> bool:
+        if self.critic_backend == "auto":
+            return CRITIC_AUTO_MIN_ENV_STEPS <= nb_env_steps <= CRITIC_AUTO_MAX_ENV_STEPS and _critic_refusal(self.critic) is None
+        return self.critic_backend == "hip"
 
     minibatches = PPOLearner.minibatches      # the sampler, over the stored env-steps: needs self.actor and self.batch_size only
 
@@ -200,8 +352,12 @@ class TarMACPPOLearner:
         """One minibatch of agents/tarmac_ppo.py:159-207.  ``state`` [M, N, F], ``action``, ``old_prob``, ``target`` [M, N]: the whole
         buffers; ``index`` picks the env-steps.  The critic's value gives the advantage, the actor's loss is clipped and stepped, then
         the critic's.  The defects of ``comm_defect_prob > 0`` are keyed by ``(seed, training_step)``.  -> (actor loss, critic loss)."""
-        delta = target[index] - self.critic(state[index])                       # [B, N]
-        advantage = delta.detach()
+        critic_kernels = self.critic_uses_kernels(int(index.shape[0]))
+        if critic_kernels:      # value, advantage, loss and the critic's gradient before anything steps; its clip and step stay last
+            value_loss, advantage = critic_loss_backward(self.critic, state, target, index=index)
+        else:
+            delta = target[index] - self.critic(state[index])                   # [B, N]
+            advantage = delta.detach()
         if self.uses_kernels(int(index.shape[0])):
             action_loss = actor_loss_backward(self.actor, state, action, old_prob, advantage.contiguous(), self.clip_param, index=index,
                                               seed=seed, step=self.training_step)
@@ -220,10 +376,11 @@ class TarMACPPOLearner:
         else:
             nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad_norm)
             self.actor_optimizer.step()
-        value_loss = torch.pow(delta, 2).mean(0).mean(0)
-        self.critic_optimizer.zero_grad()
-        value_loss.backward()
-        if isinstance(self.critic_optimizer, FusedAdam):      # autograd's own gradient tensors: the segment table covers them
+        if not critic_kernels:
+            value_loss = torch.pow(delta, 2).mean(0).mean(0)
+            self.critic_optimizer.zero_grad()
+            value_loss.backward()
+        if isinstance(self.critic_optimizer, FusedAdam):      # autograd's own tensors or views of the flat buffer: the segment table covers both
             self.critic_optimizer.step(max_grad_norm=self.max_grad_norm)
         else:
             nn.utils.clip_grad_norm_(self.critic.parameters(), self.max_grad_norm)
