@@ -640,6 +640,81 @@ int mdr_tarmac_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t 
                            int64_t nb_rows, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
                            float *advantage, void *stream);
 
+/* ---- TarMAC A2C (the reference's train_tarmac.py): MultiAgentPolicy (agents/tarmac/model.py:132-266) as A2C_ACKTR builds it
+ * (agents/tarmac/a2c_acktr.py:35-36: no GRU, one hop) - the act step and the update step of update_multi_agent (a2c_acktr.py:59-107).
+ *
+ * The network in torch's own layout (w[out][in] contiguous, device memory, read as it is on every call), F = num_obs, C = num_comm,
+ * S = state_size, K = num_key:  common_w0 [S][F + C], common_b0 [S], common_w2 [S][S], common_b2 [S] (base.common.0 / .2);
+ * critic_w0 [S][S], critic_b0 [S], critic_w3 [1][S], critic_b3 [1] (base.critic.0 / .3); query_w, key_w [K][S], query_b, key_b [K],
+ * value_w [C][S], value_b [C] (base.comm.state2query / state2key / state2value); dist_w [2][S] (dist.linear, no bias).
+ * Limits: 1 <= F <= 128, C a multiple of 4 <= 32, S a multiple of 4 <= 128, K a multiple of 4 <= 16, 1 <= N <= 64 agents per env,
+ * at most 2^24 env-steps per call, one hop (base.comm.msg2nextstate is not reached and has no place here).
+ *
+ * One env-step b of N agents, row r = b N + n, LeakyReLU slope 0.01:
+ *   in = [obs | comm_in];  h1 = leaky(W1 in + b1);  x = W2 h1 + b2;  logits = Wd x;
+ *   xbar_b = (sum_n x_bn, agent order) / N;  V_b = Wc2 leaky(Wc1 xbar_b + bc1) + bc2     (the critic's first layer is linear before
+ *   MeanAll: the mean is taken first - ONE value per env-step);
+ *   q = Wq x + bq, k = Wk x + bk, v = Wv x + bv;  attn_ij = softmax_j(q_i k_j / sqrt(C)) over ALL agents j of the env, j = i included
+ *   (the scale is sqrt(C), model.py:115-116);  comm_out_i = sum_j attn_ij v_j.
+ * Exact fp32 (the MLPs on v_mfma_f32_16x16x4_f32, the weights streamed from L2; csrc/mdr_tarmac_a2c.hip), no library GEMM, no
+ * floating-point atomics, no partial sums whose order depends on the grid: the bits of every output are independent of
+ * max_workgroups (0: the library's choice) and of where `index` points.  Stream-ordered, never synchronise, allocate nothing.
+ * Returns of the three compute calls: 0; -1 (a NULL required pointer, a misaligned workspace or x, ld_obs < F, ld_comm < C (ld_out <
+ * C), nb_steps < 0, nb_agents < 1, max_workgroups < 0, a size < 1, a struct_size that is not this header's); -3 (HIP error); -4 (a
+ * shape outside the limits).  On -1 and -4 nothing was launched and nothing written. */
+typedef struct mdr_tarmac_a2c_net {
+  uint32_t struct_size;
+  int32_t num_obs, num_comm, state_size, num_key;
+  const float *common_w0, *common_b0, *common_w2, *common_b2;
+  const float *critic_w0, *critic_b0, *critic_w3, *critic_b3;
+  const float *query_w, *query_b, *key_w, *key_b, *value_w, *value_b;
+  const float *dist_w;
+} mdr_tarmac_a2c_net_t;
+
+/* Floats of the flat gradient: the nine tensors an update reaches, in parameters() order - common_w0 | common_b0 | common_w2 |
+ * common_b2 | critic_w0 | critic_b0 | critic_w3 | critic_b3 | dist_w (evaluate_actions discards the new communication: query, key
+ * and value get no gradient).  Host-only.  -1: a NULL net, a size < 1, a shape outside the limits, another struct_size. */
+int64_t mdr_tarmac_a2c_grad_floats(const mdr_tarmac_a2c_net_t *net);
+/* Bytes of device scratch over nb_steps env-steps of nb_agents agents, with Rp = nb_steps nb_agents and Bp = nb_steps rounded up to
+ * 16, Sp = S rounded up to 16 (floats): h1 | x | dx | dz1 [Rp][Sp], logits | dlogits [Rp][2], xbar | a | da | dxbar / N [Bp][Sp], dV
+ * [Bp], the env-steps' loss terms [Bp][4].  Rows past the batch hold exact zeros after mdr_tarmac_a2c_grad.  Host-only, independent of
+ * max_workgroups.  -1 as above, or nb_steps < 0, nb_agents outside 1..64, max_workgroups < 0. */
+int64_t mdr_tarmac_a2c_workspace_bytes(const mdr_tarmac_a2c_net_t *net, int64_t nb_steps, int32_t nb_agents, int32_t max_workgroups);
+
+/* The forward of MultiAgentBase.forward + dist (model.py:169-183, 244-266) without the communication: minibatch env-step i < nb_steps
+ * is stored env-step j = index ? index[i] : i (`index` device int64, may be NULL); its agent n is row j N + n of `obs` (F floats, row
+ * stride ld_obs >= F) and of `comm_in` (C floats, row stride ld_comm >= C) - two buffers, never concatenated in memory.  `logits`
+ * float [nb_steps N][2], `value` float [nb_steps], `x` (may be NULL; 16-byte aligned) float [nb_steps N][S].  Bit for bit the logits
+ * and the value mdr_tarmac_a2c_grad forms on the same rows.  `workspace` (mdr_tarmac_a2c_workspace_bytes, 16-byte aligned) is
+ * needed only where `x` is NULL.  Two launches (the row pass, the env-step pass); nb_steps == 0 launches nothing. */
+int mdr_tarmac_a2c_forward(const mdr_tarmac_a2c_net_t *net, const float *obs, int64_t ld_obs, const float *comm_in, int64_t ld_comm,
+                           const int64_t *index, int64_t nb_steps, int32_t nb_agents, int32_t max_workgroups, void *workspace,
+                           float *logits, float *value, float *x, void *stream);
+
+/* CommAttention.forward (model.py:88-129) for one hop: `x` float [nb_envs N][S] (contiguous) -> `comm_out` float [nb_envs N][C] (row
+ * stride ld_out >= C: a slab of the next step's comm_in) and `attn` (may be NULL) float [nb_envs][N][N].  One workgroup per env
+ * (persistent over the envs), x, q, k and v of the env in LDS; the row softmax subtracts the row's maximum and adds the exponentials
+ * in ascending j; every contraction in ascending order on one accumulator.  One launch; nb_envs == 0 launches nothing. */
+int mdr_tarmac_a2c_comm(const mdr_tarmac_a2c_net_t *net, const float *x, int64_t nb_envs, int32_t nb_agents, int32_t max_workgroups,
+                        float *comm_out, int64_t ld_out, float *attn, void *stream);
+
+/* The update's loss and gradient over nb_steps env-steps (count = nb_steps N): `action` (int64, nonzero = action 1) and `ret`
+ * (float) are the whole buffers [env-steps][N], gathered through `index` like obs and comm_in.
+ *   delta_bn = ret_bn - V_b;  d = l_taken - l_other, t = exp(-|d|), p_taken / p_other = 1 / (1 + t) and t / (1 + t) by the sign of d,
+ *   -log p_taken = max(-d, 0) + log1p(t), H = -(p_taken log p_taken + p_other log p_other);
+ *   losses[0] = value_loss = sum delta^2 / count, losses[1] = action_loss = -sum delta log p_taken / count (delta detached),
+ *   losses[2] = entropy = sum H / count;  `grad` (mdr_tarmac_a2c_grad_floats floats) = d (value_coef value_loss + action_loss -
+ *   entropy_coef entropy) / d parameters as autograd takes it; leaky'(z) = 1 for z > 0, 0.01 otherwise.
+ * `value` float [nb_steps], `advantage` float [nb_steps][N] = delta (each may be NULL).  A NaN in `ret` reaches the losses, the
+ * gradient and `advantage`, never `value`.  Four launches: row pass, env-step pass, row pass backward, and a weight pass of one wave
+ * per 16 x 16 block of a weight gradient summing over the rows in row order (at most max_workgroups workgroups of four waves; 0: one
+ * wave per block), one more wave adding the env-steps' loss terms in a fixed order.  Every element of every given output is written
+ * by every successful call; nb_steps == 0 launches no kernel and writes zeros to `grad` and `losses`. */
+int mdr_tarmac_a2c_grad(const mdr_tarmac_a2c_net_t *net, const float *obs, int64_t ld_obs, const float *comm_in, int64_t ld_comm,
+                        const int64_t *action, const float *ret, const int64_t *index, int64_t nb_steps, int32_t nb_agents,
+                        float value_coef, float entropy_coef, int32_t max_workgroups, void *workspace, float *grad, float *losses,
+                        float *value, float *advantage, void *stream);
+
 /* ---- The optimiser tail of every update: clamp, norm clip, Adam and the target blend in one launch (csrc/mdr_optim.hip).
  *
  * A network's tensors as a table of segments: `param` (device float [count], updated in place), `grad` (device float [count], read

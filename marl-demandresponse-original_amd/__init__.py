@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("BatchedDemandResponseEnv", "OBS_COLUMNS"):
         from . import batched_env
         return getattr(batched_env, name)
-    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "maddpg", "optim"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
+    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "maddpg", "optim", "tarmac_a2c"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "BatchedMetrics":
@@ -37,6 +37,9 @@ def __getattr__(name):
     if name == "TarMACPPOLearner":
         from .tarmac_ppo import TarMACPPOLearner
         return TarMACPPOLearner
+    if name in ("TarMACA2CPolicy", "TarMACA2CLearner"):
+        from . import tarmac_a2c
+        return getattr(tarmac_a2c, name)
     if name == "FusedAdam":
         from .optim import FusedAdam
         return FusedAdam

@@ -151,6 +151,16 @@ class MdrTarmacNet(C.Structure):
     ]
 
 
+class MdrTarmacA2CNet(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("num_obs", C.c_int32), ("num_comm", C.c_int32), ("state_size", C.c_int32), ("num_key", C.c_int32),
+        ("common_w0", _f32p), ("common_b0", _f32p), ("common_w2", _f32p), ("common_b2", _f32p),
+        ("critic_w0", _f32p), ("critic_b0", _f32p), ("critic_w3", _f32p), ("critic_b3", _f32p),
+        ("query_w", _f32p), ("query_b", _f32p), ("key_w", _f32p), ("key_b", _f32p), ("value_w", _f32p), ("value_b", _f32p),
+        ("dist_w", _f32p),
+    ]
+
+
 MDR_ADAM_MAX_SEGMENTS = 32
 
 
@@ -186,6 +196,7 @@ EXPORTS = (
     "mdr_maddpg_grad_floats", "mdr_maddpg_workspace_bytes", "mdr_maddpg_target", "mdr_maddpg_critic_grad", "mdr_maddpg_actor_grad",
     "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
     "mdr_tarmac_critic_grad_floats", "mdr_tarmac_critic_workspace_bytes", "mdr_tarmac_critic_value", "mdr_tarmac_critic_grad",
+    "mdr_tarmac_a2c_grad_floats", "mdr_tarmac_a2c_workspace_bytes", "mdr_tarmac_a2c_forward", "mdr_tarmac_a2c_comm", "mdr_tarmac_a2c_grad",
     "mdr_adam_workspace_bytes", "mdr_adam_step",
 )
 
@@ -302,6 +313,12 @@ def load():
         "mdr_tarmac_ppo_workspace_bytes": (i64, [C.POINTER(MdrTarmacNet), i64, i32, i32]),
         "mdr_tarmac_ppo_actor_grad": (C.c_int, [C.POINTER(MdrTarmacNet), vp, i64, vp, i64, i32, vp, vp, vp, C.c_float, u64, u64, i32, vp, vp, vp,
                                                 vp, vp]),
+        "mdr_tarmac_a2c_grad_floats": (i64, [C.POINTER(MdrTarmacA2CNet)]),
+        "mdr_tarmac_a2c_workspace_bytes": (i64, [C.POINTER(MdrTarmacA2CNet), i64, i32, i32]),
+        "mdr_tarmac_a2c_forward": (C.c_int, [C.POINTER(MdrTarmacA2CNet), vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+        "mdr_tarmac_a2c_comm": (C.c_int, [C.POINTER(MdrTarmacA2CNet), vp, i64, i32, i32, vp, i64, vp, vp]),
+        "mdr_tarmac_a2c_grad": (C.c_int, [C.POINTER(MdrTarmacA2CNet), vp, i64, vp, i64, vp, vp, vp, i64, i32, C.c_float, C.c_float, i32, vp,
+                                          vp, vp, vp, vp, vp]),
         "mdr_adam_workspace_bytes": (i64, [i64]),
         "mdr_adam_step": (C.c_int, [C.POINTER(MdrAdamSegments), vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, i64, C.c_double, C.c_double,
                                     C.c_double, vp, vp, i32, vp]),

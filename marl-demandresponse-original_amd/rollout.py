@@ -335,6 +335,60 @@ def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, criti
 
 
 @torch.no_grad()
+def collect_tarmac_a2c_rollout(env, policy, nb_steps: int, gamma: float = 0.99, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """The interaction loop of train_tarmac.py:86-104 for all envs at once, with a ``TarMACA2CPolicy``: every step
+    ``env.obs_vector("rows")`` -> ``policy.act`` (mdr_tarmac_a2c_forward, mdr_logits_sample with the Philox draw of every other actor
+    for (seed, step, agent), mdr_tarmac_a2c_comm written straight into ``comm[t + 1]``) -> ``env.step``.  The message is recurrent
+    across env steps: ``comm[t + 1]`` is the communication the agents formed at step t and the input of step t + 1; ``comm[0]`` is zero
+    (the reset).  Returns ``state`` [T+1, E*N, F], ``comm`` [T+1, E*N, C], ``action`` int64 [T, E*N], ``a_prob`` [T, E*N], ``value``
+    [T+1, E] (one value per env-step; ``value[T]`` = V(state[T], comm[T]), the bootstrap), ``reward``, ``done`` (True on the last
+    step) and ``return`` [T, E*N]: storage.py:81-87's R_t = r_t + gamma R_{t+1} from R_T = value[T] broadcast to the agents, through
+    ``discounted_returns``.  House-sharded envs are refused: the attention needs every agent of an env."""
+    from .tarmac_a2c import TarMACA2CPolicy
+    if not isinstance(policy, TarMACA2CPolicy):
+        raise ValueError("collect_tarmac_a2c_rollout takes a TarMACA2CPolicy")
+    if getattr(env, "sharded", False):
+        raise ValueError("TarMAC over house-sharded envs is not supported: the attention needs every agent of an env")
+    E, N = env.nb_envs, env.nb_houses
+    F_len, Cc = env.obs_vector_length(), policy.comm_size
+    if F_len != policy.nb_obs:
+        raise ValueError("the env observes %d features, the policy takes %d" % (F_len, policy.nb_obs))
+    dev = env.device
+    T = int(nb_steps)
+    states = torch.empty((T + 1, E * N, F_len), dtype=torch.float32, device=dev)
+    comm = torch.empty((T + 1, E * N, Cc), dtype=torch.float32, device=dev)
+    comm[0].zero_()
+    act_u8 = torch.empty((T, E * N), dtype=torch.uint8, device=dev)
+    a_prob = torch.empty((T, E * N), dtype=torch.float32, device=dev)
+    value = torch.empty((T + 1, E), dtype=torch.float32, device=dev)
+    reward = torch.empty((T, E * N), dtype=torch.float32, device=dev)
+    planes_were_on = bool(getattr(env, "_obs_planes_on", True))
+    if planes_were_on:
+        env.set_obs_planes(False)
+    env.obs_vector("rows", out=states[0].view(E, N, F_len))
+    step0 = env.steps_taken
+    for t in range(T):
+        _, _, v, _ = policy.act(states[t].view(E, N, F_len), comm[t].view(E, N, Cc), seed, step0 + t, action=act_u8[t], a_prob=a_prob[t],
+                                comm_out=comm[t + 1].view(E, N, Cc))
+        value[t] = v
+        _, r, _, _ = env.step(act_u8[t].view(E, N))
+        reward[t] = r.reshape(-1)
+        env.obs_vector("rows", out=states[t + 1].view(E, N, F_len))
+    if planes_were_on and not env._obs_planes_on:
+        env.set_obs_planes(True)
+    value[T] = policy.get_value(states[T].view(E, N, F_len), comm[T].view(E, N, Cc))
+    done = torch.zeros((T, E * N), dtype=torch.bool, device=dev)
+    bootstrap = None
+    if T > 0:
+        done[T - 1] = True
+        bootstrap = torch.zeros((T, E * N), dtype=torch.float32, device=dev)
+        bootstrap[T - 1] = value[T][:, None].expand(E, N).reshape(-1)
+    env._exchange_check()
+    return {"state": states, "comm": comm, "action": act_u8.to(torch.int64), "a_prob": a_prob, "value": value, "reward": reward, "done": done,
+            "return": discounted_returns(reward, done, gamma, bootstrap)}
+
+
+@torch.no_grad()
 def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float = 1.0, epsilon_decay: float = 1.0,
                             min_epsilon: float = 0.0, seed: int = 0, policy_precision: str = "fp32") -> Dict[str, torch.Tensor]:
     """The interaction loop of train_dqn.py:55-91 for all envs at once, transitions kept on the GPU: every step the epsilon-greedy
@@ -466,7 +520,8 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     [E, N], ``sq_temp_error_sum`` [E] (sum over steps and houses of (house_temp - target)^2), ``sq_signal_error_sum`` [E] (sum over
     steps of (reg_signal - cluster_hvac_power)^2).
 
-    ``policy``: a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused), a
+    ``policy``: a ``TarMACA2CPolicy`` (the agent of train_tarmac.py; eager only, the message carried from step to step, zero before
+    the first), a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused), a
     ``FusedTarMACActor`` (the same agent as one chain of HIP kernels, exact fp32 or ``precision="bf16x3"``: observation rows, the chain with ``step_dev =
     env.device_time_index``, ``env.step`` - one stream, no parallel branches, so ``use_graph=True`` captures it), the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
     here, and observation and policy are then ONE kernel wherever ``collect_ppo_rollout`` would make them one (no observation rows at
@@ -479,14 +534,16 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     ``torch.cuda.CUDAGraph`` and replayed - the launch-bound regime of small batches."""
     from .policy import FEATURES_OBSERVE
     from .tarmac import FusedTarMACActor, TarMACActor
+    from .tarmac_a2c import TarMACA2CPolicy
     E, N = env.nb_envs, env.nb_houses
     dev = env.device
     F_len = env.obs_vector_length()
     fused_tarmac = isinstance(policy, FusedTarMACActor)
-    tarmac = fused_tarmac or isinstance(policy, TarMACActor)
+    a2c = isinstance(policy, TarMACA2CPolicy)
+    tarmac = fused_tarmac or a2c or isinstance(policy, TarMACActor)
     if tarmac:
         if use_graph and not fused_tarmac:
-            raise ValueError("deploy_policy runs a TarMACActor eagerly: its GEMMs and kernels are not captured")
+            raise ValueError("deploy_policy runs a %s eagerly: its GEMMs and kernels are not captured" % ("TarMACA2CPolicy" if a2c else "TarMACActor"))
         if getattr(env, "sharded", False):
             raise ValueError("TarMAC over house-sharded envs is not supported")
         if not fused_tarmac:
@@ -498,6 +555,8 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
                                msg_floats=4 * _observe_senders(env), greedy=greedy)
     tarmac_observe = _tarmac_observe_act(env, policy, observe_act)
     one_kernel = getattr(policy, "feature_order", 0) == FEATURES_OBSERVE
+    # a TarMACA2CPolicy carries its message between the steps: two buffers, the comm_out of one step the comm_in of the next
+    a2c_comm = [torch.zeros((E, N, policy.comm_size), dtype=torch.float32, device=dev) for _ in range(2)] if a2c else None
     obs = None if one_kernel or tarmac_observe else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
     act = torch.empty(E * N, dtype=torch.uint8, device=dev)
     act_prob = torch.empty(E * N, dtype=torch.float32, device=dev) if tarmac else None      # no allocation inside a captured step
@@ -520,6 +579,10 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
             policy.sample_env(env, seed, step0 + t, action=act, step_dev=step_dev)
         elif tarmac_observe:  # the fused TarMAC chain fed from the compact state: no observation rows either
             policy.sample_env(env, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act, a_prob=act_prob)
+        elif a2c:            # MultiAgentPolicy.act (agents/tarmac/model.py:169-178); zeros before the first step, as after a reset
+            env.obs_vector("rows", out=obs)
+            policy.act(obs, a2c_comm[0], seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act, a_prob=act_prob, comm_out=a2c_comm[1])
+            a2c_comm.reverse()
         elif tarmac:         # TarmacPPOAgent.act (agents/rl_controllers.py:86-122): the agents of an env attend to each other
             env.obs_vector("rows", out=obs)
             policy.sample(obs, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act, a_prob=act_prob)
