@@ -767,6 +767,60 @@ int mdr_adam_step(const mdr_adam_segments_t *segments, float *exp_avg, float *ex
                   double eps, int64_t step, double max_grad_norm, double grad_clamp, double tau, void *workspace,
                   float *total_norm_out, int32_t max_fused_floats, void *stream);
 
+/* The two bias corrections of mdr_adam_step as it forms them on the host, for the steps first_step .. first_step + count - 1:
+ *   out[2 k]     = (float)(lr / (1 - pow(beta1, step)))      step_size
+ *   out[2 k + 1] = (float)sqrt(1 - pow(beta2, step))         bc2_sqrt       step = first_step + k, in double, one cast to float
+ * - the very expressions, so the entries are that function's bits.  Host-only, no device call.  Returns 0; -1 (out NULL, first_step
+ * < 1, count < 0, lr NaN, betas outside [0, 1)). */
+int mdr_adam_corrections(double lr, double beta1, double beta2, int64_t first_step, int64_t count, float *out_host_floats);
+
+/* mdr_adam_step with the bias corrections read from device memory, so that a launch captured into a graph takes another step's
+ * corrections at every replay: `corrections` (device float pairs {step_size, bc2_sqrt}, mdr_adam_corrections' uploaded by the
+ * caller), pair number slot + (base_dev ? *base_dev : 0) (`base_dev`: one device int32, may be NULL; the caller keeps the sum inside
+ * the table - the kernel cannot know its length).  `lr` is not read beyond the NaN check: the table carries it.  Everything else -
+ * the arithmetic, the forms, the workspace, the return codes - as mdr_adam_step, and the same bits as its call with the step whose
+ * pair is read; additionally -1 for corrections NULL or slot < 0. */
+int mdr_adam_step_table(const mdr_adam_segments_t *segments, float *exp_avg, float *exp_avg_sq, double lr, double beta1, double beta2,
+                        double eps, const float *corrections, int32_t slot, const int32_t *base_dev, double max_grad_norm,
+                        double grad_clamp, double tau, void *workspace, float *total_norm_out, int32_t max_fused_floats, void *stream);
+
+/* ---- Minibatch indices drawn on the device (csrc/mdr_minibatch.hip), so that a whole update can be captured into a graph.
+ *
+ * A permutation of 0 .. n - 1 into `out` (device int64 [n]), one thread per element, no sort: a balanced Feistel network with
+ * cycle walking.  b = max(1, ceil(log2 n)), h = ceil(b / 2); the domain is the 2h-bit integers (fewer than 4 n of them for n > 1).
+ * Element i: x = i; x = feistel(x) until x < n; out[i] = x.  feistel: L = x >> h, R = x & (2^h - 1); four rounds r = 0..3 of
+ * (L, R) = (R, L ^ (F(r, R) & (2^h - 1))); the result is (L << h) | R.  F(r, R) = word .x of Philox4x32-10 on the counter
+ * (R, r, epoch lo + *cursor_dev, MDR_TAG_MINIBATCH ^ epoch hi) under the key (seed lo, seed hi).  A balanced Feistel network is a
+ * bijection whatever F is, and cycle walking keeps it one on [0, n).  `cursor_dev` (may be NULL): one device int32 added to the low
+ * word of `epoch` (mod 2^32, no carry), read when the kernel runs - a captured launch draws a new permutation at every replay.
+ * The _keyed form reads the key from the device as well: key_dev[0] = seed lo, key_dev[1] = seed hi (device int32 [2]).
+ * n == 0 launches nothing.  Stream-ordered, never synchronises, allocates nothing.
+ * Returns 0; -1 (n < 0, out NULL with n > 0, key_dev NULL); -3 (HIP error); -4 (n >= 2^62). */
+#define MDR_TAG_MINIBATCH 0x4D425031u /* "MBP1" */
+#define MDR_TAG_REPLAY 0x4D425331u    /* "MBS1" */
+int mdr_minibatch_permutation(int64_t n, uint64_t seed, uint64_t epoch, const int32_t *cursor_dev, int64_t *out, void *stream);
+int mdr_minibatch_permutation_keyed(int64_t n, const int32_t *key_dev, uint64_t epoch, const int32_t *cursor_dev, int64_t *out,
+                                    void *stream);
+
+/* nb positions drawn uniformly with replacement from [0, len) into `out` (device int64 [nb]) - random.choices, agents/buffer.py:26-27:
+ * out[i] = (word * len) >> 32 with word = .x of Philox4x32-10 on the counter (i lo, i hi, step lo + *cursor_dev, MDR_TAG_REPLAY ^ step hi)
+ * under the key (seed lo, seed hi).  `len_dev` (may be NULL: `len` is taken): one device int64 read when the kernel runs, so that a
+ * captured launch follows a growing buffer; either way 1 <= len <= 2^32 - 1 (a device value outside that range is clamped into it:
+ * the kernel cannot refuse).  The multiply-high maps 2^32 words onto len values, so some values are hit once more often than others:
+ * the bias of any value's probability is at most len / 2^32 relative (1.2e-4 at len = 524288).  _keyed: the key from the device, as above.
+ * nb == 0 launches nothing.  Returns 0; -1 (nb < 0, out NULL with nb > 0, len_dev NULL with len outside [1, 2^32 - 1], key_dev
+ * NULL); -3 (HIP error). */
+int mdr_minibatch_sample(int64_t nb, const int64_t *len_dev, int64_t len, uint64_t seed, uint64_t step, const int32_t *cursor_dev,
+                         int64_t *out, void *stream);
+int mdr_minibatch_sample_keyed(int64_t nb, const int64_t *len_dev, int64_t len, const int32_t *key_dev, uint64_t step,
+                               const int32_t *cursor_dev, int64_t *out, void *stream);
+
+/* The device block such captured launches read their cursors from, written stream-ordered by one-thread kernels whose values are
+ * kernel arguments (copied at launch: no staging buffer that could be overwritten too early).  _set: dst[k] = v_k for k < count
+ * (1 <= count <= 4); _add: dst[index] += delta.  Returns 0; -1 (dst NULL, count outside 1..4, index < 0); -3 (HIP error). */
+int mdr_update_cursor_set(int32_t *dst, int32_t count, int32_t v0, int32_t v1, int32_t v2, int32_t v3, void *stream);
+int mdr_update_cursor_add(int32_t *dst, int32_t index, int32_t delta, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

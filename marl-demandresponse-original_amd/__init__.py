@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("BatchedDemandResponseEnv", "OBS_COLUMNS"):
         from . import batched_env
         return getattr(batched_env, name)
-    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "maddpg", "optim", "tarmac_a2c"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
+    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "maddpg", "optim", "tarmac_a2c", "graph_update"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "BatchedMetrics":

@@ -197,7 +197,9 @@ EXPORTS = (
     "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
     "mdr_tarmac_critic_grad_floats", "mdr_tarmac_critic_workspace_bytes", "mdr_tarmac_critic_value", "mdr_tarmac_critic_grad",
     "mdr_tarmac_a2c_grad_floats", "mdr_tarmac_a2c_workspace_bytes", "mdr_tarmac_a2c_forward", "mdr_tarmac_a2c_comm", "mdr_tarmac_a2c_grad",
-    "mdr_adam_workspace_bytes", "mdr_adam_step",
+    "mdr_adam_workspace_bytes", "mdr_adam_step", "mdr_adam_step_table", "mdr_adam_corrections",
+    "mdr_minibatch_permutation", "mdr_minibatch_permutation_keyed", "mdr_minibatch_sample", "mdr_minibatch_sample_keyed",
+    "mdr_update_cursor_set", "mdr_update_cursor_add",
 )
 
 _lib = None
@@ -322,6 +324,15 @@ def load():
         "mdr_adam_workspace_bytes": (i64, [i64]),
         "mdr_adam_step": (C.c_int, [C.POINTER(MdrAdamSegments), vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, i64, C.c_double, C.c_double,
                                     C.c_double, vp, vp, i32, vp]),
+        "mdr_adam_step_table": (C.c_int, [C.POINTER(MdrAdamSegments), vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, i32, vp,
+                                          C.c_double, C.c_double, C.c_double, vp, vp, i32, vp]),
+        "mdr_adam_corrections": (C.c_int, [C.c_double, C.c_double, C.c_double, i64, i64, vp]),
+        "mdr_minibatch_permutation": (C.c_int, [i64, u64, u64, vp, vp, vp]),
+        "mdr_minibatch_permutation_keyed": (C.c_int, [i64, vp, u64, vp, vp, vp]),
+        "mdr_minibatch_sample": (C.c_int, [i64, vp, i64, u64, u64, vp, vp, vp]),
+        "mdr_minibatch_sample_keyed": (C.c_int, [i64, vp, i64, vp, u64, vp, vp, vp]),
+        "mdr_update_cursor_set": (C.c_int, [vp, i32, i32, i32, i32, i32, vp]),
+        "mdr_update_cursor_add": (C.c_int, [vp, i32, i32, vp]),
         "mdr_env_pack": (C.c_int, [vp, i32, vp, vp]),
         "mdr_env_graph_room": (i64, [vp]),
         "mdr_env_graph_replayed": (C.c_int, [vp, i64, vp]),

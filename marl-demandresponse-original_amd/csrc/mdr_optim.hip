@@ -58,6 +58,23 @@ struct StepArgs {
   int32_t do_norm, do_clip, do_blend;
 };
 
+// mdr_adam_step_table (k_adam_step<.., true>): the pair {step_size, bc2_sqrt} number slot + *base_dev of corrections.  A type of its
+// own, so that the kernels of mdr_adam_step take the arguments - and compile to the instructions - they always did.
+struct TableStepArgs : StepArgs {
+  const float* corrections;
+  const int32_t* base_dev;      // may be NULL
+  int32_t slot;
+};
+
+template <bool TABLE>
+struct ArgsOf {
+  using type = StepArgs;
+};
+template <>
+struct ArgsOf<true> {
+  using type = TableStepArgs;
+};
+
 // comparisons, not fminf / fmaxf: a NaN stays a NaN (k_grad_reduce_clamped); c = inf clamps nothing
 __device__ __forceinline__ float clampf(float g, float c) { return g < -c ? -c : (g > c ? c : g); }
 
@@ -103,12 +120,19 @@ __device__ __forceinline__ float ordered_sum(const float* x, int n) {
 }
 
 // one element: clamp -> coef g -> the moments -> the parameter -> the target, as torch.optim.Adam's defaults (no weight decay, no amsgrad)
-__device__ __forceinline__ void adam_elem(const StepArgs& a, float coef, float g, float& p, float& m, float& v, float& t) {
+// TABLE: the two bias corrections are `ss` and `bc` (read from the table), otherwise the kernel arguments'
+template <bool TABLE>
+__device__ __forceinline__ void adam_elem(const StepArgs& a, float ss, float bc, float coef, float g, float& p, float& m, float& v, float& t) {
   g = coef * clampf(g, a.clamp);      // coef == 1 without a clip: exact
   m = a.b1 * m + a.omb1 * g;
   v = a.b2 * v + a.omb2 * (g * g);
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  p = p - a.step_size * (m / denom);
+  if constexpr (TABLE) {
+    const float denom = sqrtf(v) / bc + a.eps;
+    p = p - ss * (m / denom);
+  } else {
+    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+    p = p - a.step_size * (m / denom);
+  }
   t = a.omtau * t + a.tau * p;      // stored only with a blend
 }
 
@@ -129,8 +153,9 @@ __global__ __launch_bounds__(THREADS) void k_adam_sumsq(const StepArgs a, float*
   }
 }
 
-template <bool FUSED>
-__global__ __launch_bounds__(THREADS) void k_adam_step(const StepArgs a) {
+// TABLE: the two bias corrections come from device memory (mdr_adam_step_table) instead of the kernel arguments; nothing else differs
+template <bool FUSED, bool TABLE>
+__global__ __launch_bounds__(THREADS) void k_adam_step(const typename ArgsOf<TABLE>::type a) {
   __shared__ float csum[FUSED ? MAX_FUSED_CHUNKS : 1];
   const int tid = threadIdx.x;
   float coef = 1.0f;
@@ -162,6 +187,11 @@ __global__ __launch_bounds__(THREADS) void k_adam_step(const StepArgs a) {
       coef = c > 1.0f ? 1.0f : c;      // a NaN norm gives a NaN coef
     }
   }
+  float step_size = 0.0f, bc2_sqrt = 1.0f;      // read below with TABLE only
+  if constexpr (TABLE) {
+    const int64_t pair = (int64_t)a.slot + (a.base_dev ? (int64_t)*a.base_dev : 0);
+    step_size = a.corrections[2 * pair], bc2_sqrt = a.corrections[2 * pair + 1];
+  }
   const int grid = (int)gridDim.x, b = (int)blockIdx.x;
   for (int s = 0; s < a.nseg; ++s) {
     const int c0 = a.chunk0[s], nck = a.chunk0[s + 1] - c0;
@@ -180,10 +210,10 @@ __global__ __launch_bounds__(THREADS) void k_adam_step(const StepArgs a) {
         float4 p4 = *reinterpret_cast<float4*>(sg.p + i), m4 = *reinterpret_cast<float4*>(m + i), v4 = *reinterpret_cast<float4*>(v + i);
         float4 t4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (a.do_blend) t4 = *reinterpret_cast<float4*>(sg.t + i);
-        adam_elem(a, coef, g4.x, p4.x, m4.x, v4.x, t4.x);
-        adam_elem(a, coef, g4.y, p4.y, m4.y, v4.y, t4.y);
-        adam_elem(a, coef, g4.z, p4.z, m4.z, v4.z, t4.z);
-        adam_elem(a, coef, g4.w, p4.w, m4.w, v4.w, t4.w);
+        adam_elem<TABLE>(a, step_size, bc2_sqrt, coef, g4.x, p4.x, m4.x, v4.x, t4.x);
+        adam_elem<TABLE>(a, step_size, bc2_sqrt, coef, g4.y, p4.y, m4.y, v4.y, t4.y);
+        adam_elem<TABLE>(a, step_size, bc2_sqrt, coef, g4.z, p4.z, m4.z, v4.z, t4.z);
+        adam_elem<TABLE>(a, step_size, bc2_sqrt, coef, g4.w, p4.w, m4.w, v4.w, t4.w);
         *reinterpret_cast<float4*>(sg.p + i) = p4;
         *reinterpret_cast<float4*>(m + i) = m4;
         *reinterpret_cast<float4*>(v + i) = v4;
@@ -191,7 +221,7 @@ __global__ __launch_bounds__(THREADS) void k_adam_step(const StepArgs a) {
       } else {
         for (int j = 0; j < 4 && i + j < sg.n; ++j) {
           float p1 = sg.p[i + j], m1 = m[i + j], v1 = v[i + j], t1 = a.do_blend ? sg.t[i + j] : 0.0f;
-          adam_elem(a, coef, sg.g[i + j], p1, m1, v1, t1);
+          adam_elem<TABLE>(a, step_size, bc2_sqrt, coef, sg.g[i + j], p1, m1, v1, t1);
           sg.p[i + j] = p1, m[i + j] = m1, v[i + j] = v1;
           if (a.do_blend) sg.t[i + j] = t1;
         }
@@ -199,6 +229,10 @@ __global__ __launch_bounds__(THREADS) void k_adam_step(const StepArgs a) {
     }
   }
 }
+
+// the two bias corrections of one step: formed in double, one cast to float (mdr_adam_step and mdr_adam_corrections share them)
+float step_size_of(double lr, double beta1, int64_t step) { return (float)(lr / (1.0 - std::pow(beta1, (double)step))); }
+float bc2_sqrt_of(double beta2, int64_t step) { return (float)std::sqrt(1.0 - std::pow(beta2, (double)step)); }
 
 int64_t workspace_bytes(int64_t total_floats) {
   // chunks <= sum over the segments of ceil(count / CHUNK) <= total / CHUNK + segments
@@ -211,9 +245,15 @@ extern "C" {
 
 int64_t mdr_adam_workspace_bytes(int64_t total_floats) { return total_floats < 0 ? -1 : workspace_bytes(total_floats); }
 
-int mdr_adam_step(const mdr_adam_segments_t* segments, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
-                  int64_t step, double max_grad_norm, double grad_clamp, double tau, void* workspace, float* total_norm_out,
-                  int32_t max_fused_floats, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// mdr_adam_step (corrections NULL: the bias corrections of `step` as kernel arguments) and mdr_adam_step_table (from device memory)
+int adam_step(const mdr_adam_segments_t* segments, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
+              int64_t step, const float* corrections, int32_t slot, const int32_t* base_dev, double max_grad_norm, double grad_clamp, double tau,
+              void* workspace, float* total_norm_out, int32_t max_fused_floats, void* stream) {
+  const bool table = corrections != nullptr;
   if (!segments || segments->struct_size != sizeof(mdr_adam_segments_t) || !exp_avg || !exp_avg_sq) return MDR_ERR_INVALID;
   if (segments->nb_segments < 0) return MDR_ERR_INVALID;
   if (segments->nb_segments > MDR_ADAM_MAX_SEGMENTS) return MDR_ERR_UNSUPPORTED;
@@ -222,7 +262,7 @@ int mdr_adam_step(const mdr_adam_segments_t* segments, float* exp_avg, float* ex
   if (grad_clamp != grad_clamp || grad_clamp <= 0.0) return MDR_ERR_INVALID;      // INFINITY: no clamp
   const bool blend = tau > 0.0;
   const bool clip = max_grad_norm > 0.0 && !std::isinf(max_grad_norm);      // <= 0, inf or NaN: no clip
-  StepArgs a{};
+  TableStepArgs a{};
   int64_t total = 0, chunks = 0;
   for (int s = 0; s < segments->nb_segments; ++s) {
     const mdr_adam_segment_t& in = segments->seg[s];
@@ -239,8 +279,9 @@ int mdr_adam_step(const mdr_adam_segments_t* segments, float* exp_avg, float* ex
   if (chunks == 0 && !total_norm_out) return MDR_OK;
   a.m = exp_avg, a.v = exp_avg_sq, a.norm_out = total_norm_out;
   a.b1 = (float)beta1, a.omb1 = (float)(1.0 - beta1), a.b2 = (float)beta2, a.omb2 = (float)(1.0 - beta2);
-  a.step_size = (float)(lr / (1.0 - std::pow(beta1, (double)step)));
-  a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
+  a.step_size = table ? 0.0f : step_size_of(lr, beta1, step);
+  a.bc2_sqrt = table ? 1.0f : bc2_sqrt_of(beta2, step);
+  a.corrections = corrections, a.base_dev = base_dev, a.slot = slot;
   a.eps = (float)eps, a.max_norm = (float)max_grad_norm, a.clamp = (float)grad_clamp;
   a.tau = blend ? (float)tau : 0.0f, a.omtau = blend ? (float)(1.0 - tau) : 0.0f;
   a.do_clip = clip, a.do_norm = clip || total_norm_out != nullptr, a.do_blend = blend;
@@ -249,14 +290,49 @@ int mdr_adam_step(const mdr_adam_segments_t* segments, float* exp_avg, float* ex
   const bool fused = !a.do_norm || (total <= limit && chunks <= MAX_FUSED_CHUNKS);
   const unsigned grid = (unsigned)(chunks < 1 ? 1 : (chunks > MAX_GRID ? MAX_GRID : chunks));
   if (fused) {
-    hipLaunchKernelGGL(k_adam_step<true>, dim3(grid), dim3(THREADS), 0, st, a);
+    if (table)
+      hipLaunchKernelGGL((k_adam_step<true, true>), dim3(grid), dim3(THREADS), 0, st, a);
+    else
+      hipLaunchKernelGGL((k_adam_step<true, false>), dim3(grid), dim3(THREADS), 0, st, static_cast<const StepArgs&>(a));
   } else {
     if (!workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
     a.partial = static_cast<const float*>(workspace);
-    hipLaunchKernelGGL(k_adam_sumsq, dim3((unsigned)((chunks + 3) / 4)), dim3(THREADS), 0, st, a, static_cast<float*>(workspace));
-    hipLaunchKernelGGL(k_adam_step<false>, dim3(grid), dim3(THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_adam_sumsq, dim3((unsigned)((chunks + 3) / 4)), dim3(THREADS), 0, st, static_cast<const StepArgs&>(a), static_cast<float*>(workspace));
+    if (table)
+      hipLaunchKernelGGL((k_adam_step<false, true>), dim3(grid), dim3(THREADS), 0, st, a);
+    else
+      hipLaunchKernelGGL((k_adam_step<false, false>), dim3(grid), dim3(THREADS), 0, st, static_cast<const StepArgs&>(a));
   }
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdr_adam_step(const mdr_adam_segments_t* segments, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
+                  int64_t step, double max_grad_norm, double grad_clamp, double tau, void* workspace, float* total_norm_out,
+                  int32_t max_fused_floats, void* stream) {
+  return adam_step(segments, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, nullptr, 0, nullptr, max_grad_norm, grad_clamp, tau, workspace,
+                   total_norm_out, max_fused_floats, stream);
+}
+
+int mdr_adam_step_table(const mdr_adam_segments_t* segments, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
+                        const float* corrections, int32_t slot, const int32_t* base_dev, double max_grad_norm, double grad_clamp, double tau,
+                        void* workspace, float* total_norm_out, int32_t max_fused_floats, void* stream) {
+  if (!corrections || slot < 0) return MDR_ERR_INVALID;
+  return adam_step(segments, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, 1, corrections, slot, base_dev, max_grad_norm, grad_clamp, tau,
+                   workspace, total_norm_out, max_fused_floats, stream);
+}
+
+int mdr_adam_corrections(double lr, double beta1, double beta2, int64_t first_step, int64_t count, float* out_host_floats) {
+  if (!out_host_floats || first_step < 1 || count < 0) return MDR_ERR_INVALID;
+  if (!(lr == lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return MDR_ERR_INVALID;
+  for (int64_t k = 0; k < count; ++k) {
+    out_host_floats[2 * k] = step_size_of(lr, beta1, first_step + k);
+    out_host_floats[2 * k + 1] = bc2_sqrt_of(beta2, first_step + k);
+  }
+  return MDR_OK;
 }
 
 }  // extern "C"

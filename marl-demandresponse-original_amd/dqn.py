@@ -192,7 +192,8 @@ class DQNLearner:
     GRAD_CLAMP = 1.0      # agents/dqn.py:108-109
 
     def __init__(self, policy_net, lr: float, gamma: float = 0.99, tau: float = 0.01, buffer_capacity: int = 524288, batch_size: int = 256,
-                 double: bool = False, backend: str = "auto", optimizer=torch.optim.Adam, soft_update: bool = True):
+                 double: bool = False, backend: str = "auto", optimizer=torch.optim.Adam, soft_update: bool = True,
+                 sampler: Optional[str] = None, graph: bool = False):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError("backend must be 'auto', 'hip' or 'torch'")
         if backend == "hip":
@@ -218,13 +219,30 @@ class DQNLearner:
         self._fused_target = [p for lin in self.target_net.fc for p in (lin.weight, lin.bias)] if same else None
         self.training_step = 0
         self.before_step = None      # optional callable(learner): runs after the backward (and the clamp) of an update, before the optimiser
+        # sampler="philox": the positions from csrc/mdr_minibatch.hip by (seed, training_step) instead of a torch.Generator;
+        # graph=True: every update replayed from one captured graph (graph_update.py)
+        if sampler is None:
+            sampler = "philox" if graph else "torch"
+        if sampler not in ("torch", "philox"):
+            raise ValueError("sampler must be 'torch' or 'philox'")
+        self.sampler, self.graph = sampler, bool(graph)
+        self.graph_captures = 0
+        self._graph = None
+        if self.graph:
+            from . import graph_update
+            why = graph_update.refusal(backend, sampler, (self.optimizer,), self.uses_kernels(max(self.batch_size, 1)))
+            if not why and self.soft_update and self._fused_target is None:
+                why = "the optimiser's parameters are not the six tensors the target net mirrors (the blend would be torch launches)"
+            if why:
+                raise ValueError("DQNLearner(graph=True): " + why)
 
     @classmethod
     def from_config(cls, dqn_prop: dict, policy_net, double: bool = False, backend: str = "auto", optimizer=torch.optim.Adam,
-                    soft_update: bool = True) -> "DQNLearner":
+                    soft_update: bool = True, sampler: Optional[str] = None, graph: bool = False) -> "DQNLearner":
         """From the reference's ``config_dict["DQN_prop"]`` (agents/dqn.py:23-29)."""
         return cls(policy_net, dqn_prop["lr"], gamma=dqn_prop["gamma"], tau=dqn_prop["tau"], buffer_capacity=dqn_prop["buffer_capacity"],
-                   batch_size=dqn_prop["batch_size"], double=double, backend=backend, optimizer=optimizer, soft_update=soft_update)
+                   batch_size=dqn_prop["batch_size"], double=double, backend=backend, optimizer=optimizer, soft_update=soft_update,
+                   sampler=sampler, graph=graph)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
@@ -238,9 +256,21 @@ class DQNLearner:
     def sample(self, seed: int) -> torch.Tensor:
         """The minibatch of this update: ``buffer.sample`` under a ``torch.Generator`` seeded by (seed, training_step) - the same
         positions whatever the backend."""
+        if self.sampler == "philox":      # one Philox word per position by (seed, training_step), one launch (graph_update.sample)
+            from . import graph_update
+            if len(self.buffer) == 0:
+                raise ValueError("DeviceReplayBuffer.sample: the buffer is empty")
+            return graph_update.sample(self.batch_size, len(self.buffer), seed, self.training_step, self.buffer.device)
         gen = torch.Generator(device=self.buffer.device)
         gen.manual_seed((int(seed) * 1000003 + self.training_step * 7919 + 12345) & (2 ** 63 - 1))
         return self.buffer.sample(self.batch_size, gen)
+
+    def _capture(self):
+        """Capture the graph of one update without replaying it; both nets, the moments and every counter are what they were."""
+        from . import graph_update
+        self._graph = graph_update.DQNUpdateGraph(self)
+        self.graph_captures += 1
+        return self._graph
 
     @torch.no_grad()
     def update_target_network(self) -> None:
@@ -276,7 +306,11 @@ class DQNLearner:
     def update(self, seed: int = 0) -> Optional[torch.Tensor]:
         """One ``update()`` of agents/dqn.py:84-112: sample -> TD target -> loss, backward and clamp -> ``optimizer.step()`` ->
         ``update_target_network()``.  -> the loss (0-dim device tensor), or None while the buffer holds fewer than ``batch_size``
-        transitions (:85-86)."""
+        transitions (:85-86).  ``graph=True``: the same launches replayed from a captured graph, the same bits as the eager
+        ``sampler="philox"`` update."""
+        if self.graph:
+            from . import graph_update
+            return graph_update.dqn_update(self, seed)
         if len(self.buffer) < self.batch_size:
             return None
         loss = self.loss_backward(self.sample(seed))

@@ -110,7 +110,8 @@ class MAPPOLearner(PPOLearner):
     ``"auto"``: the kernels where they take both networks and the minibatch has at least ``AUTO_MIN_ROWS`` rows."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
-                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam):
+                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
+                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError("backend must be 'auto', 'hip' or 'torch'")
         afc, cfc = ppo._layers(actor), ppo._layers(critic)
@@ -126,16 +127,19 @@ class MAPPOLearner(PPOLearner):
                 raise ValueError("MAPPOLearner(backend='hip'): " + why)
         # the base class checks PPO's critic (over the state alone) for "hip": this one's is checked above
         super().__init__(actor, critic, lr_actor, lr_critic, clip_param=clip_param, max_grad_norm=max_grad_norm, ppo_update_time=ppo_update_time,
-                         batch_size=batch_size, backend="auto" if backend == "hip" else backend, optimizer=optimizer)
+                         batch_size=batch_size, backend="auto" if backend == "hip" else backend, optimizer=optimizer, sampler=sampler, graph=graph,
+                         graph_max_minibatches=graph_max_minibatches)
         self.backend = backend
         self._others = None      # the batch's others_actions [M, N - 1] during an update of the torch backend, where it has them
 
     @classmethod
-    def from_config(cls, mappo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam) -> "MAPPOLearner":
+    def from_config(cls, mappo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam, sampler: Optional[str] = None,
+                    graph: bool = False, graph_max_minibatches: int = 1024) -> "MAPPOLearner":
         """From the reference's ``config_dict["MAPPO_prop"]`` (agents/mappo.py:23-29)."""
         return cls(actor, critic, mappo_prop["lr_actor"], mappo_prop["lr_critic"], clip_param=mappo_prop["clip_param"],
                    max_grad_norm=mappo_prop["max_grad_norm"], ppo_update_time=mappo_prop["ppo_update_time"],
-                   batch_size=mappo_prop["batch_size"], backend=backend, optimizer=optimizer)
+                   batch_size=mappo_prop["batch_size"], backend=backend, optimizer=optimizer, sampler=sampler, graph=graph,
+                   graph_max_minibatches=graph_max_minibatches)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
@@ -144,6 +148,16 @@ class MAPPOLearner(PPOLearner):
 
     def critic_backward(self, state, action, target, index):
         return joint_critic_loss_backward(self.critic, state, action, target, nb_agents=self.nb_agents, index=index)
+
+    def _critic_grad_floats(self, lib, desc) -> int:
+        return int(lib.mdr_mappo_critic_grad_floats(C.byref(desc), self.nb_agents))
+
+    def _critic_workspace_bytes(self, lib, desc, nb_rows: int) -> int:
+        return int(lib.mdr_mappo_critic_workspace_bytes(C.byref(desc), self.nb_agents, nb_rows, 0))
+
+    def _critic_launch(self, lib, desc, state, ld, action, nb_transitions, target, index, nb_rows, workspace, grad, loss, value, adv, stream) -> int:
+        return lib.mdr_mappo_critic_grad(C.byref(desc), state, ld, action, nb_transitions, self.nb_agents, index, nb_rows, target, 0, workspace, grad,
+                                         loss, value, adv, stream)
 
     def critic_input(self, state, action, index) -> torch.Tensor:
         """agents/mappo.py:87: torch.cat((state[index], others_actions[index]), dim=1)."""

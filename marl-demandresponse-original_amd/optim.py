@@ -163,13 +163,21 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, max_grad_norm: Optional[float] = None, grad_clamp: Optional[float] = None, target: Optional[Sequence[torch.Tensor]] = None,
-             tau: Optional[float] = None, want_norm: bool = False) -> Optional[torch.Tensor]:
+             tau: Optional[float] = None, want_norm: bool = False, *, corrections: Optional[torch.Tensor] = None, slot: Optional[int] = None,
+             base_dev: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """clamp -> norm clip -> Adam -> blend for every parameter that has a gradient, in one launch on the current stream; never
         synchronises.  ``max_grad_norm``: ``clip_grad_norm_``'s (None: no clip); ``grad_clamp``: ``p.grad.clamp_(-c, c)`` first (None: no
         clamp); ``target`` (tensors parallel to the parameters) with ``tau``: ``target = (1 - tau) target + tau p`` from the new p.
         ``p.grad`` is NOT modified (module docstring).  -> the total norm of the (clamped) gradient, a 0-dim device tensor overwritten
-        by the next call, with ``want_norm``; None otherwise."""
+        by the next call, with ``want_norm``; None otherwise.
+
+        ``corrections`` (float32 device tensor of ``correction_table`` pairs) with ``slot`` [and ``base_dev``, one device int32]: the
+        launch a captured graph replays (mdr_adam_step_table) - the bias corrections are pair ``slot + base_dev`` of the table, read on
+        the device, the host's step counts are neither read nor advanced (``advance`` does that after the replays), and the bits are
+        those of the plain call at the step the pair was made for."""
         group = self._check_group()
+        if corrections is not None or slot is not None or base_dev is not None:
+            return self._step_table(group, max_grad_norm, grad_clamp, target, tau, want_norm, corrections, slot, base_dev)
         blend = target is not None and tau is not None and float(tau) > 0.0
         if (target is None) != (tau is None):
             raise ValueError("FusedAdam.step: target and tau go together")
@@ -198,3 +206,70 @@ class FusedAdam(torch.optim.Optimizer):
         self._t = t
         torch._foreach_add_(self._steps, 1)      # host tensors, as torch.optim.Adam keeps them
         return self._norm if want_norm else None
+
+    # -- the step a captured graph replays -----------------------------------------------------------------------------------------
+    def _step_table(self, group, max_grad_norm, grad_clamp, target, tau, want_norm, corrections, slot, base_dev):
+        if corrections is None or slot is None:
+            raise ValueError("FusedAdam.step: corrections and slot go together (base_dev is optional)")
+        dev = self._device
+        if corrections.dtype != torch.float32 or corrections.device != dev or not corrections.is_contiguous() or corrections.numel() % 2:
+            raise ValueError("FusedAdam.step: corrections must be a contiguous float32 tensor of {step_size, bc2_sqrt} pairs on the parameters' GPU")
+        if not 0 <= int(slot) < corrections.numel() // 2:
+            raise ValueError("FusedAdam.step: slot %r outside the table of %d pairs" % (slot, corrections.numel() // 2))
+        if base_dev is not None and (base_dev.dtype != torch.int32 or base_dev.device != dev or base_dev.numel() != 1):
+            raise ValueError("FusedAdam.step: base_dev must be one int32 on the parameters' GPU")
+        blend = target is not None and tau is not None and float(tau) > 0.0
+        if (target is None) != (tau is None):
+            raise ValueError("FusedAdam.step: target and tau go together")
+        if blend and len(target) != len(self._params):
+            raise ValueError("FusedAdam.step: target must list one tensor per parameter (%d), got %d" % (len(self._params), len(target)))
+        grads = [p.grad for p in self._params]
+        key = []
+        for i, p in enumerate(self._params):
+            g = grads[i]
+            t = target[i] if blend else None
+            key += [p.data_ptr(), g.data_ptr() if g is not None else 0, t.data_ptr() if t is not None else 0]
+        if key != self._key:
+            self._build(key, grads, target if blend else None)
+        if not self._live:
+            return self._norm.zero_() if want_norm else None
+        beta1, beta2 = group["betas"]
+        with torch.cuda.device(dev):
+            rc = self._lib.mdr_adam_step_table(C.byref(self._table), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(), float(group["lr"]),
+                                               float(beta1), float(beta2), float(group["eps"]), corrections.data_ptr(), int(slot),
+                                               base_dev.data_ptr() if base_dev is not None else None,
+                                               float(max_grad_norm) if max_grad_norm is not None else 0.0,
+                                               float(grad_clamp) if grad_clamp is not None else math.inf, float(tau) if blend else 0.0,
+                                               self._workspace.data_ptr(), self._norm.data_ptr() if want_norm else None, self.max_fused_floats,
+                                               torch.cuda.current_stream(dev).cuda_stream)
+        nat.check(self._lib, None, rc, "mdr_adam_step_table")
+        return self._norm if want_norm else None
+
+    def step_count(self) -> int:
+        """The step count of the parameters that have stepped (0: none has), from the host's bookkeeping; ValueError where they differ."""
+        counts = {int(st["step"]) for st in (self.state.get(p) for p in self._params) if st}
+        if len(counts) > 1:
+            raise ValueError("FusedAdam: the parameters are at different step counts")
+        return counts.pop() if counts else 0
+
+    def correction_table(self, count: int, first_step: Optional[int] = None) -> torch.Tensor:
+        """The {step_size, bc2_sqrt} pairs of the steps ``first_step`` (default: the next one) .. ``first_step + count - 1`` as a fresh
+        pinned float32 [2 count] host tensor (mdr_adam_corrections: ``mdr_adam_step``'s own expressions, hence its bits).  A fresh
+        tensor per call, so that a stream-ordered upload that has not run yet never sees a later call's values."""
+        group = self._check_group()
+        first = self.step_count() + 1 if first_step is None else int(first_step)
+        out = torch.empty(2 * int(count), dtype=torch.float32, pin_memory=torch.cuda.is_available())
+        beta1, beta2 = group["betas"]
+        rc = self._lib.mdr_adam_corrections(float(group["lr"]), float(beta1), float(beta2), first, int(count), out.data_ptr())
+        nat.check(self._lib, None, rc, "mdr_adam_corrections")
+        return out
+
+    def advance(self, count: int) -> None:
+        """Add ``count`` to the step bookkeeping of every parameter that has a gradient - what ``count`` replayed table steps did on
+        the device.  Host only."""
+        if int(count) < 0:
+            raise ValueError("FusedAdam.advance: count must be >= 0")
+        steps = [(self.state[p] or self._adopt(i))["step"] for i, p in enumerate(self._params) if p.grad is not None]
+        if steps:
+            torch._foreach_add_(steps, int(count))
+        self._t += int(count)

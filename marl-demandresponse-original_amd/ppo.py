@@ -194,9 +194,14 @@ class PPOLearner:
     (``.grad`` then keeps the unclipped gradient), any other one is stepped after ``clip_grad_norm_``."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
-                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam):
+                 ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
+                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        if sampler is None:
+            sampler = "philox" if graph else "torch"
+        if sampler not in ("torch", "philox"):
+            raise ValueError("sampler must be 'torch' or 'philox'")
         if backend == "hip":
             for net, outs in ((actor, 2), (critic, 1)):
                 why = _refusal(net, outs)
@@ -210,13 +215,25 @@ class PPOLearner:
         self.critic_optimizer = optimizer(critic.parameters(), lr_critic)
         self.training_step = 0
         self.before_clip = None      # optional callable(learner): runs after both backward passes of a minibatch, before the clipping
+        # sampler="philox": the minibatch indices from csrc/mdr_minibatch.hip by (seed, epoch) instead of a torch.Generator;
+        # graph=True: every epoch of an update replayed from one captured graph per batch shape (graph_update.py)
+        self.sampler, self.graph, self.graph_max_minibatches = sampler, bool(graph), int(graph_max_minibatches)
+        self.graph_captures = 0
+        self._graphs: Dict[tuple, object] = {}
+        if self.graph:
+            from . import graph_update
+            why = graph_update.refusal(backend, sampler, (self.actor_optimizer, self.critic_optimizer), self.uses_kernels(max(self.batch_size, 1)))
+            if why:
+                raise ValueError("%s(graph=True): %s" % (type(self).__name__, why))
 
     @classmethod
-    def from_config(cls, ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam) -> "PPOLearner":
+    def from_config(cls, ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam, sampler: Optional[str] = None,
+                    graph: bool = False, graph_max_minibatches: int = 1024) -> "PPOLearner":
         """From the reference's ``config_dict["PPO_prop"]`` (agents/ppo.py:34-40)."""
         return cls(actor, critic, ppo_prop["lr_actor"], ppo_prop["lr_critic"], clip_param=ppo_prop["clip_param"],
                    max_grad_norm=ppo_prop["max_grad_norm"], ppo_update_time=ppo_prop["ppo_update_time"],
-                   batch_size=ppo_prop["batch_size"], backend=backend, optimizer=optimizer)
+                   batch_size=ppo_prop["batch_size"], backend=backend, optimizer=optimizer, sampler=sampler, graph=graph,
+                   graph_max_minibatches=graph_max_minibatches)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
@@ -228,6 +245,10 @@ class PPOLearner:
         ``torch.Generator`` seeded by (seed, epoch), cut into ``batch_size`` pieces; the last, shorter one is kept, as
         ``BatchSampler(SubsetRandomSampler(...), batch_size, False)`` keeps it (agents/ppo.py:140-142)."""
         dev = next(self.actor.parameters()).device
+        if getattr(self, "sampler", "torch") == "philox":      # (subclasses with a constructor of their own have no sampler: torch's)
+            # the Feistel permutation of (seed, epoch), one launch (graph_update.permutation): another permutation, cut the same way
+            from . import graph_update
+            return list(torch.split(graph_update.permutation(int(nb_transitions), seed, epoch, dev), self.batch_size))
         gen = torch.Generator(device=dev)
         gen.manual_seed((int(seed) * 1000003 + int(epoch) * 7919 + 12345) & (2 ** 63 - 1))
         perm = torch.randperm(int(nb_transitions), generator=gen, device=dev)
@@ -236,6 +257,26 @@ class PPOLearner:
     def critic_backward(self, state, action, target, index):
         """The critic's kernel call of one minibatch -> (loss, value, advantage); MAPPOLearner's takes the joint input."""
         return critic_loss_backward(self.critic, state, target, index=index)
+
+    # the same call for a captured graph, on raw pointers into its static buffers (graph_update.PPOUpdateGraph); MAPPOLearner's differ
+    def _critic_grad_floats(self, lib, desc) -> int:
+        return int(lib.mdr_mlp_grad_floats(C.byref(desc)))
+
+    def _critic_workspace_bytes(self, lib, desc, nb_rows: int) -> int:
+        return int(lib.mdr_mlp_grad_workspace_bytes(C.byref(desc), nb_rows, 0))
+
+    def _critic_launch(self, lib, desc, state, ld, action, nb_transitions, target, index, nb_rows, workspace, grad, loss, value, adv, stream) -> int:
+        return lib.mdr_ppo_critic_grad(C.byref(desc), state, ld, index, nb_rows, target, 0, workspace, grad, loss, value, adv, stream)
+
+    def _capture(self, shape):
+        """Capture the graph of one epoch over a batch of ``shape`` = (T, A, F) without replaying it; parameters, moments and every
+        counter are what they were."""
+        from . import graph_update
+        T, A, F = (int(x) for x in shape)
+        g = graph_update.PPOUpdateGraph(self, T, A, F)
+        self._graphs[(T, A, F, self.ppo_update_time, self.batch_size)] = g
+        self.graph_captures += 1
+        return g
 
     def critic_input(self, state, action, index) -> torch.Tensor:
         """The critic's input rows of one minibatch on the torch backend."""
@@ -283,7 +324,13 @@ class PPOLearner:
     def update(self, batch: Dict[str, torch.Tensor], seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, int]:
         """``ppo_update_time`` epochs over ``batch`` (``state`` [T+1, A, F], ``action``, ``a_prob``, ``return`` [T, A]): the states are
         ``batch["state"][:-1]`` flattened to [T A, F] and read in place, Gt is ``batch["return"]``.  -> (mean actor loss, mean critic
-        loss - device tensors -, number of minibatches)."""
+        loss - device tensors -, number of minibatches).  ``graph=True``: the same launches replayed from a captured graph, the same
+        bits as the eager ``sampler="philox"`` update."""
+        if getattr(self, "graph", False):
+            from . import graph_update
+            done = graph_update.ppo_update(self, batch, seed)
+            if done is not None:      # None: an empty batch, nothing to replay
+                return done
         states = batch["state"]
         T = states.shape[0] - 1
         state = states[:T].reshape(-1, states.shape[-1])      # a view: the first T slabs of a contiguous buffer
