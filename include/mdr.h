@@ -320,7 +320,9 @@ int mdr_env_step(mdr_env_t *env, uint8_t *actions, int action_source, void *stre
  * main-deploy.py:99-104 (one launch per step; see mdr_env_rollout_fused for the in-register form).
  * Between the steps of one call `reward`, `obs`, `actions` (of the in-kernel controllers) and `P` are unspecified: the interior
  * steps may leave out outputs that the next step overwrites (unsharded houses, no graph mode, no interpolated base power; the
- * environment variable MDR_ROLLOUT_INTERIOR = 0 | 1 | 2, read once, overrides how much they leave out - 0 = nothing).  After a
+ * environment variable MDR_ROLLOUT_INTERIOR = 0 | 1 | 2, read once, overrides how much they leave out - 0 = nothing, 1 = what sits
+ * behind the env-wide reduction and all but the first MDR_ROLLOUT_INTERIOR_PLANES local obs planes, 2 = all five local planes too;
+ * the environment variable MDR_ROLLOUT_INTERIOR_PLANES = 0 .. 5, read once, overrides that count, 2 as built).  After a
  * successful return the four hold the last step's values, exactly as `nb_steps` calls of mdr_env_step leave them, and so does the
  * state.  After an error return they may be older than the state. */
 int mdr_env_rollout(mdr_env_t *env, uint8_t *actions, int action_source, int32_t nb_steps, void *stream);

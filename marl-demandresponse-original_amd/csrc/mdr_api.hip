@@ -10,13 +10,16 @@
 #include "../../include/mdr_policy.h"
 #include "mdr_kernels.h"
 
-// Depth of the interior steps of mdr_env_rollout (StepArgs.interior_dead) when MDR_ROLLOUT_INTERIOR is not set in the environment.
-// Chosen by measurement (profiles/r07_README.md): depth 2 is the faster one (30.6 against 42.4 us per step at 4096 x 1024), but at 512
-// cache-resident envs it runs past the 1.25 that tests/test_gpu_bench.py allows bench.py's roofline.frac, which is computed from a
-// fixed byte count; depth 1 stays below it with room to spare.
-#ifndef MDR_ROLLOUT_INTERIOR_DEAD
-#define MDR_ROLLOUT_INTERIOR_DEAD 1
+// How many of the five local obs planes the interior steps of mdr_env_rollout still store (StepArgs.interior_local) when
+// MDR_ROLLOUT_INTERIOR_PLANES is not set in the environment; 5 = all of them, 0 = none.  Chosen by measurement
+// (profiles/r08_README.md): every plane less is 4 B per house-step less (42.4 us per step at 5, 30.6 at 0, 4096 x 1024), but at 512
+// cache-resident envs bench.py's roofline.frac, computed from a fixed byte count, rises with every byte not moved, and
+// tests/test_gpu_bench.py allows it 1.25: the default is the smallest count that stays at or below 1.25 / 1.05 = 1.1905 there in
+// each of five runs - 2 (35.3 us per step; 1.184 at most, where 1 prints up to 1.244).
+#ifndef MDR_ROLLOUT_INTERIOR_PLANES
+#define MDR_ROLLOUT_INTERIOR_PLANES 2
 #endif
+static_assert(MDR_ROLLOUT_INTERIOR_PLANES >= 0 && MDR_ROLLOUT_INTERIOR_PLANES <= 5, "there are five local obs planes");
 
 struct mdr_env {
   mdr_config_t cfg;
@@ -660,8 +663,9 @@ int mdr_env_refresh_obs(mdr_env_t* env, void* stream) {
   return MDR_OK;
 }
 
-// mdr_env_step; `interior_dead` (StepArgs.interior_dead) is non-zero only for the interior steps of mdr_env_rollout
-static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream, int interior_dead) {
+// mdr_env_step; `interior_dead` (StepArgs.interior_dead) is non-zero only for the interior steps of mdr_env_rollout, which then
+// store `interior_local` of the five local obs planes (StepArgs.interior_local)
+static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream, int interior_dead, int interior_local) {
   if (!env) return MDR_ERR_INVALID;
   if (env->cfg.nb_houses_total != env->cfg.nb_houses)
     return fail(env, MDR_ERR_INVALID, "houses are sharded: use mdr_env_step_begin / all-reduce / mdr_env_step_end");
@@ -670,6 +674,7 @@ static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* s
   int rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);
   if (rc != MDR_OK) return rc;
   a.interior_dead = interior_dead;
+  a.interior_local = interior_local;
   const bool graph = graph_mode(env);
   if (graph) {
     rc = sync_cursor(env, (hipStream_t)stream);
@@ -696,7 +701,7 @@ static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* s
 }
 
 int mdr_env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream) {
-  return env_step(env, actions, action_source, stream, 0);
+  return env_step(env, actions, action_source, stream, 0, 5);
 }
 
 int mdr_env_pack(mdr_env_t* env, int32_t env_index, double* out, void* stream) {
@@ -805,18 +810,23 @@ int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t
     return rollout_split(env, actions, action_source, nb_steps, (hipStream_t)stream);
   // Interior steps: between the steps of this loop nothing can look at reward / obs / actions / P, and the next launch on the stream
   // overwrites every one of them - so steps 0 .. nb_steps - 2 run the interior form of k_step_fused / k_step_group, which stores none
-  // of them (depth 1: the outputs behind the env-wide reduction; depth 2: the local obs planes too), and the last step is a full
-  // one.  Not where something does look at a boundary: sharded houses and graph mode never get here with a depth, interpolated base
-  // power patches the signal plane and reads P at its updates.  Other step forms ignore the depth (launch_step).
+  // of the outputs behind the env-wide reduction and only the first `planes` of the five local obs planes, and the last step is a
+  // full one.  Not where something does look at a boundary: sharded houses and graph mode never get here with a depth, interpolated
+  // base power patches the signal plane and reads P at its updates.  Other step forms ignore the depth (launch_step).
   static const int interior_depth = [] {
-    const char* t = getenv("MDR_ROLLOUT_INTERIOR");   // 0 | 1 | 2: the tests reach every depth in one build with it; profiles/r07_README.md
-    return (t && t[0] >= '0' && t[0] <= '2' && t[1] == '\0') ? t[0] - '0' : MDR_ROLLOUT_INTERIOR_DEAD;
+    const char* t = getenv("MDR_ROLLOUT_INTERIOR");   // 0 = full steps | 1 = the configured plane count | 2 = no local plane; the tests reach all three in one build
+    return (t && t[0] >= '0' && t[0] <= '2' && t[1] == '\0') ? t[0] - '0' : 1;
+  }();
+  static const int interior_planes = [] {
+    const char* t = getenv("MDR_ROLLOUT_INTERIOR_PLANES");   // 0 .. 5, at depth 1: every count from one build; profiles/r08_README.md
+    return (t && t[0] >= '0' && t[0] <= '5' && t[1] == '\0') ? t[0] - '0' : MDR_ROLLOUT_INTERIOR_PLANES;
   }();
   const bool interior_ok = env->bound && !sharded(env) && !graph_mode(env) && !interp_mode(env) &&
                            (env->plan.kind == mdr::STEP_FUSED || env->plan.kind == mdr::STEP_GROUP);
   const int depth = interior_ok ? interior_depth : 0;
+  const int planes = depth == 2 ? 0 : interior_planes;
   for (int32_t i = 0; i < nb_steps; ++i) {
-    int rc = env_step(env, actions, action_source, stream, i + 1 < nb_steps ? depth : 0);
+    int rc = env_step(env, actions, action_source, stream, (depth != 0 && i + 1 < nb_steps) ? 1 : 0, planes);
     if (rc != MDR_OK) return rc;
   }
   return MDR_OK;

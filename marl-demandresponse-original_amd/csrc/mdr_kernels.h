@@ -109,9 +109,11 @@ struct StepArgs {
   const uint32_t* hvac_dict;
   // Internal (mdr_env_rollout's interior steps; launch_step picks the instantiation, k_step_fused / k_step_group only - every other
   // step form ignores it and runs a full step): which outputs of THIS step nobody will read because the next launch overwrites them.
-  // 0 = a full step; 1 = no reward, no obs planes 5 / 6, no actions of the in-kernel controllers, no P (and with them no reduction);
-  // 2 = 1 and no local obs planes either.  The state advance is the same at every depth.
+  // interior_dead: 0 = a full step; 1 = no reward, no obs planes 5 / 6, no actions of the in-kernel controllers, no P (and with them
+  // no reduction).  interior_local (read only where interior_dead is 1): how many of the five local obs planes the step still
+  // stores, planes 0 .. interior_local - 1; 5 = all, 0 = none.  The state advance is the same whatever the two hold.
   int interior_dead;
+  int interior_local;
 };
 
 // utils.normStateDict for all houses (k_obs_vector)

@@ -794,12 +794,13 @@ hipError_t launch_cursor_set(int32_t* cursor, int32_t row, int32_t k, hipStream_
 // temp_penalty / reward_value / signal_term, load_vec / store_vec / store_out, step_vec, store_obs_local, store_reward_power:
 // mdr_step_common.h (shared with mdr_persist.hip)
 
-// The interior form (StepArgs.interior_dead, DEAD = 1 | 2): a step inside mdr_env_rollout whose outputs the next launch overwrites
+// The interior form (StepArgs.interior_dead, DEAD = 1): a step inside mdr_env_rollout whose outputs the next launch overwrites
 // before anybody can read them.  Everything behind the env-wide reduction exists for those outputs alone - reward, obs planes 5 / 6,
-// P[e] - so it goes together with the reduction, its barrier and its LDS; the in-kernel controllers' `actions` go too, and at
-// DEAD = 2 the five local planes as well.  What is left is step_vec's loads, house_step and the state stores: the same statements
-// as the full step's, so the state is the same bit for bit.  C3: 80 -> 67 -> 47 B per house-step.
-template <int VEC, int TILES, int THREADS, int DEAD>
+// P[e] - so it goes together with the reduction, its barrier and its LDS; the in-kernel controllers' `actions` go too, and of the
+// five local planes only the first LOCAL (StepArgs.interior_local) are stored.  What is left is step_vec's loads, house_step and
+// the state stores: the same statements as the full step's, so the state is the same bit for bit - `lockout` stays loaded at every
+// LOCAL, the HVAC's lockout logic in house_step reads it.  C3: 80 B per house-step -> 47 + 4 LOCAL.
+template <int VEC, int TILES, int THREADS, int LOCAL>
 __device__ __forceinline__ void step_fused_interior(StepArgs& a) {
   rebase(a);
   const int e = blockIdx.x;
@@ -812,17 +813,18 @@ __device__ __forceinline__ void step_fused_interior(StepArgs& a) {
     if (h < a.N) {
       HouseOut o[VEC];
       int lockout[VEC];
-      step_vec<VEC, DEAD>(a, base + h, od_old, solar, o, lockout);
-      if constexpr (DEAD == 1) store_obs_local<VEC>(a, base + h, o, lockout);
+      step_vec<VEC, 1>(a, base + h, od_old, solar, o, lockout);
+      store_obs_local<VEC, LOCAL>(a, base + h, o, lockout);
     }
   }
   cursor_done(a);
 }
 
-template <int VEC, int TILES, int THREADS, int DEAD = 0>
+template <int VEC, int TILES, int THREADS, int DEAD = 0, int LOCAL = 5>
 __global__ __launch_bounds__(THREADS) void k_step_fused(StepArgs a) {
+  static_assert(DEAD == 0 ? LOCAL == 5 : DEAD == 1, "a full step stores all five local planes");
   if constexpr (DEAD != 0) {
-    step_fused_interior<VEC, TILES, THREADS, DEAD>(a);
+    step_fused_interior<VEC, TILES, THREADS, LOCAL>(a);
     return;
   }
   rebase(a);
@@ -1065,9 +1067,11 @@ __global__ __launch_bounds__(THREADS) void k_rollout_fused(StepArgs a, RolloutAr
 // ---- (2) small envs: GROUP lanes per env, VEC consecutive houses per lane (N <= GROUP * VEC, N % VEC == 0), several
 // envs per wavefront; reductions by sub-wave DPP exchanges only (no LDS, no barrier).  VEC = 4 / 2 keeps the accesses
 // 16 / 8 bytes wide for the agent counts the reference actually trains with (cli.py: 20 and 50 houses).
-// DEAD = 1 | 2: the interior form, as k_step_fused's (step_fused_interior) - no DPP reduction, no signal rows, no post-reduction stores.
-template <int GROUP, int VEC, int DEAD = 0>
+// DEAD = 1: the interior form, as k_step_fused's (step_fused_interior) - no DPP reduction, no signal rows, no post-reduction stores,
+// the first LOCAL local planes only.
+template <int GROUP, int VEC, int DEAD = 0, int LOCAL = 5>
 __global__ __launch_bounds__(256) void k_step_group(StepArgs a) {
+  static_assert(DEAD == 0 ? LOCAL == 5 : DEAD == 1, "a full step stores all five local planes");
   rebase(a);
   const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) / GROUP;
   const int lane = threadIdx.x % GROUP;
@@ -1079,8 +1083,8 @@ __global__ __launch_bounds__(256) void k_step_group(StepArgs a) {
   int lockout[VEC];
   if constexpr (DEAD != 0) {
     if (active) {
-      step_vec<VEC, DEAD>(a, i, a.od_old[e], a.solar_new[e], o, lockout);
-      if constexpr (DEAD == 1) store_obs_local<VEC>(a, i, o, lockout);
+      step_vec<VEC, 1>(a, i, a.od_old[e], a.solar_new[e], o, lockout);
+      store_obs_local<VEC, LOCAL>(a, i, o, lockout);
     }
     cursor_done(a);
     return;
@@ -2460,23 +2464,30 @@ hipError_t launch_tables(const TableArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int VEC, int THREADS, int DEAD>
+template <int VEC, int THREADS, int DEAD, int LOCAL>
 static void launch_fused_tiles_dead(const StepArgs& a, int tiles, hipStream_t s) {
   const dim3 g((unsigned)a.E), b(THREADS);
   switch (tiles) {
-    case 1: hipLaunchKernelGGL((k_step_fused<VEC, 1, THREADS, DEAD>), g, b, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((k_step_fused<VEC, 2, THREADS, DEAD>), g, b, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((k_step_fused<VEC, 3, THREADS, DEAD>), g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_step_fused<VEC, 4, THREADS, DEAD>), g, b, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((k_step_fused<VEC, 1, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((k_step_fused<VEC, 2, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((k_step_fused<VEC, 3, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_step_fused<VEC, 4, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
   }
 }
 
-// StepArgs.interior_dead picks the instantiation: 0 = the full step, 1 | 2 = the interior forms (mdr_env_rollout)
+// StepArgs.interior_dead / interior_local pick the instantiation: the full step, or the interior form (mdr_env_rollout) that still
+// stores the first interior_local local planes.  interior_dead is 0 for every caller but mdr_env_rollout.
 template <int VEC, int THREADS>
 static void launch_fused_tiles(const StepArgs& a, int tiles, hipStream_t s) {
-  if (a.interior_dead == 1) launch_fused_tiles_dead<VEC, THREADS, 1>(a, tiles, s);
-  else if (a.interior_dead == 2) launch_fused_tiles_dead<VEC, THREADS, 2>(a, tiles, s);
-  else launch_fused_tiles_dead<VEC, THREADS, 0>(a, tiles, s);
+  if (a.interior_dead == 0) return launch_fused_tiles_dead<VEC, THREADS, 0, 5>(a, tiles, s);
+  switch (a.interior_local) {
+    case 0: launch_fused_tiles_dead<VEC, THREADS, 1, 0>(a, tiles, s); break;
+    case 1: launch_fused_tiles_dead<VEC, THREADS, 1, 1>(a, tiles, s); break;
+    case 2: launch_fused_tiles_dead<VEC, THREADS, 1, 2>(a, tiles, s); break;
+    case 3: launch_fused_tiles_dead<VEC, THREADS, 1, 3>(a, tiles, s); break;
+    case 4: launch_fused_tiles_dead<VEC, THREADS, 1, 4>(a, tiles, s); break;
+    default: launch_fused_tiles_dead<VEC, THREADS, 1, 5>(a, tiles, s); break;
+  }
 }
 
 static int pow2_at_least(int n) {
@@ -2747,14 +2758,18 @@ hipError_t launch_step(const StepArgs& args, const StepPlan& p, hipStream_t s) {
   if (p.kind == STEP_GROUP) {
     const int64_t lanes = (int64_t)a.E * p.threads;
     const dim3 g((unsigned)((lanes + 255) / 256)), b(256);
-#define MDR_GROUP_DEAD(G, D)                                                           \
-  if (p.vec == 4) hipLaunchKernelGGL((k_step_group<G, 4, D>), g, b, 0, s, a);          \
-  else if (p.vec == 2) hipLaunchKernelGGL((k_step_group<G, 2, D>), g, b, 0, s, a);     \
-  else hipLaunchKernelGGL((k_step_group<G, 1, D>), g, b, 0, s, a);
+#define MDR_GROUP_DEAD(G, D, L)                                                        \
+  if (p.vec == 4) hipLaunchKernelGGL((k_step_group<G, 4, D, L>), g, b, 0, s, a);       \
+  else if (p.vec == 2) hipLaunchKernelGGL((k_step_group<G, 2, D, L>), g, b, 0, s, a);  \
+  else hipLaunchKernelGGL((k_step_group<G, 1, D, L>), g, b, 0, s, a);
 #define MDR_GROUP(G)                                                                   \
-  if (a.interior_dead == 1) { MDR_GROUP_DEAD(G, 1) }                                   \
-  else if (a.interior_dead == 2) { MDR_GROUP_DEAD(G, 2) }                              \
-  else { MDR_GROUP_DEAD(G, 0) }                                                        \
+  if (a.interior_dead == 0) { MDR_GROUP_DEAD(G, 0, 5) }                                \
+  else if (a.interior_local == 0) { MDR_GROUP_DEAD(G, 1, 0) }                          \
+  else if (a.interior_local == 1) { MDR_GROUP_DEAD(G, 1, 1) }                          \
+  else if (a.interior_local == 2) { MDR_GROUP_DEAD(G, 1, 2) }                          \
+  else if (a.interior_local == 3) { MDR_GROUP_DEAD(G, 1, 3) }                          \
+  else if (a.interior_local == 4) { MDR_GROUP_DEAD(G, 1, 4) }                          \
+  else { MDR_GROUP_DEAD(G, 1, 5) }                                                     \
   break;
     switch (p.threads) {
       case 1: MDR_GROUP(1)

@@ -404,23 +404,28 @@ __device__ __forceinline__ void step_vec(const StepArgs& a, int64_t i, float od_
 }
 
 // The five observation columns that do not depend on the env-wide reductions.
-template <int VEC>
+// LOCAL (the interior steps of mdr_env_rollout, StepArgs.interior_local): planes 0 .. LOCAL - 1 are stored, the others are dead - the
+// next launch overwrites them unread - and leave no arithmetic behind: plane 4 goes first (the convert and the divide by `lockout`),
+// then 3 and 2 (the selects on `flags`), then 1 and 0.  LOCAL = 5, every full step: all five.
+template <int VEC, int LOCAL = 5>
 __device__ __forceinline__ void store_obs_local(const StepArgs& a, int64_t i, const HouseOut* o, const int* lockout) {
+  static_assert(LOCAL >= 0 && LOCAL <= 5, "five local planes");
+  if constexpr (LOCAL == 0) return;
   if (a.obs == nullptr) return;   // mdr_buffers_t.obs == NULL: nobody reads the planes (observe -> act rollouts): 28 B per house-step not written
-  float c0[VEC], c1[VEC], c2[VEC], c3[VEC], c4[VEC];
+  [[maybe_unused]] float c0[VEC], c1[VEC], c2[VEC], c3[VEC], c4[VEC];
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
-    c0[v] = (o[v].Ta + a.obs_tshift) * 0.2f;  // (house_temp - 20) / 5, utils.py:800-802
-    c1[v] = (o[v].Tm + a.obs_tshift) * 0.2f;
-    c2[v] = (o[v].flags & 1u) ? 1.0f : 0.0f;  // utils.py:823
-    c3[v] = (o[v].flags & 2u) ? 1.0f : 0.0f;  // utils.py:824
-    c4[v] = (float)o[v].sso / (float)lockout[v];  // utils.py:826-828
+    if constexpr (LOCAL > 0) c0[v] = (o[v].Ta + a.obs_tshift) * 0.2f;  // (house_temp - 20) / 5, utils.py:800-802
+    if constexpr (LOCAL > 1) c1[v] = (o[v].Tm + a.obs_tshift) * 0.2f;
+    if constexpr (LOCAL > 2) c2[v] = (o[v].flags & 1u) ? 1.0f : 0.0f;  // utils.py:823
+    if constexpr (LOCAL > 3) c3[v] = (o[v].flags & 2u) ? 1.0f : 0.0f;  // utils.py:824
+    if constexpr (LOCAL > 4) c4[v] = (float)o[v].sso / (float)lockout[v];  // utils.py:826-828
   }
-  store_out<VEC>(a.obs + 0 * a.plane, i, c0);
-  store_out<VEC>(a.obs + 1 * a.plane, i, c1);
-  store_out<VEC>(a.obs + 2 * a.plane, i, c2);
-  store_out<VEC>(a.obs + 3 * a.plane, i, c3);
-  store_out<VEC>(a.obs + 4 * a.plane, i, c4);
+  if constexpr (LOCAL > 0) store_out<VEC>(a.obs + 0 * a.plane, i, c0);
+  if constexpr (LOCAL > 1) store_out<VEC>(a.obs + 1 * a.plane, i, c1);
+  if constexpr (LOCAL > 2) store_out<VEC>(a.obs + 2 * a.plane, i, c2);
+  if constexpr (LOCAL > 3) store_out<VEC>(a.obs + 3 * a.plane, i, c3);
+  if constexpr (LOCAL > 4) store_out<VEC>(a.obs + 4 * a.plane, i, c4);
 }
 
 template <int VEC>
