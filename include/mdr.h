@@ -22,7 +22,8 @@
  * ABI 5: mdr_buffers_t ends in the optional `param_uniform` word (per-house parameter columns that hold one value for every
  * house are not streamed by the step kernels); new entry point mdr_env_params_changed.  Added under ABI 5 (a new function, nothing
  * existing changes): mdr_env_bind_hvac_code - the (Q_hvac, P_max) pair of a house as one byte into a 16-entry dictionary.
- * Likewise mdr_env_tarmac_actor_sample (mdr_policy.h): the TarMAC actor fed from the env's compact state.
+ * Likewise mdr_env_tarmac_actor_sample (mdr_policy.h): the TarMAC actor fed from the env's compact state; and
+ * mdr_env_bind_thermal_pack with its query mdr_env_rollout_plan: the five thermal columns as one 16-byte record per house.
  */
 #ifndef MDR_H
 #define MDR_H
@@ -267,8 +268,10 @@ int mdr_env_load_episode(mdr_env_t *env, const mdr_episode_t *episode, uint64_t 
                          void *stream);
 /* The caller wrote `target`, `deadband` or `lockout` of the bound buffers itself: re-derives mdr_buffers_t.param_uniform from the
  * arrays (one pass over the three columns on `stream`).  A caller that wrote `Q_hvac` or `P_max` calls it too: with a code bound
- * (mdr_env_bind_hvac_code) it rebuilds the dictionary and the class plane from those two arrays (one more pass).  Nothing to do,
- * MDR_OK, when neither the word nor the code is bound. */
+ * (mdr_env_bind_hvac_code) it rebuilds the dictionary and the class plane from those two arrays (one more pass).  And a caller that
+ * wrote `k01`, `s0`, `k10`, `s1` or `inv_Ua` calls it before the next step: with a thermal pack bound (mdr_env_bind_thermal_pack)
+ * it rebuilds the descriptor and the records from those five arrays (two more passes).  Nothing to do, MDR_OK, when none of the
+ * three is bound. */
 int mdr_env_params_changed(mdr_env_t *env, void *stream);
 /* Optional: dictionary-codes the two HVAC power columns for the single-step kernels (mdr_env_step, the records pair,
  * mdr_env_step_mailbox).  `Q_hvac` and `P_max` derive from (capacity, COP, latent), and capacity is drawn from at most
@@ -284,6 +287,36 @@ int mdr_env_params_changed(mdr_env_t *env, void *stream);
  * The arrays stay fully written (every other kernel reads them).  NULL for both turns the coding off; mdr_env_bind drops the
  * binding (bind the code again after it; the contents of the two buffers stay valid across a re-bind of the same arrays). */
 int mdr_env_bind_hvac_code(mdr_env_t *env, uint8_t *hvac_class, uint32_t *hvac_dict);
+/* Optional: the five thermal columns k01, s0, k10, s1, inv_Ua - constant for an episode, 20 of the bytes a step streams per house -
+ * as ONE lossless 16-byte record per house, for the interior steps of mdr_env_rollout on batches too large for the caches (below).
+ * Each column has one sign and a narrow range, so its float bit patterns are integers in a narrow interval: a value is stored as
+ * bits - base_c, base_c the column's smallest pattern, in a field of MDR_THERMAL_BITS_* bits; the five fields are laid end to end,
+ * k01 first, from bit 0 of a 128-bit little-endian record.
+ *   pack  uint32 [4][nb_envs * nb_houses], 16-byte aligned: plane j holds dword j of every house's record
+ *   desc  uint32 [MDR_THERMAL_DESC_WORDS], 16-byte aligned: [MDR_THERMAL_DESC_PACKED] 1 = `pack` is valid, 0 = not packed;
+ *         [MDR_THERMAL_DESC_BASE + c] the base of column c (order above); the words behind are the detection kernels' scratch.
+ *         Hand it over zeroed.
+ * The library fills both on the caller's stream where it fills mdr_buffers_t.param_uniform: mdr_env_reset, mdr_env_load_episode and
+ * mdr_env_params_changed - one min / max reduction over the five columns, whose last workgroup decides, and one pack pass.  "Not
+ * packed" (the kernels then stream the five columns): a column with both signs, with a NaN, or with max - min beyond its field.  No
+ * host code reads `desc`.  With a valid pack the packed interior steps do NOT read the five columns: a caller that writes one of
+ * them itself must call mdr_env_params_changed before the next step.  The arrays stay fully written (every other kernel reads
+ * them).  NULL for both turns the pack off; mdr_env_bind drops the binding (bind again after it).
+ * Which launches read it: mdr_env_rollout's interior steps that store no local obs plane, when nb_envs * nb_houses is at or above
+ * MDR_ROLLOUT_STREAM_HOUSES (environment, read once; default 1 << 20; 0 = every batch) and MDR_THERMAL_PACK (environment, read
+ * once) is not 0.  mdr_env_rollout_plan reports the choice. */
+#define MDR_THERMAL_BITS_K01 25
+#define MDR_THERMAL_BITS_S0 25
+#define MDR_THERMAL_BITS_K10 25
+#define MDR_THERMAL_BITS_S1 28
+#define MDR_THERMAL_BITS_INV_UA 25
+#define MDR_THERMAL_DESC_PACKED 0
+#define MDR_THERMAL_DESC_BASE 1
+#define MDR_THERMAL_DESC_WORDS 32
+int mdr_env_bind_thermal_pack(mdr_env_t *env, uint32_t *pack, uint32_t *desc);
+/* What the interior steps of the next mdr_env_rollout on this handle run: *planes = how many of the five local obs planes they
+ * store (-1: the rollout runs full steps only), *packed = 1 when they read the thermal pack.  Either pointer may be NULL. */
+int mdr_env_rollout_plan(const mdr_env_t *env, int32_t *planes, int32_t *packed);
 /* Optional: replace ClusterHouses.compute_OD_temp (env 1057-1081, incl. its random.gauss draw 1079) by a table, double [rows][E] deg C (row = time index);
  * NULL restores the model.  Takes effect at the next mdr_env_begin_episode / table refill; mdr_env_reset (a freshly sampled
  * episode) drops it. */

@@ -46,7 +46,8 @@ class BatchedDemandResponseEnv:
                  house_shard: Optional[Tuple[int, int]] = None, process_group=None,
                  stagger_bytes: int = 2304, interp_grid=None, regenerate_missing_grid: bool = True,
                  graph_mode: bool = False, exchange_always: bool = False, partial_records: Optional[int] = None,
-                 obs_planes: bool = True, prefetch_tables: bool = True, exchange=None, uniform_params: bool = True, hvac_code: bool = True):
+                 obs_planes: bool = True, prefetch_tables: bool = True, exchange=None, uniform_params: bool = True, hvac_code: bool = True,
+                 thermal_pack: bool = True):
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedDemandResponseEnv needs a ROCm device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
@@ -92,6 +93,11 @@ class BatchedDemandResponseEnv:
         # house instead of the Q_hvac and P_max columns whenever the batch holds at most 16 distinct (Q_hvac, P_max) pairs (found on
         # the device at reset / load_episode / params_changed()); False binds nothing: the two columns are streamed
         self._hvac_code = bool(hvac_code)
+        # thermal_pack: bind a 16-byte record per house and its descriptor (mdr_env_bind_thermal_pack) - the interior steps of rollout()
+        # on a batch too large for the caches (rollout_plan()) then read 16 B per house instead of the five thermal columns' 20
+        # whenever every column has one sign, no NaN and a range that fits its field (found on the device at reset / load_episode /
+        # params_changed()); False binds nothing: the five columns are streamed
+        self._thermal_pack = bool(thermal_pack)
         self._handle = C.c_void_p()
         self._cfg = self._make_config()
         rc = self._lib.mdr_env_create(C.byref(self._cfg), C.byref(self._handle))
@@ -192,6 +198,9 @@ class BatchedDemandResponseEnv:
         if self._hvac_code:      # derived from Q_hvac / P_max, never part of a snapshot: outside the slab, whose layout stays what it was
             self.t["hvac_class"] = torch.zeros((self.nb_envs, self.nb_houses), dtype=torch.uint8, device=self.device)
             self.t["hvac_dict"] = torch.zeros((nat.MDR_HVAC_DICT_WORDS,), dtype=torch.int32, device=self.device)      # count 0: not coded yet
+        if self._thermal_pack:      # derived from k01 / s0 / k10 / s1 / inv_Ua, likewise outside the slab: 16 B per house
+            self.t["thermal_pack"] = torch.zeros((4, self.nb_envs, self.nb_houses), dtype=torch.int32, device=self.device)
+            self.t["thermal_desc"] = torch.zeros((nat.MDR_THERMAL_DESC_WORDS,), dtype=torch.int32, device=self.device)      # word 0 == 0: not packed yet
 
     def _grow_partials(self, records: int) -> None:
         """Raise the record stride of `partials` to the group's maximum (a fresh zero-filled scratch buffer, re-bound)."""
@@ -220,6 +229,16 @@ class BatchedDemandResponseEnv:
         if self._hvac_code:      # mdr_env_bind drops the code; the two buffers' contents stay valid over a re-bind of the same arrays
             rc = self._lib.mdr_env_bind_hvac_code(self._handle, self.t["hvac_class"].data_ptr(), self.t["hvac_dict"].data_ptr())
             nat.check(self._lib, self._handle, rc, "mdr_env_bind_hvac_code")
+        if self._thermal_pack:   # likewise
+            rc = self._lib.mdr_env_bind_thermal_pack(self._handle, self.t["thermal_pack"].data_ptr(), self.t["thermal_desc"].data_ptr())
+            nat.check(self._lib, self._handle, rc, "mdr_env_bind_thermal_pack")
+
+    def rollout_plan(self) -> Tuple[int, bool]:
+        """What the interior steps of the next ``rollout()`` run: (local obs planes they still store, or -1 when every step is a full
+        one; whether they read the thermal pack) - mdr_env_rollout_plan."""
+        planes, packed = C.c_int32(), C.c_int32()
+        nat.check(self._lib, self._handle, self._lib.mdr_env_rollout_plan(self._handle, C.byref(planes), C.byref(packed)), "mdr_env_rollout_plan")
+        return int(planes.value), bool(packed.value)
 
     def set_obs_planes(self, on: bool) -> None:
         """Switch the seven per-step observation planes on or off (a re-bind: mdr_buffers_t.obs = NULL skips their 28 B per
@@ -380,7 +399,9 @@ class BatchedDemandResponseEnv:
         """Call after writing ``t['target']``, ``t['deadband']``, ``t['lockout']``, ``t['Q_hvac']`` or ``t['P_max']`` yourself: the
         library reads the first three at reset, at load_episode and here to find the columns that hold one value for every house
         (which the step kernels then do not stream), and with ``hvac_code`` the last two to rebuild the dictionary and the class
-        plane the step kernels read in their place.  One pass over the columns on the current stream; no host sync."""
+        plane the step kernels read in their place.  Likewise after writing ``t['k01']``, ``t['s0']``, ``t['k10']``, ``t['s1']`` or
+        ``t['inv_Ua']`` with ``thermal_pack``: the descriptor and the records are rebuilt from the five columns.  One pass over each
+        group of columns on the current stream; no host sync."""
         with torch.cuda.device(self.device):
             nat.check(self._lib, self._handle, self._lib.mdr_env_params_changed(self._handle, self._stream()), "mdr_env_params_changed")
 
@@ -974,12 +995,13 @@ class BatchedDemandResponseEnv:
         rc = self._lib.mdr_env_set_cursor(self._handle, C.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF),
                                           C.c_uint32(max(self.episode, 0) & 0xFFFFFFFF), sd["k"], sd["j0"])
         nat.check(self._lib, self._handle, rc, "mdr_env_set_cursor")
-        self.params_changed()      # the slab brought its parameter arrays: the uniformity word and the HVAC code are derived from them again
+        self.params_changed()      # the slab brought its parameter arrays: the uniformity word, the HVAC code and the thermal pack are derived from them again
 
     def __deepcopy__(self, memo):
         other = BatchedDemandResponseEnv(copy.deepcopy(self.config, memo), nb_envs=self.nb_envs, device=self.device,
                                          seed=self.seed, test=self.test, table_steps=self.table_steps, obs_planes=self._obs_planes_alloc,
                                          prefetch_tables=self._prefetch_tables, uniform_params=self._uniform_params, hvac_code=self._hvac_code,
+                                         thermal_pack=self._thermal_pack,
                                          env_offset=self.env_offset,
                                          house_shard=(self.house_offset, self.nb_houses) if self.sharded else None,
                                          exchange_always=self._exchange_always, partial_records=self._partial_records,

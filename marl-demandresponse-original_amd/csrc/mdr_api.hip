@@ -11,7 +11,8 @@
 #include "mdr_kernels.h"
 
 // How many of the five local obs planes the interior steps of mdr_env_rollout still store (StepArgs.interior_local) when
-// MDR_ROLLOUT_INTERIOR_PLANES is not set in the environment; 5 = all of them, 0 = none.  Chosen by measurement
+// MDR_ROLLOUT_INTERIOR_PLANES is not set in the environment and the batch is below MDR_ROLLOUT_STREAM_HOUSES (interior_plan; at or
+// above it the count is 0); 5 = all of them, 0 = none.  Chosen by measurement
 // (profiles/r08_README.md): every plane less is 4 B per house-step less (42.4 us per step at 5, 30.6 at 0, 4096 x 1024), but at 512
 // cache-resident envs bench.py's roofline.frac, computed from a fixed byte count, rises with every byte not moved, and
 // tests/test_gpu_bench.py allows it 1.25: the default is the smallest count that stays at or below 1.25 / 1.05 = 1.1905 there in
@@ -27,6 +28,8 @@ struct mdr_env {
   bool bound = false;
   uint8_t* hvac_class = nullptr;   // mdr_env_bind_hvac_code; mdr_env_bind drops both
   uint32_t* hvac_dict = nullptr;
+  uint32_t* thermal_pack = nullptr;   // mdr_env_bind_thermal_pack; mdr_env_bind drops both
+  uint32_t* thermal_desc = nullptr;
   bool has_episode = false;   // per-house parameters present
   bool has_tables = false;    // begin_episode done
   bool split_pending = false; // step_begin issued, step_end outstanding
@@ -141,12 +144,15 @@ std::string check_buffers(const mdr_buffers_t& b, bool need_partials) {
   return "";
 }
 
-// What the step kernels take from a summary of the parameter arrays instead of the arrays: the uniformity word and the HVAC code
+// What the step kernels take from a summary of the parameter arrays instead of the arrays: the uniformity word, the HVAC code and
+// the thermal pack
 hipError_t detect_params(const mdr_env* env, hipStream_t s) {
   const int64_t n = (int64_t)env->cfg.nb_envs * env->cfg.nb_houses;
-  const hipError_t e = mdr::launch_detect_uniform(env->buf, n, s);
+  hipError_t e = mdr::launch_detect_uniform(env->buf, n, s);
   if (e != hipSuccess) return e;
-  return mdr::launch_hvac_code(env->buf, n, env->hvac_class, env->hvac_dict, s);
+  e = mdr::launch_hvac_code(env->buf, n, env->hvac_class, env->hvac_dict, s);
+  if (e != hipSuccess) return e;
+  return mdr::launch_thermal_pack(env->buf, n, env->thermal_pack, env->thermal_desc, s);
 }
 
 mdr::EpisodeArgs episode_args(const mdr_env& env) {
@@ -400,6 +406,7 @@ int step_args(mdr_env* env, uint8_t* actions, int action_source, hipStream_t s, 
   a.target = b.target; a.deadband = b.deadband; a.lockout = b.lockout;
   a.param_uniform = b.param_uniform;
   a.hvac_class = env->hvac_class; a.hvac_dict = env->hvac_dict;
+  a.thermal_pack = env->thermal_pack; a.thermal_desc = env->thermal_desc;
   a.actions = actions;
   a.reward = b.reward; a.obs = b.obs;
   a.P = b.P; a.tot_sum = b.tot_sum; a.tot_max = b.tot_max; a.partials = b.partials;
@@ -516,6 +523,8 @@ int mdr_env_bind(mdr_env_t* env, const mdr_buffers_t* buffers) {
   env->buf = *buffers;
   env->hvac_class = nullptr;   // the code belongs to the arrays it was bound over: mdr_env_bind_hvac_code again
   env->hvac_dict = nullptr;
+  env->thermal_pack = nullptr;   // likewise: mdr_env_bind_thermal_pack again
+  env->thermal_desc = nullptr;
   env->tabs[0] = t0;
   env->tabs[1] = t1;
   env->has_alt = all2;
@@ -546,7 +555,7 @@ int mdr_env_reset(mdr_env_t* env, uint64_t seed, uint32_t episode, void* stream)
   hipError_t e = mdr::launch_sample(episode_args(*env), (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "reset");
   e = detect_params(env, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(env, e, "reset: detect_uniform / hvac_code");
+  if (e != hipSuccess) return hip_fail(env, e, "reset: detect_uniform / hvac_code / thermal_pack");
   env->has_episode = true;
   env->k = 0;
   return MDR_OK;
@@ -569,7 +578,7 @@ int mdr_env_load_episode(mdr_env_t* env, const mdr_episode_t* ep, uint64_t seed,
   hipError_t e = mdr::launch_load(episode_args(*env), *ep, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(env, e, "load_episode");
   e = detect_params(env, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(env, e, "load_episode: detect_uniform / hvac_code");
+  if (e != hipSuccess) return hip_fail(env, e, "load_episode: detect_uniform / hvac_code / thermal_pack");
   env->has_episode = true;
   env->k = 0;
   return MDR_OK;
@@ -591,6 +600,16 @@ int mdr_env_bind_hvac_code(mdr_env_t* env, uint8_t* hvac_class, uint32_t* hvac_d
   if (((uintptr_t)hvac_dict & 127u) != 0) return fail(env, MDR_ERR_INVALID, "hvac_dict must be 128-byte aligned");
   env->hvac_class = hvac_class;
   env->hvac_dict = hvac_dict;
+  return MDR_OK;
+}
+
+int mdr_env_bind_thermal_pack(mdr_env_t* env, uint32_t* pack, uint32_t* desc) {
+  if (!env) return MDR_ERR_INVALID;
+  if (!env->bound) return fail(env, MDR_ERR_UNBOUND, "buffers not bound");
+  if ((pack == nullptr) != (desc == nullptr)) return fail(env, MDR_ERR_INVALID, "thermal pack and descriptor go together");
+  if (((uintptr_t)pack & 15u) != 0 || ((uintptr_t)desc & 15u) != 0) return fail(env, MDR_ERR_INVALID, "thermal pack and descriptor must be 16-byte aligned");
+  env->thermal_pack = pack;
+  env->thermal_desc = desc;
   return MDR_OK;
 }
 
@@ -664,8 +683,8 @@ int mdr_env_refresh_obs(mdr_env_t* env, void* stream) {
 }
 
 // mdr_env_step; `interior_dead` (StepArgs.interior_dead) is non-zero only for the interior steps of mdr_env_rollout, which then
-// store `interior_local` of the five local obs planes (StepArgs.interior_local)
-static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream, int interior_dead, int interior_local) {
+// store `interior_local` of the five local obs planes (StepArgs.interior_local) and, with `interior_pack`, read the thermal pack
+static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream, int interior_dead, int interior_local, int interior_pack) {
   if (!env) return MDR_ERR_INVALID;
   if (env->cfg.nb_houses_total != env->cfg.nb_houses)
     return fail(env, MDR_ERR_INVALID, "houses are sharded: use mdr_env_step_begin / all-reduce / mdr_env_step_end");
@@ -675,6 +694,7 @@ static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* s
   if (rc != MDR_OK) return rc;
   a.interior_dead = interior_dead;
   a.interior_local = interior_local;
+  a.interior_pack = interior_pack;
   const bool graph = graph_mode(env);
   if (graph) {
     rc = sync_cursor(env, (hipStream_t)stream);
@@ -701,7 +721,7 @@ static int env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* s
 }
 
 int mdr_env_step(mdr_env_t* env, uint8_t* actions, int action_source, void* stream) {
-  return env_step(env, actions, action_source, stream, 0, 5);
+  return env_step(env, actions, action_source, stream, 0, 5, 0);
 }
 
 int mdr_env_pack(mdr_env_t* env, int32_t env_index, double* out, void* stream) {
@@ -800,6 +820,48 @@ static int rollout_split(mdr_env_t* env, uint8_t* actions, int action_source, in
   return MDR_OK;
 }
 
+// The interior steps of mdr_env_rollout: `planes` of the five local obs planes stored (-1: full steps only), `packed`: the thermal
+// columns read from the pack.  The knobs are read once per process; the batch is the handle's own.
+//   MDR_ROLLOUT_INTERIOR         0 = full steps | 1 = the configured plane count | 2 = no local plane; unset: 1 with the size rule below
+//   MDR_ROLLOUT_INTERIOR_PLANES  0 .. 5, at depth 1: that count at every size; unset: the size rule
+//   MDR_ROLLOUT_STREAM_HOUSES    the size rule's threshold in houses (default 1 << 20; 0 = every batch is a large one)
+//   MDR_THERMAL_PACK             0 = never read the pack
+// The size rule (neither of the first two set): at nb_envs * nb_houses >= threshold the count is 0, below it the compile-time default.
+// Below the threshold the 34 B per house that every step re-reads fit the L2s (1 << 20 houses: 35.7 MB against 32 MiB), the step runs
+// from the caches, and bench.py's roofline.frac - a fixed byte count over the time - is bounded by tests/test_gpu_bench.py there:
+// the r08 count stays.  Above it every line comes from HBM, no test binds, and a dead store costs fabric time like a live one.
+// The pack is read only where the count is 0 AND the batch is at or above the threshold - explicit knobs included.
+struct InteriorPlan { int planes, packed; };
+static InteriorPlan interior_plan(const mdr_env_t* env) {
+  static const int interior_depth = [] {
+    const char* t = getenv("MDR_ROLLOUT_INTERIOR");   // the tests reach all three in one build; -1 = unset
+    return (t && t[0] >= '0' && t[0] <= '2' && t[1] == '\0') ? t[0] - '0' : -1;
+  }();
+  static const int interior_planes = [] {
+    const char* t = getenv("MDR_ROLLOUT_INTERIOR_PLANES");   // every count from one build (profiles/r08_README.md); -1 = unset
+    return (t && t[0] >= '0' && t[0] <= '5' && t[1] == '\0') ? t[0] - '0' : -1;
+  }();
+  static const int64_t stream_houses = [] {
+    const char* t = getenv("MDR_ROLLOUT_STREAM_HOUSES");
+    if (!t || t[0] < '0' || t[0] > '9') return (int64_t)1 << 20;
+    char* end = nullptr;
+    const long long v = strtoll(t, &end, 10);
+    return (end && *end == '\0' && v >= 0) ? (int64_t)v : (int64_t)1 << 20;
+  }();
+  static const bool pack_on = [] { const char* t = getenv("MDR_THERMAL_PACK"); return !(t && t[0] == '0' && t[1] == '\0'); }();
+  // Not where something looks at a step boundary: sharded houses and graph mode, interpolated base power (it patches the signal
+  // plane and reads P at its updates).  Other step forms have no interior instantiation (launch_step).
+  const bool interior_ok = env->bound && !sharded(env) && !graph_mode(env) && !interp_mode(env) &&
+                           (env->plan.kind == mdr::STEP_FUSED || env->plan.kind == mdr::STEP_GROUP);
+  const int depth = interior_ok ? (interior_depth < 0 ? 1 : interior_depth) : 0;
+  if (depth == 0) return InteriorPlan{-1, 0};
+  const bool large = (int64_t)env->cfg.nb_envs * env->cfg.nb_houses >= stream_houses;
+  const bool size_rule = interior_depth < 0 && interior_planes < 0;
+  const int planes = depth == 2 ? 0 : interior_planes >= 0 ? interior_planes : (size_rule && large) ? 0 : MDR_ROLLOUT_INTERIOR_PLANES;
+  const bool packed = planes == 0 && large && pack_on && env->thermal_pack != nullptr && env->thermal_desc != nullptr;
+  return InteriorPlan{planes, packed ? 1 : 0};
+}
+
 int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t nb_steps, void* stream) {
   if (!env) return MDR_ERR_INVALID;
   if (nb_steps < 0) return fail(env, MDR_ERR_INVALID, "nb_steps must be >= 0");
@@ -811,24 +873,21 @@ int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t
   // Interior steps: between the steps of this loop nothing can look at reward / obs / actions / P, and the next launch on the stream
   // overwrites every one of them - so steps 0 .. nb_steps - 2 run the interior form of k_step_fused / k_step_group, which stores none
   // of the outputs behind the env-wide reduction and only the first `planes` of the five local obs planes, and the last step is a
-  // full one.  Not where something does look at a boundary: sharded houses and graph mode never get here with a depth, interpolated
-  // base power patches the signal plane and reads P at its updates.  Other step forms ignore the depth (launch_step).
-  static const int interior_depth = [] {
-    const char* t = getenv("MDR_ROLLOUT_INTERIOR");   // 0 = full steps | 1 = the configured plane count | 2 = no local plane; the tests reach all three in one build
-    return (t && t[0] >= '0' && t[0] <= '2' && t[1] == '\0') ? t[0] - '0' : 1;
-  }();
-  static const int interior_planes = [] {
-    const char* t = getenv("MDR_ROLLOUT_INTERIOR_PLANES");   // 0 .. 5, at depth 1: every count from one build; profiles/r08_README.md
-    return (t && t[0] >= '0' && t[0] <= '5' && t[1] == '\0') ? t[0] - '0' : MDR_ROLLOUT_INTERIOR_PLANES;
-  }();
-  const bool interior_ok = env->bound && !sharded(env) && !graph_mode(env) && !interp_mode(env) &&
-                           (env->plan.kind == mdr::STEP_FUSED || env->plan.kind == mdr::STEP_GROUP);
-  const int depth = interior_ok ? interior_depth : 0;
-  const int planes = depth == 2 ? 0 : interior_planes;
+  // full one (interior_plan).
+  const InteriorPlan ip = interior_plan(env);
   for (int32_t i = 0; i < nb_steps; ++i) {
-    int rc = env_step(env, actions, action_source, stream, (depth != 0 && i + 1 < nb_steps) ? 1 : 0, planes);
+    const bool interior = ip.planes >= 0 && i + 1 < nb_steps;
+    int rc = env_step(env, actions, action_source, stream, interior ? 1 : 0, interior ? ip.planes : 5, interior ? ip.packed : 0);
     if (rc != MDR_OK) return rc;
   }
+  return MDR_OK;
+}
+
+int mdr_env_rollout_plan(const mdr_env_t* env, int32_t* planes, int32_t* packed) {
+  if (!env) return MDR_ERR_INVALID;
+  const InteriorPlan ip = interior_plan(env);
+  if (planes) *planes = ip.planes;
+  if (packed) *packed = ip.packed;
   return MDR_OK;
 }
 

@@ -114,6 +114,12 @@ struct StepArgs {
   // stores, planes 0 .. interior_local - 1; 5 = all, 0 = none.  The state advance is the same whatever the two hold.
   int interior_dead;
   int interior_local;
+  // mdr_env_bind_thermal_pack: interior_pack != 0 (only with interior_dead 1 and interior_local 0, and both pointers set) launches
+  // the PACK instantiation, which takes k01 / s0 / k10 / s1 / inv_Ua from the 16-byte records at thermal_pack (four planes, stride
+  // `plane`) whenever thermal_desc[MDR_THERMAL_DESC_PACKED] != 0, and streams the five columns otherwise.
+  int interior_pack;
+  const uint32_t* thermal_pack;
+  const uint32_t* thermal_desc;
 };
 
 // utils.normStateDict for all houses (k_obs_vector)
@@ -254,6 +260,8 @@ hipError_t launch_load(const EpisodeArgs& a, const mdr_episode_t& ep, hipStream_
 hipError_t launch_detect_uniform(const mdr_buffers_t& b, int64_t n, hipStream_t s);   // b.param_uniform <- which of target / deadband / lockout hold one value in all n houses
 // hvac_dict / hvac_class <- the distinct (Q_hvac, P_max) bit pairs of all n houses and each house's index among them (count 0: more than 16)
 hipError_t launch_hvac_code(const mdr_buffers_t& b, int64_t n, uint8_t* hvac_class, uint32_t* hvac_dict, hipStream_t s);
+// thermal_desc / thermal_pack <- the bases of k01, s0, k10, s1, inv_Ua over all n houses and each house's 16-byte record (desc word 0 == 0: not packed)
+hipError_t launch_thermal_pack(const mdr_buffers_t& b, int64_t n, uint32_t* thermal_pack, uint32_t* thermal_desc, hipStream_t s);
 hipError_t launch_tables(const TableArgs& a, hipStream_t s);
 hipError_t launch_interp_base(const InterpArgs& a, hipStream_t s);
 hipError_t launch_patch_signal_plane(const StepArgs& a, hipStream_t s);   // obs plane 5 <- sig_old row

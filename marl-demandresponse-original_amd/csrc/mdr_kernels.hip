@@ -239,6 +239,116 @@ hipError_t launch_hvac_code(const mdr_buffers_t& b, int64_t n, uint8_t* hvac_cla
   return hipGetLastError();
 }
 
+// mdr_env_bind_thermal_pack.  desc: [0] packed, [1 .. 5] bases, then scratch: [8 .. 12] the columns' smallest bit patterns, [16 .. 20]
+// their largest, [24] a NaN was seen, [25] the ticket.  The launcher sets min = all ones and zeroes the rest ahead on the stream.
+// k_thermal_range: every workgroup reduces the five columns' u32 patterns to min / max (lanes by shuffles, waves through
+// LDS) and sends ten atomics; the last workgroup to finish (a ticket, as k_hvac_code's) decides with one thread: packed unless a
+// column mixes signs (then its smallest pattern has the sign bit clear and its largest has it set), holds a NaN, or has
+// max - min beyond its field.  One sign per column makes the patterns monotone in the value, so bits - min is the lossless offset.
+// k_thermal_pack: one pass that writes the four planes where the descriptor says packed (otherwise it leaves them alone).
+constexpr int TH_MIN = 8, TH_MAX = 16, TH_NAN = 24, TH_TICKET = 25;
+static_assert(TH_TICKET < MDR_THERMAL_DESC_WORDS && MDR_THERMAL_DESC_BASE + 5 <= TH_MIN, "descriptor layout");
+
+__global__ __launch_bounds__(256) void k_thermal_range(const uint32_t* __restrict__ c0, const uint32_t* __restrict__ c1, const uint32_t* __restrict__ c2,
+                                                       const uint32_t* __restrict__ c3, const uint32_t* __restrict__ c4, int64_t n, uint32_t* desc) {
+  __shared__ uint32_t lds[4][11];
+  const uint32_t* cols[5] = {c0, c1, c2, c3, c4};
+  uint32_t lo[5], hi[5], nan = 0u;
+#pragma unroll
+  for (int c = 0; c < 5; ++c) {
+    lo[c] = ~0u;
+    hi[c] = 0u;
+  }
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      const uint32_t x = cols[c][i];
+      lo[c] = min(lo[c], x);
+      hi[c] = max(hi[c], x);
+      nan |= (x & 0x7FFFFFFFu) > 0x7F800000u ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {   // every lane of the workgroup is here: the loop above has no early exit
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      lo[c] = min(lo[c], (uint32_t)__shfl_xor((int)lo[c], off, 64));
+      hi[c] = max(hi[c], (uint32_t)__shfl_xor((int)hi[c], off, 64));
+    }
+    nan |= (uint32_t)__shfl_xor((int)nan, off, 64);
+  }
+  const int wave = (int)(threadIdx.x >> 6);
+  if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      lds[wave][c] = lo[c];
+      lds[wave][5 + c] = hi[c];
+    }
+    lds[wave][10] = nan;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < 4; ++w) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      lo[c] = min(lo[c], lds[w][c]);
+      hi[c] = max(hi[c], lds[w][5 + c]);
+    }
+    nan |= lds[w][10];
+  }
+#pragma unroll
+  for (int c = 0; c < 5; ++c) {
+    atomicMin(desc + TH_MIN + c, lo[c]);
+    atomicMax(desc + TH_MAX + c, hi[c]);
+  }
+  if (nan != 0u) atomicOr(desc + TH_NAN, 1u);
+  __threadfence();   // the ten results above are device-visible before the ticket is
+  if (atomicAdd(desc + TH_TICKET, 1u) != gridDim.x - 1u) return;
+  constexpr int bits[5] = {TH_B0, TH_B1, TH_B2, TH_B3, TH_B4};
+  bool ok = __hip_atomic_load(desc + TH_NAN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
+  for (int c = 0; c < 5; ++c) {
+    const uint32_t mn = __hip_atomic_load(desc + TH_MIN + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t mx = __hip_atomic_load(desc + TH_MAX + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ok = ok && mx >= mn && ((mn ^ mx) >> 31) == 0u && (mx - mn) < (1u << bits[c]);
+    desc[MDR_THERMAL_DESC_BASE + c] = mn;
+  }
+  desc[MDR_THERMAL_DESC_PACKED] = ok ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_thermal_pack(const uint32_t* __restrict__ c0, const uint32_t* __restrict__ c1, const uint32_t* __restrict__ c2,
+                                                      const uint32_t* __restrict__ c3, const uint32_t* __restrict__ c4, int64_t n,
+                                                      uint32_t* __restrict__ pack, const uint32_t* __restrict__ desc) {
+  if (desc[MDR_THERMAL_DESC_PACKED] == 0u) return;
+  const uint32_t* base = desc + MDR_THERMAL_DESC_BASE;
+  const uint32_t b0 = base[0], b1 = base[1], b2 = base[2], b3 = base[3], b4 = base[4];
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const uint32_t f0 = c0[i] - b0, f1 = c1[i] - b1, f2 = c2[i] - b2, f3 = c3[i] - b3, f4 = c4[i] - b4;   // each below 1 << its width
+    pack[i] = f0 | (f1 << TH_O1);
+    pack[n + i] = (f1 >> (32 - TH_O1)) | (f2 << (TH_O2 - 32));
+    pack[2 * n + i] = (f2 >> (64 - TH_O2)) | (f3 << (TH_O3 - 64));
+    pack[3 * n + i] = (f3 >> (96 - TH_O3)) | (f4 << (TH_O4 - 96));
+  }
+}
+
+hipError_t launch_thermal_pack(const mdr_buffers_t& b, int64_t n, uint32_t* thermal_pack, uint32_t* thermal_desc, hipStream_t s) {
+  if (thermal_pack == nullptr || thermal_desc == nullptr || n < 1) return hipSuccess;
+  hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(thermal_desc), 0, MDR_THERMAL_DESC_WORDS, s);   // not packed until decided
+  if (e != hipSuccess) return e;
+  e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(thermal_desc + TH_MIN), 0xFFFFFFFF, 5, s);
+  if (e != hipSuccess) return e;
+  const uint32_t* c0 = reinterpret_cast<const uint32_t*>(b.k01);
+  const uint32_t* c1 = reinterpret_cast<const uint32_t*>(b.s0);
+  const uint32_t* c2 = reinterpret_cast<const uint32_t*>(b.k10);
+  const uint32_t* c3 = reinterpret_cast<const uint32_t*>(b.s1);
+  const uint32_t* c4 = reinterpret_cast<const uint32_t*>(b.inv_Ua);
+  const int64_t blocks = std::max<int64_t>(std::min<int64_t>((n + 255) / 256, 2048), 1);
+  hipLaunchKernelGGL(k_thermal_range, dim3((unsigned)blocks), dim3(256), 0, s, c0, c1, c2, c3, c4, n, thermal_desc);
+  hipLaunchKernelGGL(k_thermal_pack, dim3((unsigned)blocks), dim3(256), 0, s, c0, c1, c2, c3, c4, n, thermal_pack, thermal_desc);
+  return hipGetLastError();
+}
+
 // Local sum of max consumption per env (ClusterHouses.__init__, env 796-802); P <- 0.  The sum is EXACT in fp64 whatever the order
 // (fp32 addends within a factor of 8 of each other: 24 + log2(N) significant bits), so an env of more than 65,536 houses is summed by
 // several workgroups through atomic adds - one workgroup took 0.98 ms for 1,000,000 houses at every episode start.
@@ -800,7 +910,8 @@ hipError_t launch_cursor_set(int32_t* cursor, int32_t row, int32_t k, hipStream_
 // five local planes only the first LOCAL (StepArgs.interior_local) are stored.  What is left is step_vec's loads, house_step and
 // the state stores: the same statements as the full step's, so the state is the same bit for bit - `lockout` stays loaded at every
 // LOCAL, the HVAC's lockout logic in house_step reads it.  C3: 80 B per house-step -> 47 + 4 LOCAL.
-template <int VEC, int TILES, int THREADS, int LOCAL>
+// PACK (LOCAL == 0 only; StepArgs.interior_pack): the thermal columns through load_thermal, 43 instead of 47 B.
+template <int VEC, int TILES, int THREADS, int LOCAL, int PACK>
 __device__ __forceinline__ void step_fused_interior(StepArgs& a) {
   rebase(a);
   const int e = blockIdx.x;
@@ -813,18 +924,19 @@ __device__ __forceinline__ void step_fused_interior(StepArgs& a) {
     if (h < a.N) {
       HouseOut o[VEC];
       int lockout[VEC];
-      step_vec<VEC, 1>(a, base + h, od_old, solar, o, lockout);
+      step_vec<VEC, 1, PACK>(a, base + h, od_old, solar, o, lockout);
       store_obs_local<VEC, LOCAL>(a, base + h, o, lockout);
     }
   }
   cursor_done(a);
 }
 
-template <int VEC, int TILES, int THREADS, int DEAD = 0, int LOCAL = 5>
+template <int VEC, int TILES, int THREADS, int DEAD = 0, int LOCAL = 5, int PACK = 0>
 __global__ __launch_bounds__(THREADS) void k_step_fused(StepArgs a) {
   static_assert(DEAD == 0 ? LOCAL == 5 : DEAD == 1, "a full step stores all five local planes");
+  static_assert(PACK == 0 || (DEAD == 1 && LOCAL == 0), "the thermal pack is read by the interior form without local planes only");
   if constexpr (DEAD != 0) {
-    step_fused_interior<VEC, TILES, THREADS, LOCAL>(a);
+    step_fused_interior<VEC, TILES, THREADS, LOCAL, PACK>(a);
     return;
   }
   rebase(a);
@@ -1068,10 +1180,11 @@ __global__ __launch_bounds__(THREADS) void k_rollout_fused(StepArgs a, RolloutAr
 // envs per wavefront; reductions by sub-wave DPP exchanges only (no LDS, no barrier).  VEC = 4 / 2 keeps the accesses
 // 16 / 8 bytes wide for the agent counts the reference actually trains with (cli.py: 20 and 50 houses).
 // DEAD = 1: the interior form, as k_step_fused's (step_fused_interior) - no DPP reduction, no signal rows, no post-reduction stores,
-// the first LOCAL local planes only.
-template <int GROUP, int VEC, int DEAD = 0, int LOCAL = 5>
+// the first LOCAL local planes only; PACK: the thermal columns from the pack (LOCAL == 0 only).
+template <int GROUP, int VEC, int DEAD = 0, int LOCAL = 5, int PACK = 0>
 __global__ __launch_bounds__(256) void k_step_group(StepArgs a) {
   static_assert(DEAD == 0 ? LOCAL == 5 : DEAD == 1, "a full step stores all five local planes");
+  static_assert(PACK == 0 || (DEAD == 1 && LOCAL == 0), "the thermal pack is read by the interior form without local planes only");
   rebase(a);
   const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) / GROUP;
   const int lane = threadIdx.x % GROUP;
@@ -1083,7 +1196,7 @@ __global__ __launch_bounds__(256) void k_step_group(StepArgs a) {
   int lockout[VEC];
   if constexpr (DEAD != 0) {
     if (active) {
-      step_vec<VEC, 1>(a, i, a.od_old[e], a.solar_new[e], o, lockout);
+      step_vec<VEC, 1, PACK>(a, i, a.od_old[e], a.solar_new[e], o, lockout);
       store_obs_local<VEC, LOCAL>(a, i, o, lockout);
     }
     cursor_done(a);
@@ -2464,22 +2577,29 @@ hipError_t launch_tables(const TableArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int VEC, int THREADS, int DEAD, int LOCAL>
+template <int VEC, int THREADS, int DEAD, int LOCAL, int PACK = 0>
 static void launch_fused_tiles_dead(const StepArgs& a, int tiles, hipStream_t s) {
   const dim3 g((unsigned)a.E), b(THREADS);
   switch (tiles) {
-    case 1: hipLaunchKernelGGL((k_step_fused<VEC, 1, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((k_step_fused<VEC, 2, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((k_step_fused<VEC, 3, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_step_fused<VEC, 4, THREADS, DEAD, LOCAL>), g, b, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((k_step_fused<VEC, 1, THREADS, DEAD, LOCAL, PACK>), g, b, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((k_step_fused<VEC, 2, THREADS, DEAD, LOCAL, PACK>), g, b, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((k_step_fused<VEC, 3, THREADS, DEAD, LOCAL, PACK>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_step_fused<VEC, 4, THREADS, DEAD, LOCAL, PACK>), g, b, 0, s, a); break;
   }
 }
 
+// StepArgs.interior_pack is honoured only where the PACK form exists and has what it reads
+static bool use_thermal_pack(const StepArgs& a) {
+  return a.interior_dead != 0 && a.interior_local == 0 && a.interior_pack != 0 && a.thermal_pack != nullptr && a.thermal_desc != nullptr;
+}
+
 // StepArgs.interior_dead / interior_local pick the instantiation: the full step, or the interior form (mdr_env_rollout) that still
-// stores the first interior_local local planes.  interior_dead is 0 for every caller but mdr_env_rollout.
+// stores the first interior_local local planes (with none, and interior_pack: the PACK form).  interior_dead is 0 for every caller
+// but mdr_env_rollout.
 template <int VEC, int THREADS>
 static void launch_fused_tiles(const StepArgs& a, int tiles, hipStream_t s) {
   if (a.interior_dead == 0) return launch_fused_tiles_dead<VEC, THREADS, 0, 5>(a, tiles, s);
+  if (use_thermal_pack(a)) return launch_fused_tiles_dead<VEC, THREADS, 1, 0, 1>(a, tiles, s);
   switch (a.interior_local) {
     case 0: launch_fused_tiles_dead<VEC, THREADS, 1, 0>(a, tiles, s); break;
     case 1: launch_fused_tiles_dead<VEC, THREADS, 1, 1>(a, tiles, s); break;
@@ -2758,18 +2878,19 @@ hipError_t launch_step(const StepArgs& args, const StepPlan& p, hipStream_t s) {
   if (p.kind == STEP_GROUP) {
     const int64_t lanes = (int64_t)a.E * p.threads;
     const dim3 g((unsigned)((lanes + 255) / 256)), b(256);
-#define MDR_GROUP_DEAD(G, D, L)                                                        \
-  if (p.vec == 4) hipLaunchKernelGGL((k_step_group<G, 4, D, L>), g, b, 0, s, a);       \
-  else if (p.vec == 2) hipLaunchKernelGGL((k_step_group<G, 2, D, L>), g, b, 0, s, a);  \
-  else hipLaunchKernelGGL((k_step_group<G, 1, D, L>), g, b, 0, s, a);
+#define MDR_GROUP_DEAD(G, D, L, K)                                                        \
+  if (p.vec == 4) hipLaunchKernelGGL((k_step_group<G, 4, D, L, K>), g, b, 0, s, a);       \
+  else if (p.vec == 2) hipLaunchKernelGGL((k_step_group<G, 2, D, L, K>), g, b, 0, s, a);  \
+  else hipLaunchKernelGGL((k_step_group<G, 1, D, L, K>), g, b, 0, s, a);
 #define MDR_GROUP(G)                                                                   \
-  if (a.interior_dead == 0) { MDR_GROUP_DEAD(G, 0, 5) }                                \
-  else if (a.interior_local == 0) { MDR_GROUP_DEAD(G, 1, 0) }                          \
-  else if (a.interior_local == 1) { MDR_GROUP_DEAD(G, 1, 1) }                          \
-  else if (a.interior_local == 2) { MDR_GROUP_DEAD(G, 1, 2) }                          \
-  else if (a.interior_local == 3) { MDR_GROUP_DEAD(G, 1, 3) }                          \
-  else if (a.interior_local == 4) { MDR_GROUP_DEAD(G, 1, 4) }                          \
-  else { MDR_GROUP_DEAD(G, 1, 5) }                                                     \
+  if (a.interior_dead == 0) { MDR_GROUP_DEAD(G, 0, 5, 0) }                             \
+  else if (use_thermal_pack(a)) { MDR_GROUP_DEAD(G, 1, 0, 1) }                         \
+  else if (a.interior_local == 0) { MDR_GROUP_DEAD(G, 1, 0, 0) }                       \
+  else if (a.interior_local == 1) { MDR_GROUP_DEAD(G, 1, 1, 0) }                       \
+  else if (a.interior_local == 2) { MDR_GROUP_DEAD(G, 1, 2, 0) }                       \
+  else if (a.interior_local == 3) { MDR_GROUP_DEAD(G, 1, 3, 0) }                       \
+  else if (a.interior_local == 4) { MDR_GROUP_DEAD(G, 1, 4, 0) }                       \
+  else { MDR_GROUP_DEAD(G, 1, 5, 0) }                                                  \
   break;
     switch (p.threads) {
       case 1: MDR_GROUP(1)

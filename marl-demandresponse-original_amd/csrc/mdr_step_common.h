@@ -208,6 +208,55 @@ __device__ __forceinline__ void load_hvac(const StepArgs& a, bool coded, int64_t
     load_param<VEC>(a.P_max, i, pm);
   }
 }
+// The five thermal columns k01, s0, k10, s1, inv_Ua as one 16-byte record per house (mdr_env_bind_thermal_pack; PACK instantiations
+// of the interior form only): thermal_desc[MDR_THERMAL_DESC_PACKED] != 0 says that plane j of thermal_pack holds dword j of every
+// house's record - field c is bits(column c) - thermal_desc[MDR_THERMAL_DESC_BASE + c], the fields laid end to end from bit 0 - 16 B
+// per house-step streamed instead of 20.  The word and the bases are wave-uniform (scalar loads, like the uniformity word): one
+// branch, and both arms leave the same bits in the same registers.  A field is two shifts and an or across its dwords (one
+// v_alignbit), a mask and an integer add; no other lane is needed, so it is right under any EXEC mask.  The fields are decoded inside
+// the loading arm, which waits for the records there.  Decoding them behind the loads that follow (class byte, target / deadband /
+// lockout) keeps raw and decoded words live together: 84 instead of 68 VGPRs in k_step_fused<4,1,256,1,0,1>, 5 instead of 7 waves
+// per SIMD, and 29.6 instead of 28.7 us per launch at C3 (profiles/r09_README.md).
+constexpr int TH_B0 = MDR_THERMAL_BITS_K01, TH_B1 = MDR_THERMAL_BITS_S0, TH_B2 = MDR_THERMAL_BITS_K10, TH_B3 = MDR_THERMAL_BITS_S1,
+              TH_B4 = MDR_THERMAL_BITS_INV_UA;
+constexpr int TH_O1 = TH_B0, TH_O2 = TH_O1 + TH_B1, TH_O3 = TH_O2 + TH_B2, TH_O4 = TH_O3 + TH_B3;   // bit offsets of fields 1 .. 4
+static_assert(TH_O4 + TH_B4 == 128, "the five fields fill the 128-bit record");
+static_assert(TH_B0 < 32 && TH_O1 < 32 && TH_O2 > 32 && TH_O2 < 64 && TH_O3 > 64 && TH_O3 < 96 && TH_O4 > 96 &&
+              TH_O1 + TH_B1 > 32 && TH_O2 + TH_B2 > 64 && TH_O3 + TH_B3 > 96, "thermal_field below: fields 1 - 3 each straddle one dword boundary");
+// the `bits` wide field at bit offset `off` (0 < off % 32) of the dword pair lo = dword off / 32, hi = the next one
+template <int OFF, int BITS>
+__device__ __forceinline__ uint32_t thermal_field(uint32_t lo, uint32_t hi) {
+  return ((lo >> (OFF % 32)) | (hi << (32 - OFF % 32))) & ((1u << BITS) - 1u);
+}
+__device__ __forceinline__ uint32_t thermal_packed(const StepArgs& a) { return a.thermal_desc != nullptr ? a.thermal_desc[MDR_THERMAL_DESC_PACKED] : 0u; }
+template <int VEC>
+__device__ __forceinline__ void load_thermal(const StepArgs& a, bool packed, int64_t i, float* k01, float* s0, float* k10, float* s1, float* iu) {
+  if (packed) {
+    const int* pk = reinterpret_cast<const int*>(a.thermal_pack);
+    const uint32_t* base = a.thermal_desc + MDR_THERMAL_DESC_BASE;
+    const uint32_t b0 = base[0], b1 = base[1], b2 = base[2], b3 = base[3], b4 = base[4];
+    int w0[VEC], w1[VEC], w2[VEC], w3[VEC];
+    load_vec<VEC>(pk, i, w0);
+    load_vec<VEC>(pk + a.plane, i, w1);
+    load_vec<VEC>(pk + 2 * a.plane, i, w2);
+    load_vec<VEC>(pk + 3 * a.plane, i, w3);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const uint32_t d0 = (uint32_t)w0[v], d1 = (uint32_t)w1[v], d2 = (uint32_t)w2[v], d3 = (uint32_t)w3[v];
+      k01[v] = __uint_as_float((d0 & ((1u << TH_B0) - 1u)) + b0);
+      s0[v] = __uint_as_float(thermal_field<TH_O1, TH_B1>(d0, d1) + b1);
+      k10[v] = __uint_as_float(thermal_field<TH_O2, TH_B2>(d1, d2) + b2);
+      s1[v] = __uint_as_float(thermal_field<TH_O3, TH_B3>(d2, d3) + b3);
+      iu[v] = __uint_as_float((d3 >> (TH_O4 % 32)) + b4);
+    }
+  } else {
+    load_param<VEC>(a.k01, i, k01);
+    load_param<VEC>(a.s0, i, s0);
+    load_param<VEC>(a.k10, i, k10);
+    load_param<VEC>(a.s1, i, s1);
+    load_param<VEC>(a.inv_Ua, i, iu);
+  }
+}
 template <int VEC>
 __device__ __forceinline__ void store_bytes(uint8_t* __restrict__ p, int64_t i, const unsigned* v) {
   if constexpr (VEC == 4) {
@@ -326,7 +375,8 @@ __device__ __forceinline__ void house_step_vec(const StepArgs& a, int64_t i, con
 // DEAD != 0 (the interior steps of mdr_env_rollout, k_step_fused / k_step_group): the in-kernel controllers' commands are not
 // written to `actions` - the next step's launch overwrites them unread.  The loads, the arithmetic and the state stores are the
 // same statements at every DEAD, so Ta / Tm / sso / flags come out bit for bit the same.
-template <int VEC, int DEAD = 0>
+// PACK != 0 (interior steps without a local plane, large batches): the five thermal columns through load_thermal - the same bits.
+template <int VEC, int DEAD = 0, int PACK = 0>
 __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, const float* od_old, const float* solar, HouseOut* out, int* lockout) {
   float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];
   int sso[VEC];
@@ -338,11 +388,15 @@ __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, cons
   load_vec<VEC>(a.sso, i, sso);
   load_bytes<VEC>(a.flags, i, fl);
   if (a.action_source == MDR_ACTIONS_EXTERNAL) load_bytes<VEC>(a.actions, i, act);
-  load_param<VEC>(a.k01, i, k01);
-  load_param<VEC>(a.s0, i, s0);
-  load_param<VEC>(a.k10, i, k10);
-  load_param<VEC>(a.s1, i, s1);
-  load_param<VEC>(a.inv_Ua, i, iu);
+  if constexpr (PACK != 0) {
+    load_thermal<VEC>(a, thermal_packed(a) != 0u, i, k01, s0, k10, s1, iu);
+  } else {
+    load_param<VEC>(a.k01, i, k01);
+    load_param<VEC>(a.s0, i, s0);
+    load_param<VEC>(a.k10, i, k10);
+    load_param<VEC>(a.s1, i, s1);
+    load_param<VEC>(a.inv_Ua, i, iu);
+  }
   load_hvac<VEC>(a, coded, i, q, pm);
   load_param_or_first<VEC>((uni & UNIFORM_TARGET) != 0u, a.target, i, tg);
   load_param_or_first<VEC>((uni & UNIFORM_DEADBAND) != 0u, a.deadband, i, db);
@@ -392,7 +446,7 @@ __device__ __forceinline__ void step_vec_rows(const StepArgs& a, int64_t i, cons
   }
 }
 
-template <int VEC, int DEAD = 0>
+template <int VEC, int DEAD = 0, int PACK = 0>
 __device__ __forceinline__ void step_vec(const StepArgs& a, int64_t i, float od_old, float solar, HouseOut* out, int* lockout) {
   float od[VEC], so[VEC];
 #pragma unroll
@@ -400,7 +454,7 @@ __device__ __forceinline__ void step_vec(const StepArgs& a, int64_t i, float od_
     od[v] = od_old;
     so[v] = solar;
   }
-  step_vec_rows<VEC, DEAD>(a, i, od, so, out, lockout);
+  step_vec_rows<VEC, DEAD, PACK>(a, i, od, so, out, lockout);
 }
 
 // The five observation columns that do not depend on the env-wide reductions.
