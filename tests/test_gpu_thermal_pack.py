@@ -4,8 +4,9 @@ With MDR_ROLLOUT_STREAM_HOUSES=0 every batch is a "large" one: the interior step
 k_step_fused / k_step_group.  After reset the records and the descriptor on the device must equal the numpy reference
 (tests/thermal_pack_ref.py) bit for bit, and rollout(K) must leave what K single steps leave, bit for bit, over Ta, Tm, sso, flags,
 reward, obs, actions and P - K = 70 crosses a refill of the 64-row tables.  Also: the fallback when a column cannot be packed, the
-two switches, the unset threshold (the parent's plan at these sizes, read from mdr_env_rollout_plan, not from a clock), and a
-snapshot taken without a pack loaded into an env with one.
+two switches, the unset threshold (the parent's plan at these sizes, read from mdr_env_rollout_plan, not from a clock), a
+snapshot taken without a pack loaded into an env with one, and the field boundaries: a column whose range fills its field exactly
+(an all-ones field, through load_thermal's masks) and one a single pattern wider (k_thermal_range's "not packed").
 
 The knobs are read once per process: every test starts one fresh child (this file run as a script, never an exec) under its own
 timeout."""
@@ -174,10 +175,82 @@ def _mode_extras(arg):
     return bad
 
 
+def _set_pattern(env, name, house, pattern):
+    """Writes a u32 bit pattern into one house of a column, through an int32 view of the column."""
+    import torch
+    env.t[name].view(torch.int32).view(-1)[house] = pattern - (1 << 32) if pattern >= 1 << 31 else pattern
+
+
+def _all_ones_fields(label, env, tops):
+    """{column index: house}: the house holding the column's largest pattern carries an all-ones field in the device's records."""
+    from tests import thermal_pack_ref as tp
+    got = tp.fields(_device_pack(env)[1])
+    return ["%s: field %s of house %d is %#x, not all ones" % (label, tp.COLUMNS[c], h, int(got[c][h]))
+            for c, h in tops.items() if int(got[c][h]) != (1 << tp.WIDTHS[c]) - 1]
+
+
+def _mode_edges(arg):
+    """MDR_ROLLOUT_STREAM_HOUSES=0: a field that is exactly full (max - min == 2^w - 1: packed, all ones in the records, the PACK
+    decode's masks at the dword boundaries) and a range one pattern too wide (2^w: k_thermal_range must say not packed), per column
+    and for all five columns at once; rollout(K) against single steps each time."""
+    from tests import thermal_pack_ref as tp
+    from tests.test_gpu_rollout_interior import _cfg
+    bad = []
+    for E, N in ((2, 1024), (5, 20)):
+        env = _make(_cfg(N), E)
+        env.reset(episode=0)
+        bad += _pack_matches("%dx%d before" % (E, N), env)
+        if env.rollout_plan() != (0, True):
+            bad.append("%dx%d: plan %s" % (E, N, env.rollout_plan()))
+        orig = {name: env.t[name].clone() for name in tp.COLUMNS}
+        patterns = [tp.bits(orig[name].cpu().numpy()) for name in tp.COLUMNS]
+        tops = {c: int(b.argmax()) for c, b in enumerate(patterns)}
+        his = {c: int(b.max()) for c, b in enumerate(patterns)}
+        houses = {}
+        for c, (name, b) in enumerate(zip(tp.COLUMNS, patterns)):
+            # a house of its own per column, never one that holds a column's largest pattern
+            houses[c] = next(h for h in range(b.size) if h not in houses.values() and h not in tops.values())
+            span = 1 << tp.WIDTHS[c]
+            # hi - 2^w: the same sign, a smaller magnitude, still a normal number, and below the column's smallest pattern
+            assert (his[c] & 0x7FFFFFFF) - span >= 0x00800000 and his[c] - span + 1 < int(b.min()), (name, hex(his[c]))
+        for c, name in enumerate(tp.COLUMNS):
+            w = tp.WIDTHS[c]
+            label = "%dx%d %s" % (E, N, name)
+            _set_pattern(env, name, houses[c], his[c] - ((1 << w) - 1))          # the field is exactly full
+            env.params_changed()
+            bad += _pack_matches(label + " range 2^%d - 1" % w, env)
+            bad += _all_ones_fields(label + " range 2^%d - 1" % w, env, {c: tops[c]})
+            bad += _rollout_matches(label + " range 2^%d - 1" % w, env, reset=False, counts=(2, 70))
+            _set_pattern(env, name, houses[c], his[c] - (1 << w))                # one pattern too wide
+            env.params_changed()
+            bad += _pack_matches(label + " range 2^%d" % w, env, expect_packed=False)
+            if env.rollout_plan() != (0, True):                                  # the PACK form still runs: its streaming arm
+                bad.append("%s range 2^%d: plan %s" % (label, w, env.rollout_plan()))
+            bad += _rollout_matches(label + " range 2^%d" % w, env, reset=False, counts=(2, 70))
+            env.t[name].copy_(orig[name])
+        for c, name in enumerate(tp.COLUMNS):                                    # all five at full width, a house per column
+            _set_pattern(env, name, houses[c], his[c] - ((1 << tp.WIDTHS[c]) - 1))
+        env.params_changed()
+        label = "%dx%d all five fields full" % (E, N)
+        assert tp.needed_widths([env.t[n].cpu().numpy() for n in tp.COLUMNS]) == tp.WIDTHS
+        bad += _pack_matches(label, env)
+        bad += _all_ones_fields(label, env, tops)
+        bad += _rollout_matches(label, env, reset=False, counts=(2, 70))
+        for name in tp.COLUMNS:
+            env.t[name].copy_(orig[name])
+        env.params_changed()
+        bad += _pack_matches("%dx%d restored" % (E, N), env)
+        for name in tp.COLUMNS:
+            if not _same_bits(env.t[name], orig[name]):
+                bad.append("%dx%d restored: %s differs" % (E, N, name))
+    return bad
+
+
 MODES = {"forms": (_mode_forms, {"MDR_ROLLOUT_STREAM_HOUSES": "0"}),
          "pack_off": (_mode_pack_off, {"MDR_ROLLOUT_STREAM_HOUSES": "0", "MDR_THERMAL_PACK": "0"}),
          "unset": (_mode_unset, {}),
-         "extras": (_mode_extras, {"MDR_ROLLOUT_STREAM_HOUSES": "0"})}
+         "extras": (_mode_extras, {"MDR_ROLLOUT_STREAM_HOUSES": "0"}),
+         "edges": (_mode_edges, {"MDR_ROLLOUT_STREAM_HOUSES": "0"})}
 
 
 def _run_child(mode, arg="-"):
@@ -203,6 +276,10 @@ def test_pack_switched_off_in_the_environment():
 
 def test_unset_threshold_takes_the_parents_plan_at_small_shapes():
     _run_child("unset")
+
+
+def test_fields_exactly_full_and_ranges_one_pattern_too_wide():
+    _run_child("edges")
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 """The thermal pack without a GPU: the entry points are exported and host-checked, and the format (tests/thermal_pack_ref.py) is
 lossless on the oracle's own sample of the benchmark's configuration, needs the widths the field layout was chosen for at the
-corners of house_big_noise's box, and reports "not packed" for what it cannot hold."""
+corners of house_big_noise's box, reports "not packed" for what it cannot hold, and is exact at the field boundary: a range of
+2^w - 1 patterns fills field w with ones and touches no neighbour, a range of 2^w is refused."""
 import itertools
 
 import numpy as np
@@ -89,3 +90,59 @@ def test_a_column_holding_a_zero_still_packs_if_it_fits():
     assert not tp.describe(cols)[0]
     cols[2] = np.array([0.0] * (n - 1) + [-0.0], dtype=np.float32)           # -0.0 is another sign
     assert not tp.describe(cols)[0]
+
+
+def _widened(flat, c, span):
+    """The columns with one house of column c moved `span` patterns below the column's largest pattern (same sign, smaller
+    magnitude): (columns, the house holding the largest pattern, the house written)."""
+    cols = [x.copy() for x in flat]
+    b = tp.bits(cols[c])
+    top = int(b.argmax())
+    hi = int(b[top])
+    assert (hi & 0x7FFFFFFF) - span >= 0x00800000 and hi - span < int(b.min())      # still a normal number of that sign, and the new smallest
+    house = (top + 1) % b.size
+    cols[c].view(np.uint32)[house] = np.uint32(hi - span)
+    return cols, top, house
+
+
+@pytest.mark.parametrize("c", range(5))
+def test_a_field_that_is_exactly_full_round_trips(c3, c):
+    """max - min == 2^w - 1 in column c: still packed, the house with the largest pattern carries an all-ones field, the one with
+    the smallest a zero, every column comes back bit for bit and the other four columns' fields are what they were."""
+    flat = [x.ravel().copy() for x in c3[1]]
+    w = tp.WIDTHS[c]
+    before = tp.fields(tp.pack(flat)[2])
+    cols, top, house = _widened(flat, c, (1 << w) - 1)
+    assert tp.needed_widths(cols)[c] == w
+    packed, bases, planes = tp.pack(cols)
+    assert packed
+    after = tp.fields(planes)
+    assert int(after[c][top]) == (1 << w) - 1 and int(after[c][house]) == 0
+    for j in range(5):
+        if j != c:
+            assert np.array_equal(after[j], before[j]), (tp.COLUMNS[c], tp.COLUMNS[j])      # an all-ones field leaks into no neighbour
+    for name, col, back in zip(tp.COLUMNS, cols, tp.unpack(bases, planes)):
+        assert np.array_equal(tp.bits(col), tp.bits(back)), name
+
+
+@pytest.mark.parametrize("c", range(5))
+def test_a_range_one_pattern_too_wide_is_not_packed(c3, c):
+    flat = [x.ravel().copy() for x in c3[1]]
+    cols, _, _ = _widened(flat, c, 1 << tp.WIDTHS[c])
+    assert tp.needed_widths(cols)[c] == tp.WIDTHS[c] + 1
+    assert not tp.describe(cols)[0] and tp.pack(cols)[2] is None
+
+
+def test_all_five_fields_exactly_full_at_once(c3):
+    flat = [x.ravel().copy() for x in c3[1]]
+    cols, tops = flat, []
+    for c in range(5):
+        cols, top, house = _widened(cols, c, (1 << tp.WIDTHS[c]) - 1)
+        tops.append(top)
+    assert tp.needed_widths(cols) == tp.WIDTHS
+    packed, bases, planes = tp.pack(cols)
+    assert packed
+    after = tp.fields(planes)
+    assert [int(after[c][tops[c]]) for c in range(5)] == [(1 << w) - 1 for w in tp.WIDTHS]
+    for name, col, back in zip(tp.COLUMNS, cols, tp.unpack(bases, planes)):
+        assert np.array_equal(tp.bits(col), tp.bits(back)), name

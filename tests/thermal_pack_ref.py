@@ -65,13 +65,13 @@ def pack(cols):
     return True, bases, planes
 
 
-def unpack(bases, planes):
-    """The five fp32 columns (flat) back from the records."""
+def fields(planes):
+    """The five raw fields (uint32, flat) of every record."""
     p = planes.astype(np.uint64)
     lo = p[0] | (p[1] << np.uint64(32))
     hi = p[2] | (p[3] << np.uint64(32))
     out = []
-    for c, (off, w) in enumerate(zip(OFFSETS, WIDTHS)):
+    for off, w in zip(OFFSETS, WIDTHS):
         mask = np.uint64((1 << w) - 1)
         if off + w <= 64:
             f = (lo >> np.uint64(off)) & mask
@@ -79,5 +79,10 @@ def unpack(bases, planes):
             f = (hi >> np.uint64(off - 64)) & mask
         else:
             f = ((lo >> np.uint64(off)) | (hi << np.uint64(64 - off))) & mask
-        out.append((f.astype(np.uint32) + np.uint32(bases[c])).view(np.float32))
+        out.append(f.astype(np.uint32))
     return out
+
+
+def unpack(bases, planes):
+    """The five fp32 columns (flat) back from the records."""
+    return [(f + np.uint32(bases[c])).view(np.float32) for c, f in enumerate(fields(planes))]
