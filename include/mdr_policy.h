@@ -312,9 +312,10 @@ int mdr_env_tarmac_actor_sample(mdr_env_t *env, const mdr_obs_spec_t *spec, cons
  *
  * One network of agents/network.py:14-57 - Linear(F,H1) - ReLU - Linear(H1,H2) - ReLU - Linear(H2,O) - in torch's own layout,
  * w[out][in] contiguous, device memory, read as it is on every call (an optimiser step changes it between any two calls: there is
- * nothing to repack).  Limits: F <= 64, H1 <= 128, H2 <= 128, O = 2 (actor) or 1 (critic); the observations with message columns
- * (81..121 features) are outside them.  MAPPO's critic on state + others' actions has an entry point of its own with a wider input
- * (mdr_mappo_critic_grad below: up to 128 joint features). */
+ * nothing to repack).  Limits: F <= 64, H1 <= 128, H2 <= 128, O = 2 (actor) or 1 (critic).  The observations with message columns
+ * (81, 91, 121 features) are outside them and go to the mdr_*_wide entry points behind the DQN block below: F <= 128 and the LDS fit
+ * (hidden 100-100 at every F <= 128; 128-128 up to F = 100).  MAPPO's critic on state + others' actions has an entry point of its
+ * own with a wider input (mdr_mappo_critic_grad below: up to 128 joint features). */
 typedef struct mdr_mlp {
   uint32_t struct_size;
   int32_t num_state, hidden1, hidden2, num_out;
@@ -433,6 +434,42 @@ int mdr_dqn_target(const mdr_mlp_t *target_net, const mdr_mlp_t *policy_net, con
 int mdr_dqn_grad(const mdr_mlp_t *policy_net, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
                  const int64_t *action, const float *y, float grad_clamp, int32_t max_workgroups, void *workspace, float *grad,
                  float *loss, float *q, void *stream);
+
+/* ---- The same update steps for 65..128 input features: the observations with message_properties["thermal"] (81 features), ["hvac"]
+ * (91) or both (121).  Every entry point above keeps its limits; each has a sibling here with the same argument list, the same
+ * arithmetic, the same status codes and the same contract (checks on the host before any launch, nothing written on -1 and -4).
+ * Limits: F <= 128 (the joint critic: J <= 128), H1 <= 128, H2 <= 128 and the LDS fit.  From F = 65 on they run an instantiation of
+ * the kernel with 8 dW1 blocks per wave and an LDS layout in which the image of dz1 shares the storage of h2 (the two are never live
+ * at once), which fits
+ *   hidden 100-100 (.. 112-112) at every F <= 128,   128-128 up to F = 100,   64-64 .. 96-96 at every F <= 128;
+ * a shape that does not fit - 128-128 at F = 101 - returns -4 (the size queries -1).  For F <= 64 a wide entry point is its narrow
+ * sibling: the same kernel, the same bits.  mdr_mappo_critic_grad_wide takes the same kernel as mdr_mappo_critic_grad with the shared
+ * image, so 100-100 fits up to J = 128 (above: 100) and 128-128 up to J = 100 (above: 68); it returns mdr_mappo_critic_grad's bits
+ * wherever both accept.  J > 128 - F = 121 with 20 agents is J = 140 - stays refused.
+ * mdr_dqn_target_wide refuses what mdr_dqn_grad_wide refuses (its own forward-only image would fit a little more): the pair is
+ * accepted or refused together.  Sizes: mdr_mlp_wide_grad_floats / mdr_mlp_wide_grad_workspace_bytes for the actor, critic and DQN
+ * calls (equal to the narrow queries wherever those answer), mdr_mappo_critic_wide_grad_floats / _wide_workspace_bytes for the joint
+ * critic. */
+int64_t mdr_mlp_wide_grad_floats(const mdr_mlp_t *net);
+int64_t mdr_mlp_wide_grad_workspace_bytes(const mdr_mlp_t *net, int64_t nb_rows, int32_t max_workgroups);
+int mdr_ppo_actor_grad_wide(const mdr_mlp_t *actor, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                            const int64_t *action, const float *old_prob, const float *advantage, float clip_param,
+                            int32_t max_workgroups, void *workspace, float *grad, float *loss, float *ratio, void *stream);
+int mdr_ppo_critic_grad_wide(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                             const float *target, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
+                             float *advantage, void *stream);
+int mdr_dqn_target_wide(const mdr_mlp_t *target_net, const mdr_mlp_t *policy_net, const float *next_state, int64_t ld_state,
+                        const int64_t *index, int64_t nb_rows, const float *reward, float gamma, int32_t max_workgroups, float *y,
+                        float *next_q, uint8_t *next_action, void *stream);
+int mdr_dqn_grad_wide(const mdr_mlp_t *policy_net, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                      const int64_t *action, const float *y, float grad_clamp, int32_t max_workgroups, void *workspace, float *grad,
+                      float *loss, float *q, void *stream);
+int64_t mdr_mappo_critic_wide_grad_floats(const mdr_mlp_t *critic, int32_t nb_agents);
+int64_t mdr_mappo_critic_wide_workspace_bytes(const mdr_mlp_t *critic, int32_t nb_agents, int64_t nb_rows, int32_t max_workgroups);
+int mdr_mappo_critic_grad_wide(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *action,
+                               int64_t nb_transitions, int32_t nb_agents, const int64_t *index, int64_t nb_rows, const float *target,
+                               int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value, float *advantage,
+                               void *stream);
 
 /* ---- MADDPG's update step (MADDPG.update, agents/ddpg.py:305-339) with one shared actor, critic and target of each: for agent a the
  * TD target through both target nets, the joint critic's mse loss and gradient, the gumbel-softmax actor's loss and gradient.  All

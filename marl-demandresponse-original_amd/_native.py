@@ -196,6 +196,9 @@ EXPORTS = (
     "mdr_env_tarmac_actor_sample",
     "mdr_mlp_grad_floats", "mdr_mlp_grad_workspace_bytes", "mdr_ppo_actor_grad", "mdr_ppo_critic_grad", "mdr_dqn_target", "mdr_dqn_grad",
     "mdr_mappo_critic_grad_floats", "mdr_mappo_critic_workspace_bytes", "mdr_mappo_critic_grad",
+    "mdr_mlp_wide_grad_floats", "mdr_mlp_wide_grad_workspace_bytes", "mdr_ppo_actor_grad_wide", "mdr_ppo_critic_grad_wide",
+    "mdr_dqn_target_wide", "mdr_dqn_grad_wide",
+    "mdr_mappo_critic_wide_grad_floats", "mdr_mappo_critic_wide_workspace_bytes", "mdr_mappo_critic_grad_wide",
     "mdr_maddpg_grad_floats", "mdr_maddpg_workspace_bytes", "mdr_maddpg_target", "mdr_maddpg_critic_grad", "mdr_maddpg_actor_grad",
     "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
     "mdr_tarmac_critic_grad_floats", "mdr_tarmac_critic_workspace_bytes", "mdr_tarmac_critic_value", "mdr_tarmac_critic_grad",
@@ -305,6 +308,16 @@ def load():
         "mdr_mappo_critic_grad_floats": (i64, [C.POINTER(MdrMlp), i32]),
         "mdr_mappo_critic_workspace_bytes": (i64, [C.POINTER(MdrMlp), i32, i64, i32]),
         "mdr_mappo_critic_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
+        # the wide siblings (65..128 input features): the same argument lists
+        "mdr_mlp_wide_grad_floats": (i64, [C.POINTER(MdrMlp)]),
+        "mdr_mlp_wide_grad_workspace_bytes": (i64, [C.POINTER(MdrMlp), i64, i32]),
+        "mdr_ppo_actor_grad_wide": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp]),
+        "mdr_ppo_critic_grad_wide": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "mdr_dqn_target_wide": (C.c_int, [C.POINTER(MdrMlp), C.POINTER(MdrMlp), vp, i64, vp, i64, vp, C.c_float, i32, vp, vp, vp, vp]),
+        "mdr_dqn_grad_wide": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp]),
+        "mdr_mappo_critic_wide_grad_floats": (i64, [C.POINTER(MdrMlp), i32]),
+        "mdr_mappo_critic_wide_workspace_bytes": (i64, [C.POINTER(MdrMlp), i32, i64, i32]),
+        "mdr_mappo_critic_grad_wide": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
         "mdr_maddpg_grad_floats": (i64, [C.POINTER(MdrMlp)]),
         "mdr_maddpg_workspace_bytes": (i64, [C.POINTER(MdrMlp), C.POINTER(MdrMlp), i32, i64, i32]),
         "mdr_maddpg_target": (C.c_int, [C.POINTER(MdrMlp), C.POINTER(MdrMlp), vp, i64, vp, vp, i64, i32, i32, vp, C.c_float, C.c_float, i32,

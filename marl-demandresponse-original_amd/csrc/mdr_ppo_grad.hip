@@ -28,7 +28,7 @@
 //   B2       dh1 block w = W2^T dz2 (A = W2 read transposed), dz1 = relu'(z1) dh1                           -> dz1T
 //            and dW1 rows of block w += dz1^T x, db1
 // Five barriers per tile.  The accumulators of the three weight gradients stay in registers for the whole launch (dW2 8 blocks, dW1
-// 4 blocks, two bias blocks, one head register: 57 registers); each workgroup writes its partial once.  relu'(z) = 1 iff z > 0.
+// 4 blocks - 8 in the wide instantiations below -, two bias blocks, one head register: 57 or 73 registers); each workgroup writes its partial once.  relu'(z) = 1 iff z > 0.
 // Rows past the minibatch are forwarded as zero states and given zero dlogits: they add exact zeros.
 //
 // DQN.update / DDQN.update (agents/dqn.py:84-146) take two more heads of the same body.  HEAD_TARGET is forward only - staging, F1, F2
@@ -41,8 +41,13 @@
 // of xT are the state's, row F + k of transition j is the action of the k-th OTHER agent of j's env (train_mappo.py:79-84: the step's
 // action dict without agent a = j % N, in agent order), read from the `action` buffer while the tile is staged - the env-mates of
 // row j are the N entries from j - a on (collect_ppo_rollout's flat layout: the agent index runs fastest).  No others_actions
-// tensor is read or needed.  The width is a compile-time property of the instantiation (MAXF: 8 dW1 blocks per wave, 4 tile
-// elements per thread); the other heads keep 4 and 2.
+// tensor is read or needed.
+//
+// The input width is a compile-time property of the instantiation, independent of the head: MAXF = 64 (4 dW1 blocks per wave, 2 tile
+// elements per thread) or MAXF = 128 (8 and 4).  HEAD_JOINT has the wide form only; the other four heads have both, the narrow one
+// behind the entry points of up to 64 features, the wide one behind the mdr_*_wide entry points for 65..128 (the optional message
+// columns: 81, 91, 121 features).  The wide entry points lay LDS out with dz1T in h2T's storage (make_shape: `alias`), which is
+// what a 100-100 network needs at 101..128 inputs; the layout is a property of the Shape, not of the code.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -62,12 +67,13 @@ constexpr int TILE = 16;              // minibatch rows per tile
 constexpr int LT = 20;                // row stride of the transposed tile images
 constexpr int MAX_F = 64, MAX_H = 128;
 constexpr int MAX_J = 128;           // HEAD_JOINT: state + others' actions
+constexpr int MAX_WIDE = 128;        // the wide instantiations of the other heads
 constexpr int LIB_MAX_WG = 512;       // the library's own grid: min(tiles, CUs, this)
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
-__host__ __device__ inline int blocks16(int n) { return (n + 15) / 16; }
+__host__ __device__ constexpr int blocks16(int n) { return (n + 15) / 16; }
 // smallest stride >= n that is 4 (mod 32)
-__host__ __device__ inline int ld_for(int n) { return ((n + 27) / 32) * 32 + 4; }
+__host__ __device__ constexpr int ld_for(int n) { return ((n + 27) / 32) * 32 + 4; }
 
 struct Shape {
   int F, H1, H2, O;
@@ -80,8 +86,18 @@ struct Shape {
 };
 
 // backward == false (HEAD_TARGET): no h2T, dz2T, dz1T and dlogits images
-__host__ __device__ inline Shape make_shape(int F, int H1, int H2, int O, bool backward = true) {
-  Shape s;
+//
+// alias == true (the wide entry points): dz1T lies in h2T's storage, one image of max(H1p, H2p) rows.  The two never hold live data
+// at once, and every access of either is to the wave's own block w:
+//   h2T   written in F2 (wave w, rows 16 w .. 16 w + 15), last read by the dW3 chain of the head section (wave w, the same rows),
+//         which lies before the barrier that opens B2;
+//   dz1T  written in B2 (wave w, rows of block w) and read only there (dW1 / db1 of block w, behind the wave's fence); B2 ends in a
+//         barrier;
+//   h2T's next write is in the next tile's F2, behind that tile's F1 barrier (and the barrier after store_x).
+// So every read of h2T is separated by a barrier from the dz1T writes that follow it, and every read of dz1T by two barriers from the
+// h2T writes that follow.  HEAD_TARGET has neither image.
+__host__ __device__ constexpr Shape make_shape(int F, int H1, int H2, int O, bool backward = true, bool alias = false) {
+  Shape s{};
   s.F = F, s.H1 = H1, s.H2 = H2, s.O = O;
   s.nbf = blocks16(F), s.nb1 = blocks16(H1), s.nb2 = blocks16(H2);
   s.ld1 = ld_for(4 * ((F + 3) / 4)), s.ld2 = ld_for(16 * s.nb1);
@@ -97,13 +113,27 @@ __host__ __device__ inline Shape make_shape(int F, int H1, int H2, int O, bool b
   s.sx = s.sb3 + 4;
   s.sh1 = s.sx + 16 * s.nbf * LT;
   s.sh2 = s.sh1 + H1p * LT;
-  s.sdz2 = s.sh2 + (backward ? H2p * LT : 0);
-  s.sdz1 = s.sdz2 + (backward ? H2p * LT : 0);
-  s.sdl = s.sdz1 + (backward ? H1p * LT : 0);
+  if (alias) {
+    s.sdz1 = s.sh2;
+    s.sdz2 = s.sh2 + (backward ? (H1p > H2p ? H1p : H2p) * LT : 0);
+    s.sdl = s.sdz2 + (backward ? H2p * LT : 0);
+  } else {
+    s.sdz2 = s.sh2 + (backward ? H2p * LT : 0);
+    s.sdz1 = s.sdz2 + (backward ? H2p * LT : 0);
+    s.sdl = s.sdz1 + (backward ? H1p * LT : 0);
+  }
   s.slp = s.sdl + (backward ? NW * TILE * 2 : 0);
   s.lds = s.slp + NW * TILE * 2;
   return s;
 }
+
+// What the aliased layout buys, by make_shape's own arithmetic (bytes of LDS against the 160 KiB of a workgroup)
+constexpr size_t lds_bytes_of(int F, int H1, int H2, bool alias) { return (size_t)make_shape(F, H1, H2, 2, true, alias).lds * sizeof(float); }
+static_assert(lds_bytes_of(121, 100, 100, true) == 159248 && lds_bytes_of(128, 100, 100, true) == 159248, "100-100: every F <= 128 fits aliased");
+static_assert(lds_bytes_of(121, 100, 100, false) == 168208 && lds_bytes_of(121, 100, 100, false) > LDS_LIMIT, "100-100 at F = 121 needs the alias");
+static_assert(lds_bytes_of(100, 128, 128, true) == 162576 && lds_bytes_of(100, 128, 128, true) <= LDS_LIMIT, "128-128: up to F = 100");
+static_assert(lds_bytes_of(101, 128, 128, true) > LDS_LIMIT, "128-128 at F = 101 (ld1 steps from 100 to 132): refused by the LDS-fit check");
+static_assert(lds_bytes_of(64, 128, 128, false) <= LDS_LIMIT, "every shape of the narrow entry points fits un-aliased");
 
 struct GradArgs {
   Shape s;
@@ -139,13 +169,14 @@ __device__ __forceinline__ void stage_matrix(float* dst, const float* src, int r
   }
 }
 
-template <Head HEAD>
+template <Head HEAD, int MAXF>
 __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Shape& s = a.s;
   constexpr bool JOINT = HEAD == HEAD_JOINT;
   constexpr int O = (HEAD == HEAD_CRITIC || JOINT) ? 1 : 2;
-  constexpr int MAXF = JOINT ? MAX_J : MAX_F;         // input features of this instantiation
+  static_assert(MAXF == MAX_F || MAXF == MAX_WIDE, "input features of this instantiation: 64 or 128");
+  static_assert(!JOINT || MAXF == MAX_J, "the joint head has the wide form only");
   constexpr int NX = MAXF * TILE / (64 * NW);         // tile elements per thread
   constexpr bool TWO = O == 2;                        // a second logit
   constexpr bool BACKWARD = HEAD != HEAD_TARGET;
@@ -176,7 +207,7 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
   }
   if (tid < 4) b3s[tid] = tid < O ? a.b3[tid] : 0.0f;
 
-  // the tile's states: element e = tid + 512 i of the [row][Fp] image, NX per thread at most (16 x 64 / 512 = 2; joint: 16 x 128 / 512 = 4)
+  // the tile's states: element e = tid + 512 i of the [row][Fp] image, NX per thread at most (16 x 64 / 512 = 2; wide: 16 x 128 / 512 = 4)
   float xn[NX];
   auto load_x = [&](int64_t t) {
 #pragma unroll
@@ -491,9 +522,13 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_grad(GradArgs a) {
 bool net_fields_ok(const mdr_mlp_t* n) {
   return n && n->struct_size == sizeof(mdr_mlp_t) && n->num_state > 0 && n->hidden1 > 0 && n->hidden2 > 0 && n->num_out > 0;
 }
-bool net_covered(const mdr_mlp_t* n) {
-  return n->num_state <= MAX_F && n->hidden1 <= MAX_H && n->hidden2 <= MAX_H && (n->num_out == 1 || n->num_out == 2);
+// wide: the mdr_*_wide entry points (up to MAX_WIDE features)
+bool net_covered(const mdr_mlp_t* n, bool wide = false) {
+  return n->num_state <= (wide ? MAX_WIDE : MAX_F) && n->hidden1 <= MAX_H && n->hidden2 <= MAX_H && (n->num_out == 1 || n->num_out == 2);
 }
+// A wide entry point takes the wide instantiation and the aliased layout from the first width the narrow one does not cover; up to
+// MAX_F features it is its narrow sibling (every such shape fits un-aliased), so it returns that one's bits at that one's cost.
+bool wide_form(const mdr_mlp_t* n, bool wide) { return wide && n->num_state > MAX_F; }
 
 int64_t grid_for(int64_t nb_rows, int32_t max_workgroups, int cus) {
   const int64_t ntiles = (nb_rows + TILE - 1) / TILE;
@@ -516,12 +551,17 @@ void fill_rows(GradArgs& a, const mdr_mlp_t* net, const float* state, int64_t ld
   a.state = state, a.ld_state = ld_state, a.index = index, a.B = nb_rows, a.ntiles = (nb_rows + TILE - 1) / TILE;
 }
 
-int launch(Head head, const GradArgs& a, int grid, hipStream_t st) {
-  auto kernel = head == HEAD_ACTOR ? k_ppo_grad<HEAD_ACTOR>
-              : head == HEAD_CRITIC ? k_ppo_grad<HEAD_CRITIC>
-              : head == HEAD_TARGET ? k_ppo_grad<HEAD_TARGET>
-              : head == HEAD_JOINT  ? k_ppo_grad<HEAD_JOINT>
-                                    : k_ppo_grad<HEAD_HUBER>;
+// wide: the MAXF = 128 instantiation (HEAD_JOINT has no other)
+int launch(Head head, bool wide, const GradArgs& a, int grid, hipStream_t st) {
+  auto kernel = head == HEAD_JOINT ? k_ppo_grad<HEAD_JOINT, MAX_J>
+              : wide ? (head == HEAD_ACTOR    ? k_ppo_grad<HEAD_ACTOR, MAX_WIDE>
+                        : head == HEAD_CRITIC ? k_ppo_grad<HEAD_CRITIC, MAX_WIDE>
+                        : head == HEAD_TARGET ? k_ppo_grad<HEAD_TARGET, MAX_WIDE>
+                                              : k_ppo_grad<HEAD_HUBER, MAX_WIDE>)
+                     : (head == HEAD_ACTOR    ? k_ppo_grad<HEAD_ACTOR, MAX_F>
+                        : head == HEAD_CRITIC ? k_ppo_grad<HEAD_CRITIC, MAX_F>
+                        : head == HEAD_TARGET ? k_ppo_grad<HEAD_TARGET, MAX_F>
+                                              : k_ppo_grad<HEAD_HUBER, MAX_F>);
   const size_t lds_bytes = (size_t)a.s.lds * sizeof(float);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
     return MDR_ERR_HIP;
@@ -534,7 +574,7 @@ bool net_pointers_ok(const mdr_mlp_t* n) { return n->w1 && n->b1 && n->w2 && n->
 // the three heads with a backward: HEAD_ACTOR, HEAD_CRITIC, HEAD_HUBER (adv_in = y, grad_clamp > 0; 0 for the PPO heads: no clamp)
 int run(Head head, const mdr_mlp_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
         const int64_t* action, const float* old_prob, const float* adv_in, const float* target, float clip, float grad_clamp,
-        int32_t max_workgroups, void* workspace, float* grad, float* loss, float* out0, float* out1, void* stream) {
+        int32_t max_workgroups, void* workspace, float* grad, float* loss, float* out0, float* out1, void* stream, bool wide = false) {
   if (!net_fields_ok(net) || !state || !grad || !loss || !workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
   if (!net_pointers_ok(net)) return MDR_ERR_INVALID;
   if (head == HEAD_ACTOR ? (!action || !old_prob || !adv_in || !(clip >= 0.0f && clip < 1.0f))
@@ -542,9 +582,10 @@ int run(Head head, const mdr_mlp_t* net, const float* state, int64_t ld_state, c
                            : !target)
     return MDR_ERR_INVALID;
   if (nb_rows < 0 || ld_state < net->num_state || max_workgroups < 0) return MDR_ERR_INVALID;
-  if (!net_covered(net) || net->num_out != (head == HEAD_CRITIC ? 1 : 2)) return MDR_ERR_UNSUPPORTED;
+  if (!net_covered(net, wide) || net->num_out != (head == HEAD_CRITIC ? 1 : 2)) return MDR_ERR_UNSUPPORTED;
+  const bool wf = wide_form(net, wide);
   GradArgs a{};
-  a.s = make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out);
+  a.s = make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out, true, wf);
   if ((size_t)a.s.lds * sizeof(float) > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   int grid = 0;
@@ -554,7 +595,7 @@ int run(Head head, const mdr_mlp_t* net, const float* state, int64_t ld_state, c
     a.action = action, a.old_prob = old_prob, a.adv_in = adv_in, a.target = target;
     a.clip_lo = (float)(1.0 - (double)clip), a.clip_hi = (float)(1.0 + (double)clip);
     a.part = static_cast<float*>(workspace), a.out0 = out0, a.out1 = out1;
-    if (launch(head, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
+    if (launch(head, wf, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
   }
   const int n = a.s.G + 1;
   if (head == HEAD_HUBER)
@@ -566,14 +607,83 @@ int run(Head head, const mdr_mlp_t* net, const float* state, int64_t ld_state, c
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
+// the wide entry points' size queries: the net is covered and its backward layout fits
+bool wide_shape(const mdr_mlp_t* net, Shape* out) {
+  if (!net_fields_ok(net) || !net_covered(net, true)) return false;
+  *out = make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out, true, wide_form(net, true));
+  return (size_t)out->lds * sizeof(float) <= LDS_LIMIT;
+}
+
 // the joint critic's argument checks that need no device: MDR_OK, MDR_ERR_INVALID or MDR_ERR_UNSUPPORTED (the LDS fit included)
-int joint_shape(const mdr_mlp_t* critic, int32_t nb_agents, Shape* out) {
+// (alias: mdr_mappo_critic_grad_wide's layout, the same kernel)
+int joint_shape(const mdr_mlp_t* critic, int32_t nb_agents, Shape* out, bool alias = false) {
   if (!net_fields_ok(critic) || nb_agents < 1 || (int64_t)critic->num_state - (nb_agents - 1) < 1) return MDR_ERR_INVALID;
   if (critic->num_out != 1 || critic->num_state > MAX_J || critic->hidden1 > MAX_H || critic->hidden2 > MAX_H) return MDR_ERR_UNSUPPORTED;
-  const Shape s = make_shape(critic->num_state, critic->hidden1, critic->hidden2, 1);
+  const Shape s = make_shape(critic->num_state, critic->hidden1, critic->hidden2, 1, true, alias);
   if ((size_t)s.lds * sizeof(float) > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
   if (out) *out = s;
   return MDR_OK;
+}
+
+// the joint head behind both entry points; alias: the wide one's LDS layout
+int run_joint(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* action, int64_t nb_transitions,
+                     int32_t nb_agents, const int64_t* index, int64_t nb_rows, const float* target, int32_t max_workgroups, void* workspace,
+                     float* grad, float* loss, float* value, float* advantage, void* stream, bool alias) {
+  if (!net_fields_ok(critic) || !net_pointers_ok(critic) || !state || !action || !target || !grad || !loss || !workspace ||
+      ((uintptr_t)workspace & 15u))
+    return MDR_ERR_INVALID;
+  GradArgs a{};
+  const int rc = joint_shape(critic, nb_agents, &a.s, alias);
+  if (rc == MDR_ERR_INVALID) return rc;
+  const int F = critic->num_state - (nb_agents - 1);
+  if (ld_state < F || nb_transitions < 0 || nb_transitions % nb_agents != 0 || nb_rows < 0 || max_workgroups < 0) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  int grid = 0;
+  if (nb_rows > 0) {
+    grid = launch_grid(nb_rows, max_workgroups);
+    fill_rows(a, critic, state, ld_state, index, nb_rows);
+    a.action = action, a.target = target, a.Fs = F, a.N = nb_agents;
+    a.part = static_cast<float*>(workspace), a.out0 = value, a.out1 = advantage;
+    if (launch(HEAD_JOINT, true, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
+  }
+  const int n = a.s.G + 1;
+  hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), grid,
+                     a.s.stride, a.s.G, (float)nb_rows, grad, loss);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+// the TD target behind both entry points
+int run_target(const mdr_mlp_t* target_net, const mdr_mlp_t* policy_net, const float* next_state, int64_t ld_state,
+                      const int64_t* index, int64_t nb_rows, const float* reward, float gamma, int32_t max_workgroups, float* y,
+                      float* next_q, uint8_t* next_action, void* stream, bool wide) {
+  if (!net_fields_ok(target_net) || !net_pointers_ok(target_net) || !next_state || !reward || !y) return MDR_ERR_INVALID;
+  if (policy_net && (!net_fields_ok(policy_net) || !net_pointers_ok(policy_net) || !next_action)) return MDR_ERR_INVALID;
+  if (nb_rows < 0 || ld_state < target_net->num_state || max_workgroups < 0 || !(fabsf(gamma) <= FLT_MAX)) return MDR_ERR_INVALID;
+  if (!net_covered(target_net, wide) || target_net->num_out != 2) return MDR_ERR_UNSUPPORTED;
+  const bool wf = wide_form(target_net, wide);
+  if (policy_net && (policy_net->num_state != target_net->num_state || policy_net->hidden1 != target_net->hidden1 ||
+                     policy_net->hidden2 != target_net->hidden2 || policy_net->num_out != 2))
+    return MDR_ERR_UNSUPPORTED;
+  GradArgs a{};
+  a.s = make_shape(target_net->num_state, target_net->hidden1, target_net->hidden2, 2, false);
+  if ((size_t)a.s.lds * sizeof(float) > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
+  // the wide pair is accepted or refused together: a target for a network whose gradient call does not fit LDS serves no update
+  Shape fit;
+  if (wide && !wide_shape(target_net, &fit)) return MDR_ERR_UNSUPPORTED;
+  if (nb_rows == 0) return MDR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = launch_grid(nb_rows, max_workgroups);
+  if (policy_net) {      // DDQN (agents/dqn.py:129): the policy net's argmax on the next states first - the two weight sets do not share LDS
+    fill_rows(a, policy_net, next_state, ld_state, index, nb_rows);
+    a.amax = next_action;
+    if (launch(HEAD_TARGET, wf, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
+  }
+  fill_rows(a, target_net, next_state, ld_state, index, nb_rows);
+  a.target = reward, a.gamma = gamma, a.out0 = y, a.out1 = next_q;
+  a.pick = policy_net ? next_action : nullptr;
+  a.amax = policy_net ? nullptr : next_action;
+  return launch(HEAD_TARGET, wf, a, grid, st);
 }
 
 }  // namespace
@@ -590,6 +700,39 @@ int64_t mdr_mlp_grad_workspace_bytes(const mdr_mlp_t* net, int64_t nb_rows, int3
   const Shape s = make_shape(net->num_state, net->hidden1, net->hidden2, net->num_out);
   // max_workgroups == 0: room for the library's grid on any device (no device call here)
   return grid_for(nb_rows, max_workgroups, LIB_MAX_WG) * s.stride * (int64_t)sizeof(float);
+}
+
+// the wide entry points' sizes: the limits and the LDS fit of the calls with a backward (the TD target's image is smaller)
+int64_t mdr_mlp_wide_grad_floats(const mdr_mlp_t* net) {
+  Shape s;
+  return wide_shape(net, &s) ? s.G : -1;
+}
+
+int64_t mdr_mlp_wide_grad_workspace_bytes(const mdr_mlp_t* net, int64_t nb_rows, int32_t max_workgroups) {
+  Shape s;
+  if (!wide_shape(net, &s) || nb_rows < 0 || max_workgroups < 0) return -1;
+  return grid_for(nb_rows, max_workgroups, LIB_MAX_WG) * s.stride * (int64_t)sizeof(float);
+}
+
+int mdr_ppo_actor_grad_wide(const mdr_mlp_t* actor, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                            const int64_t* action, const float* old_prob, const float* advantage, float clip_param, int32_t max_workgroups,
+                            void* workspace, float* grad, float* loss, float* ratio, void* stream) {
+  return run(HEAD_ACTOR, actor, state, ld_state, index, nb_rows, action, old_prob, advantage, nullptr, clip_param, 0.0f, max_workgroups,
+             workspace, grad, loss, ratio, nullptr, stream, true);
+}
+
+int mdr_ppo_critic_grad_wide(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                             const float* target, int32_t max_workgroups, void* workspace, float* grad, float* loss, float* value,
+                             float* advantage, void* stream) {
+  return run(HEAD_CRITIC, critic, state, ld_state, index, nb_rows, nullptr, nullptr, nullptr, target, 0.0f, 0.0f, max_workgroups, workspace,
+             grad, loss, value, advantage, stream, true);
+}
+
+int mdr_dqn_grad_wide(const mdr_mlp_t* policy_net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                      const int64_t* action, const float* y, float grad_clamp, int32_t max_workgroups, void* workspace, float* grad,
+                      float* loss, float* q, void* stream) {
+  return run(HEAD_HUBER, policy_net, state, ld_state, index, nb_rows, action, nullptr, y, nullptr, 0.0f, grad_clamp, max_workgroups, workspace,
+             grad, loss, q, nullptr, stream, true);
 }
 
 int mdr_ppo_actor_grad(const mdr_mlp_t* actor, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
@@ -617,59 +760,43 @@ int64_t mdr_mappo_critic_workspace_bytes(const mdr_mlp_t* critic, int32_t nb_age
   return grid_for(nb_rows, max_workgroups, LIB_MAX_WG) * s.stride * (int64_t)sizeof(float);
 }
 
+int64_t mdr_mappo_critic_wide_grad_floats(const mdr_mlp_t* critic, int32_t nb_agents) {
+  Shape s;
+  return joint_shape(critic, nb_agents, &s, true) == MDR_OK ? s.G : -1;
+}
+
+int64_t mdr_mappo_critic_wide_workspace_bytes(const mdr_mlp_t* critic, int32_t nb_agents, int64_t nb_rows, int32_t max_workgroups) {
+  Shape s;
+  if (joint_shape(critic, nb_agents, &s, true) != MDR_OK || nb_rows < 0 || max_workgroups < 0) return -1;
+  return grid_for(nb_rows, max_workgroups, LIB_MAX_WG) * s.stride * (int64_t)sizeof(float);
+}
+
 int mdr_mappo_critic_grad(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* action, int64_t nb_transitions,
                           int32_t nb_agents, const int64_t* index, int64_t nb_rows, const float* target, int32_t max_workgroups,
                           void* workspace, float* grad, float* loss, float* value, float* advantage, void* stream) {
-  if (!net_fields_ok(critic) || !net_pointers_ok(critic) || !state || !action || !target || !grad || !loss || !workspace ||
-      ((uintptr_t)workspace & 15u))
-    return MDR_ERR_INVALID;
-  GradArgs a{};
-  const int rc = joint_shape(critic, nb_agents, &a.s);
-  if (rc == MDR_ERR_INVALID) return rc;
-  const int F = critic->num_state - (nb_agents - 1);
-  if (ld_state < F || nb_transitions < 0 || nb_transitions % nb_agents != 0 || nb_rows < 0 || max_workgroups < 0) return MDR_ERR_INVALID;
-  if (rc != MDR_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  int grid = 0;
-  if (nb_rows > 0) {
-    grid = launch_grid(nb_rows, max_workgroups);
-    fill_rows(a, critic, state, ld_state, index, nb_rows);
-    a.action = action, a.target = target, a.Fs = F, a.N = nb_agents;
-    a.part = static_cast<float*>(workspace), a.out0 = value, a.out1 = advantage;
-    if (launch(HEAD_JOINT, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
-  }
-  const int n = a.s.G + 1;
-  hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), grid,
-                     a.s.stride, a.s.G, (float)nb_rows, grad, loss);
-  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+  return run_joint(critic, state, ld_state, action, nb_transitions, nb_agents, index, nb_rows, target, max_workgroups, workspace, grad, loss,
+                   value, advantage, stream, false);
+}
+
+int mdr_mappo_critic_grad_wide(const mdr_mlp_t* critic, const float* state, int64_t ld_state, const int64_t* action, int64_t nb_transitions,
+                               int32_t nb_agents, const int64_t* index, int64_t nb_rows, const float* target, int32_t max_workgroups,
+                               void* workspace, float* grad, float* loss, float* value, float* advantage, void* stream) {
+  return run_joint(critic, state, ld_state, action, nb_transitions, nb_agents, index, nb_rows, target, max_workgroups, workspace, grad, loss,
+                   value, advantage, stream, true);
 }
 
 int mdr_dqn_target(const mdr_mlp_t* target_net, const mdr_mlp_t* policy_net, const float* next_state, int64_t ld_state,
                    const int64_t* index, int64_t nb_rows, const float* reward, float gamma, int32_t max_workgroups, float* y, float* next_q,
                    uint8_t* next_action, void* stream) {
-  if (!net_fields_ok(target_net) || !net_pointers_ok(target_net) || !next_state || !reward || !y) return MDR_ERR_INVALID;
-  if (policy_net && (!net_fields_ok(policy_net) || !net_pointers_ok(policy_net) || !next_action)) return MDR_ERR_INVALID;
-  if (nb_rows < 0 || ld_state < target_net->num_state || max_workgroups < 0 || !(fabsf(gamma) <= FLT_MAX)) return MDR_ERR_INVALID;
-  if (!net_covered(target_net) || target_net->num_out != 2) return MDR_ERR_UNSUPPORTED;
-  if (policy_net && (policy_net->num_state != target_net->num_state || policy_net->hidden1 != target_net->hidden1 ||
-                     policy_net->hidden2 != target_net->hidden2 || policy_net->num_out != 2))
-    return MDR_ERR_UNSUPPORTED;
-  GradArgs a{};
-  a.s = make_shape(target_net->num_state, target_net->hidden1, target_net->hidden2, 2, false);
-  if ((size_t)a.s.lds * sizeof(float) > LDS_LIMIT) return MDR_ERR_UNSUPPORTED;
-  if (nb_rows == 0) return MDR_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = launch_grid(nb_rows, max_workgroups);
-  if (policy_net) {      // DDQN (agents/dqn.py:129): the policy net's argmax on the next states first - the two weight sets do not share LDS
-    fill_rows(a, policy_net, next_state, ld_state, index, nb_rows);
-    a.amax = next_action;
-    if (launch(HEAD_TARGET, a, grid, st) != MDR_OK) return MDR_ERR_HIP;
-  }
-  fill_rows(a, target_net, next_state, ld_state, index, nb_rows);
-  a.target = reward, a.gamma = gamma, a.out0 = y, a.out1 = next_q;
-  a.pick = policy_net ? next_action : nullptr;
-  a.amax = policy_net ? nullptr : next_action;
-  return launch(HEAD_TARGET, a, grid, st);
+  return run_target(target_net, policy_net, next_state, ld_state, index, nb_rows, reward, gamma, max_workgroups, y, next_q, next_action, stream,
+                    false);
+}
+
+int mdr_dqn_target_wide(const mdr_mlp_t* target_net, const mdr_mlp_t* policy_net, const float* next_state, int64_t ld_state,
+                        const int64_t* index, int64_t nb_rows, const float* reward, float gamma, int32_t max_workgroups, float* y,
+                        float* next_q, uint8_t* next_action, void* stream) {
+  return run_target(target_net, policy_net, next_state, ld_state, index, nb_rows, reward, gamma, max_workgroups, y, next_q, next_action, stream,
+                    true);
 }
 
 int mdr_dqn_grad(const mdr_mlp_t* policy_net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,

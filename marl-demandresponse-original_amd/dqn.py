@@ -28,10 +28,12 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from .optim import FusedAdam
-from .ppo import _check_rows, _desc, _flat_grad, _publish, _refusal, _whole, _workspace
+from .ppo import _WIDE, _check_rows, _desc, _flat_grad, _fn, _publish, _refusal, _whole, _workspace
 
 # backend="auto": the kernels from this many minibatch rows on (profiles/dqn_update_README.md: where they measured faster than autograd)
 AUTO_MIN_ROWS = 1
+# the same for wide=True, 65..128 input features (profiles/wide_update_README.md)
+AUTO_MIN_ROWS_WIDE = 1
 
 
 class QNetworkMLP(nn.Module):
@@ -51,10 +53,10 @@ class QNetworkMLP(nn.Module):
         return self.fc[-1](x)
 
 
-def supported(net) -> bool:
+def supported(net, wide: bool = False) -> bool:
     """Do the kernels take this Q-network?  Two hidden layers, F <= 64 input features, at most 128 hidden units, 2 actions, float32
-    on the GPU."""
-    return _refusal(net, 2) is None
+    on the GPU.  ``wide=True``: the wide entry points, F <= 128 where the LDS layout fits (hidden 100-100: every F; 128-128: F <= 100)."""
+    return _refusal(net, 2, wide=wide) is None
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -62,16 +64,16 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 def td_target(target_net, next_state: torch.Tensor, reward: torch.Tensor, gamma: float, index: Optional[torch.Tensor] = None,
-              policy_net=None, max_workgroups: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+              policy_net=None, max_workgroups: int = 0, wide: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``expected_q_values`` of agents/dqn.py:96-99 in one forward-only kernel -> (y, next_q - both float32 [B] -, next_action uint8 [B]).
     ``next_state`` float32 [M, F] (any row stride >= F) and ``reward`` float32 [M] are the replay buffer, read in place through
     ``index`` (int64 [B] on the device; None: every row in order, B = M).  ``policy_net`` None: DQN, next_q = max_a Q_target(s', a) and
     next_action the target net's own argmax; a network: DDQN, next_action = argmax_a Q_policy(s', a) (a second launch) and
     next_q = Q_target(s', next_action) - the per-row target, not the [B, B, 1] broadcast of agents/dqn.py:132-135 (module docstring).
-    y = reward + gamma * next_q.  Nothing here is differentiated."""
+    y = reward + gamma * next_q.  Nothing here is differentiated.  ``wide=True``: up to 128 input features."""
     what = "td_target"
     for net in (target_net,) + ((policy_net,) if policy_net is not None else ()):
-        why = _refusal(net, 2)
+        why = _refusal(net, 2, wide=wide)
         if why:
             raise ValueError("%s: %s" % (what, why))
     dev, M, ld, B = _check_rows(target_net, next_state, index, what)
@@ -83,22 +85,22 @@ def td_target(target_net, next_state: torch.Tensor, reward: torch.Tensor, gamma:
     next_q = torch.empty(B, dtype=torch.float32, device=dev)
     next_action = torch.empty(B, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.mdr_dqn_target(C.byref(tdesc), C.byref(pdesc) if pdesc is not None else None, _ptr(next_state), ld, _ptr(index), B,
-                                _ptr(reward), C.c_float(gamma), max_workgroups, _ptr(y), _ptr(next_q), _ptr(next_action),
-                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, "mdr_dqn_target")
+        rc = _fn(lib, "mdr_dqn_target", wide)(C.byref(tdesc), C.byref(pdesc) if pdesc is not None else None, _ptr(next_state), ld, _ptr(index), B,
+                                              _ptr(reward), C.c_float(gamma), max_workgroups, _ptr(y), _ptr(next_q), _ptr(next_action),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, _WIDE["mdr_dqn_target"] if wide else "mdr_dqn_target")
     return y, next_q, next_action
 
 
 def q_loss_backward(policy_net, state: torch.Tensor, action: torch.Tensor, y: torch.Tensor, index: Optional[torch.Tensor] = None,
-                    grad_clamp: float = 1.0, want_q: bool = False, max_workgroups: int = 0):
+                    grad_clamp: float = 1.0, want_q: bool = False, max_workgroups: int = 0, wide: bool = False):
     """``nn.SmoothL1Loss()(Q(s, a), y)``, ``backward()`` and ``param.grad.data.clamp_(-grad_clamp, grad_clamp)`` of agents/dqn.py:93,
     102-109 in one kernel and its reduction: fills ``p.grad`` of the six parameters of ``policy_net`` (allocated where None, overwritten
     otherwise) and returns the loss (0-dim device tensor) [and Q(s, a), float32 [B]].  ``state`` float32 [M, F] and ``action`` int64 [M]
     are the replay buffer, read in place through ``index``; ``y`` float32 [B] (``td_target``'s) in minibatch order.
-    ``grad_clamp=float("inf")``: no clamp."""
+    ``grad_clamp=float("inf")``: no clamp.  ``wide=True``: up to 128 input features."""
     what = "q_loss_backward"
-    why = _refusal(policy_net, 2)
+    why = _refusal(policy_net, 2, wide=wide)
     if why:
         raise ValueError("%s: %s" % (what, why))
     dev, M, ld, B = _check_rows(policy_net, state, index, what)
@@ -108,14 +110,15 @@ def q_loss_backward(policy_net, state: torch.Tensor, action: torch.Tensor, y: to
         raise ValueError("%s: grad_clamp must be positive (inf: no clamp)" % what)
     lib = nat.load()
     desc = _desc(policy_net)
-    flat = _flat_grad(policy_net, lib, desc)
-    ws = _workspace(dev, int(lib.mdr_mlp_grad_workspace_bytes(C.byref(desc), B, max_workgroups)))
+    flat = _flat_grad(policy_net, lib, desc, wide=wide)
+    ws = _workspace(dev, int(_fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(desc), B, max_workgroups)))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_dqn_grad(C.byref(desc), _ptr(state), ld, _ptr(index), B, _ptr(action), _ptr(y), C.c_float(grad_clamp), max_workgroups,
-                              _ptr(ws), _ptr(flat), _ptr(loss), _ptr(q), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, "mdr_dqn_grad")
+        rc = _fn(lib, "mdr_dqn_grad", wide)(C.byref(desc), _ptr(state), ld, _ptr(index), B, _ptr(action), _ptr(y), C.c_float(grad_clamp),
+                                            max_workgroups, _ptr(ws), _ptr(flat), _ptr(loss), _ptr(q),
+                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, _WIDE["mdr_dqn_grad"] if wide else "mdr_dqn_grad")
     _publish(policy_net, flat)
     return (loss, q) if want_q else loss
 
@@ -187,17 +190,20 @@ class DQNLearner:
     the kernels (ValueError for networks they refuse); ``"torch"``: the reference's expressions under autograd with
     ``p.grad.clamp_(-1, 1)`` - the comparator and the fallback; ``"auto"``: the kernels where ``supported()`` holds and the minibatch
     has at least ``AUTO_MIN_ROWS`` rows, torch otherwise.  The optimiser step and the target blend are torch on every backend unless
-    ``optimizer=mdr_amd.optim.FusedAdam``: then, with ``soft_update``, both are one ``FusedAdam.step(target=..., tau=...)``."""
+    ``optimizer=mdr_amd.optim.FusedAdam``: then, with ``soft_update``, both are one ``FusedAdam.step(target=..., tau=...)``.
+    ``wide=True``: the wide entry points, so a Q-network of up to 128 input features (both message flags on: 121) takes the kernels,
+    eager or ``graph=True``; ``"auto"`` then takes them from ``AUTO_MIN_ROWS_WIDE`` minibatch rows on."""
 
     GRAD_CLAMP = 1.0      # agents/dqn.py:108-109
 
     def __init__(self, policy_net, lr: float, gamma: float = 0.99, tau: float = 0.01, buffer_capacity: int = 524288, batch_size: int = 256,
                  double: bool = False, backend: str = "auto", optimizer=torch.optim.Adam, soft_update: bool = True,
-                 sampler: Optional[str] = None, graph: bool = False):
+                 sampler: Optional[str] = None, graph: bool = False, wide: bool = False):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        self.wide = bool(wide)
         if backend == "hip":
-            why = _refusal(policy_net, 2)
+            why = _refusal(policy_net, 2, wide=self.wide)
             if why:
                 raise ValueError("DQNLearner(backend='hip'): " + why)
         fc = getattr(policy_net, "fc", None)
@@ -238,15 +244,16 @@ class DQNLearner:
 
     @classmethod
     def from_config(cls, dqn_prop: dict, policy_net, double: bool = False, backend: str = "auto", optimizer=torch.optim.Adam,
-                    soft_update: bool = True, sampler: Optional[str] = None, graph: bool = False) -> "DQNLearner":
+                    soft_update: bool = True, sampler: Optional[str] = None, graph: bool = False, wide: bool = False) -> "DQNLearner":
         """From the reference's ``config_dict["DQN_prop"]`` (agents/dqn.py:23-29)."""
         return cls(policy_net, dqn_prop["lr"], gamma=dqn_prop["gamma"], tau=dqn_prop["tau"], buffer_capacity=dqn_prop["buffer_capacity"],
                    batch_size=dqn_prop["batch_size"], double=double, backend=backend, optimizer=optimizer, soft_update=soft_update,
-                   sampler=sampler, graph=graph)
+                   sampler=sampler, graph=graph, wide=wide)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
-            return _refusal(self.policy_net, 2) is None and _refusal(self.target_net, 2) is None and nb_rows >= AUTO_MIN_ROWS
+            return (_refusal(self.policy_net, 2, wide=self.wide) is None and _refusal(self.target_net, 2, wide=self.wide) is None
+                    and nb_rows >= (AUTO_MIN_ROWS_WIDE if self.wide else AUTO_MIN_ROWS))
         return self.backend == "hip"
 
     def store(self, batch: Dict[str, torch.Tensor]) -> None:
@@ -285,8 +292,8 @@ class DQNLearner:
         buf = self.buffer
         if self.uses_kernels(int(index.shape[0])):
             y, _, _ = td_target(self.target_net, buf.next_state, buf.reward, self.gamma, index=index,
-                                policy_net=self.policy_net if self.double else None)
-            return q_loss_backward(self.policy_net, buf.state, buf.action, y, index=index, grad_clamp=self.GRAD_CLAMP)
+                                policy_net=self.policy_net if self.double else None, wide=self.wide)
+            return q_loss_backward(self.policy_net, buf.state, buf.action, y, index=index, grad_clamp=self.GRAD_CLAMP, wide=self.wide)
         state, action, reward, next_state = buf.state[index], buf.action[index].view(-1, 1), buf.reward[index].view(-1, 1), buf.next_state[index]
         q_values = self.policy_net(state).gather(1, action)
         with torch.no_grad():

@@ -229,11 +229,13 @@ class PPOUpdateGraph:
         self.adv = torch.zeros(self.bs, dtype=torch.float32, device=dev)
         self.a_desc, self.c_desc = ppo._desc(learner.actor), ppo._desc(learner.critic)
         rows = sorted({min(self.bs, n), n - (self.m - 1) * self.bs})
+        self.wide = wide = bool(getattr(learner, "wide", False))      # the learner's wide=True: the wide entry points, the same argument lists
         nbytes = 16
         for B in rows:
-            nbytes = max(nbytes, int(lib.mdr_mlp_grad_workspace_bytes(C.byref(self.a_desc), B, 0)), learner._critic_workspace_bytes(lib, self.c_desc, B))
+            nbytes = max(nbytes, int(ppo._fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(self.a_desc), B, 0)),
+                         learner._critic_workspace_bytes(lib, self.c_desc, B))
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # the graph's own: ppo._workspace may be reallocated
-        self.a_flat = ppo._flat_grad(learner.actor, lib, self.a_desc)
+        self.a_flat = ppo._flat_grad(learner.actor, lib, self.a_desc, wide=wide)
         self.c_flat = ppo._flat_grad(learner.critic, lib, self.c_desc, floats=learner._critic_grad_floats(lib, self.c_desc))
         _bind_grads(learner.actor, self.a_flat, ppo._params(learner.actor))
         _bind_grads(learner.critic, self.c_flat, ppo._params(learner.critic))
@@ -244,7 +246,9 @@ class PPOUpdateGraph:
 
     def _record(self) -> None:
         """The launches of one epoch on the current stream, from the static buffers alone."""
+        from . import ppo
         L, lib, dev = self.learner, self.lib, self.dev
+        actor_grad = ppo._fn(lib, "mdr_ppo_actor_grad", self.wide)
         st = _stream(dev)
         ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
         key = self.block[self.KEY:]
@@ -256,8 +260,8 @@ class PPOUpdateGraph:
                 rc = L._critic_launch(lib, self.c_desc, ptr(self.state), self.F, ptr(self.action), self.n, ptr(self.ret), index, B, ptr(self.workspace),
                                       ptr(self.c_flat), ptr(self.c_loss), ptr(self.value), ptr(self.adv), st)
                 nat.check(lib, None, rc, "critic gradient")
-                rc = lib.mdr_ppo_actor_grad(C.byref(self.a_desc), ptr(self.state), self.F, index, B, ptr(self.action), ptr(self.a_prob), ptr(self.adv),
-                                            C.c_float(L.clip_param), 0, ptr(self.workspace), ptr(self.a_flat), ptr(self.a_loss), None, st)
+                rc = actor_grad(C.byref(self.a_desc), ptr(self.state), self.F, index, B, ptr(self.action), ptr(self.a_prob), ptr(self.adv),
+                                C.c_float(L.clip_param), 0, ptr(self.workspace), ptr(self.a_flat), ptr(self.a_loss), None, st)
                 nat.check(lib, None, rc, "mdr_ppo_actor_grad")
                 L.actor_optimizer.step(max_grad_norm=L.max_grad_norm, corrections=self.a_table, slot=j, base_dev=self.block[self.BASE:self.BASE + 1])
                 L.critic_optimizer.step(max_grad_norm=L.max_grad_norm, corrections=self.c_table, slot=j, base_dev=self.block[self.BASE:self.BASE + 1])
@@ -335,8 +339,10 @@ class DQNUpdateGraph:
         self.next_action = torch.zeros(self.bs, dtype=torch.uint8, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.p_desc, self.t_desc = ppo._desc(learner.policy_net), ppo._desc(learner.target_net)
-        self.workspace = torch.empty(max(int(lib.mdr_mlp_grad_workspace_bytes(C.byref(self.p_desc), self.bs, 0)), 16), dtype=torch.uint8, device=dev)
-        self.flat = ppo._flat_grad(learner.policy_net, lib, self.p_desc)
+        self.wide = wide = bool(getattr(learner, "wide", False))      # the learner's wide=True: the wide entry points, the same argument lists
+        self.workspace = torch.empty(max(int(ppo._fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(self.p_desc), self.bs, 0)), 16),
+                                     dtype=torch.uint8, device=dev)
+        self.flat = ppo._flat_grad(learner.policy_net, lib, self.p_desc, wide=wide)
         _bind_grads(learner.policy_net, self.flat, ppo._params(learner.policy_net))
         opt = learner.optimizer
         held = list(learner.policy_net.parameters()) + list(learner.target_net.parameters()) + [opt._exp_avg, opt._exp_avg_sq]
@@ -345,17 +351,19 @@ class DQNUpdateGraph:
         self.signature = _signature((learner.policy_net, learner.target_net))
 
     def _record(self) -> None:
+        from . import ppo
         L, lib, dev, buf = self.learner, self.lib, self.dev, self.learner.buffer
+        dqn_target, dqn_grad = ppo._fn(lib, "mdr_dqn_target", self.wide), ppo._fn(lib, "mdr_dqn_grad", self.wide)
         st = _stream(dev)
         ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
         with torch.cuda.device(dev):
             sample(self.bs, self.block[self.LEN:self.LEN + 2].view(torch.int64), 0, 0, dev, out=self.index, cursor=self.block[self.STEP:],
                    key=self.block[self.KEY:])
-            rc = lib.mdr_dqn_target(C.byref(self.t_desc), C.byref(self.p_desc) if L.double else None, ptr(buf.next_state), buf.num_state, ptr(self.index),
-                                    self.bs, ptr(buf.reward), C.c_float(L.gamma), 0, ptr(self.y), ptr(self.next_q), ptr(self.next_action), st)
+            rc = dqn_target(C.byref(self.t_desc), C.byref(self.p_desc) if L.double else None, ptr(buf.next_state), buf.num_state, ptr(self.index),
+                            self.bs, ptr(buf.reward), C.c_float(L.gamma), 0, ptr(self.y), ptr(self.next_q), ptr(self.next_action), st)
             nat.check(lib, None, rc, "mdr_dqn_target")
-            rc = lib.mdr_dqn_grad(C.byref(self.p_desc), ptr(buf.state), buf.num_state, ptr(self.index), self.bs, ptr(buf.action), ptr(self.y),
-                                  C.c_float(L.GRAD_CLAMP), 0, ptr(self.workspace), ptr(self.flat), ptr(self.loss), None, st)
+            rc = dqn_grad(C.byref(self.p_desc), ptr(buf.state), buf.num_state, ptr(self.index), self.bs, ptr(buf.action), ptr(self.y),
+                          C.c_float(L.GRAD_CLAMP), 0, ptr(self.workspace), ptr(self.flat), ptr(self.loss), None, st)
             nat.check(lib, None, rc, "mdr_dqn_grad")
             if L.soft_update:
                 L.optimizer.step(target=L._fused_target, tau=L.tau, corrections=self.table, slot=0)

@@ -22,10 +22,13 @@ MAX_JOINT, MAX_HIDDEN = 128, ppo.MAX_HIDDEN      # the joint head's limits (incl
 # backend="auto": the kernels from this many minibatch rows on (profiles/mappo_update_README.md: where they measured faster than the
 # torch backend)
 AUTO_MIN_ROWS = 1
+# the same for wide=True (profiles/wide_update_README.md)
+AUTO_MIN_ROWS_WIDE = 1
 
 
-def _joint_refusal(critic, num_state: int) -> Optional[str]:
-    """Why the joint-input kernel does not take ``critic`` over states of ``num_state`` features (None: it does)."""
+def _joint_refusal(critic, num_state: int, wide: bool = False) -> Optional[str]:
+    """Why the joint-input kernel does not take ``critic`` over states of ``num_state`` features (None: it does).  ``wide``: the
+    LDS fit of mdr_mappo_critic_grad_wide's layout; the 128 joint inputs are the limit of both."""
     why = ppo._refusal(critic, 1, max_state=MAX_JOINT)
     if why:
         return why
@@ -33,17 +36,19 @@ def _joint_refusal(critic, num_state: int) -> Optional[str]:
     nb_agents = J - int(num_state) + 1
     if num_state < 1 or nb_agents < 1:
         return "a critic of %d inputs over states of %d features leaves no whole number of other agents" % (J, num_state)
-    if nat.load().mdr_mappo_critic_grad_floats(C.byref(ppo._desc(critic)), nb_agents) < 0:
+    if ppo._fn(nat.load(), "mdr_mappo_critic_grad_floats", wide)(C.byref(ppo._desc(critic)), nb_agents) < 0:
         return ("%d joint inputs with hidden layers of %d and %d units do not fit the kernel's LDS layout"
                 % (J, critic.fc[0].out_features, critic.fc[1].out_features))
     return None
 
 
-def supported(critic, num_state: int) -> bool:
+def supported(critic, num_state: int, wide: bool = False) -> bool:
     """Does the joint-input kernel take this critic over states of ``num_state`` features?  A ``CriticMLP(num_state + N - 1)`` of two
     hidden layers with at most 128 joint inputs, hidden layers of at most 128 units and an LDS layout that fits (hidden 100-100: up
-    to 100 inputs; 128-128: up to 68; 64-64: 128), float32 on the GPU."""
-    return _joint_refusal(critic, num_state) is None
+    to 100 inputs; 128-128: up to 68; 64-64: 128), float32 on the GPU.  ``wide=True``: the wide entry point, whose layout fits hidden
+    100-100 up to 128 inputs and 128-128 up to 100.  More than 128 joint inputs stay refused either way: states of 121 features (both
+    message flags on) leave room for 8 agents, and the reference's 20 agents make 140 inputs."""
+    return _joint_refusal(critic, num_state, wide=wide) is None
 
 
 def gather_others(action: torch.Tensor, nb_agents: int, index: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -58,12 +63,14 @@ def gather_others(action: torch.Tensor, nb_agents: int, index: Optional[torch.Te
 
 
 def joint_critic_loss_backward(critic, state: torch.Tensor, action: torch.Tensor, target: torch.Tensor, nb_agents: Optional[int] = None,
-                               index: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                               index: Optional[torch.Tensor] = None, max_workgroups: int = 0,
+                               wide: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """F.mse_loss(Gt, V) of agents/mappo.py:85-88, 113 with V = critic(cat(state, others_actions)) and ``backward()`` in one kernel:
     fills ``p.grad`` of ``critic`` and returns (loss 0-dim, value float32 [B], advantage float32 [B] = target - value, detached).
     ``state`` float32 [M, F] (any row stride >= F), ``action`` int64 [M], ``target`` float32 [M]: the transition buffer in
     ``collect_ppo_rollout``'s flat order (M a multiple of ``nb_agents``, default ``critic.fc[0].in_features - F + 1``), read in place
-    through ``index`` (int64 [B] on the device; None: every row in order).  The others' actions are gathered from ``action``."""
+    through ``index`` (int64 [B] on the device; None: every row in order).  The others' actions are gathered from ``action``.
+    ``wide=True``: the wide entry point's LDS fit (``supported(critic, F, wide=True)``); more than 128 joint inputs stay refused."""
     what = "joint_critic_loss_backward"
     if state.dim() != 2:
         raise ValueError("%s: state must be a float32 [M, F] tensor" % what)
@@ -71,7 +78,7 @@ def joint_critic_loss_backward(critic, state: torch.Tensor, action: torch.Tensor
     fc = ppo._layers(critic)
     if nb_agents is None and fc is not None:
         nb_agents = fc[0].in_features - F_len + 1
-    why = _joint_refusal(critic, F_len)
+    why = _joint_refusal(critic, F_len, wide=wide)
     if why:
         raise ValueError("%s: %s" % (what, why))
     if int(nb_agents) != fc[0].in_features - F_len + 1:
@@ -85,18 +92,18 @@ def joint_critic_loss_backward(critic, state: torch.Tensor, action: torch.Tensor
     ppo._whole(target, torch.float32, M, dev, what, "target")
     lib = nat.load()
     desc = ppo._desc(critic)
-    flat = ppo._flat_grad(critic, lib, desc, floats=lib.mdr_mappo_critic_grad_floats(C.byref(desc), N))
-    ws = ppo._workspace(dev, int(lib.mdr_mappo_critic_workspace_bytes(C.byref(desc), N, B, max_workgroups)))
+    flat = ppo._flat_grad(critic, lib, desc, floats=ppo._fn(lib, "mdr_mappo_critic_grad_floats", wide)(C.byref(desc), N))
+    ws = ppo._workspace(dev, int(ppo._fn(lib, "mdr_mappo_critic_workspace_bytes", wide)(C.byref(desc), N, B, max_workgroups)))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     value = torch.empty(B, dtype=torch.float32, device=dev)
     adv = torch.empty(B, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.mdr_mappo_critic_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(action.data_ptr()), M, N,
-                                       C.c_void_p(index.data_ptr()) if index is not None else None, B, C.c_void_p(target.data_ptr()),
-                                       max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
-                                       C.c_void_p(value.data_ptr()), C.c_void_p(adv.data_ptr()),
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, "mdr_mappo_critic_grad")
+        rc = ppo._fn(lib, "mdr_mappo_critic_grad", wide)(
+            C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(action.data_ptr()), M, N,
+            C.c_void_p(index.data_ptr()) if index is not None else None, B, C.c_void_p(target.data_ptr()),
+            max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
+            C.c_void_p(value.data_ptr()), C.c_void_p(adv.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, ppo._WIDE["mdr_mappo_critic_grad"] if wide else "mdr_mappo_critic_grad")
     ppo._publish(critic, flat)
     return loss, value, adv
 
@@ -107,11 +114,13 @@ class MAPPOLearner(PPOLearner):
     The critic is ``CriticMLP(F + nb_agents - 1)``: the number of agents comes from its width.  ``backend="hip"``: the joint critic
     kernel, then ``ppo.actor_loss_backward`` with its advantage (ValueError for networks they refuse); ``"torch"``: the reference's
     expressions under autograd on ``torch.cat((state[index], others[index].float()), 1)`` - the comparator and the fallback;
-    ``"auto"``: the kernels where they take both networks and the minibatch has at least ``AUTO_MIN_ROWS`` rows."""
+    ``"auto"``: the kernels where they take both networks and the minibatch has at least ``AUTO_MIN_ROWS`` rows.  ``wide=True``:
+    the wide entry points for both networks - states of up to 128 features and a joint input of up to 128 (F = 121 with at most 8
+    agents; F = 121 with 20 agents is 140 inputs and stays refused); ``"auto"`` then counts from ``AUTO_MIN_ROWS_WIDE`` rows."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
                  ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
-                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024):
+                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError("backend must be 'auto', 'hip' or 'torch'")
         afc, cfc = ppo._layers(actor), ppo._layers(critic)
@@ -122,42 +131,44 @@ class MAPPOLearner(PPOLearner):
         if self.nb_agents < 1:
             raise ValueError("MAPPOLearner: the critic takes num_state + nb_agents - 1 = %d + N - 1 inputs, not %d" % (self.num_state, cfc[0].in_features))
         if backend == "hip":
-            why = ppo._refusal(actor, 2) or _joint_refusal(critic, self.num_state)
+            why = ppo._refusal(actor, 2, wide=wide) or _joint_refusal(critic, self.num_state, wide=wide)
             if why:
                 raise ValueError("MAPPOLearner(backend='hip'): " + why)
         # the base class checks PPO's critic (over the state alone) for "hip": this one's is checked above
         super().__init__(actor, critic, lr_actor, lr_critic, clip_param=clip_param, max_grad_norm=max_grad_norm, ppo_update_time=ppo_update_time,
                          batch_size=batch_size, backend="auto" if backend == "hip" else backend, optimizer=optimizer, sampler=sampler, graph=graph,
-                         graph_max_minibatches=graph_max_minibatches)
+                         graph_max_minibatches=graph_max_minibatches, wide=wide)
         self.backend = backend
         self._others = None      # the batch's others_actions [M, N - 1] during an update of the torch backend, where it has them
 
     @classmethod
     def from_config(cls, mappo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam, sampler: Optional[str] = None,
-                    graph: bool = False, graph_max_minibatches: int = 1024) -> "MAPPOLearner":
+                    graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False) -> "MAPPOLearner":
         """From the reference's ``config_dict["MAPPO_prop"]`` (agents/mappo.py:23-29)."""
         return cls(actor, critic, mappo_prop["lr_actor"], mappo_prop["lr_critic"], clip_param=mappo_prop["clip_param"],
                    max_grad_norm=mappo_prop["max_grad_norm"], ppo_update_time=mappo_prop["ppo_update_time"],
                    batch_size=mappo_prop["batch_size"], backend=backend, optimizer=optimizer, sampler=sampler, graph=graph,
-                   graph_max_minibatches=graph_max_minibatches)
+                   graph_max_minibatches=graph_max_minibatches, wide=wide)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
-            return ppo._refusal(self.actor, 2) is None and _joint_refusal(self.critic, self.num_state) is None and nb_rows >= AUTO_MIN_ROWS
+            wide = getattr(self, "wide", False)
+            return (ppo._refusal(self.actor, 2, wide=wide) is None and _joint_refusal(self.critic, self.num_state, wide=wide) is None
+                    and nb_rows >= (AUTO_MIN_ROWS_WIDE if wide else AUTO_MIN_ROWS))
         return self.backend == "hip"
 
     def critic_backward(self, state, action, target, index):
-        return joint_critic_loss_backward(self.critic, state, action, target, nb_agents=self.nb_agents, index=index)
+        return joint_critic_loss_backward(self.critic, state, action, target, nb_agents=self.nb_agents, index=index, wide=self.wide)
 
     def _critic_grad_floats(self, lib, desc) -> int:
-        return int(lib.mdr_mappo_critic_grad_floats(C.byref(desc), self.nb_agents))
+        return int(ppo._fn(lib, "mdr_mappo_critic_grad_floats", self.wide)(C.byref(desc), self.nb_agents))
 
     def _critic_workspace_bytes(self, lib, desc, nb_rows: int) -> int:
-        return int(lib.mdr_mappo_critic_workspace_bytes(C.byref(desc), self.nb_agents, nb_rows, 0))
+        return int(ppo._fn(lib, "mdr_mappo_critic_workspace_bytes", self.wide)(C.byref(desc), self.nb_agents, nb_rows, 0))
 
     def _critic_launch(self, lib, desc, state, ld, action, nb_transitions, target, index, nb_rows, workspace, grad, loss, value, adv, stream) -> int:
-        return lib.mdr_mappo_critic_grad(C.byref(desc), state, ld, action, nb_transitions, self.nb_agents, index, nb_rows, target, 0, workspace, grad,
-                                         loss, value, adv, stream)
+        return ppo._fn(lib, "mdr_mappo_critic_grad", self.wide)(C.byref(desc), state, ld, action, nb_transitions, self.nb_agents, index, nb_rows,
+                                                                target, 0, workspace, grad, loss, value, adv, stream)
 
     def critic_input(self, state, action, index) -> torch.Tensor:
         """agents/mappo.py:87: torch.cat((state[index], others_actions[index]), dim=1)."""

@@ -5,7 +5,8 @@ leaves on the device.  Per minibatch the reference evaluates critic and actor, f
 ``backward()`` twice, clips both gradients and takes two Adam steps.  Here forward, loss and backward of one network are ONE HIP
 kernel on the matrix cores in exact fp32 (plus a small reduction): ``critic_loss_backward`` / ``actor_loss_backward`` fill the
 ``.grad`` of an ``ActorMLP`` / ``CriticMLP``, torch keeps the gradient clipping and the optimiser (``optimizer=FusedAdam``, optim.py: one launch for both).  ``PPOLearner`` is the loop.
-Nothing on the call path synchronises with the host.
+Nothing on the call path synchronises with the host.  Networks of 65..128 input features - observations with message columns -
+take the same kernels' wide instantiations with ``wide=True`` (mdr_ppo_actor_grad_wide, mdr_ppo_critic_grad_wide).
 """
 from __future__ import annotations
 
@@ -22,6 +23,20 @@ from .optim import FusedAdam
 MAX_STATE, MAX_HIDDEN = 64, 128      # the kernels' limits (include/mdr_policy.h: mdr_mlp_t)
 # backend="auto": the kernels from this many minibatch rows on (profiles/ppo_update_README.md: where they measured faster than autograd)
 AUTO_MIN_ROWS = 1
+# wide=True: 65..128 input features (the observations with message columns) through the mdr_*_wide entry points, which have the
+# narrow ones' argument lists.  Their backend="auto" threshold is measured on its own (profiles/wide_update_README.md).
+MAX_STATE_WIDE = 128
+AUTO_MIN_ROWS_WIDE = 1
+_WIDE = {"mdr_mlp_grad_floats": "mdr_mlp_wide_grad_floats", "mdr_mlp_grad_workspace_bytes": "mdr_mlp_wide_grad_workspace_bytes",
+         "mdr_ppo_actor_grad": "mdr_ppo_actor_grad_wide", "mdr_ppo_critic_grad": "mdr_ppo_critic_grad_wide",
+         "mdr_dqn_target": "mdr_dqn_target_wide", "mdr_dqn_grad": "mdr_dqn_grad_wide",
+         "mdr_mappo_critic_grad_floats": "mdr_mappo_critic_wide_grad_floats",
+         "mdr_mappo_critic_workspace_bytes": "mdr_mappo_critic_wide_workspace_bytes", "mdr_mappo_critic_grad": "mdr_mappo_critic_grad_wide"}
+
+
+def _fn(lib, name: str, wide: bool):
+    """The entry point ``name`` or, with ``wide``, its wide sibling."""
+    return getattr(lib, _WIDE[name] if wide else name)
 
 
 def _layers(net) -> Optional[List[nn.Linear]]:
@@ -31,8 +46,11 @@ def _layers(net) -> Optional[List[nn.Linear]]:
     return list(fc)
 
 
-def _refusal(net, num_out: Optional[int] = None, max_state: int = MAX_STATE) -> Optional[str]:
-    """Why the kernels do not take ``net`` (None: they do).  ``max_state``: the input width of the head asked for."""
+def _refusal(net, num_out: Optional[int] = None, max_state: int = MAX_STATE, wide: bool = False) -> Optional[str]:
+    """Why the kernels do not take ``net`` (None: they do).  ``max_state``: the input width of the head asked for.  ``wide``: the
+    wide entry points' limits - ``MAX_STATE_WIDE`` input features and the LDS fit, the message saying which of the two failed."""
+    if wide:
+        max_state = MAX_STATE_WIDE
     fc = _layers(net)
     if fc is None:
         return "the kernels cover Linear-ReLU-Linear-ReLU-Linear (an `fc` ModuleList of three biased Linear layers)"
@@ -49,13 +67,17 @@ def _refusal(net, num_out: Optional[int] = None, max_state: int = MAX_STATE) -> 
         for p in (lin.weight, lin.bias):
             if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                 return "parameters must be contiguous float32 tensors on the GPU"
+    if wide and nat.load().mdr_mlp_wide_grad_floats(C.byref(_desc(net))) < 0:
+        return ("%d input features with hidden layers of %d and %d units do not fit the kernel's LDS layout"
+                % (fc[0].in_features, fc[0].out_features, fc[1].out_features))
     return None
 
 
-def supported(net) -> bool:
+def supported(net, wide: bool = False) -> bool:
     """Do the gradient kernels take this network?  An ``ActorMLP`` / ``CriticMLP`` of two hidden layers with F <= 64 input features,
-    hidden layers of at most 128 units and 2 (actor) or 1 (critic) outputs, float32 on the GPU."""
-    return _refusal(net) is None
+    hidden layers of at most 128 units and 2 (actor) or 1 (critic) outputs, float32 on the GPU.  ``wide=True``: the wide entry
+    points, F <= 128 where the LDS layout fits (hidden 100-100: every F; 128-128: F <= 100)."""
+    return _refusal(net, wide=wide) is None
 
 
 def _params(net) -> List[torch.Tensor]:
@@ -79,12 +101,12 @@ def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
     return ws
 
 
-def _flat_grad(net, lib, desc, floats: Optional[int] = None) -> torch.Tensor:
+def _flat_grad(net, lib, desc, floats: Optional[int] = None, wide: bool = False) -> torch.Tensor:
     """The flat gradient buffer the kernels write, kept with the module; the six ``.grad`` are views of it (assigned where a
     parameter has none or another tensor of its own, which is then overwritten by a copy after the call)."""
     params = _params(net)
     flat = getattr(net, "_mdr_flat_grad", None)
-    n = int(lib.mdr_mlp_grad_floats(C.byref(desc))) if floats is None else int(floats)
+    n = int(_fn(lib, "mdr_mlp_grad_floats", wide)(C.byref(desc))) if floats is None else int(floats)
     if flat is None or flat.numel() != n or flat.device != params[0].device:
         flat = torch.empty(n, dtype=torch.float32, device=params[0].device)
         net._mdr_flat_grad = flat
@@ -124,13 +146,15 @@ def _whole(t, dtype, M, dev, what, name):
 
 
 def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_prob: torch.Tensor, advantage: torch.Tensor,
-                        clip_param: float = 0.2, index: Optional[torch.Tensor] = None, want_ratio: bool = False, max_workgroups: int = 0):
+                        clip_param: float = 0.2, index: Optional[torch.Tensor] = None, want_ratio: bool = False, max_workgroups: int = 0,
+                        wide: bool = False):
     """The clipped surrogate of agents/ppo.py:153-169 and ``backward()`` in one kernel: fills ``p.grad`` of the six parameters of
     ``actor`` (allocated where None, overwritten otherwise) and returns the loss (0-dim device tensor) [and the ratios, float32 [B]].
     ``state`` float32 [M, F] (any row stride >= F), ``action`` int64 [M], ``old_prob`` float32 [M]: the transition buffer, read in
-    place through ``index`` (int64 [B] on the device; None: every row in order, B = M); ``advantage`` float32 [B] in minibatch order."""
+    place through ``index`` (int64 [B] on the device; None: every row in order, B = M); ``advantage`` float32 [B] in minibatch order.
+    ``wide=True``: up to 128 input features (``supported(actor, wide=True)``)."""
     what = "actor_loss_backward"
-    why = _refusal(actor, 2)
+    why = _refusal(actor, 2, wide=wide)
     if why:
         raise ValueError("%s: %s" % (what, why))
     dev, M, ld, B = _check_rows(actor, state, index, what)
@@ -141,45 +165,47 @@ def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_pr
         raise ValueError("%s: clip_param must lie in [0, 1)" % what)
     lib = nat.load()
     desc = _desc(actor)
-    flat = _flat_grad(actor, lib, desc)
-    ws = _workspace(dev, int(lib.mdr_mlp_grad_workspace_bytes(C.byref(desc), B, max_workgroups)))
+    flat = _flat_grad(actor, lib, desc, wide=wide)
+    ws = _workspace(dev, int(_fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(desc), B, max_workgroups)))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ratio = torch.empty(B, dtype=torch.float32, device=dev) if want_ratio else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_ppo_actor_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None, B,
-                                    C.c_void_p(action.data_ptr()), C.c_void_p(old_prob.data_ptr()), C.c_void_p(advantage.data_ptr()),
-                                    C.c_float(clip_param), max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()),
-                                    C.c_void_p(loss.data_ptr()), C.c_void_p(ratio.data_ptr()) if want_ratio else None,
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, "mdr_ppo_actor_grad")
+        rc = _fn(lib, "mdr_ppo_actor_grad", wide)(
+            C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None, B,
+            C.c_void_p(action.data_ptr()), C.c_void_p(old_prob.data_ptr()), C.c_void_p(advantage.data_ptr()),
+            C.c_float(clip_param), max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()),
+            C.c_void_p(loss.data_ptr()), C.c_void_p(ratio.data_ptr()) if want_ratio else None,
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, _WIDE["mdr_ppo_actor_grad"] if wide else "mdr_ppo_actor_grad")
     _publish(actor, flat)
     return (loss, ratio) if want_ratio else loss
 
 
 def critic_loss_backward(critic, state: torch.Tensor, target: torch.Tensor, index: Optional[torch.Tensor] = None,
-                         max_workgroups: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         max_workgroups: int = 0, wide: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """F.mse_loss(Gt, V) of agents/ppo.py:148-150, 180 and ``backward()`` in one kernel: fills ``p.grad`` of ``critic`` and returns
     (loss 0-dim, value float32 [B], advantage float32 [B] = target - value, the detached delta the actor's loss takes).
-    ``target`` float32 [M] is read through ``index`` like ``state``."""
+    ``target`` float32 [M] is read through ``index`` like ``state``.  ``wide=True``: up to 128 input features."""
     what = "critic_loss_backward"
-    why = _refusal(critic, 1)
+    why = _refusal(critic, 1, wide=wide)
     if why:
         raise ValueError("%s: %s" % (what, why))
     dev, M, ld, B = _check_rows(critic, state, index, what)
     _whole(target, torch.float32, M, dev, what, "target")
     lib = nat.load()
     desc = _desc(critic)
-    flat = _flat_grad(critic, lib, desc)
-    ws = _workspace(dev, int(lib.mdr_mlp_grad_workspace_bytes(C.byref(desc), B, max_workgroups)))
+    flat = _flat_grad(critic, lib, desc, wide=wide)
+    ws = _workspace(dev, int(_fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(desc), B, max_workgroups)))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     value = torch.empty(B, dtype=torch.float32, device=dev)
     adv = torch.empty(B, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.mdr_ppo_critic_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None, B,
-                                     C.c_void_p(target.data_ptr()), max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()),
-                                     C.c_void_p(loss.data_ptr()), C.c_void_p(value.data_ptr()), C.c_void_p(adv.data_ptr()),
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, "mdr_ppo_critic_grad")
+        rc = _fn(lib, "mdr_ppo_critic_grad", wide)(
+            C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None, B,
+            C.c_void_p(target.data_ptr()), max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()),
+            C.c_void_p(loss.data_ptr()), C.c_void_p(value.data_ptr()), C.c_void_p(adv.data_ptr()),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, _WIDE["mdr_ppo_critic_grad"] if wide else "mdr_ppo_critic_grad")
     _publish(critic, flat)
     return loss, value, adv
 
@@ -191,20 +217,23 @@ class PPOLearner:
     reference's expressions under autograd - the comparator and the fallback; ``"auto"``: the kernels where ``supported()`` holds
     for both networks and the minibatch has at least ``AUTO_MIN_ROWS`` rows, torch otherwise.  ``optimizer``: called as
     ``optimizer(params, lr)`` for each network; an optimiser that is a ``mdr_amd.optim.FusedAdam`` clips and steps in one launch
-    (``.grad`` then keeps the unclipped gradient), any other one is stepped after ``clip_grad_norm_``."""
+    (``.grad`` then keeps the unclipped gradient), any other one is stepped after ``clip_grad_norm_``.  ``wide=True``: the wide
+    entry points, so networks of up to 128 input features (both message flags on: 121) take the kernels, eager or ``graph=True``;
+    ``"auto"`` then takes them from ``AUTO_MIN_ROWS_WIDE`` minibatch rows on."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
                  ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
-                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024):
+                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        self.wide = bool(wide)
         if sampler is None:
             sampler = "philox" if graph else "torch"
         if sampler not in ("torch", "philox"):
             raise ValueError("sampler must be 'torch' or 'philox'")
         if backend == "hip":
             for net, outs in ((actor, 2), (critic, 1)):
-                why = _refusal(net, outs)
+                why = _refusal(net, outs, wide=self.wide)
                 if why:
                     raise ValueError("PPOLearner(backend='hip'): " + why)
         self.actor, self.critic = actor, critic
@@ -228,16 +257,18 @@ class PPOLearner:
 
     @classmethod
     def from_config(cls, ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam, sampler: Optional[str] = None,
-                    graph: bool = False, graph_max_minibatches: int = 1024) -> "PPOLearner":
+                    graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False) -> "PPOLearner":
         """From the reference's ``config_dict["PPO_prop"]`` (agents/ppo.py:34-40)."""
         return cls(actor, critic, ppo_prop["lr_actor"], ppo_prop["lr_critic"], clip_param=ppo_prop["clip_param"],
                    max_grad_norm=ppo_prop["max_grad_norm"], ppo_update_time=ppo_prop["ppo_update_time"],
                    batch_size=ppo_prop["batch_size"], backend=backend, optimizer=optimizer, sampler=sampler, graph=graph,
-                   graph_max_minibatches=graph_max_minibatches)
+                   graph_max_minibatches=graph_max_minibatches, wide=wide)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
-            return _refusal(self.actor, 2) is None and _refusal(self.critic, 1) is None and nb_rows >= AUTO_MIN_ROWS
+            wide = getattr(self, "wide", False)      # (subclasses with a constructor of their own have no wide: the narrow limits)
+            return (_refusal(self.actor, 2, wide=wide) is None and _refusal(self.critic, 1, wide=wide) is None
+                    and nb_rows >= (AUTO_MIN_ROWS_WIDE if wide else AUTO_MIN_ROWS))
         return self.backend == "hip"
 
     def minibatches(self, nb_transitions: int, seed: int, epoch: int) -> List[torch.Tensor]:
@@ -256,17 +287,18 @@ class PPOLearner:
 
     def critic_backward(self, state, action, target, index):
         """The critic's kernel call of one minibatch -> (loss, value, advantage); MAPPOLearner's takes the joint input."""
-        return critic_loss_backward(self.critic, state, target, index=index)
+        return critic_loss_backward(self.critic, state, target, index=index, wide=getattr(self, "wide", False))
 
     # the same call for a captured graph, on raw pointers into its static buffers (graph_update.PPOUpdateGraph); MAPPOLearner's differ
     def _critic_grad_floats(self, lib, desc) -> int:
-        return int(lib.mdr_mlp_grad_floats(C.byref(desc)))
+        return int(_fn(lib, "mdr_mlp_grad_floats", getattr(self, "wide", False))(C.byref(desc)))
 
     def _critic_workspace_bytes(self, lib, desc, nb_rows: int) -> int:
-        return int(lib.mdr_mlp_grad_workspace_bytes(C.byref(desc), nb_rows, 0))
+        return int(_fn(lib, "mdr_mlp_grad_workspace_bytes", getattr(self, "wide", False))(C.byref(desc), nb_rows, 0))
 
     def _critic_launch(self, lib, desc, state, ld, action, nb_transitions, target, index, nb_rows, workspace, grad, loss, value, adv, stream) -> int:
-        return lib.mdr_ppo_critic_grad(C.byref(desc), state, ld, index, nb_rows, target, 0, workspace, grad, loss, value, adv, stream)
+        return _fn(lib, "mdr_ppo_critic_grad", getattr(self, "wide", False))(C.byref(desc), state, ld, index, nb_rows, target, 0, workspace, grad,
+                                                                             loss, value, adv, stream)
 
     def _capture(self, shape):
         """Capture the graph of one epoch over a batch of ``shape`` = (T, A, F) without replaying it; parameters, moments and every
@@ -287,7 +319,8 @@ class PPOLearner:
         optimiser steps.  The arguments are the whole flattened buffers; ``index`` picks the minibatch.  -> (actor loss, critic loss)."""
         if self.uses_kernels(int(index.shape[0])):
             value_loss, _, advantage = self.critic_backward(state, action, target, index)
-            action_loss = actor_loss_backward(self.actor, state, action, old_prob, advantage, self.clip_param, index=index)
+            action_loss = actor_loss_backward(self.actor, state, action, old_prob, advantage, self.clip_param, index=index,
+                                              wide=getattr(self, "wide", False))
         else:
             Gt_index = target[index].view(-1, 1)
             V = self.critic(self.critic_input(state, action, index))
