@@ -20,15 +20,18 @@ Two places leave the reference's text on purpose:
 from __future__ import annotations
 
 import ctypes as C
+from functools import partial
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _learner as L
 from . import _native as nat
+from . import graph_update
 from .optim import FusedAdam
-from .ppo import _WIDE, _check_rows, _desc, _flat_grad, _fn, _publish, _refusal, _whole, _workspace
+from .ppo import refusal
 
 # backend="auto": the kernels from this many minibatch rows on (profiles/dqn_update_README.md: where they measured faster than autograd)
 AUTO_MIN_ROWS = 1
@@ -56,11 +59,24 @@ class QNetworkMLP(nn.Module):
 def supported(net, wide: bool = False) -> bool:
     """Do the kernels take this Q-network?  Two hidden layers, F <= 64 input features, at most 128 hidden units, 2 actions, float32
     on the GPU.  ``wide=True``: the wide entry points, F <= 128 where the LDS layout fits (hidden 100-100: every F; 128-128: F <= 100)."""
-    return _refusal(net, 2, wide=wide) is None
+    return refusal(net, 2, wide=wide) is None
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+def _target_launch(tdesc, pdesc, next_state, ld, reward, index, B, y, next_q, next_action, stream, gamma, max_workgroups=0, wide=False) -> None:
+    """mdr_dqn_target[_wide] on checked tensors (``pdesc`` None: DQN), under the device of ``next_state``: the eager call and the
+    captured one."""
+    lib = nat.load()
+    call, name = L.fn(lib, "mdr_dqn_target", wide)
+    nat.check(lib, None, call(C.byref(tdesc), C.byref(pdesc) if pdesc is not None else None, L.ptr(next_state), ld, L.ptr(index), B, L.ptr(reward),
+                              C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q), L.ptr(next_action), stream), name)
+
+
+def _grad_launch(desc, state, ld, action, y, index, B, workspace, flat, loss, q, stream, grad_clamp, max_workgroups=0, wide=False) -> None:
+    """mdr_dqn_grad[_wide] on checked tensors: the eager call and the captured one."""
+    lib = nat.load()
+    call, name = L.fn(lib, "mdr_dqn_grad", wide)
+    nat.check(lib, None, call(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, L.ptr(action), L.ptr(y), C.c_float(grad_clamp), max_workgroups,
+                              L.ptr(workspace), L.ptr(flat), L.ptr(loss), L.ptr(q), stream), name)
 
 
 def td_target(target_net, next_state: torch.Tensor, reward: torch.Tensor, gamma: float, index: Optional[torch.Tensor] = None,
@@ -73,22 +89,18 @@ def td_target(target_net, next_state: torch.Tensor, reward: torch.Tensor, gamma:
     y = reward + gamma * next_q.  Nothing here is differentiated.  ``wide=True``: up to 128 input features."""
     what = "td_target"
     for net in (target_net,) + ((policy_net,) if policy_net is not None else ()):
-        why = _refusal(net, 2, wide=wide)
+        why = refusal(net, 2, wide=wide)
         if why:
             raise ValueError("%s: %s" % (what, why))
-    dev, M, ld, B = _check_rows(target_net, next_state, index, what)
-    _whole(reward, torch.float32, M, dev, what, "reward")
-    lib = nat.load()
-    tdesc = _desc(target_net)
-    pdesc = _desc(policy_net) if policy_net is not None else None
+    fc = L.fc_layers(target_net)
+    dev, M, ld, B = L.check_rows(fc, next_state, index, what)
+    L.whole(reward, torch.float32, M, dev, what, "reward")
+    pdesc = L.mlp_desc(L.fc_layers(policy_net)) if policy_net is not None else None
     y = torch.empty(B, dtype=torch.float32, device=dev)
     next_q = torch.empty(B, dtype=torch.float32, device=dev)
     next_action = torch.empty(B, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = _fn(lib, "mdr_dqn_target", wide)(C.byref(tdesc), C.byref(pdesc) if pdesc is not None else None, _ptr(next_state), ld, _ptr(index), B,
-                                              _ptr(reward), C.c_float(gamma), max_workgroups, _ptr(y), _ptr(next_q), _ptr(next_action),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, _WIDE["mdr_dqn_target"] if wide else "mdr_dqn_target")
+        _target_launch(L.mlp_desc(fc), pdesc, next_state, ld, reward, index, B, y, next_q, next_action, L.stream(dev), gamma, max_workgroups, wide)
     return y, next_q, next_action
 
 
@@ -100,78 +112,41 @@ def q_loss_backward(policy_net, state: torch.Tensor, action: torch.Tensor, y: to
     are the replay buffer, read in place through ``index``; ``y`` float32 [B] (``td_target``'s) in minibatch order.
     ``grad_clamp=float("inf")``: no clamp.  ``wide=True``: up to 128 input features."""
     what = "q_loss_backward"
-    why = _refusal(policy_net, 2, wide=wide)
+    why = refusal(policy_net, 2, wide=wide)
     if why:
         raise ValueError("%s: %s" % (what, why))
-    dev, M, ld, B = _check_rows(policy_net, state, index, what)
-    _whole(action, torch.int64, M, dev, what, "action")
-    _whole(y, torch.float32, B, dev, what, "y")
+    fc = L.fc_layers(policy_net)
+    dev, M, ld, B = L.check_rows(fc, state, index, what)
+    L.whole(action, torch.int64, M, dev, what, "action")
+    L.whole(y, torch.float32, B, dev, what, "y")
     if not float(grad_clamp) > 0.0:
         raise ValueError("%s: grad_clamp must be positive (inf: no clamp)" % what)
-    lib = nat.load()
-    desc = _desc(policy_net)
-    flat = _flat_grad(policy_net, lib, desc, wide=wide)
-    ws = _workspace(dev, int(_fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(desc), B, max_workgroups)))
+    desc = L.mlp_desc(fc)
+    floats, nbytes = L.mlp_sizes(desc, B, max_workgroups, wide)
+    flat = L.flat_grad(policy_net, floats, dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
     with torch.cuda.device(dev):
-        rc = _fn(lib, "mdr_dqn_grad", wide)(C.byref(desc), _ptr(state), ld, _ptr(index), B, _ptr(action), _ptr(y), C.c_float(grad_clamp),
-                                            max_workgroups, _ptr(ws), _ptr(flat), _ptr(loss), _ptr(q),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, _WIDE["mdr_dqn_grad"] if wide else "mdr_dqn_grad")
-    _publish(policy_net, flat)
+        _grad_launch(desc, state, ld, action, y, index, B, L.workspace(dev, nbytes), flat, loss, q, L.stream(dev), grad_clamp, max_workgroups, wide)
+    L.publish(L.mlp_params(fc), flat, L.KEEP)
     return (loss, q) if want_q else loss
 
 
-class DeviceReplayBuffer:
+class DeviceReplayBuffer(L.RingBuffer):
     """``ReplayBuffer`` (agents/buffer.py:12-31: a ``deque(maxlen=capacity)`` of Transition tuples) as four preallocated tensors on
     ``device`` - ``state`` [capacity, F], ``next_state`` [capacity, F], ``action`` int64 [capacity], ``reward`` [capacity] - written as
-    a ring: the oldest entries are overwritten first.  The fill count and the ring position live on the host; no call synchronises."""
+    a ring (``_learner.RingBuffer``).  ``push``: ``n`` transitions at once, ``state`` / ``next_state`` [n, F], ``action`` / ``reward``
+    [n] or [n, 1]; ``push_batch``: the dict of ``collect_dqn_transitions``, stored in (t, agent) order."""
 
     def __init__(self, capacity: int, num_state: int, device):
         if int(capacity) <= 0 or int(num_state) <= 0:
             raise ValueError("DeviceReplayBuffer: capacity and num_state must be positive")
-        self.capacity, self.num_state = int(capacity), int(num_state)
-        self.device = torch.device(device)
-        self.state = torch.zeros((self.capacity, self.num_state), dtype=torch.float32, device=self.device)
-        self.next_state = torch.zeros((self.capacity, self.num_state), dtype=torch.float32, device=self.device)
-        self.action = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
-        self.reward = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
-        self._len = 0
-        self._pos = 0      # where the next transition goes
+        super().__init__(capacity, (), num_state, device)
 
-    def __len__(self) -> int:
-        return self._len
-
-    def push(self, state: torch.Tensor, action: torch.Tensor, reward: torch.Tensor, next_state: torch.Tensor) -> None:
-        """``n`` transitions at once (``state`` / ``next_state`` [n, F], ``action`` / ``reward`` [n] or [n, 1]), in row order, at the
-        ring position with wrap-around; of a push larger than the capacity the last ``capacity`` rows stay, as with the deque."""
-        n = int(state.shape[0])
+    def _rows(self, n, state, next_state, action, reward):
         if state.shape != (n, self.num_state) or next_state.shape != (n, self.num_state) or action.numel() != n or reward.numel() != n:
             raise ValueError("DeviceReplayBuffer.push: state / next_state [n, %d], action and reward of n elements" % self.num_state)
-        rows = (state, next_state, action.reshape(n), reward.reshape(n))
-        skip = max(n - self.capacity, 0)
-        kept = n - skip
-        first = min(kept, self.capacity - self._pos)      # rows up to the end of the ring; the rest wraps to its start
-        for dst, src in zip((self.state, self.next_state, self.action, self.reward), rows):
-            dst[self._pos:self._pos + first].copy_(src[skip:skip + first])
-            if kept > first:
-                dst[:kept - first].copy_(src[skip + first:])
-        self._pos = (self._pos + kept) % self.capacity
-        self._len = min(self._len + kept, self.capacity)
-
-    def push_batch(self, batch: Dict[str, torch.Tensor]) -> None:
-        """The dict of ``collect_dqn_transitions`` (``state`` [T + 1, A, F], ``action``, ``reward`` [T, A]): ``state[t + 1]`` is
-        ``next_state[t]``; the T A transitions are stored in (t, agent) order."""
-        states = batch["state"]
-        T = states.shape[0] - 1
-        self.push(states[:T].reshape(-1, states.shape[-1]), batch["action"].reshape(-1), batch["reward"].reshape(-1),
-                  states[1:].reshape(-1, states.shape[-1]))
-
-    def chronological(self) -> torch.Tensor:
-        """The positions of the stored transitions, oldest first (int64 on the device, computed from the host's counters)."""
-        idx = torch.arange(self._len, dtype=torch.int64, device=self.device)
-        return (idx + self._pos) % self.capacity if self._len == self.capacity else idx
+        return state, next_state, action.reshape(n), reward.reshape(n)
 
     def sample(self, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """``batch_size`` positions (int64 on the device) drawn uniformly WITH replacement from the filled part, as ``random.choices``
@@ -199,13 +174,10 @@ class DQNLearner:
     def __init__(self, policy_net, lr: float, gamma: float = 0.99, tau: float = 0.01, buffer_capacity: int = 524288, batch_size: int = 256,
                  double: bool = False, backend: str = "auto", optimizer=torch.optim.Adam, soft_update: bool = True,
                  sampler: Optional[str] = None, graph: bool = False, wide: bool = False):
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        L.check_backend(backend)
         self.wide = bool(wide)
         if backend == "hip":
-            why = _refusal(policy_net, 2, wide=self.wide)
-            if why:
-                raise ValueError("DQNLearner(backend='hip'): " + why)
+            L.require(refusal(policy_net, 2, wide=self.wide), "DQNLearner")
         fc = getattr(policy_net, "fc", None)
         if fc is None or not all(isinstance(m, nn.Linear) for m in fc):
             raise ValueError("DQNLearner: policy_net needs the reference's `fc` ModuleList of Linear layers")
@@ -219,24 +191,19 @@ class DQNLearner:
         self.buffer = DeviceReplayBuffer(buffer_capacity, fc[0].in_features, dev)
         self.optimizer = optimizer(policy_net.parameters(), lr)
         # FusedAdam blends in its own launch where the optimiser's parameters are exactly the six the target net mirrors
-        mine = [p for lin in fc for p in (lin.weight, lin.bias)]
+        mine = L.mlp_params(fc)
         held = list(policy_net.parameters())
         same = len(held) == len(mine) and all(a is b for a, b in zip(held, mine))
-        self._fused_target = [p for lin in self.target_net.fc for p in (lin.weight, lin.bias)] if same else None
+        self._fused_target = L.mlp_params(self.target_net.fc) if same else None
         self.training_step = 0
         self.before_step = None      # optional callable(learner): runs after the backward (and the clamp) of an update, before the optimiser
         # sampler="philox": the positions from csrc/mdr_minibatch.hip by (seed, training_step) instead of a torch.Generator;
         # graph=True: every update replayed from one captured graph (graph_update.py)
-        if sampler is None:
-            sampler = "philox" if graph else "torch"
-        if sampler not in ("torch", "philox"):
-            raise ValueError("sampler must be 'torch' or 'philox'")
-        self.sampler, self.graph = sampler, bool(graph)
+        self.sampler, self.graph = L.check_sampler(sampler, graph), bool(graph)
         self.graph_captures = 0
         self._graph = None
         if self.graph:
-            from . import graph_update
-            why = graph_update.refusal(backend, sampler, (self.optimizer,), self.uses_kernels(max(self.batch_size, 1)))
+            why = graph_update.refusal(backend, self.sampler, (self.optimizer,), self.uses_kernels(max(self.batch_size, 1)))
             if not why and self.soft_update and self._fused_target is None:
                 why = "the optimiser's parameters are not the six tensors the target net mirrors (the blend would be torch launches)"
             if why:
@@ -252,9 +219,15 @@ class DQNLearner:
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
-            return (_refusal(self.policy_net, 2, wide=self.wide) is None and _refusal(self.target_net, 2, wide=self.wide) is None
+            return (refusal(self.policy_net, 2, wide=self.wide) is None and refusal(self.target_net, 2, wide=self.wide) is None
                     and nb_rows >= (AUTO_MIN_ROWS_WIDE if self.wide else AUTO_MIN_ROWS))
         return self.backend == "hip"
+
+    def _kernels(self):
+        """(sizes, target launch, gradient launch) of the calls ``loss_backward`` makes, this learner's fixed arguments bound: what a
+        captured graph runs on its static buffers (graph_update.DQNUpdateGraph)."""
+        return (partial(L.mlp_sizes, wide=self.wide), partial(_target_launch, gamma=self.gamma, wide=self.wide),
+                partial(_grad_launch, grad_clamp=self.GRAD_CLAMP, wide=self.wide))
 
     def store(self, batch: Dict[str, torch.Tensor]) -> None:
         """``store_transition`` (agents/dqn.py:58-63) for every transition of a ``collect_dqn_transitions`` dict."""
@@ -264,28 +237,20 @@ class DQNLearner:
         """The minibatch of this update: ``buffer.sample`` under a ``torch.Generator`` seeded by (seed, training_step) - the same
         positions whatever the backend."""
         if self.sampler == "philox":      # one Philox word per position by (seed, training_step), one launch (graph_update.sample)
-            from . import graph_update
             if len(self.buffer) == 0:
                 raise ValueError("DeviceReplayBuffer.sample: the buffer is empty")
             return graph_update.sample(self.batch_size, len(self.buffer), seed, self.training_step, self.buffer.device)
-        gen = torch.Generator(device=self.buffer.device)
-        gen.manual_seed((int(seed) * 1000003 + self.training_step * 7919 + 12345) & (2 ** 63 - 1))
-        return self.buffer.sample(self.batch_size, gen)
+        return self.buffer.sample(self.batch_size, L.seeded_generator(seed, self.training_step, self.buffer.device))
 
     def _capture(self):
         """Capture the graph of one update without replaying it; both nets, the moments and every counter are what they were."""
-        from . import graph_update
         self._graph = graph_update.DQNUpdateGraph(self)
         self.graph_captures += 1
         return self._graph
 
-    @torch.no_grad()
     def update_target_network(self) -> None:
         """agents/dqn.py:77-82: params = (1 - tau) * params + tau * new over the six tensors (two fused launches)."""
-        target = [p for lin in self.target_net.fc for p in (lin.weight, lin.bias)]
-        new = [p for lin in self.policy_net.fc for p in (lin.weight, lin.bias)]
-        torch._foreach_mul_(target, 1.0 - self.tau)
-        torch._foreach_add_(target, new, alpha=self.tau)
+        L.blend(L.mlp_params(self.target_net.fc), L.mlp_params(self.policy_net.fc), self.tau)
 
     def loss_backward(self, index: torch.Tensor) -> torch.Tensor:
         """Target, Huber loss, backward and the clamp for the transitions at ``index``: fills the policy net's ``.grad``."""
@@ -316,7 +281,6 @@ class DQNLearner:
         transitions (:85-86).  ``graph=True``: the same launches replayed from a captured graph, the same bits as the eager
         ``sampler="philox"`` update."""
         if self.graph:
-            from . import graph_update
             return graph_update.dqn_update(self, seed)
         if len(self.buffer) < self.batch_size:
             return None

@@ -27,6 +27,7 @@ from typing import Optional, Sequence
 
 import torch
 
+from . import _learner as L
 from . import _native as nat
 from .optim import FusedAdam
 
@@ -35,10 +36,6 @@ def _i32(x: int) -> int:
     """The low 32 bits of x as the int32 of the same bit pattern."""
     x = int(x) & 0xFFFFFFFF
     return x - (1 << 32) if x >= (1 << 31) else x
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check_int32(t: Optional[torch.Tensor], dev, count: int, what: str) -> None:
@@ -56,7 +53,7 @@ def cursor_set(block: torch.Tensor, values: Sequence[int], offset: int = 0) -> N
         raise ValueError("cursor_set: a device block and an offset >= 0")
     lib = nat.load()
     with torch.cuda.device(block.device):
-        rc = lib.mdr_update_cursor_set(C.c_void_p(block.data_ptr() + 4 * int(offset)), len(vals), *(vals + [0] * (4 - len(vals))), _stream(block.device))
+        rc = lib.mdr_update_cursor_set(C.c_void_p(block.data_ptr() + 4 * int(offset)), len(vals), *(vals + [0] * (4 - len(vals))), L.stream(block.device))
     nat.check(lib, None, rc, "mdr_update_cursor_set")
 
 
@@ -67,7 +64,7 @@ def cursor_add(block: torch.Tensor, index: int, delta: int) -> None:
         raise ValueError("cursor_add: a device block and an index >= 0")
     lib = nat.load()
     with torch.cuda.device(block.device):
-        rc = lib.mdr_update_cursor_add(C.c_void_p(block.data_ptr()), int(index), _i32(delta), _stream(block.device))
+        rc = lib.mdr_update_cursor_add(C.c_void_p(block.data_ptr()), int(index), _i32(delta), L.stream(block.device))
     nat.check(lib, None, rc, "mdr_update_cursor_add")
 
 
@@ -95,9 +92,9 @@ def permutation(n: int, seed: int, epoch: int, device, out: Optional[torch.Tenso
     cur = C.c_void_p(cursor.data_ptr()) if cursor is not None else None
     with torch.cuda.device(dev):
         if key is not None:
-            rc = lib.mdr_minibatch_permutation_keyed(n, C.c_void_p(key.data_ptr()), int(epoch) & (2 ** 64 - 1), cur, C.c_void_p(res.data_ptr()), _stream(dev))
+            rc = lib.mdr_minibatch_permutation_keyed(n, C.c_void_p(key.data_ptr()), int(epoch) & (2 ** 64 - 1), cur, C.c_void_p(res.data_ptr()), L.stream(dev))
         else:
-            rc = lib.mdr_minibatch_permutation(n, int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), cur, C.c_void_p(res.data_ptr()), _stream(dev))
+            rc = lib.mdr_minibatch_permutation(n, int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), cur, C.c_void_p(res.data_ptr()), L.stream(dev))
     nat.check(lib, None, rc, "mdr_minibatch_permutation")
     return res[:n] if out is not None else res
 
@@ -129,10 +126,10 @@ def sample(nb: int, length, seed: int, step: int, device, out: Optional[torch.Te
     with torch.cuda.device(dev):
         if key is not None:
             rc = lib.mdr_minibatch_sample_keyed(nb, len_dev, len_host, C.c_void_p(key.data_ptr()), int(step) & (2 ** 64 - 1), cur, C.c_void_p(res.data_ptr()),
-                                                _stream(dev))
+                                                L.stream(dev))
         else:
             rc = lib.mdr_minibatch_sample(nb, len_dev, len_host, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), cur, C.c_void_p(res.data_ptr()),
-                                          _stream(dev))
+                                          L.stream(dev))
     nat.check(lib, None, rc, "mdr_minibatch_sample")
     return res[:nb] if out is not None else res
 
@@ -151,22 +148,18 @@ def refusal(backend: str, sampler: str, optimizers, uses_kernels: bool) -> Optio
     return None
 
 
-def _bind_grads(net, flat: torch.Tensor, params) -> None:
-    """``p.grad`` of the six parameters as views of the flat gradient the kernels write (what ``ppo._publish`` leaves where a parameter
-    had no gradient): the captured optimiser step reads them at these addresses."""
-    off = 0
-    for p in params:
-        view = flat[off:off + p.numel()].view_as(p)
-        off += p.numel()
-        if p.grad is None or p.grad.data_ptr() != view.data_ptr():
-            p.grad = view
+def _flat_grad(net, floats: int) -> torch.Tensor:
+    """The flat gradient of ``net`` with the six ``p.grad`` rebound to views of it: the captured optimiser step reads them there."""
+    params = L.mlp_params(L.fc_layers(net))
+    flat = L.flat_grad(net, floats, params[0].device)
+    L.publish(params, flat, L.REBIND)
+    return flat
 
 
 def _signature(nets) -> list:
-    from . import ppo
     sig = []
     for net in nets:
-        for p in ppo._params(net):
+        for p in L.mlp_params(L.fc_layers(net)):
             sig += [p.data_ptr(), p.grad.data_ptr() if p.grad is not None else 0]
     return sig
 
@@ -205,9 +198,7 @@ class PPOUpdateGraph:
     EPOCH, BASE, KEY = 0, 1, 2      # the cursor block: epoch, table base, key lo, key hi
 
     def __init__(self, learner, T: int, A: int, F: int):
-        from . import ppo
         self.learner = learner
-        self.lib = lib = nat.load()
         dev = next(learner.actor.parameters()).device
         self.dev = dev
         self.n, self.F, self.bs, self.epochs = T * A, F, learner.batch_size, learner.ppo_update_time
@@ -227,18 +218,14 @@ class PPOUpdateGraph:
         self.c_loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.value = torch.zeros(self.bs, dtype=torch.float32, device=dev)
         self.adv = torch.zeros(self.bs, dtype=torch.float32, device=dev)
-        self.a_desc, self.c_desc = ppo._desc(learner.actor), ppo._desc(learner.critic)
-        rows = sorted({min(self.bs, n), n - (self.m - 1) * self.bs})
-        self.wide = wide = bool(getattr(learner, "wide", False))      # the learner's wide=True: the wide entry points, the same argument lists
-        nbytes = 16
-        for B in rows:
-            nbytes = max(nbytes, int(ppo._fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(self.a_desc), B, 0)),
-                         learner._critic_workspace_bytes(lib, self.c_desc, B))
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # the graph's own: ppo._workspace may be reallocated
-        self.a_flat = ppo._flat_grad(learner.actor, lib, self.a_desc, wide=wide)
-        self.c_flat = ppo._flat_grad(learner.critic, lib, self.c_desc, floats=learner._critic_grad_floats(lib, self.c_desc))
-        _bind_grads(learner.actor, self.a_flat, ppo._params(learner.actor))
-        _bind_grads(learner.critic, self.c_flat, ppo._params(learner.critic))
+        self.a_desc, self.c_desc = L.mlp_desc(L.fc_layers(learner.actor)), L.mlp_desc(L.fc_layers(learner.critic))
+        # the learner's own calls (wide or narrow, MAPPO's joint critic), here on the graph's static buffers
+        (a_sizes, self.actor_launch), (c_sizes, self.critic_launch) = learner._actor_kernel(), learner._critic_kernel()
+        rows = {min(self.bs, n), n - (self.m - 1) * self.bs}      # a full minibatch and the tail
+        a_floats, a_bytes = zip(*(a_sizes(self.a_desc, B) for B in rows))
+        c_floats, c_bytes = zip(*(c_sizes(self.c_desc, B) for B in rows))
+        self.workspace = torch.empty(max(16, *a_bytes, *c_bytes), dtype=torch.uint8, device=dev)      # the graph's own: the shared one may be reallocated
+        self.a_flat, self.c_flat = _flat_grad(learner.actor, a_floats[0]), _flat_grad(learner.critic, c_floats[0])
         a_opt, c_opt = learner.actor_optimizer, learner.critic_optimizer
         held = list(learner.actor.parameters()) + list(learner.critic.parameters()) + [a_opt._exp_avg, a_opt._exp_avg_sq, c_opt._exp_avg, c_opt._exp_avg_sq]
         self.graph = _capture(self._record, held, dev)
@@ -246,25 +233,20 @@ class PPOUpdateGraph:
 
     def _record(self) -> None:
         """The launches of one epoch on the current stream, from the static buffers alone."""
-        from . import ppo
-        L, lib, dev = self.learner, self.lib, self.dev
-        actor_grad = ppo._fn(lib, "mdr_ppo_actor_grad", self.wide)
-        st = _stream(dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
-        key = self.block[self.KEY:]
+        learner, dev = self.learner, self.dev
+        st = L.stream(dev)
+        base = self.block[self.BASE:self.BASE + 1]
         with torch.cuda.device(dev):
-            permutation(self.n, 0, 0, dev, out=self.perm, cursor=self.block[self.EPOCH:], key=key)
+            permutation(self.n, 0, 0, dev, out=self.perm, cursor=self.block[self.EPOCH:], key=self.block[self.KEY:])
             for j in range(self.m):
-                B = min(self.bs, self.n - j * self.bs)
-                index = C.c_void_p(self.perm.data_ptr() + 8 * j * self.bs)
-                rc = L._critic_launch(lib, self.c_desc, ptr(self.state), self.F, ptr(self.action), self.n, ptr(self.ret), index, B, ptr(self.workspace),
-                                      ptr(self.c_flat), ptr(self.c_loss), ptr(self.value), ptr(self.adv), st)
-                nat.check(lib, None, rc, "critic gradient")
-                rc = actor_grad(C.byref(self.a_desc), ptr(self.state), self.F, index, B, ptr(self.action), ptr(self.a_prob), ptr(self.adv),
-                                C.c_float(L.clip_param), 0, ptr(self.workspace), ptr(self.a_flat), ptr(self.a_loss), None, st)
-                nat.check(lib, None, rc, "mdr_ppo_actor_grad")
-                L.actor_optimizer.step(max_grad_norm=L.max_grad_norm, corrections=self.a_table, slot=j, base_dev=self.block[self.BASE:self.BASE + 1])
-                L.critic_optimizer.step(max_grad_norm=L.max_grad_norm, corrections=self.c_table, slot=j, base_dev=self.block[self.BASE:self.BASE + 1])
+                index = self.perm[j * self.bs:(j + 1) * self.bs]      # a view (the last one shorter): slicing launches nothing
+                B = int(index.shape[0])
+                self.critic_launch(self.c_desc, self.state, self.F, self.action, self.ret, index, B, self.workspace, self.c_flat, self.c_loss,
+                                   self.value, self.adv, st)
+                self.actor_launch(self.a_desc, self.state, self.F, self.action, self.a_prob, index, B, self.adv, self.workspace, self.a_flat,
+                                  self.a_loss, None, st)
+                for net, opt, table in ((learner.actor, learner.actor_optimizer, self.a_table), (learner.critic, learner.critic_optimizer, self.c_table)):
+                    L.clip_and_step(opt, net.parameters(), learner.max_grad_norm, corrections=table, slot=j, base_dev=base)
                 self.a_sum.add_(self.a_loss)
                 self.c_sum.add_(self.c_loss)
             cursor_add(self.block, self.EPOCH, 1)
@@ -273,7 +255,7 @@ class PPOUpdateGraph:
     @torch.no_grad()
     def run(self, state, action, old_prob, target, seed: int):
         """Copy the batch in, reset the cursors, upload the corrections of all steps, replay once per epoch."""
-        L = self.learner
+        learner = self.learner
         self.state.copy_(state)
         self.action.copy_(action)
         self.a_prob.copy_(old_prob)
@@ -282,15 +264,15 @@ class PPOUpdateGraph:
         cursor_set(self.block, [0, 0, seed & 0xFFFFFFFF, seed >> 32])
         steps = self.epochs * self.m
         # fresh pinned tensors: torch's host allocator does not hand them out again before the copies that read them have run
-        self.a_table.copy_(L.actor_optimizer.correction_table(steps), non_blocking=True)
-        self.c_table.copy_(L.critic_optimizer.correction_table(steps), non_blocking=True)
+        self.a_table.copy_(learner.actor_optimizer.correction_table(steps), non_blocking=True)
+        self.c_table.copy_(learner.critic_optimizer.correction_table(steps), non_blocking=True)
         self.a_sum.zero_()
         self.c_sum.zero_()
         for _ in range(self.epochs):
             self.graph.replay()
-        L.actor_optimizer.advance(steps)
-        L.critic_optimizer.advance(steps)
-        L.training_step += steps
+        learner.actor_optimizer.advance(steps)
+        learner.critic_optimizer.advance(steps)
+        learner.training_step += steps
         return self.a_sum / max(steps, 1), self.c_sum / max(steps, 1), steps
 
 
@@ -325,11 +307,8 @@ class DQNUpdateGraph:
     LEN, STEP, KEY = 0, 2, 4      # the cursor block: len (int64 = two words), step, -, key lo, key hi
 
     def __init__(self, learner):
-        from . import ppo
         self.learner = learner
-        self.lib = lib = nat.load()
-        buf = learner.buffer
-        self.dev = dev = buf.device
+        self.dev = dev = learner.buffer.device
         self.bs = learner.batch_size
         self.block = torch.zeros(8, dtype=torch.int32, device=dev)
         self.table = torch.ones(2, dtype=torch.float32, device=dev)
@@ -338,12 +317,11 @@ class DQNUpdateGraph:
         self.next_q = torch.zeros(self.bs, dtype=torch.float32, device=dev)
         self.next_action = torch.zeros(self.bs, dtype=torch.uint8, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
-        self.p_desc, self.t_desc = ppo._desc(learner.policy_net), ppo._desc(learner.target_net)
-        self.wide = wide = bool(getattr(learner, "wide", False))      # the learner's wide=True: the wide entry points, the same argument lists
-        self.workspace = torch.empty(max(int(ppo._fn(lib, "mdr_mlp_grad_workspace_bytes", wide)(C.byref(self.p_desc), self.bs, 0)), 16),
-                                     dtype=torch.uint8, device=dev)
-        self.flat = ppo._flat_grad(learner.policy_net, lib, self.p_desc, wide=wide)
-        _bind_grads(learner.policy_net, self.flat, ppo._params(learner.policy_net))
+        self.p_desc, self.t_desc = L.mlp_desc(L.fc_layers(learner.policy_net)), L.mlp_desc(L.fc_layers(learner.target_net))
+        sizes, self.target_launch, self.grad_launch = learner._kernels()      # the learner's own calls (wide or narrow), on static buffers
+        floats, nbytes = sizes(self.p_desc, self.bs)
+        self.workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # the graph's own
+        self.flat = _flat_grad(learner.policy_net, floats)
         opt = learner.optimizer
         held = list(learner.policy_net.parameters()) + list(learner.target_net.parameters()) + [opt._exp_avg, opt._exp_avg_sq]
         cursor_set(self.block, [1, 0, 0, 0])      # the warm-up pass reads row 0 of the (allocated, possibly empty) buffer
@@ -351,35 +329,30 @@ class DQNUpdateGraph:
         self.signature = _signature((learner.policy_net, learner.target_net))
 
     def _record(self) -> None:
-        from . import ppo
-        L, lib, dev, buf = self.learner, self.lib, self.dev, self.learner.buffer
-        dqn_target, dqn_grad = ppo._fn(lib, "mdr_dqn_target", self.wide), ppo._fn(lib, "mdr_dqn_grad", self.wide)
-        st = _stream(dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+        learner, dev, buf = self.learner, self.dev, self.learner.buffer
+        st = L.stream(dev)
         with torch.cuda.device(dev):
             sample(self.bs, self.block[self.LEN:self.LEN + 2].view(torch.int64), 0, 0, dev, out=self.index, cursor=self.block[self.STEP:],
                    key=self.block[self.KEY:])
-            rc = dqn_target(C.byref(self.t_desc), C.byref(self.p_desc) if L.double else None, ptr(buf.next_state), buf.num_state, ptr(self.index),
-                            self.bs, ptr(buf.reward), C.c_float(L.gamma), 0, ptr(self.y), ptr(self.next_q), ptr(self.next_action), st)
-            nat.check(lib, None, rc, "mdr_dqn_target")
-            rc = dqn_grad(C.byref(self.p_desc), ptr(buf.state), buf.num_state, ptr(self.index), self.bs, ptr(buf.action), ptr(self.y),
-                          C.c_float(L.GRAD_CLAMP), 0, ptr(self.workspace), ptr(self.flat), ptr(self.loss), None, st)
-            nat.check(lib, None, rc, "mdr_dqn_grad")
-            if L.soft_update:
-                L.optimizer.step(target=L._fused_target, tau=L.tau, corrections=self.table, slot=0)
+            self.target_launch(self.t_desc, self.p_desc if learner.double else None, buf.next_state, buf.num_state, buf.reward, self.index, self.bs,
+                               self.y, self.next_q, self.next_action, st)
+            self.grad_launch(self.p_desc, buf.state, buf.num_state, buf.action, self.y, self.index, self.bs, self.workspace, self.flat, self.loss,
+                             None, st)
+            if learner.soft_update:
+                learner.optimizer.step(target=learner._fused_target, tau=learner.tau, corrections=self.table, slot=0)
             else:
-                L.optimizer.step(corrections=self.table, slot=0)
+                learner.optimizer.step(corrections=self.table, slot=0)
 
     @torch.no_grad()
     def run(self, seed: int) -> torch.Tensor:
-        L = self.learner
+        learner = self.learner
         seed = int(seed) & (2 ** 64 - 1)
-        cursor_set(self.block, [len(L.buffer), 0, L.training_step, 0])
+        cursor_set(self.block, [len(learner.buffer), 0, learner.training_step, 0])
         cursor_set(self.block, [seed & 0xFFFFFFFF, seed >> 32], offset=self.KEY)
-        self.table.copy_(L.optimizer.correction_table(1), non_blocking=True)
+        self.table.copy_(learner.optimizer.correction_table(1), non_blocking=True)
         self.graph.replay()
-        L.optimizer.advance(1)
-        L.training_step += 1
+        learner.optimizer.advance(1)
+        learner.training_step += 1
         return self.loss.clone()
 
 

@@ -31,9 +31,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _learner as L
 from . import _native as nat
 from .optim import FusedAdam
-from .ppo import _desc, _flat_grad, _publish, _whole, _workspace
 
 MAX_STATE, MAX_HIDDEN, MAX_JOINT = 64, 256, 1280      # the kernels' limits (include/mdr_policy.h: mdr_maddpg_*)
 # backend="auto": the kernels for minibatches of this many rows (profiles/maddpg_update_README.md: they measured 2.3-2.9x faster than
@@ -60,23 +60,16 @@ class DDPGNetworkMLP(nn.Module):
 
     @property
     def fc(self):
-        """The three Linear layers, as the gradient helpers of ppo.py index them."""
+        """The three Linear layers, as the gradient helpers of _learner.py index them."""
         return [self.net[0], self.net[2], self.net[4]]
 
     def forward(self, x):
         return self.net(x)
 
 
-def _linears(net):
-    fc = getattr(net, "fc", None)
-    if fc is None or len(fc) != 3 or not all(isinstance(m, nn.Linear) and m.bias is not None for m in fc):
-        return None
-    return list(fc)
-
-
 def _refusal(actor, critic, nb_agents: int) -> Optional[str]:
     """Why the kernels do not take this pair (None: they do)."""
-    fa, fc = _linears(actor), _linears(critic)
+    fa, fc = L.fc_layers(actor), L.fc_layers(critic)
     if fa is None or fc is None:
         return "the kernels cover Linear-ReLU-Linear-ReLU-Linear (DDPGNetworkMLP, or an `fc` list of three biased Linear layers)"
     for f in (fa, fc):
@@ -84,10 +77,8 @@ def _refusal(actor, critic, nb_agents: int) -> Optional[str]:
             return "the three layers do not chain"
         if f[0].out_features > MAX_HIDDEN or f[1].out_features > MAX_HIDDEN:
             return "hidden layers of %d and %d units: the kernels cover at most %d" % (f[0].out_features, f[1].out_features, MAX_HIDDEN)
-        for lin in f:
-            for p in (lin.weight, lin.bias):
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    return "parameters must be contiguous float32 tensors on the GPU"
+        if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in L.mlp_params(f)):
+            return "parameters must be contiguous float32 tensors on the GPU"
     F_len = fa[0].in_features
     if int(nb_agents) < 1 or fc[0].in_features != int(nb_agents) * (F_len + 2):
         return "the critic must read nb_agents * (num_state + 2) = %d inputs, not %d" % (int(nb_agents) * (F_len + 2), fc[0].in_features)
@@ -104,13 +95,9 @@ def supported(actor, critic, nb_agents: int) -> bool:
     return _refusal(actor, critic, nb_agents) is None
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _check_steps(actor, state, index, nb_agents, what):
     """``state`` [M, N, F] (or [M, N F]) float32 with unit inner strides and an env-step stride >= N F -> (dev, M, ld, B)."""
-    fa = _linears(actor)
+    fa = L.fc_layers(actor)
     dev, F_len, N = fa[0].weight.device, fa[0].in_features, int(nb_agents)
     if state.dim() == 3:
         ok = state.shape[1:] == (N, F_len) and (F_len == 1 or state.stride(2) == 1) and (N == 1 or state.stride(1) == F_len)
@@ -121,14 +108,9 @@ def _check_steps(actor, state, index, nb_agents, what):
     M = int(state.shape[0])
     if M > 1 and state.stride(0) < N * F_len:
         raise ValueError("%s: the env-step stride must be >= nb_agents * F" % what)
-    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.device != dev or not index.is_contiguous()):
-        raise ValueError("%s: index must be a contiguous int64 [B] tensor on the device" % what)
+    L.check_index(index, dev, what)
     ld = int(state.stride(0)) if M > 1 else N * F_len
     return dev, M, ld, (int(index.shape[0]) if index is not None else M)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch.Tensor, agent: int, noise: torch.Tensor,
@@ -144,17 +126,17 @@ def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch
     if why:
         raise ValueError("%s: %s" % (what, why))
     dev, M, ld, B = _check_steps(tgt_actor, next_state, index, N, what)
-    _whole(reward, torch.float32, M * N, dev, what, "reward")
-    _whole(noise, torch.float32, B * N * 2, dev, what, "noise")
+    L.whole(reward, torch.float32, M * N, dev, what, "reward")
+    L.whole(noise, torch.float32, B * N * 2, dev, what, "noise")
     lib = nat.load()
-    adesc, cdesc = _desc(tgt_actor), _desc(tgt_critic)
+    adesc, cdesc = L.mlp_desc(L.fc_layers(tgt_actor)), L.mlp_desc(L.fc_layers(tgt_critic))
     y = torch.empty(B, dtype=torch.float32, device=dev)
     next_q = torch.empty(B, dtype=torch.float32, device=dev)
     next_action = torch.empty((B, N), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.mdr_maddpg_target(C.byref(adesc), C.byref(cdesc), _ptr(next_state), ld, _ptr(reward), _ptr(index), B, N, int(agent),
-                                   _ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, _ptr(y), _ptr(next_q), _ptr(next_action),
-                                   _stream(dev))
+        rc = lib.mdr_maddpg_target(C.byref(adesc), C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
+                                   L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q), L.ptr(next_action),
+                                   L.stream(dev))
     nat.check(lib, None, rc, "mdr_maddpg_target")
     return y, next_q, next_action
 
@@ -171,19 +153,19 @@ def joint_q_loss_backward(actor, critic, state: torch.Tensor, action: torch.Tens
     if why:
         raise ValueError("%s: %s" % (what, why))
     dev, M, ld, B = _check_steps(actor, state, index, N, what)
-    _whole(action, torch.int64, M * N, dev, what, "action")
-    _whole(y, torch.float32, B, dev, what, "y")
+    L.whole(action, torch.int64, M * N, dev, what, "action")
+    L.whole(y, torch.float32, B, dev, what, "y")
     lib = nat.load()
-    adesc, cdesc = _desc(actor), _desc(critic)
-    flat = _flat_grad(critic, lib, cdesc, floats=int(lib.mdr_maddpg_grad_floats(C.byref(cdesc))))
-    ws = _workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
+    adesc, cdesc = L.mlp_desc(L.fc_layers(actor)), L.mlp_desc(L.fc_layers(critic))
+    flat = L.flat_grad(critic, lib.mdr_maddpg_grad_floats(C.byref(cdesc)), dev)
+    ws = L.workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_maddpg_critic_grad(C.byref(cdesc), _ptr(state), ld, _ptr(action), _ptr(index), B, N, _ptr(y), max_workgroups, _ptr(ws),
-                                        _ptr(flat), _ptr(loss), _ptr(q), _stream(dev))
+        rc = lib.mdr_maddpg_critic_grad(C.byref(cdesc), L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, L.ptr(y), max_workgroups, L.ptr(ws),
+                                        L.ptr(flat), L.ptr(loss), L.ptr(q), L.stream(dev))
     nat.check(lib, None, rc, "mdr_maddpg_critic_grad")
-    _publish(critic, flat)
+    L.publish(L.mlp_params(L.fc_layers(critic)), flat, L.KEEP)
     return (loss, q) if want_q else loss
 
 
@@ -198,75 +180,41 @@ def actor_loss_backward(actor, critic, state: torch.Tensor, action: torch.Tensor
     if why:
         raise ValueError("%s: %s" % (what, why))
     dev, M, ld, B = _check_steps(actor, state, index, N, what)
-    _whole(action, torch.int64, M * N, dev, what, "action")
-    _whole(noise, torch.float32, B * 2, dev, what, "noise")
+    L.whole(action, torch.int64, M * N, dev, what, "action")
+    L.whole(noise, torch.float32, B * 2, dev, what, "noise")
     lib = nat.load()
-    adesc, cdesc = _desc(actor), _desc(critic)
-    flat = _flat_grad(actor, lib, adesc, floats=int(lib.mdr_maddpg_grad_floats(C.byref(adesc))))
-    ws = _workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
+    adesc, cdesc = L.mlp_desc(L.fc_layers(actor)), L.mlp_desc(L.fc_layers(critic))
+    flat = L.flat_grad(actor, lib.mdr_maddpg_grad_floats(C.byref(adesc)), dev)
+    ws = L.workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
     logits = torch.empty((B, 2), dtype=torch.float32, device=dev) if want_q else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_maddpg_actor_grad(C.byref(adesc), C.byref(cdesc), _ptr(state), ld, _ptr(action), _ptr(index), B, N, int(agent),
-                                       _ptr(noise), C.c_float(tau), C.c_float(pse), max_workgroups, _ptr(ws), _ptr(flat), _ptr(loss),
-                                       _ptr(q), _ptr(logits), _stream(dev))
+        rc = lib.mdr_maddpg_actor_grad(C.byref(adesc), C.byref(cdesc), L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, int(agent),
+                                       L.ptr(noise), C.c_float(tau), C.c_float(pse), max_workgroups, L.ptr(ws), L.ptr(flat), L.ptr(loss),
+                                       L.ptr(q), L.ptr(logits), L.stream(dev))
     nat.check(lib, None, rc, "mdr_maddpg_actor_grad")
-    _publish(actor, flat)
+    L.publish(L.mlp_params(L.fc_layers(actor)), flat, L.KEEP)
     return (loss, q, logits) if want_q else loss
 
 
-class JointReplayBuffer:
+class JointReplayBuffer(L.RingBuffer):
     """The N per-agent ``Buffer``s of ddpg.py:208-213, 250-262 (which always hold the same env-steps) as one ring over env-steps on
-    ``device``: ``state`` / ``next_state`` [capacity, N, F], ``action`` int64 [capacity, N], ``reward`` [capacity, N]; the oldest
-    env-steps are overwritten first.  The fill count and the ring position live on the host; no call synchronises."""
+    ``device`` (``_learner.RingBuffer``): ``state`` / ``next_state`` [capacity, N, F], ``action`` int64 [capacity, N], ``reward``
+    [capacity, N].  ``push``: ``n`` env-steps at once, ``state`` / ``next_state`` [n, N, F], ``action`` / ``reward`` [n, N];
+    ``push_batch``: the dict of ``collect_maddpg_transitions`` (``state`` [T + 1, E, N, F]), stored in (t, env) order."""
 
     def __init__(self, capacity: int, nb_agents: int, num_state: int, device):
         if int(capacity) <= 0 or int(nb_agents) <= 0 or int(num_state) <= 0:
             raise ValueError("JointReplayBuffer: capacity, nb_agents and num_state must be positive")
-        self.capacity, self.nb_agents, self.num_state = int(capacity), int(nb_agents), int(num_state)
-        self.device = torch.device(device)
-        shape = (self.capacity, self.nb_agents)
-        self.state = torch.zeros(shape + (self.num_state,), dtype=torch.float32, device=self.device)
-        self.next_state = torch.zeros(shape + (self.num_state,), dtype=torch.float32, device=self.device)
-        self.action = torch.zeros(shape, dtype=torch.int64, device=self.device)
-        self.reward = torch.zeros(shape, dtype=torch.float32, device=self.device)
-        self._len = 0
-        self._pos = 0      # where the next env-step goes
+        self.nb_agents = int(nb_agents)
+        super().__init__(capacity, (self.nb_agents,), num_state, device)
 
-    def __len__(self) -> int:
-        return self._len
-
-    def push(self, state: torch.Tensor, action: torch.Tensor, reward: torch.Tensor, next_state: torch.Tensor) -> None:
-        """``n`` env-steps at once (``state`` / ``next_state`` [n, N, F], ``action`` / ``reward`` [n, N]), in row order, at the ring
-        position with wrap-around; of a push larger than the capacity the last ``capacity`` env-steps stay."""
-        n = int(state.shape[0])
+    def _rows(self, n, state, next_state, action, reward):
         s3, s2 = (n, self.nb_agents, self.num_state), (n, self.nb_agents)
         if state.shape != s3 or next_state.shape != s3 or action.shape != s2 or reward.shape != s2:
             raise ValueError("JointReplayBuffer.push: state / next_state [n, %d, %d], action and reward [n, %d]" % (s3[1], s3[2], s3[1]))
-        skip = max(n - self.capacity, 0)
-        kept = n - skip
-        first = min(kept, self.capacity - self._pos)      # env-steps up to the end of the ring; the rest wraps to its start
-        for dst, src in zip((self.state, self.next_state, self.action, self.reward), (state, next_state, action, reward)):
-            dst[self._pos:self._pos + first].copy_(src[skip:skip + first])
-            if kept > first:
-                dst[:kept - first].copy_(src[skip + first:])
-        self._pos = (self._pos + kept) % self.capacity
-        self._len = min(self._len + kept, self.capacity)
-
-    def push_batch(self, batch: Dict[str, torch.Tensor]) -> None:
-        """The dict of ``collect_maddpg_transitions`` (``state`` [T + 1, E, N, F], ``action``, ``reward`` [T, E, N]): ``state[t + 1]``
-        is ``next_state[t]``; the T E env-steps are stored in (t, env) order."""
-        states = batch["state"]
-        T = states.shape[0] - 1
-        N, F_len = states.shape[-2], states.shape[-1]
-        self.push(states[:T].reshape(-1, N, F_len), batch["action"].reshape(-1, N), batch["reward"].reshape(-1, N),
-                  states[1:].reshape(-1, N, F_len))
-
-    def chronological(self) -> torch.Tensor:
-        """The positions of the stored env-steps, oldest first (int64 on the device, computed from the host's counters)."""
-        idx = torch.arange(self._len, dtype=torch.int64, device=self.device)
-        return (idx + self._pos) % self.capacity if self._len == self.capacity else idx
+        return state, next_state, action, reward
 
     def sample(self, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """``batch_size`` distinct positions (int64 on the device) drawn uniformly from the filled part WITHOUT replacement, as
@@ -291,13 +239,10 @@ class MADDPGLearner:
     def __init__(self, actor, critic, nb_agents: int, lr_actor: float, lr_critic: float, gamma: float = 0.99, soft_tau: float = 0.01,
                  gumbel_tau: float = 1.0, batch_size: int = 64, buffer_capacity: int = 524288, backend: str = "auto",
                  optimizer=torch.optim.Adam):
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        L.check_backend(backend)
         if backend == "hip":
-            why = _refusal(actor, critic, nb_agents)
-            if why:
-                raise ValueError("MADDPGLearner(backend='hip'): " + why)
-        fa, fc = _linears(actor), _linears(critic)
+            L.require(_refusal(actor, critic, nb_agents), "MADDPGLearner")
+        fa, fc = L.fc_layers(actor), L.fc_layers(critic)
         if fa is None or fc is None:
             raise ValueError("MADDPGLearner: actor and critic need the reference's Linear-ReLU-Linear-ReLU-Linear stack (DDPGNetworkMLP)")
         self.actor, self.critic, self.nb_agents = actor, critic, int(nb_agents)
@@ -344,8 +289,7 @@ class MADDPGLearner:
         ``-log(Exp(1))`` (what ``F.gumbel_softmax`` draws) float32 [N, B, N + 1, 2]: [a, :, :N] for the target actor's picks of agent
         a's update, [a, :, N] for the actor's own sample."""
         dev, N, B = self.buffer.device, self.nb_agents, self.batch_size
-        gen = torch.Generator(device=dev)
-        gen.manual_seed((int(seed) * 1000003 + self.training_step * 7919 + 12345) & (2 ** 63 - 1))
+        gen = L.seeded_generator(seed, self.training_step, dev)
         index = torch.stack([self.buffer.sample(B, gen) for _ in range(N)])
         noise = -torch.empty((N, B, N + 1, 2), dtype=torch.float32, device=dev).exponential_(generator=gen).log()
         return index, noise[:, :, :N].contiguous(), noise[:, :, N].contiguous()
@@ -358,26 +302,18 @@ class MADDPGLearner:
         y_hard = torch.zeros_like(logits).scatter_(-1, index, 1.0)
         return y_hard - y_soft.detach() + y_soft
 
-    @torch.no_grad()
     def update_target(self) -> None:
         """ddpg.py:167-174: to = soft_tau * from + (1 - soft_tau) * to over both pairs of nets."""
         for tgt, net in ((self.tgt_actor, self.actor), (self.tgt_critic, self.critic)):
-            target = [p for lin in tgt.fc for p in (lin.weight, lin.bias)]
-            new = [p for lin in net.fc for p in (lin.weight, lin.bias)]
-            torch._foreach_mul_(target, 1.0 - self.soft_tau)
-            torch._foreach_add_(target, new, alpha=self.soft_tau)
+            L.blend(L.mlp_params(tgt.fc), L.mlp_params(net.fc), self.soft_tau)
 
     def _step(self, opt, net, blend_target) -> None:
-        """clip_grad_norm_(0.5) and the optimiser step of one net; ``blend_target``: the target net whose blend rides on this step."""
-        if isinstance(opt, FusedAdam):
-            if blend_target is not None:
-                opt.step(max_grad_norm=self.MAX_GRAD_NORM, target=[p for lin in blend_target.fc for p in (lin.weight, lin.bias)],
-                         tau=self.soft_tau)
-            else:
-                opt.step(max_grad_norm=self.MAX_GRAD_NORM)
+        """clip_grad_norm_(0.5) and the optimiser step of one net; ``blend_target``: the target net whose blend rides on this step
+        (a FusedAdam's; None: no blend)."""
+        if blend_target is not None:
+            L.clip_and_step(opt, net.parameters(), self.MAX_GRAD_NORM, target=L.mlp_params(blend_target.fc), tau=self.soft_tau)
         else:
-            nn.utils.clip_grad_norm_(net.parameters(), self.MAX_GRAD_NORM)
-            opt.step()
+            L.clip_and_step(opt, net.parameters(), self.MAX_GRAD_NORM)
 
     def critic_backward(self, agent: int, index: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
         """Target, mse loss and backward of the critic for agent ``agent`` on the env-steps at ``index``: fills the critic's ``.grad``."""
@@ -443,13 +379,9 @@ class MADDPGLearner:
             if self.before_step is not None:
                 self.before_step(self, "actor", a)
             self._step(self.actor_optimizer, self.actor, self.tgt_actor if last and fused_a else None)
-        if not (fused_a and fused_c):
-            with torch.no_grad():
-                for tgt, net, done in ((self.tgt_actor, self.actor, fused_a), (self.tgt_critic, self.critic, fused_c)):
-                    if not done:
-                        target = [p for lin in tgt.fc for p in (lin.weight, lin.bias)]
-                        torch._foreach_mul_(target, 1.0 - self.soft_tau)
-                        torch._foreach_add_(target, [p for lin in net.fc for p in (lin.weight, lin.bias)], alpha=self.soft_tau)
+        for tgt, net, done in ((self.tgt_actor, self.actor, fused_a), (self.tgt_critic, self.critic, fused_c)):
+            if not done:      # the blend did not ride on this net's last step
+                L.blend(L.mlp_params(tgt.fc), L.mlp_params(net.fc), self.soft_tau)
         self.training_step += 1
         return torch.stack(a_losses), torch.stack(c_losses)
 

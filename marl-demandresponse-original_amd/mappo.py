@@ -10,10 +10,12 @@ neither read nor needed.  ``MAPPOLearner`` is the loop; clipping and Adam stay t
 from __future__ import annotations
 
 import ctypes as C
+from functools import partial
 from typing import Dict, Optional, Tuple
 
 import torch
 
+from . import _learner as L
 from . import _native as nat
 from . import ppo
 from .ppo import PPOLearner
@@ -29,14 +31,14 @@ AUTO_MIN_ROWS_WIDE = 1
 def _joint_refusal(critic, num_state: int, wide: bool = False) -> Optional[str]:
     """Why the joint-input kernel does not take ``critic`` over states of ``num_state`` features (None: it does).  ``wide``: the
     LDS fit of mdr_mappo_critic_grad_wide's layout; the 128 joint inputs are the limit of both."""
-    why = ppo._refusal(critic, 1, max_state=MAX_JOINT)
+    why = ppo.refusal(critic, 1, max_state=MAX_JOINT)
     if why:
         return why
     J = critic.fc[0].in_features
     nb_agents = J - int(num_state) + 1
     if num_state < 1 or nb_agents < 1:
         return "a critic of %d inputs over states of %d features leaves no whole number of other agents" % (J, num_state)
-    if ppo._fn(nat.load(), "mdr_mappo_critic_grad_floats", wide)(C.byref(ppo._desc(critic)), nb_agents) < 0:
+    if L.fn(nat.load(), "mdr_mappo_critic_grad_floats", wide)[0](C.byref(L.mlp_desc(L.fc_layers(critic))), nb_agents) < 0:
         return ("%d joint inputs with hidden layers of %d and %d units do not fit the kernel's LDS layout"
                 % (J, critic.fc[0].out_features, critic.fc[1].out_features))
     return None
@@ -62,6 +64,23 @@ def gather_others(action: torch.Tensor, nb_agents: int, index: Optional[torch.Te
     return action.reshape(-1)[(j[:, None] - a) + k + (k >= a).to(k.dtype)]
 
 
+def _joint_sizes(desc, nb_rows: int, max_workgroups: int = 0, *, nb_agents: int, wide: bool = False) -> Tuple[int, int]:
+    """(floats of the flat gradient, bytes of workspace) of the joint critic's call over ``nb_rows`` rows."""
+    lib = nat.load()
+    return (int(L.fn(lib, "mdr_mappo_critic_grad_floats", wide)[0](C.byref(desc), nb_agents)),
+            int(L.fn(lib, "mdr_mappo_critic_workspace_bytes", wide)[0](C.byref(desc), nb_agents, nb_rows, max_workgroups)))
+
+
+def _joint_critic_launch(desc, state, ld, action, target, index, B, workspace, flat, loss, value, adv, stream, max_workgroups=0, *, nb_agents,
+                         wide=False) -> None:
+    """mdr_mappo_critic_grad[_wide] on checked tensors (``action``: the whole buffer, one element per transition), under the device
+    of ``state``: the eager call and the captured one.  The argument list of ``ppo._critic_launch``."""
+    lib = nat.load()
+    call, name = L.fn(lib, "mdr_mappo_critic_grad", wide)
+    nat.check(lib, None, call(C.byref(desc), L.ptr(state), ld, L.ptr(action), action.numel(), nb_agents, L.ptr(index), B, L.ptr(target),
+                              max_workgroups, L.ptr(workspace), L.ptr(flat), L.ptr(loss), L.ptr(value), L.ptr(adv), stream), name)
+
+
 def joint_critic_loss_backward(critic, state: torch.Tensor, action: torch.Tensor, target: torch.Tensor, nb_agents: Optional[int] = None,
                                index: Optional[torch.Tensor] = None, max_workgroups: int = 0,
                                wide: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -75,7 +94,7 @@ def joint_critic_loss_backward(critic, state: torch.Tensor, action: torch.Tensor
     if state.dim() != 2:
         raise ValueError("%s: state must be a float32 [M, F] tensor" % what)
     F_len = int(state.shape[1])
-    fc = ppo._layers(critic)
+    fc = L.fc_layers(critic)
     if nb_agents is None and fc is not None:
         nb_agents = fc[0].in_features - F_len + 1
     why = _joint_refusal(critic, F_len, wide=wide)
@@ -85,26 +104,21 @@ def joint_critic_loss_backward(critic, state: torch.Tensor, action: torch.Tensor
         raise ValueError("%s: a critic of %d inputs over states of %d features has %d agents, not %d"
                          % (what, fc[0].in_features, F_len, fc[0].in_features - F_len + 1, nb_agents))
     N = int(nb_agents)
-    dev, M, ld, B = ppo._check_rows(critic, state, index, what, num_state=F_len)
+    dev, M, ld, B = L.check_rows(fc, state, index, what, num_state=F_len)
     if M % N:
         raise ValueError("%s: a buffer of %d transitions is no whole number of env-steps of %d agents" % (what, M, N))
-    ppo._whole(action, torch.int64, M, dev, what, "action")
-    ppo._whole(target, torch.float32, M, dev, what, "target")
-    lib = nat.load()
-    desc = ppo._desc(critic)
-    flat = ppo._flat_grad(critic, lib, desc, floats=ppo._fn(lib, "mdr_mappo_critic_grad_floats", wide)(C.byref(desc), N))
-    ws = ppo._workspace(dev, int(ppo._fn(lib, "mdr_mappo_critic_workspace_bytes", wide)(C.byref(desc), N, B, max_workgroups)))
+    L.whole(action, torch.int64, M, dev, what, "action")
+    L.whole(target, torch.float32, M, dev, what, "target")
+    desc = L.mlp_desc(fc)
+    floats, nbytes = _joint_sizes(desc, B, max_workgroups, nb_agents=N, wide=wide)
+    flat = L.flat_grad(critic, floats, dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     value = torch.empty(B, dtype=torch.float32, device=dev)
     adv = torch.empty(B, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = ppo._fn(lib, "mdr_mappo_critic_grad", wide)(
-            C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(action.data_ptr()), M, N,
-            C.c_void_p(index.data_ptr()) if index is not None else None, B, C.c_void_p(target.data_ptr()),
-            max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
-            C.c_void_p(value.data_ptr()), C.c_void_p(adv.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    nat.check(lib, None, rc, ppo._WIDE["mdr_mappo_critic_grad"] if wide else "mdr_mappo_critic_grad")
-    ppo._publish(critic, flat)
+        _joint_critic_launch(desc, state, ld, action, target, index, B, L.workspace(dev, nbytes), flat, loss, value, adv, L.stream(dev),
+                             max_workgroups, nb_agents=N, wide=wide)
+    L.publish(L.mlp_params(fc), flat, L.KEEP)
     return loss, value, adv
 
 
@@ -121,9 +135,8 @@ class MAPPOLearner(PPOLearner):
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
                  ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
                  sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False):
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
-        afc, cfc = ppo._layers(actor), ppo._layers(critic)
+        L.check_backend(backend)
+        afc, cfc = L.fc_layers(actor), L.fc_layers(critic)
         if afc is None or cfc is None:
             raise ValueError("MAPPOLearner: actor and critic must be Linear-ReLU-Linear-ReLU-Linear (an `fc` ModuleList of three biased Linear layers)")
         self.num_state = afc[0].in_features
@@ -131,9 +144,7 @@ class MAPPOLearner(PPOLearner):
         if self.nb_agents < 1:
             raise ValueError("MAPPOLearner: the critic takes num_state + nb_agents - 1 = %d + N - 1 inputs, not %d" % (self.num_state, cfc[0].in_features))
         if backend == "hip":
-            why = ppo._refusal(actor, 2, wide=wide) or _joint_refusal(critic, self.num_state, wide=wide)
-            if why:
-                raise ValueError("MAPPOLearner(backend='hip'): " + why)
+            L.require(ppo.refusal(actor, 2, wide=wide) or _joint_refusal(critic, self.num_state, wide=wide), "MAPPOLearner")
         # the base class checks PPO's critic (over the state alone) for "hip": this one's is checked above
         super().__init__(actor, critic, lr_actor, lr_critic, clip_param=clip_param, max_grad_norm=max_grad_norm, ppo_update_time=ppo_update_time,
                          batch_size=batch_size, backend="auto" if backend == "hip" else backend, optimizer=optimizer, sampler=sampler, graph=graph,
@@ -152,23 +163,16 @@ class MAPPOLearner(PPOLearner):
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
-            wide = getattr(self, "wide", False)
-            return (ppo._refusal(self.actor, 2, wide=wide) is None and _joint_refusal(self.critic, self.num_state, wide=wide) is None
-                    and nb_rows >= (AUTO_MIN_ROWS_WIDE if wide else AUTO_MIN_ROWS))
+            return (ppo.refusal(self.actor, 2, wide=self.wide) is None and _joint_refusal(self.critic, self.num_state, wide=self.wide) is None
+                    and nb_rows >= (AUTO_MIN_ROWS_WIDE if self.wide else AUTO_MIN_ROWS))
         return self.backend == "hip"
 
     def critic_backward(self, state, action, target, index):
         return joint_critic_loss_backward(self.critic, state, action, target, nb_agents=self.nb_agents, index=index, wide=self.wide)
 
-    def _critic_grad_floats(self, lib, desc) -> int:
-        return int(ppo._fn(lib, "mdr_mappo_critic_grad_floats", self.wide)(C.byref(desc), self.nb_agents))
-
-    def _critic_workspace_bytes(self, lib, desc, nb_rows: int) -> int:
-        return int(ppo._fn(lib, "mdr_mappo_critic_workspace_bytes", self.wide)(C.byref(desc), self.nb_agents, nb_rows, 0))
-
-    def _critic_launch(self, lib, desc, state, ld, action, nb_transitions, target, index, nb_rows, workspace, grad, loss, value, adv, stream) -> int:
-        return ppo._fn(lib, "mdr_mappo_critic_grad", self.wide)(C.byref(desc), state, ld, action, nb_transitions, self.nb_agents, index, nb_rows,
-                                                                target, 0, workspace, grad, loss, value, adv, stream)
+    def _critic_kernel(self):
+        return (partial(_joint_sizes, nb_agents=self.nb_agents, wide=self.wide),
+                partial(_joint_critic_launch, nb_agents=self.nb_agents, wide=self.wide))
 
     def critic_input(self, state, action, index) -> torch.Tensor:
         """agents/mappo.py:87: torch.cat((state[index], others_actions[index]), dim=1)."""

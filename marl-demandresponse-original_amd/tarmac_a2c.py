@@ -23,9 +23,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _learner as L
 from . import _native as nat
-from .optim import FusedAdam
-from .ppo import PPOLearner, _workspace
 
 # the kernels' limits (include/mdr_policy.h: mdr_tarmac_a2c_*)
 MAX_OBS, MAX_COMM, MAX_STATE, MAX_KEY, MAX_AGENTS = 128, 32, 128, 16, 64
@@ -151,12 +150,10 @@ class TarMACA2CPolicy(nn.Module):
         logits = torch.empty((E * N, 2), dtype=torch.float32, device=dev)
         value = torch.empty(E, dtype=torch.float32, device=dev)
         x = torch.empty((E * N, self.state_size), dtype=torch.float32, device=dev) if want_x else None
-        ws = None if want_x else _workspace(dev, int(lib.mdr_tarmac_a2c_workspace_bytes(C.byref(desc), E, N, 0)))
+        ws = None if want_x else L.workspace(dev, int(lib.mdr_tarmac_a2c_workspace_bytes(C.byref(desc), E, N, 0)))
         with torch.cuda.device(dev):
-            rc = lib.mdr_tarmac_a2c_forward(C.byref(desc), C.c_void_p(obs.data_ptr()), self.nb_obs, C.c_void_p(comm_in.data_ptr()),
-                                            int(comm_in.stride(1)), None, E, N, 0, C.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                            C.c_void_p(logits.data_ptr()), C.c_void_p(value.data_ptr()),
-                                            C.c_void_p(x.data_ptr()) if want_x else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = lib.mdr_tarmac_a2c_forward(C.byref(desc), L.ptr(obs), self.nb_obs, L.ptr(comm_in), int(comm_in.stride(1)), None, E, N, 0, L.ptr(ws),
+                                            L.ptr(logits), L.ptr(value), L.ptr(x), L.stream(dev))
         nat.check(lib, None, rc, "mdr_tarmac_a2c_forward")
         return logits, value, x
 
@@ -176,8 +173,7 @@ class TarMACA2CPolicy(nn.Module):
         lib = nat.load()
         desc = _desc(self)
         with torch.cuda.device(dev):
-            rc = lib.mdr_tarmac_a2c_comm(C.byref(desc), C.c_void_p(x.data_ptr()), E, N, 0, C.c_void_p(out.data_ptr()), int(out.stride(1)),
-                                         C.c_void_p(attn.data_ptr()) if want_attn else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = lib.mdr_tarmac_a2c_comm(C.byref(desc), L.ptr(x), E, N, 0, L.ptr(out), int(out.stride(1)), L.ptr(attn), L.stream(dev))
         nat.check(lib, None, rc, "mdr_tarmac_a2c_comm")
         return (out, attn) if want_attn else out
 
@@ -209,10 +205,8 @@ class TarMACA2CPolicy(nn.Module):
             a_prob = torch.empty(E * N, dtype=torch.float32, device=dev)
         lib = nat.load()
         with torch.cuda.device(dev):
-            rc = lib.mdr_logits_sample(C.c_void_p(logits.data_ptr()), 2, E * N, C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                       C.c_uint64(int(step) & (2 ** 64 - 1)), C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None,
-                                       int(bool(greedy)), C.c_void_p(action.data_ptr()), C.c_void_p(a_prob.data_ptr()), None,
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = lib.mdr_logits_sample(L.ptr(logits), 2, E * N, C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(step) & (2 ** 64 - 1)),
+                                       L.ptr(step_dev), int(bool(greedy)), L.ptr(action), L.ptr(a_prob), None, L.stream(dev))
         nat.check(lib, None, rc, "mdr_logits_sample")
         if kernels:
             comm_out = self.comm_kernel(x, E, N, out=comm_out)
@@ -306,41 +300,23 @@ def loss_backward(policy, obs: torch.Tensor, comm: torch.Tensor, action: torch.T
     Mc, Nc, ld_comm = _rows(comm, policy.comm_size, what, "comm", dev)
     if (Mc, Nc) != (M, N):
         raise ValueError("%s: comm must hold the same [M, N] env-steps as obs" % what)
-    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.device != dev or not index.is_contiguous()):
-        raise ValueError("%s: index must be a contiguous int64 [B] tensor on the device" % what)
+    L.check_index(index, dev, what)
     B = int(index.shape[0]) if index is not None else M
-    for name, t, dt in (("action", action, torch.int64), ("ret", ret, torch.float32)):
-        if t.dtype != dt or t.device != dev or t.numel() != M * N or not t.is_contiguous():
-            raise ValueError("%s: %s must be a contiguous %s tensor of %d elements on the device" % (what, name, str(dt).replace("torch.", ""), M * N))
+    L.whole(action, torch.int64, M * N, dev, what, "action")
+    L.whole(ret, torch.float32, M * N, dev, what, "ret")
     lib = nat.load()
     desc = _desc(policy)
-    flat = getattr(policy, "_mdr_flat_grad", None)
-    n = int(lib.mdr_tarmac_a2c_grad_floats(C.byref(desc)))
-    if flat is None or flat.numel() != n or flat.device != dev:
-        flat = policy._mdr_flat_grad = torch.empty(n, dtype=torch.float32, device=dev)
-    nbytes = int(lib.mdr_tarmac_a2c_workspace_bytes(C.byref(desc), B, N, max_workgroups))
-    if nbytes < 0:
-        raise ValueError("%s: mdr_tarmac_a2c_workspace_bytes refused the sizes" % what)
-    ws = _workspace(dev, nbytes)
+    flat = L.flat_grad(policy, lib.mdr_tarmac_a2c_grad_floats(C.byref(desc)), dev)
+    ws = L.workspace(dev, L.sized(lib.mdr_tarmac_a2c_workspace_bytes(C.byref(desc), B, N, max_workgroups), what, "mdr_tarmac_a2c_workspace_bytes"))
     losses = torch.empty(3, dtype=torch.float32, device=dev)
     value = torch.empty(B, dtype=torch.float32, device=dev) if want_value else None
     advantage = torch.empty((B, N), dtype=torch.float32, device=dev) if want_value else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_tarmac_a2c_grad(C.byref(desc), C.c_void_p(obs.data_ptr()), ld_obs, C.c_void_p(comm.data_ptr()), ld_comm,
-                                     C.c_void_p(action.data_ptr()), C.c_void_p(ret.data_ptr()),
-                                     C.c_void_p(index.data_ptr()) if index is not None else None, B, N, C.c_float(value_loss_coef),
-                                     C.c_float(entropy_coef), max_workgroups, C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()),
-                                     C.c_void_p(losses.data_ptr()), C.c_void_p(value.data_ptr()) if want_value else None,
-                                     C.c_void_p(advantage.data_ptr()) if want_value else None,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = lib.mdr_tarmac_a2c_grad(C.byref(desc), L.ptr(obs), ld_obs, L.ptr(comm), ld_comm, L.ptr(action), L.ptr(ret), L.ptr(index), B, N,
+                                     C.c_float(value_loss_coef), C.c_float(entropy_coef), max_workgroups, L.ptr(ws), L.ptr(flat), L.ptr(losses),
+                                     L.ptr(value), L.ptr(advantage), L.stream(dev))
     nat.check(lib, None, rc, "mdr_tarmac_a2c_grad")
-    off = 0
-    for p in _reached(policy):
-        view = flat[off:off + p.numel()].view_as(p)
-        off += p.numel()
-        if p.grad is not None and p.grad.data_ptr() != view.data_ptr():
-            p.grad.copy_(view)      # whoever holds the tensor that was there sees the new gradient too
-        p.grad = view
+    L.publish(_reached(policy), flat, L.REPLACE)      # whoever holds a tensor that was there sees the new gradient too
     out = (losses[0], losses[1], losses[2])
     return out + (value, advantage) if want_value else out
 
@@ -370,13 +346,10 @@ class TarMACA2CLearner:
 
     def __init__(self, policy, lr: float = 7e-4, value_loss_coef: float = 0.5, entropy_coef: float = 0.01, max_grad_norm: float = 0.5,
                  nb_updates: int = 10, batch_size: int = 128, backend: str = "auto", optimizer=torch.optim.Adam):
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        L.check_backend(backend)
         if backend == "hip":
-            why = _refusal(policy)
-            if why:
-                raise ValueError("TarMACA2CLearner(backend='hip'): " + why)
-        self.policy = self.actor = policy      # `actor`: what PPOLearner.minibatches reads the device from
+            L.require(_refusal(policy), "TarMACA2CLearner")
+        self.policy = policy
         self.value_loss_coef, self.entropy_coef, self.max_grad_norm = float(value_loss_coef), float(entropy_coef), float(max_grad_norm)
         self.nb_updates, self.batch_size, self.backend = int(nb_updates), int(batch_size), backend
         self.optimizer = optimizer(policy.parameters(), lr)
@@ -396,7 +369,9 @@ class TarMACA2CLearner:
             return AUTO_MIN_AGENT_ROWS <= nb_env_steps * nb_agents <= AUTO_MAX_AGENT_ROWS and _refusal(self.policy, nb_agents) is None
         return self.backend == "hip"
 
-    minibatches = PPOLearner.minibatches      # the sampler, over the stored env-steps
+    def minibatches(self, nb_env_steps: int, seed: int, epoch: int) -> List[torch.Tensor]:
+        """The index tensors of one epoch over the stored env-steps (``_learner.minibatches``, torch's sampler)."""
+        return L.minibatches(next(self.policy.parameters()).device, nb_env_steps, self.batch_size, "torch", seed, epoch)
 
     def step_minibatch(self, obs, comm, action, ret, index) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """One minibatch of a2c_acktr.py:61-107 on the whole buffers ``obs`` [M, N, F], ``comm`` [M, N, C], ``action``, ``ret`` [M, N];
@@ -409,11 +384,7 @@ class TarMACA2CLearner:
             self.optimizer.zero_grad()
             (value_loss * self.value_loss_coef + action_loss - entropy * self.entropy_coef).backward()
             value_loss, action_loss, entropy = value_loss.detach(), action_loss.detach(), entropy.detach()
-        if isinstance(self.optimizer, FusedAdam):      # clip and step in one launch; .grad keeps the unclipped gradient (optim.py)
-            self.optimizer.step(max_grad_norm=self.max_grad_norm)
-        else:
-            nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
-            self.optimizer.step()
+        L.clip_and_step(self.optimizer, self.policy.parameters(), self.max_grad_norm)
         self.training_step += 1
         return value_loss, action_loss, entropy
 

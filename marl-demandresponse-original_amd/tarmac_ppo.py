@@ -18,9 +18,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
+from . import _learner as L
 from . import _native as nat
-from .optim import FusedAdam
-from .ppo import PPOLearner, _whole, _workspace
 from .tarmac import FUSED_MAX_HIDDEN, FUSED_MAX_KEY, FUSED_MAX_OBS, FUSED_MAX_VALUE, MAX_COMM, MODES, TarMACActor
 
 # backend="auto": the kernels from this many env-steps per minibatch on (profiles/tarmac_ppo_README.md: they measured faster than
@@ -90,28 +89,6 @@ def _desc(actor) -> nat.MdrTarmacNet:
                             actor.num_hops, int(actor.with_comm), actor.comm_defect_prob, *ptr)
 
 
-def _flat_grad(actor, lib, desc) -> torch.Tensor:
-    """The flat gradient buffer the kernels write, kept with the module; the reached ``.grad`` are views of it."""
-    dev = actor.obs2hidden[0].weight.device
-    flat = getattr(actor, "_mdr_flat_grad", None)
-    n = int(lib.mdr_tarmac_net_grad_floats(C.byref(desc)))
-    if flat is None or flat.numel() != n or flat.device != dev:
-        flat = torch.empty(n, dtype=torch.float32, device=dev)
-        actor._mdr_flat_grad = flat
-    return flat
-
-
-def _publish(actor, flat: torch.Tensor) -> None:
-    off = 0
-    for p in _params(actor):
-        view = flat[off:off + p.numel()].view_as(p)
-        off += p.numel()
-        if p.grad is None:
-            p.grad = view
-        elif p.grad.data_ptr() != view.data_ptr():
-            p.grad.copy_(view)
-
-
 def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_prob: torch.Tensor, advantage: torch.Tensor,
                         clip_param: float = 0.2, index: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0,
                         want_ratio: bool = False, max_workgroups: int = 0):
@@ -136,33 +113,25 @@ def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_pr
     ld = int(state.stride(1)) if N > 1 else (int(state.stride(0)) if M > 1 else F_len)
     if (F_len > 1 and state.stride(2) != 1) or ld < F_len or (M > 1 and N > 1 and state.stride(0) != N * ld):
         raise ValueError("%s: state rows need unit inner stride and one row stride >= F over all agents" % what)
-    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.device != dev or not index.is_contiguous()):
-        raise ValueError("%s: index must be a contiguous int64 [B] tensor on the device" % what)
+    L.check_index(index, dev, what)
     B = int(index.shape[0]) if index is not None else M
-    for name, t, dt, n in (("action", action, torch.int64, M * N), ("old_prob", old_prob, torch.float32, M * N),
-                           ("advantage", advantage, torch.float32, B * N)):
-        if t.dtype != dt or t.device != dev or t.numel() != n or not t.is_contiguous():
-            raise ValueError("%s: %s must be a contiguous %s tensor of %d elements on the device" % (what, name, str(dt).replace("torch.", ""), n))
+    L.whole(action, torch.int64, M * N, dev, what, "action")
+    L.whole(old_prob, torch.float32, M * N, dev, what, "old_prob")
+    L.whole(advantage, torch.float32, B * N, dev, what, "advantage")
     if not 0.0 <= float(clip_param) < 1.0:
         raise ValueError("%s: clip_param must lie in [0, 1)" % what)
     lib = nat.load()
     desc = _desc(actor)
-    flat = _flat_grad(actor, lib, desc)
-    nbytes = int(lib.mdr_tarmac_ppo_workspace_bytes(C.byref(desc), B, N, max_workgroups))
-    if nbytes < 0:
-        raise ValueError("%s: mdr_tarmac_ppo_workspace_bytes refused the sizes" % what)
-    ws = _workspace(dev, nbytes)
+    flat = L.flat_grad(actor, lib.mdr_tarmac_net_grad_floats(C.byref(desc)), dev)
+    ws = L.workspace(dev, L.sized(lib.mdr_tarmac_ppo_workspace_bytes(C.byref(desc), B, N, max_workgroups), what, "mdr_tarmac_ppo_workspace_bytes"))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ratio = torch.empty((B, N), dtype=torch.float32, device=dev) if want_ratio else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_tarmac_ppo_actor_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None,
-                                           B, N, C.c_void_p(action.data_ptr()), C.c_void_p(old_prob.data_ptr()), C.c_void_p(advantage.data_ptr()),
+        rc = lib.mdr_tarmac_ppo_actor_grad(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, N, L.ptr(action), L.ptr(old_prob), L.ptr(advantage),
                                            C.c_float(clip_param), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(step & (2 ** 64 - 1)), max_workgroups,
-                                           C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
-                                           C.c_void_p(ratio.data_ptr()) if want_ratio else None,
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                           L.ptr(ws), L.ptr(flat), L.ptr(loss), L.ptr(ratio), L.stream(dev))
     nat.check(lib, None, rc, "mdr_tarmac_ppo_actor_grad")
-    _publish(actor, flat)
+    L.publish(_params(actor), flat, L.KEEP)
     return (loss, ratio) if want_ratio else loss
 
 
@@ -174,10 +143,6 @@ def _critic_layers(critic) -> Optional[List[nn.Linear]]:
     if not all(isinstance(m, nn.Linear) and m.bias is not None for m in lin) or not all(isinstance(seq[i], nn.ReLU) for i in (1, 3)):
         return None
     return lin
-
-
-def _critic_params(critic) -> List[torch.Tensor]:
-    return [p for lin in _critic_layers(critic) for p in (lin.weight, lin.bias)]
 
 
 def _critic_refusal(critic) -> Optional[str]:
@@ -196,9 +161,8 @@ def _critic_refusal(critic) -> Optional[str]:
         return "joint input = %d: the kernels cover at most %d columns" % (J, CRITIC_MAX_JOINT)
     if lin[0].out_features > CRITIC_MAX_HIDDEN or lin[1].out_features > CRITIC_MAX_HIDDEN:
         return "hidden layers of %d and %d units: the kernels cover at most %d" % (lin[0].out_features, lin[1].out_features, CRITIC_MAX_HIDDEN)
-    for p in _critic_params(critic):
-        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-            return "parameters must be contiguous float32 tensors on the GPU"
+    if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in L.mlp_params(lin)):
+        return "parameters must be contiguous float32 tensors on the GPU"
     return None
 
 
@@ -206,12 +170,6 @@ def critic_supported(critic) -> bool:
     """Do the critic kernels take this critic?  A ``TarMACCritic`` on N F <= 4096 inputs with hidden layers of at most 256 units (any
     size) and 1 <= N <= 64 agents, float32 on the GPU."""
     return _critic_refusal(critic) is None
-
-
-def _critic_desc(critic) -> nat.MdrMlp:
-    lin = _critic_layers(critic)
-    ptr = [C.c_void_p(p.data_ptr()) for p in _critic_params(critic)]
-    return nat.MdrMlp(C.sizeof(nat.MdrMlp), lin[0].in_features, lin[0].out_features, lin[1].out_features, lin[2].out_features, *ptr)
 
 
 def _critic_steps(critic, state, index, what):
@@ -227,8 +185,7 @@ def _critic_steps(critic, state, index, what):
     M = int(state.shape[0])
     if (F_len > 1 and state.stride(2) != 1) or (N > 1 and state.stride(1) != F_len) or (M > 1 and state.stride(0) < J):
         raise ValueError("%s: state needs contiguous env-steps and an env-step stride >= N F" % what)
-    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.device != dev or not index.is_contiguous()):
-        raise ValueError("%s: index must be a contiguous int64 [B] tensor on the device" % what)
+    L.check_index(index, dev, what)
     ld = int(state.stride(0)) if M > 1 else J
     return dev, M, N, ld, (int(index.shape[0]) if index is not None else M)
 
@@ -239,11 +196,10 @@ def critic_value(critic, state: torch.Tensor, index: Optional[torch.Tensor] = No
     what = "tarmac_ppo.critic_value"
     dev, M, N, ld, B = _critic_steps(critic, state, index, what)
     lib = nat.load()
-    desc = _critic_desc(critic)
+    desc = L.mlp_desc(_critic_layers(critic))
     value = torch.empty((B, N), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.mdr_tarmac_critic_value(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(index.data_ptr()) if index is not None else None,
-                                         B, max_workgroups, C.c_void_p(value.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = lib.mdr_tarmac_critic_value(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, max_workgroups, L.ptr(value), L.stream(dev))
     nat.check(lib, None, rc, "mdr_tarmac_critic_value")
     return value
 
@@ -257,35 +213,20 @@ def critic_loss_backward(critic, state: torch.Tensor, target: torch.Tensor, inde
     place through ``index`` (int64 [B] on the device; None: every env-step in order, B = M)."""
     what = "tarmac_ppo.critic_loss_backward"
     dev, M, N, ld, B = _critic_steps(critic, state, index, what)
-    _whole(target, torch.float32, M * N, dev, what, "target")
+    L.whole(target, torch.float32, M * N, dev, what, "target")
     lib = nat.load()
-    desc = _critic_desc(critic)
-    flat = getattr(critic, "_mdr_flat_grad", None)
-    n = int(lib.mdr_tarmac_critic_grad_floats(C.byref(desc)))
-    if flat is None or flat.numel() != n or flat.device != dev:
-        flat = critic._mdr_flat_grad = torch.empty(n, dtype=torch.float32, device=dev)
-    nbytes = int(lib.mdr_tarmac_critic_workspace_bytes(C.byref(desc), B, max_workgroups))
-    if nbytes < 0:
-        raise ValueError("%s: mdr_tarmac_critic_workspace_bytes refused the sizes" % what)
-    ws = _workspace(dev, nbytes)
+    lin = _critic_layers(critic)
+    desc = L.mlp_desc(lin)
+    flat = L.flat_grad(critic, lib.mdr_tarmac_critic_grad_floats(C.byref(desc)), dev)
+    ws = L.workspace(dev, L.sized(lib.mdr_tarmac_critic_workspace_bytes(C.byref(desc), B, max_workgroups), what, "mdr_tarmac_critic_workspace_bytes"))
     loss = torch.empty((), dtype=torch.float32, device=dev)
     advantage = torch.empty((B, N), dtype=torch.float32, device=dev)
     value = torch.empty((B, N), dtype=torch.float32, device=dev) if want_value else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_tarmac_critic_grad(C.byref(desc), C.c_void_p(state.data_ptr()), ld, C.c_void_p(target.data_ptr()),
-                                        C.c_void_p(index.data_ptr()) if index is not None else None, B, max_workgroups,
-                                        C.c_void_p(ws.data_ptr()), C.c_void_p(flat.data_ptr()), C.c_void_p(loss.data_ptr()),
-                                        C.c_void_p(value.data_ptr()) if want_value else None, C.c_void_p(advantage.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = lib.mdr_tarmac_critic_grad(C.byref(desc), L.ptr(state), ld, L.ptr(target), L.ptr(index), B, max_workgroups, L.ptr(ws), L.ptr(flat),
+                                        L.ptr(loss), L.ptr(value), L.ptr(advantage), L.stream(dev))
     nat.check(lib, None, rc, "mdr_tarmac_critic_grad")
-    off = 0
-    for p in _critic_params(critic):
-        view = flat[off:off + p.numel()].view_as(p)
-        off += p.numel()
-        if p.grad is None:
-            p.grad = view
-        elif p.grad.data_ptr() != view.data_ptr():
-            p.grad.copy_(view)
+    L.publish(L.mlp_params(lin), flat, L.KEEP)
     return (loss, advantage, value) if want_value else (loss, advantage)
 
 
@@ -307,18 +248,12 @@ class TarMACPPOLearner:
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
                  ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
                  critic_backend: str = "torch"):
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
-        if critic_backend not in ("auto", "hip", "torch"):
-            raise ValueError("critic_backend must be 'auto', 'hip' or 'torch'")
+        L.check_backend(backend)
+        L.check_backend(critic_backend, "critic_backend")
         if backend == "hip":
-            why = _refusal(actor)
-            if why:
-                raise ValueError("TarMACPPOLearner(backend='hip'): " + why)
+            L.require(_refusal(actor), "TarMACPPOLearner")
         if critic_backend == "hip":
-            why = _critic_refusal(critic)
-            if why:
-                raise ValueError("TarMACPPOLearner(critic_backend='hip'): " + why)
+            L.require(_critic_refusal(critic), "TarMACPPOLearner", "critic_backend")
         self.actor, self.critic = actor, critic
         self.clip_param, self.max_grad_norm = float(clip_param), float(max_grad_norm)
         self.ppo_update_time, self.batch_size = int(ppo_update_time), int(batch_size)
@@ -346,7 +281,9 @@ class TarMACPPOLearner:
             return CRITIC_AUTO_MIN_ENV_STEPS <= nb_env_steps <= CRITIC_AUTO_MAX_ENV_STEPS and _critic_refusal(self.critic) is None
         return self.critic_backend == "hip"
 
-    minibatches = PPOLearner.minibatches      # the sampler, over the stored env-steps: needs self.actor and self.batch_size only
+    def minibatches(self, nb_env_steps: int, seed: int, epoch: int) -> List[torch.Tensor]:
+        """The index tensors of one epoch over the stored env-steps (``_learner.minibatches``, torch's sampler)."""
+        return L.minibatches(next(self.actor.parameters()).device, nb_env_steps, self.batch_size, "torch", seed, epoch)
 
     def step_minibatch(self, state, action, old_prob, target, index, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """One minibatch of agents/tarmac_ppo.py:159-207.  ``state`` [M, N, F], ``action``, ``old_prob``, ``target`` [M, N]: the whole
@@ -371,20 +308,13 @@ class TarMACPPOLearner:
             self.actor_optimizer.zero_grad()
             action_loss.backward()
             action_loss = action_loss.detach()
-        if isinstance(self.actor_optimizer, FusedAdam):      # clip and step in one launch; .grad keeps the unclipped gradient (optim.py)
-            self.actor_optimizer.step(max_grad_norm=self.max_grad_norm)
-        else:
-            nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad_norm)
-            self.actor_optimizer.step()
+        L.clip_and_step(self.actor_optimizer, self.actor.parameters(), self.max_grad_norm)
         if not critic_kernels:
             value_loss = torch.pow(delta, 2).mean(0).mean(0)
             self.critic_optimizer.zero_grad()
             value_loss.backward()
-        if isinstance(self.critic_optimizer, FusedAdam):      # autograd's own tensors or views of the flat buffer: the segment table covers both
-            self.critic_optimizer.step(max_grad_norm=self.max_grad_norm)
-        else:
-            nn.utils.clip_grad_norm_(self.critic.parameters(), self.max_grad_norm)
-            self.critic_optimizer.step()
+        # (a FusedAdam's segment table covers autograd's own tensors and views of the flat buffer alike)
+        L.clip_and_step(self.critic_optimizer, self.critic.parameters(), self.max_grad_norm)
         self.training_step += 1
         return action_loss, value_loss.detach()
 
@@ -401,14 +331,5 @@ class TarMACPPOLearner:
         action = batch["action"].reshape(-1, N)
         old_prob = batch["a_prob"].reshape(-1, N)
         target = batch["return"].reshape(-1, N)
-        n = state.shape[0]
-        a_sum = torch.zeros((), dtype=torch.float32, device=state.device)
-        c_sum = torch.zeros((), dtype=torch.float32, device=state.device)
-        count = 0
-        for epoch in range(self.ppo_update_time):
-            for index in self.minibatches(n, seed, epoch):
-                a_loss, c_loss = self.step_minibatch(state, action, old_prob, target, index, seed=seed)
-                a_sum += a_loss
-                c_sum += c_loss
-                count += 1
-        return a_sum / max(count, 1), c_sum / max(count, 1), count
+        return L.mean_losses(state.device, 2, self.ppo_update_time, lambda epoch: self.minibatches(state.shape[0], seed, epoch),
+                             lambda index: self.step_minibatch(state, action, old_prob, target, index, seed=seed))
