@@ -24,6 +24,7 @@
  * existing changes): mdr_env_bind_hvac_code - the (Q_hvac, P_max) pair of a house as one byte into a 16-entry dictionary.
  * Likewise mdr_env_tarmac_actor_sample (mdr_policy.h): the TarMAC actor fed from the env's compact state; and
  * mdr_env_bind_thermal_pack with its query mdr_env_rollout_plan: the five thermal columns as one 16-byte record per house.
+ * Likewise mdr_env_rollout_resident: whether mdr_env_rollout keeps the houses in registers between its interior steps.
  */
 #ifndef MDR_H
 #define MDR_H
@@ -317,6 +318,12 @@ int mdr_env_bind_thermal_pack(mdr_env_t *env, uint32_t *pack, uint32_t *desc);
 /* What the interior steps of the next mdr_env_rollout on this handle run: *planes = how many of the five local obs planes they
  * store (-1: the rollout runs full steps only), *packed = 1 when they read the thermal pack.  Either pointer may be NULL. */
 int mdr_env_rollout_plan(const mdr_env_t *env, int32_t *planes, int32_t *packed);
+/* *resident = 1 when the next mdr_env_rollout on this handle runs its interior steps with the houses resident in registers - one
+ * launch per table window instead of one per step, the same bits: wherever mdr_env_rollout_plan reports interior steps (planes >= 0)
+ * and nb_envs * nb_houses is at or above MDR_ROLLOUT_RESIDENT_HOUSES (environment, read once; default 1 << 20; 0 = every batch),
+ * unless MDR_ROLLOUT_RESIDENT (environment, read once) is 0.  mdr_env_rollout_plan's answers are what the per-step form would run;
+ * its `packed` also says whether the resident launches read the thermal pack.  The pointer may be NULL. */
+int mdr_env_rollout_resident(const mdr_env_t *env, int32_t *resident);
 /* Optional: replace ClusterHouses.compute_OD_temp (env 1057-1081, incl. its random.gauss draw 1079) by a table, double [rows][E] deg C (row = time index);
  * NULL restores the model.  Takes effect at the next mdr_env_begin_episode / table refill; mdr_env_reset (a freshly sampled
  * episode) drops it. */

@@ -240,6 +240,13 @@ class BatchedDemandResponseEnv:
         nat.check(self._lib, self._handle, self._lib.mdr_env_rollout_plan(self._handle, C.byref(planes), C.byref(packed)), "mdr_env_rollout_plan")
         return int(planes.value), bool(packed.value)
 
+    def rollout_resident(self) -> bool:
+        """Whether the next ``rollout()`` runs its interior steps with the houses resident in registers, one launch per table window
+        (large batches) - mdr_env_rollout_resident."""
+        resident = C.c_int32()
+        nat.check(self._lib, self._handle, self._lib.mdr_env_rollout_resident(self._handle, C.byref(resident)), "mdr_env_rollout_resident")
+        return bool(resident.value)
+
     def set_obs_planes(self, on: bool) -> None:
         """Switch the seven per-step observation planes on or off (a re-bind: mdr_buffers_t.obs = NULL skips their 28 B per
         house-step).  Switched on again - or on for the first time - they are brought up to date from the current state."""

@@ -862,6 +862,30 @@ static InteriorPlan interior_plan(const mdr_env_t* env) {
   return InteriorPlan{planes, packed ? 1 : 0};
 }
 
+// Whether mdr_env_rollout runs its interior steps with the houses resident in registers (k_rollout_resident): wherever interior steps
+// run at all (interior_plan) and the batch is large.  Read once per process:
+//   MDR_ROLLOUT_RESIDENT         0 = never; unset or 1 = by size
+//   MDR_ROLLOUT_RESIDENT_HOUSES  the threshold in houses (default 1 << 20; 0 = every batch qualifies) - a knob of its own, not
+//                                MDR_ROLLOUT_STREAM_HOUSES: that one at 0 is how a small batch reaches the per-step PACK forms
+static bool rollout_resident(const mdr_env_t* env, const InteriorPlan& ip) {
+  static const bool resident_on = [] { const char* t = getenv("MDR_ROLLOUT_RESIDENT"); return !(t && t[0] == '0' && t[1] == '\0'); }();
+  static const int64_t resident_houses = [] {
+    const char* t = getenv("MDR_ROLLOUT_RESIDENT_HOUSES");
+    if (!t || t[0] < '0' || t[0] > '9') return (int64_t)1 << 20;
+    char* end = nullptr;
+    const long long v = strtoll(t, &end, 10);
+    return (end && *end == '\0' && v >= 0) ? (int64_t)v : (int64_t)1 << 20;
+  }();
+  return resident_on && ip.planes >= 0 && mdr::rollout_resident_supported(env->plan) &&
+         (int64_t)env->cfg.nb_envs * env->cfg.nb_houses >= resident_houses;
+}
+
+int mdr_env_rollout_resident(const mdr_env_t* env, int32_t* resident) {
+  if (!env) return MDR_ERR_INVALID;
+  if (resident) *resident = rollout_resident(env, interior_plan(env)) ? 1 : 0;
+  return MDR_OK;
+}
+
 int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t nb_steps, void* stream) {
   if (!env) return MDR_ERR_INVALID;
   if (nb_steps < 0) return fail(env, MDR_ERR_INVALID, "nb_steps must be >= 0");
@@ -871,10 +895,33 @@ int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t
       mdr_partials_per_env(env->cfg.nb_houses) >= 2 * env->nblk)
     return rollout_split(env, actions, action_source, nb_steps, (hipStream_t)stream);
   // Interior steps: between the steps of this loop nothing can look at reward / obs / actions / P, and the next launch on the stream
-  // overwrites every one of them - so steps 0 .. nb_steps - 2 run the interior form of k_step_fused / k_step_group, which stores none
-  // of the outputs behind the env-wide reduction and only the first `planes` of the five local obs planes, and the last step is a
-  // full one (interior_plan).
+  // overwrites every one of them - so steps 0 .. nb_steps - 2 run an interior form, which stores none of the outputs behind the
+  // env-wide reduction, and the last step is a full one.  Two interior forms, chosen by size (rollout_resident):
+  //   at or above MDR_ROLLOUT_RESIDENT_HOUSES houses   k_rollout_resident: the houses stay in registers over every step the current
+  //       tables cover - the state and the parameters cross HBM once per table window instead of once per step;
+  //   below it   one interior launch of k_step_fused / k_step_group per step (interior_plan), exactly as before.
+  // Why a size rule and not the resident form everywhere: tests/test_gpu_bench.py bounds bench.py's roofline.frac - a fixed 99 B per
+  // house-step over the time - below 1.25 at 512 envs x 1024 houses, and a step that moves no state through memory passes it many
+  // times over.  At or above 1 << 20 houses no test binds and the interior plan already differs (the r08 / r09 criterion).
   const InteriorPlan ip = interior_plan(env);
+  if (rollout_resident(env, ip) && nb_steps > 1) {
+    if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin without step_end");
+    int32_t done = 0;
+    while (done < nb_steps - 1) {
+      mdr::StepArgs a;
+      int rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);   // refills or swaps the tables if the cursor left them
+      if (rc != MDR_OK) return rc;
+      if (!ip.packed) a.thermal_pack = a.thermal_desc = nullptr;   // MDR_THERMAL_PACK=0, a batch below the stream threshold: the columns
+      const int64_t room = env->cfg.table_steps - (env->k - env->j0);   // steps the current tables still cover
+      mdr::RolloutArgs r{};
+      r.nsteps = (int)std::min<int64_t>(room, nb_steps - 1 - done);
+      hipError_t e = mdr::launch_rollout_resident(a, r, env->plan, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(env, e, "rollout_resident");
+      env->k += r.nsteps;
+      done += r.nsteps;
+    }
+    return env_step(env, actions, action_source, stream, 0, 5, 0);
+  }
   for (int32_t i = 0; i < nb_steps; ++i) {
     const bool interior = ip.planes >= 0 && i + 1 < nb_steps;
     int rc = env_step(env, actions, action_source, stream, interior ? 1 : 0, interior ? ip.planes : 5, interior ? ip.packed : 0);

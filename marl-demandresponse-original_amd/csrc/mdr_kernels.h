@@ -279,6 +279,10 @@ hipError_t launch_step_end_begin_split(const StepArgs& finish, const StepArgs& b
 bool rollout_fused_supported(const StepPlan& p);
 hipError_t launch_rollout_accumulate(const StepArgs& a, const RolloutArgs& ro, hipStream_t s);   // after ONE single step
 hipError_t launch_rollout_fused(const StepArgs& a, const RolloutArgs& r, const StepPlan& p, hipStream_t s);
+// k_rollout_resident / k_rollout_resident_group: r.nsteps interior steps of mdr_env_rollout in one launch, by the STEP plan (STEP_FUSED /
+// STEP_GROUP); of `r` only nsteps is read.  a.thermal_desc == nullptr: the five thermal columns are streamed.
+bool rollout_resident_supported(const StepPlan& p);
+hipError_t launch_rollout_resident(const StepArgs& a, const RolloutArgs& r, const StepPlan& p, hipStream_t s);
 hipError_t launch_obs_vector(const ObsArgs& a, int layout, hipStream_t s);
 hipError_t launch_obs_messages(const ObsArgs& a, hipStream_t s);               // msg_ext_out[e][h][:] for the local houses
 hipError_t launch_obs_vector_ext(const ObsArgs& a, int layout, hipStream_t s);  // senders read from msg_ext_in through links
