@@ -545,6 +545,32 @@ int mdr_maddpg_actor_grad(const mdr_mlp_t *actor, const mdr_mlp_t *critic, const
                           float pse, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *q, float *logits,
                           void *stream);
 
+/* ---- Acting with an actor of up to 256 hidden units per layer - MADDPG's (DDPG_prop.actor_hidden_dim = 256; ddpg.py:289-298,
+ * train_ddpg.py:95-116), beyond the MDR_ACTOR_MAX_HIDDEN = 127 of mdr_actor_sample - in ONE launch: observation rows -> Linear - ReLU -
+ * Linear - ReLU - Linear(2) -> softmax -> draw or argmax, for every agent (csrc/mdr_mlp_actor.hip).
+ *
+ * `actor` is the learners' mdr_mlp_t: torch's own layout, w[out][in] contiguous, device memory, read as it is on every call - nothing
+ * is packed on the host, so an optimiser step between two calls is seen by the next call (train_maddpg changes the actor at every
+ * update: the reason not to go through mdr_actor_t's fragment arrays).  Limits: 1 <= num_state = F <= 128 (the 81 / 91 / 121-feature
+ * observations are inside), 1 <= hidden1, hidden2 <= 256, any size (no multiple of 16 needed), num_out == 2.
+ * `obs`: float rows, agent i at obs + i * ld_obs, ld_obs >= F; 4-byte alignment suffices (a 51-float row is 204 bytes).  `action` uint8
+ * [nb_agents], `a_prob` float [nb_agents] (may be NULL), `probs` float [nb_agents][2] (may be NULL).
+ * Semantics, word for word mdr_actor_sample's: d = logit0 - logit1, p0 = 1 / (1 + exp(-d)), p1 = 1 / (1 + exp(d)); the draw of
+ * csrc/mdr_draw.h with the agent's index in the batch as the counter and *step_dev (device int32, may be NULL) added to the low word
+ * of `step`; action = u < p0 ? 0 : 1, a_prob = probs[action].  greedy != 0: d >= 0 ? 0 : 1, no draw.  For equal probabilities
+ * mdr_logits_sample and this call pick the same action for the same (seed, step, agent).
+ * Exact fp32: products on v_mfma_f32_16x16x4_f32, accumulation in fp32 starting from the bias; the head is one dot product with
+ * W3[0] - W3[1] (the difference rounded to fp32) in per-wave partials added in wave order.  No floating-point atomics: an agent's
+ * `probs` bits depend on its row and the weights only - not on its position in the batch, on nb_agents or on the grid.
+ * Persistent workgroups hold their slabs of W1 and W2 in registers - loaded once per launch - and stride over tiles of 32 agents; the
+ * grid is min(tiles, compute units, max_workgroups if > 0).  Stream-ordered, never synchronises, allocates nothing.
+ * Returns 0; -1 (NULL `actor`, a NULL weight pointer, NULL `obs` or `action`, nb_agents < 0, max_workgroups < 0, ld_obs < F, a
+ * struct_size that is not this header's); -3 (HIP error); -4 (a shape outside the limits).  On -1 and -4 nothing was launched and
+ * nothing written.  nb_agents == 0 returns 0 and launches nothing. */
+int mdr_mlp_actor_sample(const mdr_mlp_t *actor, const float *obs, int64_t ld_obs, int64_t nb_agents, uint64_t seed, uint64_t step,
+                         const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob, float *probs,
+                         void *stream);
+
 /* ---- TarMAC-PPO's update step for the actor (TarmacPPO.update, agents/tarmac_ppo.py:168-186): loss and gradient of one minibatch.
  *
  * The actor's weights in torch's own layout - every layer w[out][in] contiguous and its bias, device memory, read as they are on

@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("BatchedDemandResponseEnv", "OBS_COLUMNS"):
         from . import batched_env
         return getattr(batched_env, name)
-    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "maddpg", "optim", "tarmac_a2c", "graph_update"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
+    if name in ("sharding", "comm", "rollout", "policy", "tarmac", "metrics", "montecarlo", "ppo", "tarmac_ppo", "dqn", "mappo", "maddpg", "mlp_actor", "optim", "tarmac_a2c", "graph_update"):      # submodules on first use (mdr_amd.sharding.house_shard ...)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "BatchedMetrics":
@@ -34,6 +34,9 @@ def __getattr__(name):
     if name in ("MADDPGLearner", "DDPGNetworkMLP", "JointReplayBuffer", "GreedyDDPGActor", "train_maddpg"):
         from . import maddpg
         return getattr(maddpg, name)
+    if name == "FusedMLPActor":
+        from .mlp_actor import FusedMLPActor
+        return FusedMLPActor
     if name == "TarMACPPOLearner":
         from .tarmac_ppo import TarMACPPOLearner
         return TarMACPPOLearner

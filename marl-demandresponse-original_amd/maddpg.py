@@ -388,13 +388,28 @@ class MADDPGLearner:
 
 class GreedyDDPGActor:
     """``DDPGAgent.act`` (agents/rl_controllers.py): the argmax of the actor's logits, in the shape ``deploy_policy`` takes through
-    its duck-typed branch - ``.sample(rows, seed, step, action=None, step_dev=None)`` -> uint8 actions."""
+    its duck-typed branch - ``.sample(rows, seed, step, action=None, step_dev=None)`` -> uint8 actions.  ``backend="torch"`` (default):
+    a torch forward and a compare; ``"hip"``: the greedy form of ``FusedMLPActor`` - forward and argmax in one kernel (ValueError for a
+    net it does not take); it honours ``step_dev``, which a greedy pick does not read."""
 
-    def __init__(self, actor):
-        self.actor = actor
+    def __init__(self, actor, backend: str = "torch"):
+        if backend not in ("torch", "hip"):
+            raise ValueError("backend must be 'torch' or 'hip'")
+        self.actor, self.backend = actor, backend
+        self._fused = self._a_prob = None
+        if backend == "hip":
+            from .mlp_actor import FusedMLPActor
+            why = FusedMLPActor.refusal(actor)
+            if why:
+                raise ValueError("GreedyDDPGActor(backend='hip'): " + why)
+            self._fused = FusedMLPActor(actor, greedy=True)
 
     @torch.no_grad()
     def sample(self, rows: torch.Tensor, seed: int = 0, step: int = 0, action: Optional[torch.Tensor] = None, step_dev=None) -> torch.Tensor:
+        if self._fused is not None:
+            if self._a_prob is None or self._a_prob.numel() != rows.shape[0] or self._a_prob.device != rows.device:
+                self._a_prob = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)      # kept: a captured step allocates nothing
+            return self._fused.sample(rows, seed, step, step_dev=step_dev, action=action, a_prob=self._a_prob)[0]
         logits = self.actor(rows)
         act = logits[:, 1] > logits[:, 0]      # argmax keeps the first maximum
         if action is None:
@@ -403,18 +418,19 @@ class GreedyDDPGActor:
         return action
 
 
-def train_maddpg(env, learner: MADDPGLearner, nb_steps: int, update_every: int = 1, random_steps: int = 0, seed: int = 0
-                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+def train_maddpg(env, learner: MADDPGLearner, nb_steps: int, update_every: int = 1, random_steps: int = 0, seed: int = 0,
+                 actor_backend: str = "torch") -> Tuple[torch.Tensor, torch.Tensor]:
     """The loop of train_ddpg.py:95-131 on a batched env (reset by the caller): every iteration one ``collect_maddpg_transitions``
     step of all envs (uniformly random actions while the 1-based step is below ``random_steps``, the actor's gumbel sample after), ``store``, and
-    after every ``update_every``-th step from ``random_steps`` on one ``update()`` (which ends with the target blend).  -> (actor losses
-    [n, N], critic losses [n, N]) of the updates that ran, on the device."""
+    after every ``update_every``-th step from ``random_steps`` on one ``update()`` (which ends with the target blend).
+    ``actor_backend`` is ``collect_maddpg_transitions``': "hip" acts through ``FusedMLPActor``, which reads the actor's weights in
+    place and so sees every update.  -> (actor losses [n, N], critic losses [n, N]) of the updates that ran, on the device."""
     from .rollout import collect_maddpg_transitions
     a_losses, c_losses = [], []
     for t in range(int(nb_steps)):
         step = t + 1      # train_ddpg.py:96-97, 124-127: random while step < random_steps, learn from step >= random_steps on
         batch = collect_maddpg_transitions(env, learner.actor, 1, random_steps_left=max(int(random_steps) - step, 0),
-                                           seed=(int(seed) * 1000003 + t) & (2 ** 63 - 1))
+                                           seed=(int(seed) * 1000003 + t) & (2 ** 63 - 1), actor_backend=actor_backend)
         learner.store(batch)
         if step >= int(random_steps) and step % int(update_every) == 0:
             out = learner.update(seed=seed)

@@ -443,17 +443,34 @@ def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float
     return {"state": state, "action": action, "reward": reward, "explored": explored, "epsilon": eps}
 
 
-def collect_maddpg_transitions(env, actor: nn.Module, nb_steps: int, random_steps_left: int = 0, seed: int = 0) -> Dict[str, torch.Tensor]:
+def collect_maddpg_transitions(env, actor: nn.Module, nb_steps: int, random_steps_left: int = 0, seed: int = 0,
+                               actor_backend: str = "torch") -> Dict[str, torch.Tensor]:
     """The interaction loop of train_ddpg.py:95-116 for all envs at once, env-steps kept on the GPU: every step the actor's logits on
     every agent's OWN observation (the reference stores agent 0's for all, train_ddpg.py:86-91), the acting action, ``env.step``,
     and the env-step (state, action, reward, next_state) of ``MADDPG.push``.  ``select_action`` takes the argmax of a hard
     gumbel-softmax sample (ddpg.py:289-298); an argmax over logits plus gumbel noise is a draw from softmax(logits) whatever tau, so
     the action is ``mdr_logits_sample`` on the logits - the same distribution from the project's Philox stream.  The first
     ``random_steps_left`` steps act uniformly at random instead (train_ddpg.py:97-103).  Returns ``state`` [T + 1, E, N, F]
-    (``state[t + 1]`` is ``next_state[t]``), ``action`` int64 and ``reward`` [T, E, N]."""
+    (``state[t + 1]`` is ``next_state[t]``), ``action`` int64 and ``reward`` [T, E, N].
+
+    ``actor_backend``: "torch" (default) - ``actor(state[t])`` under torch, then ``mdr_logits_sample``; "hip" - forward, softmax and
+    draw in one kernel (``FusedMLPActor`` on ``state[t]``, the same (seed, ``env.steps_taken``): the same draw, on probabilities that
+    agree with torch's to fp32 rounding), ValueError for a net the kernel does not take.  It measured faster than "torch" at every
+    size tried (profiles/mlp_actor_README.md; F = 51, hidden 256-256): 1.9-2.0x at 1 x 20 and 64 x 50 agents (both paths bound by the host
+    there), 1.36x at 4096 x 20, 1.57x at 4096 x 1024; 1.40x at F = 121 and 4096 x 1024.  Other sizes: not measured.
+    The random steps are the same under both."""
     import ctypes as C
 
     from . import _native as nat
+    if actor_backend not in ("torch", "hip"):
+        raise ValueError("actor_backend must be 'torch' or 'hip'")
+    fused = None
+    if actor_backend == "hip":
+        from .mlp_actor import FusedMLPActor
+        why = FusedMLPActor.refusal(actor)
+        if why:
+            raise ValueError("collect_maddpg_transitions(actor_backend='hip'): " + why)
+        fused = FusedMLPActor(actor)
     E, N = env.nb_envs, env.nb_houses
     dev = env.device
     F_len = env.obs_vector_length()
@@ -463,12 +480,15 @@ def collect_maddpg_transitions(env, actor: nn.Module, nb_steps: int, random_step
     action = torch.empty((T, E, N), dtype=torch.int64, device=dev)
     reward = torch.empty((T, E, N), dtype=torch.float32, device=dev)
     act = torch.empty(E * N, dtype=torch.uint8, device=dev)
+    a_prob = torch.empty(E * N, dtype=torch.float32, device=dev) if fused is not None else None
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
     env.obs_vector("rows", out=state[0])
     for t in range(T):
         if t < int(random_steps_left):
             act.copy_(torch.randint(0, 2, (E * N,), device=dev, generator=gen, dtype=torch.uint8))
+        elif fused is not None:
+            fused.sample(state[t].view(E * N, F_len), seed, env.steps_taken, action=act, a_prob=a_prob)
         else:
             with torch.no_grad():
                 logits = actor(state[t].view(E * N, F_len)).contiguous()
