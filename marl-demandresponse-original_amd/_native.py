@@ -6,11 +6,29 @@ sizes (``struct_size``).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import gc
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDR_HIP_LIB") or os.path.join(HERE, "csrc", "libmdr_hip.so")   # MDR_HIP_LIB: experiment builds
+
+
+@contextlib.contextmanager
+def gc_paused():
+    """No cyclic garbage collection inside the block: what a stream capture runs under.  A collection that starts between two
+    launches of a capture destroys whatever dead cycles earlier work left behind - a learner and its update graph hold each other,
+    an env holds its library handle - and their destructors free device memory and destroy streams and graphs, runtime calls a
+    capture in progress does not allow: the process aborts.  The garbage is collected as usual once the block is left."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
 
 MDR_ABI_VERSION = 5
 MDR_MAX_SINUSOIDS = 8

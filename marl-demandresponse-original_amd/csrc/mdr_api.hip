@@ -876,8 +876,11 @@ static bool rollout_resident(const mdr_env_t* env, const InteriorPlan& ip) {
     const long long v = strtoll(t, &end, 10);
     return (end && *end == '\0' && v >= 0) ? (int64_t)v : (int64_t)1 << 20;
   }();
+  // ... and time_step x table_steps < 2^31: a launch covers at most table_steps steps, and in it the lane of a blank house (a lane past
+  // the env's end) counts its never-stored seconds-since-off up by time_step per step without a reset.  Longer tables: the per-step path.
   return resident_on && ip.planes >= 0 && mdr::rollout_resident_supported(env->plan) &&
-         (int64_t)env->cfg.nb_envs * env->cfg.nb_houses >= resident_houses;
+         (int64_t)env->cfg.nb_envs * env->cfg.nb_houses >= resident_houses &&
+         (int64_t)env->cfg.time_step * env->cfg.table_steps < ((int64_t)1 << 31);
 }
 
 int mdr_env_rollout_resident(const mdr_env_t* env, int32_t* resident) {
@@ -898,7 +901,8 @@ int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t
   // overwrites every one of them - so steps 0 .. nb_steps - 2 run an interior form, which stores none of the outputs behind the
   // env-wide reduction, and the last step is a full one.  Two interior forms, chosen by size (rollout_resident):
   //   at or above MDR_ROLLOUT_RESIDENT_HOUSES houses   k_rollout_resident: the houses stay in registers over every step the current
-  //       tables cover - the state and the parameters cross HBM once per table window instead of once per step;
+  //       tables cover - the state and the parameters cross HBM once per table window instead of once per step (mdr_resident.hip;
+  //       only while time_step x table_steps < 2^31, rollout_resident: otherwise the per-step path below);
   //   below it   one interior launch of k_step_fused / k_step_group per step (interior_plan), exactly as before.
   // Why a size rule and not the resident form everywhere: tests/test_gpu_bench.py bounds bench.py's roofline.frac - a fixed 99 B per
   // house-step over the time - below 1.25 at 512 envs x 1024 houses, and a step that moves no state through memory passes it many

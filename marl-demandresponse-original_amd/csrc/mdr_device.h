@@ -270,6 +270,45 @@ __device__ __forceinline__ HouseNextM house_advance_m(const HouseIn& h, uint64_t
   return o;
 }
 
+// The per-step update of the kernels that keep a house in registers over many steps and store nothing in between
+// (k_rollout_resident*): house_advance_m without what only the last step of a launch needs.  Same f32 expressions, same bits.
+//   * no lock mask: `lock` reads the step's `can` and the sso it leaves, so house_lock_m forms it once, behind the last step;
+//   * no pen / power;
+//   * LEAN: after any step on2 => sso2 == 0, so from the second step of a launch on `on => sso == 0` holds and
+//       sso1 = on ? sso : sso + dt   is   sso + dt   wherever it is read (can is true for an `on` house whatever sso1 is), and
+//       sso2 = on2 ? 0 : sso1        is   (on | on2) ? 0 : sso + dt
+//     one add and one select per house, the OR on the scalar unit.  The first step of a launch runs LEAN = false: load_state_dict,
+//     load_episode and the step behind a reset can hand in an `on` house with sso != 0.
+// A blank lane (HouseIn{}) gains at most dt per step and is never stored: the caller bounds dt x steps per launch below 2^31.
+struct HouseLeanM {
+  float Ta, Tm;
+  int sso;
+  uint64_t on, can;
+};
+
+template <bool LEAN>
+__device__ __forceinline__ HouseLeanM house_advance_lean_m(const HouseIn& h, uint64_t on_m, uint64_t cmd_m, float od_old, float solar, int dt) {
+  const int sso1 = LEAN ? h.sso + dt : (lane_bit(on_m) ? h.sso : h.sso + dt);                  // env 475-476
+  const uint64_t can_m = on_m | __builtin_amdgcn_ballot_w64(sso1 >= h.lockout);                // env 478-481
+  const uint64_t on2_m = can_m & cmd_m;                                                        // env 483-486
+  const int sso2 = lane_bit(LEAN ? (on_m | on2_m) : on2_m) ? 0 : sso1;                         // env 487-488
+  const float Qa = (lane_bit(on2_m) ? h.Q_hvac : 0.0f) + solar;  // env 690-699
+  const float Tinf = fmaf(Qa, h.inv_Ua, od_old);     // uses the PREVIOUS step's outdoor temperature (env 1034)
+  const float dm = h.Tm - h.Ta;
+  HouseLeanM o;
+  o.Ta = h.Ta + fmaf(h.k01, dm, h.s0 * (h.Ta - Tinf));
+  o.Tm = h.Tm + fmaf(-h.k10, dm, h.s1 * (h.Tm - Tinf));
+  o.sso = sso2;
+  o.on = on2_m;
+  o.can = can_m;
+  return o;
+}
+
+// env 489-492 behind the last step: `can_m`, `on_m` and `sso` as that step left them
+__device__ __forceinline__ uint64_t house_lock_m(uint64_t can_m, uint64_t on_m, int sso, int lockout, int dt) {
+  return ~can_m | (~on_m & __builtin_amdgcn_ballot_w64(sso + dt < lockout));
+}
+
 __device__ __forceinline__ unsigned house_flags(bool on, bool lock) { return (on ? 1u : 0u) | (lock ? 2u : 0u); }
 
 __device__ __forceinline__ HouseOut house_step(const HouseIn& h, bool cmd, float od_old, float solar, int dt) {

@@ -1457,162 +1457,6 @@ __global__ __launch_bounds__(256) void k_rollout_group(StepArgs a, RolloutArgs r
   }
 }
 
-// ---- (2c) the interior steps of mdr_env_rollout with the houses resident in registers (large batches: mdr_api.hip's resident rule).
-// An interior step has no env-wide reduction, no reward and no obs: step_fused_interior is step_vec's loads, house_step and the
-// state stores, and a house depends on itself and on its env's od_old / solar_new rows alone.  So `ro.nsteps` of them are one
-// launch: the prologue loads a house through the very helpers the interior step uses (the same bits arrive in registers), the loop
-// reads two table values per env and step and advances the houses as k_rollout_fused does - lane masks, blank houses in the lanes
-// past the env's end so that every ballot sees the whole wave - and the epilogue stores Ta, Tm, sso and flags, nothing else: the
-// full step that ends the rollout overwrites every other output.  No LDS, no barrier, no accumulator; the pen / power that
-// house_advance_m returns are dead.  The step forms it replaces, by env->plan as launch_step picks them:
-//   k_rollout_resident<VEC, TILES, THREADS, BB>   for k_step_fused<VEC, TILES, THREADS, 1, ..>: the rows are wave-uniform scalar
-//                                                 loads, fetched one step ahead; the other resident waves hide the rest
-//   k_rollout_resident_group<GROUP, VEC, BB>      for k_step_group<GROUP, VEC, 1, ..>: each lane reads its own env's rows
-// BB: the bang-bang rule compiled in; otherwise controller_cmd_m, or - external actions - the caller's buffer, which nothing
-// writes during a rollout: read once, one constant mask.
-template <int VEC>
-__device__ __forceinline__ void resident_load(const StepArgs& a, uint32_t uni, bool coded, bool packed, bool ext, int64_t i, HouseIn* hs,
-                                              unsigned* act) {
-  float Ta[VEC], Tm[VEC], k01[VEC], s0[VEC], k10[VEC], s1[VEC], iu[VEC], q[VEC], pm[VEC], tg[VEC], db[VEC];
-  int sso[VEC], lk[VEC];
-  unsigned fl[VEC];
-  load_vec<VEC>(a.Ta, i, Ta);
-  load_vec<VEC>(a.Tm, i, Tm);
-  load_vec<VEC>(a.sso, i, sso);
-  load_bytes<VEC>(a.flags, i, fl);
-  if (ext) load_bytes<VEC>(a.actions, i, act);
-  load_thermal<VEC>(a, packed, i, k01, s0, k10, s1, iu);
-  load_hvac<VEC>(a, coded, i, q, pm);
-  load_param_or_first<VEC>((uni & UNIFORM_TARGET) != 0u, a.target, i, tg);
-  load_param_or_first<VEC>((uni & UNIFORM_DEADBAND) != 0u, a.deadband, i, db);
-  load_vec_or_first<VEC>((uni & UNIFORM_LOCKOUT) != 0u, a.lockout, i, lk);
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) hs[v] = HouseIn{Ta[v], Tm[v], sso[v], fl[v], k01[v], s0[v], k10[v], s1[v], iu[v], q[v], pm[v], tg[v], db[v], lk[v]};
-}
-
-template <int VEC>
-__device__ __forceinline__ void resident_store(const StepArgs& a, int64_t i, const HouseIn* hs, const uint64_t* on_m, const uint64_t* lock_m) {
-  float nTa[VEC], nTm[VEC];
-  int nsso[VEC];
-  unsigned nfl[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    nTa[v] = hs[v].Ta;
-    nTm[v] = hs[v].Tm;
-    nsso[v] = hs[v].sso;
-    nfl[v] = house_flags(lane_bit(on_m[v]), lane_bit(lock_m[v]));
-  }
-  store_vec<VEC>(a.Ta, i, nTa);
-  store_vec<VEC>(a.Tm, i, nTm);
-  store_vec<VEC>(a.sso, i, nsso);
-  store_bytes<VEC>(a.flags, i, nfl);
-}
-
-template <int VEC, int TILES, int THREADS, bool BB>
-__global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, RolloutArgs ro) {
-  if (ro.nsteps <= 0) return;
-  const int e = blockIdx.x;
-  const int64_t base = (int64_t)e * a.N;
-  const uint32_t uni = uniform_word(a);
-  const bool coded = hvac_coded(a) != 0u, packed = thermal_packed(a) != 0u;
-  const bool ext = !BB && a.action_source == MDR_ACTIONS_EXTERNAL;
-  HouseIn hs[TILES][VEC];
-  uint64_t on_m[TILES][VEC], lock_m[TILES][VEC], cmd_m[TILES][VEC];
-  bool live[TILES];
-#pragma unroll
-  for (int t = 0; t < TILES; ++t) {
-    const int h = (t * THREADS + (int)threadIdx.x) * VEC;
-    live[t] = h < a.N;
-    unsigned act[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      hs[t][v] = HouseIn{};
-      act[v] = 0u;
-    }
-    if (live[t]) resident_load<VEC>(a, uni, coded, packed, ext, base + h, hs[t], act);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {   // (outside the branch: a ballot is a wave-wide value)
-      on_m[t][v] = __builtin_amdgcn_ballot_w64(live[t] && (hs[t][v].flags & 1u) != 0u);
-      lock_m[t][v] = __builtin_amdgcn_ballot_w64(live[t] && (hs[t][v].flags & 2u) != 0u);
-      cmd_m[t][v] = __builtin_amdgcn_ballot_w64(live[t] && act[v] != 0u);
-    }
-  }
-  float od_old = a.od_old[e], solar = a.solar_new[e];
-  for (int s = 0; s < ro.nsteps; ++s) {
-    const int64_t next = (int64_t)min(s + 1, ro.nsteps - 1) * a.E + e;   // the rows of the step after this one: in flight over this step's arithmetic
-    const float od_next = a.od_old[next], solar_next = a.solar_new[next];
-#pragma unroll
-    for (int t = 0; t < TILES; ++t) {
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {   // every lane, also those past the env's end (k_rollout_fused): blank houses, no divergent branch around the ballots
-        if (BB) cmd_m[t][v] = __builtin_amdgcn_ballot_w64(hs[t][v].Ta > hs[t][v].target);   // agents/bangbang_controllers.py:49-59
-        else if (!ext) cmd_m[t][v] = controller_cmd_m(a.action_source, hs[t][v].Ta, hs[t][v].target, hs[t][v].deadband, on_m[t][v]);
-        const HouseNextM n = house_advance_m(hs[t][v], on_m[t][v], cmd_m[t][v], od_old, solar, a.dt);
-        hs[t][v].Ta = n.Ta;
-        hs[t][v].Tm = n.Tm;
-        hs[t][v].sso = live[t] ? n.sso : 0;
-        on_m[t][v] = n.on;
-        lock_m[t][v] = n.lock;
-      }
-    }
-    od_old = od_next;
-    solar = solar_next;
-  }
-#pragma unroll
-  for (int t = 0; t < TILES; ++t) {
-    if (!live[t]) continue;
-    resident_store<VEC>(a, base + (t * THREADS + (int)threadIdx.x) * VEC, hs[t], on_m[t], lock_m[t]);
-  }
-}
-
-template <int GROUP, int VEC, bool BB>
-__global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, RolloutArgs ro) {
-  if (ro.nsteps <= 0) return;
-  const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) / GROUP;
-  const int lane = threadIdx.x % GROUP;
-  const bool env_ok = gid < a.E;
-  const int e = env_ok ? (int)gid : a.E - 1;
-  const bool active = env_ok && lane * VEC < a.N;
-  const int64_t i = (int64_t)e * a.N + lane * VEC;
-  const uint32_t uni = uniform_word(a);
-  const bool coded = hvac_coded(a) != 0u, packed = thermal_packed(a) != 0u;
-  const bool ext = !BB && a.action_source == MDR_ACTIONS_EXTERNAL;
-  HouseIn hs[VEC];
-  unsigned act[VEC];
-  uint64_t on_m[VEC], lock_m[VEC], cmd_m[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    hs[v] = HouseIn{};
-    act[v] = 0u;
-  }
-  if (active) resident_load<VEC>(a, uni, coded, packed, ext, i, hs, act);
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {   // idle lanes hold blank houses (k_rollout_group): the masks are formed in wave-uniform control flow
-    on_m[v] = __builtin_amdgcn_ballot_w64(active && (hs[v].flags & 1u) != 0u);
-    lock_m[v] = __builtin_amdgcn_ballot_w64(active && (hs[v].flags & 2u) != 0u);
-    cmd_m[v] = __builtin_amdgcn_ballot_w64(active && act[v] != 0u);
-  }
-  float od_old = a.od_old[e], solar = a.solar_new[e];   // several envs per wave: each lane reads its own env's rows (an idle env_ok == false lane: env E - 1's)
-  for (int s = 0; s < ro.nsteps; ++s) {
-    const int64_t next = (int64_t)min(s + 1, ro.nsteps - 1) * a.E + e;
-    const float od_next = a.od_old[next], solar_next = a.solar_new[next];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      if (BB) cmd_m[v] = __builtin_amdgcn_ballot_w64(hs[v].Ta > hs[v].target);
-      else if (!ext) cmd_m[v] = controller_cmd_m(a.action_source, hs[v].Ta, hs[v].target, hs[v].deadband, on_m[v]);
-      const HouseNextM n = house_advance_m(hs[v], on_m[v], cmd_m[v], od_old, solar, a.dt);
-      hs[v].Ta = n.Ta;
-      hs[v].Tm = n.Tm;
-      hs[v].sso = active ? n.sso : 0;
-      on_m[v] = n.on;
-      lock_m[v] = n.lock;
-    }
-    od_old = od_next;
-    solar = solar_next;
-  }
-  if (active) resident_store<VEC>(a, i, hs, on_m, lock_m);
-}
-
 // ---- (3) split path: any N, several workgroups per env, and the sharded-houses case -------------
 // grid = (split_blocks, E); workgroup b of env e owns houses [b * THREADS * VEC, (b + 1) * THREADS * VEC).  THREADS = 64 when
 // the launch would otherwise have fewer workgroups than CUs to spread over (a 125,000-house shard is 123 workgroups of 1024
@@ -2986,64 +2830,6 @@ hipError_t launch_rollout_fused(const StepArgs& a, const RolloutArgs& r, const S
     if (p.tiles == 1) MDR_ROLL(1, 1, 256); else MDR_ROLL(1, 2, 256);
   }
 #undef MDR_ROLL
-  return hipGetLastError();
-}
-
-// The interior steps of mdr_env_rollout, r.nsteps of them, by the STEP plan: the grid and the lane mapping of the k_step_fused /
-// k_step_group instantiation that launch_step would launch r.nsteps times.  Other step forms have no interior form: an error.
-bool rollout_resident_supported(const StepPlan& p) { return p.kind == STEP_FUSED || p.kind == STEP_GROUP; }
-
-template <int VEC, int THREADS>
-static void launch_resident_tiles(const StepArgs& a, const RolloutArgs& r, int tiles, hipStream_t s) {
-  const dim3 g((unsigned)a.E), b(THREADS);
-  const bool bb = a.action_source == MDR_ACTIONS_BANGBANG;
-#define MDR_RESIDENT(T)                                                                     \
-  if (bb) hipLaunchKernelGGL((k_rollout_resident<VEC, T, THREADS, true>), g, b, 0, s, a, r); \
-  else hipLaunchKernelGGL((k_rollout_resident<VEC, T, THREADS, false>), g, b, 0, s, a, r);   \
-  break;
-  switch (tiles) {
-    case 1: MDR_RESIDENT(1)
-    case 2: MDR_RESIDENT(2)
-    case 3: MDR_RESIDENT(3)
-    default: MDR_RESIDENT(4)
-  }
-#undef MDR_RESIDENT
-}
-
-hipError_t launch_rollout_resident(const StepArgs& a, const RolloutArgs& r, const StepPlan& p, hipStream_t s) {
-  if (!rollout_resident_supported(p) || a.cursor != nullptr) return hipErrorInvalidValue;
-  if (p.kind == STEP_FUSED) {
-    if (p.vec == 4) {
-      if (p.threads == 64) launch_resident_tiles<4, 64>(a, r, p.tiles, s);
-      else if (p.threads == 128) launch_resident_tiles<4, 128>(a, r, p.tiles, s);
-      else launch_resident_tiles<4, 256>(a, r, p.tiles, s);
-    } else {
-      launch_resident_tiles<1, 256>(a, r, p.tiles, s);
-    }
-    return hipGetLastError();
-  }
-  const int64_t lanes = (int64_t)a.E * p.threads;
-  const dim3 g((unsigned)((lanes + 255) / 256)), b(256);
-  const bool bb = a.action_source == MDR_ACTIONS_BANGBANG;
-#define MDR_RESIDENT_GV(G, V)                                                                   \
-  if (bb) hipLaunchKernelGGL((k_rollout_resident_group<G, V, true>), g, b, 0, s, a, r);         \
-  else hipLaunchKernelGGL((k_rollout_resident_group<G, V, false>), g, b, 0, s, a, r);
-#define MDR_RESIDENT_G(G)                          \
-  if (p.vec == 4) { MDR_RESIDENT_GV(G, 4) }        \
-  else if (p.vec == 2) { MDR_RESIDENT_GV(G, 2) }   \
-  else { MDR_RESIDENT_GV(G, 1) }                   \
-  break;
-  switch (p.threads) {
-    case 1: MDR_RESIDENT_G(1)
-    case 2: MDR_RESIDENT_G(2)
-    case 4: MDR_RESIDENT_G(4)
-    case 8: MDR_RESIDENT_G(8)
-    case 16: MDR_RESIDENT_G(16)
-    case 32: MDR_RESIDENT_G(32)
-    default: MDR_RESIDENT_G(64)
-  }
-#undef MDR_RESIDENT_G
-#undef MDR_RESIDENT_GV
   return hipGetLastError();
 }
 

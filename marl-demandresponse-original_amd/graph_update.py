@@ -187,7 +187,7 @@ def _capture(record, snapshot_tensors, dev) -> torch.cuda.CUDAGraph:
         snap.restore()
     torch.cuda.current_stream(dev).wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
+    with nat.gc_paused(), torch.cuda.graph(graph, stream=side):
         record()
     return graph
 

@@ -552,6 +552,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
 
     ``use_graph`` (default: when the env was built with ``graph_mode=True``): the step is captured once in a
     ``torch.cuda.CUDAGraph`` and replayed - the launch-bound regime of small batches."""
+    from . import _native as nat
     from .policy import FEATURES_OBSERVE
     from .tarmac import FusedTarMACActor, TarMACActor
     from .tarmac_a2c import TarMACA2CPolicy
@@ -636,7 +637,7 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
             continue
         if g is None:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with nat.gc_paused(), torch.cuda.graph(g):
                 one_step(0)
         for _ in range(n):
             g.replay()
