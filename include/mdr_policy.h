@@ -571,6 +571,44 @@ int mdr_mlp_actor_sample(const mdr_mlp_t *actor, const float *obs, int64_t ld_ob
                          const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob, float *probs,
                          void *stream);
 
+/* ---- MADDPG with one network per agent (ddpg.py:200-213: every agent its own actor, critic and target of each; what every
+ * checkpoint of saveDDPGDict holds).  At most MDR_MAX_AGENT_NETS nets per call: their weight pointers travel in the kernel argument
+ * block (32 x 6 pointers = 1.5 KB), so no device table is owned by anybody and a captured call stays valid while the parameter
+ * tensors stay where they are. */
+#define MDR_MAX_AGENT_NETS 32
+
+/* mdr_mlp_actor_sample with one actor per agent: row r of `obs` (nb_rows = envs x nb_nets rows, env-major: r = e nb_nets + k) goes
+ * through net r % nb_nets.  `actors`: a HOST array of nb_nets descriptors in torch's own layout, all of one shape (num_state,
+ * hidden1, hidden2; the limits of mdr_mlp_actor_sample), the weights read in place on every call.  Outputs, draw, `step_dev`, `greedy`
+ * as there; the draw's counter is the GLOBAL row r, so a row's bits depend on the row, its net and (seed, step) only - with nb_nets
+ * equal nets the call returns the bits of mdr_mlp_actor_sample on the same rows, and rows k, k + nb_nets, ... always equal
+ * mdr_mlp_actor_sample(net k) on the whole batch.
+ * A unit of work is (net k, tile of 32 envs): rows (32 t + j) nb_nets + k, F contiguous floats each, nb_nets ld_obs floats apart.  A
+ * persistent workgroup holds net k's slabs of W1 and W2 in registers, walks a contiguous run of units and reloads the slabs only when
+ * the run moves to the next net; the grid is min(units, compute units, max_workgroups if > 0) - with max_workgroups = 1 one workgroup
+ * walks every net.  The outputs do not depend on the grid.  Stream-ordered, never synchronises, allocates nothing.
+ * Returns 0; -1 (NULL `actors`, `obs` or `action`, a NULL weight pointer, a struct_size that is not this header's, nb_nets < 1,
+ * nb_rows < 0, nb_rows not a multiple of nb_nets, max_workgroups < 0, ld_obs < F); -3 (HIP error); -4 (nb_nets >
+ * MDR_MAX_AGENT_NETS, nets of differing shapes, a shape outside the limits).  On -1 and -4 nothing was launched and nothing written.
+ * nb_rows == 0 returns 0 and launches nothing. */
+int mdr_mlp_actors_sample(const mdr_mlp_t *actors, int32_t nb_nets, const float *obs, int64_t ld_obs, int64_t nb_rows, uint64_t seed,
+                          uint64_t step, const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob,
+                          float *probs, void *stream);
+
+/* mdr_maddpg_target with one target actor per agent (ddpg.py:282-284: agent k's next action comes from agent k's OWN target actor).
+ * `tgt_actors`: a HOST array of nb_nets = nb_agents descriptors of one shape; `tgt_critic` is agent `agent`'s own target critic, one
+ * net.  Everything else - rows, noise, outputs, the two launches - is mdr_maddpg_target's.  The pick launch tiles the picks per
+ * agent: tile t holds agent k = t / ceil(nb_rows / 16) and the minibatch rows 16 (t mod ceil(nb_rows / 16)) + c, so that a tile's
+ * MFMA A operand is one net; a row's arithmetic is a chain over k whatever its column, so next_action[:, k] has the bits
+ * mdr_maddpg_target writes in column k when called with net k as its shared target actor, and with nb_nets equal nets every output
+ * equals mdr_maddpg_target's bit for bit.
+ * Returns as mdr_maddpg_target; -1 also for nb_nets != nb_agents; -4 also for nb_nets > MDR_MAX_AGENT_NETS and nets of differing
+ * shapes.  On -1 and -4 nothing was launched and nothing written. */
+int mdr_maddpg_target_agents(const mdr_mlp_t *tgt_actors, int32_t nb_nets, const mdr_mlp_t *tgt_critic, const float *next_state,
+                             int64_t ld_state, const float *reward, const int64_t *index, int64_t nb_rows, int32_t nb_agents,
+                             int32_t agent, const float *noise, float tau, float gamma, int32_t max_workgroups, float *y,
+                             float *next_q, uint8_t *next_action, void *stream);
+
 /* ---- TarMAC-PPO's update step for the actor (TarmacPPO.update, agents/tarmac_ppo.py:168-186): loss and gradient of one minibatch.
  *
  * The actor's weights in torch's own layout - every layer w[out][in] contiguous and its bias, device memory, read as they are on

@@ -34,9 +34,9 @@ def __getattr__(name):
     if name in ("MADDPGLearner", "DDPGNetworkMLP", "JointReplayBuffer", "GreedyDDPGActor", "train_maddpg"):
         from . import maddpg
         return getattr(maddpg, name)
-    if name == "FusedMLPActor":
-        from .mlp_actor import FusedMLPActor
-        return FusedMLPActor
+    if name in ("FusedMLPActor", "FusedMLPActors"):
+        from . import mlp_actor
+        return getattr(mlp_actor, name)
     if name == "TarMACPPOLearner":
         from .tarmac_ppo import TarMACPPOLearner
         return TarMACPPOLearner

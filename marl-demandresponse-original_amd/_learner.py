@@ -87,6 +87,11 @@ def mlp_desc(layers: Sequence[nn.Linear]) -> nat.MdrMlp:
                       *[C.c_void_p(p.data_ptr()) for p in mlp_params(layers)])
 
 
+def mlp_descs(nets: Sequence[Sequence[nn.Linear]]):
+    """A host array of ``mdr_mlp_t``, one per net (the per-agent entry points: mdr_mlp_actors_sample, mdr_maddpg_target_agents)."""
+    return (nat.MdrMlp * len(nets))(*[mlp_desc(layers) for layers in nets])
+
+
 def mlp_sizes(desc, nb_rows: int, max_workgroups: int = 0, wide: bool = False) -> Tuple[int, int]:
     """(floats of the flat gradient, bytes of workspace) of an ``mdr_ppo_*`` / ``mdr_dqn_grad`` call over ``nb_rows`` rows."""
     lib = nat.load()

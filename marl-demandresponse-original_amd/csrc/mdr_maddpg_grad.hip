@@ -27,7 +27,9 @@
 
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/mdr.h"
 #include "../../include/mdr_policy.h"
@@ -52,7 +54,8 @@ struct Net {
   int K, H1, H2, O;
 };
 
-enum Mode : int { MODE_PICK = 0, MODE_TARGET = 1, MODE_CRITIC = 2, MODE_ACTOR = 3 };
+// MODE_PICK_AGENTS: the picks with one target actor per agent (mdr_maddpg_target_agents) - tiles of 16 minibatch rows of ONE agent
+enum Mode : int { MODE_PICK = 0, MODE_TARGET = 1, MODE_CRITIC = 2, MODE_ACTOR = 3, MODE_PICK_AGENTS = 4 };
 
 struct RowArgs {
   Net actor, critic;
@@ -71,6 +74,21 @@ struct RowArgs {
   float *out0, *out1;         // TARGET: y, next_q; CRITIC: q; ACTOR: q, logits
   float *h1, *h2, *dz1, *dz2, *dl, *term;      // workspace of the net whose gradient is taken: [Rp][H1p], [Rp][H2p], ..., [Rp][2], [Rp]
 };
+
+// MODE_PICK_AGENTS: the nets' pointers travel in the kernel argument block (32 x 48 bytes: no device table to own); the shapes are
+// those of r.actor.  Tile t: agent k = t / TB, minibatch rows 16 (t mod TB) + c - the MFMA A operand, the weights, is one net's
+struct NetPtrs {
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+};
+struct PickAgentsArgs {
+  RowArgs r;
+  int64_t TB;      // tiles per agent: ceil(B / 16)
+  NetPtrs nets[MDR_MAX_AGENT_NETS];
+};
+template <Mode MODE>
+using ArgsOf = std::conditional_t<MODE == MODE_PICK_AGENTS, PickAgentsArgs, RowArgs>;
+__host__ __device__ __forceinline__ const RowArgs& row_args(const RowArgs& a) { return a; }
+__host__ __device__ __forceinline__ const RowArgs& row_args(const PickAgentsArgs& a) { return a.r; }
 
 // the wave's share of two dot products over its block of vT: sum_u coef_o[u * su] vT[u][row c] -> lp[w][row][o]
 __device__ __forceinline__ void dot2_share(const float* vT, const float* __restrict__ coef0, const float* __restrict__ coef1, int64_t su, int H, float* lp,
@@ -105,7 +123,8 @@ __device__ __forceinline__ void dot2_sum(const float* lp, int nb, int c, float& 
 }
 
 template <Mode MODE>
-__global__ __launch_bounds__(64 * NW) void k_maddpg_rows(RowArgs a) {
+__global__ __launch_bounds__(64 * NW) void k_maddpg_rows(ArgsOf<MODE> args) {
+  const RowArgs& a = row_args(args);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
   float* xT = lds + S_X;
@@ -117,15 +136,31 @@ __global__ __launch_bounds__(64 * NW) void k_maddpg_rows(RowArgs a) {
   float* pk = lds + S_PK;       // MODE_ACTOR: the tile's picks of agent a, 0 / 1
   // weights in flight per wave (MFMA k-steps loaded together); the actor's step holds more live state, so fewer fit its 128 registers
   constexpr int UNR = MODE == MODE_ACTOR ? 4 : 8;
-  constexpr bool HAS_ACTOR = MODE == MODE_PICK || MODE == MODE_ACTOR;
-  constexpr bool HAS_CRITIC = MODE != MODE_PICK;
-  const Net& A = a.actor;
+  constexpr bool AGENTS = MODE == MODE_PICK_AGENTS;
+  constexpr bool PICKS = MODE == MODE_PICK || AGENTS;
+  constexpr bool HAS_ACTOR = PICKS || MODE == MODE_ACTOR;
+  constexpr bool HAS_CRITIC = !PICKS;
+  const Net& A0 = a.actor;
   const Net& Cn = a.critic;
   const int NF = a.N * a.F;
 
   for (int64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-    const int64_t row = t * TILE + c;      // the row this lane's MFMA column and head work belong to
-    const bool valid = row < a.R;
+    int64_t row = t * TILE + c;      // the row this lane's MFMA column and head work belong to
+    bool valid = row < a.R;
+    Net A = A0;
+    [[maybe_unused]] int kt = 0;         // AGENTS: the tile's agent and its first minibatch row
+    [[maybe_unused]] int64_t i0 = 0;
+    if constexpr (AGENTS) {
+      kt = (int)(t / args.TB);
+      i0 = (t - kt * args.TB) * TILE;
+      valid = i0 + c < a.B;
+      row = (i0 + c) * a.N + kt;      // of noise and picks: [B][N]
+      // the table is read through the argument block's own address (its first argument starts the block): indexing the by-value
+      // parameter by a variable would copy all of it to private memory
+      const char* seg = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+      const NetPtrs net = reinterpret_cast<const NetPtrs*>(seg + offsetof(PickAgentsArgs, nets))[kt];
+      A.w1 = net.w1, A.b1 = net.b1, A.w2 = net.w2, A.b2 = net.b2, A.w3 = net.w3, A.b3 = net.b3;
+    }
     float l0 = 0.0f, l1 = 0.0f, p0 = 0.0f, p1 = 0.0f;
     bool pick = false;
 
@@ -135,9 +170,9 @@ __global__ __launch_bounds__(64 * NW) void k_maddpg_rows(RowArgs a) {
         const int r = e / MAX_F, f = e - r * MAX_F;
         const int64_t rr = t * TILE + r;
         float v = 0.0f;
-        if (f < a.F && rr < a.R) {
-          const int64_t i = MODE == MODE_PICK ? rr / a.N : rr;
-          const int k = MODE == MODE_PICK ? (int)(rr - i * a.N) : a.agent;
+        if (f < a.F && (AGENTS ? i0 + r < a.B : rr < a.R)) {
+          const int64_t i = AGENTS ? i0 + r : MODE == MODE_PICK ? rr / a.N : rr;
+          const int k = AGENTS ? kt : MODE == MODE_PICK ? (int)(rr - i * a.N) : a.agent;
           const int64_t j = a.index ? a.index[i] : i;
           v = a.state[j * a.ld + (int64_t)k * a.F + f];
         }
@@ -175,7 +210,7 @@ __global__ __launch_bounds__(64 * NW) void k_maddpg_rows(RowArgs a) {
         t1 = sum1 / a.tau;
       }
       pick = t1 > t0;
-      if constexpr (MODE == MODE_PICK) {
+      if constexpr (PICKS) {
         if (valid && w == 0 && g == 0) a.picks[row] = pick ? 1 : 0;
         __syncthreads();      // xT, lp and the images are rewritten by the next tile
         continue;
@@ -443,12 +478,13 @@ int64_t ws_floats(const mdr_mlp_t* n, int64_t nb_rows) {
 }
 
 template <Mode MODE>
-int launch_rows(const RowArgs& a, int cap, hipStream_t st) {
+int launch_rows(const ArgsOf<MODE>& args, int cap, hipStream_t st) {
+  const RowArgs& a = row_args(args);
   const size_t bytes = (size_t)S_END * sizeof(float);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_maddpg_rows<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
     return MDR_ERR_HIP;
   const int64_t grid = a.ntiles < cap ? a.ntiles : cap;
-  hipLaunchKernelGGL(k_maddpg_rows<MODE>, dim3((unsigned)grid), dim3(64 * NW), bytes, st, a);
+  hipLaunchKernelGGL(k_maddpg_rows<MODE>, dim3((unsigned)grid), dim3(64 * NW), bytes, st, args);
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
@@ -512,6 +548,46 @@ int mdr_maddpg_target(const mdr_mlp_t* tgt_actor, const mdr_mlp_t* tgt_critic, c
   a.noise = noise, a.tau = tau, a.gamma = gamma, a.reward = reward, a.picks = next_action, a.out0 = y, a.out1 = next_q;
   a.R = nb_rows * nb_agents, a.ntiles = (a.R + TILE - 1) / TILE;
   if (launch_rows<MODE_PICK>(a, cap, st) != MDR_OK) return MDR_ERR_HIP;
+  a.R = nb_rows, a.ntiles = (a.R + TILE - 1) / TILE;
+  return launch_rows<MODE_TARGET>(a, cap, st);
+}
+
+int mdr_maddpg_target_agents(const mdr_mlp_t* tgt_actors, int32_t nb_nets, const mdr_mlp_t* tgt_critic, const float* next_state,
+                             int64_t ld_state, const float* reward, const int64_t* index, int64_t nb_rows, int32_t nb_agents, int32_t agent,
+                             const float* noise, float tau, float gamma, int32_t max_workgroups, float* y, float* next_q,
+                             uint8_t* next_action, void* stream) {
+  if (!tgt_actors || !next_state || !reward || !noise || !y || !next_action || nb_nets < 1 || nb_nets != nb_agents) return MDR_ERR_INVALID;
+  if (nb_nets > MDR_MAX_AGENT_NETS) return MDR_ERR_UNSUPPORTED;
+  for (int k = 0; k < nb_nets; ++k)
+    if (!fields_ok(&tgt_actors[k])) return MDR_ERR_INVALID;
+  const int rc = pair_shape(&tgt_actors[0], tgt_critic, nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  if (!pointers_ok(tgt_critic)) return MDR_ERR_INVALID;
+  for (int k = 0; k < nb_nets; ++k)
+    if (!pointers_ok(&tgt_actors[k])) return MDR_ERR_INVALID;
+  const int F = tgt_actors[0].num_state;
+  if (nb_rows < 0 || max_workgroups < 0 || ld_state < (int64_t)nb_agents * F || agent < 0 || agent >= nb_agents) return MDR_ERR_INVALID;
+  if (!(tau > 0.0f) || !(fabsf(tau) <= FLT_MAX) || !(fabsf(gamma) <= FLT_MAX)) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  for (int k = 1; k < nb_nets; ++k) {
+    const mdr_mlp_t &n = tgt_actors[k], &n0 = tgt_actors[0];
+    if (n.num_state != n0.num_state || n.hidden1 != n0.hidden1 || n.hidden2 != n0.hidden2 || n.num_out != n0.num_out) return MDR_ERR_UNSUPPORTED;
+  }
+  if (nb_rows == 0) return MDR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int cap = lib_cap(max_workgroups);
+  PickAgentsArgs pa{};
+  static_assert(sizeof(PickAgentsArgs) <= 4096, "the kernel argument block");
+  RowArgs& a = pa.r;
+  a.actor = make_net(&tgt_actors[0]), a.critic = make_net(tgt_critic);
+  a.state = next_state, a.ld = ld_state, a.index = index, a.B = nb_rows, a.N = nb_agents, a.F = F, a.agent = agent;
+  a.noise = noise, a.tau = tau, a.gamma = gamma, a.reward = reward, a.picks = next_action, a.out0 = y, a.out1 = next_q;
+  for (int k = 0; k < nb_nets; ++k)
+    pa.nets[k] = NetPtrs{tgt_actors[k].w1, tgt_actors[k].b1, tgt_actors[k].w2, tgt_actors[k].b2, tgt_actors[k].w3, tgt_actors[k].b3};
+  // the picks: per agent ceil(B / 16) tiles of that agent's rows, through that agent's own target actor (ddpg.py:282-284)
+  pa.TB = (nb_rows + TILE - 1) / TILE;
+  a.R = nb_rows * nb_agents, a.ntiles = pa.TB * nb_agents;
+  if (launch_rows<MODE_PICK_AGENTS>(pa, cap, st) != MDR_OK) return MDR_ERR_HIP;
   a.R = nb_rows, a.ntiles = (a.R + TILE - 1) / TILE;
   return launch_rows<MODE_TARGET>(a, cap, st);
 }

@@ -17,13 +17,17 @@ Places that leave the reference's text on purpose:
 * train_ddpg.py:86-91 and :111-115 store agent 0's observation for every agent.  Here every agent stores its own.
 * The sharing block of ``MADDPG.__init__`` sits outside the loop (ddpg.py:217-223): under ``DDPG_shared: True`` only the last agent
   shares with agent 0.  Here there is one actor, one critic and one target of each for all agents - what the flag means and what every
-  other learner of this project does.  Unshared per-agent networks are not covered.
+  other learner of this project does - ``MADDPGLearner(shared=True)``, the default.  ``shared=False`` is the reference's other
+  setting, which every checkpoint of ``saveDDPGDict`` holds: one actor, critic and target of each PER AGENT.  Acting then goes
+  through ``FusedMLPActors`` and the target's picks through ``mdr_maddpg_target_agents`` (agent k's next action from agent k's own
+  target actor); the critic's and the actor's step read agent a's nets alone and use the same kernels as the shared mode.
 * There is no terminal mask, as in ``mdr_dqn_target``: the reference's env never ends.
 * The actor step does not write the critic's ``.grad``.  The reference pollutes it and zeroes it before its next use: unobservable.
 * The clip norm is the literal 0.5 of ddpg.py:157 and :163; ``DDPG_prop["max_grad_norm"]`` is read by nobody in the reference.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 from typing import Dict, Optional, Tuple
 
@@ -40,6 +44,9 @@ MAX_STATE, MAX_HIDDEN, MAX_JOINT = 64, 256, 1280      # the kernels' limits (inc
 # autograd per update at 64 and 256 rows and 0.6-0.7x at 4096; nothing between was measured, so auto stays with the largest size they won)
 AUTO_MIN_ROWS = 1
 AUTO_MAX_ROWS = 256
+# ... and for unshared per-agent networks (MADDPGLearner(shared=False)): torch, until profiles/maddpg_agents_README.md holds a table in
+# which the kernels won at 64 and 256 rows by three times the run-to-run spread
+AUTO_UNSHARED = False
 PSE = 1e-3      # ddpg.py:339
 
 
@@ -113,18 +120,45 @@ def _check_steps(actor, state, index, nb_agents, what):
     return dev, M, ld, (int(index.shape[0]) if index is not None else M)
 
 
+def _is_seq(nets) -> bool:
+    return isinstance(nets, (list, tuple))
+
+
+def _agents_refusal(actors, critic, nb_agents: int) -> Optional[str]:
+    """Why the per-agent kernels do not take these N actors with this critic (None: they do)."""
+    actors = list(actors)
+    if len(actors) != int(nb_agents):
+        return "%d actors for %d agents" % (len(actors), int(nb_agents))
+    if len(actors) > nat.MDR_MAX_AGENT_NETS:
+        return "%d per-agent networks: the kernels cover at most %d" % (len(actors), nat.MDR_MAX_AGENT_NETS)
+    for k, actor in enumerate(actors):
+        why = _refusal(actor, critic, nb_agents)
+        if why:
+            return "agent %d: %s" % (k, why)
+    shape = [lin.weight.shape for lin in L.fc_layers(actors[0])]
+    for k, actor in enumerate(actors):
+        if [lin.weight.shape for lin in L.fc_layers(actor)] != shape:
+            return "agent %d's actor has another shape than agent 0's" % k
+    return None
+
+
 def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch.Tensor, agent: int, noise: torch.Tensor,
                   tau: float = 1.0, gamma: float = 0.99, index: Optional[torch.Tensor] = None, max_workgroups: int = 0
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``target_value`` of ddpg.py:317-322 for agent ``agent`` -> (y, next_q - float32 [B] -, next_action uint8 [B, N]).
     ``next_state`` float32 [M, N, F] and ``reward`` float32 [M, N] are the replay buffer, read in place through ``index`` (int64 [B];
-    None: every env-step in order); ``noise`` float32 [B, N, 2] the gumbel noise of the N picks of every row.  Nothing is
-    differentiated."""
+    None: every env-step in order); ``noise`` float32 [B, N, 2] the gumbel noise of the N picks of every row.  ``tgt_actor``: one
+    module for all agents, or a sequence of N - agent k's pick then comes from ``tgt_actor[k]`` (ddpg.py:282-284;
+    mdr_maddpg_target_agents).  Nothing is differentiated."""
     what = "maddpg_target"
     N = int(reward.shape[1]) if reward.dim() == 2 else 0
-    why = _refusal(tgt_actor, tgt_critic, N)
+    per_agent = _is_seq(tgt_actor)
+    why = _agents_refusal(tgt_actor, tgt_critic, N) if per_agent else _refusal(tgt_actor, tgt_critic, N)
     if why:
         raise ValueError("%s: %s" % (what, why))
+    tgt_actors = list(tgt_actor) if per_agent else None
+    if per_agent:
+        tgt_actor = tgt_actors[0]
     dev, M, ld, B = _check_steps(tgt_actor, next_state, index, N, what)
     L.whole(reward, torch.float32, M * N, dev, what, "reward")
     L.whole(noise, torch.float32, B * N * 2, dev, what, "noise")
@@ -134,10 +168,16 @@ def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch
     next_q = torch.empty(B, dtype=torch.float32, device=dev)
     next_action = torch.empty((B, N), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.mdr_maddpg_target(C.byref(adesc), C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
-                                   L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q), L.ptr(next_action),
-                                   L.stream(dev))
-    nat.check(lib, None, rc, "mdr_maddpg_target")
+        if per_agent:
+            descs = L.mlp_descs([L.fc_layers(m) for m in tgt_actors])
+            rc = lib.mdr_maddpg_target_agents(descs, N, C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
+                                              L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q),
+                                              L.ptr(next_action), L.stream(dev))
+        else:
+            rc = lib.mdr_maddpg_target(C.byref(adesc), C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
+                                       L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q),
+                                       L.ptr(next_action), L.stream(dev))
+    nat.check(lib, None, rc, "mdr_maddpg_target_agents" if per_agent else "mdr_maddpg_target")
     return y, next_q, next_action
 
 
@@ -225,59 +265,119 @@ class JointReplayBuffer(L.RingBuffer):
 
 
 class MADDPGLearner:
-    """``MADDPG`` of agents/ddpg.py without the acting half, with shared networks (module docstring): the actor, the critic, a target
-    of each loaded from it (ddpg.py:79-91), the joint replay buffer and the two optimisers; ``store`` and ``update``.
+    """``MADDPG`` of agents/ddpg.py without the acting half: the actor, the critic, a target of each loaded from it (ddpg.py:79-91),
+    the joint replay buffer and the two optimisers; ``store`` and ``update``.  ``shared=True`` (default): one actor, one critic and
+    one target of each for all agents (module docstring).  ``shared=False``: the reference's per-agent networks (ddpg.py:200-213) -
+    ``actor`` and ``critic`` are sequences of ``nb_agents`` modules of one shape each, and every agent has its own targets and its
+    own two optimisers.  Either way ``actors``, ``critics``, ``tgt_actors``, ``tgt_critics``, ``actor_optimizers`` and
+    ``critic_optimizers`` are lists of ``nb_agents`` (shared: every entry the one shared object); ``actor``, ``critic``,
+    ``tgt_actor``, ``tgt_critic``, ``actor_optimizer`` and ``critic_optimizer`` are the shared objects, and None when unshared.
 
     ``backend="hip"``: target, both losses and both gradients from the kernels (ValueError for networks they refuse); ``"torch"``: the
     reference's expressions under autograd - the comparator and the fallback; ``"auto"``: the kernels where ``supported()`` holds
     and the minibatch has ``AUTO_MIN_ROWS`` to ``AUTO_MAX_ROWS`` rows (where they measured faster), torch otherwise.  ``optimizer``: called as ``optimizer(params, lr)`` for
     each network; with ``mdr_amd.optim.FusedAdam`` every clip + Adam is one ``step(max_grad_norm=0.5)`` and the last step of each net
-    in an ``update()`` carries the target blend (``target=..., tau=soft_tau``)."""
+    in an ``update()`` carries the target blend (``target=..., tau=soft_tau``).  Unshared nets take ONE step each per ``update()``:
+    critic a's blend rides on critic a's step (nobody reads ``tgt_critics[a]`` afterwards), the actors' blends never ride - every
+    later agent of the same update reads ``tgt_actors[a]`` as the previous update left it - and follow the loop.  ``"auto"`` resolves
+    to torch for unshared nets (``AUTO_UNSHARED`` above)."""
 
     MAX_GRAD_NORM = 0.5      # ddpg.py:157, 163
 
     def __init__(self, actor, critic, nb_agents: int, lr_actor: float, lr_critic: float, gamma: float = 0.99, soft_tau: float = 0.01,
                  gumbel_tau: float = 1.0, batch_size: int = 64, buffer_capacity: int = 524288, backend: str = "auto",
-                 optimizer=torch.optim.Adam):
+                 optimizer=torch.optim.Adam, shared: bool = True):
         L.check_backend(backend)
-        if backend == "hip":
-            L.require(_refusal(actor, critic, nb_agents), "MADDPGLearner")
-        fa, fc = L.fc_layers(actor), L.fc_layers(critic)
-        if fa is None or fc is None:
+        self.shared, self.nb_agents = bool(shared), int(nb_agents)
+        N = self.nb_agents
+        if self.shared:
+            if backend == "hip":
+                L.require(_refusal(actor, critic, nb_agents), "MADDPGLearner")
+            actors, critics = [actor], [critic]
+        else:
+            if not _is_seq(actor) or not _is_seq(critic) or len(actor) != N or len(critic) != N:
+                raise ValueError("MADDPGLearner(shared=False): actor and critic must be sequences of nb_agents = %d modules" % N)
+            actors, critics = list(actor), list(critic)
+        if any(L.fc_layers(m) is None for m in actors + critics):
             raise ValueError("MADDPGLearner: actor and critic need the reference's Linear-ReLU-Linear-ReLU-Linear stack (DDPGNetworkMLP)")
-        self.actor, self.critic, self.nb_agents = actor, critic, int(nb_agents)
+        for nets, what in ((actors, "actor"), (critics, "critic")):
+            shape = [lin.weight.shape for lin in L.fc_layers(nets[0])]
+            for k, m in enumerate(nets):
+                if [lin.weight.shape for lin in L.fc_layers(m)] != shape:
+                    raise ValueError("MADDPGLearner(shared=False): agent %d's %s has another shape than agent 0's" % (k, what))
+        if not self.shared and backend == "hip":
+            L.require(_agents_refusal(actors, critics[0], N), "MADDPGLearner")
+            for k in range(N):
+                L.require(_refusal(actors[k], critics[k], N), "MADDPGLearner")
+        fa, fc = L.fc_layers(actors[0]), L.fc_layers(critics[0])
         dev = fa[0].weight.device
         self.num_state = fa[0].in_features
         if fc[0].in_features != self.nb_agents * (self.num_state + 2):
             raise ValueError("MADDPGLearner: the critic must read nb_agents * (num_state + 2) inputs")
-        self.tgt_actor = DDPGNetworkMLP(self.num_state, fa[2].out_features, fa[0].out_features).to(dev)
-        self.tgt_critic = DDPGNetworkMLP(fc[0].in_features, fc[2].out_features, fc[0].out_features).to(dev)
-        for tgt, net in ((self.tgt_actor, actor), (self.tgt_critic, critic)):
+        tgt_actors = [DDPGNetworkMLP(self.num_state, fa[2].out_features, fa[0].out_features).to(dev) for _ in actors]
+        tgt_critics = [DDPGNetworkMLP(fc[0].in_features, fc[2].out_features, fc[0].out_features).to(dev) for _ in critics]
+        for tgt, net in list(zip(tgt_actors, actors)) + list(zip(tgt_critics, critics)):
             for t, s in zip(tgt.fc, net.fc):
                 if t.weight.shape != s.weight.shape:
                     raise ValueError("MADDPGLearner: both hidden layers of a net have the same width in the reference")
                 t.weight.data.copy_(s.weight.data)
                 t.bias.data.copy_(s.bias.data)
         self.gamma, self.soft_tau, self.gumbel_tau = float(gamma), float(soft_tau), float(gumbel_tau)
+        self.lr_actor, self.lr_critic = lr_actor, lr_critic
         self.batch_size, self.backend = int(batch_size), backend
         self.buffer = JointReplayBuffer(buffer_capacity, self.nb_agents, self.num_state, dev)
-        self.actor_optimizer = optimizer(actor.parameters(), lr_actor)
-        self.critic_optimizer = optimizer(critic.parameters(), lr_critic)
+        actor_optimizers = [optimizer(m.parameters(), lr_actor) for m in actors]
+        critic_optimizers = [optimizer(m.parameters(), lr_critic) for m in critics]
+        rep = N if self.shared else 1      # shared: every entry of the lists is the one shared object
+        self.actors, self.critics, self.tgt_actors, self.tgt_critics = actors * rep, critics * rep, tgt_actors * rep, tgt_critics * rep
+        self.actor_optimizers, self.critic_optimizers = actor_optimizers * rep, critic_optimizers * rep
+        one = (lambda lst: lst[0]) if self.shared else (lambda lst: None)
+        self.actor, self.critic, self.tgt_actor, self.tgt_critic = one(actors), one(critics), one(tgt_actors), one(tgt_critics)
+        self.actor_optimizer, self.critic_optimizer = one(actor_optimizers), one(critic_optimizers)
         self.training_step = 0
-        self.before_step = None      # optional callable(learner, "critic" | "actor", agent): after a backward, before its clip and step
+        # optional callable(learner, "critic" | "actor", agent): after a backward, before its clip and step - the gradient to look at
+        # is critics[agent]'s or actors[agent]'s
+        self.before_step = None
 
     @classmethod
     def from_config(cls, ddpg_prop: dict, actor, critic, nb_agents: int, backend: str = "auto", optimizer=torch.optim.Adam) -> "MADDPGLearner":
-        """From the reference's ``config_dict["DDPG_prop"]`` (agents/ddpg.py:60-70)."""
+        """From the reference's ``config_dict["DDPG_prop"]`` (agents/ddpg.py:60-70).  ``DDPG_shared`` (ddpg.py:214-215; absent: shared)
+        false: ``actor`` and ``critic`` are the caller's lists of ``nb_agents`` modules."""
         return cls(actor, critic, nb_agents, ddpg_prop["lr_actor"], ddpg_prop["lr_critic"], gamma=ddpg_prop["gamma"],
                    soft_tau=ddpg_prop["soft_tau"], gumbel_tau=ddpg_prop["gumbel_softmax_tau"], batch_size=ddpg_prop["batch_size"],
-                   buffer_capacity=ddpg_prop["buffer_capacity"], backend=backend, optimizer=optimizer)
+                   buffer_capacity=ddpg_prop["buffer_capacity"], backend=backend, optimizer=optimizer,
+                   shared=bool(ddpg_prop.get("DDPG_shared", True)))
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
+            if not self.shared:      # every net would have to pass (_agents_refusal and _refusal of each pair, targets too)
+                return AUTO_UNSHARED
             return (_refusal(self.actor, self.critic, self.nb_agents) is None and
                     _refusal(self.tgt_actor, self.tgt_critic, self.nb_agents) is None and AUTO_MIN_ROWS <= nb_rows <= AUTO_MAX_ROWS)
         return self.backend == "hip"
+
+    def network_dict(self) -> Dict[int, dict]:
+        """The dict ``saveDDPGDict`` writes (utils.py:1165-1187): one entry per agent - the four state_dicts (keys ``net.0|2|4.*``),
+        the two optimisers' and the scalars.  Shared: every entry repeats the one set."""
+        return {i: {"actor_state_dict": self.actors[i].state_dict(), "actor_optimizer_state_dict": self.actor_optimizers[i].state_dict(),
+                    "critic_state_dict": self.critics[i].state_dict(), "critic_optimizer_state_dict": self.critic_optimizers[i].state_dict(),
+                    "tgt_actor_net_state_dict": self.tgt_actors[i].state_dict(), "tgt_critic_net_state_dict": self.tgt_critics[i].state_dict(),
+                    "lr_actor": self.lr_actor, "lr_critic": self.lr_critic, "gamma": self.gamma, "soft_tau": self.soft_tau}
+                for i in range(self.nb_agents)}
+
+    def load_network_dict(self, d: Dict[int, dict]) -> None:
+        """Load a ``network_dict()`` - or a dict the reference wrote - in place: the tensors keep their addresses.  Entry i goes to
+        agent i's nets (shared: entry 0 to the one set); optimiser states are loaded where the entry has them."""
+        if sorted(d.keys()) != list(range(self.nb_agents)):
+            raise ValueError("load_network_dict: one entry per agent 0 .. %d expected" % (self.nb_agents - 1))
+        for i in range(1 if self.shared else self.nb_agents):
+            e = d[i]
+            for net, key in ((self.actors[i], "actor_state_dict"), (self.critics[i], "critic_state_dict"),
+                             (self.tgt_actors[i], "tgt_actor_net_state_dict"), (self.tgt_critics[i], "tgt_critic_net_state_dict")):
+                net.load_state_dict(e[key])
+            for opt, key in ((self.actor_optimizers[i], "actor_optimizer_state_dict"), (self.critic_optimizers[i], "critic_optimizer_state_dict")):
+                if e.get(key) is not None:      # a copy: torch keeps tensors of the right dtype and device as they are, and a dict taken
+                    opt.load_state_dict(copy.deepcopy(e[key]))      # from a live learner would share its Adam moments with this one
 
     def store(self, batch: Dict[str, torch.Tensor]) -> None:
         """``MADDPG.push`` (ddpg.py:250-262) for every env-step of a ``collect_maddpg_transitions`` dict."""
@@ -304,7 +404,8 @@ class MADDPGLearner:
 
     def update_target(self) -> None:
         """ddpg.py:167-174: to = soft_tau * from + (1 - soft_tau) * to over both pairs of nets."""
-        for tgt, net in ((self.tgt_actor, self.actor), (self.tgt_critic, self.critic)):
+        n = 1 if self.shared else self.nb_agents
+        for tgt, net in list(zip(self.tgt_actors[:n], self.actors[:n])) + list(zip(self.tgt_critics[:n], self.critics[:n])):
             L.blend(L.mlp_params(tgt.fc), L.mlp_params(net.fc), self.soft_tau)
 
     def _step(self, opt, net, blend_target) -> None:
@@ -316,45 +417,53 @@ class MADDPGLearner:
             L.clip_and_step(opt, net.parameters(), self.MAX_GRAD_NORM)
 
     def critic_backward(self, agent: int, index: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
-        """Target, mse loss and backward of the critic for agent ``agent`` on the env-steps at ``index``: fills the critic's ``.grad``."""
+        """Target, mse loss and backward of the critic for agent ``agent`` on the env-steps at ``index``: fills the ``.grad`` of
+        ``critics[agent]``.  Unshared: every agent's next action from ITS OWN target actor (ddpg.py:282-284), the value from
+        ``tgt_critics[agent]``."""
         buf, N = self.buffer, self.nb_agents
+        critic, tgt_critic = self.critics[agent], self.tgt_critics[agent]
         if self.uses_kernels(int(index.shape[0])):
-            y, _, _ = maddpg_target(self.tgt_actor, self.tgt_critic, buf.next_state, buf.reward, agent, noise, self.gumbel_tau, self.gamma,
-                                    index=index)
-            return joint_q_loss_backward(self.actor, self.critic, buf.state, buf.action, y, index=index)
+            y, _, _ = maddpg_target(self.tgt_actor if self.shared else self.tgt_actors, tgt_critic, buf.next_state, buf.reward, agent, noise,
+                                    self.gumbel_tau, self.gamma, index=index)
+            return joint_q_loss_backward(self.actors[agent], critic, buf.state, buf.action, y, index=index)
         B = int(index.shape[0])
         state, next_state = buf.state[index], buf.next_state[index]
         action = F.one_hot(buf.action[index].clamp(max=1), 2).to(torch.float32)
         with torch.no_grad():
-            next_action = self._hard(self.tgt_actor(next_state), noise, self.gumbel_tau)
-            next_q = self.tgt_critic(torch.cat((next_state.reshape(B, -1), next_action.reshape(B, -1)), 1)).squeeze(1)
+            if self.shared:
+                logits = self.tgt_actor(next_state)
+            else:
+                logits = torch.stack([self.tgt_actors[k](next_state[:, k]) for k in range(N)], 1)
+            next_action = self._hard(logits, noise, self.gumbel_tau)
+            next_q = tgt_critic(torch.cat((next_state.reshape(B, -1), next_action.reshape(B, -1)), 1)).squeeze(1)
             target_value = buf.reward[index][:, agent] + self.gamma * next_q
-        critic_value = self.critic(torch.cat((state.reshape(B, -1), action.reshape(B, -1)), 1)).squeeze(1)
+        critic_value = critic(torch.cat((state.reshape(B, -1), action.reshape(B, -1)), 1)).squeeze(1)
         loss = F.mse_loss(critic_value, target_value, reduction="mean")
-        self.critic_optimizer.zero_grad()
+        self.critic_optimizers[agent].zero_grad()
         loss.backward()
         return loss.detach()
 
     def actor_backward(self, agent: int, index: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
-        """The actor's loss and backward for agent ``agent``: fills the actor's ``.grad``."""
+        """The actor's loss and backward for agent ``agent``: fills the ``.grad`` of ``actors[agent]``, through ``critics[agent]``."""
         buf = self.buffer
+        actor, critic = self.actors[agent], self.critics[agent]
         if self.uses_kernels(int(index.shape[0])):
-            return actor_loss_backward(self.actor, self.critic, buf.state, buf.action, agent, noise, self.gumbel_tau, PSE, index=index)
+            return actor_loss_backward(actor, critic, buf.state, buf.action, agent, noise, self.gumbel_tau, PSE, index=index)
         B = int(index.shape[0])
         state = buf.state[index]
         action = F.one_hot(buf.action[index].clamp(max=1), 2).to(torch.float32)
-        logits = self.actor(state[:, agent])
+        logits = actor(state[:, agent])
         action_ = self._hard(logits, noise, self.gumbel_tau)
         action = torch.cat((action[:, :agent], action_[:, None], action[:, agent + 1:]), 1)
-        for p in self.critic.parameters():      # the reference lets this backward write the critic's .grad and zeroes it later
+        for p in critic.parameters():      # the reference lets this backward write the critic's .grad and zeroes it later
             p.requires_grad_(False)
         try:
-            actor_loss = -self.critic(torch.cat((state.reshape(B, -1), action.reshape(B, -1)), 1)).squeeze(1).mean()
+            actor_loss = -critic(torch.cat((state.reshape(B, -1), action.reshape(B, -1)), 1)).squeeze(1).mean()
             loss = actor_loss + PSE * torch.pow(logits, 2).mean()
-            self.actor_optimizer.zero_grad()
+            self.actor_optimizers[agent].zero_grad()
             loss.backward()
         finally:
-            for p in self.critic.parameters():
+            for p in critic.parameters():
                 p.requires_grad_(True)
         return loss.detach()
 
@@ -367,8 +476,27 @@ class MADDPGLearner:
             return None
         N = self.nb_agents
         index, noise_t, noise_a = self.draws(seed)
-        fused_a, fused_c = isinstance(self.actor_optimizer, FusedAdam), isinstance(self.critic_optimizer, FusedAdam)
+        fused_a, fused_c = isinstance(self.actor_optimizers[0], FusedAdam), isinstance(self.critic_optimizers[0], FusedAdam)
         a_losses, c_losses = [], []
+        if not self.shared:
+            # ddpg.py:305-339 literally: per agent a fresh minibatch, every agent's next action from its own target actor as the
+            # PREVIOUS update left it, critic a's step, actor a's step; then the 2 N blends.  Critic a's blend may ride on its step;
+            # an actor's may not - tgt_actors[a] is read by every later agent of this update
+            for a in range(N):
+                c_losses.append(self.critic_backward(a, index[a], noise_t[a]))
+                if self.before_step is not None:
+                    self.before_step(self, "critic", a)
+                self._step(self.critic_optimizers[a], self.critics[a], self.tgt_critics[a] if fused_c else None)
+                a_losses.append(self.actor_backward(a, index[a], noise_a[a]))
+                if self.before_step is not None:
+                    self.before_step(self, "actor", a)
+                self._step(self.actor_optimizers[a], self.actors[a], None)
+            for a in range(N):
+                L.blend(L.mlp_params(self.tgt_actors[a].fc), L.mlp_params(self.actors[a].fc), self.soft_tau)
+                if not fused_c:
+                    L.blend(L.mlp_params(self.tgt_critics[a].fc), L.mlp_params(self.critics[a].fc), self.soft_tau)
+            self.training_step += 1
+            return torch.stack(a_losses), torch.stack(c_losses)
         for a in range(N):
             last = a == N - 1
             c_losses.append(self.critic_backward(a, index[a], noise_t[a]))
@@ -390,19 +518,22 @@ class GreedyDDPGActor:
     """``DDPGAgent.act`` (agents/rl_controllers.py): the argmax of the actor's logits, in the shape ``deploy_policy`` takes through
     its duck-typed branch - ``.sample(rows, seed, step, action=None, step_dev=None)`` -> uint8 actions.  ``backend="torch"`` (default):
     a torch forward and a compare; ``"hip"``: the greedy form of ``FusedMLPActor`` - forward and argmax in one kernel (ValueError for a
-    net it does not take); it honours ``step_dev``, which a greedy pick does not read."""
+    net it does not take); it honours ``step_dev``, which a greedy pick does not read.  ``actor``: one module, or a sequence of N
+    (unshared networks): row e N + k is agent k's and goes through ``actor[k]`` - N torch forwards, or ``FusedMLPActors``."""
 
     def __init__(self, actor, backend: str = "torch"):
         if backend not in ("torch", "hip"):
             raise ValueError("backend must be 'torch' or 'hip'")
-        self.actor, self.backend = actor, backend
+        self.actor, self.backend = (list(actor) if _is_seq(actor) else actor), backend
+        self.per_agent = _is_seq(actor)
         self._fused = self._a_prob = None
         if backend == "hip":
-            from .mlp_actor import FusedMLPActor
-            why = FusedMLPActor.refusal(actor)
+            from .mlp_actor import FusedMLPActor, FusedMLPActors
+            kind = FusedMLPActors if self.per_agent else FusedMLPActor
+            why = kind.refusal(self.actor)
             if why:
                 raise ValueError("GreedyDDPGActor(backend='hip'): " + why)
-            self._fused = FusedMLPActor(actor, greedy=True)
+            self._fused = kind(self.actor, greedy=True)
 
     @torch.no_grad()
     def sample(self, rows: torch.Tensor, seed: int = 0, step: int = 0, action: Optional[torch.Tensor] = None, step_dev=None) -> torch.Tensor:
@@ -410,7 +541,12 @@ class GreedyDDPGActor:
             if self._a_prob is None or self._a_prob.numel() != rows.shape[0] or self._a_prob.device != rows.device:
                 self._a_prob = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)      # kept: a captured step allocates nothing
             return self._fused.sample(rows, seed, step, step_dev=step_dev, action=action, a_prob=self._a_prob)[0]
-        logits = self.actor(rows)
+        if self.per_agent:
+            N = len(self.actor)
+            per = rows.view(rows.shape[0] // N, N, rows.shape[1])
+            logits = torch.stack([self.actor[k](per[:, k]) for k in range(N)], 1).view(rows.shape[0], 2)
+        else:
+            logits = self.actor(rows)
         act = logits[:, 1] > logits[:, 0]      # argmax keeps the first maximum
         if action is None:
             return act.to(torch.uint8)
@@ -429,7 +565,7 @@ def train_maddpg(env, learner: MADDPGLearner, nb_steps: int, update_every: int =
     a_losses, c_losses = [], []
     for t in range(int(nb_steps)):
         step = t + 1      # train_ddpg.py:96-97, 124-127: random while step < random_steps, learn from step >= random_steps on
-        batch = collect_maddpg_transitions(env, learner.actor, 1, random_steps_left=max(int(random_steps) - step, 0),
+        batch = collect_maddpg_transitions(env, learner.actor if getattr(learner, "shared", True) else learner.actors, 1, random_steps_left=max(int(random_steps) - step, 0),
                                            seed=(int(seed) * 1000003 + t) & (2 ** 63 - 1), actor_backend=actor_backend)
         learner.store(batch)
         if step >= int(random_steps) and step % int(update_every) == 0:

@@ -91,3 +91,79 @@ class FusedMLPActor:
                                                 L.ptr(a_prob), L.ptr(probs), L.stream(dev))
         nat.check(self._lib, None, rc, "mdr_mlp_actor_sample")
         return (action, a_prob, probs) if want_probs else (action, a_prob)
+
+
+class FusedMLPActors:
+    """One actor per agent (MADDPG with unshared networks, ddpg.py:200-213) acting in ONE launch (include/mdr_policy.h:
+    mdr_mlp_actors_sample): row ``e * N + k`` of the observation rows goes through ``modules[k]``.  ``modules``: a sequence of 1 to 32
+    nets ``FusedMLPActor`` takes, all of one shape and on one device.  The modules are held, not copied, and their descriptors are
+    rebuilt from the live tensors on every call, so every agent's optimiser step is seen by the next call.  The draw is keyed by the
+    row's index in the whole batch: rows ``k::N`` have the bits ``FusedMLPActor(modules[k])`` gives them on the same batch."""
+
+    def __init__(self, modules, greedy: bool = False):
+        modules = list(modules)
+        why = self.refusal(modules)
+        if why:
+            raise ValueError("FusedMLPActors: " + why)
+        self.modules, self.greedy = modules, bool(greedy)
+        self._lib = nat.load()
+
+    @staticmethod
+    def refusal(modules) -> Optional[str]:
+        """Why the kernel does not take these nets (None: it does)."""
+        modules = list(modules)
+        if not 1 <= len(modules) <= nat.MDR_MAX_AGENT_NETS:
+            return "%d nets: the kernel covers 1 to %d" % (len(modules), nat.MDR_MAX_AGENT_NETS)
+        for k, m in enumerate(modules):
+            why = FusedMLPActor.refusal(m)
+            if why:
+                return "net %d: %s" % (k, why)
+        fcs = [L.fc_layers(m) for m in modules]
+        shape = [lin.weight.shape for lin in fcs[0]]
+        for k, fc in enumerate(fcs):
+            if [lin.weight.shape for lin in fc] != shape:
+                return "net %d has another shape than net 0: all nets share num_state and both hidden sizes" % k
+            if fc[0].weight.device != fcs[0][0].weight.device:
+                return "net %d is on another device than net 0" % k
+        return None
+
+    @classmethod
+    def supported(cls, modules) -> bool:
+        """Does the kernel take these nets?  1 to 32 of them, each one ``FusedMLPActor`` takes, of one shape, on one device."""
+        return cls.refusal(modules) is None
+
+    @property
+    def device(self) -> torch.device:
+        return L.fc_layers(self.modules[0])[0].weight.device
+
+    @property
+    def num_state(self) -> int:
+        return L.fc_layers(self.modules[0])[0].in_features
+
+    def sample(self, rows: torch.Tensor, seed: int, step: int, step_dev: Optional[torch.Tensor] = None, greedy: Optional[bool] = None,
+               action: Optional[torch.Tensor] = None, a_prob: Optional[torch.Tensor] = None, want_probs: bool = False,
+               max_workgroups: int = 0) -> Tuple[torch.Tensor, ...]:
+        """``rows`` float32 [E * N, F] (env-major: row e N + k is agent k of env e) -> what ``FusedMLPActor.sample`` returns, every
+        argument as there."""
+        what = "FusedMLPActors.sample"
+        why = self.refusal(self.modules)      # the modules are the caller's: they may have changed since the constructor looked
+        if why:
+            raise ValueError("%s: %s" % (what, why))
+        fcs = [L.fc_layers(m) for m in self.modules]
+        N = len(fcs)
+        dev, _, ld, A = L.check_rows(fcs[0], rows, None, what)
+        if A % N != 0:
+            raise ValueError("%s: %d rows are no multiple of the %d nets" % (what, A, N))
+        if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.device != dev):
+            raise ValueError("step_dev must be an int32 tensor on the device (env.device_time_index)")
+        action = torch.empty(A, dtype=torch.uint8, device=dev) if action is None else L.whole(action, torch.uint8, A, dev, what, "action")
+        a_prob = torch.empty(A, dtype=torch.float32, device=dev) if a_prob is None else L.whole(a_prob, torch.float32, A, dev, what, "a_prob")
+        probs = torch.empty((A, 2), dtype=torch.float32, device=dev) if want_probs else None
+        descs = L.mlp_descs(fcs)
+        with torch.cuda.device(dev):
+            rc = self._lib.mdr_mlp_actors_sample(descs, N, L.ptr(rows), ld, A, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                 C.c_uint64(int(step) & (2 ** 64 - 1)), L.ptr(step_dev),
+                                                 int(self.greedy if greedy is None else bool(greedy)), int(max_workgroups), L.ptr(action),
+                                                 L.ptr(a_prob), L.ptr(probs), L.stream(dev))
+        nat.check(self._lib, None, rc, "mdr_mlp_actors_sample")
+        return (action, a_prob, probs) if want_probs else (action, a_prob)

@@ -443,7 +443,7 @@ def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float
     return {"state": state, "action": action, "reward": reward, "explored": explored, "epsilon": eps}
 
 
-def collect_maddpg_transitions(env, actor: nn.Module, nb_steps: int, random_steps_left: int = 0, seed: int = 0,
+def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int = 0, seed: int = 0,
                                actor_backend: str = "torch") -> Dict[str, torch.Tensor]:
     """The interaction loop of train_ddpg.py:95-116 for all envs at once, env-steps kept on the GPU: every step the actor's logits on
     every agent's OWN observation (the reference stores agent 0's for all, train_ddpg.py:86-91), the acting action, ``env.step``,
@@ -458,20 +458,28 @@ def collect_maddpg_transitions(env, actor: nn.Module, nb_steps: int, random_step
     agree with torch's to fp32 rounding), ValueError for a net the kernel does not take.  It measured faster than "torch" at every
     size tried (profiles/mlp_actor_README.md; F = 51, hidden 256-256): 1.9-2.0x at 1 x 20 and 64 x 50 agents (both paths bound by the host
     there), 1.36x at 4096 x 20, 1.57x at 4096 x 1024; 1.40x at F = 121 and 4096 x 1024.  Other sizes: not measured.
-    The random steps are the same under both."""
+    The random steps are the same under both.
+
+    ``actor``: one module for all agents, or a sequence of N modules - agent k acts through ``actor[k]`` (MADDPG with unshared
+    networks, ddpg.py:200-213).  "torch": N forwards on ``state[t][:, k]``, the logits gathered to [E N, 2], then the one
+    ``mdr_logits_sample``; "hip": ``FusedMLPActors`` - one launch, the same (seed, step), so the same draws."""
     import ctypes as C
 
     from . import _native as nat
     if actor_backend not in ("torch", "hip"):
         raise ValueError("actor_backend must be 'torch' or 'hip'")
+    per_agent = isinstance(actor, (list, tuple))
     fused = None
     if actor_backend == "hip":
-        from .mlp_actor import FusedMLPActor
-        why = FusedMLPActor.refusal(actor)
+        from .mlp_actor import FusedMLPActor, FusedMLPActors
+        kind = FusedMLPActors if per_agent else FusedMLPActor
+        why = kind.refusal(actor)
         if why:
             raise ValueError("collect_maddpg_transitions(actor_backend='hip'): " + why)
-        fused = FusedMLPActor(actor)
+        fused = kind(actor)
     E, N = env.nb_envs, env.nb_houses
+    if per_agent and len(actor) != N:
+        raise ValueError("collect_maddpg_transitions: %d actors for %d agents" % (len(actor), N))
     dev = env.device
     F_len = env.obs_vector_length()
     T = int(nb_steps)
@@ -491,7 +499,10 @@ def collect_maddpg_transitions(env, actor: nn.Module, nb_steps: int, random_step
             fused.sample(state[t].view(E * N, F_len), seed, env.steps_taken, action=act, a_prob=a_prob)
         else:
             with torch.no_grad():
-                logits = actor(state[t].view(E * N, F_len)).contiguous()
+                if per_agent:
+                    logits = torch.stack([actor[k](state[t][:, k]) for k in range(N)], 1).view(E * N, 2).contiguous()
+                else:
+                    logits = actor(state[t].view(E * N, F_len)).contiguous()
             with torch.cuda.device(dev):
                 rc = lib.mdr_logits_sample(C.c_void_p(logits.data_ptr()), logits.stride(0), E * N, C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                            C.c_uint64(int(env.steps_taken) & (2 ** 64 - 1)), None, 0, C.c_void_p(act.data_ptr()), None, None,
