@@ -916,6 +916,34 @@ int mdr_minibatch_sample(int64_t nb, const int64_t *len_dev, int64_t len, uint64
 int mdr_minibatch_sample_keyed(int64_t nb, const int64_t *len_dev, int64_t len, const int32_t *key_dev, uint64_t step,
                                const int32_t *cursor_dev, int64_t *out, void *stream);
 
+/* Everything one MADDPG update draws (MADDPGLearner.draws: a fresh minibatch per agent, ddpg.py:268, 307, and the gumbel noise of
+ * every F.gumbel_softmax of the update), in ONE launch.  With c2 = step lo + *cursor_dev (mod 2^32, no carry), c3 = TAG ^ step hi and
+ * the key (k0, k1) = (seed lo, seed hi):
+ * `index` int64 [nb_agents][batch]: index[a][i] = element i of the permutation of mdr_minibatch_permutation over `len` elements - the
+ *   same Feistel network and cycle walk - with the round function word .x of Philox4x32-10 on the counter (R, (a << 8) | r, c2,
+ *   MDR_TAG_MADDPG_INDEX ^ step hi): `batch` DISTINCT positions below len per agent (np.random.choice(len, batch, replace=False)),
+ *   no sort, no scratch.  `len_dev` (may be NULL: `len` is taken): one device int64 read when the kernel runs, h = ceil(max(1,
+ *   ceil(log2 len)) / 2) then computed on the device; a device len < 1 is read as 1 (>= 2^62: as 2^62 - 1), and where it is below
+ *   `batch` the walk of element i starts at i mod len - such rows repeat positions, no position >= len is ever stored and no
+ *   walk is endless (a walk that starts below len returns to its start).
+ * `noise_t` float [nb_agents][batch][nb_agents][2], `noise_a` float [nb_agents][batch][2]: Gumbel(0, 1) noise, contiguous, as
+ *   mdr_maddpg_target[_agents] and mdr_maddpg_actor_grad read it per agent slice.  For q = (a batch + b) (nb_agents + 1) + k the words
+ *   .x, .y of Philox4x32-10 on the counter (q lo, q hi, c2, MDR_TAG_MADDPG_NOISE ^ step hi) give components 0 and 1 of
+ *   noise_t[a][b][k] (k < nb_agents) or noise_a[a][b] (k = nb_agents); the value is (float)(-log(-log(u))) with u = (word + 0.5) / 2^32,
+ *   evaluated in double (in fp32 u rounds to 1 for the top words and the noise would be infinite): finite, in about [-3.2, 22.9].
+ * nb_agents <= MDR_MADDPG_DRAWS_MAX_AGENTS = 1280 / 3: what mdr_maddpg_target's joint input of nb_agents (F + 2) <= 1280 columns
+ * admits at F = 1.  _keyed: the key from the device (int32 [2]), as above.  batch == 0 launches nothing.  Stream-ordered, never
+ * synchronises, allocates nothing.
+ * Returns 0; -1 (nb_agents < 1, batch < 0, a NULL output with batch > 0, len_dev NULL with len < 1 or batch > len, key_dev NULL);
+ * -3 (HIP error); -4 (nb_agents > MDR_MADDPG_DRAWS_MAX_AGENTS, len >= 2^62, more than 2^31 - 1 workgroups). */
+#define MDR_TAG_MADDPG_INDEX 0x4D444931u /* "MDI1" */
+#define MDR_TAG_MADDPG_NOISE 0x4D444E31u /* "MDN1" */
+#define MDR_MADDPG_DRAWS_MAX_AGENTS 426
+int mdr_maddpg_draws(int32_t nb_agents, int64_t batch, const int64_t *len_dev, int64_t len, uint64_t seed, uint64_t step,
+                     const int32_t *cursor_dev, int64_t *index, float *noise_t, float *noise_a, void *stream);
+int mdr_maddpg_draws_keyed(int32_t nb_agents, int64_t batch, const int64_t *len_dev, int64_t len, const int32_t *key_dev, uint64_t step,
+                           const int32_t *cursor_dev, int64_t *index, float *noise_t, float *noise_a, void *stream);
+
 /* The device block such captured launches read their cursors from, written stream-ordered by one-thread kernels whose values are
  * kernel arguments (copied at launch: no staging buffer that could be overwritten too early).  _set: dst[k] = v_k for k < count
  * (1 <= count <= 4); _add: dst[index] += delta.  Returns 0; -1 (dst NULL, count outside 1..4, index < 0); -3 (HIP error). */

@@ -183,6 +183,7 @@ class MdrTarmacA2CNet(C.Structure):
 
 MDR_ADAM_MAX_SEGMENTS = 32
 MDR_MAX_AGENT_NETS = 32      # include/mdr_policy.h: nets per call of mdr_mlp_actors_sample / mdr_maddpg_target_agents
+MDR_MADDPG_DRAWS_MAX_AGENTS = 426      # include/mdr_policy.h: agents per call of mdr_maddpg_draws
 
 
 class MdrAdamSegment(C.Structure):
@@ -225,7 +226,7 @@ EXPORTS = (
     "mdr_tarmac_a2c_grad_floats", "mdr_tarmac_a2c_workspace_bytes", "mdr_tarmac_a2c_forward", "mdr_tarmac_a2c_comm", "mdr_tarmac_a2c_grad",
     "mdr_adam_workspace_bytes", "mdr_adam_step", "mdr_adam_step_table", "mdr_adam_corrections",
     "mdr_minibatch_permutation", "mdr_minibatch_permutation_keyed", "mdr_minibatch_sample", "mdr_minibatch_sample_keyed",
-    "mdr_update_cursor_set", "mdr_update_cursor_add",
+    "mdr_update_cursor_set", "mdr_update_cursor_add", "mdr_maddpg_draws", "mdr_maddpg_draws_keyed",
 )
 
 _lib = None
@@ -375,6 +376,8 @@ def load():
         "mdr_minibatch_permutation_keyed": (C.c_int, [i64, vp, u64, vp, vp, vp]),
         "mdr_minibatch_sample": (C.c_int, [i64, vp, i64, u64, u64, vp, vp, vp]),
         "mdr_minibatch_sample_keyed": (C.c_int, [i64, vp, i64, vp, u64, vp, vp, vp]),
+        "mdr_maddpg_draws": (C.c_int, [i32, i64, vp, i64, u64, u64, vp, vp, vp, vp, vp]),
+        "mdr_maddpg_draws_keyed": (C.c_int, [i32, i64, vp, i64, vp, u64, vp, vp, vp, vp, vp]),
         "mdr_update_cursor_set": (C.c_int, [vp, i32, i32, i32, i32, i32, vp]),
         "mdr_update_cursor_add": (C.c_int, [vp, i32, i32, vp]),
         "mdr_env_pack": (C.c_int, [vp, i32, vp, vp]),

@@ -75,6 +75,69 @@ __global__ __launch_bounds__(THREADS) void k_minibatch_sample(const DrawArgs a) 
   a.out[i] = mdr::mulhi_pick(word, len);      // < len
 }
 
+// Everything MADDPGLearner.draws() returns, in one launch (include/mdr_policy.h: mdr_maddpg_draws).  Thread t < N B (N + 1) draws the
+// two gumbel values of noise counter q = t; the first N B threads also walk position t % B of agent t / B's Feistel permutation.
+struct MaddpgDrawArgs {
+  int64_t batch;                // B
+  int64_t rows;                 // N B
+  int64_t draws;                // N B (N + 1)
+  int64_t* index;               // [N][B]
+  float* noise_t;               // [N][B][N][2]
+  float* noise_a;               // [N][B][2]
+  const int32_t* cursor_dev;    // may be NULL
+  const int32_t* key_dev;       // may be NULL: k0, k1 below
+  const int64_t* len_dev;       // may be NULL: len below
+  int64_t len;
+  uint32_t k0, k1, c2, c3_index, c3_noise;
+  int32_t nb_agents;            // N
+};
+
+__device__ __forceinline__ float gumbel(uint32_t word) {
+  return (float)(-log(-log(mdr::u01(word))));      // in double: -log(u) stays in [1.2e-10, 22.9], the value is finite for every word
+}
+
+__global__ __launch_bounds__(THREADS) void k_maddpg_draws(const MaddpgDrawArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (t >= a.draws) return;
+  const uint32_t k0 = a.key_dev ? (uint32_t)a.key_dev[0] : a.k0;
+  const uint32_t k1 = a.key_dev ? (uint32_t)a.key_dev[1] : a.k1;
+  const uint32_t c2 = a.c2 + (a.cursor_dev ? (uint32_t)*a.cursor_dev : 0u);
+  const int64_t N = a.nb_agents;
+  {
+    const mdr::u32x4 w = philox4x32_10((uint32_t)t, (uint32_t)((uint64_t)t >> 32), c2, a.c3_noise, k0, k1);
+    const int64_t row = t / (N + 1), k = t - row * (N + 1);      // row = a B + b < N B
+    float* dst = k < N ? a.noise_t + (row * N + k) * 2 : a.noise_a + row * 2;
+    dst[0] = gumbel(w.x);
+    dst[1] = gumbel(w.y);
+  }
+  if (t >= a.rows) return;
+  int64_t len = a.len;
+  if (a.len_dev) {
+    len = *a.len_dev;
+    len = len < 1 ? 1 : (len > (1ll << 62) - 1 ? (1ll << 62) - 1 : len);
+  }
+  const int b = len > 1 ? 64 - __clzll((unsigned long long)(len - 1)) : 1;      // max(1, ceil(log2 len)) <= 62
+  const int h = (b + 1) / 2;                                                     // <= 31
+  const uint32_t mask = (uint32_t)((1ull << h) - 1ull);
+  const uint32_t agent = (uint32_t)(t / a.batch);
+  // a walk that starts below len comes back to its start, so it ends; a start at or beyond len (a device len below the batch) is
+  // reduced first - such rows repeat positions, none leaves [0, len)
+  uint64_t x = (uint64_t)(t - (int64_t)agent * a.batch);
+  if (x >= (uint64_t)len) x %= (uint64_t)len;
+  do {
+    uint32_t L = (uint32_t)(x >> h), R = (uint32_t)x & mask;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+      const uint32_t f = philox4x32_10(R, (agent << 8) | r, c2, a.c3_index, k0, k1).x & mask;
+      const uint32_t nr = L ^ f;
+      L = R;
+      R = nr;
+    }
+    x = ((uint64_t)L << h) | (uint64_t)R;
+  } while (x >= (uint64_t)len);
+  a.index[t] = (int64_t)x;
+}
+
 struct CursorArgs {
   int32_t* dst;
   int32_t count, index;
@@ -124,9 +187,44 @@ int sample(int64_t nb, const int64_t* len_dev, int64_t len, const int32_t* key_d
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
+int maddpg_draws(int32_t nb_agents, int64_t batch, const int64_t* len_dev, int64_t len, const int32_t* key_dev, uint64_t seed, uint64_t step,
+                 const int32_t* cursor_dev, int64_t* index, float* noise_t, float* noise_a, void* stream) {
+  if (nb_agents < 1 || batch < 0) return MDR_ERR_INVALID;
+  if (batch > 0 && (!index || !noise_t || !noise_a)) return MDR_ERR_INVALID;
+  if (!len_dev && len < 1) return MDR_ERR_INVALID;
+  if (nb_agents > MDR_MADDPG_DRAWS_MAX_AGENTS) return MDR_ERR_UNSUPPORTED;
+  if (!len_dev && len >= (1ll << 62)) return MDR_ERR_UNSUPPORTED;
+  if (!len_dev && batch > len) return MDR_ERR_INVALID;      // no batch distinct positions among len
+  if (batch == 0) return MDR_OK;
+  const int64_t per_agent = (int64_t)nb_agents * (nb_agents + 1);      // <= 426 x 427
+  if (batch > (0x7FFFFFFFll * THREADS) / per_agent) return MDR_ERR_UNSUPPORTED;
+  MaddpgDrawArgs a{};
+  a.batch = batch, a.rows = batch * nb_agents, a.draws = batch * per_agent;
+  a.index = index, a.noise_t = noise_t, a.noise_a = noise_a;
+  a.cursor_dev = cursor_dev, a.key_dev = key_dev, a.len_dev = len_dev, a.len = len_dev ? 1 : len;
+  a.k0 = (uint32_t)(seed & 0xFFFFFFFFull), a.k1 = (uint32_t)(seed >> 32);
+  a.c2 = (uint32_t)(step & 0xFFFFFFFFull);
+  a.c3_index = MDR_TAG_MADDPG_INDEX ^ (uint32_t)(step >> 32), a.c3_noise = MDR_TAG_MADDPG_NOISE ^ (uint32_t)(step >> 32);
+  a.nb_agents = nb_agents;
+  const int64_t blocks = (a.draws + THREADS - 1) / THREADS;
+  hipLaunchKernelGGL(k_maddpg_draws, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mdr_maddpg_draws(int32_t nb_agents, int64_t batch, const int64_t* len_dev, int64_t len, uint64_t seed, uint64_t step,
+                     const int32_t* cursor_dev, int64_t* index, float* noise_t, float* noise_a, void* stream) {
+  return maddpg_draws(nb_agents, batch, len_dev, len, nullptr, seed, step, cursor_dev, index, noise_t, noise_a, stream);
+}
+
+int mdr_maddpg_draws_keyed(int32_t nb_agents, int64_t batch, const int64_t* len_dev, int64_t len, const int32_t* key_dev, uint64_t step,
+                           const int32_t* cursor_dev, int64_t* index, float* noise_t, float* noise_a, void* stream) {
+  if (!key_dev) return MDR_ERR_INVALID;
+  return maddpg_draws(nb_agents, batch, len_dev, len, key_dev, 0, step, cursor_dev, index, noise_t, noise_a, stream);
+}
 
 int mdr_minibatch_permutation(int64_t n, uint64_t seed, uint64_t epoch, const int32_t* cursor_dev, int64_t* out, void* stream) {
   return permutation(n, nullptr, seed, epoch, cursor_dev, out, stream);

@@ -1,13 +1,15 @@
-"""Device-side minibatch indices and the captured update of PPOLearner, MAPPOLearner and DQNLearner (csrc/mdr_minibatch.hip,
-include/mdr_policy.h: mdr_minibatch_permutation, mdr_minibatch_sample, mdr_update_cursor_set, mdr_adam_step_table).
+"""Device-side minibatch indices and the captured update of PPOLearner, MAPPOLearner, DQNLearner and MADDPGLearner
+(csrc/mdr_minibatch.hip, include/mdr_policy.h: mdr_minibatch_permutation, mdr_minibatch_sample, mdr_maddpg_draws, mdr_update_cursor_set,
+mdr_adam_step_table).
 
 At the reference's sizes an update is host time: a PPO minibatch is six launches of 60-80 us of GPU work behind 190 us of Python,
 ctypes and launch overhead (profiles/optim_step_README.md).  Three host-side things keep an update from being replayed as a graph -
 the minibatch indices (``torch.randperm`` under a generator seeded per epoch), Adam's bias corrections (kernel arguments formed from
 the host's step count) and host counters.  Here each has a device-side counterpart:
 
-* ``permutation`` / ``sample``: the indices as a function of (seed, epoch or step, element) through Philox - ``sampler="philox"`` of
-  the learners, eager launches, usable on its own;
+* ``permutation`` / ``sample`` / ``maddpg_draws``: the indices (MADDPG: every agent's distinct positions and all gumbel noise of an
+  update, one launch) as a function of (seed, epoch or step, element) through Philox - ``sampler="philox"`` of the learners, eager
+  launches, usable on its own;
 * ``FusedAdam.step(corrections=, slot=, base_dev=)``: the bias corrections from a table in device memory;
 * a block of int32 cursors (epoch, table base, the seed as the Philox key; DQN: the buffer's fill count and the step) that one-thread
   kernels set and advance.
@@ -15,7 +17,7 @@ the host's step count) and host counters.  Here each has a device-side counterpa
 ``PPOUpdateGraph`` holds ONE epoch - the permutation, every minibatch's critic call, actor call and two table steps, the loss sums,
 the cursor advance - as one ``torch.cuda.CUDAGraph`` captured on one side stream (a chain of nodes, no fork); an update copies the batch
 into the graph's static input buffers, resets the cursors, uploads the corrections of all its steps and replays the graph
-``ppo_update_time`` times.  ``DQNUpdateGraph`` holds one update.  Nothing is allocated inside a capture, and a capture leaves no
+``ppo_update_time`` times.  ``DQNUpdateGraph`` and ``MADDPGUpdateGraph`` hold one update each, reading the replay buffer in place.  Nothing is allocated inside a capture, and a capture leaves no
 trace: kernels do not run while capturing, and the warm-up pass before it (first-use kernel attributes, the flat gradient buffers, the
 optimiser's segment table) runs on a snapshot of parameters and moments that is restored.  The graphed update launches the same
 kernels with the same arguments as the eager ``sampler="philox"`` update and gives the same bits.
@@ -132,6 +134,45 @@ def sample(nb: int, length, seed: int, step: int, device, out: Optional[torch.Te
                                           L.stream(dev))
     nat.check(lib, None, rc, "mdr_minibatch_sample")
     return res[:nb] if out is not None else res
+
+
+def maddpg_draws(nb_agents: int, batch: int, length, seed: int, step: int, device, out=None, cursor: Optional[torch.Tensor] = None,
+                 key: Optional[torch.Tensor] = None):
+    """Everything one MADDPG update draws, by (seed, step), in one launch (mdr_maddpg_draws) -> (index int64 [N, B]: B distinct
+    positions of [0, length) per agent; noise_t float32 [N, B, N, 2] and noise_a float32 [N, B, 2]: Gumbel(0, 1) noise).  ``out``:
+    the three tensors to write (contiguous, of these shapes).  ``length``: an int >= B or one device int64 read when the kernel runs;
+    ``cursor`` / ``key`` as ``permutation``'s (the cursor is added to the low word of ``step``)."""
+    dev = torch.device(device)
+    N, B = int(nb_agents), int(batch)
+    if N < 1 or B < 0:
+        raise ValueError("maddpg_draws: nb_agents >= 1 and batch >= 0")
+    shapes = ((N, B), (N, B, N, 2), (N, B, 2))
+    dtypes = (torch.int64, torch.float32, torch.float32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    if len(out) != 3 or any(t.shape != s or t.dtype != d or t.device != dev or not t.is_contiguous() for t, s, d in zip(out, shapes, dtypes)):
+        raise ValueError("maddpg_draws: out must be contiguous (int64 %s, float32 %s, float32 %s) on %s" % (shapes + (dev,)))
+    _check_int32(cursor, dev, 1, "maddpg_draws: cursor")
+    _check_int32(key, dev, 2, "maddpg_draws: key")
+    len_dev, len_host = None, 0
+    if isinstance(length, torch.Tensor):
+        if length.dtype != torch.int64 or length.device != dev or length.numel() != 1:
+            raise ValueError("maddpg_draws: a device length must be one int64 on %s" % dev)
+        len_dev = C.c_void_p(length.data_ptr())
+    else:
+        len_host = int(length)
+        if len_host < 1 or B > len_host:
+            raise ValueError("maddpg_draws: %d distinct positions asked of %d" % (B, len_host))
+    lib = nat.load()
+    cur = C.c_void_p(cursor.data_ptr()) if cursor is not None else None
+    ptrs = [C.c_void_p(t.data_ptr()) for t in out]
+    with torch.cuda.device(dev):
+        if key is not None:
+            rc = lib.mdr_maddpg_draws_keyed(N, B, len_dev, len_host, C.c_void_p(key.data_ptr()), int(step) & (2 ** 64 - 1), cur, *ptrs, L.stream(dev))
+        else:
+            rc = lib.mdr_maddpg_draws(N, B, len_dev, len_host, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), cur, *ptrs, L.stream(dev))
+    nat.check(lib, None, rc, "mdr_maddpg_draws")
+    return tuple(out)
 
 
 # -- what a captured update needs of a learner ---------------------------------------------------------------------------------------
@@ -366,6 +407,137 @@ def dqn_update(learner, seed: int) -> Optional[torch.Tensor]:
         raise ValueError("graph=True: the kernels do not take these networks")
     g = learner._graph
     if g is not None and (g.signature != _signature((learner.policy_net, learner.target_net)) or g.bs != learner.batch_size):
+        g = None
+    if g is None:
+        g = learner._capture()
+    return g.run(seed)
+
+
+class MADDPGUpdateGraph:
+    """One ``MADDPGLearner.update`` as one graph: the draws, then for every agent in order target -> critic loss and gradient ->
+    critic step -> actor loss and gradient -> actor step, the target blends where the eager update puts them (shared: on each net's
+    last step; unshared: critic a's on its one step, the N actor blends after the loop).  A chain of nodes on one stream."""
+
+    LEN, STEP, KEY = 0, 2, 4      # the cursor block: len (int64 = two words), step, -, key lo, key hi
+
+    def __init__(self, learner):
+        self.learner = learner
+        self.dev = dev = learner.buffer.device
+        self.N, self.bs, self.shared = learner.nb_agents, learner.batch_size, learner.shared
+        N, B = self.N, self.bs
+        n = self.nets = 1 if self.shared else N
+        self.block = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.index = torch.zeros((N, B), dtype=torch.int64, device=dev)
+        self.noise_t = torch.zeros((N, B, N, 2), dtype=torch.float32, device=dev)
+        self.noise_a = torch.zeros((N, B, 2), dtype=torch.float32, device=dev)
+        self.y = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.next_q = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.next_action = torch.zeros((B, N), dtype=torch.uint8, device=dev)
+        self.a_loss = torch.zeros(N, dtype=torch.float32, device=dev)      # slot a: written by agent a's gradient kernel
+        self.c_loss = torch.zeros(N, dtype=torch.float32, device=dev)
+        # shared: one table of N pairs per net (slot a = the net's a-th step of the update); unshared: one pair per optimiser (row a)
+        self.a_table = torch.ones((N, 2), dtype=torch.float32, device=dev)
+        self.c_table = torch.ones((N, 2), dtype=torch.float32, device=dev)
+        actors, critics = learner.actors[:n], learner.critics[:n]
+        tgt_actors, tgt_critics = learner.tgt_actors[:n], learner.tgt_critics[:n]
+        self.a_descs = [L.mlp_desc(L.fc_layers(m)) for m in actors]
+        self.c_descs = [L.mlp_desc(L.fc_layers(m)) for m in critics]
+        self.tc_descs = [L.mlp_desc(L.fc_layers(m)) for m in tgt_critics]
+        # one descriptor: mdr_maddpg_target; a host array of N: mdr_maddpg_target_agents
+        self.ta_desc = L.mlp_desc(L.fc_layers(tgt_actors[0])) if self.shared else L.mlp_descs([L.fc_layers(m) for m in tgt_actors])
+        sizes, self.target_launch, self.critic_launch, self.actor_launch = learner._kernels()      # the learner's own calls, on static buffers
+        a_floats, c_floats, nbytes = sizes(self.a_descs[0], self.c_descs[0], N, B)
+        self.workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # the graph's own: the shared one may be reallocated
+        self.a_flats = [_flat_grad(m, a_floats) for m in actors]
+        self.c_flats = [_flat_grad(m, c_floats) for m in critics]
+        held = [p for m in actors + critics + tgt_actors + tgt_critics for p in m.parameters()]
+        for opt in learner.actor_optimizers[:n] + learner.critic_optimizers[:n]:
+            held += [opt._exp_avg, opt._exp_avg_sq]
+        cursor_set(self.block, [max(len(learner.buffer), 1), 0, 0, 0])      # the warm-up pass reads rows the buffer holds (row 0 of an empty one)
+        self.graph = _capture(self._record, held, dev)
+        self.signature = _signature(maddpg_nets(learner))
+
+    def _record(self) -> None:
+        learner, dev, buf = self.learner, self.dev, self.learner.buffer
+        N, B = self.N, self.bs
+        st = L.stream(dev)
+        ld = N * buf.num_state      # the buffer's env-steps are contiguous
+        norm, tau = learner.MAX_GRAD_NORM, learner.soft_tau
+        with torch.cuda.device(dev):
+            maddpg_draws(N, B, self.block[self.LEN:self.LEN + 2].view(torch.int64), 0, 0, dev, out=(self.index, self.noise_t, self.noise_a),
+                         cursor=self.block[self.STEP:], key=self.block[self.KEY:])
+            for a in range(N):
+                k = 0 if self.shared else a
+                critic, actor = learner.critics[a], learner.actors[a]
+                c_opt, a_opt = learner.critic_optimizers[a], learner.actor_optimizers[a]
+                # shared: slot a of the net's table, the blend on its last step; unshared: the optimiser's one pair, critic a's blend
+                # on its one step, no actor blend here (every later agent reads tgt_actors[a] as the previous update left it)
+                c_table, a_table, slot = (self.c_table, self.a_table, a) if self.shared else (self.c_table[a], self.a_table[a], 0)
+                c_blend = a == N - 1 if self.shared else True
+                a_blend = a == N - 1 if self.shared else False
+                self.target_launch(self.ta_desc, self.tc_descs[k], buf.next_state, ld, buf.reward, self.index[a], B, N, a, self.noise_t[a], self.y,
+                                   self.next_q, self.next_action, st)
+                self.critic_launch(self.c_descs[k], buf.state, ld, buf.action, self.index[a], B, N, self.y, self.workspace, self.c_flats[k],
+                                   self.c_loss[a:a + 1], None, st)
+                if c_blend:
+                    L.clip_and_step(c_opt, critic.parameters(), norm, target=L.mlp_params(L.fc_layers(learner.tgt_critics[a])), tau=tau,
+                                    corrections=c_table, slot=slot)
+                else:
+                    L.clip_and_step(c_opt, critic.parameters(), norm, corrections=c_table, slot=slot)
+                self.actor_launch(self.a_descs[k], self.c_descs[k], buf.state, ld, buf.action, self.index[a], B, N, a, self.noise_a[a], self.workspace,
+                                  self.a_flats[k], self.a_loss[a:a + 1], None, None, st)
+                if a_blend:
+                    L.clip_and_step(a_opt, actor.parameters(), norm, target=L.mlp_params(L.fc_layers(learner.tgt_actors[a])), tau=tau,
+                                    corrections=a_table, slot=slot)
+                else:
+                    L.clip_and_step(a_opt, actor.parameters(), norm, corrections=a_table, slot=slot)
+            if not self.shared:
+                for a in range(N):
+                    L.blend(L.mlp_params(L.fc_layers(learner.tgt_actors[a])), L.mlp_params(L.fc_layers(learner.actors[a])), tau)
+
+    def _corrections(self, optimizers) -> torch.Tensor:
+        """The pairs of this update's steps, [N, 2] on the host: the N next steps of the one shared optimiser, or the next step of
+        each of the N.  A fresh pinned tensor, as ``correction_table``'s."""
+        if self.shared:
+            return optimizers[0].correction_table(self.N).view(self.N, 2)
+        host = torch.empty((self.N, 2), dtype=torch.float32, pin_memory=True)
+        for a, opt in enumerate(optimizers):
+            host[a].copy_(opt.correction_table(1))
+        return host
+
+    @torch.no_grad()
+    def run(self, seed: int):
+        learner = self.learner
+        seed = int(seed) & (2 ** 64 - 1)
+        fill = len(learner.buffer)
+        cursor_set(self.block, [fill & 0xFFFFFFFF, fill >> 32, learner.training_step, 0])
+        cursor_set(self.block, [seed & 0xFFFFFFFF, seed >> 32], offset=self.KEY)
+        self.a_table.copy_(self._corrections(learner.actor_optimizers), non_blocking=True)
+        self.c_table.copy_(self._corrections(learner.critic_optimizers), non_blocking=True)
+        self.graph.replay()
+        steps = self.N if self.shared else 1
+        for opt in learner.actor_optimizers[:self.nets] + learner.critic_optimizers[:self.nets]:
+            opt.advance(steps)
+        learner.training_step += 1
+        return self.a_loss.clone(), self.c_loss.clone()
+
+
+def maddpg_nets(learner) -> list:
+    """Every net an update of ``learner`` reads or writes (shared: one of each kind)."""
+    n = 1 if learner.shared else learner.nb_agents
+    return learner.actors[:n] + learner.critics[:n] + learner.tgt_actors[:n] + learner.tgt_critics[:n]
+
+
+def maddpg_update(learner, seed: int):
+    """``MADDPGLearner.update`` with ``graph=True``."""
+    if learner.before_step is not None:
+        raise ValueError("graph=True: a before_step hook is host code between the launches; unset it or construct with graph=False")
+    if len(learner.buffer) < learner.batch_size:
+        return None
+    if not learner.uses_kernels(learner.batch_size):
+        raise ValueError("graph=True: the kernels do not take these networks")
+    g = learner._graph
+    if g is not None and (g.signature != _signature(maddpg_nets(learner)) or g.bs != learner.batch_size):
         g = None
     if g is None:
         g = learner._capture()

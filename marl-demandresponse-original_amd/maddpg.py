@@ -9,8 +9,9 @@ N (F + 2) inputs - 1060 at the reference's 20 agents - through 256 hidden units:
 them from L2 (csrc/mdr_maddpg_grad.hip) and leave the other learners' kernels as they are.  ``maddpg_target``,
 ``joint_q_loss_backward`` and ``actor_loss_backward`` are two launches each; ``JointReplayBuffer`` holds env-steps as preallocated
 device tensors the kernels read in place through the sampled indices; ``MADDPGLearner`` is the update, ``train_maddpg`` the loop.
-The gumbel noise is an input of every call, drawn by the learner under a seeded generator: every backend sees the same noise.  Nothing
-on the call path synchronises with the host.
+The gumbel noise is an input of every call, drawn by the learner - under a seeded generator or, with ``sampler="philox"``, by one launch
+of mdr_maddpg_draws together with the minibatches: every backend sees the same noise.  ``graph=True`` replays a whole update from one
+captured graph (graph_update.MADDPGUpdateGraph).  Nothing on the call path synchronises with the host.
 
 Places that leave the reference's text on purpose:
 
@@ -29,6 +30,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+from functools import partial
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -37,6 +39,7 @@ import torch.nn.functional as F
 
 from . import _learner as L
 from . import _native as nat
+from . import graph_update
 from .optim import FusedAdam
 
 MAX_STATE, MAX_HIDDEN, MAX_JOINT = 64, 256, 1280      # the kernels' limits (include/mdr_policy.h: mdr_maddpg_*)
@@ -142,6 +145,46 @@ def _agents_refusal(actors, critic, nb_agents: int) -> Optional[str]:
     return None
 
 
+# -- the launches, on caller-owned buffers: what the functional wrappers below call and what a captured update records -----------------
+def _sizes(adesc, cdesc, N: int, B: int, max_workgroups: int = 0) -> Tuple[int, int, int]:
+    """(floats of the actor's flat gradient, of the critic's, bytes of workspace of either gradient call over B rows)."""
+    lib = nat.load()
+    return (int(lib.mdr_maddpg_grad_floats(C.byref(adesc))), int(lib.mdr_maddpg_grad_floats(C.byref(cdesc))),
+            int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
+
+
+def _target_launch(tgt_actors, cdesc, next_state, ld, reward, index, B, N, agent, noise, y, next_q, next_action, st, tau, gamma,
+                   max_workgroups: int = 0) -> None:
+    """mdr_maddpg_target (``tgt_actors``: one ``mdr_mlp_t``) or mdr_maddpg_target_agents (a host array of N) on stream ``st``."""
+    lib = nat.load()
+    if isinstance(tgt_actors, nat.MdrMlp):
+        name = "mdr_maddpg_target"
+        rc = lib.mdr_maddpg_target(C.byref(tgt_actors), C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
+                                   L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q), L.ptr(next_action), st)
+    else:
+        name = "mdr_maddpg_target_agents"
+        rc = lib.mdr_maddpg_target_agents(tgt_actors, N, C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
+                                          L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q),
+                                          L.ptr(next_action), st)
+    nat.check(lib, None, rc, name)
+
+
+def _critic_launch(cdesc, state, ld, action, index, B, N, y, workspace, flat, loss, q, st, max_workgroups: int = 0) -> None:
+    lib = nat.load()
+    rc = lib.mdr_maddpg_critic_grad(C.byref(cdesc), L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, L.ptr(y), max_workgroups, L.ptr(workspace),
+                                    L.ptr(flat), L.ptr(loss), L.ptr(q), st)
+    nat.check(lib, None, rc, "mdr_maddpg_critic_grad")
+
+
+def _actor_launch(adesc, cdesc, state, ld, action, index, B, N, agent, noise, workspace, flat, loss, q, logits, st, tau, pse,
+                  max_workgroups: int = 0) -> None:
+    lib = nat.load()
+    rc = lib.mdr_maddpg_actor_grad(C.byref(adesc), C.byref(cdesc), L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, int(agent), L.ptr(noise),
+                                   C.c_float(tau), C.c_float(pse), max_workgroups, L.ptr(workspace), L.ptr(flat), L.ptr(loss), L.ptr(q),
+                                   L.ptr(logits), st)
+    nat.check(lib, None, rc, "mdr_maddpg_actor_grad")
+
+
 def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch.Tensor, agent: int, noise: torch.Tensor,
                   tau: float = 1.0, gamma: float = 0.99, index: Optional[torch.Tensor] = None, max_workgroups: int = 0
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -162,22 +205,14 @@ def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch
     dev, M, ld, B = _check_steps(tgt_actor, next_state, index, N, what)
     L.whole(reward, torch.float32, M * N, dev, what, "reward")
     L.whole(noise, torch.float32, B * N * 2, dev, what, "noise")
-    lib = nat.load()
-    adesc, cdesc = L.mlp_desc(L.fc_layers(tgt_actor)), L.mlp_desc(L.fc_layers(tgt_critic))
+    cdesc = L.mlp_desc(L.fc_layers(tgt_critic))
+    adescs = L.mlp_descs([L.fc_layers(m) for m in tgt_actors]) if per_agent else L.mlp_desc(L.fc_layers(tgt_actor))
     y = torch.empty(B, dtype=torch.float32, device=dev)
     next_q = torch.empty(B, dtype=torch.float32, device=dev)
     next_action = torch.empty((B, N), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        if per_agent:
-            descs = L.mlp_descs([L.fc_layers(m) for m in tgt_actors])
-            rc = lib.mdr_maddpg_target_agents(descs, N, C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
-                                              L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q),
-                                              L.ptr(next_action), L.stream(dev))
-        else:
-            rc = lib.mdr_maddpg_target(C.byref(adesc), C.byref(cdesc), L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, int(agent),
-                                       L.ptr(noise), C.c_float(tau), C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q),
-                                       L.ptr(next_action), L.stream(dev))
-    nat.check(lib, None, rc, "mdr_maddpg_target_agents" if per_agent else "mdr_maddpg_target")
+        _target_launch(adescs, cdesc, next_state, ld, reward, index, B, N, agent, noise, y, next_q, next_action, L.stream(dev), tau, gamma,
+                       max_workgroups)
     return y, next_q, next_action
 
 
@@ -195,16 +230,14 @@ def joint_q_loss_backward(actor, critic, state: torch.Tensor, action: torch.Tens
     dev, M, ld, B = _check_steps(actor, state, index, N, what)
     L.whole(action, torch.int64, M * N, dev, what, "action")
     L.whole(y, torch.float32, B, dev, what, "y")
-    lib = nat.load()
     adesc, cdesc = L.mlp_desc(L.fc_layers(actor)), L.mlp_desc(L.fc_layers(critic))
-    flat = L.flat_grad(critic, lib.mdr_maddpg_grad_floats(C.byref(cdesc)), dev)
-    ws = L.workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
+    _, c_floats, nbytes = _sizes(adesc, cdesc, N, B, max_workgroups)
+    flat = L.flat_grad(critic, c_floats, dev)
+    ws = L.workspace(dev, nbytes)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_maddpg_critic_grad(C.byref(cdesc), L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, L.ptr(y), max_workgroups, L.ptr(ws),
-                                        L.ptr(flat), L.ptr(loss), L.ptr(q), L.stream(dev))
-    nat.check(lib, None, rc, "mdr_maddpg_critic_grad")
+        _critic_launch(cdesc, state, ld, action, index, B, N, y, ws, flat, loss, q, L.stream(dev), max_workgroups)
     L.publish(L.mlp_params(L.fc_layers(critic)), flat, L.KEEP)
     return (loss, q) if want_q else loss
 
@@ -222,18 +255,15 @@ def actor_loss_backward(actor, critic, state: torch.Tensor, action: torch.Tensor
     dev, M, ld, B = _check_steps(actor, state, index, N, what)
     L.whole(action, torch.int64, M * N, dev, what, "action")
     L.whole(noise, torch.float32, B * 2, dev, what, "noise")
-    lib = nat.load()
     adesc, cdesc = L.mlp_desc(L.fc_layers(actor)), L.mlp_desc(L.fc_layers(critic))
-    flat = L.flat_grad(actor, lib.mdr_maddpg_grad_floats(C.byref(adesc)), dev)
-    ws = L.workspace(dev, int(lib.mdr_maddpg_workspace_bytes(C.byref(adesc), C.byref(cdesc), N, B, max_workgroups)))
+    a_floats, _, nbytes = _sizes(adesc, cdesc, N, B, max_workgroups)
+    flat = L.flat_grad(actor, a_floats, dev)
+    ws = L.workspace(dev, nbytes)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     q = torch.empty(B, dtype=torch.float32, device=dev) if want_q else None
     logits = torch.empty((B, 2), dtype=torch.float32, device=dev) if want_q else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_maddpg_actor_grad(C.byref(adesc), C.byref(cdesc), L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, int(agent),
-                                       L.ptr(noise), C.c_float(tau), C.c_float(pse), max_workgroups, L.ptr(ws), L.ptr(flat), L.ptr(loss),
-                                       L.ptr(q), L.ptr(logits), L.stream(dev))
-    nat.check(lib, None, rc, "mdr_maddpg_actor_grad")
+        _actor_launch(adesc, cdesc, state, ld, action, index, B, N, agent, noise, ws, flat, loss, q, logits, L.stream(dev), tau, pse, max_workgroups)
     L.publish(L.mlp_params(L.fc_layers(actor)), flat, L.KEEP)
     return (loss, q, logits) if want_q else loss
 
@@ -280,14 +310,21 @@ class MADDPGLearner:
     in an ``update()`` carries the target blend (``target=..., tau=soft_tau``).  Unshared nets take ONE step each per ``update()``:
     critic a's blend rides on critic a's step (nobody reads ``tgt_critics[a]`` afterwards), the actors' blends never ride - every
     later agent of the same update reads ``tgt_actors[a]`` as the previous update left it - and follow the loop.  ``"auto"`` resolves
-    to torch for unshared nets (``AUTO_UNSHARED`` above)."""
+    to torch for unshared nets (``AUTO_UNSHARED`` above).
+
+    ``sampler="philox"``: ``draws()`` is one launch of mdr_maddpg_draws keyed by (seed, training_step) instead of N ``randperm`` and
+    one ``exponential_`` under a ``torch.Generator`` (``"torch"``, the default) - other draws of the same laws, on every backend.
+    ``graph=True`` (implies ``sampler="philox"``; needs ``optimizer=FusedAdam`` and networks the kernels take): every ``update()`` is
+    replayed from one captured graph (graph_update.MADDPGUpdateGraph) and gives the bits of the eager ``sampler="philox"`` update;
+    ``graph_captures`` counts the captures."""
 
     MAX_GRAD_NORM = 0.5      # ddpg.py:157, 163
 
     def __init__(self, actor, critic, nb_agents: int, lr_actor: float, lr_critic: float, gamma: float = 0.99, soft_tau: float = 0.01,
                  gumbel_tau: float = 1.0, batch_size: int = 64, buffer_capacity: int = 524288, backend: str = "auto",
-                 optimizer=torch.optim.Adam, shared: bool = True):
+                 optimizer=torch.optim.Adam, shared: bool = True, sampler: Optional[str] = None, graph: bool = False):
         L.check_backend(backend)
+        self.sampler, self.graph = L.check_sampler(sampler, graph), bool(graph)
         self.shared, self.nb_agents = bool(shared), int(nb_agents)
         N = self.nb_agents
         if self.shared:
@@ -338,15 +375,22 @@ class MADDPGLearner:
         # optional callable(learner, "critic" | "actor", agent): after a backward, before its clip and step - the gradient to look at
         # is critics[agent]'s or actors[agent]'s
         self.before_step = None
+        self.graph_captures = 0
+        self._graph = None
+        if self.graph:
+            why = graph_update.refusal(backend, self.sampler, actor_optimizers + critic_optimizers, self.uses_kernels(max(self.batch_size, 1)))
+            if why:
+                raise ValueError("MADDPGLearner(graph=True): " + why)
 
     @classmethod
-    def from_config(cls, ddpg_prop: dict, actor, critic, nb_agents: int, backend: str = "auto", optimizer=torch.optim.Adam) -> "MADDPGLearner":
+    def from_config(cls, ddpg_prop: dict, actor, critic, nb_agents: int, backend: str = "auto", optimizer=torch.optim.Adam,
+                    sampler: Optional[str] = None, graph: bool = False) -> "MADDPGLearner":
         """From the reference's ``config_dict["DDPG_prop"]`` (agents/ddpg.py:60-70).  ``DDPG_shared`` (ddpg.py:214-215; absent: shared)
         false: ``actor`` and ``critic`` are the caller's lists of ``nb_agents`` modules."""
         return cls(actor, critic, nb_agents, ddpg_prop["lr_actor"], ddpg_prop["lr_critic"], gamma=ddpg_prop["gamma"],
                    soft_tau=ddpg_prop["soft_tau"], gumbel_tau=ddpg_prop["gumbel_softmax_tau"], batch_size=ddpg_prop["batch_size"],
                    buffer_capacity=ddpg_prop["buffer_capacity"], backend=backend, optimizer=optimizer,
-                   shared=bool(ddpg_prop.get("DDPG_shared", True)))
+                   shared=bool(ddpg_prop.get("DDPG_shared", True)), sampler=sampler, graph=graph)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
@@ -389,6 +433,8 @@ class MADDPGLearner:
         ``-log(Exp(1))`` (what ``F.gumbel_softmax`` draws) float32 [N, B, N + 1, 2]: [a, :, :N] for the target actor's picks of agent
         a's update, [a, :, N] for the actor's own sample."""
         dev, N, B = self.buffer.device, self.nb_agents, self.batch_size
+        if self.sampler == "philox":      # one launch by (seed, training_step): graph_update.maddpg_draws
+            return graph_update.maddpg_draws(N, B, len(self.buffer), seed, self.training_step, dev)
         gen = L.seeded_generator(seed, self.training_step, dev)
         index = torch.stack([self.buffer.sample(B, gen) for _ in range(N)])
         noise = -torch.empty((N, B, N + 1, 2), dtype=torch.float32, device=dev).exponential_(generator=gen).log()
@@ -401,6 +447,18 @@ class MADDPGLearner:
         index = y_soft.max(-1, keepdim=True)[1]
         y_hard = torch.zeros_like(logits).scatter_(-1, index, 1.0)
         return y_hard - y_soft.detach() + y_soft
+
+    def _kernels(self):
+        """(sizes, target launch, critic launch, actor launch) of the calls ``critic_backward`` and ``actor_backward`` make, this
+        learner's fixed arguments bound: what a captured graph runs on its static buffers (graph_update.MADDPGUpdateGraph)."""
+        return (_sizes, partial(_target_launch, tau=self.gumbel_tau, gamma=self.gamma), _critic_launch,
+                partial(_actor_launch, tau=self.gumbel_tau, pse=PSE))
+
+    def _capture(self):
+        """Capture the graph of one update without replaying it; every net, the moments and every counter are what they were."""
+        self._graph = graph_update.MADDPGUpdateGraph(self)
+        self.graph_captures += 1
+        return self._graph
 
     def update_target(self) -> None:
         """ddpg.py:167-174: to = soft_tau * from + (1 - soft_tau) * to over both pairs of nets."""
@@ -472,6 +530,8 @@ class MADDPGLearner:
         in order a fresh minibatch, the critic's step, the actor's step; then one blend of both target nets.  -> (actor_loss [N],
         critic_loss [N]) as device tensors (the actor's loss includes the 1e-3 logits term), or None while the buffer holds fewer
         than ``batch_size`` env-steps."""
+        if self.graph:
+            return graph_update.maddpg_update(self, seed)
         if len(self.buffer) < self.batch_size:
             return None
         N = self.nb_agents

@@ -11,6 +11,15 @@ Three measurements per size and optimiser (torch.optim.Adam, mdr_amd.optim.Fused
   "actor step"    one agent's ``actor_backward`` (sample, critic forward and backward to two input columns, the actor's backward) + clip + Adam
   "update"        a whole ``MADDPGLearner.update``: the N agents in order, then the target blend
 The reference's shape: N = 20 agents, F = 51, hidden 256-256, J = 1060 joint inputs; the buffer holds 8192 env-steps.
+
+    python tools/bench_maddpg_update.py --graph-leg [--rows 64,256] [--repeats 7] [--iters 50] [--out FILE]
+
+The graph leg: a whole update with ``backend="hip"`` and ``FusedAdam`` in three forms - "torch" (``sampler="torch"``: N ``randperm`` and one
+``exponential_`` on the host side of every update, the code before the device-side draws), "philox" (``sampler="philox"``: one
+mdr_maddpg_draws launch, the rest eager) and "graph" (``graph=True``: the update replayed from one captured graph) - with shared and with
+per-agent networks.  Windows of ``--iters`` updates, the three forms alternating, ``--repeats`` windows each (7 x 50 = 350 updates per
+form); per update the median window, the fastest and the slowest.  After the last window "philox" and "graph" have made the same
+updates from the same nets: ``graph_bits_equal_philox`` says whether every parameter is bit-equal.
 Per-kernel times come from `rocprofv3 --kernel-trace --stats -- python tools/bench_maddpg_update.py --only hip` in a run of its own.
 """
 import argparse
@@ -47,6 +56,41 @@ def learner_for(backend, B, optimizer, steps):
     return lrn
 
 
+def graph_leg(args, steps, emit):
+    forms = (("torch", dict(sampler="torch")), ("philox", dict(sampler="philox")), ("graph", dict(graph=True)))
+    for B in (int(x) for x in args.rows.split(",")):
+        for shared in (True, False):
+            lrn = {}
+            for name, kw in forms:
+                torch.manual_seed(0)
+                n = 1 if shared else N
+                actors = [maddpg.DDPGNetworkMLP(F_OBS, 2, HIDDEN).to(DEV) for _ in range(n)]
+                critics = [maddpg.DDPGNetworkMLP(N * (F_OBS + 2), 1, HIDDEN).to(DEV) for _ in range(n)]
+                lrn[name] = maddpg.MADDPGLearner(actors[0] if shared else actors, critics[0] if shared else critics, N, 1e-3, 3e-3, batch_size=B,
+                                                 buffer_capacity=CAPACITY, backend="hip", optimizer=FusedAdam, shared=shared, **kw)
+                lrn[name].buffer.push(*steps)
+            t = {name: [] for name in lrn}
+            for _ in range(args.warmup):
+                for l in lrn.values():
+                    l.update(seed=1)
+            torch.cuda.synchronize()
+            for _ in range(args.repeats):      # alternating windows
+                for name, l in lrn.items():
+                    t[name].append(window(lambda: l.update(seed=1), args.iters))
+            equal = all(torch.equal(p, q) for a, b in zip(lrn["philox"].actors + lrn["philox"].critics, lrn["graph"].actors + lrn["graph"].critics)
+                        for p, q in zip(a.parameters(), b.parameters()))
+            rec = dict(what="update, three forms", rows=B, agents=N, shared=shared, iters_per_window=args.iters, repeats=args.repeats,
+                       updates_per_form=args.iters * args.repeats, graph_bits_equal_philox=equal, graph_captures=lrn["graph"].graph_captures)
+            for name, v in t.items():
+                rec[name + "_us_median"] = round(statistics.median(v), 1)
+                rec[name + "_us_min"], rec[name + "_us_max"] = round(min(v), 1), round(max(v), 1)
+            for name in ("philox", "graph"):
+                rec["torch_over_" + name] = round(statistics.median(t["torch"]) / statistics.median(t[name]), 3)
+            emit(**rec)
+            del lrn
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="64,256,4096")
@@ -54,6 +98,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", choices=("hip", "torch"), default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--graph-leg", action="store_true", help="the three forms of the update (module docstring) instead of the backends' table")
+    ap.add_argument("--iters", type=int, default=50, help="updates per window of the graph leg")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_maddpg_update.py needs a GPU"
     lines = []
@@ -66,7 +112,11 @@ def main():
     steps = (torch.rand((CAPACITY, N, F_OBS), device=DEV, generator=gen) * 2 - 1, torch.randint(0, 2, (CAPACITY, N), device=DEV, generator=gen),
              torch.randn((CAPACITY, N), device=DEV, generator=gen), torch.rand((CAPACITY, N, F_OBS), device=DEV, generator=gen) * 2 - 1)
     backends = [b for b in ("hip", "torch") if args.only in (None, b)]
-    for B in (int(x) for x in args.rows.split(",")):
+    rows = [int(x) for x in args.rows.split(",")]
+    if args.graph_leg:
+        graph_leg(args, steps, emit)
+        rows = []
+    for B in rows:
         for opt_name, opt in (("Adam", torch.optim.Adam), ("FusedAdam", FusedAdam)):
             lrn = {b: learner_for(b, B, opt, steps) for b in backends}
             index, noise_t, noise_a = next(iter(lrn.values())).draws(0)
