@@ -571,6 +571,21 @@ int mdr_mlp_actor_sample(const mdr_mlp_t *actor, const float *obs, int64_t ld_ob
                          const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob, float *probs,
                          void *stream);
 
+/* mdr_mlp_actor_sample in bf16x3 (csrc/mdr_mlp_actor_bf16.hip): the same call - parameters, limits, outputs, draw, `step_dev`,
+ * `greedy`, grid and return codes word for word - with the two hidden layers on v_mfma_f32_16x16x32_bf16.  Every weight and every
+ * input of a hidden layer (the observation floats, relu(h1)) is split into a bf16 head and tail, xh = bf16(x), xl = bf16(x - xh),
+ * round to nearest even, and every product is wh xh + wl xh + wh xl (the tail x tail product is dropped), accumulated in fp32
+ * starting from the fp32 bias.  The weights are read in place and split on every call - nothing is packed or cached - and every
+ * activation is split once.  The head (one fp32 dot product with W3[0] - W3[1] in per-wave partials added in wave order), the softmax
+ * and the draw are mdr_mlp_actor_sample's, so for equal probabilities both calls pick the same action.  No floating-point atomics: an
+ * agent's `probs` bits depend on its row and the weights only - not on its position in the batch, on nb_agents, ld_obs or the grid.
+ * Contract: each probability within 2e-3 |p| + 2e-5 of an fp64 forward of the same weights (mean absolute error below 5e-6 on the
+ * tested inputs); the split keeps 2^-16 of every product on top of the fp32 accumulation.  It is NOT the bits of mdr_mlp_actor_sample.
+ * On -1 and -4 nothing was launched and nothing written.  nb_agents == 0 returns 0 and launches nothing. */
+int mdr_mlp_actor_sample_bf16x3(const mdr_mlp_t *actor, const float *obs, int64_t ld_obs, int64_t nb_agents, uint64_t seed, uint64_t step,
+                                const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob,
+                                float *probs, void *stream);
+
 /* ---- MADDPG with one network per agent (ddpg.py:200-213: every agent its own actor, critic and target of each; what every
  * checkpoint of saveDDPGDict holds).  At most MDR_MAX_AGENT_NETS nets per call: their weight pointers travel in the kernel argument
  * block (32 x 6 pointers = 1.5 KB), so no device table is owned by anybody and a captured call stays valid while the parameter

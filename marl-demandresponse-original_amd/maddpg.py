@@ -578,22 +578,25 @@ class GreedyDDPGActor:
     """``DDPGAgent.act`` (agents/rl_controllers.py): the argmax of the actor's logits, in the shape ``deploy_policy`` takes through
     its duck-typed branch - ``.sample(rows, seed, step, action=None, step_dev=None)`` -> uint8 actions.  ``backend="torch"`` (default):
     a torch forward and a compare; ``"hip"``: the greedy form of ``FusedMLPActor`` - forward and argmax in one kernel (ValueError for a
-    net it does not take); it honours ``step_dev``, which a greedy pick does not read.  ``actor``: one module, or a sequence of N
-    (unshared networks): row e N + k is agent k's and goes through ``actor[k]`` - N torch forwards, or ``FusedMLPActors``."""
+    net it does not take); it honours ``step_dev``, which a greedy pick does not read.  ``"hip-bf16x3"``: that form with
+    ``precision="bf16x3"`` (one shared net only).  ``actor``: one module, or a sequence of N (unshared networks): row e N + k is
+    agent k's and goes through ``actor[k]`` - N torch forwards, or ``FusedMLPActors`` (fp32 only: ValueError with "hip-bf16x3")."""
 
     def __init__(self, actor, backend: str = "torch"):
-        if backend not in ("torch", "hip"):
-            raise ValueError("backend must be 'torch' or 'hip'")
+        if backend not in ("torch", "hip", "hip-bf16x3"):
+            raise ValueError("backend must be 'torch', 'hip' or 'hip-bf16x3'")
         self.actor, self.backend = (list(actor) if _is_seq(actor) else actor), backend
         self.per_agent = _is_seq(actor)
         self._fused = self._a_prob = None
-        if backend == "hip":
+        if backend != "torch":
             from .mlp_actor import FusedMLPActor, FusedMLPActors
+            if self.per_agent and backend == "hip-bf16x3":
+                raise ValueError("GreedyDDPGActor(backend='hip-bf16x3'): one net per agent acts in fp32 only (FusedMLPActors)")
             kind = FusedMLPActors if self.per_agent else FusedMLPActor
             why = kind.refusal(self.actor)
             if why:
-                raise ValueError("GreedyDDPGActor(backend='hip'): " + why)
-            self._fused = kind(self.actor, greedy=True)
+                raise ValueError("GreedyDDPGActor(backend=%r): %s" % (backend, why))
+            self._fused = kind(self.actor, greedy=True) if backend == "hip" else kind(self.actor, greedy=True, precision="bf16x3")
 
     @torch.no_grad()
     def sample(self, rows: torch.Tensor, seed: int = 0, step: int = 0, action: Optional[torch.Tensor] = None, step_dev=None) -> torch.Tensor:
@@ -620,7 +623,7 @@ def train_maddpg(env, learner: MADDPGLearner, nb_steps: int, update_every: int =
     step of all envs (uniformly random actions while the 1-based step is below ``random_steps``, the actor's gumbel sample after), ``store``, and
     after every ``update_every``-th step from ``random_steps`` on one ``update()`` (which ends with the target blend).
     ``actor_backend`` is ``collect_maddpg_transitions``': "hip" acts through ``FusedMLPActor``, which reads the actor's weights in
-    place and so sees every update.  -> (actor losses [n, N], critic losses [n, N]) of the updates that ran, on the device."""
+    place and so sees every update; "hip-bf16x3" is its bf16x3 precision (a shared actor only).  -> (actor losses [n, N], critic losses [n, N]) of the updates that ran, on the device."""
     from .rollout import collect_maddpg_transitions
     a_losses, c_losses = [], []
     for t in range(int(nb_steps)):

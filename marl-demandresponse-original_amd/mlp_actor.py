@@ -19,18 +19,24 @@ from . import _learner as L
 from . import _native as nat
 
 MAX_STATE, MAX_HIDDEN = 128, 256      # the kernel's limits (include/mdr_policy.h: mdr_mlp_actor_sample)
+PRECISIONS = {"fp32": "mdr_mlp_actor_sample", "bf16x3": "mdr_mlp_actor_sample_bf16x3"}      # precision -> entry point
 
 
 class FusedMLPActor:
     """``module``: anything ``_learner.fc_layers`` resolves (``DDPGNetworkMLP``, ``ActorMLP``, the reference's nets) with at most 128
     input features, at most 256 units in each hidden layer (any size) and 2 outputs, float32 on the GPU.  The module is held, not
-    copied.  ``greedy=True``: the argmax (the first maximum on ties) instead of a draw - ``DDPGAgent.act``."""
+    copied.  ``greedy=True``: the argmax (the first maximum on ties) instead of a draw - ``DDPGAgent.act``.  ``precision``: "fp32"
+    (default) - exact fp32 products; "bf16x3" - both hidden layers on the bf16 matrix cores with every operand split into a bf16 head
+    and tail (``mdr_mlp_actor_sample_bf16x3``, csrc/mdr_mlp_actor_bf16.hip): probabilities within 2e-3 |p| + 2e-5 of fp64, the same
+    nets, arguments and draw.  Measured: profiles/mlp_actor_bf16_README.md."""
 
-    def __init__(self, module, greedy: bool = False):
+    def __init__(self, module, greedy: bool = False, precision: str = "fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError("FusedMLPActor: precision must be 'fp32' or 'bf16x3', not %r" % (precision,))
         why = self.refusal(module)
         if why:
             raise ValueError("FusedMLPActor: " + why)
-        self.module, self.greedy = module, bool(greedy)
+        self.module, self.greedy, self.precision = module, bool(greedy), precision
         self._lib = nat.load()
 
     @staticmethod
@@ -84,12 +90,13 @@ class FusedMLPActor:
         a_prob = torch.empty(A, dtype=torch.float32, device=dev) if a_prob is None else L.whole(a_prob, torch.float32, A, dev, "FusedMLPActor.sample", "a_prob")
         probs = torch.empty((A, 2), dtype=torch.float32, device=dev) if want_probs else None
         desc = L.mlp_desc(fc)
+        entry = PRECISIONS[self.precision]
         with torch.cuda.device(dev):
-            rc = self._lib.mdr_mlp_actor_sample(C.byref(desc), L.ptr(rows), ld, A, C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                                C.c_uint64(int(step) & (2 ** 64 - 1)), L.ptr(step_dev),
-                                                int(self.greedy if greedy is None else bool(greedy)), int(max_workgroups), L.ptr(action),
-                                                L.ptr(a_prob), L.ptr(probs), L.stream(dev))
-        nat.check(self._lib, None, rc, "mdr_mlp_actor_sample")
+            rc = getattr(self._lib, entry)(C.byref(desc), L.ptr(rows), ld, A, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                           C.c_uint64(int(step) & (2 ** 64 - 1)), L.ptr(step_dev),
+                                           int(self.greedy if greedy is None else bool(greedy)), int(max_workgroups), L.ptr(action),
+                                           L.ptr(a_prob), L.ptr(probs), L.stream(dev))
+        nat.check(self._lib, None, rc, entry)
         return (action, a_prob, probs) if want_probs else (action, a_prob)
 
 

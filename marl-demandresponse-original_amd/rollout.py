@@ -458,7 +458,9 @@ def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int
     agree with torch's to fp32 rounding), ValueError for a net the kernel does not take.  It measured faster than "torch" at every
     size tried (profiles/mlp_actor_README.md; F = 51, hidden 256-256): 1.9-2.0x at 1 x 20 and 64 x 50 agents (both paths bound by the host
     there), 1.36x at 4096 x 20, 1.57x at 4096 x 1024; 1.40x at F = 121 and 4096 x 1024.  Other sizes: not measured.
-    The random steps are the same under both.
+    "hip-bf16x3": "hip" with ``FusedMLPActor(precision="bf16x3")`` - the hidden layers on the bf16 matrix cores, probabilities within
+    the bf16x3 contract of fp64, the same draw; one shared net only (ValueError with a list).  Measured:
+    profiles/mlp_actor_bf16_README.md.  The random steps are the same under all.
 
     ``actor``: one module for all agents, or a sequence of N modules - agent k acts through ``actor[k]`` (MADDPG with unshared
     networks, ddpg.py:200-213).  "torch": N forwards on ``state[t][:, k]``, the logits gathered to [E N, 2], then the one
@@ -466,17 +468,19 @@ def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int
     import ctypes as C
 
     from . import _native as nat
-    if actor_backend not in ("torch", "hip"):
-        raise ValueError("actor_backend must be 'torch' or 'hip'")
+    if actor_backend not in ("torch", "hip", "hip-bf16x3"):
+        raise ValueError("actor_backend must be 'torch', 'hip' or 'hip-bf16x3'")
     per_agent = isinstance(actor, (list, tuple))
     fused = None
-    if actor_backend == "hip":
+    if actor_backend != "torch":
         from .mlp_actor import FusedMLPActor, FusedMLPActors
+        if per_agent and actor_backend == "hip-bf16x3":
+            raise ValueError("collect_maddpg_transitions(actor_backend='hip-bf16x3'): one net per agent acts in fp32 only (FusedMLPActors)")
         kind = FusedMLPActors if per_agent else FusedMLPActor
         why = kind.refusal(actor)
         if why:
-            raise ValueError("collect_maddpg_transitions(actor_backend='hip'): " + why)
-        fused = kind(actor)
+            raise ValueError("collect_maddpg_transitions(actor_backend=%r): %s" % (actor_backend, why))
+        fused = kind(actor) if actor_backend == "hip" else kind(actor, precision="bf16x3")
     E, N = env.nb_envs, env.nb_houses
     if per_agent and len(actor) != N:
         raise ValueError("collect_maddpg_transitions: %d actors for %d agents" % (len(actor), N))

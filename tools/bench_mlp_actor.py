@@ -3,12 +3,15 @@
 without it - ``actor(rows)`` under ``torch.no_grad()`` + ``mdr_logits_sample`` - on the same rows, same GPU, same session.  HIP events
 after warm-up, the two paths alternating; the median of `--repeats` windows and their spread; one JSON line per batch.
 
-    python tools/bench_mlp_actor.py [--repeats 7] [--warmup 3] [--only hip|torch] [--cases 51:1x20,...] [--out FILE]
+    python tools/bench_mlp_actor.py [--repeats 7] [--warmup 3] [--only hip|torch] [--precision fp32,bf16x3] [--cases 51:1x20,...] [--out FILE]
 
 Batches (features : envs x houses), hidden 256-256: 51:1x20, 51:64x50, 51:4096x20, 51:4096x1024 and 121:4096x1024.  Before anything is
 timed the worst difference between the two paths' probabilities is printed.  ``floor_us`` is the batch's FLOPs - 2 (F H1 + H1 H2 + 2 H2)
 per agent, counted from the shapes - at the 157.3 TFLOP/s fp32 matrix peak of the MI355X, ``floor_share`` that over the kernel path's
 median window (launch overhead included: at the small batches the share is that of an empty launch).
+``--precision fp32,bf16x3`` times ``FusedMLPActor(precision="bf16x3")`` (csrc/mdr_mlp_actor_bf16.hip) as a third path in the same
+alternating windows: ``hip_bf16x3_*``, its floor - three bf16 products of 32 k at 16 cycles against eight fp32 k-steps of 4 at 32
+cycles, 3/16 of ``floor_us`` - and ``fp32_over_bf16x3`` with ``spread_us``, the wider of the two kernels' max - min.
 Per-kernel times come from `rocprofv3 --kernel-trace --stats -- python tools/bench_mlp_actor.py --only hip` in a run of its own.
 """
 import argparse
@@ -50,8 +53,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", choices=("hip", "torch"), default=None)
+    ap.add_argument("--precision", default="fp32", help="comma-separated precisions of the kernel path: fp32, bf16x3")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    precisions = args.precision.split(",")
+    assert precisions and all(p in ("fp32", "bf16x3") for p in precisions), "--precision takes fp32 and bf16x3"
+    hip_paths = {"hip" if p == "fp32" else "hip_" + p: p for p in precisions}      # path name -> precision
     assert torch.cuda.is_available(), "bench_mlp_actor.py needs a GPU"
     lib = nat.load()
     lines = []
@@ -60,7 +67,7 @@ def main():
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
-    paths = [b for b in ("hip", "torch") if args.only in (None, b)]
+    paths = [b for b in (*hip_paths, "torch") if args.only in (None, "hip" if b in hip_paths else b)]
     for case in args.cases.split(","):
         F, shape = case.split(":")
         F, (E, N) = int(F), (int(x) for x in shape.split("x"))
@@ -71,12 +78,16 @@ def main():
             actor.fc[2].weight.mul_(8.0)      # probabilities away from 1/2
         rows = torch.rand((A, F), device=DEV, generator=torch.Generator(device=DEV).manual_seed(1)) * 2 - 1
         fused = FusedMLPActor(actor)
-        act = {b: torch.empty(A, dtype=torch.uint8, device=DEV) for b in ("hip", "torch")}
+        split = FusedMLPActor(actor, precision="bf16x3")
+        act = {b: torch.empty(A, dtype=torch.uint8, device=DEV) for b in ("hip", "hip_bf16x3", "torch")}
         a_prob = torch.empty(A, dtype=torch.float32, device=DEV)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
         def hip(probs=None):
             return fused.sample(rows, 5, 7, action=act["hip"], a_prob=a_prob)
+
+        def hip_bf16x3(probs=None):
+            return split.sample(rows, 5, 7, action=act["hip_bf16x3"], a_prob=a_prob)
 
         def torch_path(probs=None):      # rollout.collect_maddpg_transitions, actor_backend="torch"
             with torch.no_grad():
@@ -86,7 +97,7 @@ def main():
             assert rc == 0
 
         diff = flips = None
-        if len(paths) == 2:      # the two paths agree before anything is timed
+        if "hip" in paths and "torch" in paths:      # the two paths agree before anything is timed
             p_t = torch.empty((A, 2), dtype=torch.float32, device=DEV)
             torch_path(p_t)
             _, _, p_h = fused.sample(rows, 5, 7, action=act["hip"], want_probs=True)
@@ -95,7 +106,14 @@ def main():
             print("# %s: worst |p_hip - p_torch| = %.3e, %d of %d actions differ, p0 in [%.3f, %.3f]"
                   % (case, diff, flips, A, float(p_h[:, 0].min()), float(p_h[:, 0].max())), flush=True)
             del p_t, p_h
-        fns = {"hip": hip, "torch": torch_path}
+        diff_split = None
+        if "hip" in paths and "hip_bf16x3" in paths:
+            _, _, p_h = fused.sample(rows, 5, 7, action=act["hip"], want_probs=True)
+            _, _, p_s = split.sample(rows, 5, 7, action=act["hip_bf16x3"], want_probs=True)
+            diff_split = float((p_h - p_s).abs().max())
+            print("# %s: worst |p_fp32 - p_bf16x3| = %.3e, %d of %d actions differ" % (case, diff_split, int((act["hip"] != act["hip_bf16x3"]).sum()), A), flush=True)
+            del p_h, p_s
+        fns = {"hip": hip, "hip_bf16x3": hip_bf16x3, "torch": torch_path}
         iters = max(3, min(200, 2000000 // A + 3))
         t = {b: [] for b in paths}
         for _ in range(args.warmup):
@@ -113,10 +131,17 @@ def main():
             rec[b + "_us_min"], rec[b + "_us_max"] = round(min(v), 2), round(max(v), 2)
         if "hip" in t:
             rec["floor_share"] = round(floor_us / statistics.median(t["hip"]), 4)
-        if len(paths) == 2:
+        if "hip_bf16x3" in t:
+            rec["bf16x3_floor_us"] = round(floor_us * 3.0 / 16.0, 3)
+            rec["bf16x3_floor_share"] = round(floor_us * 3.0 / 16.0 / statistics.median(t["hip_bf16x3"]), 4)
+            rec["max_abs_diff_fp32_bf16x3"] = diff_split
+        if "hip" in t and "hip_bf16x3" in t:
+            rec["fp32_over_bf16x3"] = round(statistics.median(t["hip"]) / statistics.median(t["hip_bf16x3"]), 3)
+            rec["spread_us"] = round(max(max(t[b]) - min(t[b]) for b in ("hip", "hip_bf16x3")), 2)
+        if "hip" in t and "torch" in t:
             rec["torch_over_hip"] = round(statistics.median(t["torch"]) / statistics.median(t["hip"]), 3)
         emit(**rec)
-        del actor, rows, fused, act, a_prob
+        del actor, rows, fused, split, act, a_prob
         torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
