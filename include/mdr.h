@@ -25,6 +25,8 @@
  * Likewise mdr_env_tarmac_actor_sample (mdr_policy.h): the TarMAC actor fed from the env's compact state; and
  * mdr_env_bind_thermal_pack with its query mdr_env_rollout_plan: the five thermal columns as one 16-byte record per house.
  * Likewise mdr_env_rollout_resident: whether mdr_env_rollout keeps the houses in registers between its interior steps.
+ * Likewise mdr_env_mlp_actor_sample and mdr_env_mlp_actor_sample_bf16x3 (mdr_policy.h): the 256-unit actor fed from the env's
+ * compact state.
  */
 #ifndef MDR_H
 #define MDR_H

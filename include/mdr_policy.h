@@ -586,6 +586,30 @@ int mdr_mlp_actor_sample_bf16x3(const mdr_mlp_t *actor, const float *obs, int64_
                                 const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob,
                                 float *probs, void *stream);
 
+/* Observe -> act for this actor: mdr_mlp_actor_sample / mdr_mlp_actor_sample_bf16x3 on the observation of every agent of `env` in its
+ * current state, WITHOUT the observation rows (csrc/mdr_mlp_actor_observe.hip).  Per tile of 32 agents one wavefront of the workgroup
+ * builds the 51 normStateDict features in LDS from the compact state - the staging of mdr_env_actor_sample and
+ * mdr_env_tarmac_actor_sample - and the workgroup copies them, feature by feature in torch's order, into the LDS image the rows
+ * kernel stages; both layers, the head, the softmax and the draw are that kernel's.  `action`, `a_prob` and `probs` are bit for bit
+ * those of mdr_mlp_actor_sample (_bf16x3: of mdr_mlp_actor_sample_bf16x3) on the rows of mdr_env_obs_vector(MDR_OBS_ROWS) with
+ * ld_obs = 51 for the same (seed, step, *step_dev, greedy), whatever max_workgroups (agent index = env * nb_houses + house).
+ * `rows_out` (may be NULL): float [nb_agents][51], 4-byte aligned, receives the rows as a by-product, bit for bit those of
+ * mdr_env_obs_vector.  `actor`, `step_dev`, `greedy`, `max_workgroups`, the grid and capture in a graph as mdr_mlp_actor_sample; the
+ * env is only read.  One launch on `stream`, no synchronisation, no allocation.
+ * Covers what mdr_env_tarmac_actor_sample covers - every optional state / message column off, agents_comm_mode "neighbours" with
+ * nb_agents_comm = 10, no link table, no link defects, unsharded houses, nb_houses >= 11 (the tiles of 32 agents of every cluster
+ * size up to 1999 fit the 64 staging lanes; the library checks it for the size it is given) - and actor->num_state == 51, hidden1 and
+ * hidden2 anything in 1 .. 256, num_out == 2.  Anything else returns MDR_ERR_UNSUPPORTED (-4) with mdr_last_error set: fall back to
+ * mdr_env_obs_vector + mdr_mlp_actor_sample.  -1: NULL `env`, `spec`, `actor` or `action`, a NULL weight pointer, a struct_size that
+ * is not this header's, max_workgroups < 0.  Every refusal is decided before anything touches the device: nothing is launched,
+ * nothing written.  -3: HIP error.  nb_envs * nb_houses == 0 returns 0 and launches nothing. */
+int mdr_env_mlp_actor_sample(mdr_env_t *env, const mdr_obs_spec_t *spec, const mdr_mlp_t *actor, uint64_t seed, uint64_t step,
+                             const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob, float *probs,
+                             float *rows_out, void *stream);
+int mdr_env_mlp_actor_sample_bf16x3(mdr_env_t *env, const mdr_obs_spec_t *spec, const mdr_mlp_t *actor, uint64_t seed, uint64_t step,
+                                    const int32_t *step_dev, int32_t greedy, int32_t max_workgroups, uint8_t *action, float *a_prob,
+                                    float *probs, float *rows_out, void *stream);
+
 /* ---- MADDPG with one network per agent (ddpg.py:200-213: every agent its own actor, critic and target of each; what every
  * checkpoint of saveDDPGDict holds).  At most MDR_MAX_AGENT_NETS nets per call: their weight pointers travel in the kernel argument
  * block (32 x 6 pointers = 1.5 KB), so no device table is owned by anybody and a captured call stays valid while the parameter

@@ -221,6 +221,7 @@ EXPORTS = (
     "mdr_mappo_critic_wide_grad_floats", "mdr_mappo_critic_wide_workspace_bytes", "mdr_mappo_critic_grad_wide",
     "mdr_maddpg_grad_floats", "mdr_maddpg_workspace_bytes", "mdr_maddpg_target", "mdr_maddpg_critic_grad", "mdr_maddpg_actor_grad",
     "mdr_mlp_actor_sample", "mdr_mlp_actor_sample_bf16x3", "mdr_mlp_actors_sample", "mdr_maddpg_target_agents",
+    "mdr_env_mlp_actor_sample", "mdr_env_mlp_actor_sample_bf16x3",
     "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
     "mdr_tarmac_critic_grad_floats", "mdr_tarmac_critic_workspace_bytes", "mdr_tarmac_critic_value", "mdr_tarmac_critic_grad",
     "mdr_tarmac_a2c_grad_floats", "mdr_tarmac_a2c_workspace_bytes", "mdr_tarmac_a2c_forward", "mdr_tarmac_a2c_comm", "mdr_tarmac_a2c_grad",
@@ -349,6 +350,8 @@ def load():
                                             i32, vp, vp, vp, vp, vp, vp]),
         "mdr_mlp_actor_sample": (C.c_int, [C.POINTER(MdrMlp), vp, i64, i64, u64, u64, vp, i32, i32, vp, vp, vp, vp]),
         "mdr_mlp_actor_sample_bf16x3": (C.c_int, [C.POINTER(MdrMlp), vp, i64, i64, u64, u64, vp, i32, i32, vp, vp, vp, vp]),
+        "mdr_env_mlp_actor_sample": (C.c_int, [vp, C.POINTER(MdrObsSpec), C.POINTER(MdrMlp), u64, u64, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "mdr_env_mlp_actor_sample_bf16x3": (C.c_int, [vp, C.POINTER(MdrObsSpec), C.POINTER(MdrMlp), u64, u64, vp, i32, i32, vp, vp, vp, vp, vp]),
         # one net per agent: a host array of descriptors and its length in front
         "mdr_mlp_actors_sample": (C.c_int, [C.POINTER(MdrMlp), i32, vp, i64, i64, u64, u64, vp, i32, i32, vp, vp, vp, vp]),
         "mdr_maddpg_target_agents": (C.c_int, [C.POINTER(MdrMlp), i32, C.POINTER(MdrMlp), vp, i64, vp, vp, i64, i32, i32, vp, C.c_float,

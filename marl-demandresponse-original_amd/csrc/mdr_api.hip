@@ -1621,6 +1621,42 @@ int mdr_env_tarmac_actor_sample(mdr_env_t* env, const mdr_obs_spec_t* spec, cons
   return MDR_OK;
 }
 
+// mdr_env_mlp_actor_sample / _bf16x3: mdr_mlp_actor_sample's argument checks, then mdr_env_tarmac_actor_sample's - all of them before
+// anything touches the device
+static int mlp_actor_observe_impl(mdr_env_t* env, const mdr_obs_spec_t* spec, const mdr_mlp_t* actor, bool bf16x3, uint64_t seed, uint64_t step,
+                                  const int32_t* step_dev, int32_t greedy, int32_t max_workgroups, uint8_t* action, float* a_prob, float* probs,
+                                  float* rows_out, void* stream) {
+  if (!env || !spec || !action || max_workgroups < 0) return MDR_ERR_INVALID;
+  int rc = mdr::mlp_actor_observe_status(actor, 32);      // the net alone (32 houses: a cluster every form takes)
+  if (rc == MDR_ERR_INVALID) return fail(env, rc, "MLP observe -> act: NULL actor or weight pointer, or a struct_size that is not this header's");
+  if (env->cfg.nb_houses_total != env->cfg.nb_houses) return fail(env, MDR_ERR_UNSUPPORTED, "observe -> act needs unsharded houses");
+  if (spec->state_hour || spec->state_day || spec->state_solar_gain || spec->state_thermal || spec->state_hvac || spec->message_thermal ||
+      spec->message_hvac || spec->nb_comm != 10 || spec->links != nullptr || spec->random_links || spec->comm_defect_prob > 0.0)
+    return fail(env, MDR_ERR_UNSUPPORTED, "MLP observe -> act covers the default observation: no optional column, 10 circular neighbours, no link defects");
+  if (rc == MDR_OK) rc = mdr::mlp_actor_observe_status(actor, env->cfg.nb_houses);
+  if (rc != MDR_OK)
+    return fail(env, rc, "MLP observe -> act covers 51 features: nb_houses >= 11 whose tiles of 32 agents fit a wave's staging lanes, and an actor with num_state = 51, hidden layers of 1 .. 256 units and 2 outputs");
+  mdr::ObserveArgs o;
+  rc = observe_args(env, spec, nullptr, nullptr, stream, &o);
+  if (rc != MDR_OK) return rc;
+  if (o.ext) return fail(env, MDR_ERR_UNSUPPORTED, "MLP observe -> act covers the default observation");
+  rc = mdr::launch_mlp_actor_observe(actor, o, bf16x3, seed, step, step_dev, greedy, max_workgroups, action, a_prob, probs, rows_out, (hipStream_t)stream);
+  if (rc != MDR_OK) return fail(env, rc, "MLP observe -> act: launch failed");
+  return MDR_OK;
+}
+
+int mdr_env_mlp_actor_sample(mdr_env_t* env, const mdr_obs_spec_t* spec, const mdr_mlp_t* actor, uint64_t seed, uint64_t step,
+                             const int32_t* step_dev, int32_t greedy, int32_t max_workgroups, uint8_t* action, float* a_prob, float* probs,
+                             float* rows_out, void* stream) {
+  return mlp_actor_observe_impl(env, spec, actor, false, seed, step, step_dev, greedy, max_workgroups, action, a_prob, probs, rows_out, stream);
+}
+
+int mdr_env_mlp_actor_sample_bf16x3(mdr_env_t* env, const mdr_obs_spec_t* spec, const mdr_mlp_t* actor, uint64_t seed, uint64_t step,
+                                    const int32_t* step_dev, int32_t greedy, int32_t max_workgroups, uint8_t* action, float* a_prob,
+                                    float* probs, float* rows_out, void* stream) {
+  return mlp_actor_observe_impl(env, spec, actor, true, seed, step, step_dev, greedy, max_workgroups, action, a_prob, probs, rows_out, stream);
+}
+
 int mdr_env_comm_draws(mdr_env_t* env, const mdr_obs_spec_t* spec, int32_t* senders, uint8_t* keep, void* stream) {
   if (!env || !spec || !senders || !keep) return MDR_ERR_INVALID;
   mdr::ObsArgs a;

@@ -295,6 +295,13 @@ int launch_actor_observe(const struct mdr_actor* actor, const ObserveArgs& o, ui
 // and results, MDR_ERR_UNSUPPORTED with nothing launched for what tarmac_observe_covered (mdr_tarmac_mlp.h) rules out
 int tarmac_sample_observe(const struct mdr_tarmac_actor* actor, const ObserveArgs& o, uint64_t seed, uint64_t step, const int32_t* step_dev,
                           void* workspace, uint8_t* action, float* a_prob, float* probs, float* rows_out, hipStream_t s);
+// The 256-unit actor on the compact state (mdr_mlp_actor_observe.hip; mdr_env_mlp_actor_sample[_bf16x3]).  _status: what of the net
+// and the cluster size the observe forms take - MDR_OK, MDR_ERR_INVALID or MDR_ERR_UNSUPPORTED, decided on the host.  The launch
+// repeats it, refuses an extended `o` and launches nothing for an empty batch.
+int mlp_actor_observe_status(const struct mdr_mlp* actor, int32_t nb_houses);
+int launch_mlp_actor_observe(const struct mdr_mlp* actor, const ObserveArgs& o, bool bf16x3, uint64_t seed, uint64_t step, const int32_t* step_dev,
+                             int32_t greedy, int32_t max_workgroups, uint8_t* action, float* a_prob, float* probs, float* rows_out,
+                             hipStream_t s);
 int obs_vector_length(const mdr_obs_spec_t& spec);
 hipError_t launch_step_begin_split(const StepArgs& a, bool reduce, hipStream_t s);
 hipError_t launch_step_end_split(const StepArgs& a, hipStream_t s);

@@ -1,6 +1,6 @@
 // What the TarMAC actor's matrix-core kernels share between the exact-fp32 forms (mdr_tarmac_mlp.hip) and the bf16x3 forms
 // (mdr_tarmac_mlp_bf16.hip): the limits, the layout of mdr_tarmac_actor_t.vec, the kernel arguments, the activations, the kernels'
-// prologue (stage_weights), the head's tail (head_finish), the observe forms' LDS window (ObserveWindow), the fragment sizes, the
+// prologue (stage_weights), the head's tail (head_finish), the fragment sizes, the
 // persistent-grid launch and the launch chain of a sample (run_chain<Forms>).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -196,78 +196,8 @@ struct WindowArgs {
 };
 
 // ---- observe -> act (mdr_env_tarmac_actor_sample): the encode kernels' forms that build their features in LDS (mdr_observe.h)
-constexpr int TARMAC_OBS_ROW = 60;      // floats per staged row (ObserveSource, mdr_tarmac_mlp.hip, says why)
+// (the window itself: ObserveWindow and its row stride TARMAC_OBS_ROW, mdr_observe.h)
 constexpr size_t LDS_PER_CU = 160 * 1024;
-
-// The window of one wavefront behind the staged weights: TILE consecutive agents' rows, staged from the env's compact state by the
-// helpers of mdr_observe.h exactly as k_actor_observe16 / k_actor_observe_bf16 (mdr_policy.hip) stage theirs for the default
-// observation, and what the two precisions do with it alike.  GEN: tiles that may leave their env (N no multiple of TILE).  STORE:
-// the rows are also written to rows_out through the workgroup's offset table.
-template <int TILE, bool STORE, bool GEN>
-struct ObserveWindow {
-  static constexpr int ROW = TARMAC_OBS_ROW, WIN = TILE * ROW;
-  const mdr::ObserveArgs& o;
-  float* rows_out;
-  int64_t A, ntiles;
-  float* rows;
-  uint16_t* table;      // [TILE * 51] (only when rows are stored)
-  const double* sig_row;
-  int lane0;
-  TileCursor tc;
-  SegSlot slot;
-  HouseRegs nxt;
-  int64_t next_tile, stride;      // the wavefront's tile after this one
-  bool more;                      // ... is there
-
-  // normStateDict feature n of a tile row sits at this float of the row
-  static __device__ __forceinline__ int at(int n) { return n < 11 ? 4 * OBS_C + n : n - 11; }
-
-  // before the workgroup's barrier: `nw` = as many of the form's waves as the windows leave room for
-  __device__ __forceinline__ void carve(float* behind_weights, int nw) {
-    const int tid = threadIdx.x;
-    rows = behind_weights + (tid >> 6) * WIN;
-    table = reinterpret_cast<uint16_t*>(behind_weights + nw * WIN);
-    lane0 = tid & 63;
-    for (int i = lane0; i < WIN; i += 64) rows[i] = 0.0f;
-    if (STORE) observe_build_table<TILE, ROW>(table, tid, 64 * nw);
-  }
-  __device__ __forceinline__ void start(int64_t wave, int64_t nwaves) {
-    sig_row = observe_sig_row(o);
-    tc.init(wave * TILE, nwaves * TILE, o.N);
-    slot = SegSlot{};
-    stride = nwaves;
-  }
-  __device__ __forceinline__ void advance(int64_t t) {
-    next_tile = t + stride;
-    more = next_tile < ntiles;
-    tc.next();
-    nxt = HouseRegs{};
-  }
-  // the compact state of the tile at the cursor, which starts at first_agent, into registers / from them into the window
-  __device__ __forceinline__ void load(int64_t first_agent) {
-    nxt = GEN ? observe_load_gen<TILE>(o, sig_row, tc.e, tc.h0, first_agent, A, lane0, slot) : observe_load<TILE>(o, sig_row, tc.e, tc.h0, lane0);
-  }
-  __device__ __forceinline__ void stage_rows() {
-    if (GEN) observe_stage_gen<false, ROW>(o, nxt, slot, rows);
-    else observe_stage<TILE, false, ROW>(o, nxt, rows, lane0);
-  }
-  // the senders' seconds_since_off become quotients by the RECEIVER's lockout, in place: lane group g takes the messages g, g + 4
-  // and g + 8 of tile row `r` (k_actor_observe16)
-  __device__ __forceinline__ void lockout_quotients(int r, int g) {
-    float* row = rows + r * ROW;
-    const float lock = row[4 * OBS_C + 11], y = row[4 * OBS_C + 12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int m = g + 4 * i;
-      if (m < OBS_C) row[4 * m + 1] = mdr::div_by_lockout(row[4 * m + 1], lock, y);
-    }
-  }
-  __device__ __forceinline__ void store_rows(int64_t first_agent) {
-    if (STORE)
-      observe_store_rows<TILE>(rows, table, rows_out + first_agent * 51, lane0,
-                               GEN ? (int)((A - first_agent) < (int64_t)TILE ? (A - first_agent) : (int64_t)TILE) : TILE);
-  }
-};
 
 // ---- host: the launches.  Each kernel is a persistent grid: the weights are staged once per workgroup
 template <typename K, typename... Extra>

@@ -580,7 +580,9 @@ class GreedyDDPGActor:
     a torch forward and a compare; ``"hip"``: the greedy form of ``FusedMLPActor`` - forward and argmax in one kernel (ValueError for a
     net it does not take); it honours ``step_dev``, which a greedy pick does not read.  ``"hip-bf16x3"``: that form with
     ``precision="bf16x3"`` (one shared net only).  ``actor``: one module, or a sequence of N (unshared networks): row e N + k is
-    agent k's and goes through ``actor[k]`` - N torch forwards, or ``FusedMLPActors`` (fp32 only: ValueError with "hip-bf16x3")."""
+    agent k's and goes through ``actor[k]`` - N torch forwards, or ``FusedMLPActors`` (fp32 only: ValueError with "hip-bf16x3").
+    One shared net on a hip backend also has ``sample_env`` - the actions from the env's compact state, no observation rows -
+    which ``deploy_policy(..., observe_act=True)`` takes where ``observe_supported(env)`` holds."""
 
     def __init__(self, actor, backend: str = "torch"):
         if backend not in ("torch", "hip", "hip-bf16x3"):
@@ -616,20 +618,42 @@ class GreedyDDPGActor:
         action.copy_(act)
         return action
 
+    def observe_supported(self, env) -> bool:
+        """Can ``sample_env`` serve ``env``?  One shared net behind ``backend="hip"`` or ``"hip-bf16x3"`` and
+        ``FusedMLPActor.observe_supported(env)``.  Decided on the host."""
+        return self._fused is not None and not self.per_agent and self._fused.observe_supported(env)
+
+    @torch.no_grad()
+    def sample_env(self, env, seed: int = 0, step: int = 0, action: Optional[torch.Tensor] = None, step_dev=None) -> torch.Tensor:
+        """``sample(env.obs_vector("rows").view(E * N, 51), ...)`` without the rows (``FusedMLPActor.sample_env``): the same actions,
+        bit for bit.  ValueError for a list of nets, ``backend="torch"`` or an env the kernel does not cover."""
+        if self._fused is None or self.per_agent:
+            raise ValueError("GreedyDDPGActor.sample_env: one shared net with backend='hip' or 'hip-bf16x3' only")
+        why = self._fused._observe_refusal(env)
+        if why:
+            raise ValueError("GreedyDDPGActor.sample_env: " + why)
+        A = env.nb_envs * env.nb_houses
+        if self._a_prob is None or self._a_prob.numel() != A or self._a_prob.device != env.device:
+            self._a_prob = torch.empty(A, dtype=torch.float32, device=env.device)      # kept: a captured step allocates nothing
+        return self._fused.sample_env(env, seed, step, step_dev=step_dev, action=action, a_prob=self._a_prob)[0]
+
 
 def train_maddpg(env, learner: MADDPGLearner, nb_steps: int, update_every: int = 1, random_steps: int = 0, seed: int = 0,
-                 actor_backend: str = "torch") -> Tuple[torch.Tensor, torch.Tensor]:
+                 actor_backend: str = "torch", observe_act: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """The loop of train_ddpg.py:95-131 on a batched env (reset by the caller): every iteration one ``collect_maddpg_transitions``
     step of all envs (uniformly random actions while the 1-based step is below ``random_steps``, the actor's gumbel sample after), ``store``, and
     after every ``update_every``-th step from ``random_steps`` on one ``update()`` (which ends with the target blend).
     ``actor_backend`` is ``collect_maddpg_transitions``': "hip" acts through ``FusedMLPActor``, which reads the actor's weights in
-    place and so sees every update; "hip-bf16x3" is its bf16x3 precision (a shared actor only).  -> (actor losses [n, N], critic losses [n, N]) of the updates that ran, on the device."""
+    place and so sees every update; "hip-bf16x3" is its bf16x3 precision (a shared actor only).  ``observe_act`` is
+    ``collect_maddpg_transitions``' too: the acting steps through ``FusedMLPActor.sample_env``, the same transitions bit for bit.
+    -> (actor losses [n, N], critic losses [n, N]) of the updates that ran, on the device."""
     from .rollout import collect_maddpg_transitions
     a_losses, c_losses = [], []
     for t in range(int(nb_steps)):
         step = t + 1      # train_ddpg.py:96-97, 124-127: random while step < random_steps, learn from step >= random_steps on
         batch = collect_maddpg_transitions(env, learner.actor if getattr(learner, "shared", True) else learner.actors, 1, random_steps_left=max(int(random_steps) - step, 0),
-                                           seed=(int(seed) * 1000003 + t) & (2 ** 63 - 1), actor_backend=actor_backend)
+                                           seed=(int(seed) * 1000003 + t) & (2 ** 63 - 1), actor_backend=actor_backend,
+                                           observe_act=observe_act)
         learner.store(batch)
         if step >= int(random_steps) and step % int(update_every) == 0:
             out = learner.update(seed=seed)

@@ -7,6 +7,8 @@ their slabs of W1 and W2 in registers and stride over tiles of 32 agents.  The w
 call - there is no packed copy - so an optimiser step between two calls is seen by the next one, which is what ``train_maddpg`` needs:
 it changes the actor at every update.  Draws, outputs and ``step_dev`` are ``FusedActor.sample``'s, so ``deploy_policy`` takes a
 ``FusedMLPActor`` through its duck-typed branch.  Nothing on the call path synchronises with the host.
+``FusedMLPActor.sample_env`` is observe -> act (mdr_env_mlp_actor_sample, csrc/mdr_mlp_actor_observe.hip): the same outputs, bit for
+bit, from the env's compact state - no row kernel, no rows - for the default observation of 51 features; opt-in everywhere.
 """
 from __future__ import annotations
 
@@ -20,6 +22,25 @@ from . import _native as nat
 
 MAX_STATE, MAX_HIDDEN = 128, 256      # the kernel's limits (include/mdr_policy.h: mdr_mlp_actor_sample)
 PRECISIONS = {"fp32": "mdr_mlp_actor_sample", "bf16x3": "mdr_mlp_actor_sample_bf16x3"}      # precision -> entry point
+OBSERVE_ENTRIES = {"fp32": "mdr_env_mlp_actor_sample", "bf16x3": "mdr_env_mlp_actor_sample_bf16x3"}      # ... of sample_env
+OBSERVE_NUM_STATE = 51      # the default observation, which the observe forms build
+
+
+def default_observation_refusal(env) -> Optional[str]:
+    """Why observe -> act does not cover ``env`` (None: it does) - what ``mdr_env_mlp_actor_sample`` checks of the env, read on the
+    host: the default observation of an unsharded env of at least 11 houses."""
+    if getattr(env, "sharded", False):
+        return "house-sharded envs are not covered"
+    spec = env._obs_spec("rows")
+    if spec.state_hour or spec.state_day or spec.state_solar_gain or spec.state_thermal or spec.state_hvac or spec.message_thermal or spec.message_hvac:
+        return "an optional state or message column is on"
+    if spec.nb_comm != 10 or spec.links or spec.random_links:
+        return "the env's agents_comm_mode must be 'neighbours' with nb_agents_comm = 10"
+    if spec.comm_defect_prob > 0.0:
+        return "link defects on the env's messages are not covered"
+    if env.nb_houses < 11:
+        return "10 distinct neighbours need at least 11 houses"
+    return None
 
 
 class FusedMLPActor:
@@ -97,6 +118,58 @@ class FusedMLPActor:
                                            int(self.greedy if greedy is None else bool(greedy)), int(max_workgroups), L.ptr(action),
                                            L.ptr(a_prob), L.ptr(probs), L.stream(dev))
         nat.check(self._lib, None, rc, entry)
+        return (action, a_prob, probs) if want_probs else (action, a_prob)
+
+    def _observe_refusal(self, env) -> Optional[str]:
+        """Why ``sample_env`` cannot serve ``env`` (None: it can): the net's input size, the env, then ``refusal`` of the net."""
+        fc = L.fc_layers(self.module)
+        if fc is not None and fc[0].in_features != OBSERVE_NUM_STATE:
+            return "the actor takes %d features, observe -> act builds the default observation of %d" % (fc[0].in_features, OBSERVE_NUM_STATE)
+        return default_observation_refusal(env) or self.refusal(self.module)
+
+    def observe_supported(self, env) -> bool:
+        """Can ``sample_env`` serve ``env``?  The default observation of 51 features (no optional state / message column, ten circular
+        neighbours, no link defects) of an unsharded env of at least 11 houses, and a net ``sample`` takes with ``num_state == 51``.
+        Decided on the host: nothing is launched."""
+        return self._observe_refusal(env) is None
+
+    def sample_env(self, env, seed: int, step: int, step_dev: Optional[torch.Tensor] = None, greedy: Optional[bool] = None,
+                   action: Optional[torch.Tensor] = None, a_prob: Optional[torch.Tensor] = None, want_probs: bool = False,
+                   rows_out: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> Tuple[torch.Tensor, ...]:
+        """Observe -> act (``mdr_env_mlp_actor_sample``, ``_bf16x3`` with ``precision="bf16x3"``; csrc/mdr_mlp_actor_observe.hip):
+        ``sample(env.obs_vector("rows").view(E * N, 51), ...)`` without the rows - no row kernel, no row read; the kernel builds the 51
+        features of its tile of agents in LDS from the env's compact state.  Returns what ``sample`` returns, bit for bit, every
+        argument as there.  ``rows_out`` (float32, contiguous, A * 51 elements, on the env's device): also receives the rows, bit for
+        bit ``env.obs_vector("rows")`` (the transition buffer's ``state``).  ``ValueError`` before any launch for an env or net it
+        does not cover (``observe_supported``).  With ``action`` and ``a_prob`` given (and no ``want_probs``) nothing is allocated.
+        Measured against rows + ``sample``: profiles/mlp_actor_observe_README.md."""
+        what = "FusedMLPActor.sample_env"
+        why = self._observe_refusal(env)
+        if why:
+            raise ValueError("%s: %s" % (what, why))
+        fc = L.fc_layers(self.module)
+        dev = env.device
+        if dev != fc[0].weight.device:
+            raise ValueError("%s: the env and the actor's parameters must be on the same device" % what)
+        if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.device != dev):
+            raise ValueError("step_dev must be an int32 tensor on the device (env.device_time_index)")
+        A = env.nb_envs * env.nb_houses
+        action = torch.empty(A, dtype=torch.uint8, device=dev) if action is None else L.whole(action, torch.uint8, A, dev, what, "action")
+        a_prob = torch.empty(A, dtype=torch.float32, device=dev) if a_prob is None else L.whole(a_prob, torch.float32, A, dev, what, "a_prob")
+        if rows_out is not None:
+            L.whole(rows_out, torch.float32, A * OBSERVE_NUM_STATE, dev, what, "rows_out")
+        probs = torch.empty((A, 2), dtype=torch.float32, device=dev) if want_probs else None
+        desc = L.mlp_desc(fc)
+        spec = env._obs_spec("rows")
+        entry = OBSERVE_ENTRIES[self.precision]
+        with torch.cuda.device(dev):
+            rc = getattr(self._lib, entry)(env._handle, C.byref(spec), C.byref(desc), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                           C.c_uint64(int(step) & (2 ** 64 - 1)), L.ptr(step_dev),
+                                           int(self.greedy if greedy is None else bool(greedy)), int(max_workgroups), L.ptr(action),
+                                           L.ptr(a_prob), L.ptr(probs), L.ptr(rows_out), L.stream(dev))
+        if rc == nat.MDR_ERR_UNSUPPORTED:
+            raise ValueError("%s: %s" % (what, self._lib.mdr_last_error(env._handle).decode()))
+        nat.check(self._lib, env._handle, rc, entry)
         return (action, a_prob, probs) if want_probs else (action, a_prob)
 
 

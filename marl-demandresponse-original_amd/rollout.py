@@ -268,6 +268,20 @@ def _tarmac_observe_act(env, actor, observe_act: Optional[bool]) -> bool:
     return can if observe_act is None else bool(observe_act)
 
 
+def _mlp_observe_act(env, policy, observe_act: Optional[bool]) -> bool:
+    """``observe_act`` of deploy_policy for the 256-unit actor - a ``FusedMLPActor``, or a ``GreedyDDPGActor`` of one shared net on a
+    hip backend: opt-in - True -> ``sample_env`` (ValueError where it cannot serve the env), None and False -> observation rows.
+    False for every other kind of policy, whatever ``observe_act``."""
+    from .maddpg import GreedyDDPGActor
+    from .mlp_actor import FusedMLPActor
+    if not isinstance(policy, (GreedyDDPGActor, FusedMLPActor)) or not observe_act:
+        return False
+    if not policy.observe_supported(env):
+        raise ValueError("observe_act=True needs a FusedMLPActor, or a GreedyDDPGActor of one shared net with backend='hip' or "
+                         "'hip-bf16x3', and an env its sample_env covers (observe_supported)")
+    return True
+
+
 @torch.no_grad()
 def collect_tarmac_rollout(env, actor, nb_steps: int, gamma: float = 0.99, critic: Optional[nn.Module] = None, seed: int = 0,
                            store_states: bool = True, observe_act: Optional[bool] = None) -> Dict[str, torch.Tensor]:
@@ -444,7 +458,7 @@ def collect_dqn_transitions(env, q_net: nn.Module, nb_steps: int, epsilon: float
 
 
 def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int = 0, seed: int = 0,
-                               actor_backend: str = "torch") -> Dict[str, torch.Tensor]:
+                               actor_backend: str = "torch", observe_act: bool = False) -> Dict[str, torch.Tensor]:
     """The interaction loop of train_ddpg.py:95-116 for all envs at once, env-steps kept on the GPU: every step the actor's logits on
     every agent's OWN observation (the reference stores agent 0's for all, train_ddpg.py:86-91), the acting action, ``env.step``,
     and the env-step (state, action, reward, next_state) of ``MADDPG.push``.  ``select_action`` takes the argmax of a hard
@@ -464,7 +478,12 @@ def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int
 
     ``actor``: one module for all agents, or a sequence of N modules - agent k acts through ``actor[k]`` (MADDPG with unshared
     networks, ddpg.py:200-213).  "torch": N forwards on ``state[t][:, k]``, the logits gathered to [E N, 2], then the one
-    ``mdr_logits_sample``; "hip": ``FusedMLPActors`` - one launch, the same (seed, step), so the same draws."""
+    ``mdr_logits_sample``; "hip": ``FusedMLPActors`` - one launch, the same (seed, step), so the same draws.
+
+    ``observe_act=True`` (one shared net, a hip backend and an env ``FusedMLPActor.observe_supported`` covers; ValueError otherwise,
+    before the env is touched): the acting steps go through ``FusedMLPActor.sample_env`` - no row kernel, no row read - and that
+    kernel writes ``state[t]`` on the side; the random steps and ``state[T]`` take ``obs_vector("rows")``.  The returned dict is bit
+    for bit the ``observe_act=False`` one.  Measured: profiles/mlp_actor_observe_README.md."""
     import ctypes as C
 
     from . import _native as nat
@@ -481,6 +500,9 @@ def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int
         if why:
             raise ValueError("collect_maddpg_transitions(actor_backend=%r): %s" % (actor_backend, why))
         fused = kind(actor) if actor_backend == "hip" else kind(actor, precision="bf16x3")
+    if observe_act and (fused is None or per_agent or not fused.observe_supported(env)):
+        raise ValueError("collect_maddpg_transitions(observe_act=True) needs one shared net, actor_backend 'hip' or 'hip-bf16x3' and an "
+                         "env FusedMLPActor.sample_env covers (FusedMLPActor.observe_supported)")
     E, N = env.nb_envs, env.nb_houses
     if per_agent and len(actor) != N:
         raise ValueError("collect_maddpg_transitions: %d actors for %d agents" % (len(actor), N))
@@ -495,10 +517,15 @@ def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int
     a_prob = torch.empty(E * N, dtype=torch.float32, device=dev) if fused is not None else None
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
-    env.obs_vector("rows", out=state[0])
+    if not observe_act or T == 0:
+        env.obs_vector("rows", out=state[0])
     for t in range(T):
         if t < int(random_steps_left):
+            if observe_act:
+                env.obs_vector("rows", out=state[t])
             act.copy_(torch.randint(0, 2, (E * N,), device=dev, generator=gen, dtype=torch.uint8))
+        elif observe_act:      # normStateDict + act in one kernel: no row kernel, state[t] written on the side
+            fused.sample_env(env, seed, env.steps_taken, action=act, a_prob=a_prob, rows_out=state[t])
         elif fused is not None:
             fused.sample(state[t].view(E * N, F_len), seed, env.steps_taken, action=act, a_prob=a_prob)
         else:
@@ -516,7 +543,8 @@ def collect_maddpg_transitions(env, actor, nb_steps: int, random_steps_left: int
         _, r, _, _ = env.step(act.view(E, N))
         action[t] = act.view(E, N).to(torch.int64)
         reward[t] = r.view(E, N)
-        env.obs_vector("rows", out=state[t + 1])
+        if not observe_act or t == T - 1:
+            env.obs_vector("rows", out=state[t + 1])
     env._exchange_check()
     return {"state": state, "action": action, "reward": reward}
 
@@ -563,11 +591,16 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     all) - or a ready ``FusedActor``: one packed with ``feature_order=FEATURES_OBSERVE`` takes the same one-kernel path, any other
     gets observation rows.  ``observe_act`` concerns a ``FusedTarMACActor`` only: None (default) - ``sample_env`` instead of rows +
     ``sample`` wherever ``observe_supported(env)`` holds, the same actions bit for bit, captured in the graph like the rows path;
-    False - always rows; True - required (ValueError otherwise, and for every other kind of policy).
+    False - always rows; True - required (ValueError otherwise, and for every other kind of policy but the next).  A
+    ``FusedMLPActor`` (MADDPG's 256-unit actor, either precision) or a ``GreedyDDPGActor`` acts on observation rows through ``sample``;
+    for these ``observe_act`` is opt-in: True - ``sample_env`` every step, no observation rows, the same actions bit for bit, captured
+    like the rows path (ValueError for a list of nets, ``backend="torch"`` or an env ``observe_supported`` refuses); None and False -
+    rows (measured: profiles/mlp_actor_observe_README.md).
 
     ``use_graph`` (default: when the env was built with ``graph_mode=True``): the step is captured once in a
     ``torch.cuda.CUDAGraph`` and replayed - the launch-bound regime of small batches."""
     from . import _native as nat
+    from .mlp_actor import FusedMLPActor
     from .policy import FEATURES_OBSERVE
     from .tarmac import FusedTarMACActor, TarMACActor
     from .tarmac_a2c import TarMACA2CPolicy
@@ -589,13 +622,15 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
             raise ValueError("deploy_policy takes Linear(F,H1) - Linear(H1,H2) - Linear(H2,2) networks on the device (or a FusedActor)")
         policy = _fused_policy(policy, dev, policy_precision, observe=_observe_act_supported(env, policy),
                                msg_floats=4 * _observe_senders(env), greedy=greedy)
-    tarmac_observe = _tarmac_observe_act(env, policy, observe_act)
+    mlp_observe = _mlp_observe_act(env, policy, observe_act)
+    tarmac_observe = False if mlp_observe else _tarmac_observe_act(env, policy, observe_act)
     one_kernel = getattr(policy, "feature_order", 0) == FEATURES_OBSERVE
     # a TarMACA2CPolicy carries its message between the steps: two buffers, the comm_out of one step the comm_in of the next
     a2c_comm = [torch.zeros((E, N, policy.comm_size), dtype=torch.float32, device=dev) for _ in range(2)] if a2c else None
-    obs = None if one_kernel or tarmac_observe else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
+    obs = None if one_kernel or tarmac_observe or mlp_observe else torch.empty((E, N, F_len), dtype=torch.float32, device=dev)
     act = torch.empty(E * N, dtype=torch.uint8, device=dev)
-    act_prob = torch.empty(E * N, dtype=torch.float32, device=dev) if tarmac else None      # no allocation inside a captured step
+    act_prob = torch.empty(E * N, dtype=torch.float32, device=dev) if tarmac or mlp_observe else None      # no allocation inside a captured step
+    mlp_kw = {"a_prob": act_prob} if isinstance(policy, FusedMLPActor) else {}      # (a GreedyDDPGActor keeps its own)
     out = {"reward_sum": torch.zeros((E, N), dtype=torch.float32, device=dev),
            "sq_temp_error_sum": torch.zeros(E, dtype=torch.float64, device=dev),
            "sq_signal_error_sum": torch.zeros(E, dtype=torch.float64, device=dev)}
@@ -613,6 +648,8 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     def one_step(t):
         if one_kernel:       # normStateDict + act for all agents in one kernel: no observation rows
             policy.sample_env(env, seed, step0 + t, action=act, step_dev=step_dev)
+        elif mlp_observe:    # the 256-unit actor fed from the compact state: no observation rows either
+            policy.sample_env(env, seed, step0 + t, action=act, step_dev=step_dev, **mlp_kw)
         elif tarmac_observe:  # the fused TarMAC chain fed from the compact state: no observation rows either
             policy.sample_env(env, seed, step0 + t, step_dev=step_dev, greedy=greedy, action=act, a_prob=act_prob)
         elif a2c:            # MultiAgentPolicy.act (agents/tarmac/model.py:169-178); zeros before the first step, as after a reset
