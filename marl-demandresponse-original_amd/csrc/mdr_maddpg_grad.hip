@@ -389,11 +389,13 @@ __global__ __launch_bounds__(64 * WW) void k_maddpg_weights(WeightArgs a) {
   const int NF = a.N * a.F;
   for (int blk = blockIdx.x * WW + w; blk < total; blk += gridDim.x * WW) {
     if (blk == total - 1) {
-      // the loss: 64 strided sums, added in lane order
+      // the loss: 64 strided sums, added as a tree across the lanes (every lane ends on the same sum).  A chain in lane order
+      // carried the rounding of a running sum B times the mean term: off by two float32 spacings of the loss at B = 24, where
+      // torch's pairwise mean is within a third of one (profiles/learner_golden_README.md)
       float s = 0.0f;
       for (int64_t r = lane; r < a.B; r += 64) s += a.term[r];
-      float sum = 0.0f;
-      for (int l = 0; l < 64; ++l) sum += __shfl(s, l);
+      float sum = s;
+      for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
       if (lane == 0) *a.loss = a.B > 0 ? sum / (float)a.B : 0.0f;
       continue;
     }

@@ -22,6 +22,11 @@ Places that leave the reference's text on purpose:
   setting, which every checkpoint of ``saveDDPGDict`` holds: one actor, critic and target of each PER AGENT.  Acting then goes
   through ``FusedMLPActors`` and the target's picks through ``mdr_maddpg_target_agents`` (agent k's next action from agent k's own
   target actor); the critic's and the actor's step read agent a's nets alone and use the same kernels as the shared mode.
+* ``MADDPG.update_target`` calls ``agent.update_target()`` once per entry of ``self.agents`` (ddpg.py:300-303): nets that several
+  entries alias are blended once PER ALIASING ENTRY and update - with two agents, where the sharing block above does share
+  everything, twice: to <- (1 - tau)^2 to + (1 - (1 - tau)^2) from.  ``MADDPGLearner(shared=True)`` blends its one pair of targets
+  once per update with ``soft_tau``; ``soft_tau = 2 tau - tau^2`` reproduces the reference's two-agent run (tests/learner_golden.py:
+  ``stated_relation``).  Unshared nets are blended once each, as in the reference.
 * There is no terminal mask, as in ``mdr_dqn_target``: the reference's env never ends.
 * The actor step does not write the critic's ``.grad``.  The reference pollutes it and zeroes it before its next use: unobservable.
 * The clip norm is the literal 0.5 of ddpg.py:157 and :163; ``DDPG_prop["max_grad_norm"]`` is read by nobody in the reference.

@@ -6,6 +6,15 @@ device.  Its actor step is PPO's line for line (mappo.py:92-110), so ``ppo.actor
 forward, F.mse_loss and backward of that critic in ONE HIP kernel, which gathers the other agents' actions of a transition from the
 ``action`` buffer while it stages the tile (they are the transition's env-mates): the int64 [T, E N, N - 1] ``others_actions`` tensor is
 neither read nor needed.  ``MAPPOLearner`` is the loop; clipping and Adam stay torch.  Nothing on the call path synchronises.
+
+Places that leave the reference's text on purpose:
+
+* ``MAPPO.update`` runs ONE ``Gt`` recursion over its flat buffer (mappo.py:68-74), which train_mappo.py:86 fills step by step with the
+  agents interleaved: within an episode the return of agent k at step t continues with agent k + 1's reward of the SAME step (agent
+  N - 1's with agent 0's of the next), so one step's N rewards are discounted against each other N times per step.  Here
+  ``batch["return"]`` is ``rollout.discounted_returns`` along time for each agent's own rewards, as in PPO - what the reference
+  computes when the same transitions are stored agent by agent.  ``MAPPOLearner.update`` itself takes ``batch["return"]`` as given:
+  fed the reference's storage-order ``Gt`` it reproduces the reference's update (tests/test_learner_golden.py pins both).
 """
 from __future__ import annotations
 

@@ -131,7 +131,16 @@ def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_pr
                                            C.c_float(clip_param), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(step & (2 ** 64 - 1)), max_workgroups,
                                            L.ptr(ws), L.ptr(flat), L.ptr(loss), L.ptr(ratio), L.stream(dev))
     nat.check(lib, None, rc, "mdr_tarmac_ppo_actor_grad")
-    L.publish(_params(actor), flat, L.KEEP)
+    params = _params(actor)
+    if actor.with_comm:
+        # hidden2key's last bias adds q_i . b to every score of receiver i: the softmax over its senders does not see it, and the
+        # reference's autograd returns exact zeros for it.  The kernels' sums leave 1e-9 of rounding there, which Adam - dividing by
+        # |g| + 1e-8 - turns into a tenth of a learning rate per step on a parameter the reference never moves
+        # (profiles/learner_golden_README.md).  The identically vanishing gradient is written as what it is.
+        at = [id(p) for p in params].index(id(actor.comm.hidden2key[2].bias))
+        off = sum(p.numel() for p in params[:at])
+        flat[off:off + params[at].numel()].zero_()
+    L.publish(params, flat, L.KEEP)
     return (loss, ratio) if want_ratio else loss
 
 
