@@ -648,6 +648,44 @@ int mdr_maddpg_target_agents(const mdr_mlp_t *tgt_actors, int32_t nb_nets, const
                              int32_t agent, const float *noise, float tau, float gamma, int32_t max_workgroups, float *y,
                              float *next_q, uint8_t *next_action, void *stream);
 
+/* ---- The update of ALL agents in one pass, one actor, critic and target of each per agent.  With unshared nets the N steps of one
+ * MADDPG.update() do not depend on each other: agent a's critic step reads critics[a], tgt_critics[a] and every tgt_actors[k] as the
+ * PREVIOUS update left it, its actor step actors[a] and the stepped critics[a], and the targets are blended after the loop
+ * (ddpg.py:300-339).  So the three calls below take the agent as a grid axis: tile t of a row pass is tile t mod TB of agent t / TB's
+ * own minibatch (TB = ceil(nb_rows / 16)) and a weight-pass block's agent is the grid's y - N times the workgroups per launch, two
+ * launches per call.  The nets of a kind are HOST arrays of nb_agents <= MDR_MAX_AGENT_NETS descriptors of one shape (the limits of
+ * mdr_maddpg_target); their pointers travel in the kernel argument block (32 x 12 pointers = 3 KB), so nothing is allocated or owned
+ * and a captured call stays valid while the tensors stay put.  The per-agent arrays are those mdr_maddpg_draws writes and their like:
+ * `index` int64 [N][nb_rows] (required), the target's `noise` [N][nb_rows][N][2], the actor's [N][nb_rows][2], `y`, `next_q`, `q`
+ * [N][nb_rows], `logits` [N][nb_rows][2], `next_action` uint8 [N][nb_rows][N], `grad` [N][mdr_maddpg_grad_floats], `loss` [N];
+ * `workspace`: N times the single call's, 16-byte aligned (mdr_maddpg_workspace_bytes_all; agent a's part starts a whole share in).
+ *
+ * Slice a of every output holds, bit for bit, what mdr_maddpg_target_agents (agent = a, tgt_critics[a]), mdr_maddpg_critic_grad
+ * (critics[a]) and mdr_maddpg_actor_grad (actors[a], critics[a], agent = a) write on index[a], noise[a], y[a], whatever
+ * max_workgroups: a tile's work, the weight pass's sums in row order and the loss wave are the single calls' own code and none of
+ * them knows the grid.  max_workgroups bounds the row pass's grid and, in the weight pass, the workgroups of ONE agent.
+ * Stream-ordered, never synchronises.  Returns as mdr_maddpg_target_agents: 0; -1 (a NULL argument other than next_q / q / logits, a
+ * struct_size that is not this header's, nb_agents < 1, shapes that do not fit each other (critic inputs != nb_agents (F + 2)),
+ * nb_rows < 0, max_workgroups < 0, ld_state < nb_agents F, tau <= 0 or not finite, a workspace that is not 16-byte aligned); -3 (HIP
+ * error); -4 (nb_agents > MDR_MAX_AGENT_NETS, nets of differing shapes, a shape outside the limits).  On -1 and -4 nothing was
+ * launched and nothing written.  nb_rows == 0: as the single calls (the target launches nothing; the gradients are zeros, the
+ * losses 0). */
+int64_t mdr_maddpg_workspace_bytes_all(const mdr_mlp_t *actor, const mdr_mlp_t *critic, int32_t nb_agents, int64_t nb_rows,
+                                       int32_t max_workgroups);
+/* Launch one: every agent's picks for all N minibatches - mdr_maddpg_target_agents' pick launch over the N nb_rows concatenated rows
+ * (a row's pick does not depend on its tile, so these tiles may straddle minibatches).  Launch two: y[a] = reward[:, a] + gamma
+ * tgt_critics[a](next states, picks) on minibatch a. */
+int mdr_maddpg_target_all(const mdr_mlp_t *tgt_actors, const mdr_mlp_t *tgt_critics, const float *next_state, int64_t ld_state,
+                          const float *reward, const int64_t *index, int64_t nb_rows, int32_t nb_agents, const float *noise, float tau,
+                          float gamma, int32_t max_workgroups, float *y, float *next_q, uint8_t *next_action, void *stream);
+int mdr_maddpg_critic_grad_all(const mdr_mlp_t *critics, const float *state, int64_t ld_state, const int64_t *action,
+                               const int64_t *index, int64_t nb_rows, int32_t nb_agents, const float *y, int32_t max_workgroups,
+                               void *workspace, float *grad, float *loss, float *q, void *stream);
+int mdr_maddpg_actor_grad_all(const mdr_mlp_t *actors, const mdr_mlp_t *critics, const float *state, int64_t ld_state,
+                              const int64_t *action, const int64_t *index, int64_t nb_rows, int32_t nb_agents, const float *noise,
+                              float tau, float pse, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *q,
+                              float *logits, void *stream);
+
 /* ---- TarMAC-PPO's update step for the actor (TarmacPPO.update, agents/tarmac_ppo.py:168-186): loss and gradient of one minibatch.
  *
  * The actor's weights in torch's own layout - every layer w[out][in] contiguous and its bias, device memory, read as they are on
@@ -923,6 +961,26 @@ int mdr_adam_corrections(double lr, double beta1, double beta2, int64_t first_st
 int mdr_adam_step_table(const mdr_adam_segments_t *segments, float *exp_avg, float *exp_avg_sq, double lr, double beta1, double beta2,
                         double eps, const float *corrections, int32_t slot, const int32_t *base_dev, double max_grad_norm,
                         double grad_clamp, double tau, void *workspace, float *total_norm_out, int32_t max_fused_floats, void *stream);
+
+/* mdr_adam_step for N nets at once - the N critics, then the N actors of MADDPG's per-agent networks: clip and Adam of all of them in
+ * at most two launches, every net with its own total norm, its own clip and its own target blend.  One net's segment records are
+ * 1.5 KB, so those of N nets live in a device TABLE the caller owns: mdr_adam_nets_table_bytes(nb_nets) bytes, 16-byte aligned.
+ * mdr_adam_nets_bind writes record `net` (0 <= net < the nb_nets the table was sized for - the library cannot check that) from
+ * `segments` (mdr_adam_step's own table, a NULL grad a dead segment, targets NULL or all set) and the net's two moment buffers: one
+ * small launch whose values are its kernel arguments, stream-ordered; call it once per net and again only when an address changes.
+ * mdr_adam_step_nets steps the nets 0 .. nb_nets - 1 of the table with one set of hyper-parameters and ONE step count (nets at
+ * different counts take mdr_adam_step each): launch one writes the chunk sums of every net to `workspace` (nb_nets x
+ * mdr_adam_workspace_bytes(max_net_floats) bytes, 16-byte aligned; skipped with neither clip nor total_norm_out), launch two adds
+ * each net's own chunk sums in chunk order and steps it.  `max_net_floats`: an upper bound of the floats of every bound net (it sizes
+ * the grid and the workspace's shares; a net bound with more chunks than a share holds is left untouched).  tau > 0 blends the nets
+ * bound with targets.  `total_norm_out`: float [nb_nets] or NULL.  The chunks, the sums and the element's expressions are
+ * mdr_adam_step's, so every net's parameters, moments, targets and norm are, bit for bit, those of mdr_adam_step on that net alone.
+ * Return codes as mdr_adam_step; nb_nets == 0 returns 0. */
+int64_t mdr_adam_nets_table_bytes(int32_t nb_nets);
+int mdr_adam_nets_bind(void *table, int32_t net, const mdr_adam_segments_t *segments, float *exp_avg, float *exp_avg_sq, void *stream);
+int mdr_adam_step_nets(const void *table, int32_t nb_nets, int64_t max_net_floats, double lr, double beta1, double beta2, double eps,
+                       int64_t step, double max_grad_norm, double grad_clamp, double tau, void *workspace, float *total_norm_out,
+                       void *stream);
 
 /* ---- Minibatch indices drawn on the device (csrc/mdr_minibatch.hip), so that a whole update can be captured into a graph.
  *

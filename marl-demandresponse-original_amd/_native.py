@@ -182,7 +182,7 @@ class MdrTarmacA2CNet(C.Structure):
 
 
 MDR_ADAM_MAX_SEGMENTS = 32
-MDR_MAX_AGENT_NETS = 32      # include/mdr_policy.h: nets per call of mdr_mlp_actors_sample / mdr_maddpg_target_agents
+MDR_MAX_AGENT_NETS = 32      # include/mdr_policy.h: nets per call of mdr_mlp_actors_sample / mdr_maddpg_target_agents / mdr_maddpg_*_all
 MDR_MADDPG_DRAWS_MAX_AGENTS = 426      # include/mdr_policy.h: agents per call of mdr_maddpg_draws
 
 
@@ -222,10 +222,12 @@ EXPORTS = (
     "mdr_maddpg_grad_floats", "mdr_maddpg_workspace_bytes", "mdr_maddpg_target", "mdr_maddpg_critic_grad", "mdr_maddpg_actor_grad",
     "mdr_mlp_actor_sample", "mdr_mlp_actor_sample_bf16x3", "mdr_mlp_actors_sample", "mdr_maddpg_target_agents",
     "mdr_env_mlp_actor_sample", "mdr_env_mlp_actor_sample_bf16x3",
+    "mdr_maddpg_workspace_bytes_all", "mdr_maddpg_target_all", "mdr_maddpg_critic_grad_all", "mdr_maddpg_actor_grad_all",
     "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
     "mdr_tarmac_critic_grad_floats", "mdr_tarmac_critic_workspace_bytes", "mdr_tarmac_critic_value", "mdr_tarmac_critic_grad",
     "mdr_tarmac_a2c_grad_floats", "mdr_tarmac_a2c_workspace_bytes", "mdr_tarmac_a2c_forward", "mdr_tarmac_a2c_comm", "mdr_tarmac_a2c_grad",
     "mdr_adam_workspace_bytes", "mdr_adam_step", "mdr_adam_step_table", "mdr_adam_corrections",
+    "mdr_adam_nets_table_bytes", "mdr_adam_nets_bind", "mdr_adam_step_nets",
     "mdr_minibatch_permutation", "mdr_minibatch_permutation_keyed", "mdr_minibatch_sample", "mdr_minibatch_sample_keyed",
     "mdr_update_cursor_set", "mdr_update_cursor_add", "mdr_maddpg_draws", "mdr_maddpg_draws_keyed",
 )
@@ -356,6 +358,13 @@ def load():
         "mdr_mlp_actors_sample": (C.c_int, [C.POINTER(MdrMlp), i32, vp, i64, i64, u64, u64, vp, i32, i32, vp, vp, vp, vp]),
         "mdr_maddpg_target_agents": (C.c_int, [C.POINTER(MdrMlp), i32, C.POINTER(MdrMlp), vp, i64, vp, vp, i64, i32, i32, vp, C.c_float,
                                                C.c_float, i32, vp, vp, vp, vp]),
+        # all agents in one pass: host arrays of one descriptor per agent, no `agent` argument
+        "mdr_maddpg_workspace_bytes_all": (i64, [C.POINTER(MdrMlp), C.POINTER(MdrMlp), i32, i64, i32]),
+        "mdr_maddpg_target_all": (C.c_int, [C.POINTER(MdrMlp), C.POINTER(MdrMlp), vp, i64, vp, vp, i64, i32, vp, C.c_float, C.c_float, i32,
+                                            vp, vp, vp, vp]),
+        "mdr_maddpg_critic_grad_all": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "mdr_maddpg_actor_grad_all": (C.c_int, [C.POINTER(MdrMlp), C.POINTER(MdrMlp), vp, i64, vp, vp, i64, i32, vp, C.c_float, C.c_float,
+                                                i32, vp, vp, vp, vp, vp, vp]),
         "mdr_tarmac_critic_grad_floats": (i64, [C.POINTER(MdrMlp)]),
         "mdr_tarmac_critic_workspace_bytes": (i64, [C.POINTER(MdrMlp), i64, i32]),
         "mdr_tarmac_critic_value": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, i32, vp, vp]),
@@ -376,6 +385,10 @@ def load():
         "mdr_adam_step_table": (C.c_int, [C.POINTER(MdrAdamSegments), vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, i32, vp,
                                           C.c_double, C.c_double, C.c_double, vp, vp, i32, vp]),
         "mdr_adam_corrections": (C.c_int, [C.c_double, C.c_double, C.c_double, i64, i64, vp]),
+        "mdr_adam_nets_table_bytes": (i64, [i32]),
+        "mdr_adam_nets_bind": (C.c_int, [vp, i32, C.POINTER(MdrAdamSegments), vp, vp, vp]),
+        "mdr_adam_step_nets": (C.c_int, [vp, i32, i64, C.c_double, C.c_double, C.c_double, C.c_double, i64, C.c_double, C.c_double, C.c_double,
+                                         vp, vp, vp]),
         "mdr_minibatch_permutation": (C.c_int, [i64, u64, u64, vp, vp, vp]),
         "mdr_minibatch_permutation_keyed": (C.c_int, [i64, vp, u64, vp, vp, vp]),
         "mdr_minibatch_sample": (C.c_int, [i64, vp, i64, u64, u64, vp, vp, vp]),

@@ -20,6 +20,10 @@
 //                grid.  The first layer's input is gathered again from `state` / `action` through `index`, never stored.  The blocks
 //                of column 0 also take the bias (the same product against ones); one more wave sums the loss terms.
 //
+// With one net of a kind per agent (mdr_maddpg_target_all, mdr_maddpg_critic_grad_all, mdr_maddpg_actor_grad_all) both passes take the
+// agent as a grid axis - row-pass tile t is tile t mod TB of agent t / TB, a weight-pass block's agent is blockIdx.y - and run the
+// same bodies on that agent's slices: N times the workgroups per launch, the bits of the N single-agent calls.
+//
 // Exact fp32 on v_mfma_f32_16x16x4_f32 (A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15], C/D: col = l & 15, row = 4 (l >> 4) +
 // reg).  relu'(z) = 1 iff z > 0 iff relu(z) > 0, so the backward reads the activations, not z.  Rows past the minibatch are forwarded as
 // zero inputs and given zero dlogits: they add exact zeros.  The 1 / B of the mean sits in dlogits, as autograd has it.
@@ -55,7 +59,21 @@ struct Net {
 };
 
 // MODE_PICK_AGENTS: the picks with one target actor per agent (mdr_maddpg_target_agents) - tiles of 16 minibatch rows of ONE agent
-enum Mode : int { MODE_PICK = 0, MODE_TARGET = 1, MODE_CRITIC = 2, MODE_ACTOR = 3, MODE_PICK_AGENTS = 4 };
+// MODE_*_ALL: the target critic, the critic's step and the actor's step of ALL agents in one launch, one net of a kind per agent
+// (mdr_maddpg_target_all, mdr_maddpg_critic_grad_all, mdr_maddpg_actor_grad_all): tile t is tile t mod TB of agent t / TB's own
+// minibatch and does what the mode without _ALL does for that agent on that agent's slices - the same instructions, hence the same bits
+enum Mode : int {
+  MODE_PICK = 0,
+  MODE_TARGET = 1,
+  MODE_CRITIC = 2,
+  MODE_ACTOR = 3,
+  MODE_PICK_AGENTS = 4,
+  MODE_TARGET_ALL = 5,
+  MODE_CRITIC_ALL = 6,
+  MODE_ACTOR_ALL = 7
+};
+constexpr bool all_agents(Mode m) { return m >= MODE_TARGET_ALL; }
+constexpr Mode per_agent_mode(Mode m) { return all_agents(m) ? (Mode)(m - MODE_TARGET_ALL + MODE_TARGET) : m; }
 
 struct RowArgs {
   Net actor, critic;
@@ -85,10 +103,24 @@ struct PickAgentsArgs {
   int64_t TB;      // tiles per agent: ceil(B / 16)
   NetPtrs nets[MDR_MAX_AGENT_NETS];
 };
+// MODE_*_ALL: r holds what the agents share (the shapes in r.actor / r.critic, the buffer, B, the scalars) and the bases of the
+// per-agent arrays - index [N][B], noise [N][B][2], y / q [N][B], logits [N][B][2], picks [N][B][N], the workspace images, each
+// agent's ws floats apart; agent a's tiles shift them by a.  critics: the net the critic's input goes through (TARGET_ALL: the
+// target critics); actors: MODE_ACTOR_ALL only.  12 x 32 pointers and r: 3.4 KB of the 4 KB argument block
+struct AllAgentsArgs {
+  RowArgs r;
+  int64_t TB;      // tiles per agent: ceil(B / 16)
+  int64_t ws;      // floats of one agent's workspace
+  NetPtrs critics[MDR_MAX_AGENT_NETS];
+  NetPtrs actors[MDR_MAX_AGENT_NETS];
+};
 template <Mode MODE>
 using ArgsOf = std::conditional_t<MODE == MODE_PICK_AGENTS, PickAgentsArgs, RowArgs>;
 __host__ __device__ __forceinline__ const RowArgs& row_args(const RowArgs& a) { return a; }
 __host__ __device__ __forceinline__ const RowArgs& row_args(const PickAgentsArgs& a) { return a.r; }
+__host__ __device__ __forceinline__ const RowArgs& row_args(const AllAgentsArgs& a) { return a.r; }
+
+__device__ __forceinline__ void set_ptrs(Net& n, const NetPtrs& p) { n.w1 = p.w1, n.b1 = p.b1, n.w2 = p.w2, n.b2 = p.b2, n.w3 = p.w3, n.b3 = p.b3; }
 
 // the wave's share of two dot products over its block of vT: sum_u coef_o[u * su] vT[u][row c] -> lp[w][row][o]
 __device__ __forceinline__ void dot2_share(const float* vT, const float* __restrict__ coef0, const float* __restrict__ coef1, int64_t su, int H, float* lp,
@@ -122,9 +154,12 @@ __device__ __forceinline__ void dot2_sum(const float* lp, int nb, int c, float& 
   }
 }
 
-template <Mode MODE>
-__global__ __launch_bounds__(64 * NW) void k_maddpg_rows(ArgsOf<MODE> args) {
-  const RowArgs& a = row_args(args);
+// the tiles blockIdx.x, + gridDim.x, ... of a row pass: the body of k_maddpg_rows and k_maddpg_rows_all
+template <Mode FULL, class Args>
+__device__ __forceinline__ void maddpg_rows(const Args args) {
+  constexpr Mode MODE = per_agent_mode(FULL);      // what a tile does
+  constexpr bool ALL = all_agents(FULL);           // ... for the agent the tile belongs to
+  const RowArgs& a0 = row_args(args);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
   float* xT = lds + S_X;
@@ -140,12 +175,39 @@ __global__ __launch_bounds__(64 * NW) void k_maddpg_rows(ArgsOf<MODE> args) {
   constexpr bool PICKS = MODE == MODE_PICK || AGENTS;
   constexpr bool HAS_ACTOR = PICKS || MODE == MODE_ACTOR;
   constexpr bool HAS_CRITIC = !PICKS;
-  const Net& A0 = a.actor;
-  const Net& Cn = a.critic;
-  const int NF = a.N * a.F;
+  const int NF = a0.N * a0.F;
 
-  for (int64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-    int64_t row = t * TILE + c;      // the row this lane's MFMA column and head work belong to
+  for (int64_t t = blockIdx.x; t < a0.ntiles; t += gridDim.x) {
+    int64_t tl = t;                  // the tile's number among the tiles of its rows
+    [[maybe_unused]] RowArgs mine;   // ALL: the arguments of the tile's agent
+    const RowArgs* ap = &a0;
+    if constexpr (ALL) {
+      // agent ag's tile tl: every per-agent array shifted to slice ag, the nets' pointers from the tables - read through the
+      // argument block's own address, as MODE_PICK_AGENTS reads its table
+      const int ag = (int)(t / args.TB);
+      tl = t - ag * args.TB;
+      mine = a0;
+      const char* seg = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+      set_ptrs(mine.critic, reinterpret_cast<const NetPtrs*>(seg + offsetof(AllAgentsArgs, critics))[ag]);
+      if constexpr (MODE == MODE_ACTOR) set_ptrs(mine.actor, reinterpret_cast<const NetPtrs*>(seg + offsetof(AllAgentsArgs, actors))[ag]);
+      const int64_t o = ag * a0.B;
+      mine.agent = ag;
+      mine.index += o;
+      if constexpr (MODE == MODE_TARGET) mine.picks += o * a0.N, mine.out0 += o;
+      if constexpr (MODE == MODE_CRITIC) mine.y += o;
+      if constexpr (MODE == MODE_ACTOR) mine.noise += 2 * o;
+      if (MODE != MODE_TARGET && mine.out0) mine.out0 += o;
+      if (mine.out1) mine.out1 += MODE == MODE_ACTOR ? 2 * o : o;
+      if constexpr (MODE != MODE_TARGET) {
+        const int64_t wo = ag * args.ws;
+        mine.h1 += wo, mine.dz1 += wo, mine.h2 += wo, mine.dz2 += wo, mine.dl += wo, mine.term += wo;
+      }
+      ap = &mine;
+    }
+    const RowArgs& a = *ap;
+    const Net& A0 = a.actor;
+    const Net& Cn = a.critic;
+    int64_t row = tl * TILE + c;     // the row this lane's MFMA column and head work belong to
     bool valid = row < a.R;
     Net A = A0;
     [[maybe_unused]] int kt = 0;         // AGENTS: the tile's agent and its first minibatch row
@@ -168,7 +230,7 @@ __global__ __launch_bounds__(64 * NW) void k_maddpg_rows(ArgsOf<MODE> args) {
       // ---- the actor's input: F floats of agent k of env-step j
       for (int e = tid; e < TILE * MAX_F; e += 64 * NW) {
         const int r = e / MAX_F, f = e - r * MAX_F;
-        const int64_t rr = t * TILE + r;
+        const int64_t rr = tl * TILE + r;
         float v = 0.0f;
         if (f < a.F && (AGENTS ? i0 + r < a.B : rr < a.R)) {
           const int64_t i = AGENTS ? i0 + r : MODE == MODE_PICK ? rr / a.N : rr;
@@ -236,7 +298,7 @@ __global__ __launch_bounds__(64 * NW) void k_maddpg_rows(ArgsOf<MODE> args) {
         __syncthreads();      // the chunk before (or the actor's input, or pk) is read
         for (int e = tid; e < TILE * KC; e += 64 * NW) {
           const int r = e / KC, f = e - r * KC, col = k0 + f;
-          const int64_t rr = t * TILE + r;
+          const int64_t rr = tl * TILE + r;
           float v = 0.0f;
           if (col < J && rr < a.B) {
             const int64_t j = a.index ? a.index[rr] : rr;
@@ -365,6 +427,16 @@ __global__ __launch_bounds__(64 * NW) void k_maddpg_rows(ArgsOf<MODE> args) {
   }
 }
 
+template <Mode MODE>
+__global__ __launch_bounds__(64 * NW) void k_maddpg_rows(ArgsOf<MODE> args) {
+  maddpg_rows<MODE>(args);
+}
+
+template <Mode MODE>
+__global__ __launch_bounds__(64 * NW) void k_maddpg_rows_all(AllAgentsArgs args) {
+  maddpg_rows<MODE>(args);
+}
+
 // ---- the weight pass
 struct WeightArgs {
   int K, H1, H2, O;            // of the net whose gradient is taken
@@ -381,7 +453,8 @@ struct WeightArgs {
   int nbk, nb1, nb2;           // 16-blocks of K, H1, H2
 };
 
-__global__ __launch_bounds__(64 * WW) void k_maddpg_weights(WeightArgs a) {
+// the blocks blockIdx.x * WW + wave, + gridDim.x * WW, ... of the gradient `a` describes
+__device__ __forceinline__ void weight_blocks(const WeightArgs a) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int n1 = a.nb1 * a.nbk, n2 = a.nb2 * a.nb1, n3 = a.nb2;
   const int total = n1 + n2 + n3 + 1;
@@ -449,6 +522,28 @@ __global__ __launch_bounds__(64 * WW) void k_maddpg_weights(WeightArgs a) {
   }
 }
 
+__global__ __launch_bounds__(64 * WW) void k_maddpg_weights(WeightArgs a) { weight_blocks(a); }
+
+// the weight pass of all agents (mdr_maddpg_critic_grad_all, mdr_maddpg_actor_grad_all): blockIdx.y is the agent; its workspace, its
+// minibatch, its slice of grad [N][G] and of loss [N] lie one stride each behind agent 0's, which `w` describes
+struct WeightAllArgs {
+  WeightArgs w;
+  int64_t ws, G;      // floats of one agent's workspace and of one gradient
+  int actor;          // the actor's step: agent y's input is its own F floats (WeightArgs::agent = y)
+};
+
+__global__ __launch_bounds__(64 * WW) void k_maddpg_weights_all(WeightAllArgs b) {
+  const int64_t y = blockIdx.y;
+  WeightArgs a = b.w;
+  const int64_t wo = y * b.ws;
+  a.h1 += wo, a.h2 += wo, a.dz1 += wo, a.dz2 += wo, a.dl += wo, a.term += wo;
+  a.index += y * a.B;
+  a.agent = b.actor ? (int)y : -1;
+  a.grad += y * b.G;
+  a.loss += y;
+  weight_blocks(a);
+}
+
 bool fields_ok(const mdr_mlp_t* n) {
   return n && n->struct_size == sizeof(mdr_mlp_t) && n->num_state > 0 && n->hidden1 > 0 && n->hidden2 > 0 && n->num_out > 0;
 }
@@ -479,14 +574,17 @@ int64_t ws_floats(const mdr_mlp_t* n, int64_t nb_rows) {
   return Bp * (2 * pad16(n->hidden1) + 2 * pad16(n->hidden2) + 3);
 }
 
-template <Mode MODE>
-int launch_rows(const ArgsOf<MODE>& args, int cap, hipStream_t st) {
+template <Mode MODE, class Args>
+int launch_rows(const Args& args, int cap, hipStream_t st) {
   const RowArgs& a = row_args(args);
   const size_t bytes = (size_t)S_END * sizeof(float);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_maddpg_rows<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+  void (*kernel)(Args);
+  if constexpr (all_agents(MODE)) kernel = k_maddpg_rows_all<MODE>;
+  else kernel = k_maddpg_rows<MODE>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
     return MDR_ERR_HIP;
   const int64_t grid = a.ntiles < cap ? a.ntiles : cap;
-  hipLaunchKernelGGL(k_maddpg_rows<MODE>, dim3((unsigned)grid), dim3(64 * NW), bytes, st, args);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * NW), bytes, st, args);
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
@@ -513,6 +611,40 @@ int launch_weights(const WeightArgs& wa, int cap, hipStream_t st) {
   hipLaunchKernelGGL(k_maddpg_weights, dim3((unsigned)grid), dim3(64 * WW), 0, st, wa);
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
+
+int launch_weights_all(const WeightAllArgs& b, int nb_agents, int cap, hipStream_t st) {
+  const int total = b.w.nb1 * b.w.nbk + b.w.nb2 * b.w.nb1 + b.w.nb2 + 1;
+  int grid = (total + WW - 1) / WW;
+  if (cap > 0 && grid > cap) grid = cap;      // max_workgroups bounds the workgroups of ONE agent here: the agent is the grid's y
+  hipLaunchKernelGGL(k_maddpg_weights_all, dim3((unsigned)grid, (unsigned)nb_agents), dim3(64 * WW), 0, st, b);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+// The nets of the _all calls, one of a kind per agent, 1 <= nb_agents <= MDR_MAX_AGENT_NETS (actors may be null: the critic's step).
+// MDR_ERR_INVALID: a refusal; otherwise pair_shape of agent 0's pair, for the caller to return after its own argument checks
+int all_fields(const mdr_mlp_t* actors, const mdr_mlp_t* critics, int32_t nb_agents) {
+  for (int k = 0; k < nb_agents; ++k)
+    if ((actors && !fields_ok(&actors[k])) || !fields_ok(&critics[k])) return MDR_ERR_INVALID;
+  const int rc = pair_shape(actors ? &actors[0] : nullptr, &critics[0], nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  for (int k = 0; k < nb_agents; ++k)
+    if ((actors && !pointers_ok(&actors[k])) || !pointers_ok(&critics[k])) return MDR_ERR_INVALID;
+  return rc;
+}
+
+bool one_shape(const mdr_mlp_t* nets, int32_t nb) {
+  for (int k = 1; k < nb; ++k) {
+    const mdr_mlp_t &n = nets[k], &n0 = nets[0];
+    if (n.num_state != n0.num_state || n.hidden1 != n0.hidden1 || n.hidden2 != n0.hidden2 || n.num_out != n0.num_out) return false;
+  }
+  return true;
+}
+
+void set_table(NetPtrs* table, const mdr_mlp_t* nets, int32_t nb) {
+  for (int k = 0; k < nb; ++k) table[k] = NetPtrs{nets[k].w1, nets[k].b1, nets[k].w2, nets[k].b2, nets[k].w3, nets[k].b3};
+}
+
+static_assert(sizeof(AllAgentsArgs) <= 4096, "the kernel argument block");
 
 }  // namespace
 
@@ -643,6 +775,117 @@ int mdr_maddpg_actor_grad(const mdr_mlp_t* actor, const mdr_mlp_t* critic, const
   wa.state = state, wa.ld = ld_state, wa.action = action, wa.index = index, wa.N = nb_agents, wa.F = F, wa.agent = agent;
   wa.grad = grad, wa.loss = loss;
   return launch_weights(wa, max_workgroups, st);
+}
+
+int64_t mdr_maddpg_workspace_bytes_all(const mdr_mlp_t* actor, const mdr_mlp_t* critic, int32_t nb_agents, int64_t nb_rows, int32_t max_workgroups) {
+  const int64_t one = mdr_maddpg_workspace_bytes(actor, critic, nb_agents, nb_rows, max_workgroups);
+  if (one < 0 || nb_agents > MDR_MAX_AGENT_NETS) return -1;
+  const int64_t fa = ws_floats(actor, nb_rows), fc = ws_floats(critic, nb_rows);
+  const int64_t f = (fa > fc ? fa : fc) * nb_agents;
+  return (f > 4 ? f : 4) * (int64_t)sizeof(float);
+}
+
+int mdr_maddpg_target_all(const mdr_mlp_t* tgt_actors, const mdr_mlp_t* tgt_critics, const float* next_state, int64_t ld_state,
+                          const float* reward, const int64_t* index, int64_t nb_rows, int32_t nb_agents, const float* noise, float tau,
+                          float gamma, int32_t max_workgroups, float* y, float* next_q, uint8_t* next_action, void* stream) {
+  if (!tgt_actors || !tgt_critics || !next_state || !reward || !index || !noise || !y || !next_action || nb_agents < 1) return MDR_ERR_INVALID;
+  if (nb_agents > MDR_MAX_AGENT_NETS) return MDR_ERR_UNSUPPORTED;
+  const int rc = all_fields(tgt_actors, tgt_critics, nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  const int F = tgt_actors[0].num_state;
+  if (nb_rows < 0 || max_workgroups < 0 || ld_state < (int64_t)nb_agents * F) return MDR_ERR_INVALID;
+  if (!(tau > 0.0f) || !(fabsf(tau) <= FLT_MAX) || !(fabsf(gamma) <= FLT_MAX)) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  if (!one_shape(tgt_actors, nb_agents) || !one_shape(tgt_critics, nb_agents)) return MDR_ERR_UNSUPPORTED;
+  if (nb_rows == 0) return MDR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int cap = lib_cap(max_workgroups);
+  // the picks of all N minibatches: mdr_maddpg_target_agents' launch over the N B concatenated rows (a row's pick does not depend on
+  // the tile it sits in, so these tiles may straddle two agents' minibatches)
+  PickAgentsArgs pa{};
+  RowArgs& p = pa.r;
+  p.actor = make_net(&tgt_actors[0]), p.critic = make_net(&tgt_critics[0]);
+  p.state = next_state, p.ld = ld_state, p.index = index, p.B = nb_rows * nb_agents, p.N = nb_agents, p.F = F;
+  p.noise = noise, p.tau = tau, p.gamma = gamma, p.reward = reward, p.picks = next_action;
+  set_table(pa.nets, tgt_actors, nb_agents);
+  pa.TB = (p.B + TILE - 1) / TILE;
+  p.R = p.B * nb_agents, p.ntiles = pa.TB * nb_agents;
+  if (launch_rows<MODE_PICK_AGENTS>(pa, cap, st) != MDR_OK) return MDR_ERR_HIP;
+  // agent a's y from its own target critic on its own minibatch, reward column a
+  AllAgentsArgs aa{};
+  RowArgs& a = aa.r;
+  a = p;
+  a.B = nb_rows, a.out0 = y, a.out1 = next_q;
+  set_table(aa.critics, tgt_critics, nb_agents);
+  aa.TB = (nb_rows + TILE - 1) / TILE;
+  a.R = nb_rows, a.ntiles = aa.TB * nb_agents;
+  return launch_rows<MODE_TARGET_ALL>(aa, cap, st);
+}
+
+int mdr_maddpg_critic_grad_all(const mdr_mlp_t* critics, const float* state, int64_t ld_state, const int64_t* action, const int64_t* index,
+                               int64_t nb_rows, int32_t nb_agents, const float* y, int32_t max_workgroups, void* workspace, float* grad,
+                               float* loss, float* q, void* stream) {
+  if (!critics || !state || !action || !index || !y || !grad || !loss || !workspace || ((uintptr_t)workspace & 15u) || nb_agents < 1)
+    return MDR_ERR_INVALID;
+  if (nb_agents > MDR_MAX_AGENT_NETS) return MDR_ERR_UNSUPPORTED;
+  const int rc = all_fields(nullptr, critics, nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  const int F = critics[0].num_state / nb_agents - 2;
+  if (nb_rows < 0 || max_workgroups < 0 || ld_state < (int64_t)nb_agents * F) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  if (!one_shape(critics, nb_agents)) return MDR_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int cap = lib_cap(max_workgroups);
+  AllAgentsArgs aa{};
+  WeightAllArgs wb{};
+  RowArgs& a = aa.r;
+  WeightArgs& wa = wb.w;
+  carve(a, wa, &critics[0], workspace, nb_rows);      // agent 0's; agent k's lie k ws behind
+  aa.ws = wb.ws = ws_floats(&critics[0], nb_rows), wb.G = grad_floats(&critics[0]), wb.actor = 0;
+  a.critic = make_net(&critics[0]);
+  set_table(aa.critics, critics, nb_agents);
+  a.state = state, a.ld = ld_state, a.action = action, a.index = index, a.B = nb_rows, a.N = nb_agents, a.F = F, a.agent = -1;
+  a.y = y, a.out0 = q, a.invB = nb_rows > 0 ? 1.0f / (float)nb_rows : 0.0f;
+  aa.TB = (nb_rows + TILE - 1) / TILE;
+  a.R = nb_rows, a.ntiles = aa.TB * nb_agents;
+  if (nb_rows > 0 && launch_rows<MODE_CRITIC_ALL>(aa, cap, st) != MDR_OK) return MDR_ERR_HIP;
+  wa.state = state, wa.ld = ld_state, wa.action = action, wa.index = index, wa.N = nb_agents, wa.F = F, wa.agent = -1;
+  wa.grad = grad, wa.loss = loss;
+  return launch_weights_all(wb, nb_agents, max_workgroups, st);
+}
+
+int mdr_maddpg_actor_grad_all(const mdr_mlp_t* actors, const mdr_mlp_t* critics, const float* state, int64_t ld_state, const int64_t* action,
+                              const int64_t* index, int64_t nb_rows, int32_t nb_agents, const float* noise, float tau, float pse,
+                              int32_t max_workgroups, void* workspace, float* grad, float* loss, float* q, float* logits, void* stream) {
+  if (!actors || !critics || !state || !action || !index || !noise || !grad || !loss || !workspace || ((uintptr_t)workspace & 15u) || nb_agents < 1)
+    return MDR_ERR_INVALID;
+  if (nb_agents > MDR_MAX_AGENT_NETS) return MDR_ERR_UNSUPPORTED;
+  const int rc = all_fields(actors, critics, nb_agents);
+  if (rc == MDR_ERR_INVALID) return rc;
+  const int F = actors[0].num_state;
+  if (nb_rows < 0 || max_workgroups < 0 || ld_state < (int64_t)nb_agents * F) return MDR_ERR_INVALID;
+  if (!(tau > 0.0f) || !(fabsf(tau) <= FLT_MAX) || !(fabsf(pse) <= FLT_MAX)) return MDR_ERR_INVALID;
+  if (rc != MDR_OK) return rc;
+  if (!one_shape(actors, nb_agents) || !one_shape(critics, nb_agents)) return MDR_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int cap = lib_cap(max_workgroups);
+  AllAgentsArgs aa{};
+  WeightAllArgs wb{};
+  RowArgs& a = aa.r;
+  WeightArgs& wa = wb.w;
+  carve(a, wa, &actors[0], workspace, nb_rows);
+  aa.ws = wb.ws = ws_floats(&actors[0], nb_rows), wb.G = grad_floats(&actors[0]), wb.actor = 1;
+  a.actor = make_net(&actors[0]), a.critic = make_net(&critics[0]);
+  set_table(aa.actors, actors, nb_agents);
+  set_table(aa.critics, critics, nb_agents);
+  a.state = state, a.ld = ld_state, a.action = action, a.index = index, a.B = nb_rows, a.N = nb_agents, a.F = F;
+  a.noise = noise, a.tau = tau, a.pse = pse, a.out0 = q, a.out1 = logits, a.invB = nb_rows > 0 ? 1.0f / (float)nb_rows : 0.0f;
+  aa.TB = (nb_rows + TILE - 1) / TILE;
+  a.R = nb_rows, a.ntiles = aa.TB * nb_agents;
+  if (nb_rows > 0 && launch_rows<MODE_ACTOR_ALL>(aa, cap, st) != MDR_OK) return MDR_ERR_HIP;
+  wa.state = state, wa.ld = ld_state, wa.action = action, wa.index = index, wa.N = nb_agents, wa.F = F, wa.agent = 0;
+  wa.grad = grad, wa.loss = loss;
+  return launch_weights_all(wb, nb_agents, max_workgroups, st);
 }
 
 }  // extern "C"

@@ -121,8 +121,8 @@ __device__ __forceinline__ float ordered_sum(const float* x, int n) {
 
 // one element: clamp -> coef g -> the moments -> the parameter -> the target, as torch.optim.Adam's defaults (no weight decay, no amsgrad)
 // TABLE: the two bias corrections are `ss` and `bc` (read from the table), otherwise the kernel arguments'
-template <bool TABLE>
-__device__ __forceinline__ void adam_elem(const StepArgs& a, float ss, float bc, float coef, float g, float& p, float& m, float& v, float& t) {
+template <bool TABLE, class Args = StepArgs>
+__device__ __forceinline__ void adam_elem(const Args& a, float ss, float bc, float coef, float g, float& p, float& m, float& v, float& t) {
   g = coef * clampf(g, a.clamp);      // coef == 1 without a clip: exact
   m = a.b1 * m + a.omb1 * g;
   v = a.b2 * v + a.omb2 * (g * g);
@@ -230,6 +230,108 @@ __global__ __launch_bounds__(THREADS) void k_adam_step(const typename ArgsOf<TAB
   }
 }
 
+// ---- N nets in one step (mdr_adam_nets_bind, mdr_adam_step_nets).  One net's segment records are what StepArgs carries by value -
+// 1.5 KB -, so those of N nets live in a device table the caller owns: record `net` is written by k_adam_bind from its kernel
+// arguments and read by every later step until an address changes.  The step is the two-launch form with the net as the grid's y:
+// chunk sums of all nets into the workspace (net y's at y * stride), then every net adds ITS chunk sums in chunk order, takes its
+// own norm and clip and steps its own chunks - chunk_sumsq, ordered_sum and adam_elem as above, hence mdr_adam_step's bits per net.
+struct NetRec {
+  Seg seg[MDR_ADAM_MAX_SEGMENTS];
+  int32_t chunk0[MDR_ADAM_MAX_SEGMENTS + 1];
+  int32_t nseg, nchunks;
+  float* m;
+  float* v;
+};
+static_assert(sizeof(NetRec) % 8 == 0 && sizeof(NetRec) + 8 <= 4096, "a record travels in the kernel argument block, in 8-byte words");
+
+struct NetsArgs {
+  const NetRec* table;
+  const float* partial;      // [nets][stride] chunk sums; NULL without a norm
+  float* norm_out;           // [nets]; may be NULL
+  int32_t stride;            // chunk sums per net the workspace has room for: a net bound with more chunks is left alone
+  float b1, omb1, b2, omb2, step_size, bc2_sqrt, eps, max_norm, clamp, tau, omtau;
+  int32_t do_norm, do_clip, do_blend;
+};
+
+// the record is copied word by word from the argument block's own address (indexing the by-value struct would copy it to private memory)
+__global__ __launch_bounds__(THREADS) void k_adam_bind(const NetRec rec, NetRec* dst) {
+  const uint64_t* src = (const uint64_t*)__builtin_amdgcn_kernarg_segment_ptr();
+  uint64_t* out = reinterpret_cast<uint64_t*>(dst);
+  for (int i = threadIdx.x; i < (int)(sizeof(NetRec) / 8); i += THREADS) out[i] = src[i];
+}
+
+// chunk c = 4 blockIdx.x + wave, + 4 gridDim.x, ... of net blockIdx.y -> partial[y * stride + c]
+__global__ __launch_bounds__(THREADS) void k_adam_sumsq_nets(const NetRec* __restrict__ table, float clamp, float* __restrict__ partial, int32_t stride) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const NetRec& r = table[blockIdx.y];
+  const int nchunks = r.nchunks;
+  if (nchunks > stride) return;
+  for (int c = blockIdx.x * 4 + wave; c < nchunks; c += gridDim.x * 4) {
+    for (int s = 0; s < r.nseg; ++s) {
+      const int c0 = r.chunk0[s], c1 = r.chunk0[s + 1];
+      if (c < c0 || c >= c1) continue;
+      const float* g = r.seg[s].g;
+      const int64_t off = (int64_t)(c - c0) * CHUNK;
+      const float sum = chunk_sumsq(g + off, r.seg[s].n - off, clamp, lane, aligned16(g));
+      if (lane == 0) partial[(int64_t)blockIdx.y * stride + c] = sum;
+    }
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void k_adam_step_nets(const NetsArgs a) {
+  const int tid = threadIdx.x;
+  const NetRec& r = a.table[blockIdx.y];
+  const int nchunks = r.nchunks;
+  if (nchunks > a.stride) return;
+  float coef = 1.0f;
+  if (a.do_norm) {
+    const float ss = ordered_sum(a.partial + (int64_t)blockIdx.y * a.stride, nchunks);
+    const float norm = sqrtf(ss);
+    if (a.norm_out && blockIdx.x == 0 && tid == 0) a.norm_out[blockIdx.y] = norm;
+    if (a.do_clip) {
+      const float c = a.max_norm / (norm + 1e-6f);
+      coef = c > 1.0f ? 1.0f : c;
+    }
+  }
+  const int grid = (int)gridDim.x, b = (int)blockIdx.x;
+  for (int s = 0; s < r.nseg; ++s) {
+    const int c0 = r.chunk0[s], nck = r.chunk0[s + 1] - c0;
+    if (nck == 0) continue;
+    const Seg sg = r.seg[s];
+    float* m = r.m + sg.moff;
+    float* v = r.v + sg.moff;
+    const bool blend = a.do_blend && sg.t;      // a net bound without targets takes no blend
+    const bool vec = aligned16(sg.p) && aligned16(sg.g) && aligned16(m) && aligned16(v) && (!blend || aligned16(sg.t));
+    int k = (b - c0) % grid;
+    if (k < 0) k += grid;
+    for (; k < nck; k += grid) {      // the chunks c0 + k = b (mod grid)
+      const int64_t i = (int64_t)k * CHUNK + 4 * tid;
+      if (i >= sg.n) continue;
+      if (vec && i + 4 <= sg.n) {
+        const float4 g4 = *reinterpret_cast<const float4*>(sg.g + i);
+        float4 p4 = *reinterpret_cast<float4*>(sg.p + i), m4 = *reinterpret_cast<float4*>(m + i), v4 = *reinterpret_cast<float4*>(v + i);
+        float4 t4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (blend) t4 = *reinterpret_cast<float4*>(sg.t + i);
+        adam_elem<false>(a, 0.0f, 1.0f, coef, g4.x, p4.x, m4.x, v4.x, t4.x);
+        adam_elem<false>(a, 0.0f, 1.0f, coef, g4.y, p4.y, m4.y, v4.y, t4.y);
+        adam_elem<false>(a, 0.0f, 1.0f, coef, g4.z, p4.z, m4.z, v4.z, t4.z);
+        adam_elem<false>(a, 0.0f, 1.0f, coef, g4.w, p4.w, m4.w, v4.w, t4.w);
+        *reinterpret_cast<float4*>(sg.p + i) = p4;
+        *reinterpret_cast<float4*>(m + i) = m4;
+        *reinterpret_cast<float4*>(v + i) = v4;
+        if (blend) *reinterpret_cast<float4*>(sg.t + i) = t4;
+      } else {
+        for (int j = 0; j < 4 && i + j < sg.n; ++j) {
+          float p1 = sg.p[i + j], m1 = m[i + j], v1 = v[i + j], t1 = blend ? sg.t[i + j] : 0.0f;
+          adam_elem<false>(a, 0.0f, 1.0f, coef, sg.g[i + j], p1, m1, v1, t1);
+          sg.p[i + j] = p1, m[i + j] = m1, v[i + j] = v1;
+          if (blend) sg.t[i + j] = t1;
+        }
+      }
+    }
+  }
+}
+
 // the two bias corrections of one step: formed in double, one cast to float (mdr_adam_step and mdr_adam_corrections share them)
 float step_size_of(double lr, double beta1, int64_t step) { return (float)(lr / (1.0 - std::pow(beta1, (double)step))); }
 float bc2_sqrt_of(double beta2, int64_t step) { return (float)std::sqrt(1.0 - std::pow(beta2, (double)step)); }
@@ -323,6 +425,62 @@ int mdr_adam_step_table(const mdr_adam_segments_t* segments, float* exp_avg, flo
   if (!corrections || slot < 0) return MDR_ERR_INVALID;
   return adam_step(segments, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, 1, corrections, slot, base_dev, max_grad_norm, grad_clamp, tau,
                    workspace, total_norm_out, max_fused_floats, stream);
+}
+
+int64_t mdr_adam_nets_table_bytes(int32_t nb_nets) { return nb_nets < 0 ? -1 : (int64_t)nb_nets * (int64_t)sizeof(NetRec); }
+
+int mdr_adam_nets_bind(void* table, int32_t net, const mdr_adam_segments_t* segments, float* exp_avg, float* exp_avg_sq, void* stream) {
+  if (!table || ((uintptr_t)table & 15u) || net < 0) return MDR_ERR_INVALID;
+  if (!segments || segments->struct_size != sizeof(mdr_adam_segments_t) || !exp_avg || !exp_avg_sq) return MDR_ERR_INVALID;
+  if (segments->nb_segments < 0) return MDR_ERR_INVALID;
+  if (segments->nb_segments > MDR_ADAM_MAX_SEGMENTS) return MDR_ERR_UNSUPPORTED;
+  NetRec rec{};
+  int64_t total = 0, chunks = 0;
+  for (int s = 0; s < segments->nb_segments; ++s) {      // mdr_adam_step's own table: the same chunks, the same moment offsets
+    const mdr_adam_segment_t& in = segments->seg[s];
+    if (!in.param || in.count < 0) return MDR_ERR_INVALID;
+    rec.seg[s] = Seg{in.param, in.grad, in.target, in.count, total};
+    rec.chunk0[s] = (int32_t)chunks;
+    if (in.grad) chunks += (in.count + CHUNK - 1) / CHUNK;
+    total += in.count;
+    if (chunks > INT32_MAX / 2) return MDR_ERR_UNSUPPORTED;
+  }
+  rec.nseg = segments->nb_segments, rec.nchunks = (int32_t)chunks;
+  rec.chunk0[rec.nseg] = rec.nchunks;
+  rec.m = exp_avg, rec.v = exp_avg_sq;
+  hipLaunchKernelGGL(k_adam_bind, dim3(1), dim3(THREADS), 0, (hipStream_t)stream, rec, static_cast<NetRec*>(table) + net);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+int mdr_adam_step_nets(const void* table, int32_t nb_nets, int64_t max_net_floats, double lr, double beta1, double beta2, double eps, int64_t step,
+                       double max_grad_norm, double grad_clamp, double tau, void* workspace, float* total_norm_out, void* stream) {
+  if (!table || nb_nets < 0 || max_net_floats < 0 || step < 1) return MDR_ERR_INVALID;
+  if (!(lr == lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(tau <= 1.0)) return MDR_ERR_INVALID;
+  if (grad_clamp != grad_clamp || grad_clamp <= 0.0) return MDR_ERR_INVALID;
+  const int64_t stride = workspace_bytes(max_net_floats) / (int64_t)sizeof(float);
+  if (stride > INT32_MAX / 2) return MDR_ERR_UNSUPPORTED;
+  if (nb_nets == 0) return MDR_OK;
+  const bool blend = tau > 0.0;
+  const bool clip = max_grad_norm > 0.0 && !std::isinf(max_grad_norm);
+  NetsArgs a{};
+  a.table = static_cast<const NetRec*>(table), a.norm_out = total_norm_out, a.stride = (int32_t)stride;
+  a.b1 = (float)beta1, a.omb1 = (float)(1.0 - beta1), a.b2 = (float)beta2, a.omb2 = (float)(1.0 - beta2);
+  a.step_size = step_size_of(lr, beta1, step), a.bc2_sqrt = bc2_sqrt_of(beta2, step);
+  a.eps = (float)eps, a.max_norm = (float)max_grad_norm, a.clamp = (float)grad_clamp;
+  a.tau = blend ? (float)tau : 0.0f, a.omtau = blend ? (float)(1.0 - tau) : 0.0f;
+  a.do_clip = clip, a.do_norm = clip || total_norm_out != nullptr, a.do_blend = blend;
+  hipStream_t st = (hipStream_t)stream;
+  // a net of max_net_floats has at most `stride` chunks: one workgroup per chunk of the largest net, as mdr_adam_step launches
+  const int64_t most = max_net_floats / CHUNK + MDR_ADAM_MAX_SEGMENTS;
+  const unsigned grid = (unsigned)(most > MAX_GRID ? MAX_GRID : most);
+  if (a.do_norm) {
+    if (!workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
+    a.partial = static_cast<const float*>(workspace);
+    hipLaunchKernelGGL(k_adam_sumsq_nets, dim3((grid + 3) / 4, (unsigned)nb_nets), dim3(THREADS), 0, st, a.table, a.clamp, static_cast<float*>(workspace),
+                       a.stride);
+  }
+  hipLaunchKernelGGL(k_adam_step_nets, dim3(grid, (unsigned)nb_nets), dim3(THREADS), 0, st, a);
+  return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
 }
 
 int mdr_adam_corrections(double lr, double beta1, double beta2, int64_t first_step, int64_t count, float* out_host_floats) {

@@ -11,7 +11,9 @@ them from L2 (csrc/mdr_maddpg_grad.hip) and leave the other learners' kernels as
 device tensors the kernels read in place through the sampled indices; ``MADDPGLearner`` is the update, ``train_maddpg`` the loop.
 The gumbel noise is an input of every call, drawn by the learner - under a seeded generator or, with ``sampler="philox"``, by one launch
 of mdr_maddpg_draws together with the minibatches: every backend sees the same noise.  ``graph=True`` replays a whole update from one
-captured graph (graph_update.MADDPGUpdateGraph).  Nothing on the call path synchronises with the host.
+captured graph (graph_update.MADDPGUpdateGraph).  ``agent_steps="batched"`` (per-agent networks only) takes the N agents through every
+stage of an update together - mdr_maddpg_target_all, mdr_maddpg_critic_grad_all, mdr_maddpg_actor_grad_all and ``optim.step_nets`` -
+with the bits of the agents one after the other.  Nothing on the call path synchronises with the host.
 
 Places that leave the reference's text on purpose:
 
@@ -45,7 +47,7 @@ import torch.nn.functional as F
 from . import _learner as L
 from . import _native as nat
 from . import graph_update
-from .optim import FusedAdam
+from .optim import FusedAdam, nets_refusal, step_nets
 
 MAX_STATE, MAX_HIDDEN, MAX_JOINT = 64, 256, 1280      # the kernels' limits (include/mdr_policy.h: mdr_maddpg_*)
 # backend="auto": the kernels for minibatches of this many rows (profiles/maddpg_update_README.md: they measured 2.3-2.9x faster than
@@ -190,6 +192,30 @@ def _actor_launch(adesc, cdesc, state, ld, action, index, B, N, agent, noise, wo
     nat.check(lib, None, rc, "mdr_maddpg_actor_grad")
 
 
+def _target_all_launch(tgt_adescs, tgt_cdescs, next_state, ld, reward, index, B, N, noise, y, next_q, next_action, st, tau, gamma,
+                       max_workgroups: int = 0) -> None:
+    """mdr_maddpg_target_all: every agent's y on its own minibatch; the descriptors are host arrays of N (``_learner.mlp_descs``)."""
+    lib = nat.load()
+    rc = lib.mdr_maddpg_target_all(tgt_adescs, tgt_cdescs, L.ptr(next_state), ld, L.ptr(reward), L.ptr(index), B, N, L.ptr(noise), C.c_float(tau),
+                                   C.c_float(gamma), max_workgroups, L.ptr(y), L.ptr(next_q), L.ptr(next_action), st)
+    nat.check(lib, None, rc, "mdr_maddpg_target_all")
+
+
+def _critic_all_launch(cdescs, state, ld, action, index, B, N, y, workspace, flat, loss, q, st, max_workgroups: int = 0) -> None:
+    lib = nat.load()
+    rc = lib.mdr_maddpg_critic_grad_all(cdescs, L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, L.ptr(y), max_workgroups, L.ptr(workspace),
+                                        L.ptr(flat), L.ptr(loss), L.ptr(q), st)
+    nat.check(lib, None, rc, "mdr_maddpg_critic_grad_all")
+
+
+def _actor_all_launch(adescs, cdescs, state, ld, action, index, B, N, noise, workspace, flat, loss, q, logits, st, tau, pse,
+                      max_workgroups: int = 0) -> None:
+    lib = nat.load()
+    rc = lib.mdr_maddpg_actor_grad_all(adescs, cdescs, L.ptr(state), ld, L.ptr(action), L.ptr(index), B, N, L.ptr(noise), C.c_float(tau),
+                                       C.c_float(pse), max_workgroups, L.ptr(workspace), L.ptr(flat), L.ptr(loss), L.ptr(q), L.ptr(logits), st)
+    nat.check(lib, None, rc, "mdr_maddpg_actor_grad_all")
+
+
 def maddpg_target(tgt_actor, tgt_critic, next_state: torch.Tensor, reward: torch.Tensor, agent: int, noise: torch.Tensor,
                   tau: float = 1.0, gamma: float = 0.99, index: Optional[torch.Tensor] = None, max_workgroups: int = 0
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -321,14 +347,34 @@ class MADDPGLearner:
     one ``exponential_`` under a ``torch.Generator`` (``"torch"``, the default) - other draws of the same laws, on every backend.
     ``graph=True`` (implies ``sampler="philox"``; needs ``optimizer=FusedAdam`` and networks the kernels take): every ``update()`` is
     replayed from one captured graph (graph_update.MADDPGUpdateGraph) and gives the bits of the eager ``sampler="philox"`` update;
-    ``graph_captures`` counts the captures."""
+    ``graph_captures`` counts the captures.
+
+    ``agent_steps="batched"`` (``shared=False``, ``backend="hip"``, ``optimizer=FusedAdam``, no graph; ValueError otherwise): the N
+    agents go through every stage of an update TOGETHER instead of one after the other - mdr_maddpg_target_all,
+    mdr_maddpg_critic_grad_all, one ``optim.step_nets`` over the N critics (each critic's blend riding on it), mdr_maddpg_actor_grad_all,
+    one ``step_nets`` over the N actors, the actors' blends - about ten launches with N times the workgroups each, and the bits of
+    the default ``"sequential"``: with unshared nets agent a's steps read nothing another agent's steps of the same update write
+    (DESIGN.md).  ``before_step`` is called for the N critics after the critics' gradients and for the N actors after the actors'.
+    The gradients are slices of one [N, G] buffer per kind; the nets' tensors must keep their addresses (``load_network_dict``
+    does).  The attribute may be changed between updates; optimisers at different step counts (a heterogeneous
+    ``load_network_dict``) take their steps one by one for that update."""
 
     MAX_GRAD_NORM = 0.5      # ddpg.py:157, 163
 
     def __init__(self, actor, critic, nb_agents: int, lr_actor: float, lr_critic: float, gamma: float = 0.99, soft_tau: float = 0.01,
                  gumbel_tau: float = 1.0, batch_size: int = 64, buffer_capacity: int = 524288, backend: str = "auto",
-                 optimizer=torch.optim.Adam, shared: bool = True, sampler: Optional[str] = None, graph: bool = False):
+                 optimizer=torch.optim.Adam, shared: bool = True, sampler: Optional[str] = None, graph: bool = False,
+                 agent_steps: str = "sequential"):
         L.check_backend(backend)
+        if agent_steps not in ("sequential", "batched"):
+            raise ValueError("agent_steps must be 'sequential' or 'batched'")
+        if agent_steps == "batched":      # decided before anything touches the GPU
+            for bad, why in ((shared, "shared=False (the steps of agents that share their nets depend on each other)"),
+                             (backend != "hip", "backend='hip'"), (optimizer is not FusedAdam, "optimizer=FusedAdam"),
+                             (graph, "graph=False (capturing the batched update is not offered)")):
+                if bad:
+                    raise ValueError("MADDPGLearner(agent_steps='batched') needs " + why)
+        self.agent_steps = agent_steps
         self.sampler, self.graph = L.check_sampler(sampler, graph), bool(graph)
         self.shared, self.nb_agents = bool(shared), int(nb_agents)
         N = self.nb_agents
@@ -382,6 +428,9 @@ class MADDPGLearner:
         self.before_step = None
         self.graph_captures = 0
         self._graph = None
+        self._batched = None
+        if agent_steps == "batched":
+            self._batched_state()      # the gradients' slices exist before any update, whichever form takes it
         if self.graph:
             why = graph_update.refusal(backend, self.sampler, actor_optimizers + critic_optimizers, self.uses_kernels(max(self.batch_size, 1)))
             if why:
@@ -389,13 +438,13 @@ class MADDPGLearner:
 
     @classmethod
     def from_config(cls, ddpg_prop: dict, actor, critic, nb_agents: int, backend: str = "auto", optimizer=torch.optim.Adam,
-                    sampler: Optional[str] = None, graph: bool = False) -> "MADDPGLearner":
+                    sampler: Optional[str] = None, graph: bool = False, agent_steps: str = "sequential") -> "MADDPGLearner":
         """From the reference's ``config_dict["DDPG_prop"]`` (agents/ddpg.py:60-70).  ``DDPG_shared`` (ddpg.py:214-215; absent: shared)
         false: ``actor`` and ``critic`` are the caller's lists of ``nb_agents`` modules."""
         return cls(actor, critic, nb_agents, ddpg_prop["lr_actor"], ddpg_prop["lr_critic"], gamma=ddpg_prop["gamma"],
                    soft_tau=ddpg_prop["soft_tau"], gumbel_tau=ddpg_prop["gumbel_softmax_tau"], batch_size=ddpg_prop["batch_size"],
                    buffer_capacity=ddpg_prop["buffer_capacity"], backend=backend, optimizer=optimizer,
-                   shared=bool(ddpg_prop.get("DDPG_shared", True)), sampler=sampler, graph=graph)
+                   shared=bool(ddpg_prop.get("DDPG_shared", True)), sampler=sampler, graph=graph, agent_steps=agent_steps)
 
     def uses_kernels(self, nb_rows: int) -> bool:
         if self.backend == "auto":
@@ -530,6 +579,73 @@ class MADDPGLearner:
                 p.requires_grad_(True)
         return loss.detach()
 
+    def _batched_state(self) -> dict:
+        """What the batched update keeps: the four host arrays of descriptors, the parameter lists, and one [N, G] gradient buffer per
+        kind whose slice a is ``_mdr_flat_grad`` of agent a's module - what ``publish`` and the sequential calls write too."""
+        if self._batched is not None:
+            return self._batched
+        if self.shared or self.backend != "hip" or self.graph:
+            raise ValueError("MADDPGLearner: agent_steps='batched' needs shared=False, backend='hip' and graph=False")
+        N, B, dev = self.nb_agents, self.batch_size, self.buffer.device
+        lib = nat.load()
+        descs = [L.mlp_descs([L.fc_layers(m) for m in nets]) for nets in (self.actors, self.critics, self.tgt_actors, self.tgt_critics)]
+        a_floats, c_floats, _ = _sizes(descs[0][0], descs[1][0], N, B)
+        nbytes = L.sized(int(lib.mdr_maddpg_workspace_bytes_all(C.byref(descs[0][0]), C.byref(descs[1][0]), N, B, 0)), "MADDPGLearner",
+                         "mdr_maddpg_workspace_bytes_all")
+        flat_a = torch.empty((N, a_floats), dtype=torch.float32, device=dev)
+        flat_c = torch.empty((N, c_floats), dtype=torch.float32, device=dev)
+        for a in range(N):
+            self.actors[a]._mdr_flat_grad, self.critics[a]._mdr_flat_grad = flat_a[a], flat_c[a]
+        self._batched = dict(descs=descs, nbytes=nbytes, flat_a=flat_a, flat_c=flat_c,
+                             a_params=[L.mlp_params(m.fc) for m in self.actors], c_params=[L.mlp_params(m.fc) for m in self.critics],
+                             tc_params=[L.mlp_params(m.fc) for m in self.tgt_critics],
+                             ta_all=[p for m in self.tgt_actors for p in L.mlp_params(m.fc)],
+                             a_all=[p for m in self.actors for p in L.mlp_params(m.fc)])
+        return self._batched
+
+    def _update_batched(self, seed: int) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """``update`` with the agents side by side (class docstring): the stages of the unshared loop below, each over all N agents."""
+        if len(self.buffer) < self.batch_size:
+            return None
+        st, buf, N, B = self._batched_state(), self.buffer, self.nb_agents, self.batch_size
+        adescs, cdescs, tgt_adescs, tgt_cdescs = st["descs"]
+        dev = buf.device
+        index, noise_t, noise_a = self.draws(seed)
+        _, _, ld, _ = _check_steps(self.actors[0], buf.state, index[0], N, "MADDPGLearner.update")
+        y = torch.empty((N, B), dtype=torch.float32, device=dev)
+        next_action = torch.empty((N, B, N), dtype=torch.uint8, device=dev)
+        c_loss = torch.empty(N, dtype=torch.float32, device=dev)
+        a_loss = torch.empty(N, dtype=torch.float32, device=dev)
+        ws = L.workspace(dev, st["nbytes"])
+        with torch.cuda.device(dev):
+            stream = L.stream(dev)
+            _target_all_launch(tgt_adescs, tgt_cdescs, buf.next_state, ld, buf.reward, index, B, N, noise_t, y, None, next_action, stream,
+                               self.gumbel_tau, self.gamma)
+            _critic_all_launch(cdescs, buf.state, ld, buf.action, index, B, N, y, ws, st["flat_c"], c_loss, None, stream)
+        self._publish_and_step("critic", self.critics, self.critic_optimizers, st["c_params"], st["flat_c"], st["tc_params"])
+        with torch.cuda.device(dev):      # the actors' step reads the stepped critics
+            _actor_all_launch(adescs, cdescs, buf.state, ld, buf.action, index, B, N, noise_a, ws, st["flat_a"], a_loss, None, None,
+                              L.stream(dev), self.gumbel_tau, PSE)
+        self._publish_and_step("actor", self.actors, self.actor_optimizers, st["a_params"], st["flat_a"], None)
+        L.blend(st["ta_all"], st["a_all"], self.soft_tau)      # the N actors' blends: after every step, as the loop has them
+        self.training_step += 1
+        return a_loss, c_loss
+
+    def _publish_and_step(self, which, nets, optimizers, params, flat, blend_targets) -> None:
+        """``.grad`` of the N nets from the slices of ``flat``, the N ``before_step`` calls, then clip + Adam [+ blend] of all N: one
+        ``step_nets``, or the nets' own steps where their optimisers do not go together."""
+        N = self.nb_agents
+        for a in range(N):
+            L.publish(params[a], flat[a], L.KEEP)
+        if self.before_step is not None:
+            for a in range(N):
+                self.before_step(self, which, a)
+        if nets_refusal(optimizers) is None:
+            step_nets(optimizers, self.MAX_GRAD_NORM, targets=blend_targets, tau=self.soft_tau if blend_targets is not None else 0.0)
+        else:
+            for a in range(N):
+                self._step(optimizers[a], nets[a], self.tgt_critics[a] if blend_targets is not None else None)
+
     def update(self, seed: int = 0) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
         """One ``MADDPG.update()`` (ddpg.py:305-339) and the ``update_target()`` train_ddpg.py:124-131 follows it with: for every agent
         in order a fresh minibatch, the critic's step, the actor's step; then one blend of both target nets.  -> (actor_loss [N],
@@ -537,6 +653,8 @@ class MADDPGLearner:
         than ``batch_size`` env-steps."""
         if self.graph:
             return graph_update.maddpg_update(self, seed)
+        if self.agent_steps == "batched":
+            return self._update_batched(seed)
         if len(self.buffer) < self.batch_size:
             return None
         N = self.nb_agents

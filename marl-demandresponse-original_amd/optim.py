@@ -12,11 +12,15 @@ buffers owned by the optimiser; ``state[p]["exp_avg"]`` / ``["exp_avg_sq"]`` are
 
 One visible difference from ``clip_grad_norm_`` + ``Adam.step()``: the gradient is never written.  After ``step(max_grad_norm=...)``
 ``p.grad`` still holds the unclipped gradient (``clip_grad_norm_`` scales ``.grad`` in place).
+
+``step_nets`` steps a LIST of ``FusedAdam`` instances - the N critics or the N actors of MADDPG's per-agent networks - in at most two
+launches (mdr_adam_step_nets), every net with its own norm, clip and blend and with the bits of its own ``step``.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import weakref
 from typing import List, Optional, Sequence
 
 import torch
@@ -161,6 +165,19 @@ class FusedAdam(torch.optim.Optimizer):
         self._t = counts.pop() if counts else 0
         self._key = key
 
+    def _table_key(self, target, blend: bool) -> list:
+        """The pointers the segment table stands for - parameter, gradient, target of every tensor; autograd reallocates ``.grad``, so
+        the table is rebuilt only when one of them moved (``step`` and ``step_nets``)."""
+        grads = [p.grad for p in self._params]
+        key = []
+        for i, p in enumerate(self._params):
+            g = grads[i]
+            t = target[i] if blend else None
+            key += [p.data_ptr(), g.data_ptr() if g is not None else 0, t.data_ptr() if t is not None else 0]
+        if key != self._key:
+            self._build(key, grads, target if blend else None)
+        return key
+
     @torch.no_grad()
     def step(self, max_grad_norm: Optional[float] = None, grad_clamp: Optional[float] = None, target: Optional[Sequence[torch.Tensor]] = None,
              tau: Optional[float] = None, want_norm: bool = False, *, corrections: Optional[torch.Tensor] = None, slot: Optional[int] = None,
@@ -183,14 +200,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("FusedAdam.step: target and tau go together")
         if blend and len(target) != len(self._params):
             raise ValueError("FusedAdam.step: target must list one tensor per parameter (%d), got %d" % (len(self._params), len(target)))
-        grads = [p.grad for p in self._params]
-        key = []
-        for i, p in enumerate(self._params):
-            g = grads[i]
-            t = target[i] if blend else None
-            key += [p.data_ptr(), g.data_ptr() if g is not None else 0, t.data_ptr() if t is not None else 0]
-        if key != self._key:      # autograd reallocates .grad: the table is rebuilt only when a pointer moved
-            self._build(key, grads, target if blend else None)
+        self._table_key(target, blend)
         if not self._live:
             return self._norm.zero_() if want_norm else None
         t = self._t + 1
@@ -223,14 +233,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("FusedAdam.step: target and tau go together")
         if blend and len(target) != len(self._params):
             raise ValueError("FusedAdam.step: target must list one tensor per parameter (%d), got %d" % (len(self._params), len(target)))
-        grads = [p.grad for p in self._params]
-        key = []
-        for i, p in enumerate(self._params):
-            g = grads[i]
-            t = target[i] if blend else None
-            key += [p.data_ptr(), g.data_ptr() if g is not None else 0, t.data_ptr() if t is not None else 0]
-        if key != self._key:
-            self._build(key, grads, target if blend else None)
+        self._table_key(target, blend)
         if not self._live:
             return self._norm.zero_() if want_norm else None
         beta1, beta2 = group["betas"]
@@ -273,3 +276,93 @@ class FusedAdam(torch.optim.Optimizer):
         if steps:
             torch._foreach_add_(steps, int(count))
         self._t += int(count)
+
+
+# -- N optimisers in one step ---------------------------------------------------------------------------------------------------------
+class _NetsPlan:
+    """What ``step_nets`` keeps for one list of optimisers: the device table of their segment records (mdr_adam_nets_bind), the
+    workspace of their chunk sums, their norms, and the pointers every record was bound from."""
+
+    def __init__(self, optimizers):
+        lib, dev, n = nat.load(), optimizers[0]._device, len(optimizers)
+        self.max_floats = max(sum(o._counts) for o in optimizers)
+        self.table = torch.empty(max(int(lib.mdr_adam_nets_table_bytes(n)), 16), dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty(max(n * int(lib.mdr_adam_workspace_bytes(self.max_floats)), 16), dtype=torch.uint8, device=dev)
+        self.norms = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.bound = [None] * n
+        self.refs = [weakref.ref(o) for o in optimizers]      # an id may be taken again by a later object
+
+
+def nets_refusal(optimizers) -> Optional[str]:
+    """Why ``step_nets`` does not take these optimisers together (None: it does).  Decided on the host."""
+    optimizers = list(optimizers)
+    if not optimizers:
+        return "no optimisers"
+    if not all(isinstance(o, FusedAdam) for o in optimizers):
+        return "every optimiser must be a FusedAdam"
+    if len(set(map(id, optimizers))) != len(optimizers):
+        return "an optimiser is listed twice"
+    first = optimizers[0]
+    g0 = first.param_groups[0]
+    for o in optimizers:
+        g = o._check_group()
+        if o._device != first._device:
+            return "the optimisers' parameters are on different GPUs"
+        if float(g["lr"]) != float(g0["lr"]) or tuple(g["betas"]) != tuple(g0["betas"]) or float(g["eps"]) != float(g0["eps"]):
+            return "lr, betas and eps must be the same for every optimiser (one launch takes one set)"
+    if len({o.step_count() for o in optimizers}) > 1:
+        return "the optimisers are at different step counts (one launch takes one bias correction)"
+    return None
+
+
+@torch.no_grad()
+def step_nets(optimizers: Sequence[FusedAdam], max_grad_norm: Optional[float] = None, targets=None, tau: float = 0.0,
+              want_norm: bool = False) -> Optional[torch.Tensor]:
+    """``opt.step(max_grad_norm, target=targets[i], tau=tau)`` for every ``FusedAdam`` of ``optimizers`` in at most two
+    launches (mdr_adam_step_nets): every net takes its own total norm, its own clip and its own blend, and its parameters, moments
+    and targets end with the bits ``step`` gives.  The optimisers' own moment buffers are stepped and their own step counts advanced,
+    so ``state_dict()`` does not know which form ran and a caller may change between the two at any step.  ``targets``: one list of
+    tensors per optimiser, with ``tau`` > 0 (None: no blend).  ValueError (``nets_refusal``) where lr, betas, eps or the step counts
+    differ between the optimisers: the caller then steps them one by one.  -> the N total norms (a float32 [N] device tensor
+    overwritten by the next call) with ``want_norm``; None otherwise.  Never synchronises."""
+    optimizers = list(optimizers)
+    why = nets_refusal(optimizers)
+    if why:
+        raise ValueError("step_nets: " + why)
+    blend = targets is not None and float(tau) > 0.0
+    if targets is not None and len(targets) != len(optimizers):
+        raise ValueError("step_nets: targets must list one sequence of tensors per optimiser")
+    for i, o in enumerate(optimizers):
+        if blend and len(targets[i]) != len(o._params):
+            raise ValueError("step_nets: targets[%d] must list one tensor per parameter" % i)
+    first = optimizers[0]
+    plans = first.__dict__.setdefault("_nets_plans", {})
+    ids = tuple(map(id, optimizers))
+    plan = plans.get(ids)
+    if plan is None or any(r() is not o for r, o in zip(plan.refs, optimizers)):
+        plan = plans[ids] = _NetsPlan(optimizers)
+    lib, dev = first._lib, first._device
+    keys = [o._table_key(targets[i] if blend else None, blend) for i, o in enumerate(optimizers)]
+    live = [o for o in optimizers if o._live]
+    if len({o._t for o in live}) > 1:
+        raise ValueError("step_nets: the optimisers are at different step counts (one launch takes one bias correction)")
+    group = first.param_groups[0]
+    beta1, beta2 = group["betas"]
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for i, o in enumerate(optimizers):      # a record is bound again only when one of its pointers moved
+            if plan.bound[i] != keys[i]:
+                rc = lib.mdr_adam_nets_bind(plan.table.data_ptr(), i, C.byref(o._table), o._exp_avg.data_ptr(), o._exp_avg_sq.data_ptr(), st)
+                nat.check(lib, None, rc, "mdr_adam_nets_bind")
+                plan.bound[i] = list(keys[i])
+        if live:
+            rc = lib.mdr_adam_step_nets(plan.table.data_ptr(), len(optimizers), plan.max_floats, float(group["lr"]), float(beta1), float(beta2),
+                                        float(group["eps"]), live[0]._t + 1, float(max_grad_norm) if max_grad_norm is not None else 0.0,
+                                        math.inf, float(tau) if blend else 0.0, plan.workspace.data_ptr(), plan.norms.data_ptr() if want_norm else None, st)
+            nat.check(lib, None, rc, "mdr_adam_step_nets")
+    for o in live:
+        o._t += 1
+        torch._foreach_add_(o._steps, 1)
+    if not want_norm:
+        return None
+    return plan.norms if live else plan.norms.zero_()
