@@ -198,6 +198,56 @@ int mdr_tarmac_comm_backward(const float *query, int64_t ldq, const float *key, 
  * negative or zero sizes of the rows. */
 int64_t mdr_tarmac_comm_backward_workspace_bytes(int64_t nb_agents, int32_t num_key, int32_t num_value);
 
+/* ---- The two non-banded masks of make_masks (network.py:138-177), tarmac_comm_mode "all" and "random_sample": entry points of
+ * their own (csrc/mdr_tarmac_gather.hip); enum mdr_tarmac_mode and the calls above keep their two banded modes. */
+enum mdr_tarmac_gather_mode {
+  MDR_TARMAC_ALL = 0,          /* "all": receiver r attends to all nb_houses agents of its env, itself included; nothing is drawn,
+                                  nb_comm is ignored */
+  MDR_TARMAC_RANDOM_SAMPLE = 1 /* "random_sample": r attends to itself and to c = min(nb_comm, nb_houses - 1) distinct other agents of
+                                  its env, uniform among the c-subsets of the others */
+};
+
+/* mdr_tarmac_comm for these masks: the same operands (rows, leading dimensions, packed buffers and column blocks in place), limits
+ * (num_key a multiple of 4 <= 32, num_value a multiple of 4 <= 64, 16-byte alignment), status codes, `step_dev` and `hop`, without
+ * defect_prob - the reference applies comm_defect_prob in mode "neighbours" only (network.py:159-163), these modes have no defects.
+ * score_s = query_r . key_s / sqrt(num_key), softmax over the receiver's senders with the maximum over THOSE senders subtracted (as
+ * mdr_tarmac_comm), out_r = sum_s attn_s value_s; MDR_TARMAC_ALL sums the senders in ascending house order, MDR_TARMAC_RANDOM_SAMPLE
+ * the receiver first, then the drawn senders in the order drawn.  nb_houses == 1 or c == 0: out = value, bit for bit.
+ * The draw of MDR_TARMAC_RANDOM_SAMPLE - Floyd's algorithm over the M = nb_houses - 1 others of receiver r, other index o standing
+ * for house o if o < r and o + 1 otherwise: for j = M - c .. M - 1 in this order, t = (word_j * (j + 1)) >> 32 in 64-bit arithmetic;
+ * t is taken unless it already was, then j is.  word_j = word (j & 3) of Philox4x32-10 with key = seed and counter
+ *   (a low word,  a >> 32 | (j >> 2) << 16 | hop << 29 | 1 << 31,  step low word + *step_dev,  0x544D4732 ^ step high word),
+ * a the RECEIVER's agent index in the whole batch (below 2^48; -4 beyond).  Bit 31 of the second word is never set in the counters of
+ * the action draw (mdr_actor_sample) and of the dead-sender draw (mdr_tarmac_comm), whose second word is a >> 32 < 2^16, and the
+ * fourth word's tag differs from theirs: the three streams are disjoint for every (agent, step, hop).  The draw depends on (seed,
+ * step + *step_dev, hop, agent) alone - not on the grid, the tiling or the number of envs - and c = nb_houses - 1 gives every other
+ * agent.  The reference draws ONE mask per forward call with np.random and shares it among the envs of the batch; here every env
+ * (every receiver) has its own draw, as every env has its own dead senders in mdr_tarmac_comm.
+ * Further limits (-4): c <= 64 in MDR_TARMAC_RANDOM_SAMPLE; all nb_houses key | value rows of an env are staged in the 160 KB of LDS
+ * of a workgroup at a stride of K + V floats rounded up to an odd multiple of 4, beside 512 * c bytes of index lists in
+ * MDR_TARMAC_RANDOM_SAMPLE (K = 8, V = 16: nb_houses <= 1462, or 1417 at c = 10).  Every element of every out row is written, no
+ * column beyond num_value is; a refused call launches nothing and writes nothing.  An unknown mode is -1. */
+int mdr_tarmac_gather(const float *query, int64_t ldq, const float *key, int64_t ldk, const float *value, int64_t ldv, int32_t nb_envs,
+                      int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, uint64_t seed,
+                      uint64_t step, const int32_t *step_dev, int32_t hop, float *out, int64_t ldo, void *stream);
+
+/* Its gradient: the formulas and the operand conventions of mdr_tarmac_comm_backward with S(r) the sender sets above, redrawn from the
+ * same (seed, step, *step_dev, hop) - no mask is stored between forward and backward.  Two passes, no floating-point atomics: per
+ * receiver the statistics and grad_query (MDR_TARMAC_RANDOM_SAMPLE: and the receiver's index list, left in the workspace), then per
+ * sender, which scans the receivers of its env in ascending order - the same operands give the same bits.  Covers nb_houses <= 256
+ * (whole envs per workgroup; the training minibatches are envs of tens of agents), -4 beyond.  `workspace`: 16-byte aligned device
+ * memory of mdr_tarmac_gather_backward_workspace_bytes() bytes, always required. */
+int mdr_tarmac_gather_backward(const float *query, int64_t ldq, const float *key, int64_t ldk, const float *value, int64_t ldv,
+                               int32_t nb_envs, int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode,
+                               uint64_t seed, uint64_t step, const int32_t *step_dev, int32_t hop, const float *out, int64_t ldo,
+                               const float *grad_out, int64_t ldg, float *grad_query, int64_t ldgq, float *grad_key, int64_t ldgk,
+                               float *grad_value, int64_t ldgv, void *workspace, void *stream);
+
+/* 16 bytes of statistics per agent, plus in MDR_TARMAC_RANDOM_SAMPLE 2 c bytes per agent rounded up to 16 in all
+ * (c = min(nb_comm, nb_houses - 1)); -1 for sizes or a mode the calls refuse. */
+int64_t mdr_tarmac_gather_backward_workspace_bytes(int32_t nb_envs, int32_t nb_houses, int32_t num_key, int32_t num_value,
+                                                   int32_t nb_comm, int32_t mode);
+
 /* The policy head's last step for two logits per agent (`logits` float [nb_agents][ld], ld >= 2, columns 0 and 1):
  * d = l0 - l1, p0 = 1 / (1 + exp(-d)), p1 = 1 / (1 + exp(d)), then the draw, `action`, `a_prob`, `probs` and `step_dev` exactly as
  * mdr_actor_sample: for equal probabilities the same (seed, step, agent) draws the same action.  greedy != 0: argmax, the first

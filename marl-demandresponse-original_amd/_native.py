@@ -211,6 +211,7 @@ EXPORTS = (
     # include/mdr_policy.h
     "mdr_actor_steps1", "mdr_actor_steps1_order", "mdr_actor_steps2", "mdr_actor_frag1_floats", "mdr_actor_frag2_floats", "mdr_actor_sample", "mdr_env_actor_sample", "mdr_env_actor_sample_links",
     "mdr_discounted_returns", "mdr_tarmac_comm", "mdr_logits_sample", "mdr_tarmac_comm_backward", "mdr_tarmac_comm_backward_workspace_bytes",
+    "mdr_tarmac_gather", "mdr_tarmac_gather_backward", "mdr_tarmac_gather_backward_workspace_bytes",
     "mdr_tarmac_frag_encode_floats", "mdr_tarmac_frag_proj_floats", "mdr_tarmac_frag_msg_floats", "mdr_tarmac_frag_head_floats",
     "mdr_tarmac_vec_floats", "mdr_tarmac_frag_words", "mdr_tarmac_actor_workspace_bytes", "mdr_tarmac_actor_sample",
     "mdr_env_tarmac_actor_sample",
@@ -315,6 +316,10 @@ def load():
         "mdr_tarmac_comm_backward": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, u64, u64, vp, i32, vp, i64,
                                                vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
         "mdr_tarmac_comm_backward_workspace_bytes": (i64, [i64, i32, i32]),
+        "mdr_tarmac_gather": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, u64, u64, vp, i32, vp, i64, vp]),
+        "mdr_tarmac_gather_backward": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, u64, u64, vp, i32, vp, i64,
+                                                 vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
+        "mdr_tarmac_gather_backward_workspace_bytes": (i64, [i32, i32, i32, i32, i32, i32]),
         "mdr_tarmac_frag_encode_floats": (i64, [i32, i32]),
         "mdr_tarmac_frag_proj_floats": (i64, [i32, i32]),
         "mdr_tarmac_frag_msg_floats": (i64, [i32, i32]),

@@ -584,7 +584,8 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     steps of (reg_signal - cluster_hvac_power)^2).
 
     ``policy``: a ``TarMACA2CPolicy`` (the agent of train_tarmac.py; eager only, the message carried from step to step, zero before
-    the first), a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused), a
+    the first), a ``TarMACActor`` (main-deploy.py --agent TarmacPPO; eager only, ``use_graph=True`` is refused - except with
+    ``attention="gather"``, the comm modes "all" and "random_sample", whose chain is captured), a
     ``FusedTarMACActor`` (the same agent as one chain of HIP kernels, exact fp32 or ``precision="bf16x3"``: observation rows, the chain with ``step_dev =
     env.device_time_index``, ``env.step`` - one stream, no parallel branches, so ``use_graph=True`` captures it), the network itself (``ActorMLP`` / the reference's ``Actor``; ``greedy=True`` for a ``DQN_network``: argmax) - packed
     here, and observation and policy are then ONE kernel wherever ``collect_ppo_rollout`` would make them one (no observation rows at
@@ -610,12 +611,15 @@ def deploy_policy(env, policy, nb_steps: int, seed: int = 0, use_graph: Optional
     fused_tarmac = isinstance(policy, FusedTarMACActor)
     a2c = isinstance(policy, TarMACA2CPolicy)
     tarmac = fused_tarmac or a2c or isinstance(policy, TarMACActor)
+    # a TarMACActor with attention="gather" (comm modes "all" / "random_sample"): its buffer-reusing chain is one stream of GEMMs
+    # and kernels with step_dev = env.device_time_index, so it is captured like the fused chain
+    capturable = fused_tarmac or (isinstance(policy, TarMACActor) and policy.attention == "gather")
     if tarmac:
-        if use_graph and not fused_tarmac:
+        if use_graph and not capturable:
             raise ValueError("deploy_policy runs a %s eagerly: its GEMMs and kernels are not captured" % ("TarMACA2CPolicy" if a2c else "TarMACActor"))
         if getattr(env, "sharded", False):
             raise ValueError("TarMAC over house-sharded envs is not supported")
-        if not fused_tarmac:
+        if not capturable:
             use_graph = False
     elif isinstance(policy, nn.Module):
         if not _fusable(policy):

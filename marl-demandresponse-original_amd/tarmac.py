@@ -14,6 +14,15 @@ Two ways to evaluate the attention of ``TarMAC_Comm.forward``:
                        ``forward(..., differentiable=True)`` is the training path: the same MLPs as autograd ops around
                        ``band_attention``, whose backward is ``mdr_tarmac_comm_backward`` - O(E N c) as the forward.
 
+``attention="gather"`` CUDA, opt-in: tarmac_comm_mode "all" (every agent of the env, one dense N x N softmax per env) and
+                       "random_sample" (the receiver and c distinct others, as sparse as the band) on ``mdr_tarmac_gather`` /
+                       ``gather_attention`` - the band path's chains with the other attention call.  The reference draws one
+                       random mask per forward call with ``np.random`` and shares it among the batch; the port draws per env from
+                       Philox, keyed by ``(seed, step, hop)`` and the receiver, as it already does for dead senders.  With
+                       ``attention="auto"`` both modes stay refused; ``attention="dense"`` takes them with ``mask=`` (the
+                       reference's own masks, replayable on any device).  ``FusedTarMACActor``, ``sample_env`` and the fused
+                       update kernels (``tarmac_ppo``) refuse them: the learner trains through ``forward(differentiable=True)``.
+
 The update step of the reference's learner (agents/tarmac_ppo.py:152-191) on a batch of ``collect_tarmac_rollout``, T steps of E envs::
 
     state = ro["state"][:-1].view(T * E, N, F)                         # one stored env-step per batch row
@@ -46,6 +55,7 @@ from . import _native as nat
 from .policy import OBSERVE_NUM_STATE, observe_feature_order
 
 MODES = {"neighbours": 0, "none": 1}      # mdr_tarmac_mode
+GATHER_MODES = {"all": 0, "random_sample": 1}      # mdr_tarmac_gather_mode: opt-in, attention="gather" (or "dense")
 MAX_HOPS, MAX_KEY, MAX_VALUE, MAX_COMM = 4, 32, 64, 64
 
 
@@ -162,6 +172,100 @@ def band_attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, 
     return _BandAttention.apply(query, key, value, int(nb_comm), MODES[mode], float(defect_prob), seed, step, step_dev, int(hop))
 
 
+_GATHER_WORKSPACES = {}      # (E, N, c, mode, device) -> uint8 tensor: statistics and index lists of mdr_tarmac_gather_backward
+
+
+def _gather_workspace(E: int, N: int, K: int, V: int, nb_comm: int, mode: int, dev) -> torch.Tensor:
+    n = nat.load().mdr_tarmac_gather_backward_workspace_bytes(E, N, K, V, nb_comm, mode)
+    if n < 0:
+        raise RuntimeError("mdr_tarmac_gather_backward_workspace_bytes refused the shape")
+    key = (E, N, min(nb_comm, N - 1), mode, dev)
+    ws = _GATHER_WORKSPACES.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _GATHER_WORKSPACES[key] = torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _gather_call(lib, q, k, v, ldq, ldk, ldv, E, N, K, V, nb_comm, mode, seed, step, step_dev, hop, out, ldo, dev):
+    with torch.cuda.device(dev):
+        rc = lib.mdr_tarmac_gather(C.c_void_p(q.data_ptr()), ldq, C.c_void_p(k.data_ptr()), ldk, C.c_void_p(v.data_ptr()), ldv, E, N, K, V,
+                                   nb_comm, mode, C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(step & (2 ** 64 - 1)),
+                                   C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, hop,
+                                   C.c_void_p(out.data_ptr()), ldo, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    nat.check(lib, None, rc, "mdr_tarmac_gather")
+
+
+class _GatherAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, query, key, value, nb_comm, mode, seed, step, step_dev, hop):
+        E, N, K = query.shape
+        V = value.shape[2]
+        dev = query.device
+        q, k, v = _rows(query.detach()), _rows(key.detach()), _rows(value.detach())
+        out = torch.empty((E, N, V), dtype=torch.float32, device=dev)
+        # the backward redraws the sender sets from the forward's key: keep the value the counter offset had
+        step_dev = step_dev.clone() if step_dev is not None else None
+        ctx.key = (int(nb_comm), int(mode), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(hop))
+        ctx.step_dev = step_dev
+        _gather_call(nat.load(), q, k, v, _ld(q), _ld(k), _ld(v), E, N, K, V, ctx.key[0], ctx.key[1], ctx.key[2], ctx.key[3], step_dev,
+                     ctx.key[4], out, V, dev)
+        ctx.save_for_backward(q, k, v, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, out = ctx.saved_tensors
+        E, N, K = q.shape
+        V = v.shape[2]
+        dev = q.device
+        g = _rows(grad_out if grad_out.dtype == torch.float32 else grad_out.float())
+        dq, dk = torch.empty((E, N, K), dtype=torch.float32, device=dev), torch.empty((E, N, K), dtype=torch.float32, device=dev)
+        dv = torch.empty((E, N, V), dtype=torch.float32, device=dev)
+        nb_comm, mode, seed, step, hop = ctx.key
+        ws = _gather_workspace(E, N, K, V, nb_comm, mode, dev)
+        step_dev = ctx.step_dev
+        lib = nat.load()
+        with torch.cuda.device(dev):
+            rc = lib.mdr_tarmac_gather_backward(C.c_void_p(q.data_ptr()), _ld(q), C.c_void_p(k.data_ptr()), _ld(k), C.c_void_p(v.data_ptr()), _ld(v),
+                                                E, N, K, V, nb_comm, mode, C.c_uint64(seed), C.c_uint64(step),
+                                                C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, hop,
+                                                C.c_void_p(out.data_ptr()), V, C.c_void_p(g.data_ptr()), _ld(g), C.c_void_p(dq.data_ptr()), K,
+                                                C.c_void_p(dk.data_ptr()), K, C.c_void_p(dv.data_ptr()), V, C.c_void_p(ws.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        nat.check(lib, None, rc, "mdr_tarmac_gather_backward")
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def gather_attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, nb_comm: int, mode: str, seed: int = 0, step: int = 0,
+                     step_dev: Optional[torch.Tensor] = None, hop: int = 0) -> torch.Tensor:
+    """The attention of ``TarMAC_Comm.forward`` under the masks of tarmac_comm_mode "all" and "random_sample", with a gradient:
+    float32 CUDA ``query``, ``key`` [E, N, K] and ``value`` [E, N, V] -> [E, N, V].  Forward ``mdr_tarmac_gather``, backward
+    ``mdr_tarmac_gather_backward`` (include/mdr_policy.h; once differentiable, N <= 256).  "all": every agent of the env, ``nb_comm``
+    ignored.  "random_sample": the receiver and min(nb_comm, N - 1) <= 64 distinct others, drawn PER ENV from Philox, keyed by
+    ``(seed, step, step_dev, hop)`` and the receiver's index in the batch - the reference draws one mask per forward call with
+    ``np.random`` and shares it among the whole batch; the port draws per env, as it does for dead senders.  The backward redraws the
+    forward's sets from the same key, nothing is stored but the operands and the result.  No defects in these modes (nor in the
+    reference's).  Views and the workspace cache as ``band_attention``."""
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3:
+            raise ValueError("%s must be a float32 CUDA tensor [E, N, D]" % name)
+    if key.shape != query.shape or value.shape[:2] != query.shape[:2] or key.device != query.device or value.device != query.device:
+        raise ValueError("query and key [E, N, K] and value [E, N, V] must agree in E, N, K and share a device")
+    K, V = query.shape[2], value.shape[2]
+    if K == 0 or K % 4 or K > MAX_KEY or V == 0 or V % 4 or V > MAX_VALUE or query.shape[1] == 0:
+        raise ValueError("gather attention: K a multiple of 4 <= %d, V a multiple of 4 <= %d, at least one agent" % (MAX_KEY, MAX_VALUE))
+    if mode not in GATHER_MODES:
+        raise ValueError("mode must be 'all' or 'random_sample'")
+    if int(nb_comm) < 0 or not 0 <= int(hop) < MAX_HOPS:
+        raise ValueError("nb_comm >= 0, hop in 0..%d" % (MAX_HOPS - 1))
+    if mode == "random_sample" and min(int(nb_comm), query.shape[1] - 1) > MAX_COMM:
+        raise ValueError("gather attention draws at most %d senders per receiver" % MAX_COMM)
+    if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.device != query.device):
+        raise ValueError("step_dev must be an int32 tensor on the device (env.device_time_index)")
+    return _GatherAttention.apply(query, key, value, int(nb_comm), GATHER_MODES[mode], seed, step, step_dev, int(hop))
+
+
 class TarMACComm(nn.Module):
     """The parameters of TarMAC_Comm (network.py:103-136); evaluated by ``TarMACActor``."""
 
@@ -180,12 +284,15 @@ class TarMACActor(nn.Module):
         super().__init__()
         if with_gru:
             raise ValueError("with_gru is not implemented (nor is it in the reference: network.py:205-207)")
-        if comm_mode not in MODES:
-            raise ValueError("tarmac_comm_mode %r: only 'neighbours' and 'none' are covered ('all' and 'random_sample' are not banded)" % (comm_mode,))
+        if attention not in ("auto", "band", "dense", "gather"):
+            raise ValueError("attention must be 'auto', 'band', 'dense' or 'gather'")
+        if comm_mode not in MODES and not (comm_mode in GATHER_MODES and attention in ("gather", "dense")):
+            raise ValueError("tarmac_comm_mode %r: only 'neighbours' and 'none' are covered ('all' and 'random_sample' are not banded)"
+                             "%s" % (comm_mode, " - they are opt-in: attention='gather' or 'dense'" if comm_mode in GATHER_MODES else ""))
+        if attention == "gather" and comm_mode not in GATHER_MODES:
+            raise ValueError("attention='gather' evaluates the comm modes 'all' and 'random_sample'; %r is banded" % (comm_mode,))
         if not 1 <= int(num_hops) <= MAX_HOPS:
             raise ValueError("num_hops must be 1..%d (one Philox word per hop)" % MAX_HOPS)
-        if attention not in ("auto", "band", "dense"):
-            raise ValueError("attention must be 'auto', 'band' or 'dense'")
         if not 0.0 <= float(comm_defect_prob) <= 1.0 or int(number_agents_comm) < 0:
             raise ValueError("comm_defect_prob in [0, 1], number_agents_comm >= 0")
         self.num_obs, self.num_key, self.num_value, self.hidden = int(num_obs), int(num_key), int(num_value), int(hidden_state_size)
@@ -201,12 +308,13 @@ class TarMACActor(nn.Module):
             self.hidden2action = _mlp(H, H, num_action, nn.ReLU)
         self._buffers_for = None
         self._packed = None
-        if attention == "band":
+        if attention in ("band", "gather"):
             self._check_band(None)
 
     @classmethod
     def from_config(cls, tarmac_ppo_prop: dict, num_obs: int, **kw) -> "TarMACActor":
-        """From the reference's ``config_dict["TarMAC_PPO_prop"]`` (agents/tarmac_ppo.py:21-36)."""
+        """From the reference's ``config_dict["TarMAC_PPO_prop"]`` (agents/tarmac_ppo.py:21-36).  A ``tarmac_comm_mode`` of "all" or
+        "random_sample" is opt-in: ``from_config(prop, F, attention="gather")`` (the HIP kernels) or ``attention="dense"``."""
         p = tarmac_ppo_prop
         return cls(num_obs, num_key=p["key_size"], num_value=p["communication_size"], hidden_state_size=p["actor_hidden_state_size"],
                    number_agents_comm=p["number_agents_comm_tarmac"], comm_mode=p["tarmac_comm_mode"],
@@ -220,6 +328,10 @@ class TarMACActor(nn.Module):
         mask = torch.zeros((N, N), dtype=torch.bool, device=device)
         if self.comm_mode == "none":
             return mask      # no diagonal either: 0 / 0 -> NaN -> 0
+        if self.comm_mode == "all":
+            return ~mask
+        if self.comm_mode == "random_sample":
+            raise ValueError("comm mode 'random_sample' has no fixed mask: pass mask= (the draw of mdr_tarmac_gather: include/mdr_policy.h)")
         r = torch.arange(N, device=device)
         mask[r, r] = True
         for o in band_offsets(min(self.number_agents_comm, N - 1)):
@@ -232,13 +344,23 @@ class TarMACActor(nn.Module):
         d = dead[hop] if (isinstance(dead, (list, tuple)) or dead.dim() == 3) else dead
         return d.bool()
 
-    def dense_logits(self, obs: torch.Tensor, dead=None) -> torch.Tensor:
+    def dense_logits(self, obs: torch.Tensor, dead=None, mask=None) -> torch.Tensor:
         """The reference's forward up to the logits, ``obs`` [E, N, F] in the dtype of the parameters.  ``dead``: the silenced senders,
         bool [E, N] (every hop) or [num_hops, E, N] / a list per hop - required when ``comm_defect_prob > 0`` (the band path draws them
-        from Philox; tests hand the same draws over)."""
+        from Philox; tests hand the same draws over).  ``mask``: the masks themselves, bool [receiver, sender] per hop, [num_hops, N, N]
+        (one for the whole batch, what the reference's ``make_masks`` returns) or [num_hops, E, N, N] (one per env, what the kernels
+        draw); they replace the mode's own mask - required in mode "random_sample", optional elsewhere (mode "all": ones)."""
         x = self.obs2hidden(obs)
         if not self.with_comm:
             return self.hidden2action(x)
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=x.device).bool()
+            if mask.dim() not in (3, 4) or mask.shape[0] != self.num_hops or tuple(mask.shape[-2:]) != (x.shape[1], x.shape[1]) or \
+                    (mask.dim() == 4 and mask.shape[1] != x.shape[0]):
+                raise ValueError("mask must be bool [num_hops, N, N] or [num_hops, E, N, N]")
+            return self._dense_masked(x, mask)
+        if self.comm_mode == "random_sample":
+            raise ValueError("the dense path takes the masks of comm mode 'random_sample' explicitly: mask=")
         if dead is None and self.comm_defect_prob > 0.0 and self.comm_mode == "neighbours":
             raise ValueError("the dense path takes the dead-sender mask explicitly when comm_defect_prob > 0")
         E, N, _ = x.shape
@@ -261,6 +383,21 @@ class TarMACActor(nn.Module):
             comm = torch.matmul(attn, value)
         return self.comm_hidden2action(torch.cat([x, comm], dim=2))
 
+    def _dense_masked(self, x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+        """``dense_logits`` from the hidden state on under explicit masks, one per hop."""
+        h, comm = x, None
+        for hop in range(self.num_hops):
+            if hop > 0:
+                h = self.comm.msg_state2state(torch.cat([comm, h], dim=2))
+            key, value, query = self.comm.hidden2key(h), self.comm.hidden2value(h), self.comm.hidden2query(h)
+            scores = torch.matmul(query, key.transpose(-2, -1)) / math.sqrt(self.num_key)
+            s = scores - scores.max(dim=-1, keepdim=True)[0]                         # MaskedSoftmax, utils.py:1353-1358
+            e = torch.exp(s) * mask[hop].to(s.dtype)
+            attn = e / e.sum(dim=-1, keepdim=True)
+            attn = torch.where(torch.isnan(attn), torch.zeros_like(attn), attn)
+            comm = torch.matmul(attn, value)
+        return self.comm_hidden2action(torch.cat([x, comm], dim=2))
+
     # ------------------------------------------------------------------------------------------------------------------- band
     def _check_band(self, nb_agents: Optional[int]):
         if self.num_action != 2:
@@ -274,13 +411,15 @@ class TarMACActor(nn.Module):
         c = self.number_agents_comm if nb_agents is None else min(self.number_agents_comm, nb_agents - 1)
         if self.comm_mode == "neighbours" and nb_agents is not None and c > MAX_COMM:
             raise ValueError("band attention covers at most %d senders per receiver" % MAX_COMM)
+        if self.comm_mode == "random_sample" and nb_agents is not None and c > MAX_COMM:
+            raise ValueError("gather attention draws at most %d senders per receiver" % MAX_COMM)
 
     def _use_band(self, obs) -> bool:
         if self.attention == "dense":
             return False
         if not obs.is_cuda:
-            if self.attention == "band":
-                raise ValueError("attention='band' needs the observations and the parameters on the GPU")
+            if self.attention in ("band", "gather"):
+                raise ValueError("attention=%r needs the observations and the parameters on the GPU" % self.attention)
             return False
         return True
 
@@ -361,6 +500,10 @@ class TarMACActor(nn.Module):
             torch.tanh_(b["t3"])
             torch.addmm(b2, b["t3"], w2, out=qkv)
             q, k, v = qkv[:, :K], qkv[:, K:2 * K], qkv[:, 2 * K:]
+            if self.comm_mode in GATHER_MODES:      # attention="gather": the same buffers, the other entry point
+                _gather_call(lib, q, k, v, qkv.stride(0), qkv.stride(0), qkv.stride(0), E, N, K, V, self.number_agents_comm,
+                             GATHER_MODES[self.comm_mode], seed, step, step_dev, hop, comm, cat.stride(0), dev)
+                continue
             with torch.cuda.device(dev):
                 rc = lib.mdr_tarmac_comm(C.c_void_p(q.data_ptr()), qkv.stride(0), C.c_void_p(k.data_ptr()), qkv.stride(0),
                                          C.c_void_p(v.data_ptr()), qkv.stride(0), E, N, K, V, self.number_agents_comm, MODES[self.comm_mode],
@@ -387,7 +530,10 @@ class TarMACActor(nn.Module):
             if hop > 0:
                 h = self.comm.msg_state2state(torch.cat([comm, h], dim=2))
             key, value, query = self.comm.hidden2key(h), self.comm.hidden2value(h), self.comm.hidden2query(h)
-            comm = band_attention(query, key, value, self.number_agents_comm, self.comm_mode, self.comm_defect_prob, seed, step, step_dev, hop)
+            if self.comm_mode in GATHER_MODES:
+                comm = gather_attention(query, key, value, self.number_agents_comm, self.comm_mode, seed, step, step_dev, hop)
+            else:
+                comm = band_attention(query, key, value, self.number_agents_comm, self.comm_mode, self.comm_defect_prob, seed, step, step_dev, hop)
         return self.comm_hidden2action(torch.cat([x, comm], dim=2))
 
     def _head(self, logits, seed, step, step_dev, greedy, want_probs, action=None, a_prob=None):
@@ -411,28 +557,31 @@ class TarMACActor(nn.Module):
 
     # ----------------------------------------------------------------------------------------------------------------- public
     def forward(self, obs: torch.Tensor, dead=None, seed: int = 0, step: int = 0, step_dev: Optional[torch.Tensor] = None,
-                differentiable: bool = False) -> torch.Tensor:
+                differentiable: bool = False, mask=None) -> torch.Tensor:
         """``obs`` [E, N, F] -> probabilities [E, N, 2] (TarMAC_Actor.forward).  Band path: float32 on the GPU, ``seed`` / ``step``
         key the defect draws; no gradients unless ``differentiable`` - then the result backpropagates into every parameter and into
         ``obs`` through ``band_attention`` (the update step: see the module docstring; with defects, fresh draws keyed by
-        ``(seed, step)`` with the batch row as the env).  Dense path: differentiable either way; ``dead`` as in ``dense_logits``."""
+        ``(seed, step)`` with the batch row as the env).  ``attention="gather"`` (comm modes "all" / "random_sample") is the band path
+        with ``mdr_tarmac_gather`` / ``gather_attention`` in the attention's place; ``seed`` / ``step`` key the sender sets, one draw per
+        env.  Dense path (also whenever ``dead`` or ``mask`` is given): differentiable either way; ``dead``, ``mask`` as in
+        ``dense_logits``."""
         if obs.dim() != 3:
             raise ValueError("TarMAC attends over the agents of an env: obs must be [E, N, F]")
-        if dead is None and self._use_band(obs):
+        if dead is None and mask is None and self._use_band(obs):
             if differentiable:
                 return F.softmax(self._band_logits_grad(obs, seed, step, step_dev), dim=-1)
             logits = self._band_logits(obs, seed, step, step_dev)
             return self._head(logits, seed, step, step_dev, False, True)[2].view(obs.shape[0], obs.shape[1], 2)
-        return F.softmax(self.dense_logits(obs, dead), dim=-1)
+        return F.softmax(self.dense_logits(obs, dead, mask), dim=-1)
 
     @torch.no_grad()
     def sample(self, obs: torch.Tensor, seed: int, step: int, step_dev: Optional[torch.Tensor] = None, greedy: bool = False,
                dead=None, want_probs: bool = False, action: Optional[torch.Tensor] = None,
-               a_prob: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
+               a_prob: Optional[torch.Tensor] = None, mask=None) -> Tuple[torch.Tensor, ...]:
         """``TarmacPPO.select_actions`` (agents/tarmac_ppo.py:83-95) for every env at once: ``obs`` float32 [E, N, F] on the GPU ->
         (action uint8 [E * N], a_prob float32 [E * N][, probs [E * N, 2]]).  The draw is the one of ``FusedActor.sample`` for the same
         (seed, step, agent); ``step_dev`` (device int32) is added to ``step`` inside the kernels.  ``greedy``: the argmax, the first
-        maximum on ties.  The dense path (``attention="dense"``, or ``dead`` given) evaluates the reference's formula in torch
+        maximum on ties.  The dense path (``attention="dense"``, or ``dead`` / ``mask`` given) evaluates the reference's formula in torch
         and samples with the same kernel."""
         if not obs.is_cuda:
             raise ValueError("sampling runs on the GPU (mdr_logits_sample); the dense forward() is the CPU path")
@@ -440,10 +589,10 @@ class TarMACActor(nn.Module):
             raise ValueError("sampling covers two actions")
         if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.device != obs.device):
             raise ValueError("step_dev must be an int32 tensor on the device (env.device_time_index)")
-        if dead is None and self._use_band(obs):
+        if dead is None and mask is None and self._use_band(obs):
             logits = self._band_logits(obs, seed, step, step_dev)
         else:
-            logits = self.dense_logits(obs, dead).reshape(-1, 2).float().contiguous()
+            logits = self.dense_logits(obs, dead, mask).reshape(-1, 2).float().contiguous()
         action, a_prob, probs = self._head(logits, seed, step, step_dev, greedy, want_probs, action, a_prob)
         return (action, a_prob, probs) if want_probs else (action, a_prob)
 
