@@ -27,6 +27,9 @@
  * Likewise mdr_env_rollout_resident: whether mdr_env_rollout keeps the houses in registers between its interior steps.
  * Likewise mdr_env_mlp_actor_sample and mdr_env_mlp_actor_sample_bf16x3 (mdr_policy.h): the 256-unit actor fed from the env's
  * compact state.
+ * Likewise mdr_env_bind_rollout_rows with mdr_rollout_rows, mdr_env_rollout_steps_per_launch and mdr_env_fill_rollout_rows: the
+ * resident launches of mdr_env_rollout read their two table values per step from rows built for the launch, and no longer end where
+ * the time tables end.  Without rows bound mdr_env_rollout takes its per-step form.
  */
 #ifndef MDR_H
 #define MDR_H
@@ -321,11 +324,34 @@ int mdr_env_bind_thermal_pack(mdr_env_t *env, uint32_t *pack, uint32_t *desc);
  * store (-1: the rollout runs full steps only), *packed = 1 when they read the thermal pack.  Either pointer may be NULL. */
 int mdr_env_rollout_plan(const mdr_env_t *env, int32_t *planes, int32_t *packed);
 /* *resident = 1 when the next mdr_env_rollout on this handle runs its interior steps with the houses resident in registers - one
- * launch per table window instead of one per step, the same bits: wherever mdr_env_rollout_plan reports interior steps (planes >= 0)
- * and nb_envs * nb_houses is at or above MDR_ROLLOUT_RESIDENT_HOUSES (environment, read once; default 1 << 20; 0 = every batch),
- * unless MDR_ROLLOUT_RESIDENT (environment, read once) is 0.  mdr_env_rollout_plan's answers are what the per-step form would run;
- * its `packed` also says whether the resident launches read the thermal pack.  The pointer may be NULL. */
+ * launch per mdr_env_rollout_steps_per_launch() steps instead of one per step, the same bits: wherever mdr_env_rollout_plan reports
+ * interior steps (planes >= 0), rollout rows are bound (mdr_env_bind_rollout_rows) and nb_envs * nb_houses is at or above
+ * MDR_ROLLOUT_RESIDENT_HOUSES (environment, read once; default 1 << 20; 0 = every batch), unless MDR_ROLLOUT_RESIDENT (environment,
+ * read once) is 0.  mdr_env_rollout_plan's answers are what the per-step form would run; its `packed` also says whether the
+ * resident launches read the thermal pack.  The pointer may be NULL.  (A call made while `stream` is being captured runs the
+ * per-step form whatever this says.) */
 int mdr_env_rollout_resident(const mdr_env_t *env, int32_t *resident);
+/* Optional: scratch for mdr_env_rollout's resident launches (mdr_env_rollout_resident), the "rollout rows":
+ *   rows  float [nrows][nb_envs][2] on the device, 8-byte aligned, nrows >= 2
+ * For every step of a launch and every env the two table values the step reads - {tab_od of the step's time index, tab_solar of the
+ * next} - built on the caller's stream in front of the launch from the handle's current (seed, episode, t0, phase, od table, time
+ * index), bit for bit what the time tables hold there.  A launch then runs up to mdr_env_rollout_steps_per_launch() steps instead of
+ * ending where the time tables end; the tables are refilled once, by the full step that ends the rollout.  Nothing in the rows
+ * outlives the call that wrote them: they are no part of the state.  Without them mdr_env_rollout runs every interior step as a
+ * launch of its own.  NULL turns them off; mdr_env_bind drops the binding (bind again after it).
+ * mdr_rollout_rows: the rows to hand over for nb_envs envs - 1024 steps per launch plus one spare row (the loop loads one row ahead),
+ * fewer where that would pass 64 MiB (never below two), fewer where MDR_ROLLOUT_ROWS (environment, read once: steps per launch,
+ * >= 1) says so.  Rows beyond that count are not used. */
+int64_t mdr_rollout_rows(int32_t nb_envs);
+int mdr_env_bind_rollout_rows(mdr_env_t *env, float *rows, int64_t nrows);
+/* *steps = the interior steps one resident launch of mdr_env_rollout runs at most: the rows bound less the spare one, at most
+ * mdr_rollout_rows(nb_envs) - 1, clipped so that time_step x steps < 2^31 (the lane of a blank house counts its seconds-since-off up by time_step per step of a launch); 0 where
+ * mdr_env_rollout_resident reports 0 - every interior step is then a launch of its own. */
+int mdr_env_rollout_steps_per_launch(const mdr_env_t *env, int64_t *steps);
+/* dst [nrows][nb_envs][2] floats on the device <- the rollout rows of nrows steps from time index k of the current episode, as
+ * mdr_env_rollout builds them: dst[r][e] = {tab_od[e] at time index k + r, tab_solar[e] at k + r + 1}.  Needs an episode
+ * (reset / load_episode); reads no table and moves no cursor.  1 <= nrows <= 1 << 20, k >= 0. */
+int mdr_env_fill_rollout_rows(mdr_env_t *env, int64_t k, int32_t nrows, float *dst, void *stream);
 /* Optional: replace ClusterHouses.compute_OD_temp (env 1057-1081, incl. its random.gauss draw 1079) by a table, double [rows][E] deg C (row = time index);
  * NULL restores the model.  Takes effect at the next mdr_env_begin_episode / table refill; mdr_env_reset (a freshly sampled
  * episode) drops it. */

@@ -200,6 +200,7 @@ EXPORTS = (
     "mdr_abi_version", "mdr_status_string", "mdr_last_error", "mdr_partials_per_env", "mdr_env_partial_records",
     "mdr_env_create", "mdr_env_destroy", "mdr_env_bind", "mdr_env_reset", "mdr_env_load_episode", "mdr_env_params_changed", "mdr_env_bind_hvac_code",
     "mdr_env_bind_thermal_pack", "mdr_env_rollout_plan", "mdr_env_rollout_resident",
+    "mdr_rollout_rows", "mdr_env_bind_rollout_rows", "mdr_env_rollout_steps_per_launch", "mdr_env_fill_rollout_rows",
     "mdr_env_set_od_table", "mdr_env_set_interp_grid", "mdr_env_begin_episode", "mdr_env_refresh_obs", "mdr_env_step", "mdr_env_rollout", "mdr_env_rollout_fused",
     "mdr_env_step_begin", "mdr_env_step_end", "mdr_env_step_end_gathered", "mdr_env_step_begin_records", "mdr_env_step_end_records", "mdr_env_step_end_begin_records",
     "mdr_env_interp_due", "mdr_env_interp_local", "mdr_env_interp_apply", "mdr_obs_vector_length", "mdr_env_obs_vector",
@@ -275,6 +276,10 @@ def load():
         "mdr_env_bind_thermal_pack": (C.c_int, [vp, vp, vp]),
         "mdr_env_rollout_plan": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "mdr_env_rollout_resident": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+        "mdr_rollout_rows": (i64, [i32]),
+        "mdr_env_bind_rollout_rows": (C.c_int, [vp, vp, i64]),
+        "mdr_env_rollout_steps_per_launch": (C.c_int, [vp, C.POINTER(i64)]),
+        "mdr_env_fill_rollout_rows": (C.c_int, [vp, i64, i32, vp, vp]),
         "mdr_env_set_od_table": (C.c_int, [vp, vp, i64]),
         "mdr_env_set_interp_grid": (C.c_int, [vp, C.POINTER(MdrInterpGrid)]),
         "mdr_env_begin_episode": (C.c_int, [vp, vp]),

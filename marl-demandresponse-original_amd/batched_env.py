@@ -47,7 +47,7 @@ class BatchedDemandResponseEnv:
                  stagger_bytes: int = 2304, interp_grid=None, regenerate_missing_grid: bool = True,
                  graph_mode: bool = False, exchange_always: bool = False, partial_records: Optional[int] = None,
                  obs_planes: bool = True, prefetch_tables: bool = True, exchange=None, uniform_params: bool = True, hvac_code: bool = True,
-                 thermal_pack: bool = True):
+                 thermal_pack: bool = True, rollout_rows: bool = True):
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedDemandResponseEnv needs a ROCm device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
@@ -98,6 +98,11 @@ class BatchedDemandResponseEnv:
         # whenever every column has one sign, no NaN and a range that fits its field (found on the device at reset / load_episode /
         # params_changed()); False binds nothing: the five columns are streamed
         self._thermal_pack = bool(thermal_pack)
+        # rollout_rows: bind rollout rows (mdr_env_bind_rollout_rows) - scratch for the two table values per env and step that a resident launch of
+        # rollout() reads (large batches, rollout_resident()): a launch then runs up to rollout_steps_per_launch() steps instead of
+        # ending with the time tables.  Not where rollout() has no resident form (sharded houses, graph mode, interpolation mode);
+        # False binds NULL: the interior steps of rollout() are one launch each
+        self._rollout_rows = bool(rollout_rows) and house_shard is None and not self.graph_mode and self.spec.base_power_mode != 1
         self._handle = C.c_void_p()
         self._cfg = self._make_config()
         rc = self._lib.mdr_env_create(C.byref(self._cfg), C.byref(self._handle))
@@ -201,6 +206,9 @@ class BatchedDemandResponseEnv:
         if self._thermal_pack:      # derived from k01 / s0 / k10 / s1 / inv_Ua, likewise outside the slab: 16 B per house
             self.t["thermal_pack"] = torch.zeros((4, self.nb_envs, self.nb_houses), dtype=torch.int32, device=self.device)
             self.t["thermal_desc"] = torch.zeros((nat.MDR_THERMAL_DESC_WORDS,), dtype=torch.int32, device=self.device)      # word 0 == 0: not packed yet
+        if self._rollout_rows:      # scratch that every rollout() rebuilds before it reads it, never part of a snapshot: outside the slab as well
+            rows = int(self._lib.mdr_rollout_rows(self.nb_envs))
+            self.t["rollout_rows"] = torch.zeros((rows, self.nb_envs, 2), dtype=torch.float32, device=self.device)
 
     def _grow_partials(self, records: int) -> None:
         """Raise the record stride of `partials` to the group's maximum (a fresh zero-filled scratch buffer, re-bound)."""
@@ -232,6 +240,9 @@ class BatchedDemandResponseEnv:
         if self._thermal_pack:   # likewise
             rc = self._lib.mdr_env_bind_thermal_pack(self._handle, self.t["thermal_pack"].data_ptr(), self.t["thermal_desc"].data_ptr())
             nat.check(self._lib, self._handle, rc, "mdr_env_bind_thermal_pack")
+        if self._rollout_rows:   # likewise
+            rc = self._lib.mdr_env_bind_rollout_rows(self._handle, self.t["rollout_rows"].data_ptr(), self.t["rollout_rows"].shape[0])
+            nat.check(self._lib, self._handle, rc, "mdr_env_bind_rollout_rows")
 
     def rollout_plan(self) -> Tuple[int, bool]:
         """What the interior steps of the next ``rollout()`` run: (local obs planes they still store, or -1 when every step is a full
@@ -241,11 +252,27 @@ class BatchedDemandResponseEnv:
         return int(planes.value), bool(packed.value)
 
     def rollout_resident(self) -> bool:
-        """Whether the next ``rollout()`` runs its interior steps with the houses resident in registers, one launch per table window
-        (large batches) - mdr_env_rollout_resident."""
+        """Whether the next ``rollout()`` runs its interior steps with the houses resident in registers, one launch per
+        ``rollout_steps_per_launch()`` steps (large batches) - mdr_env_rollout_resident."""
         resident = C.c_int32()
         nat.check(self._lib, self._handle, self._lib.mdr_env_rollout_resident(self._handle, C.byref(resident)), "mdr_env_rollout_resident")
         return bool(resident.value)
+
+    def rollout_steps_per_launch(self) -> int:
+        """The interior steps one resident launch of ``rollout()`` runs at most (0: ``rollout_resident()`` is False, every interior step is
+        a launch of its own) - mdr_env_rollout_steps_per_launch."""
+        steps = C.c_int64()
+        nat.check(self._lib, self._handle, self._lib.mdr_env_rollout_steps_per_launch(self._handle, C.byref(steps)), "mdr_env_rollout_steps_per_launch")
+        return int(steps.value)
+
+    def fill_rollout_rows(self, k: int, nrows: int) -> torch.Tensor:
+        """float32 [nrows][nb_envs][2]: the rollout rows of `nrows` steps from time index `k` of the current episode, as ``rollout()``
+        builds them - {tab_od at time index k + r, tab_solar at k + r + 1} - mdr_env_fill_rollout_rows."""
+        out = torch.empty((int(nrows), self.nb_envs, 2), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.mdr_env_fill_rollout_rows(self._handle, int(k), int(nrows), out.data_ptr(), self._stream())
+        nat.check(self._lib, self._handle, rc, "mdr_env_fill_rollout_rows")
+        return out
 
     def set_obs_planes(self, on: bool) -> None:
         """Switch the seven per-step observation planes on or off (a re-bind: mdr_buffers_t.obs = NULL skips their 28 B per
@@ -1008,7 +1035,7 @@ class BatchedDemandResponseEnv:
         other = BatchedDemandResponseEnv(copy.deepcopy(self.config, memo), nb_envs=self.nb_envs, device=self.device,
                                          seed=self.seed, test=self.test, table_steps=self.table_steps, obs_planes=self._obs_planes_alloc,
                                          prefetch_tables=self._prefetch_tables, uniform_params=self._uniform_params, hvac_code=self._hvac_code,
-                                         thermal_pack=self._thermal_pack,
+                                         thermal_pack=self._thermal_pack, rollout_rows=self._rollout_rows,
                                          env_offset=self.env_offset,
                                          house_shard=(self.house_offset, self.nb_houses) if self.sharded else None,
                                          exchange_always=self._exchange_always, partial_records=self._partial_records,

@@ -7,7 +7,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ("mdr_kernels.hip", "mdr_resident.hip", "mdr_multi.hip", "mdr_persist.hip", "mdr_mailbox.hip", "mdr_control.hip", "mdr_api.hip", "mdr_policy.hip", "mdr_tarmac.hip", "mdr_tarmac_mlp.hip", "mdr_tarmac_mlp_bf16.hip", "mdr_tarmac_grad.hip", "mdr_tarmac_gather.hip", "mdr_ppo_grad.hip", "mdr_tarmac_ppo_grad.hip", "mdr_optim.hip", "mdr_maddpg_grad.hip", "mdr_mlp_actor.hip", "mdr_mlp_actor_bf16.hip", "mdr_mlp_actor_observe.hip", "mdr_tarmac_critic_grad.hip", "mdr_tarmac_a2c.hip", "mdr_minibatch.hip")
+SOURCES = ("mdr_kernels.hip", "mdr_resident.hip", "mdr_rollout_rows.hip", "mdr_multi.hip", "mdr_persist.hip", "mdr_mailbox.hip", "mdr_control.hip", "mdr_api.hip", "mdr_policy.hip", "mdr_tarmac.hip", "mdr_tarmac_mlp.hip", "mdr_tarmac_mlp_bf16.hip", "mdr_tarmac_grad.hip", "mdr_tarmac_gather.hip", "mdr_ppo_grad.hip", "mdr_tarmac_ppo_grad.hip", "mdr_optim.hip", "mdr_maddpg_grad.hip", "mdr_mlp_actor.hip", "mdr_mlp_actor_bf16.hip", "mdr_mlp_actor_observe.hip", "mdr_tarmac_critic_grad.hip", "mdr_tarmac_a2c.hip", "mdr_minibatch.hip")
 HEADERS = ("mdr_device.h", "mdr_kernels.h", "mdr_step_common.h", "mdr_mailbox.h", "mdr_draw.h", "mdr_bf16_split.h", "mdr_tarmac_mlp.h", "mdr_observe.h", "mdr_grad_reduce.h", "mdr_stream_mlp.h", os.path.join("..", "..", "include", "mdr.h"), os.path.join("..", "..", "include", "mdr_policy.h"))
 OUTPUT = os.path.join(CSRC, "libmdr_hip.so")
 
@@ -32,10 +32,12 @@ def is_stale() -> bool:
 # "fast" lets the back end fuse depending on the surrounding code)
 FLAGS = ("--offload-arch=gfx950", "-O3", "-ffp-contract=on", "-std=c++17", "-fPIC")
 # Extra flags of single translation units, behind FLAGS, in the product library and in every experiment build alike.
-# None today.  The one candidate measured so far, {"mdr_resident.hip": ("-fno-slp-vectorize",)} - the resident rollout loop in plain
-# f32 instructions instead of v_pk_*_f32 pairs, the same bits - was 4.5 - 4.8 % faster in bench.py, 1.5 and 2.3 times the run-to-run
-# spread where the project asks for 3 (profiles/r11_README.md section 2); build_variant(name, source_flags=...) rebuilds that arm.
-SOURCE_FLAGS = {}
+# mdr_resident.hip with -fno-slp-vectorize: the resident rollout loop in plain f32 instructions instead of v_pk_*_f32 pairs, the same
+# bits (bench.py's dumps are byte-identical).  With one launch per table window it was 4.5 - 4.8 % faster in bench.py, 1.5 and 2.3
+# times the run-to-run spread where the project asks for 3 (profiles/r11_README.md section 2), and stayed out; with one launch per
+# rollout the loop is nine tenths of the time and the difference is 10 %, 5.5 and 6.1 times the larger spread in two sets of five
+# (profiles/r12_README.md section 2).  build_variant(name, source_flags={}) rebuilds the packed arm.
+SOURCE_FLAGS = {"mdr_resident.hip": ("-fno-slp-vectorize",)}
 
 
 def _compile_and_link(out: str, objdir: str, defines=(), source_flags=None, force: bool = False, verbose: bool = False) -> str:

@@ -30,6 +30,8 @@ struct mdr_env {
   uint32_t* hvac_dict = nullptr;
   uint32_t* thermal_pack = nullptr;   // mdr_env_bind_thermal_pack; mdr_env_bind drops both
   uint32_t* thermal_desc = nullptr;
+  float* rollout_rows = nullptr;      // mdr_env_bind_rollout_rows; mdr_env_bind drops it
+  int64_t rollout_rows_n = 0;
   bool has_episode = false;   // per-house parameters present
   bool has_tables = false;    // begin_episode done
   bool split_pending = false; // step_begin issued, step_end outstanding
@@ -199,15 +201,10 @@ void use_tables(mdr_env* env, int which) {
   env->buf.tab_abs_noise = env->tabs[which].abs_noise;
 }
 
-// `into` == nullptr: the tables the steps read (the active set) from time index j0, on the caller's stream; else a prefetch into
-// the other set (the host cursor does not move)
-int fill_tables(mdr_env* env, int64_t j0, hipStream_t s, const mdr_env::TableSet* into = nullptr) {
+// What the time tables of `rows` time indices from j0 are functions of (the table pointers stay NULL: the caller's)
+mdr::TableArgs table_args(const mdr_env* env, int64_t j0, int rows) {
   const mdr_config_t& c = env->cfg;
   mdr::TableArgs t{};
-  t.tab_od = into ? into->od : env->buf.tab_od;
-  t.tab_solar = into ? into->solar : env->buf.tab_solar;
-  t.tab_signal = into ? into->signal : env->buf.tab_signal;
-  t.tab_abs_noise = into ? into->abs_noise : env->buf.tab_abs_noise;
   t.t0 = env->buf.t0;
   t.phase = env->buf.phase;
   t.ratio = env->buf.ratio;
@@ -215,7 +212,7 @@ int fill_tables(mdr_env* env, int64_t j0, hipStream_t s, const mdr_env::TableSet
   t.od_ext = env->od_ext;
   t.od_ext_rows = env->od_ext_rows;
   t.j0 = j0;
-  t.rows = c.table_steps + 1;
+  t.rows = rows;
   t.E = c.nb_envs;
   t.dt = c.time_step;
   t.env_offset = c.env_offset;
@@ -243,6 +240,17 @@ int fill_tables(mdr_env* env, int64_t j0, hipStream_t s, const mdr_env::TableSet
   t.perlin_amp = c.perlin_amplitude;
   t.perlin_step = c.perlin_octaves_step;
   t.perlin_period = c.perlin_period;
+  return t;
+}
+
+// `into` == nullptr: the tables the steps read (the active set) from time index j0, on the caller's stream; else a prefetch into
+// the other set (the host cursor does not move)
+int fill_tables(mdr_env* env, int64_t j0, hipStream_t s, const mdr_env::TableSet* into = nullptr) {
+  mdr::TableArgs t = table_args(env, j0, env->cfg.table_steps + 1);
+  t.tab_od = into ? into->od : env->buf.tab_od;
+  t.tab_solar = into ? into->solar : env->buf.tab_solar;
+  t.tab_signal = into ? into->signal : env->buf.tab_signal;
+  t.tab_abs_noise = into ? into->abs_noise : env->buf.tab_abs_noise;
   hipError_t e = mdr::launch_tables(t, s);
   if (e != hipSuccess) return hip_fail(env, e, "fill_tables");
   if (into == nullptr) {
@@ -370,8 +378,9 @@ void graph_rows(const mdr_env* env, mdr::StepArgs* a) {
 // current time index, and the reg_signal observation plane of the step just taken re-written with the final signal.
 int interp_boundary(mdr_env* env, hipStream_t s, double* sq_signal_error_sum);
 
-// Builds the argument block of step k -> k+1, refilling the time tables when the cursor leaves them.
-int step_args(mdr_env* env, uint8_t* actions, int action_source, hipStream_t s, mdr::StepArgs* out) {
+// Builds the argument block of step k -> k+1, refilling the time tables when the cursor leaves them.  `table_rows` false: for a
+// launch that reads no table row (the resident rollout reads its rollout rows) - no refill, and the four row pointers stay NULL.
+int step_args(mdr_env* env, uint8_t* actions, int action_source, hipStream_t s, mdr::StepArgs* out, bool table_rows = true) {
   const mdr_config_t& c = env->cfg;
   if (!env->bound) return fail(env, MDR_ERR_UNBOUND, "buffers not bound");
   if (!env->has_tables) return fail(env, MDR_ERR_UNBOUND, "no episode: call reset/load_episode and begin_episode first");
@@ -382,7 +391,7 @@ int step_args(mdr_env* env, uint8_t* actions, int action_source, hipStream_t s, 
     return fail(env, MDR_ERR_INVALID, "actions must be 4-byte aligned when nb_houses is a multiple of 4");
   if (actions && c.nb_houses % 2 == 0 && ((uintptr_t)actions & 1u) != 0)  // uchar2 accesses when N is even
     return fail(env, MDR_ERR_INVALID, "actions must be 2-byte aligned when nb_houses is even");
-  if (env->k + 1 - env->j0 > c.table_steps) {
+  if (table_rows && env->k + 1 - env->j0 > c.table_steps) {
     if (capturing(s)) return fail(env, MDR_ERR_INVALID, "the time tables end here: a refill cannot be captured (mdr_env_graph_room() is 0)");
     int rc;
     if (env->prefetched && env->prefetch_j0 == env->k) {   // built meanwhile on the side stream: wait for it (long done) and swap the sets
@@ -410,10 +419,12 @@ int step_args(mdr_env* env, uint8_t* actions, int action_source, hipStream_t s, 
   a.actions = actions;
   a.reward = b.reward; a.obs = b.obs;
   a.P = b.P; a.tot_sum = b.tot_sum; a.tot_max = b.tot_max; a.partials = b.partials;
-  a.od_old = b.tab_od + r0 * c.nb_envs;
-  a.solar_new = b.tab_solar + r1 * c.nb_envs;
-  a.sig_old = b.tab_signal + r0 * c.nb_envs;
-  a.sig_new = b.tab_signal + r1 * c.nb_envs;
+  if (table_rows) {
+    a.od_old = b.tab_od + r0 * c.nb_envs;
+    a.solar_new = b.tab_solar + r1 * c.nb_envs;
+    a.sig_old = b.tab_signal + r0 * c.nb_envs;
+    a.sig_new = b.tab_signal + r1 * c.nb_envs;
+  }
   a.plane = (int64_t)c.nb_envs * c.nb_houses;
   a.E = c.nb_envs; a.N = c.nb_houses; a.dt = c.time_step;
   a.penalty_mode = c.penalty_mode;
@@ -525,6 +536,8 @@ int mdr_env_bind(mdr_env_t* env, const mdr_buffers_t* buffers) {
   env->hvac_dict = nullptr;
   env->thermal_pack = nullptr;   // likewise: mdr_env_bind_thermal_pack again
   env->thermal_desc = nullptr;
+  env->rollout_rows = nullptr;   // likewise: mdr_env_bind_rollout_rows again
+  env->rollout_rows_n = 0;
   env->tabs[0] = t0;
   env->tabs[1] = t1;
   env->has_alt = all2;
@@ -876,16 +889,64 @@ static bool rollout_resident(const mdr_env_t* env, const InteriorPlan& ip) {
     const long long v = strtoll(t, &end, 10);
     return (end && *end == '\0' && v >= 0) ? (int64_t)v : (int64_t)1 << 20;
   }();
-  // ... and time_step x table_steps < 2^31: a launch covers at most table_steps steps, and in it the lane of a blank house (a lane past
-  // the env's end) counts its never-stored seconds-since-off up by time_step per step without a reset.  Longer tables: the per-step path.
-  return resident_on && ip.planes >= 0 && mdr::rollout_resident_supported(env->plan) &&
-         (int64_t)env->cfg.nb_envs * env->cfg.nb_houses >= resident_houses &&
-         (int64_t)env->cfg.time_step * env->cfg.table_steps < ((int64_t)1 << 31);
+  // ... and the rollout rows are bound: the resident launches read nothing else (mdr_env_bind_rollout_rows)
+  return resident_on && ip.planes >= 0 && mdr::rollout_resident_supported(env->plan) && env->rollout_rows != nullptr &&
+         (int64_t)env->cfg.nb_envs * env->cfg.nb_houses >= resident_houses;
+}
+
+// Steps per resident launch: what the bound rollout rows hold (one row is a spare; mdr_rollout_rows' count at most, so that
+// MDR_ROLLOUT_ROWS binds whatever the caller handed over), and time_step x steps < 2^31 - in a
+// launch the lane of a blank house (a lane past the env's end) counts its never-stored seconds-since-off up by time_step per step
+// without a reset.
+static int64_t resident_steps(const mdr_env_t* env) {
+  const int64_t held = std::min<int64_t>(env->rollout_rows_n, mdr_rollout_rows(env->cfg.nb_envs)) - 1;
+  return std::max<int64_t>(1, std::min<int64_t>(held, (((int64_t)1 << 31) - 1) / env->cfg.time_step));
 }
 
 int mdr_env_rollout_resident(const mdr_env_t* env, int32_t* resident) {
   if (!env) return MDR_ERR_INVALID;
   if (resident) *resident = rollout_resident(env, interior_plan(env)) ? 1 : 0;
+  return MDR_OK;
+}
+
+int64_t mdr_rollout_rows(int32_t nb_envs) {
+  static const int64_t knob = [] {   // MDR_ROLLOUT_ROWS: steps per launch (the tests force short launches); 0 = unset
+    const char* t = getenv("MDR_ROLLOUT_ROWS");
+    if (!t || t[0] < '0' || t[0] > '9') return (int64_t)0;
+    char* end = nullptr;
+    const long long v = strtoll(t, &end, 10);
+    return (end && *end == '\0' && v >= 1) ? (int64_t)v : (int64_t)0;
+  }();
+  if (nb_envs < 1) return 0;
+  const int64_t budget = ((int64_t)64 << 20) / ((int64_t)nb_envs * 2 * (int64_t)sizeof(float));   // rows within 64 MiB
+  int64_t steps = std::min<int64_t>(1024, budget - 1);
+  if (knob > 0) steps = std::min(steps, knob);
+  return std::max<int64_t>(steps, 1) + 1;
+}
+
+int mdr_env_bind_rollout_rows(mdr_env_t* env, float* rows, int64_t nrows) {
+  if (!env) return MDR_ERR_INVALID;
+  if (!env->bound) return fail(env, MDR_ERR_UNBOUND, "buffers not bound");
+  if (rows != nullptr && (nrows < 2 || ((uintptr_t)rows & 7u) != 0))
+    return fail(env, MDR_ERR_INVALID, "rollout rows: at least two rows, 8-byte aligned");
+  env->rollout_rows = rows;
+  env->rollout_rows_n = rows ? nrows : 0;
+  return MDR_OK;
+}
+
+int mdr_env_rollout_steps_per_launch(const mdr_env_t* env, int64_t* steps) {
+  if (!env) return MDR_ERR_INVALID;
+  if (steps) *steps = rollout_resident(env, interior_plan(env)) ? resident_steps(env) : 0;
+  return MDR_OK;
+}
+
+int mdr_env_fill_rollout_rows(mdr_env_t* env, int64_t k, int32_t nrows, float* dst, void* stream) {
+  if (!env) return MDR_ERR_INVALID;
+  if (!env->bound || !env->has_episode) return fail(env, MDR_ERR_UNBOUND, "no episode: call reset/load_episode first");
+  if (!dst || ((uintptr_t)dst & 7u) != 0) return fail(env, MDR_ERR_INVALID, "dst is NULL or not 8-byte aligned");
+  if (k < 0 || nrows < 1 || nrows > (1 << 20)) return fail(env, MDR_ERR_INVALID, "k must be >= 0 and nrows in 1 .. 1 << 20");
+  const hipError_t e = mdr::launch_rollout_rows(table_args(env, k, nrows), reinterpret_cast<float2*>(dst), (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(env, e, "fill_rollout_rows");
   return MDR_OK;
 }
 
@@ -900,26 +961,33 @@ int mdr_env_rollout(mdr_env_t* env, uint8_t* actions, int action_source, int32_t
   // Interior steps: between the steps of this loop nothing can look at reward / obs / actions / P, and the next launch on the stream
   // overwrites every one of them - so steps 0 .. nb_steps - 2 run an interior form, which stores none of the outputs behind the
   // env-wide reduction, and the last step is a full one.  Two interior forms, chosen by size (rollout_resident):
-  //   at or above MDR_ROLLOUT_RESIDENT_HOUSES houses   k_rollout_resident: the houses stay in registers over every step the current
-  //       tables cover - the state and the parameters cross HBM once per table window instead of once per step (mdr_resident.hip;
-  //       only while time_step x table_steps < 2^31, rollout_resident: otherwise the per-step path below);
+  //   at or above MDR_ROLLOUT_RESIDENT_HOUSES houses   k_rollout_resident: the houses stay in registers over up to resident_steps()
+  //       steps - the state and the parameters cross HBM once per launch instead of once per step (mdr_resident.hip).  The two table
+  //       values a step reads come from the rollout rows, built here in front of each launch for exactly its steps from the handle's
+  //       current (seed, episode, t0, phase, od table, k) - nothing is kept between calls.  The time tables are not touched: the
+  //       launches run past their end, and the full last step finds the cursor outside them and refills once from env->k (step_args);
+  //       a prefetch issued for a window the launches skipped is superseded there (fill_tables) like any other stale one.
+  //       Not inside a capture (the per-step path below, which stops where the tables end as it always did);
   //   below it   one interior launch of k_step_fused / k_step_group per step (interior_plan), exactly as before.
   // Why a size rule and not the resident form everywhere: tests/test_gpu_bench.py bounds bench.py's roofline.frac - a fixed 99 B per
   // house-step over the time - below 1.25 at 512 envs x 1024 houses, and a step that moves no state through memory passes it many
   // times over.  At or above 1 << 20 houses no test binds and the interior plan already differs (the r08 / r09 criterion).
   const InteriorPlan ip = interior_plan(env);
-  if (rollout_resident(env, ip) && nb_steps > 1) {
+  if (rollout_resident(env, ip) && nb_steps > 1 && !capturing((hipStream_t)stream)) {
     if (env->split_pending) return fail(env, MDR_ERR_INVALID, "step_begin without step_end");
+    const int64_t capacity = resident_steps(env);
+    float2* rows = reinterpret_cast<float2*>(env->rollout_rows);
     int32_t done = 0;
     while (done < nb_steps - 1) {
       mdr::StepArgs a;
-      int rc = step_args(env, actions, action_source, (hipStream_t)stream, &a);   // refills or swaps the tables if the cursor left them
+      int rc = step_args(env, actions, action_source, (hipStream_t)stream, &a, false);
       if (rc != MDR_OK) return rc;
       if (!ip.packed) a.thermal_pack = a.thermal_desc = nullptr;   // MDR_THERMAL_PACK=0, a batch below the stream threshold: the columns
-      const int64_t room = env->cfg.table_steps - (env->k - env->j0);   // steps the current tables still cover
       mdr::RolloutArgs r{};
-      r.nsteps = (int)std::min<int64_t>(room, nb_steps - 1 - done);
-      hipError_t e = mdr::launch_rollout_resident(a, r, env->plan, (hipStream_t)stream);
+      r.nsteps = (int)std::min<int64_t>(capacity, nb_steps - 1 - done);
+      hipError_t e = mdr::launch_rollout_rows(table_args(env, env->k, r.nsteps), rows, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(env, e, "rollout rows");
+      e = mdr::launch_rollout_resident(a, r, rows, env->plan, (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(env, e, "rollout_resident");
       env->k += r.nsteps;
       done += r.nsteps;

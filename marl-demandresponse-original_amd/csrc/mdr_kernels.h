@@ -280,9 +280,14 @@ bool rollout_fused_supported(const StepPlan& p);
 hipError_t launch_rollout_accumulate(const StepArgs& a, const RolloutArgs& ro, hipStream_t s);   // after ONE single step
 hipError_t launch_rollout_fused(const StepArgs& a, const RolloutArgs& r, const StepPlan& p, hipStream_t s);
 // k_rollout_resident / k_rollout_resident_group: r.nsteps interior steps of mdr_env_rollout in one launch, by the STEP plan (STEP_FUSED /
-// STEP_GROUP); of `r` only nsteps is read.  a.thermal_desc == nullptr: the five thermal columns are streamed.
+// STEP_GROUP); of `r` only nsteps is read.  a.thermal_desc == nullptr: the five thermal columns are streamed.  The steps read
+// `rows`, [r.nsteps + 1][a.E] {od of step r, solar of step r} (launch_rollout_rows; the last row is only ever loaded, its value
+// unused), not a.od_old / a.solar_new.
 bool rollout_resident_supported(const StepPlan& p);
-hipError_t launch_rollout_resident(const StepArgs& a, const RolloutArgs& r, const StepPlan& p, hipStream_t s);
+hipError_t launch_rollout_resident(const StepArgs& a, const RolloutArgs& r, const float2* rows, const StepPlan& p, hipStream_t s);
+// dst[a.rows][a.E] <- {tab_od at time index a.j0 + r, tab_solar at a.j0 + r + 1}, bit for bit what launch_tables writes there
+// (mdr_rollout_rows.hip); of `a` neither the table pointers nor the signal fields are read
+hipError_t launch_rollout_rows(const TableArgs& a, float2* dst, hipStream_t s);
 hipError_t launch_obs_vector(const ObsArgs& a, int layout, hipStream_t s);
 hipError_t launch_obs_messages(const ObsArgs& a, hipStream_t s);               // msg_ext_out[e][h][:] for the local houses
 hipError_t launch_obs_vector_ext(const ObsArgs& a, int layout, hipStream_t s);  // senders read from msg_ext_in through links

@@ -2,21 +2,24 @@
 //
 // A translation unit of its own because its loop is bound by vector issue, where code generation options matter that matter to
 // no other kernel: build.py can give a single source extra flags (SOURCE_FLAGS, build_variant's source_flags) while every other
-// kernel keeps the flags and the instruction stream it had.  The product build passes none: the thermal map's f32 operations
-// are SLP-packed pairs (v_pk_*_f32); -fno-slp-vectorize was faster, but by less than the project's bar
-// (profiles/r11_README.md).  -ffp-contract=on applies here as everywhere.
+// kernel keeps the flags and the instruction stream it had.  The product build passes -fno-slp-vectorize: the thermal map's f32
+// operations are plain v_add / v_mul / v_fma instead of SLP-packed pairs (v_pk_*_f32), the same bits and 10 % more house-steps/s in
+// bench.py now that one launch covers the rollout (profiles/r12_README.md; with a launch per table window the difference stayed
+// under the project's bar, profiles/r11_README.md).  -ffp-contract=on applies here as everywhere.
 //
 // An interior step has no env-wide reduction, no reward and no obs: step_fused_interior is step_vec's loads, house_step and the
 // state stores, and a house depends on itself and on its env's od_old / solar_new rows alone.  So `ro.nsteps` of them are one
 // launch: the prologue loads a house through the very helpers the interior step uses (the same bits arrive in registers), the loop
-// reads two table values per env and step and advances the houses as k_rollout_fused does - lane masks, blank houses in the lanes
+// reads one float2 per env and step - {od_old, solar_new} of that step, from the rollout rows mdr_api.hip fills in front of the launch
+// (mdr_rollout_rows.hip: [nsteps + 1][E], the address steps by E entries, the row behind the last step is a spare one so that the
+// load one step ahead needs no clamp) - and advances the houses as k_rollout_fused does - lane masks, blank houses in the lanes
 // past the env's end so that every ballot sees the whole wave - and the epilogue stores Ta, Tm, sso and flags, nothing else: the
 // full step that ends the rollout overwrites every other output.  No LDS, no barrier, no accumulator.
 //
 // The loop body is house_advance_lean_m (mdr_device.h): the first step of a launch in the general form, every later one in the lean
 // form (one add, one compare, one select for the HVAC's integer state), and the lock mask once, behind the last step
 // (house_lock_m on the `can` mask that step left in scalar registers).  A blank lane's sso is never stored and is left to grow by
-// dt per step: mdr_api.hip takes this arm only while dt x table_steps < 2^31.  The step forms it replaces, by env->plan as
+// dt per step: mdr_api.hip keeps dt x (steps of a launch) below 2^31.  The step forms it replaces, by env->plan as
 // launch_step picks them:
 //   k_rollout_resident<VEC, TILES, THREADS, BB>   for k_step_fused<VEC, TILES, THREADS, 1, ..>: the rows are wave-uniform scalar
 //                                                 loads, fetched one step ahead; the other resident waves hide the rest
@@ -88,7 +91,7 @@ __device__ __forceinline__ void resident_advance(const StepArgs& a, bool ext, Ho
 }
 
 template <int VEC, int TILES, int THREADS, bool BB>
-__global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, RolloutArgs ro) {
+__global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, RolloutArgs ro, const float2* __restrict__ rows) {
   if (ro.nsteps <= 0) return;
   const int e = blockIdx.x;
   const int64_t base = (int64_t)e * a.N;
@@ -115,22 +118,21 @@ __global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, Rollou
       cmd_m[t][v] = __builtin_amdgcn_ballot_w64(live[t] && act[v] != 0u);
     }
   }
-  float od_old = a.od_old[e], solar = a.solar_new[e];
+  const float2* row = rows + e;   // {od, solar} of step 0; every step's row lies a.E entries behind the one before
+  float2 cur = *row;
   {   // step 0 in the general form: the state as it was handed in
-    const int64_t next = (int64_t)min(1, ro.nsteps - 1) * a.E + e;   // the rows of the step after this one: in flight over this step's arithmetic
-    const float od_next = a.od_old[next], solar_next = a.solar_new[next];
+    row += a.E;
+    const float2 nxt = *row;   // the row of the step after this one: in flight over this step's arithmetic (behind the last step: the spare row)
 #pragma unroll
-    for (int t = 0; t < TILES; ++t) resident_advance<VEC, BB, false>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], od_old, solar);
-    od_old = od_next;
-    solar = solar_next;
+    for (int t = 0; t < TILES; ++t) resident_advance<VEC, BB, false>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], cur.x, cur.y);
+    cur = nxt;
   }
   for (int s = 1; s < ro.nsteps; ++s) {   // on => sso == 0 from here on
-    const int64_t next = (int64_t)min(s + 1, ro.nsteps - 1) * a.E + e;
-    const float od_next = a.od_old[next], solar_next = a.solar_new[next];
+    row += a.E;
+    const float2 nxt = *row;
 #pragma unroll
-    for (int t = 0; t < TILES; ++t) resident_advance<VEC, BB, true>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], od_old, solar);
-    od_old = od_next;
-    solar = solar_next;
+    for (int t = 0; t < TILES; ++t) resident_advance<VEC, BB, true>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], cur.x, cur.y);
+    cur = nxt;
   }
   uint64_t lock_m[TILES][VEC];
 #pragma unroll
@@ -146,7 +148,7 @@ __global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, Rollou
 }
 
 template <int GROUP, int VEC, bool BB>
-__global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, RolloutArgs ro) {
+__global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, RolloutArgs ro, const float2* __restrict__ rows) {
   if (ro.nsteps <= 0) return;
   const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) / GROUP;
   const int lane = threadIdx.x % GROUP;
@@ -171,20 +173,19 @@ __global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, Roll
     on_m[v] = __builtin_amdgcn_ballot_w64(active && (hs[v].flags & 1u) != 0u);
     cmd_m[v] = __builtin_amdgcn_ballot_w64(active && act[v] != 0u);
   }
-  float od_old = a.od_old[e], solar = a.solar_new[e];   // several envs per wave: each lane reads its own env's rows (an idle env_ok == false lane: env E - 1's)
+  const float2* row = rows + e;   // several envs per wave: each lane reads its own env's rows (an idle env_ok == false lane: env E - 1's)
+  float2 cur = *row;
   {   // step 0 in the general form
-    const int64_t next = (int64_t)min(1, ro.nsteps - 1) * a.E + e;
-    const float od_next = a.od_old[next], solar_next = a.solar_new[next];
-    resident_advance<VEC, BB, false>(a, ext, hs, on_m, can_m, cmd_m, od_old, solar);
-    od_old = od_next;
-    solar = solar_next;
+    row += a.E;
+    const float2 nxt = *row;
+    resident_advance<VEC, BB, false>(a, ext, hs, on_m, can_m, cmd_m, cur.x, cur.y);
+    cur = nxt;
   }
   for (int s = 1; s < ro.nsteps; ++s) {   // on => sso == 0 from here on
-    const int64_t next = (int64_t)min(s + 1, ro.nsteps - 1) * a.E + e;
-    const float od_next = a.od_old[next], solar_next = a.solar_new[next];
-    resident_advance<VEC, BB, true>(a, ext, hs, on_m, can_m, cmd_m, od_old, solar);
-    od_old = od_next;
-    solar = solar_next;
+    row += a.E;
+    const float2 nxt = *row;
+    resident_advance<VEC, BB, true>(a, ext, hs, on_m, can_m, cmd_m, cur.x, cur.y);
+    cur = nxt;
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) lock_m[v] = house_lock_m(can_m[v], on_m[v], hs[v].sso, hs[v].lockout, a.dt);
@@ -196,12 +197,12 @@ __global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, Roll
 bool rollout_resident_supported(const StepPlan& p) { return p.kind == STEP_FUSED || p.kind == STEP_GROUP; }
 
 template <int VEC, int THREADS>
-static void launch_resident_tiles(const StepArgs& a, const RolloutArgs& r, int tiles, hipStream_t s) {
+static void launch_resident_tiles(const StepArgs& a, const RolloutArgs& r, const float2* rows, int tiles, hipStream_t s) {
   const dim3 g((unsigned)a.E), b(THREADS);
   const bool bb = a.action_source == MDR_ACTIONS_BANGBANG;
 #define MDR_RESIDENT(T)                                                                     \
-  if (bb) hipLaunchKernelGGL((k_rollout_resident<VEC, T, THREADS, true>), g, b, 0, s, a, r); \
-  else hipLaunchKernelGGL((k_rollout_resident<VEC, T, THREADS, false>), g, b, 0, s, a, r);   \
+  if (bb) hipLaunchKernelGGL((k_rollout_resident<VEC, T, THREADS, true>), g, b, 0, s, a, r, rows); \
+  else hipLaunchKernelGGL((k_rollout_resident<VEC, T, THREADS, false>), g, b, 0, s, a, r, rows);   \
   break;
   switch (tiles) {
     case 1: MDR_RESIDENT(1)
@@ -212,15 +213,15 @@ static void launch_resident_tiles(const StepArgs& a, const RolloutArgs& r, int t
 #undef MDR_RESIDENT
 }
 
-hipError_t launch_rollout_resident(const StepArgs& a, const RolloutArgs& r, const StepPlan& p, hipStream_t s) {
-  if (!rollout_resident_supported(p) || a.cursor != nullptr) return hipErrorInvalidValue;
+hipError_t launch_rollout_resident(const StepArgs& a, const RolloutArgs& r, const float2* rows, const StepPlan& p, hipStream_t s) {
+  if (!rollout_resident_supported(p) || a.cursor != nullptr || rows == nullptr) return hipErrorInvalidValue;
   if (p.kind == STEP_FUSED) {
     if (p.vec == 4) {
-      if (p.threads == 64) launch_resident_tiles<4, 64>(a, r, p.tiles, s);
-      else if (p.threads == 128) launch_resident_tiles<4, 128>(a, r, p.tiles, s);
-      else launch_resident_tiles<4, 256>(a, r, p.tiles, s);
+      if (p.threads == 64) launch_resident_tiles<4, 64>(a, r, rows, p.tiles, s);
+      else if (p.threads == 128) launch_resident_tiles<4, 128>(a, r, rows, p.tiles, s);
+      else launch_resident_tiles<4, 256>(a, r, rows, p.tiles, s);
     } else {
-      launch_resident_tiles<1, 256>(a, r, p.tiles, s);
+      launch_resident_tiles<1, 256>(a, r, rows, p.tiles, s);
     }
     return hipGetLastError();
   }
@@ -228,8 +229,8 @@ hipError_t launch_rollout_resident(const StepArgs& a, const RolloutArgs& r, cons
   const dim3 g((unsigned)((lanes + 255) / 256)), b(256);
   const bool bb = a.action_source == MDR_ACTIONS_BANGBANG;
 #define MDR_RESIDENT_GV(G, V)                                                                   \
-  if (bb) hipLaunchKernelGGL((k_rollout_resident_group<G, V, true>), g, b, 0, s, a, r);         \
-  else hipLaunchKernelGGL((k_rollout_resident_group<G, V, false>), g, b, 0, s, a, r);
+  if (bb) hipLaunchKernelGGL((k_rollout_resident_group<G, V, true>), g, b, 0, s, a, r, rows);         \
+  else hipLaunchKernelGGL((k_rollout_resident_group<G, V, false>), g, b, 0, s, a, r, rows);
 #define MDR_RESIDENT_G(G)                          \
   if (p.vec == 4) { MDR_RESIDENT_GV(G, 4) }        \
   else if (p.vec == 2) { MDR_RESIDENT_GV(G, 2) }   \
