@@ -198,6 +198,23 @@ int mdr_tarmac_comm_backward(const float *query, int64_t ldq, const float *key, 
  * negative or zero sizes of the rows. */
 int64_t mdr_tarmac_comm_backward_workspace_bytes(int64_t nb_agents, int32_t num_key, int32_t num_value);
 
+/* The two calls above with the Philox key of the dead-sender draw read from device memory when the kernel runs: `key_dev` int32 [2] =
+ * (seed low word, seed high word), the convention of mdr_minibatch_permutation_keyed, in place of `seed`; every other argument, the
+ * counter (sender lo, sender hi, step low word + *step_dev, 0x544D4331 ^ step high word, word `hop`), the limits and the status codes
+ * are the by-value calls'.  A call whose `key_dev` holds the two words of `seed` gives the by-value call's bits, so a captured node
+ * need not bake the seed in (graph_update.py: TarMACPPOUpdateGraph).  defect_prob == 0 never reads `key_dev`; a NULL `key_dev` is -1
+ * with nothing launched and nothing written. */
+int mdr_tarmac_comm_keyed(const float *query, int64_t ldq, const float *key, int64_t ldk, const float *value, int64_t ldv,
+                          int32_t nb_envs, int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode,
+                          float defect_prob, const int32_t *key_dev, uint64_t step, const int32_t *step_dev, int32_t hop, float *out,
+                          int64_t ldo, void *stream);
+int mdr_tarmac_comm_backward_keyed(const float *query, int64_t ldq, const float *key, int64_t ldk, const float *value, int64_t ldv,
+                                   int32_t nb_envs, int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm,
+                                   int32_t mode, float defect_prob, const int32_t *key_dev, uint64_t step, const int32_t *step_dev,
+                                   int32_t hop, const float *out, int64_t ldo, const float *grad_out, int64_t ldg, float *grad_query,
+                                   int64_t ldgq, float *grad_key, int64_t ldgk, float *grad_value, int64_t ldgv, void *workspace,
+                                   void *stream);
+
 /* ---- The two non-banded masks of make_masks (network.py:138-177), tarmac_comm_mode "all" and "random_sample": entry points of
  * their own (csrc/mdr_tarmac_gather.hip); enum mdr_tarmac_mode and the calls above keep their two banded modes. */
 enum mdr_tarmac_gather_mode {
@@ -814,6 +831,17 @@ int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t *net, const float *state, i
                               int32_t nb_houses, const int64_t *action, const float *old_prob, const float *advantage, float clip_param,
                               uint64_t seed, uint64_t step, int32_t max_workgroups, void *workspace, float *grad, float *loss,
                               float *ratio, void *stream);
+
+/* The same call with the key of the dead-sender draw from device memory (`key_dev` int32 [2] = seed low word, seed high word, as
+ * mdr_tarmac_comm_keyed reads it) and `step_dev` (device int32, may be NULL) added to the low word of `step` when the kernels run;
+ * both are handed to the two attention calls of the chain, no other kernel draws.  key_dev = the words of `seed` and
+ * step + *step_dev = the by-value `step` (below 2^32: the sum wraps in the low word) give mdr_tarmac_ppo_actor_grad's bits.  A NULL
+ * `key_dev` is -1 with nothing launched and nothing written. */
+int mdr_tarmac_ppo_actor_grad_keyed(const mdr_tarmac_net_t *net, const float *state, int64_t ld_state, const int64_t *index,
+                                    int64_t nb_rows, int32_t nb_houses, const int64_t *action, const float *old_prob,
+                                    const float *advantage, float clip_param, const int32_t *key_dev, uint64_t step,
+                                    const int32_t *step_dev, int32_t max_workgroups, void *workspace, float *grad, float *loss,
+                                    float *ratio, void *stream);
 
 /* ---- TarMAC-PPO's update step for the centralised critic (TarmacPPO.update, agents/tarmac_ppo.py:159-166, 196-204): value,
  * advantage, value loss and gradient of one minibatch.

@@ -212,6 +212,7 @@ EXPORTS = (
     # include/mdr_policy.h
     "mdr_actor_steps1", "mdr_actor_steps1_order", "mdr_actor_steps2", "mdr_actor_frag1_floats", "mdr_actor_frag2_floats", "mdr_actor_sample", "mdr_env_actor_sample", "mdr_env_actor_sample_links",
     "mdr_discounted_returns", "mdr_tarmac_comm", "mdr_logits_sample", "mdr_tarmac_comm_backward", "mdr_tarmac_comm_backward_workspace_bytes",
+    "mdr_tarmac_comm_keyed", "mdr_tarmac_comm_backward_keyed",
     "mdr_tarmac_gather", "mdr_tarmac_gather_backward", "mdr_tarmac_gather_backward_workspace_bytes",
     "mdr_tarmac_frag_encode_floats", "mdr_tarmac_frag_proj_floats", "mdr_tarmac_frag_msg_floats", "mdr_tarmac_frag_head_floats",
     "mdr_tarmac_vec_floats", "mdr_tarmac_frag_words", "mdr_tarmac_actor_workspace_bytes", "mdr_tarmac_actor_sample",
@@ -225,7 +226,7 @@ EXPORTS = (
     "mdr_mlp_actor_sample", "mdr_mlp_actor_sample_bf16x3", "mdr_mlp_actors_sample", "mdr_maddpg_target_agents",
     "mdr_env_mlp_actor_sample", "mdr_env_mlp_actor_sample_bf16x3",
     "mdr_maddpg_workspace_bytes_all", "mdr_maddpg_target_all", "mdr_maddpg_critic_grad_all", "mdr_maddpg_actor_grad_all",
-    "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad",
+    "mdr_tarmac_net_grad_floats", "mdr_tarmac_ppo_workspace_bytes", "mdr_tarmac_ppo_actor_grad", "mdr_tarmac_ppo_actor_grad_keyed",
     "mdr_tarmac_critic_grad_floats", "mdr_tarmac_critic_workspace_bytes", "mdr_tarmac_critic_value", "mdr_tarmac_critic_grad",
     "mdr_tarmac_a2c_grad_floats", "mdr_tarmac_a2c_workspace_bytes", "mdr_tarmac_a2c_forward", "mdr_tarmac_a2c_comm", "mdr_tarmac_a2c_grad",
     "mdr_adam_workspace_bytes", "mdr_adam_step", "mdr_adam_step_table", "mdr_adam_corrections",
@@ -321,6 +322,10 @@ def load():
         "mdr_tarmac_comm_backward": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, u64, u64, vp, i32, vp, i64,
                                                vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
         "mdr_tarmac_comm_backward_workspace_bytes": (i64, [i64, i32, i32]),
+        # the keyed siblings: a device int32 [2] key in place of the seed
+        "mdr_tarmac_comm_keyed": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, vp, u64, vp, i32, vp, i64, vp]),
+        "mdr_tarmac_comm_backward_keyed": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, vp, u64, vp, i32, vp,
+                                                     i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
         "mdr_tarmac_gather": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, u64, u64, vp, i32, vp, i64, vp]),
         "mdr_tarmac_gather_backward": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, u64, u64, vp, i32, vp, i64,
                                                  vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
@@ -383,6 +388,8 @@ def load():
         "mdr_tarmac_ppo_workspace_bytes": (i64, [C.POINTER(MdrTarmacNet), i64, i32, i32]),
         "mdr_tarmac_ppo_actor_grad": (C.c_int, [C.POINTER(MdrTarmacNet), vp, i64, vp, i64, i32, vp, vp, vp, C.c_float, u64, u64, i32, vp, vp, vp,
                                                 vp, vp]),
+        "mdr_tarmac_ppo_actor_grad_keyed": (C.c_int, [C.POINTER(MdrTarmacNet), vp, i64, vp, i64, i32, vp, vp, vp, C.c_float, vp, u64, vp, i32, vp,
+                                                      vp, vp, vp, vp]),
         "mdr_tarmac_a2c_grad_floats": (i64, [C.POINTER(MdrTarmacA2CNet)]),
         "mdr_tarmac_a2c_workspace_bytes": (i64, [C.POINTER(MdrTarmacA2CNet), i64, i32, i32]),
         "mdr_tarmac_a2c_forward": (C.c_int, [C.POINTER(MdrTarmacA2CNet), vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp]),

@@ -55,6 +55,7 @@ struct CommArgs {
   uint32_t k0, k1, step_lo, step_hi;
   int hop;
   const int32_t* step_dev;
+  const int32_t* key;      // may be NULL: k0, k1 above
 };
 
 __device__ __forceinline__ int wrap(int h, int n) {      // h in [-n, 2 n)
@@ -116,9 +117,12 @@ __global__ __launch_bounds__(TILE) void k_tarmac_comm(CommArgs a) {
   const bool defects = a.defect_prob > 0.0f;
   if (defects) {
     const uint32_t c2 = a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u), c3 = TAG_TARMAC ^ a.step_hi;
+    // the key from device memory is the same word in every lane: readfirstlane hands loop_local the scalar it asks for
+    const uint32_t k0 = a.key ? (uint32_t)__builtin_amdgcn_readfirstlane(a.key[0]) : a.k0;
+    const uint32_t k1 = a.key ? (uint32_t)__builtin_amdgcn_readfirstlane(a.key[1]) : a.k1;
     for (int row = t; row < nrows; row += TILE) {
       const int64_t ag = agent0 + (whole ? row : wrap(start - a.hm + row, N));
-      const u32x4 r = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), c2, c3, loop_local(a.k0), loop_local(a.k1));
+      const u32x4 r = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), c2, c3, loop_local(k0), loop_local(k1));
       const uint32_t word = a.hop == 0 ? r.x : a.hop == 1 ? r.y : a.hop == 2 ? r.z : r.w;
       dead[row] = action_uniform(word) < a.defect_prob ? 1u : 0u;
     }
@@ -214,13 +218,10 @@ int launch_comm(K kernel, unsigned grid, size_t lds_bytes, hipStream_t s, const 
 
 bool aligned16(const void* p, int64_t ld) { return ((uintptr_t)p & 15u) == 0 && (ld & 3) == 0; }
 
-}  // namespace
-
-extern "C" {
-
-int mdr_tarmac_comm(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv, int32_t nb_envs,
-                    int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob, uint64_t seed,
-                    uint64_t step, const int32_t* step_dev, int32_t hop, float* out, int64_t ldo, void* stream) {
+// the by-value entry point (key_dev NULL: the key is `seed`) and the keyed one
+int comm(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv, int32_t nb_envs, int32_t nb_houses,
+         int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob, const int32_t* key_dev, uint64_t seed,
+         uint64_t step, const int32_t* step_dev, int32_t hop, float* out, int64_t ldo, void* stream) {
   if (!query || !key || !value || !out || nb_envs < 0 || nb_houses <= 0 || nb_comm < 0) return MDR_ERR_INVALID;
   if (mode != MDR_TARMAC_NEIGHBOURS && mode != MDR_TARMAC_NONE) return MDR_ERR_INVALID;
   if (hop < 0 || hop > 3 || !(defect_prob >= 0.0f && defect_prob <= 1.0f)) return MDR_ERR_INVALID;
@@ -257,6 +258,7 @@ int mdr_tarmac_comm(const float* query, int64_t ldq, const float* key, int64_t l
   a.step_lo = (uint32_t)step, a.step_hi = (uint32_t)(step >> 32);
   a.hop = hop;
   a.step_dev = step_dev;
+  a.key = key_dev;
   const int64_t grid = a.epw ? ((int64_t)nb_envs + a.epw - 1) / a.epw : (int64_t)nb_envs * a.slices;
   if (grid > 0x7FFFFFFF) return MDR_ERR_UNSUPPORTED;
   const size_t lds_bytes = ((size_t)max_rows * a.stride + (defect_prob > 0.0f ? max_rows : 0)) * sizeof(float);
@@ -264,6 +266,25 @@ int mdr_tarmac_comm(const float* query, int64_t ldq, const float* key, int64_t l
   if (a.kq == 2 && a.vq == 4) return launch_comm(k_tarmac_comm<2, 4, true>, (unsigned)grid, lds_bytes, s, a);      // the reference's sizes
   if (a.kq <= 4 && a.vq <= 8) return launch_comm(k_tarmac_comm<4, 8, false>, (unsigned)grid, lds_bytes, s, a);
   return launch_comm(k_tarmac_comm<8, 16, false>, (unsigned)grid, lds_bytes, s, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdr_tarmac_comm(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv, int32_t nb_envs,
+                    int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob, uint64_t seed,
+                    uint64_t step, const int32_t* step_dev, int32_t hop, float* out, int64_t ldo, void* stream) {
+  return comm(query, ldq, key, ldk, value, ldv, nb_envs, nb_houses, num_key, num_value, nb_comm, mode, defect_prob, nullptr, seed, step, step_dev,
+              hop, out, ldo, stream);
+}
+
+int mdr_tarmac_comm_keyed(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv, int32_t nb_envs,
+                          int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob,
+                          const int32_t* key_dev, uint64_t step, const int32_t* step_dev, int32_t hop, float* out, int64_t ldo, void* stream) {
+  if (!key_dev) return MDR_ERR_INVALID;
+  return comm(query, ldq, key, ldk, value, ldv, nb_envs, nb_houses, num_key, num_value, nb_comm, mode, defect_prob, key_dev, 0, step, step_dev,
+              hop, out, ldo, stream);
 }
 
 int mdr_logits_sample(const float* logits, int64_t ld, int64_t nb_agents, uint64_t seed, uint64_t step, const int32_t* step_dev,

@@ -62,6 +62,7 @@ struct GradArgs {
   uint32_t k0, k1, step_lo, step_hi;
   int hop;
   const int32_t* step_dev;
+  const int32_t* key;      // may be NULL: k0, k1 above
 };
 
 __device__ __forceinline__ int wrap(int h, int n) {      // h in [-n, 2 n)
@@ -74,7 +75,10 @@ __device__ __forceinline__ int band_offset(int i) { return (i & 1) ? (i + 1) >> 
 
 __device__ __forceinline__ bool sender_dead(const GradArgs& a, int64_t ag) {
   const uint32_t c2 = a.step_lo + (a.step_dev ? (uint32_t)*a.step_dev : 0u), c3 = TAG_TARMAC ^ a.step_hi;
-  const u32x4 r = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), c2, c3, loop_local(a.k0), loop_local(a.k1));
+  // the key from device memory is the same word in every lane: readfirstlane hands loop_local the scalar it asks for
+  const uint32_t k0 = a.key ? (uint32_t)__builtin_amdgcn_readfirstlane(a.key[0]) : a.k0;
+  const uint32_t k1 = a.key ? (uint32_t)__builtin_amdgcn_readfirstlane(a.key[1]) : a.k1;
+  const u32x4 r = philox4x32_10((uint32_t)ag, (uint32_t)((uint64_t)ag >> 32), c2, c3, loop_local(k0), loop_local(k1));
   const uint32_t word = a.hop == 0 ? r.x : a.hop == 1 ? r.y : a.hop == 2 ? r.z : r.w;
   return action_uniform(word) < a.defect_prob;
 }
@@ -313,20 +317,12 @@ int launch_grad(unsigned grid, size_t lds_recv, size_t lds_send, hipStream_t s, 
 
 bool aligned16(const void* p, int64_t ld) { return ((uintptr_t)p & 15u) == 0 && (ld & 3) == 0; }
 
-}  // namespace
-
-extern "C" {
-
-int64_t mdr_tarmac_comm_backward_workspace_bytes(int64_t nb_agents, int32_t num_key, int32_t num_value) {
-  if (nb_agents < 0 || num_key <= 0 || num_value <= 0) return -1;
-  return nb_agents * (int64_t)sizeof(float4);
-}
-
-int mdr_tarmac_comm_backward(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv, int32_t nb_envs,
-                             int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob,
-                             uint64_t seed, uint64_t step, const int32_t* step_dev, int32_t hop, const float* out, int64_t ldo,
-                             const float* grad_out, int64_t ldg, float* grad_query, int64_t ldgq, float* grad_key, int64_t ldgk,
-                             float* grad_value, int64_t ldgv, void* workspace, void* stream) {
+// the by-value entry point (key_dev NULL: the key is `seed`) and the keyed one
+int comm_backward(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv, int32_t nb_envs,
+                  int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob,
+                  const int32_t* key_dev, uint64_t seed, uint64_t step, const int32_t* step_dev, int32_t hop, const float* out, int64_t ldo,
+                  const float* grad_out, int64_t ldg, float* grad_query, int64_t ldgq, float* grad_key, int64_t ldgk, float* grad_value,
+                  int64_t ldgv, void* workspace, void* stream) {
   if (!query || !key || !value || !out || !grad_out || !grad_query || !grad_key || !grad_value) return MDR_ERR_INVALID;
   if (nb_envs < 0 || nb_houses <= 0 || nb_comm < 0) return MDR_ERR_INVALID;
   if (mode != MDR_TARMAC_NEIGHBOURS && mode != MDR_TARMAC_NONE) return MDR_ERR_INVALID;
@@ -378,6 +374,7 @@ int mdr_tarmac_comm_backward(const float* query, int64_t ldq, const float* key, 
   a.step_lo = (uint32_t)step, a.step_hi = (uint32_t)(step >> 32);
   a.hop = hop;
   a.step_dev = step_dev;
+  a.key = key_dev;
   const int64_t grid = a.epw ? ((int64_t)nb_envs + a.epw - 1) / a.epw : (int64_t)nb_envs * a.slices;
   if (grid > 0x7FFFFFFF) return MDR_ERR_UNSUPPORTED;
   // at most 320 rows of 100 floats: 128,000 bytes (+ 1,280 of flags), inside the 160 KB of a workgroup for every served shape
@@ -387,6 +384,34 @@ int mdr_tarmac_comm_backward(const float* query, int64_t ldq, const float* key, 
   if (kq == 2 && vq == 4) return launch_grad<2, 4, true>((unsigned)grid, lds_recv, lds_send, s, a);      // the reference's sizes
   if (kq <= 4 && vq <= 8) return launch_grad<4, 8, false>((unsigned)grid, lds_recv, lds_send, s, a);
   return launch_grad<8, 16, false>((unsigned)grid, lds_recv, lds_send, s, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mdr_tarmac_comm_backward_workspace_bytes(int64_t nb_agents, int32_t num_key, int32_t num_value) {
+  if (nb_agents < 0 || num_key <= 0 || num_value <= 0) return -1;
+  return nb_agents * (int64_t)sizeof(float4);
+}
+
+int mdr_tarmac_comm_backward(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv, int32_t nb_envs,
+                             int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode, float defect_prob,
+                             uint64_t seed, uint64_t step, const int32_t* step_dev, int32_t hop, const float* out, int64_t ldo,
+                             const float* grad_out, int64_t ldg, float* grad_query, int64_t ldgq, float* grad_key, int64_t ldgk,
+                             float* grad_value, int64_t ldgv, void* workspace, void* stream) {
+  return comm_backward(query, ldq, key, ldk, value, ldv, nb_envs, nb_houses, num_key, num_value, nb_comm, mode, defect_prob, nullptr, seed, step,
+                       step_dev, hop, out, ldo, grad_out, ldg, grad_query, ldgq, grad_key, ldgk, grad_value, ldgv, workspace, stream);
+}
+
+int mdr_tarmac_comm_backward_keyed(const float* query, int64_t ldq, const float* key, int64_t ldk, const float* value, int64_t ldv,
+                                   int32_t nb_envs, int32_t nb_houses, int32_t num_key, int32_t num_value, int32_t nb_comm, int32_t mode,
+                                   float defect_prob, const int32_t* key_dev, uint64_t step, const int32_t* step_dev, int32_t hop,
+                                   const float* out, int64_t ldo, const float* grad_out, int64_t ldg, float* grad_query, int64_t ldgq,
+                                   float* grad_key, int64_t ldgk, float* grad_value, int64_t ldgv, void* workspace, void* stream) {
+  if (!key_dev) return MDR_ERR_INVALID;
+  return comm_backward(query, ldq, key, ldk, value, ldv, nb_envs, nb_houses, num_key, num_value, nb_comm, mode, defect_prob, key_dev, 0, step,
+                       step_dev, hop, out, ldo, grad_out, ldg, grad_query, ldgq, grad_key, ldgk, grad_value, ldgv, workspace, stream);
 }
 
 }  // extern "C"

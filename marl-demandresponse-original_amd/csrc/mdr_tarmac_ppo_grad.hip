@@ -566,28 +566,11 @@ int prepare(K kernel, int lds_floats) {
              : MDR_ERR_HIP;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t mdr_tarmac_net_grad_floats(const mdr_tarmac_net_t* net) {
-  if (!net_fields_ok(net) || !net_covered(net)) return -1;
-  return net_of(net).G;
-}
-
-int64_t mdr_tarmac_ppo_workspace_bytes(const mdr_tarmac_net_t* net, int64_t nb_rows, int32_t nb_houses, int32_t max_workgroups) {
-  if (!net_fields_ok(net) || !net_covered(net) || nb_rows < 0 || nb_houses <= 0 || max_workgroups < 0) return -1;
-  if (nb_rows > MAX_AGENTS / nb_houses) return -1;
-  const Net n = net_of(net);
-  const int64_t agents = nb_rows * nb_houses;
-  // max_workgroups == 0: room for the library's grid on any device (no device call here)
-  return layout_of(n, agents, grid_for(agents, max_workgroups, LIB_MAX_WG)).total;
-}
-
-int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
-                              int32_t nb_houses, const int64_t* action, const float* old_prob, const float* advantage, float clip_param,
-                              uint64_t seed, uint64_t step, int32_t max_workgroups, void* workspace, float* grad, float* loss, float* ratio,
-                              void* stream) {
+// the by-value entry point (key_dev and step_dev NULL: the defects' key is `seed`) and the keyed one
+int actor_grad(const mdr_tarmac_net_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows, int32_t nb_houses,
+               const int64_t* action, const float* old_prob, const float* advantage, float clip_param, const int32_t* key_dev, uint64_t seed,
+               uint64_t step, const int32_t* step_dev, int32_t max_workgroups, void* workspace, float* grad, float* loss, float* ratio,
+               void* stream) {
   if (!net_fields_ok(net) || !state || !action || !old_prob || !advantage || !grad || !loss) return MDR_ERR_INVALID;
   if (!workspace || ((uintptr_t)workspace & 15u)) return MDR_ERR_INVALID;
   if (!net->encode_w0 || !net->encode_b0 || !net->encode_w2 || !net->encode_b2 || !net->head_w0 || !net->head_b0 || !net->head_w2 || !net->head_b2)
@@ -644,16 +627,23 @@ int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t* net, const float* state, i
     if (n.comm) {
       hipLaunchKernelGGL(k_tppo_proj<false>, g3, b3, b_proj, st, a);
       if (hipGetLastError() != hipSuccess) return MDR_ERR_HIP;
-      const int rc = mdr_tarmac_comm(q, n.Q, k, n.Q, v, n.Q, (int32_t)nb_rows, nb_houses, n.K, n.V, net->nb_comm, net->mode, net->defect_prob, seed,
-                                     step, nullptr, 0, comm, n.M, stream);
+      const int rc = key_dev ? mdr_tarmac_comm_keyed(q, n.Q, k, n.Q, v, n.Q, (int32_t)nb_rows, nb_houses, n.K, n.V, net->nb_comm, net->mode,
+                                                     net->defect_prob, key_dev, step, step_dev, 0, comm, n.M, stream)
+                             : mdr_tarmac_comm(q, n.Q, k, n.Q, v, n.Q, (int32_t)nb_rows, nb_houses, n.K, n.V, net->nb_comm, net->mode,
+                                               net->defect_prob, seed, step, step_dev, 0, comm, n.M, stream);
       if (rc != MDR_OK) return MDR_ERR_HIP;
     }
     hipLaunchKernelGGL(k_tppo_head, g3, b3, b_head, st, a);
     if (hipGetLastError() != hipSuccess) return MDR_ERR_HIP;
     if (n.comm) {
-      const int rc = mdr_tarmac_comm_backward(q, n.Q, k, n.Q, v, n.Q, (int32_t)nb_rows, nb_houses, n.K, n.V, net->nb_comm, net->mode,
-                                              net->defect_prob, seed, step, nullptr, 0, comm, n.M, a.dcat + n.H, n.M, a.dqkv, n.Q, a.dqkv + n.K,
-                                              n.Q, a.dqkv + 2 * n.K, n.Q, ws + l.stats, stream);
+      float *dq = a.dqkv, *dk = a.dqkv + n.K, *dv = a.dqkv + 2 * n.K, *dcomm = a.dcat + n.H;
+      const int rc =
+          key_dev ? mdr_tarmac_comm_backward_keyed(q, n.Q, k, n.Q, v, n.Q, (int32_t)nb_rows, nb_houses, n.K, n.V, net->nb_comm, net->mode,
+                                                   net->defect_prob, key_dev, step, step_dev, 0, comm, n.M, dcomm, n.M, dq, n.Q, dk, n.Q, dv, n.Q,
+                                                   ws + l.stats, stream)
+                  : mdr_tarmac_comm_backward(q, n.Q, k, n.Q, v, n.Q, (int32_t)nb_rows, nb_houses, n.K, n.V, net->nb_comm, net->mode,
+                                             net->defect_prob, seed, step, step_dev, 0, comm, n.M, dcomm, n.M, dq, n.Q, dk, n.Q, dv, n.Q,
+                                             ws + l.stats, stream);
       if (rc != MDR_OK) return MDR_ERR_HIP;
       hipLaunchKernelGGL(k_tppo_proj<true>, g3, b3, b_proj, st, a);
       if (hipGetLastError() != hipSuccess) return MDR_ERR_HIP;
@@ -665,6 +655,41 @@ int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t* net, const float* state, i
   hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(workspace), SUB * grid,
                      n.stride, n.G, (float)agents, grad, loss);
   return hipGetLastError() == hipSuccess ? MDR_OK : MDR_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mdr_tarmac_net_grad_floats(const mdr_tarmac_net_t* net) {
+  if (!net_fields_ok(net) || !net_covered(net)) return -1;
+  return net_of(net).G;
+}
+
+int64_t mdr_tarmac_ppo_workspace_bytes(const mdr_tarmac_net_t* net, int64_t nb_rows, int32_t nb_houses, int32_t max_workgroups) {
+  if (!net_fields_ok(net) || !net_covered(net) || nb_rows < 0 || nb_houses <= 0 || max_workgroups < 0) return -1;
+  if (nb_rows > MAX_AGENTS / nb_houses) return -1;
+  const Net n = net_of(net);
+  const int64_t agents = nb_rows * nb_houses;
+  // max_workgroups == 0: room for the library's grid on any device (no device call here)
+  return layout_of(n, agents, grid_for(agents, max_workgroups, LIB_MAX_WG)).total;
+}
+
+int mdr_tarmac_ppo_actor_grad(const mdr_tarmac_net_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                              int32_t nb_houses, const int64_t* action, const float* old_prob, const float* advantage, float clip_param,
+                              uint64_t seed, uint64_t step, int32_t max_workgroups, void* workspace, float* grad, float* loss, float* ratio,
+                              void* stream) {
+  return actor_grad(net, state, ld_state, index, nb_rows, nb_houses, action, old_prob, advantage, clip_param, nullptr, seed, step, nullptr,
+                    max_workgroups, workspace, grad, loss, ratio, stream);
+}
+
+int mdr_tarmac_ppo_actor_grad_keyed(const mdr_tarmac_net_t* net, const float* state, int64_t ld_state, const int64_t* index, int64_t nb_rows,
+                                    int32_t nb_houses, const int64_t* action, const float* old_prob, const float* advantage, float clip_param,
+                                    const int32_t* key_dev, uint64_t step, const int32_t* step_dev, int32_t max_workgroups, void* workspace,
+                                    float* grad, float* loss, float* ratio, void* stream) {
+  if (!key_dev) return MDR_ERR_INVALID;
+  return actor_grad(net, state, ld_state, index, nb_rows, nb_houses, action, old_prob, advantage, clip_param, key_dev, 0, step, step_dev,
+                    max_workgroups, workspace, grad, loss, ratio, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""Device-side minibatch indices and the captured update of PPOLearner, MAPPOLearner, DQNLearner and MADDPGLearner
-(csrc/mdr_minibatch.hip, include/mdr_policy.h: mdr_minibatch_permutation, mdr_minibatch_sample, mdr_maddpg_draws, mdr_update_cursor_set,
+"""Device-side minibatch indices and the captured update of PPOLearner, MAPPOLearner, DQNLearner, MADDPGLearner, TarMACPPOLearner and
+TarMACA2CLearner (csrc/mdr_minibatch.hip, include/mdr_policy.h: mdr_minibatch_permutation, mdr_minibatch_sample, mdr_maddpg_draws, mdr_update_cursor_set,
 mdr_adam_step_table).
 
 At the reference's sizes an update is host time: a PPO minibatch is six launches of 60-80 us of GPU work behind 190 us of Python,
@@ -17,7 +17,9 @@ the host's step count) and host counters.  Here each has a device-side counterpa
 ``PPOUpdateGraph`` holds ONE epoch - the permutation, every minibatch's critic call, actor call and two table steps, the loss sums,
 the cursor advance - as one ``torch.cuda.CUDAGraph`` captured on one side stream (a chain of nodes, no fork); an update copies the batch
 into the graph's static input buffers, resets the cursors, uploads the corrections of all its steps and replays the graph
-``ppo_update_time`` times.  ``DQNUpdateGraph`` and ``MADDPGUpdateGraph`` hold one update each, reading the replay buffer in place.  Nothing is allocated inside a capture, and a capture leaves no
+``ppo_update_time`` times.  ``DQNUpdateGraph`` and ``MADDPGUpdateGraph`` hold one update each, reading the replay buffer in place.
+``TarMACPPOUpdateGraph`` and ``TarMACA2CUpdateGraph`` hold one epoch over env-steps in the same way; the Philox key of TarMAC-PPO's
+communication defects and its step come from the cursor block too (mdr_tarmac_ppo_actor_grad_keyed).  Nothing is allocated inside a capture, and a capture leaves no
 trace: kernels do not run while capturing, and the warm-up pass before it (first-use kernel attributes, the flat gradient buffers, the
 optimiser's segment table) runs on a snapshot of parameters and moments that is restored.  The graphed update launches the same
 kernels with the same arguments as the eager ``sampler="philox"`` update and gives the same bits.
@@ -189,18 +191,28 @@ def refusal(backend: str, sampler: str, optimizers, uses_kernels: bool) -> Optio
     return None
 
 
-def _flat_grad(net, floats: int) -> torch.Tensor:
-    """The flat gradient of ``net`` with the six ``p.grad`` rebound to views of it: the captured optimiser step reads them there."""
-    params = L.mlp_params(L.fc_layers(net))
+def _flat_grad(net, floats: int, params: Optional[Sequence[torch.Tensor]] = None, keep: bool = False) -> torch.Tensor:
+    """The flat gradient of ``net`` with the ``p.grad`` of ``params`` - the tensors it covers, in its order; default: the six of an
+    ``fc`` MLP - rebound to views of it: the captured optimiser step reads them there.  ``keep``: a gradient held in a tensor of its
+    own is copied into its view first, so that ``p.grad`` keeps its value."""
+    params = L.mlp_params(L.fc_layers(net)) if params is None else list(params)
     flat = L.flat_grad(net, floats, params[0].device)
+    if keep:
+        off = 0
+        for p in params:
+            view = flat[off:off + p.numel()].view_as(p)
+            off += p.numel()
+            if p.grad is not None and p.grad.data_ptr() != view.data_ptr():
+                view.copy_(p.grad)
     L.publish(params, flat, L.REBIND)
     return flat
 
 
 def _signature(nets) -> list:
+    """Where the parameters and gradients of ``nets`` are; an entry is an ``fc`` MLP or the list of tensors itself."""
     sig = []
     for net in nets:
-        for p in L.mlp_params(L.fc_layers(net)):
+        for p in (net if isinstance(net, (list, tuple)) else L.mlp_params(L.fc_layers(net))):
             sig += [p.data_ptr(), p.grad.data_ptr() if p.grad is not None else 0]
     return sig
 
@@ -542,3 +554,259 @@ def maddpg_update(learner, seed: int):
     if g is None:
         g = learner._capture()
     return g.run(seed)
+
+
+def _minibatch_rows(n: int, bs: int) -> set:
+    """The env-step counts of an epoch's minibatches: a full one and the tail."""
+    m = (n + bs - 1) // bs
+    return {min(bs, n), n - (m - 1) * bs}
+
+
+class TarMACPPOUpdateGraph:
+    """One epoch of ``TarMACPPOLearner.update`` over a batch of n = T x E env-steps of N agents and F features as one graph: the
+    permutation, then per minibatch the critic's two launches (loss, advantage, gradient), the actor's chain
+    (mdr_tarmac_ppo_actor_grad_keyed), the ``zero_()`` on the key bias, the actor's clip + step, the critic's clip + step and the loss
+    sums - the eager order -, then the cursor advance.  A chain of nodes on one stream.
+
+    The communication defects are keyed by (seed, training_step) in the eager update.  Here the seed is the key of the cursor block
+    and the step is ``j`` by value for minibatch ``j`` plus the STEP cursor, which ``run`` sets to ``training_step`` and the graph
+    advances by the minibatches of an epoch.  The cursor is one int32 added to the low word of the step: the replay reproduces the
+    eager keys as long as ``training_step`` plus the update's steps stays below 2^32 (past it the eager update carries into the high
+    word, the cursor wraps)."""
+
+    EPOCH, BASE, KEY, STEP = 0, 1, 2, 4      # the cursor block: epoch, table base, key lo, key hi, the defects' step
+
+    def __init__(self, learner, T: int, A: int, N: int, F: int):
+        from . import tarmac_ppo as tp      # (tarmac_ppo imports this module)
+        self.learner, self.tp = learner, tp
+        actor, critic = learner.actor, learner.critic
+        dev = next(actor.parameters()).device
+        self.dev = dev
+        self.n, self.N, self.F, self.bs, self.epochs = T * (A // N), N, F, learner.batch_size, learner.ppo_update_time
+        self.m = (self.n + self.bs - 1) // self.bs
+        n = self.n
+        self.state = torch.zeros((n, N, F), dtype=torch.float32, device=dev)
+        self.action = torch.zeros((n, N), dtype=torch.int64, device=dev)
+        self.a_prob = torch.ones((n, N), dtype=torch.float32, device=dev)
+        self.ret = torch.zeros((n, N), dtype=torch.float32, device=dev)
+        self.perm = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.block = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.a_table = torch.ones(2 * self.epochs * self.m, dtype=torch.float32, device=dev)
+        self.c_table = torch.ones(2 * self.epochs * self.m, dtype=torch.float32, device=dev)
+        self.a_sum = torch.zeros((), dtype=torch.float32, device=dev)
+        self.c_sum = torch.zeros((), dtype=torch.float32, device=dev)
+        self.a_loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.c_loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.adv = torch.zeros((min(self.bs, n), N), dtype=torch.float32, device=dev)
+        self.a_params, self.c_params = tp._params(actor), L.mlp_params(tp._critic_layers(critic))
+        self.a_desc, self.c_desc = tp._desc(actor), L.mlp_desc(tp._critic_layers(critic))
+        rows = _minibatch_rows(n, self.bs)
+        a_floats, a_bytes = zip(*(tp._actor_sizes(self.a_desc, B, N) for B in rows))
+        c_floats, c_bytes = zip(*(tp._critic_sizes(self.c_desc, B) for B in rows))
+        self.workspace = torch.empty(max(16, *a_bytes, *c_bytes), dtype=torch.uint8, device=dev)      # the graph's own: the shared one may be reallocated
+        self.a_flat = _flat_grad(actor, a_floats[0], self.a_params, keep=True)
+        self.c_flat = _flat_grad(critic, c_floats[0], self.c_params, keep=True)
+        a_opt, c_opt = learner.actor_optimizer, learner.critic_optimizer
+        # the warm-up pass writes the flat gradients too: they are held, so that every ``.grad`` keeps its value over a capture
+        held = (list(actor.parameters()) + list(critic.parameters()) + [a_opt._exp_avg, a_opt._exp_avg_sq, c_opt._exp_avg, c_opt._exp_avg_sq]
+                + [self.a_flat, self.c_flat])
+        self.graph = _capture(self._record, held, dev)
+        self.signature = tarmac_ppo_signature(learner)
+
+    def _record(self) -> None:
+        """The launches of one epoch on the current stream, from the static buffers alone."""
+        learner, dev, tp, N = self.learner, self.dev, self.tp, self.N
+        st = L.stream(dev)
+        base = self.block[self.BASE:self.BASE + 1]
+        key, step_dev = self.block[self.KEY:self.KEY + 2], self.block[self.STEP:self.STEP + 1]
+        ld_actor, ld_critic = self.F, N * self.F      # the static state buffer is contiguous
+        with torch.cuda.device(dev):
+            permutation(self.n, 0, 0, dev, out=self.perm, cursor=self.block[self.EPOCH:], key=key)
+            for j in range(self.m):
+                index = self.perm[j * self.bs:(j + 1) * self.bs]      # a view (the last one shorter): slicing launches nothing
+                B = int(index.shape[0])
+                tp._critic_launch(self.c_desc, self.state, ld_critic, self.ret, index, B, self.workspace, self.c_flat, self.c_loss, None, self.adv, st)
+                tp._actor_launch(self.a_desc, self.state, ld_actor, self.action, self.a_prob, index, B, N, self.adv, self.workspace, self.a_flat,
+                                 self.a_loss, None, st, learner.clip_param, step=j, key=key, step_dev=step_dev)
+                tp._zero_key_bias(learner.actor, self.a_flat, self.a_params)
+                # comm.msg_state2state has no gradient: the optimiser's segment table skips it, here as in the eager step
+                L.clip_and_step(learner.actor_optimizer, learner.actor.parameters(), learner.max_grad_norm, corrections=self.a_table, slot=j,
+                                base_dev=base)
+                L.clip_and_step(learner.critic_optimizer, learner.critic.parameters(), learner.max_grad_norm, corrections=self.c_table, slot=j,
+                                base_dev=base)
+                self.a_sum.add_(self.a_loss)
+                self.c_sum.add_(self.c_loss)
+            cursor_add(self.block, self.EPOCH, 1)
+            cursor_add(self.block, self.BASE, self.m)
+            cursor_add(self.block, self.STEP, self.m)
+
+    @torch.no_grad()
+    def run(self, state, action, old_prob, target, seed: int):
+        """Copy the batch in, reset the cursors, upload the corrections of all steps, replay once per epoch."""
+        learner = self.learner
+        self.state.copy_(state)
+        self.action.copy_(action)
+        self.a_prob.copy_(old_prob)
+        self.ret.copy_(target)
+        seed = int(seed) & (2 ** 64 - 1)
+        cursor_set(self.block, [0, 0, seed & 0xFFFFFFFF, seed >> 32])
+        cursor_set(self.block, [learner.training_step], offset=self.STEP)
+        steps = self.epochs * self.m
+        # fresh pinned tensors: torch's host allocator does not hand them out again before the copies that read them have run
+        self.a_table.copy_(learner.actor_optimizer.correction_table(steps), non_blocking=True)
+        self.c_table.copy_(learner.critic_optimizer.correction_table(steps), non_blocking=True)
+        self.a_sum.zero_()
+        self.c_sum.zero_()
+        for _ in range(self.epochs):
+            self.graph.replay()
+        learner.actor_optimizer.advance(steps)
+        learner.critic_optimizer.advance(steps)
+        learner.training_step += steps
+        return self.a_sum / max(steps, 1), self.c_sum / max(steps, 1), steps
+
+
+def tarmac_ppo_signature(learner) -> list:
+    """Every parameter of both networks (``comm.msg_state2state``, which has no gradient, included) and where its gradient is."""
+    return _signature((list(learner.actor.parameters()), list(learner.critic.parameters())))
+
+
+def _epoch_checks(learner, n: int) -> None:
+    m = (n + learner.batch_size - 1) // learner.batch_size
+    if m > learner.graph_max_minibatches:
+        raise ValueError("graph=True: %d minibatches per epoch, graph_max_minibatches is %d (it bounds the graph's node count and capture time)"
+                         % (m, learner.graph_max_minibatches))
+
+
+def tarmac_ppo_update(learner, batch, seed: int, nb_houses: Optional[int] = None):
+    """``TarMACPPOLearner.update`` with ``graph=True``."""
+    from . import tarmac_ppo as tp
+    states = batch["state"]
+    N = int(nb_houses) if nb_houses is not None else int(learner.critic.critic[-1].out_features)
+    T, A, F = int(states.shape[0]) - 1, int(states.shape[1]), int(states.shape[-1])
+    if N < 1 or A % N:
+        raise ValueError("TarMACPPOLearner.update: %d agents per step are no whole number of envs of %d houses" % (A, N))
+    n = T * (A // N)
+    _epoch_checks(learner, n)
+    if n == 0:
+        return None
+    why = tp._refusal(learner.actor, N) or tp._critic_refusal(learner.critic)
+    if why:
+        raise ValueError("graph=True: %s" % why)
+    for B in _minibatch_rows(n, learner.batch_size):
+        if not learner.uses_kernels(B) or not learner.critic_uses_kernels(B):
+            raise ValueError("graph=True: a minibatch of %d env-steps does not take the actor and the critic kernels" % B)
+    if N != int(learner.critic.critic[-1].out_features) or F != learner.actor.num_obs:
+        raise ValueError("graph=True: the batch holds %d houses of %d features, the networks take %d of %d"
+                         % (N, F, int(learner.critic.critic[-1].out_features), learner.actor.num_obs))
+    key = (T, A, N, F, learner.ppo_update_time, learner.batch_size)
+    g = learner._graphs.get(key)
+    if g is not None and g.signature != tarmac_ppo_signature(learner):      # a parameter or a gradient moved: every graph is stale
+        learner._graphs.clear()
+        g = None
+    if g is None:
+        g = learner._capture(key[:2] + (F,), N)
+    return g.run(states[:T].reshape(n, N, F), batch["action"].reshape(n, N), batch["a_prob"].reshape(n, N), batch["return"].reshape(n, N), seed)
+
+
+class TarMACA2CUpdateGraph:
+    """One epoch of ``TarMACA2CLearner.update`` over a batch of n = T x E env-steps of N agents as one graph: the permutation, then
+    per minibatch ``mdr_tarmac_a2c_grad`` on the static buffers, ONE clip + step over all parameters (the ``base.comm.*`` tensors
+    have no gradient and stay skipped) and the sum of the three losses.  Nothing is drawn besides the permutation."""
+
+    EPOCH, BASE, KEY = 0, 1, 2      # the cursor block: epoch, table base, key lo, key hi
+
+    def __init__(self, learner, T: int, A: int, N: int, F: int):
+        from . import tarmac_a2c as ta      # (tarmac_a2c imports this module)
+        self.learner, self.ta = learner, ta
+        policy = learner.policy
+        dev = policy.dist.linear.weight.device
+        self.dev = dev
+        self.n, self.N, self.F, self.C, self.bs, self.epochs = T * (A // N), N, F, policy.comm_size, learner.batch_size, learner.nb_updates
+        self.m = (self.n + self.bs - 1) // self.bs
+        n = self.n
+        self.obs = torch.zeros((n, N, F), dtype=torch.float32, device=dev)
+        self.comm = torch.zeros((n, N, self.C), dtype=torch.float32, device=dev)
+        self.action = torch.zeros((n, N), dtype=torch.int64, device=dev)
+        self.ret = torch.zeros((n, N), dtype=torch.float32, device=dev)
+        self.perm = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.block = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.table = torch.ones(2 * self.epochs * self.m, dtype=torch.float32, device=dev)
+        self.losses = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.sums = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.params = ta._reached(policy)
+        self.desc = ta._desc(policy)
+        floats, nbytes = zip(*(ta._grad_sizes(self.desc, B, N) for B in _minibatch_rows(n, self.bs)))
+        self.workspace = torch.empty(max(16, *nbytes), dtype=torch.uint8, device=dev)      # the graph's own
+        self.flat = _flat_grad(policy, floats[0], self.params, keep=True)
+        opt = learner.optimizer
+        held = list(policy.parameters()) + [opt._exp_avg, opt._exp_avg_sq, self.flat]      # the flat gradient: ``.grad`` keeps its value over a capture
+        self.graph = _capture(self._record, held, dev)
+        self.signature = _signature((list(policy.parameters()),))
+
+    def _record(self) -> None:
+        """The launches of one epoch on the current stream, from the static buffers alone."""
+        learner, dev, ta = self.learner, self.dev, self.ta
+        st = L.stream(dev)
+        base = self.block[self.BASE:self.BASE + 1]
+        with torch.cuda.device(dev):
+            permutation(self.n, 0, 0, dev, out=self.perm, cursor=self.block[self.EPOCH:], key=self.block[self.KEY:])
+            for j in range(self.m):
+                index = self.perm[j * self.bs:(j + 1) * self.bs]
+                B = int(index.shape[0])
+                ta._grad_launch(self.desc, self.obs, self.F, self.comm, self.C, self.action, self.ret, index, B, self.N, self.workspace, self.flat,
+                                self.losses, None, None, st, learner.value_loss_coef, learner.entropy_coef)
+                L.clip_and_step(learner.optimizer, learner.policy.parameters(), learner.max_grad_norm, corrections=self.table, slot=j, base_dev=base)
+                self.sums.add_(self.losses)
+            cursor_add(self.block, self.EPOCH, 1)
+            cursor_add(self.block, self.BASE, self.m)
+
+    @torch.no_grad()
+    def run(self, obs, comm, action, ret, seed: int):
+        learner = self.learner
+        self.obs.copy_(obs)
+        self.comm.copy_(comm)
+        self.action.copy_(action)
+        self.ret.copy_(ret)
+        seed = int(seed) & (2 ** 64 - 1)
+        cursor_set(self.block, [0, 0, seed & 0xFFFFFFFF, seed >> 32])
+        steps = self.epochs * self.m
+        self.table.copy_(learner.optimizer.correction_table(steps), non_blocking=True)      # a fresh pinned tensor, as PPOUpdateGraph's
+        self.sums.zero_()
+        for _ in range(self.epochs):
+            self.graph.replay()
+        learner.optimizer.advance(steps)
+        learner.training_step += steps
+        out = self.sums / max(steps, 1)
+        return out[0], out[1], out[2], steps
+
+
+def tarmac_a2c_update(learner, batch, seed: int, nb_agents: Optional[int] = None):
+    """``TarMACA2CLearner.update`` with ``graph=True``."""
+    from . import tarmac_a2c as ta
+    states, comms = batch["state"], batch["comm"]
+    T, A, F = int(states.shape[0]) - 1, int(states.shape[1]), int(states.shape[-1])
+    N = int(nb_agents) if nb_agents is not None else A // int(batch["value"].shape[1])
+    if N < 1 or A % N:
+        raise ValueError("TarMACA2CLearner.update: %d agents per step are no whole number of envs of %d agents" % (A, N))
+    n = T * (A // N)
+    _epoch_checks(learner, n)
+    if n == 0:
+        return None
+    why = ta._refusal(learner.policy, N)
+    if why:
+        raise ValueError("graph=True: %s" % why)
+    for B in _minibatch_rows(n, learner.batch_size):
+        if not learner.uses_kernels(B, N):
+            raise ValueError("graph=True: a minibatch of %d env-steps of %d agents does not take the kernels" % (B, N))
+    if F != learner.policy.nb_obs or int(comms.shape[-1]) != learner.policy.comm_size:
+        raise ValueError("graph=True: the batch holds %d features and %d comm columns, the policy takes %d and %d"
+                         % (F, int(comms.shape[-1]), learner.policy.nb_obs, learner.policy.comm_size))
+    key = (T, A, N, F, learner.nb_updates, learner.batch_size)
+    g = learner._graphs.get(key)
+    if g is not None and g.signature != _signature((list(learner.policy.parameters()),)):
+        learner._graphs.clear()
+        g = None
+    if g is None:
+        g = learner._capture(key[:2] + (F,), N)
+    Cc = learner.policy.comm_size
+    return g.run(states[:T].reshape(n, N, F), comms[:T].reshape(n, N, Cc), batch["action"].reshape(n, N), batch["return"].reshape(n, N), seed)

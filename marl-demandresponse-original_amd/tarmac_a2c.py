@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from . import _learner as L
 from . import _native as nat
+from . import graph_update
 
 # the kernels' limits (include/mdr_policy.h: mdr_tarmac_a2c_*)
 MAX_OBS, MAX_COMM, MAX_STATE, MAX_KEY, MAX_AGENTS = 128, 32, 128, 16, 64
@@ -304,21 +305,35 @@ def loss_backward(policy, obs: torch.Tensor, comm: torch.Tensor, action: torch.T
     B = int(index.shape[0]) if index is not None else M
     L.whole(action, torch.int64, M * N, dev, what, "action")
     L.whole(ret, torch.float32, M * N, dev, what, "ret")
-    lib = nat.load()
     desc = _desc(policy)
-    flat = L.flat_grad(policy, lib.mdr_tarmac_a2c_grad_floats(C.byref(desc)), dev)
-    ws = L.workspace(dev, L.sized(lib.mdr_tarmac_a2c_workspace_bytes(C.byref(desc), B, N, max_workgroups), what, "mdr_tarmac_a2c_workspace_bytes"))
+    floats, nbytes = _grad_sizes(desc, B, N, max_workgroups, what)
+    flat = L.flat_grad(policy, floats, dev)
     losses = torch.empty(3, dtype=torch.float32, device=dev)
     value = torch.empty(B, dtype=torch.float32, device=dev) if want_value else None
     advantage = torch.empty((B, N), dtype=torch.float32, device=dev) if want_value else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_tarmac_a2c_grad(C.byref(desc), L.ptr(obs), ld_obs, L.ptr(comm), ld_comm, L.ptr(action), L.ptr(ret), L.ptr(index), B, N,
-                                     C.c_float(value_loss_coef), C.c_float(entropy_coef), max_workgroups, L.ptr(ws), L.ptr(flat), L.ptr(losses),
-                                     L.ptr(value), L.ptr(advantage), L.stream(dev))
-    nat.check(lib, None, rc, "mdr_tarmac_a2c_grad")
+        _grad_launch(desc, obs, ld_obs, comm, ld_comm, action, ret, index, B, N, L.workspace(dev, nbytes), flat, losses, value, advantage,
+                     L.stream(dev), value_loss_coef, entropy_coef, max_workgroups)
     L.publish(_reached(policy), flat, L.REPLACE)      # whoever holds a tensor that was there sees the new gradient too
     out = (losses[0], losses[1], losses[2])
     return out + (value, advantage) if want_value else out
+
+
+def _grad_sizes(desc, B: int, N: int, max_workgroups: int = 0, what: str = "tarmac_a2c") -> Tuple[int, int]:
+    """(floats of the flat gradient, bytes of workspace) of an ``mdr_tarmac_a2c_grad`` call over ``B`` env-steps of ``N`` agents."""
+    lib = nat.load()
+    return (int(lib.mdr_tarmac_a2c_grad_floats(C.byref(desc))),
+            L.sized(lib.mdr_tarmac_a2c_workspace_bytes(C.byref(desc), B, N, max_workgroups), what, "mdr_tarmac_a2c_workspace_bytes"))
+
+
+def _grad_launch(desc, obs, ld_obs, comm, ld_comm, action, ret, index, B, N, workspace, flat, losses, value, advantage, stream,
+                 value_loss_coef: float, entropy_coef: float, max_workgroups: int = 0) -> None:
+    """mdr_tarmac_a2c_grad on checked tensors and caller-owned buffers, under the device of ``obs``: the eager call and the captured one."""
+    lib = nat.load()
+    rc = lib.mdr_tarmac_a2c_grad(C.byref(desc), L.ptr(obs), ld_obs, L.ptr(comm), ld_comm, L.ptr(action), L.ptr(ret), L.ptr(index), B, N,
+                                 C.c_float(value_loss_coef), C.c_float(entropy_coef), max_workgroups, L.ptr(workspace), L.ptr(flat), L.ptr(losses),
+                                 L.ptr(value), L.ptr(advantage), stream)
+    nat.check(lib, None, rc, "mdr_tarmac_a2c_grad")
 
 
 def dense_losses(policy, obs, comm, action, ret):
@@ -342,11 +357,18 @@ class TarMACA2CLearner:
     comparator, the CPU path and the path for more than one hop; ``"auto"``: the kernels where ``supported(policy)`` holds and the
     minibatch has ``AUTO_MIN_AGENT_ROWS`` to ``AUTO_MAX_AGENT_ROWS`` agent rows - env-steps x agents - (where they measured
     faster, profiles/tarmac_a2c_README.md), torch otherwise.  ``optimizer=FusedAdam``: clip + Adam in one launch; parameters whose ``grad`` is
-    None (``base.comm.*``) are skipped, as torch's Adam skips them."""
+    None (``base.comm.*``) are skipped, as torch's Adam skips them.
+
+    ``sampler="philox"``: the minibatch indices from csrc/mdr_minibatch.hip by (seed, epoch) instead of a ``torch.Generator`` (default
+    ``"torch"``; ``"philox"`` under ``graph=True``).  ``graph=True``: every epoch of an update replayed from one captured graph per
+    batch shape (graph_update.TarMACA2CUpdateGraph), the bits of the eager ``sampler="philox"`` update; it needs the kernels,
+    ``optimizer=FusedAdam`` and the philox sampler.  ``graph_max_minibatches`` bounds the minibatches (of env-steps) per epoch."""
 
     def __init__(self, policy, lr: float = 7e-4, value_loss_coef: float = 0.5, entropy_coef: float = 0.01, max_grad_norm: float = 0.5,
-                 nb_updates: int = 10, batch_size: int = 128, backend: str = "auto", optimizer=torch.optim.Adam):
+                 nb_updates: int = 10, batch_size: int = 128, backend: str = "auto", optimizer=torch.optim.Adam,
+                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024):
         L.check_backend(backend)
+        sampler = L.check_sampler(sampler, graph)
         if backend == "hip":
             L.require(_refusal(policy), "TarMACA2CLearner")
         self.policy = policy
@@ -354,15 +376,27 @@ class TarMACA2CLearner:
         self.nb_updates, self.batch_size, self.backend = int(nb_updates), int(batch_size), backend
         self.optimizer = optimizer(policy.parameters(), lr)
         self.training_step = 0
+        self.sampler, self.graph, self.graph_max_minibatches = sampler, bool(graph), int(graph_max_minibatches)
+        self.graph_captures = 0
+        self._graphs: Dict[tuple, object] = {}
+        if self.graph:
+            # the agents per env come with the batch: "auto" is held to its window again at every update (graph_update.tarmac_a2c_update)
+            takes = _refusal(policy) is None if backend == "auto" else backend == "hip"
+            why = graph_update.refusal(backend, sampler, (self.optimizer,), takes)
+            if not why and backend == "auto":
+                why = _refusal(policy)
+            if why:
+                raise ValueError("TarMACA2CLearner(graph=True): %s" % why)
 
     @classmethod
-    def from_config(cls, tarmac_prop: dict, policy, backend: str = "auto", optimizer=torch.optim.Adam) -> "TarMACA2CLearner":
+    def from_config(cls, tarmac_prop: dict, policy, backend: str = "auto", optimizer=torch.optim.Adam, sampler: Optional[str] = None,
+                    graph: bool = False, graph_max_minibatches: int = 1024) -> "TarMACA2CLearner":
         """From the reference's ``config_dict["TarMAC_prop"]`` (a2c_acktr.py:17-32); tarmac_eps and tarmac_alpha belong to the
         RMSprop line the reference has commented out and are not read."""
         p = tarmac_prop
         return cls(policy, lr=p["tarmac_lr"], value_loss_coef=p["value_loss_coef"], entropy_coef=p["entropy_coef"],
                    max_grad_norm=p["tarmac_max_grad_norm"], nb_updates=p["nb_tarmac_updates"], batch_size=p["tarmac_batch_size"],
-                   backend=backend, optimizer=optimizer)
+                   backend=backend, optimizer=optimizer, sampler=sampler, graph=graph, graph_max_minibatches=graph_max_minibatches)
 
     def uses_kernels(self, nb_env_steps: int, nb_agents: int) -> bool:
         if self.backend == "auto":
@@ -370,8 +404,17 @@ class TarMACA2CLearner:
         return self.backend == "hip"
 
     def minibatches(self, nb_env_steps: int, seed: int, epoch: int) -> List[torch.Tensor]:
-        """The index tensors of one epoch over the stored env-steps (``_learner.minibatches``, torch's sampler)."""
-        return L.minibatches(next(self.policy.parameters()).device, nb_env_steps, self.batch_size, "torch", seed, epoch)
+        """The index tensors of one epoch over the stored env-steps (``_learner.minibatches`` under this learner's sampler)."""
+        return L.minibatches(next(self.policy.parameters()).device, nb_env_steps, self.batch_size, self.sampler, seed, epoch)
+
+    def _capture(self, shape, nb_agents: int):
+        """Capture the graph of one epoch over a batch of ``shape`` = (T, A, F) - A = E N agents per step, N = ``nb_agents`` - without
+        replaying it; parameters, moments and every counter are what they were."""
+        T, A, F = (int(x) for x in shape)
+        g = graph_update.TarMACA2CUpdateGraph(self, T, A, int(nb_agents), F)
+        self._graphs[(T, A, int(nb_agents), F, self.nb_updates, self.batch_size)] = g
+        self.graph_captures += 1
+        return g
 
     def step_minibatch(self, obs, comm, action, ret, index) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """One minibatch of a2c_acktr.py:61-107 on the whole buffers ``obs`` [M, N, F], ``comm`` [M, N, C], ``action``, ``ret`` [M, N];
@@ -391,7 +434,12 @@ class TarMACA2CLearner:
     def update(self, batch: Dict[str, torch.Tensor], seed: int = 0, nb_agents: Optional[int] = None):
         """``nb_updates`` epochs over ``batch`` (``state`` [T+1, E*N, F], ``comm`` [T+1, E*N, C], ``action``, ``return`` [T, E*N],
         ``value`` [T+1, E] - which gives E): the T E stored env-steps are ``state[:-1]`` and ``comm[:-1]`` viewed as [T E, N, .] and read
-        in place.  -> (mean value_loss, mean action_loss, mean entropy - device tensors -, number of minibatches)."""
+        in place.  -> (mean value_loss, mean action_loss, mean entropy - device tensors -, number of minibatches).  ``graph=True``: the
+        same launches replayed from a captured graph, the same bits as the eager ``sampler="philox"`` update."""
+        if self.graph:
+            done = graph_update.tarmac_a2c_update(self, batch, seed, nb_agents)
+            if done is not None:      # None: an empty batch, nothing to replay
+                return done
         states, comms = batch["state"], batch["comm"]
         T = states.shape[0] - 1
         N = int(nb_agents) if nb_agents is not None else states.shape[1] // int(batch["value"].shape[1])

@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import _learner as L
 from . import _native as nat
+from . import graph_update
 from .tarmac import FUSED_MAX_HIDDEN, FUSED_MAX_KEY, FUSED_MAX_OBS, FUSED_MAX_VALUE, MAX_COMM, MODES, TarMACActor
 
 # backend="auto": the kernels from this many env-steps per minibatch on (profiles/tarmac_ppo_README.md: they measured faster than
@@ -38,8 +39,8 @@ def _head(actor):
     return actor.comm_hidden2action if actor.with_comm else actor.hidden2action
 
 
-def _refusal(actor, nb_houses: Optional[int] = None) -> Optional[str]:
-    """Why the kernels do not take ``actor`` (None: they do)."""
+def _shape_refusal(actor, nb_houses: Optional[int] = None) -> Optional[str]:
+    """Why the kernels do not take an actor of this class, these sizes, hops and comm mode, wherever its parameters are."""
     if not isinstance(actor, TarMACActor):
         return "the kernels cover a TarMACActor"
     if actor.num_hops != 1:
@@ -59,6 +60,14 @@ def _refusal(actor, nb_houses: Optional[int] = None) -> Optional[str]:
             return "the kernels cover the comm modes 'neighbours' and 'none'"
         if nb_houses is not None and actor.comm_mode == "neighbours" and min(actor.number_agents_comm, nb_houses - 1) > MAX_COMM:
             return "band attention covers at most %d senders per receiver" % MAX_COMM
+    return None
+
+
+def _refusal(actor, nb_houses: Optional[int] = None) -> Optional[str]:
+    """Why the kernels do not take ``actor`` (None: they do)."""
+    why = _shape_refusal(actor, nb_houses)
+    if why:
+        return why
     for p in _params(actor):
         if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
             return "parameters must be contiguous float32 tensors on the GPU"
@@ -120,28 +129,60 @@ def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_pr
     L.whole(advantage, torch.float32, B * N, dev, what, "advantage")
     if not 0.0 <= float(clip_param) < 1.0:
         raise ValueError("%s: clip_param must lie in [0, 1)" % what)
-    lib = nat.load()
     desc = _desc(actor)
-    flat = L.flat_grad(actor, lib.mdr_tarmac_net_grad_floats(C.byref(desc)), dev)
-    ws = L.workspace(dev, L.sized(lib.mdr_tarmac_ppo_workspace_bytes(C.byref(desc), B, N, max_workgroups), what, "mdr_tarmac_ppo_workspace_bytes"))
+    floats, nbytes = _actor_sizes(desc, B, N, max_workgroups, what)
+    flat = L.flat_grad(actor, floats, dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ratio = torch.empty((B, N), dtype=torch.float32, device=dev) if want_ratio else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_tarmac_ppo_actor_grad(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, N, L.ptr(action), L.ptr(old_prob), L.ptr(advantage),
-                                           C.c_float(clip_param), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(step & (2 ** 64 - 1)), max_workgroups,
-                                           L.ptr(ws), L.ptr(flat), L.ptr(loss), L.ptr(ratio), L.stream(dev))
-    nat.check(lib, None, rc, "mdr_tarmac_ppo_actor_grad")
+        _actor_launch(desc, state, ld, action, old_prob, index, B, N, advantage, L.workspace(dev, nbytes), flat, loss, ratio, L.stream(dev),
+                      clip_param, seed=seed, step=step, max_workgroups=max_workgroups)
     params = _params(actor)
-    if actor.with_comm:
-        # hidden2key's last bias adds q_i . b to every score of receiver i: the softmax over its senders does not see it, and the
-        # reference's autograd returns exact zeros for it.  The kernels' sums leave 1e-9 of rounding there, which Adam - dividing by
-        # |g| + 1e-8 - turns into a tenth of a learning rate per step on a parameter the reference never moves
-        # (profiles/learner_golden_README.md).  The identically vanishing gradient is written as what it is.
-        at = [id(p) for p in params].index(id(actor.comm.hidden2key[2].bias))
-        off = sum(p.numel() for p in params[:at])
-        flat[off:off + params[at].numel()].zero_()
+    _zero_key_bias(actor, flat, params)
     L.publish(params, flat, L.KEEP)
     return (loss, ratio) if want_ratio else loss
+
+
+def _actor_sizes(desc, B: int, N: int, max_workgroups: int = 0, what: str = "tarmac_ppo") -> Tuple[int, int]:
+    """(floats of the flat gradient, bytes of workspace) of an ``mdr_tarmac_ppo_actor_grad`` call over ``B`` env-steps of ``N`` agents."""
+    lib = nat.load()
+    return (int(lib.mdr_tarmac_net_grad_floats(C.byref(desc))),
+            L.sized(lib.mdr_tarmac_ppo_workspace_bytes(C.byref(desc), B, N, max_workgroups), what, "mdr_tarmac_ppo_workspace_bytes"))
+
+
+def _actor_launch(desc, state, ld, action, old_prob, index, B, N, advantage, workspace, flat, loss, ratio, stream, clip_param, seed: int = 0,
+                  step: int = 0, key: Optional[torch.Tensor] = None, step_dev: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> None:
+    """mdr_tarmac_ppo_actor_grad on checked tensors and caller-owned buffers, under the device of ``state``: the eager call and the
+    captured one.  ``key`` (device int32 [2] = seed lo, hi): mdr_tarmac_ppo_actor_grad_keyed, which reads the defects' key there and
+    adds ``step_dev`` (one device int32, optional) to the low word of ``step`` when the kernels run."""
+    lib = nat.load()
+    step = C.c_uint64(int(step) & (2 ** 64 - 1))
+    if key is not None:
+        rc = lib.mdr_tarmac_ppo_actor_grad_keyed(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, N, L.ptr(action), L.ptr(old_prob), L.ptr(advantage),
+                                                 C.c_float(clip_param), L.ptr(key), step, L.ptr(step_dev), max_workgroups, L.ptr(workspace),
+                                                 L.ptr(flat), L.ptr(loss), L.ptr(ratio), stream)
+        nat.check(lib, None, rc, "mdr_tarmac_ppo_actor_grad_keyed")
+        return
+    if step_dev is not None:
+        raise ValueError("tarmac_ppo: step_dev goes with key (mdr_tarmac_ppo_actor_grad_keyed)")
+    rc = lib.mdr_tarmac_ppo_actor_grad(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, N, L.ptr(action), L.ptr(old_prob), L.ptr(advantage),
+                                       C.c_float(clip_param), C.c_uint64(int(seed) & (2 ** 64 - 1)), step, max_workgroups, L.ptr(workspace),
+                                       L.ptr(flat), L.ptr(loss), L.ptr(ratio), stream)
+    nat.check(lib, None, rc, "mdr_tarmac_ppo_actor_grad")
+
+
+def _zero_key_bias(actor, flat: torch.Tensor, params: Optional[List[torch.Tensor]] = None) -> None:
+    """hidden2key's last bias adds q_i . b to every score of receiver i: the softmax over its senders does not see it, and the
+    reference's autograd returns exact zeros for it.  The kernels' sums leave 1e-9 of rounding there, which Adam - dividing by
+    |g| + 1e-8 - turns into a tenth of a learning rate per step on a parameter the reference never moves
+    (profiles/learner_golden_README.md).  The identically vanishing gradient is written as what it is: one ``zero_()`` on its slice of
+    the flat gradient (nothing without communication).  ``params``: ``_params(actor)`` where the caller has it."""
+    if not actor.with_comm:
+        return
+    params = _params(actor) if params is None else params
+    at = [id(p) for p in params].index(id(actor.comm.hidden2key[2].bias))
+    off = sum(p.numel() for p in params[:at])
+    flat[off:off + params[at].numel()].zero_()
 
 
 def _critic_layers(critic) -> Optional[List[nn.Linear]]:
@@ -223,20 +264,32 @@ def critic_loss_backward(critic, state: torch.Tensor, target: torch.Tensor, inde
     what = "tarmac_ppo.critic_loss_backward"
     dev, M, N, ld, B = _critic_steps(critic, state, index, what)
     L.whole(target, torch.float32, M * N, dev, what, "target")
-    lib = nat.load()
     lin = _critic_layers(critic)
     desc = L.mlp_desc(lin)
-    flat = L.flat_grad(critic, lib.mdr_tarmac_critic_grad_floats(C.byref(desc)), dev)
-    ws = L.workspace(dev, L.sized(lib.mdr_tarmac_critic_workspace_bytes(C.byref(desc), B, max_workgroups), what, "mdr_tarmac_critic_workspace_bytes"))
+    floats, nbytes = _critic_sizes(desc, B, max_workgroups, what)
+    flat = L.flat_grad(critic, floats, dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     advantage = torch.empty((B, N), dtype=torch.float32, device=dev)
     value = torch.empty((B, N), dtype=torch.float32, device=dev) if want_value else None
     with torch.cuda.device(dev):
-        rc = lib.mdr_tarmac_critic_grad(C.byref(desc), L.ptr(state), ld, L.ptr(target), L.ptr(index), B, max_workgroups, L.ptr(ws), L.ptr(flat),
-                                        L.ptr(loss), L.ptr(value), L.ptr(advantage), L.stream(dev))
-    nat.check(lib, None, rc, "mdr_tarmac_critic_grad")
+        _critic_launch(desc, state, ld, target, index, B, L.workspace(dev, nbytes), flat, loss, value, advantage, L.stream(dev), max_workgroups)
     L.publish(L.mlp_params(lin), flat, L.KEEP)
     return (loss, advantage, value) if want_value else (loss, advantage)
+
+
+def _critic_sizes(desc, B: int, max_workgroups: int = 0, what: str = "tarmac_ppo") -> Tuple[int, int]:
+    """(floats of the flat gradient, bytes of workspace) of an ``mdr_tarmac_critic_grad`` call over ``B`` env-steps."""
+    lib = nat.load()
+    return (int(lib.mdr_tarmac_critic_grad_floats(C.byref(desc))),
+            L.sized(lib.mdr_tarmac_critic_workspace_bytes(C.byref(desc), B, max_workgroups), what, "mdr_tarmac_critic_workspace_bytes"))
+
+
+def _critic_launch(desc, state, ld, target, index, B, workspace, flat, loss, value, advantage, stream, max_workgroups: int = 0) -> None:
+    """mdr_tarmac_critic_grad on checked tensors and caller-owned buffers: the eager call and the captured one."""
+    lib = nat.load()
+    rc = lib.mdr_tarmac_critic_grad(C.byref(desc), L.ptr(state), ld, L.ptr(target), L.ptr(index), B, max_workgroups, L.ptr(workspace), L.ptr(flat),
+                                    L.ptr(loss), L.ptr(value), L.ptr(advantage), stream)
+    nat.check(lib, None, rc, "mdr_tarmac_critic_grad")
 
 
 class TarMACPPOLearner:
@@ -252,13 +305,21 @@ class TarMACPPOLearner:
     gradient come first and give the advantage, then the actor's loss, clip and step, then the critic's clip and step, the
     reference's order; no ``zero_grad()`` on the critic, the kernels overwrite its gradient; ``"auto"``: the kernels where
     ``critic_supported(critic)`` holds and the minibatch has ``CRITIC_AUTO_MIN_ENV_STEPS`` to ``CRITIC_AUTO_MAX_ENV_STEPS`` env-steps
-    (where they measured faster, profiles/tarmac_critic_README.md), torch otherwise."""
+    (where they measured faster, profiles/tarmac_critic_README.md), torch otherwise.
+
+    ``sampler="philox"``: the minibatch indices from csrc/mdr_minibatch.hip by (seed, epoch) instead of a ``torch.Generator`` (default
+    ``"torch"``; ``"philox"`` under ``graph=True``).  ``graph=True``: every epoch of an update replayed from one captured graph per
+    batch shape (graph_update.TarMACPPOUpdateGraph), the bits of the eager ``sampler="philox"`` update; it needs the kernels for the
+    actor AND the critic (``critic_backend="hip"``, or ``"auto"`` with ``batch_size`` inside its window - a torch-autograd critic is
+    refused), ``optimizer=FusedAdam`` and the philox sampler.  ``graph_max_minibatches`` bounds the minibatches (of env-steps) per
+    epoch, hence the graph's node count."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
                  ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
-                 critic_backend: str = "torch"):
+                 critic_backend: str = "torch", sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024):
         L.check_backend(backend)
         L.check_backend(critic_backend, "critic_backend")
+        sampler = L.check_sampler(sampler, graph)
         if backend == "hip":
             L.require(_refusal(actor), "TarMACPPOLearner")
         if critic_backend == "hip":
@@ -270,15 +331,34 @@ class TarMACPPOLearner:
         self.actor_optimizer = optimizer(actor.parameters(), lr_actor)
         self.critic_optimizer = optimizer(critic.parameters(), lr_critic)
         self.training_step = 0
+        self.sampler, self.graph, self.graph_max_minibatches = sampler, bool(graph), int(graph_max_minibatches)
+        self.graph_captures = 0
+        self._graphs: Dict[tuple, object] = {}
+        if self.graph:
+            rows = max(self.batch_size, 1)
+            # backend and sampler first, then what the networks are (reasons that name the network), then the optimisers
+            why = graph_update.refusal(backend, sampler, (), True) or _shape_refusal(actor)
+            if not why and critic_backend == "auto":
+                why = _critic_refusal(critic)
+            if not why and not self.critic_uses_kernels(rows):
+                why = ("critic_backend=%r steps the critic through torch's autograd at %d env-steps per minibatch, not a fixed chain of "
+                       "launches; graph=True needs the critic kernels (critic_backend='hip', or 'auto' inside its window)" % (critic_backend, rows))
+            if not why and backend == "auto":      # uses_kernels() asks supported(), which gives no reason
+                why = _refusal(actor)
+            if not why:
+                why = graph_update.refusal(backend, sampler, (self.actor_optimizer, self.critic_optimizer), self.uses_kernels(rows))
+            if why:
+                raise ValueError("TarMACPPOLearner(graph=True): %s" % why)
 
     @classmethod
     def from_config(cls, tarmac_ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam,
-                    critic_backend: str = "torch") -> "TarMACPPOLearner":
+                    critic_backend: str = "torch", sampler: Optional[str] = None, graph: bool = False,
+                    graph_max_minibatches: int = 1024) -> "TarMACPPOLearner":
         """From the reference's ``config_dict["TarMAC_PPO_prop"]`` (agents/tarmac_ppo.py:39-45)."""
         p = tarmac_ppo_prop
         return cls(actor, critic, p["lr_actor"], p["lr_critic"], clip_param=p["clip_param"], max_grad_norm=p["max_grad_norm"],
                    ppo_update_time=p["ppo_update_time"], batch_size=p["batch_size"], backend=backend, optimizer=optimizer,
-                   critic_backend=critic_backend)
+                   critic_backend=critic_backend, sampler=sampler, graph=graph, graph_max_minibatches=graph_max_minibatches)
 
     def uses_kernels(self, nb_env_steps: int) -> bool:
         if self.backend == "auto":
@@ -291,8 +371,18 @@ class TarMACPPOLearner:
         return self.critic_backend == "hip"
 
     def minibatches(self, nb_env_steps: int, seed: int, epoch: int) -> List[torch.Tensor]:
-        """The index tensors of one epoch over the stored env-steps (``_learner.minibatches``, torch's sampler)."""
-        return L.minibatches(next(self.actor.parameters()).device, nb_env_steps, self.batch_size, "torch", seed, epoch)
+        """The index tensors of one epoch over the stored env-steps (``_learner.minibatches`` under this learner's sampler)."""
+        return L.minibatches(next(self.actor.parameters()).device, nb_env_steps, self.batch_size, self.sampler, seed, epoch)
+
+    def _capture(self, shape, nb_houses: Optional[int] = None):
+        """Capture the graph of one epoch over a batch of ``shape`` = (T, A, F) - A = E N agents per step, N = ``nb_houses`` (default:
+        the critic's number of agents) - without replaying it; parameters, moments and every counter are what they were."""
+        T, A, F = (int(x) for x in shape)
+        N = int(nb_houses) if nb_houses is not None else int(self.critic.critic[-1].out_features)
+        g = graph_update.TarMACPPOUpdateGraph(self, T, A, N, F)
+        self._graphs[(T, A, N, F, self.ppo_update_time, self.batch_size)] = g
+        self.graph_captures += 1
+        return g
 
     def step_minibatch(self, state, action, old_prob, target, index, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """One minibatch of agents/tarmac_ppo.py:159-207.  ``state`` [M, N, F], ``action``, ``old_prob``, ``target`` [M, N]: the whole
@@ -330,7 +420,12 @@ class TarMACPPOLearner:
     def update(self, batch: Dict[str, torch.Tensor], seed: int = 0, nb_houses: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, int]:
         """``ppo_update_time`` epochs over ``batch`` (``state`` [T+1, E*N, F], ``action``, ``a_prob``, ``return`` [T, E*N]): the T E
         stored env-steps are ``batch["state"][:-1]`` viewed as [T E, N, F] and read in place, Gt is ``batch["return"]``.  ``nb_houses``
-        (N): default the critic's number of agents.  -> (mean actor loss, mean critic loss - device tensors -, number of minibatches)."""
+        (N): default the critic's number of agents.  -> (mean actor loss, mean critic loss - device tensors -, number of minibatches).
+        ``graph=True``: the same launches replayed from a captured graph, the same bits as the eager ``sampler="philox"`` update."""
+        if self.graph:
+            done = graph_update.tarmac_ppo_update(self, batch, seed, nb_houses)
+            if done is not None:      # None: an empty batch, nothing to replay
+                return done
         states = batch["state"]
         N = int(nb_houses) if nb_houses is not None else int(self.critic.critic[-1].out_features)
         T = states.shape[0] - 1
