@@ -304,6 +304,37 @@ __device__ __forceinline__ HouseLeanM house_advance_lean_m(const HouseIn& h, uin
   return o;
 }
 
+// The lean step with a TIME STAMP in place of the counter, for a lockout that is one value L for every house (UNIFORM_LOCKOUT).
+// Times count in seconds from the launch's first step: step s starts at Ts = s dt and ends at Tn = Ts + dt, both scalars.  The house
+// keeps z, the end of the last step that left its HVAC on; a house off since before the launch keeps the z that time would have had.
+// At the start of a step an `on` house then has z = Ts and an `off` one sso = Ts - dt - z (the step behind the last `on` one leaves
+// 0, env 475-476), so the lean form reads
+//     can  = on or sso + dt >= L                     is   on or z <= Ts - L            one compare against a scalar
+//     sso2 = 0 if (on or on2) else sso + dt          is   z2 = Tn if on2 else z        one select steered by on2 itself
+// - no add, no OR for the select's mask, no lockout register.  Integers throughout: exact wherever the counter form does not overflow
+// (the caller's bound dt x (steps of a launch) < 2^31 stays; z >= -(the sso the first step left) and Ts - L >= -L cannot).
+// house_stamp forms z behind the launch's general first step, house_stamp_sso the counter behind its last, in front of house_lock_m.
+__device__ __forceinline__ HouseLeanM house_advance_stamp_m(const HouseIn& h, int z, uint64_t on_m, uint64_t cmd_m, float od_old, float solar, int Tn,
+                                                            int Ts_minus_L) {
+  const uint64_t can_m = on_m | __builtin_amdgcn_ballot_w64(z <= Ts_minus_L);                  // env 475-481
+  const uint64_t on2_m = can_m & cmd_m;                                                        // env 483-486
+  const int z2 = lane_bit(on2_m) ? Tn : z;                                                     // env 487-488
+  const float Qa = (lane_bit(on2_m) ? h.Q_hvac : 0.0f) + solar;  // env 690-699
+  const float Tinf = fmaf(Qa, h.inv_Ua, od_old);     // uses the PREVIOUS step's outdoor temperature (env 1034)
+  const float dm = h.Tm - h.Ta;
+  HouseLeanM o;
+  o.Ta = h.Ta + fmaf(h.k01, dm, h.s0 * (h.Ta - Tinf));
+  o.Tm = h.Tm + fmaf(-h.k10, dm, h.s1 * (h.Tm - Tinf));
+  o.sso = z2;
+  o.on = on2_m;
+  o.can = can_m;
+  return o;
+}
+
+// Into the stamp at time T, the end of a step that left (on, sso) with on => sso == 0, and back: sso = 0 for an `on` house (z = T).
+__device__ __forceinline__ int house_stamp(bool on, int sso, int T, int dt) { return on ? T : T - dt - sso; }
+__device__ __forceinline__ int house_stamp_sso(int z, int T, int dt) { return max(0, T - dt - z); }
+
 // env 489-492 behind the last step: `can_m`, `on_m` and `sso` as that step left them
 __device__ __forceinline__ uint64_t house_lock_m(uint64_t can_m, uint64_t on_m, int sso, int lockout, int dt) {
   return ~can_m | (~on_m & __builtin_amdgcn_ballot_w64(sso + dt < lockout));

@@ -19,8 +19,18 @@
 // The loop body is house_advance_lean_m (mdr_device.h): the first step of a launch in the general form, every later one in the lean
 // form (one add, one compare, one select for the HVAC's integer state), and the lock mask once, behind the last step
 // (house_lock_m on the `can` mask that step left in scalar registers).  A blank lane's sso is never stored and is left to grow by
-// dt per step: mdr_api.hip keeps dt x (steps of a launch) below 2^31.  The step forms it replaces, by env->plan as
-// launch_step picks them:
+// dt per step: mdr_api.hip keeps dt x (steps of a launch) below 2^31.
+//
+// Where one lockout holds for every house (UNIFORM_LOCKOUT of the param_uniform word: every configuration the reference trains with)
+// the steps behind the first run house_advance_stamp_m instead: the house keeps the TIME its HVAC was last on, not a counter, and the
+// launch's step time is a scalar that doubles as the loop's counter - one compare against a scalar and one select steered by on2
+// itself for the HVAC's integer state: no add, no OR for the select's mask, no lockout register, no separate loop counter.  The
+// same bits (tests/test_stamp_step_algebra.py, tests/test_gpu_rollout_resident_stamps.py).  The word is device-side, so each kernel
+// holds both forms of its body behind one wave-uniform branch, each with the registers it needs; without the bit the loop is the
+// counter form's, instruction for instruction.  k_rollout_resident<4,1,256,true> per trip: 61 vector and 17 other instructions where
+// the counter form has 64 and 23 (profiles/r13_README.md).
+//
+// The step forms it replaces, by env->plan as launch_step picks them:
 //   k_rollout_resident<VEC, TILES, THREADS, BB>   for k_step_fused<VEC, TILES, THREADS, 1, ..>: the rows are wave-uniform scalar
 //                                                 loads, fetched one step ahead; the other resident waves hide the rest
 //   k_rollout_resident_group<GROUP, VEC, BB>      for k_step_group<GROUP, VEC, 1, ..>: each lane reads its own env's rows
@@ -90,12 +100,35 @@ __device__ __forceinline__ void resident_advance(const StepArgs& a, bool ext, Ho
   }
 }
 
-template <int VEC, int TILES, int THREADS, bool BB>
-__global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, RolloutArgs ro, const float2* __restrict__ rows) {
-  if (ro.nsteps <= 0) return;
+// The same step in the time-stamp form (house_advance_stamp_m; hs[v].sso holds the stamp z), under a uniform lockout.
+template <int VEC, bool BB>
+__device__ __forceinline__ void resident_advance_stamp(const StepArgs& a, bool ext, HouseIn* hs, uint64_t* on_m,
+                                                       uint64_t* can_m, uint64_t* cmd_m, float od_old, float solar, int Tn, int Ts_minus_L) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    if (BB) cmd_m[v] = __builtin_amdgcn_ballot_w64(hs[v].Ta > hs[v].target);   // agents/bangbang_controllers.py:49-59
+    else if (!ext) cmd_m[v] = controller_cmd_m(a.action_source, hs[v].Ta, hs[v].target, hs[v].deadband, on_m[v]);
+    const HouseLeanM n = house_advance_stamp_m(hs[v], hs[v].sso, on_m[v], cmd_m[v], od_old, solar, Tn, Ts_minus_L);
+    hs[v].Ta = n.Ta;
+    hs[v].Tm = n.Tm;
+    hs[v].sso = n.sso;
+    on_m[v] = n.on;
+    can_m[v] = n.can;
+  }
+}
+
+// Where k_rollout_resident holds the stamp copy of its body at all: one tile per lane with the bang-bang rule compiled in.  A lane
+// mask is a scalar register pair and a house has three, so with more tiles, or with the controller's own scalars, the masks fill
+// the scalar register file already and a second copy of the body spills more of them into vector lanes (several tiles) or costs a
+// wave per SIMD (controllers with several tiles): those keep the counter form alone, as it was.  Every group instantiation holds
+// both bodies (profiles/r13_resource_usage.txt).
+constexpr bool resident_stamps(int tiles, bool bb) { return bb && tiles == 1; }
+
+// STAMP: the loop in the time-stamp form; the caller passes it where `uni` has UNIFORM_LOCKOUT.
+template <int VEC, int TILES, int THREADS, bool BB, bool STAMP>
+__device__ __forceinline__ void rollout_resident_body(const StepArgs& a, const RolloutArgs& ro, const float2* __restrict__ rows, uint32_t uni) {
   const int e = blockIdx.x;
   const int64_t base = (int64_t)e * a.N;
-  const uint32_t uni = uniform_word(a);
   const bool coded = hvac_coded(a) != 0u, packed = thermal_packed(a) != 0u;
   const bool ext = !BB && a.action_source == MDR_ACTIONS_EXTERNAL;
   HouseIn hs[TILES][VEC];
@@ -127,18 +160,46 @@ __global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, Rollou
     for (int t = 0; t < TILES; ++t) resident_advance<VEC, BB, false>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], cur.x, cur.y);
     cur = nxt;
   }
-  for (int s = 1; s < ro.nsteps; ++s) {   // on => sso == 0 from here on
-    row += a.E;
-    const float2 nxt = *row;
-#pragma unroll
-    for (int t = 0; t < TILES; ++t) resident_advance<VEC, BB, true>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], cur.x, cur.y);
-    cur = nxt;
-  }
   uint64_t lock_m[TILES][VEC];
+  if (STAMP) {   // one lockout for every house: time stamps, on => sso == 0 from here on
+    const int L = __builtin_amdgcn_readfirstlane(a.lockout[0]);   // a scalar, also where the loader's copy of it sits in a vector register
+    const int Tend = ro.nsteps * a.dt;   // (< 2^31: mdr_api.hip's bound on the steps of a launch)
+    int Ts = a.dt;                       // step 1 starts here
 #pragma unroll
-  for (int t = 0; t < TILES; ++t) {   // (outside the branch below: a ballot is a wave-wide value)
+    for (int t = 0; t < TILES; ++t) {
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) lock_m[t][v] = house_lock_m(can_m[t][v], on_m[t][v], hs[t][v].sso, hs[t][v].lockout, a.dt);
+      for (int v = 0; v < VEC; ++v) hs[t][v].sso = house_stamp(lane_bit(on_m[t][v]), hs[t][v].sso, Ts, a.dt);   // hs[][].sso holds the stamp from here
+    }
+    while (Ts != Tend) {   // the time is the loop's counter
+      row += a.E;
+      const float2 nxt = *row;
+      const int Tn = Ts + a.dt;
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) resident_advance_stamp<VEC, BB>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], cur.x, cur.y, Tn, Ts - L);
+      cur = nxt;
+      Ts = Tn;
+    }
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        hs[t][v].sso = house_stamp_sso(hs[t][v].sso, Tend, a.dt);   // back into the counter, in front of the lock mask, which reads it
+        lock_m[t][v] = house_lock_m(can_m[t][v], on_m[t][v], hs[t][v].sso, L, a.dt);
+      }
+    }
+  } else {   // a streamed lockout column: the counter
+    for (int s = 1; s < ro.nsteps; ++s) {   // on => sso == 0 from here on
+      row += a.E;
+      const float2 nxt = *row;
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) resident_advance<VEC, BB, true>(a, ext, hs[t], on_m[t], can_m[t], cmd_m[t], cur.x, cur.y);
+      cur = nxt;
+    }
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {   // (outside the branch below: a ballot is a wave-wide value)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) lock_m[t][v] = house_lock_m(can_m[t][v], on_m[t][v], hs[t][v].sso, hs[t][v].lockout, a.dt);
+    }
   }
 #pragma unroll
   for (int t = 0; t < TILES; ++t) {
@@ -147,16 +208,24 @@ __global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, Rollou
   }
 }
 
-template <int GROUP, int VEC, bool BB>
-__global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, RolloutArgs ro, const float2* __restrict__ rows) {
+// The word of uniform columns is device-side, so the two forms of the loop are two copies of the body behind one wave-uniform branch
+// (like `coded` / `packed`), each with the registers it needs: without the bit the instruction stream is the counter form's.
+template <int VEC, int TILES, int THREADS, bool BB>
+__global__ __launch_bounds__(THREADS) void k_rollout_resident(StepArgs a, RolloutArgs ro, const float2* __restrict__ rows) {
   if (ro.nsteps <= 0) return;
+  const uint32_t uni = uniform_word(a);
+  if (resident_stamps(TILES, BB) && (uni & UNIFORM_LOCKOUT) != 0u) rollout_resident_body<VEC, TILES, THREADS, BB, true>(a, ro, rows, uni);
+  else rollout_resident_body<VEC, TILES, THREADS, BB, false>(a, ro, rows, uni);
+}
+
+template <int GROUP, int VEC, bool BB, bool STAMP>
+__device__ __forceinline__ void rollout_resident_group_body(const StepArgs& a, const RolloutArgs& ro, const float2* __restrict__ rows, uint32_t uni) {
   const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) / GROUP;
   const int lane = threadIdx.x % GROUP;
   const bool env_ok = gid < a.E;
   const int e = env_ok ? (int)gid : a.E - 1;
   const bool active = env_ok && lane * VEC < a.N;
   const int64_t i = (int64_t)e * a.N + lane * VEC;
-  const uint32_t uni = uniform_word(a);
   const bool coded = hvac_coded(a) != 0u, packed = thermal_packed(a) != 0u;
   const bool ext = !BB && a.action_source == MDR_ACTIONS_EXTERNAL;
   HouseIn hs[VEC];
@@ -181,15 +250,44 @@ __global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, Roll
     resident_advance<VEC, BB, false>(a, ext, hs, on_m, can_m, cmd_m, cur.x, cur.y);
     cur = nxt;
   }
-  for (int s = 1; s < ro.nsteps; ++s) {   // on => sso == 0 from here on
-    row += a.E;
-    const float2 nxt = *row;
-    resident_advance<VEC, BB, true>(a, ext, hs, on_m, can_m, cmd_m, cur.x, cur.y);
-    cur = nxt;
-  }
+  if (STAMP) {   // time stamps, as in k_rollout_resident
+    const int L = __builtin_amdgcn_readfirstlane(a.lockout[0]);
+    const int Tend = ro.nsteps * a.dt;
+    int Ts = a.dt;
 #pragma unroll
-  for (int v = 0; v < VEC; ++v) lock_m[v] = house_lock_m(can_m[v], on_m[v], hs[v].sso, hs[v].lockout, a.dt);
+    for (int v = 0; v < VEC; ++v) hs[v].sso = house_stamp(lane_bit(on_m[v]), hs[v].sso, Ts, a.dt);
+    while (Ts != Tend) {
+      row += a.E;
+      const float2 nxt = *row;
+      const int Tn = Ts + a.dt;
+      resident_advance_stamp<VEC, BB>(a, ext, hs, on_m, can_m, cmd_m, cur.x, cur.y, Tn, Ts - L);
+      cur = nxt;
+      Ts = Tn;
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      hs[v].sso = house_stamp_sso(hs[v].sso, Tend, a.dt);
+      lock_m[v] = house_lock_m(can_m[v], on_m[v], hs[v].sso, L, a.dt);
+    }
+  } else {
+    for (int s = 1; s < ro.nsteps; ++s) {   // on => sso == 0 from here on
+      row += a.E;
+      const float2 nxt = *row;
+      resident_advance<VEC, BB, true>(a, ext, hs, on_m, can_m, cmd_m, cur.x, cur.y);
+      cur = nxt;
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) lock_m[v] = house_lock_m(can_m[v], on_m[v], hs[v].sso, hs[v].lockout, a.dt);
+  }
   if (active) resident_store<VEC>(a, i, hs, on_m, lock_m);
+}
+
+template <int GROUP, int VEC, bool BB>
+__global__ __launch_bounds__(256) void k_rollout_resident_group(StepArgs a, RolloutArgs ro, const float2* __restrict__ rows) {
+  if (ro.nsteps <= 0) return;
+  const uint32_t uni = uniform_word(a);
+  if ((uni & UNIFORM_LOCKOUT) != 0u) rollout_resident_group_body<GROUP, VEC, BB, true>(a, ro, rows, uni);
+  else rollout_resident_group_body<GROUP, VEC, BB, false>(a, ro, rows, uni);
 }
 
 // The interior steps of mdr_env_rollout, r.nsteps of them, by the STEP plan: the grid and the lane mapping of the k_step_fused /
