@@ -427,6 +427,25 @@ int mdr_ppo_critic_grad(const mdr_mlp_t *critic, const float *state, int64_t ld_
                         const float *target, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
                         float *advantage, void *stream);
 
+/* The bf16x3 precision of the two calls above: the argument lists, the limits, the flat gradient, the workspace
+ * (mdr_mlp_grad_floats, mdr_mlp_grad_workspace_bytes: the same grid of 16-row tiles), the determinism and the return codes of
+ * mdr_ppo_actor_grad / mdr_ppo_critic_grad, with the five matrix products on v_mfma_f32_16x16x32_bf16.  The contract:
+ *   F1 (W1 x), F2 (W2 h1), B2 (W2^T dz2), dW2 = dz2^T h1 and dW1 = dz1^T x take every operand split a = ah + al, ah = bf16(a),
+ *   al = bf16(a - ah), round to nearest even, and every product as ah bh + al bh + ah bl, accumulated in fp32 (the al bl term is
+ *   dropped: a product of two operands that do not split exactly is off by up to 2^-15 |a| |b|, operands that are exact in bf16
+ *   or split exactly lose nothing);
+ *   everything else is fp32 as in the calls above: biases, ReLU, the logits and dW3 / db3, the head's loss and dlogits, relu'(z) =
+ *   [z > 0] on the call's own z, the bias gradients, rows past the minibatch adding exact zeros.
+ * The weights are read in place and split on every call: nothing is packed, the next call sees an optimiser step.  Every shape
+ * inside the limits (F <= 64, H1, H2 <= 128) is taken; -4: a shape outside them, num_out != 2 (actor) / 1 (critic).  On -1 and -4
+ * nothing was launched and nothing written. */
+int mdr_ppo_actor_grad_bf16x3(const mdr_mlp_t *actor, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                              const int64_t *action, const float *old_prob, const float *advantage, float clip_param,
+                              int32_t max_workgroups, void *workspace, float *grad, float *loss, float *ratio, void *stream);
+int mdr_ppo_critic_grad_bf16x3(const mdr_mlp_t *critic, const float *state, int64_t ld_state, const int64_t *index, int64_t nb_rows,
+                               const float *target, int32_t max_workgroups, void *workspace, float *grad, float *loss, float *value,
+                               float *advantage, void *stream);
+
 /* ---- MAPPO's update step (MAPPO.update, agents/mappo.py:60-119).  Its actor step is PPO's line for line (mappo.py:92-110 against
  * ppo.py:153-169): mdr_ppo_actor_grad serves it.  Its critic is Critic(num_state + nb_agents - 1) on torch.cat((state, others_actions))
  * (mappo.py:21, 87): an mdr_mlp_t with num_state = J = F + (nb_agents - 1) and num_out = 1, parameters in torch's own layout.

@@ -218,6 +218,7 @@ EXPORTS = (
     "mdr_tarmac_vec_floats", "mdr_tarmac_frag_words", "mdr_tarmac_actor_workspace_bytes", "mdr_tarmac_actor_sample",
     "mdr_env_tarmac_actor_sample",
     "mdr_mlp_grad_floats", "mdr_mlp_grad_workspace_bytes", "mdr_ppo_actor_grad", "mdr_ppo_critic_grad", "mdr_dqn_target", "mdr_dqn_grad",
+    "mdr_ppo_actor_grad_bf16x3", "mdr_ppo_critic_grad_bf16x3",
     "mdr_mappo_critic_grad_floats", "mdr_mappo_critic_workspace_bytes", "mdr_mappo_critic_grad",
     "mdr_mlp_wide_grad_floats", "mdr_mlp_wide_grad_workspace_bytes", "mdr_ppo_actor_grad_wide", "mdr_ppo_critic_grad_wide",
     "mdr_dqn_target_wide", "mdr_dqn_grad_wide",
@@ -343,6 +344,8 @@ def load():
         "mdr_mlp_grad_workspace_bytes": (i64, [C.POINTER(MdrMlp), i64, i32]),
         "mdr_ppo_actor_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp]),
         "mdr_ppo_critic_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "mdr_ppo_actor_grad_bf16x3": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp]),
+        "mdr_ppo_critic_grad_bf16x3": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
         "mdr_dqn_target": (C.c_int, [C.POINTER(MdrMlp), C.POINTER(MdrMlp), vp, i64, vp, i64, vp, C.c_float, i32, vp, vp, vp, vp]),
         "mdr_dqn_grad": (C.c_int, [C.POINTER(MdrMlp), vp, i64, vp, i64, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp]),
         "mdr_mappo_critic_grad_floats": (i64, [C.POINTER(MdrMlp), i32]),

@@ -7,7 +7,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ("mdr_kernels.hip", "mdr_resident.hip", "mdr_rollout_rows.hip", "mdr_multi.hip", "mdr_persist.hip", "mdr_mailbox.hip", "mdr_control.hip", "mdr_api.hip", "mdr_policy.hip", "mdr_tarmac.hip", "mdr_tarmac_mlp.hip", "mdr_tarmac_mlp_bf16.hip", "mdr_tarmac_grad.hip", "mdr_tarmac_gather.hip", "mdr_ppo_grad.hip", "mdr_tarmac_ppo_grad.hip", "mdr_optim.hip", "mdr_maddpg_grad.hip", "mdr_mlp_actor.hip", "mdr_mlp_actor_bf16.hip", "mdr_mlp_actor_observe.hip", "mdr_tarmac_critic_grad.hip", "mdr_tarmac_a2c.hip", "mdr_minibatch.hip")
+SOURCES = ("mdr_kernels.hip", "mdr_resident.hip", "mdr_rollout_rows.hip", "mdr_multi.hip", "mdr_persist.hip", "mdr_mailbox.hip", "mdr_control.hip", "mdr_api.hip", "mdr_policy.hip", "mdr_tarmac.hip", "mdr_tarmac_mlp.hip", "mdr_tarmac_mlp_bf16.hip", "mdr_tarmac_grad.hip", "mdr_tarmac_gather.hip", "mdr_ppo_grad.hip", "mdr_ppo_grad_bf16.hip", "mdr_tarmac_ppo_grad.hip", "mdr_optim.hip", "mdr_maddpg_grad.hip", "mdr_mlp_actor.hip", "mdr_mlp_actor_bf16.hip", "mdr_mlp_actor_observe.hip", "mdr_tarmac_critic_grad.hip", "mdr_tarmac_a2c.hip", "mdr_minibatch.hip")
 HEADERS = ("mdr_device.h", "mdr_kernels.h", "mdr_step_common.h", "mdr_mailbox.h", "mdr_draw.h", "mdr_bf16_split.h", "mdr_tarmac_mlp.h", "mdr_observe.h", "mdr_grad_reduce.h", "mdr_stream_mlp.h", os.path.join("..", "..", "include", "mdr.h"), os.path.join("..", "..", "include", "mdr_policy.h"))
 OUTPUT = os.path.join(CSRC, "libmdr_hip.so")
 

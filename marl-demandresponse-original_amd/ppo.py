@@ -7,6 +7,8 @@ kernel on the matrix cores in exact fp32 (plus a small reduction): ``critic_loss
 ``.grad`` of an ``ActorMLP`` / ``CriticMLP``, torch keeps the gradient clipping and the optimiser (``optimizer=FusedAdam``, optim.py: one launch for both).  ``PPOLearner`` is the loop.
 Nothing on the call path synchronises with the host.  Networks of 65..128 input features - observations with message columns -
 take the same kernels' wide instantiations with ``wide=True`` (mdr_ppo_actor_grad_wide, mdr_ppo_critic_grad_wide).
+``precision="bf16x3"`` (opt-in, narrow networks only) takes the same chain with its five matrix products on the bf16 matrix cores, every
+operand split into a bf16 head and tail (mdr_ppo_actor_grad_bf16x3, mdr_ppo_critic_grad_bf16x3; profiles/ppo_update_bf16_README.md).
 """
 from __future__ import annotations
 
@@ -29,51 +31,76 @@ AUTO_MIN_ROWS = 1
 MAX_STATE_WIDE = 128
 AUTO_MIN_ROWS_WIDE = 1
 _WIDE = L.WIDE
+# precision="bf16x3": the entry points with the five matrix products as three bf16 products each (csrc/mdr_ppo_grad_bf16.hip); the
+# argument lists, the limits and the size functions of the fp32 ones
+PRECISIONS = ("fp32", "bf16x3")
+_BF16X3 = {"mdr_ppo_actor_grad": "mdr_ppo_actor_grad_bf16x3", "mdr_ppo_critic_grad": "mdr_ppo_critic_grad_bf16x3"}
 
 
-def refusal(net, num_out: Optional[int] = None, max_state: int = MAX_STATE, wide: bool = False) -> Optional[str]:
+def check_precision(precision: str, wide: bool = False, what: str = "precision") -> str:
+    """``precision`` if it is one of ``PRECISIONS`` and the entry points asked for have it (ValueError otherwise)."""
+    if precision not in PRECISIONS:
+        raise ValueError("%s must be 'fp32' or 'bf16x3'" % what)
+    if precision == "bf16x3" and wide:
+        raise ValueError("precision='bf16x3' covers the narrow entry points only (F <= %d): not with wide=True" % MAX_STATE)
+    return precision
+
+
+def _entry(lib, name: str, wide: bool, precision: str):
+    if precision == "bf16x3":
+        name = _BF16X3[name]
+        return getattr(lib, name), name
+    return L.fn(lib, name, wide)
+
+
+def refusal(net, num_out: Optional[int] = None, max_state: int = MAX_STATE, wide: bool = False, precision: str = "fp32") -> Optional[str]:
     """Why the kernels do not take ``net`` (None: they do).  ``max_state``: the input width of the head asked for.  ``wide``: the
-    wide entry points' limits - ``MAX_STATE_WIDE`` input features and the LDS fit, the message saying which of the two failed."""
+    wide entry points' limits - ``MAX_STATE_WIDE`` input features and the LDS fit, the message saying which of the two failed.
+    ``precision="bf16x3"``: the narrow limits, every shape inside them (ValueError with ``wide=True`` or an unknown precision)."""
+    check_precision(precision, wide)
     return L.mlp_refusal(net, (1, 2) if num_out is None else (num_out,), MAX_STATE_WIDE if wide else max_state, MAX_HIDDEN, wide)
 
 
 _refusal = refusal      # (its name before mappo and dqn called it)
 
 
-def supported(net, wide: bool = False) -> bool:
+def supported(net, wide: bool = False, precision: str = "fp32") -> bool:
     """Do the gradient kernels take this network?  An ``ActorMLP`` / ``CriticMLP`` of two hidden layers with F <= 64 input features,
     hidden layers of at most 128 units and 2 (actor) or 1 (critic) outputs, float32 on the GPU.  ``wide=True``: the wide entry
-    points, F <= 128 where the LDS layout fits (hidden 100-100: every F; 128-128: F <= 100)."""
-    return refusal(net, wide=wide) is None
+    points, F <= 128 where the LDS layout fits (hidden 100-100: every F; 128-128: F <= 100).  ``precision="bf16x3"``: the narrow
+    limits again - those kernels refuse no shape inside them."""
+    return refusal(net, wide=wide, precision=precision) is None
 
 
 def _actor_launch(desc, state, ld, action, old_prob, index, B, advantage, workspace, flat, loss, ratio, stream, clip_param, max_workgroups=0,
-                  wide=False) -> None:
-    """mdr_ppo_actor_grad[_wide] on checked tensors, under the device of ``state``: the eager call and the captured one."""
+                  wide=False, precision="fp32") -> None:
+    """mdr_ppo_actor_grad[_wide | _bf16x3] on checked tensors, under the device of ``state``: the eager call and the captured one."""
     lib = nat.load()
-    call, name = L.fn(lib, "mdr_ppo_actor_grad", wide)
+    call, name = _entry(lib, "mdr_ppo_actor_grad", wide, precision)
     nat.check(lib, None, call(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, L.ptr(action), L.ptr(old_prob), L.ptr(advantage),
                               C.c_float(clip_param), max_workgroups, L.ptr(workspace), L.ptr(flat), L.ptr(loss), L.ptr(ratio), stream), name)
 
 
-def _critic_launch(desc, state, ld, action, target, index, B, workspace, flat, loss, value, adv, stream, max_workgroups=0, wide=False) -> None:
-    """mdr_ppo_critic_grad[_wide] on checked tensors; ``action`` is not read (mappo's joint launch, with the same list, reads it)."""
+def _critic_launch(desc, state, ld, action, target, index, B, workspace, flat, loss, value, adv, stream, max_workgroups=0, wide=False,
+                   precision="fp32") -> None:
+    """mdr_ppo_critic_grad[_wide | _bf16x3] on checked tensors; ``action`` is not read (mappo's joint launch, with the same list, reads it)."""
     lib = nat.load()
-    call, name = L.fn(lib, "mdr_ppo_critic_grad", wide)
+    call, name = _entry(lib, "mdr_ppo_critic_grad", wide, precision)
     nat.check(lib, None, call(C.byref(desc), L.ptr(state), ld, L.ptr(index), B, L.ptr(target), max_workgroups, L.ptr(workspace), L.ptr(flat),
                               L.ptr(loss), L.ptr(value), L.ptr(adv), stream), name)
 
 
 def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_prob: torch.Tensor, advantage: torch.Tensor,
                         clip_param: float = 0.2, index: Optional[torch.Tensor] = None, want_ratio: bool = False, max_workgroups: int = 0,
-                        wide: bool = False):
+                        wide: bool = False, precision: str = "fp32"):
     """The clipped surrogate of agents/ppo.py:153-169 and ``backward()`` in one kernel: fills ``p.grad`` of the six parameters of
     ``actor`` (allocated where None, overwritten otherwise) and returns the loss (0-dim device tensor) [and the ratios, float32 [B]].
     ``state`` float32 [M, F] (any row stride >= F), ``action`` int64 [M], ``old_prob`` float32 [M]: the transition buffer, read in
     place through ``index`` (int64 [B] on the device; None: every row in order, B = M); ``advantage`` float32 [B] in minibatch order.
-    ``wide=True``: up to 128 input features (``supported(actor, wide=True)``)."""
+    ``wide=True``: up to 128 input features (``supported(actor, wide=True)``).  ``precision="bf16x3"``: the matrix products as three
+    bf16 products of split operands each, fp32 accumulation, everything else as it is (include/mdr_policy.h has the contract)."""
     what = "actor_loss_backward"
-    why = refusal(actor, 2, wide=wide)
+    why = refusal(actor, 2, wide=wide, precision=precision)
     if why:
         raise ValueError("%s: %s" % (what, why))
     fc = L.fc_layers(actor)
@@ -90,18 +117,19 @@ def actor_loss_backward(actor, state: torch.Tensor, action: torch.Tensor, old_pr
     ratio = torch.empty(B, dtype=torch.float32, device=dev) if want_ratio else None
     with torch.cuda.device(dev):
         _actor_launch(desc, state, ld, action, old_prob, index, B, advantage, L.workspace(dev, nbytes), flat, loss, ratio, L.stream(dev),
-                      clip_param, max_workgroups, wide)
+                      clip_param, max_workgroups, wide, precision)
     L.publish(L.mlp_params(fc), flat, L.KEEP)
     return (loss, ratio) if want_ratio else loss
 
 
 def critic_loss_backward(critic, state: torch.Tensor, target: torch.Tensor, index: Optional[torch.Tensor] = None,
-                         max_workgroups: int = 0, wide: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         max_workgroups: int = 0, wide: bool = False, precision: str = "fp32") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """F.mse_loss(Gt, V) of agents/ppo.py:148-150, 180 and ``backward()`` in one kernel: fills ``p.grad`` of ``critic`` and returns
     (loss 0-dim, value float32 [B], advantage float32 [B] = target - value, the detached delta the actor's loss takes).
-    ``target`` float32 [M] is read through ``index`` like ``state``.  ``wide=True``: up to 128 input features."""
+    ``target`` float32 [M] is read through ``index`` like ``state``.  ``wide=True``: up to 128 input features.  ``precision``: as
+    ``actor_loss_backward``."""
     what = "critic_loss_backward"
-    why = refusal(critic, 1, wide=wide)
+    why = refusal(critic, 1, wide=wide, precision=precision)
     if why:
         raise ValueError("%s: %s" % (what, why))
     fc = L.fc_layers(critic)
@@ -114,7 +142,8 @@ def critic_loss_backward(critic, state: torch.Tensor, target: torch.Tensor, inde
     value = torch.empty(B, dtype=torch.float32, device=dev)
     adv = torch.empty(B, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _critic_launch(desc, state, ld, None, target, index, B, L.workspace(dev, nbytes), flat, loss, value, adv, L.stream(dev), max_workgroups, wide)
+        _critic_launch(desc, state, ld, None, target, index, B, L.workspace(dev, nbytes), flat, loss, value, adv, L.stream(dev), max_workgroups, wide,
+                       precision)
     L.publish(L.mlp_params(fc), flat, L.KEEP)
     return loss, value, adv
 
@@ -128,16 +157,22 @@ class PPOLearner:
     ``optimizer(params, lr)`` for each network; an optimiser that is a ``mdr_amd.optim.FusedAdam`` clips and steps in one launch
     (``.grad`` then keeps the unclipped gradient), any other one is stepped after ``clip_grad_norm_``.  ``wide=True``: the wide
     entry points, so networks of up to 128 input features (both message flags on: 121) take the kernels, eager or ``graph=True``;
-    ``"auto"`` then takes them from ``AUTO_MIN_ROWS_WIDE`` minibatch rows on."""
+    ``"auto"`` then takes them from ``AUTO_MIN_ROWS_WIDE`` minibatch rows on.  ``precision="bf16x3"``: every kernel call of this
+    learner in that precision, eager or ``graph=True``; opt-in only (``"auto"`` never picks it by itself), it needs the kernels:
+    ValueError for a network they refuse, with ``backend="torch"`` and with ``wide=True``."""
 
     def __init__(self, actor, critic, lr_actor: float, lr_critic: float, clip_param: float = 0.2, max_grad_norm: float = 0.5,
                  ppo_update_time: int = 10, batch_size: int = 256, backend: str = "auto", optimizer=torch.optim.Adam,
-                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False):
+                 sampler: Optional[str] = None, graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False,
+                 precision: str = "fp32"):
         L.check_backend(backend)
         self.wide = bool(wide)
+        self.precision = check_precision(precision, self.wide, "%s: precision" % type(self).__name__)
         sampler = L.check_sampler(sampler, graph)
         if backend == "hip":
             L.require(refusal(actor, 2, wide=self.wide) or refusal(critic, 1, wide=self.wide), "PPOLearner")
+        if self.precision == "bf16x3":
+            self._require_bf16x3(actor, critic, backend)
         self.actor, self.critic = actor, critic
         self.clip_param, self.max_grad_norm = float(clip_param), float(max_grad_norm)
         self.ppo_update_time, self.batch_size = int(ppo_update_time), int(batch_size)
@@ -156,16 +191,26 @@ class PPOLearner:
             if why:
                 raise ValueError("%s(graph=True): %s" % (type(self).__name__, why))
 
+    def _require_bf16x3(self, actor, critic, backend: str) -> None:
+        """``precision="bf16x3"`` exists in the kernels alone, for the networks they take."""
+        if backend == "torch":
+            raise ValueError("%s(precision='bf16x3'): the precision of the HIP kernels, not of backend='torch'" % type(self).__name__)
+        why = refusal(actor, 2, precision="bf16x3") or refusal(critic, 1, precision="bf16x3")
+        if why:
+            raise ValueError("%s(precision='bf16x3'): %s" % (type(self).__name__, why))
+
     @classmethod
     def from_config(cls, ppo_prop: dict, actor, critic, backend: str = "auto", optimizer=torch.optim.Adam, sampler: Optional[str] = None,
-                    graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False) -> "PPOLearner":
+                    graph: bool = False, graph_max_minibatches: int = 1024, wide: bool = False, precision: str = "fp32") -> "PPOLearner":
         """From the reference's ``config_dict["PPO_prop"]`` (agents/ppo.py:34-40)."""
         return cls(actor, critic, ppo_prop["lr_actor"], ppo_prop["lr_critic"], clip_param=ppo_prop["clip_param"],
                    max_grad_norm=ppo_prop["max_grad_norm"], ppo_update_time=ppo_prop["ppo_update_time"],
                    batch_size=ppo_prop["batch_size"], backend=backend, optimizer=optimizer, sampler=sampler, graph=graph,
-                   graph_max_minibatches=graph_max_minibatches, wide=wide)
+                   graph_max_minibatches=graph_max_minibatches, wide=wide, precision=precision)
 
     def uses_kernels(self, nb_rows: int) -> bool:
+        if self.precision == "bf16x3":      # asked for by name and checked at construction: never autograd at another precision
+            return True
         if self.backend == "auto":
             return (refusal(self.actor, 2, wide=self.wide) is None and refusal(self.critic, 1, wide=self.wide) is None
                     and nb_rows >= (AUTO_MIN_ROWS_WIDE if self.wide else AUTO_MIN_ROWS))
@@ -177,16 +222,16 @@ class PPOLearner:
 
     def critic_backward(self, state, action, target, index):
         """The critic's kernel call of one minibatch -> (loss, value, advantage); MAPPOLearner's takes the joint input."""
-        return critic_loss_backward(self.critic, state, target, index=index, wide=self.wide)
+        return critic_loss_backward(self.critic, state, target, index=index, wide=self.wide, precision=self.precision)
 
     def _critic_kernel(self):
         """(sizes, launch) of the call ``critic_backward`` makes, this learner's fixed arguments bound: what a captured graph runs on
         its static buffers (graph_update.PPOUpdateGraph).  MAPPOLearner's is the joint one, with the same argument lists."""
-        return partial(L.mlp_sizes, wide=self.wide), partial(_critic_launch, wide=self.wide)
+        return partial(L.mlp_sizes, wide=self.wide), partial(_critic_launch, wide=self.wide, precision=self.precision)
 
     def _actor_kernel(self):
         """The same of the actor's call."""
-        return partial(L.mlp_sizes, wide=self.wide), partial(_actor_launch, clip_param=self.clip_param, wide=self.wide)
+        return partial(L.mlp_sizes, wide=self.wide), partial(_actor_launch, clip_param=self.clip_param, wide=self.wide, precision=self.precision)
 
     def _capture(self, shape):
         """Capture the graph of one epoch over a batch of ``shape`` = (T, A, F) without replaying it; parameters, moments and every
@@ -206,7 +251,8 @@ class PPOLearner:
         optimiser steps.  The arguments are the whole flattened buffers; ``index`` picks the minibatch.  -> (actor loss, critic loss)."""
         if self.uses_kernels(int(index.shape[0])):
             value_loss, _, advantage = self.critic_backward(state, action, target, index)
-            action_loss = actor_loss_backward(self.actor, state, action, old_prob, advantage, self.clip_param, index=index, wide=self.wide)
+            action_loss = actor_loss_backward(self.actor, state, action, old_prob, advantage, self.clip_param, index=index, wide=self.wide,
+                                              precision=self.precision)
         else:
             Gt_index = target[index].view(-1, 1)
             V = self.critic(self.critic_input(state, action, index))
