@@ -286,22 +286,44 @@ struct HouseLeanM {
   uint64_t on, can;
 };
 
+// The step in two parts, so that a loop can stand between them: house_*_front is the HVAC's integer state machine, which reads no
+// table value - compares, mask logic on the scalar unit, selects - and house_thermal_back the thermal map, which reads the step's
+// {od_old, solar}.  The resident loops wait for the row of a step between the two (mdr_resident.hip).  house_advance_lean_m and
+// house_advance_stamp_m are the one behind the other: the same f32 expressions in the same order, the same bits.
+struct HouseFrontM {
+  int sso;
+  uint64_t on, can;
+};
+
+struct HouseTemps {
+  float Ta, Tm;
+};
+
 template <bool LEAN>
-__device__ __forceinline__ HouseLeanM house_advance_lean_m(const HouseIn& h, uint64_t on_m, uint64_t cmd_m, float od_old, float solar, int dt) {
+__device__ __forceinline__ HouseFrontM house_lean_front(const HouseIn& h, uint64_t on_m, uint64_t cmd_m, int dt) {
   const int sso1 = LEAN ? h.sso + dt : (lane_bit(on_m) ? h.sso : h.sso + dt);                  // env 475-476
   const uint64_t can_m = on_m | __builtin_amdgcn_ballot_w64(sso1 >= h.lockout);                // env 478-481
   const uint64_t on2_m = can_m & cmd_m;                                                        // env 483-486
   const int sso2 = lane_bit(LEAN ? (on_m | on2_m) : on2_m) ? 0 : sso1;                         // env 487-488
+  return HouseFrontM{sso2, on2_m, can_m};
+}
+
+// `on2_m`: the HVAC's on bit as this step's front left it
+__device__ __forceinline__ HouseTemps house_thermal_back(const HouseIn& h, uint64_t on2_m, float od_old, float solar) {
   const float Qa = (lane_bit(on2_m) ? h.Q_hvac : 0.0f) + solar;  // env 690-699
   const float Tinf = fmaf(Qa, h.inv_Ua, od_old);     // uses the PREVIOUS step's outdoor temperature (env 1034)
   const float dm = h.Tm - h.Ta;
-  HouseLeanM o;
+  HouseTemps o;
   o.Ta = h.Ta + fmaf(h.k01, dm, h.s0 * (h.Ta - Tinf));
   o.Tm = h.Tm + fmaf(-h.k10, dm, h.s1 * (h.Tm - Tinf));
-  o.sso = sso2;
-  o.on = on2_m;
-  o.can = can_m;
   return o;
+}
+
+template <bool LEAN>
+__device__ __forceinline__ HouseLeanM house_advance_lean_m(const HouseIn& h, uint64_t on_m, uint64_t cmd_m, float od_old, float solar, int dt) {
+  const HouseFrontM f = house_lean_front<LEAN>(h, on_m, cmd_m, dt);
+  const HouseTemps t = house_thermal_back(h, f.on, od_old, solar);
+  return HouseLeanM{t.Ta, t.Tm, f.sso, f.on, f.can};
 }
 
 // The lean step with a TIME STAMP in place of the counter, for a lockout that is one value L for every house (UNIFORM_LOCKOUT).
@@ -314,21 +336,18 @@ __device__ __forceinline__ HouseLeanM house_advance_lean_m(const HouseIn& h, uin
 // - no add, no OR for the select's mask, no lockout register.  Integers throughout: exact wherever the counter form does not overflow
 // (the caller's bound dt x (steps of a launch) < 2^31 stays; z >= -(the sso the first step left) and Ts - L >= -L cannot).
 // house_stamp forms z behind the launch's general first step, house_stamp_sso the counter behind its last, in front of house_lock_m.
-__device__ __forceinline__ HouseLeanM house_advance_stamp_m(const HouseIn& h, int z, uint64_t on_m, uint64_t cmd_m, float od_old, float solar, int Tn,
-                                                            int Ts_minus_L) {
+__device__ __forceinline__ HouseFrontM house_stamp_front(int z, uint64_t on_m, uint64_t cmd_m, int Tn, int Ts_minus_L) {
   const uint64_t can_m = on_m | __builtin_amdgcn_ballot_w64(z <= Ts_minus_L);                  // env 475-481
   const uint64_t on2_m = can_m & cmd_m;                                                        // env 483-486
   const int z2 = lane_bit(on2_m) ? Tn : z;                                                     // env 487-488
-  const float Qa = (lane_bit(on2_m) ? h.Q_hvac : 0.0f) + solar;  // env 690-699
-  const float Tinf = fmaf(Qa, h.inv_Ua, od_old);     // uses the PREVIOUS step's outdoor temperature (env 1034)
-  const float dm = h.Tm - h.Ta;
-  HouseLeanM o;
-  o.Ta = h.Ta + fmaf(h.k01, dm, h.s0 * (h.Ta - Tinf));
-  o.Tm = h.Tm + fmaf(-h.k10, dm, h.s1 * (h.Tm - Tinf));
-  o.sso = z2;
-  o.on = on2_m;
-  o.can = can_m;
-  return o;
+  return HouseFrontM{z2, on2_m, can_m};
+}
+
+__device__ __forceinline__ HouseLeanM house_advance_stamp_m(const HouseIn& h, int z, uint64_t on_m, uint64_t cmd_m, float od_old, float solar, int Tn,
+                                                            int Ts_minus_L) {
+  const HouseFrontM f = house_stamp_front(z, on_m, cmd_m, Tn, Ts_minus_L);
+  const HouseTemps t = house_thermal_back(h, f.on, od_old, solar);
+  return HouseLeanM{t.Ta, t.Tm, f.sso, f.on, f.can};
 }
 
 // Into the stamp at time T, the end of a step that left (on, sso) with on => sso == 0, and back: sso = 0 for an `on` house (z = T).

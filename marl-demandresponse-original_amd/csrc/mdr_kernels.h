@@ -279,6 +279,12 @@ hipError_t launch_step_end_begin_split(const StepArgs& finish, const StepArgs& b
 bool rollout_fused_supported(const StepPlan& p);
 hipError_t launch_rollout_accumulate(const StepArgs& a, const RolloutArgs& ro, hipStream_t s);   // after ONE single step
 hipError_t launch_rollout_fused(const StepArgs& a, const RolloutArgs& r, const StepPlan& p, hipStream_t s);
+// Where the rollout rows lie, as the resident kernels take it: row r of env e at rows[e * env + r * step].  Always {1, E}; two 32-bit
+// kernel arguments because the stride formed from a.E inside the kernel costs k_rollout_resident<4,1,256,true> a scalar register,
+// and the allocator then copies a row pair right behind its load (mdr_resident.hip, launch_rollout_resident).
+struct RowStrides {
+  uint32_t env, step;   // in entries (float2) of the rollout rows; the kernels address the rows by 32-bit byte offsets
+};
 // k_rollout_resident / k_rollout_resident_group: r.nsteps interior steps of mdr_env_rollout in one launch, by the STEP plan (STEP_FUSED /
 // STEP_GROUP); of `r` only nsteps is read.  a.thermal_desc == nullptr: the five thermal columns are streamed.  The steps read
 // `rows`, [r.nsteps + 1][a.E] {od of step r, solar of step r} (launch_rollout_rows; the last row is only ever loaded, its value
